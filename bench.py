@@ -23,15 +23,25 @@ steps.  The documented BASELINE configs[4] line is
     python bench.py --gpus 8 --workload tgp_airline_tanh5x6 --steps 20 --warmup 3     (N = 2 M rows, 250 k per GPU, weak)
 `--capture-allreduce` records the collective inside the HIP graph instead of between two graphs.
 
-Timing: after W warm-up steps the K steps are timed `--repeats` times (default 5), each repeat bracketed by a barrier +
-synchronize and reduced with MAX over ranks; the line reports the MEDIAN repeat (`ms_per_step`, `value`) and the
-spread (`ms_per_step_min`, `ms_per_step_max`).
+Timing: after W warm-up steps the K steps are timed once, bracketed by a barrier + synchronize and reduced with MAX over
+ranks: `ms_per_step` = that time / K, `value` = steps per second.  `--repeats R` times R windows of K steps and reports
+the MEDIAN window (`ms_per_step`, `value`) and the spread (`ms_per_step_min`, `ms_per_step_max`).
 
-Extra objects on the JSON line (rank 0):
+`--full` adds what the headline figure does not need (a plain run sets up, warms up, times the K steps and prints):
+  repeats       default 5 instead of 1, after one untimed window of K steps; a short run is repeated until >= 50 ms
+                have been timed (with --repeats R too).
+  config.expected  the predicted ms/step of this configuration beside the measured one (see EXPECT below).
   roofline      dominant kernel = the fused row kernel k_rows; achieved = algorithmic FLOP per launch
                  / its average duration measured with HIP events on the launch stream.
   cpu_baseline  the oracle (CPU restatement of the reference's op sequence, eager PyTorch float64 + torch Adam)
                 timed on this host's cores on a bounded number of steps of the same workload (N=1 only).
+
+`--dump-outputs DIR` (rank 0, after the timed steps): what the last timed step handed its caller, as DIR/<name>.npy in
+float64 -- elbo_ell_kl (that step's ELBO, ELL, KL), grad_<parameter> (its gradients) and param_<parameter> (the
+parameters after its Adam update).  The inputs are seeded: the same arguments give the same inputs and, in a plain run,
+the same number of steps before the dump (min(W, 10) eager steps before the capture, W warm-up steps, then R x K timed
+ones); --full may add repeats by the clock.  Above 64 MB in all, every array is replaced by a fixed, seeded sample of
+its entries.
 """
 import argparse
 import json
@@ -258,6 +268,40 @@ def cpu_baseline(prob, budget_s=15.0, max_steps=400, mlp=None):
                       % (", ".join("%.1f" % x for x in wins), n_tot, ns, N, ", rate scaled by rows" if ns < N else "", best, cal, per, t_tot)}
 
 
+OUT_NAMES = {"Z": "Z", "raw_ls": "raw_lengthscale", "raw_os": "raw_outputscale", "m": "m", "Lam": "Lam",
+             "lvn": "log_var_noise", "theta": "theta", "nn": "nn_weights"}
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def step_outputs(eng):
+    """What the engine hands its caller after a step: (ELBO, ELL, KL) of that step, the gradient of every parameter and the
+    parameters after the Adam update -- as float64 numpy arrays."""
+    fp = eng.fp
+    out = {"elbo_ell_kl": fp.out[:3]}
+    for k in fp.offsets:
+        out["grad_" + OUT_NAMES[k]] = fp.gview(k)
+        out["param_" + OUT_NAMES[k]] = fp.view(k)
+    return {k: v.detach().to("cpu", torch.float64).numpy() for k, v in out.items()}
+
+
+def write_outputs(d, arrays, cap=DUMP_BYTES, seed=0):
+    """DIR/<name>.npy, float64.  When the arrays hold more than `cap` bytes in all, the small ones are kept whole and each
+    large one is replaced by the same seeded sample of its flattened entries every time (sorted positions): smallest first,
+    every array may take an equal share of what the earlier ones left."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    left = (cap - 4096 * len(arrays)) // 8               # doubles (room kept for the .npy headers)
+    names = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, name in enumerate(names):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float64)
+        k = max(1, left // (len(names) - i))
+        if a.size > k:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))]
+        left -= a.size
+        np.save(os.path.join(d, name + ".npy"), a)
+    log("bench.py: wrote %d arrays to %s" % (len(arrays), d))
+
+
 def launch_ranks(n):
     """Parent of a multi-GPU run: `python -m torch.distributed.run` as a child process (one rank per GPU, rendezvous on
     127.0.0.1 at a free port), stdout / stderr inherited.  Returns the child's exit code."""
@@ -285,7 +329,12 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--repeats", type=int, default=5, help="timed repeats of the K steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed repeats of the K steps; the median is reported "
+                    "(default 1; with --full 5, and a short run is repeated until >= 50 ms have been timed)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: repeats, the "
+                    "expected line, the row kernel's roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last step "
+                    "computed (ELBO / ELL / KL, gradients, updated parameters) as DIR/<name>.npy, float64, <= 64 MB in all")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="default: strong for the Power / Boston workloads (north_star: the same problem on 1/2/4/8 GPUs), "
                          "weak for the airline workloads (a rank's 250 k rows are 1/8 of configs[4])")
@@ -309,6 +358,8 @@ def main():
                     "--pmc pass, keyed by the source hash of the library it was measured on (default: "
                     "profiles/rows_traffic.json); a summary of other sources is rejected and roofline.traffic is null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.scaling is None:
         args.scaling = "weak" if args.workload.startswith("tgp_airline") else "strong"
 
@@ -490,20 +541,21 @@ def run_bench(args, world, rank, dev, backend):
             for _ in range(k):
                 run()
     run_steps(args.warmup)
-    # A short run (the driver's --steps 20 at 0.11 ms is 2 ms of GPU work) is repeated until >= 50 ms have been timed in
-    # total: `steps` stays as given, the median repeat is still what is reported, `repeats` says how many there were.
-    barrier()
-    t0 = time.perf_counter()
-    run_steps(args.steps)
-    barrier()
-    probe = time.perf_counter() - t0
-    nrep = max(args.repeats, 1)
-    if probe * nrep < 0.05:
-        nrep = min(int(0.05 / max(probe, 1e-6)) + 1, 2000)
-        if world > 1:                              # the same count on every rank
-            t = torch.tensor([float(nrep)], dtype=torch.float64, device=dev)
-            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            nrep = int(t[0])
+    nrep = max(args.repeats if args.repeats is not None else (5 if args.full else 1), 1)
+    if args.full:
+        # A short run (the driver's --steps 20 at 0.11 ms is 2 ms of GPU work) is repeated until >= 50 ms have been timed in
+        # total: `steps` stays as given, the median repeat is still what is reported, `repeats` says how many there were.
+        barrier()
+        t0 = time.perf_counter()
+        run_steps(args.steps)
+        barrier()
+        probe = time.perf_counter() - t0
+        if probe * nrep < 0.05:
+            nrep = min(int(0.05 / max(probe, 1e-6)) + 1, 2000)
+            if world > 1:                              # the same count on every rank
+                t = torch.tensor([float(nrep)], dtype=torch.float64, device=dev)
+                torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+                nrep = int(t[0])
     dts = []
     for _ in range(nrep):
         barrier()
@@ -518,6 +570,8 @@ def run_bench(args, world, rank, dev, backend):
         dts.append(dt)
     dts.sort()
     dt = dts[len(dts) // 2]                       # median repeat: the reported K steps
+    if args.dump_outputs and rank == 0:           # before anything below launches on the engine's buffers
+        write_outputs(args.dump_outputs, step_outputs(eng))
     eng.check_status()
     elbo, ell, kl = eng.scalars()
     if not (elbo == elbo):
@@ -525,40 +579,6 @@ def run_bench(args, world, rank, dev, backend):
 
     result = None
     if rank == 0:
-        # ---- roofline of the dominant kernel: HIP events around the row-kernel launch, same stream -----------------
-        eng.elbo(1)
-        n_ev = min(max(args.steps // 4, 50), 500) if w["M"] <= 128 else 5
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
-        torch.cuda.synchronize()
-        for a, b in evs:
-            a.record()
-            eng.elbo(2)
-            b.record()
-        torch.cuda.synchronize()
-        ks = sorted(a.elapsed_time(b) for a, b in evs)
-        k_ms = sum(ks) / len(ks)
-        flop = rows_kernel_flops(dict(w, N=int(Xr.shape[0])))      # this rank's rows
-        big = w["M"] > 128
-        kname = ("rows phase of the general-M path: per 16k-row chunk K_NM tile kernel + 6 k_gemm launches (4 triangular, "
-                 "SYRK, statistics) + flow quadrature" if big else
-                 "k_rows (fused K_NM + 4 triangular GEMMs + flow quadrature + SYRK)")
-        achieved = flop / (k_ms * 1e-3) / 1e12
-        # HBM bytes per launch of the dominant kernel: from a rocprofv3 --pmc pass (separate FETCH_SIZE / WRITE_SIZE passes,
-        # tools/probes/profile_round.sh) of THE SAME SOURCES -- the summary carries the source hash of the library it was
-        # measured on and is rejected when the library loaded now was built from anything else; never a bare constant
-        traffic = None
-        tj = args.traffic_json or os.path.join(ROOT, "profiles", "rows_traffic.json")
-        if os.path.exists(tj):
-            try:
-                from tgp.pytorch_amd import lib as _lib
-                rec = json.load(open(tj))
-                if rec.get("source_hash") == _lib.load().tgp_source_hash().decode():
-                    traffic = rec.get("bytes_per_launch", {}).get(args.workload)
-                else:
-                    log("note: %s was measured on sources %s, this library is %s: roofline.traffic = null"
-                        % (tj, rec.get("source_hash"), _lib.load().tgp_source_hash().decode()))
-            except Exception:
-                traffic = None
         units = (world if args.scaling == "weak" else 1) * (1 + len(extra))
         pg = {"world_size": torch.distributed.get_world_size() if world > 1 else 1,
               "backend": torch.distributed.get_backend() if world > 1 else None,
@@ -572,31 +592,15 @@ def run_bench(args, world, rank, dev, backend):
             "metric": metric_name(args.workload, w, n_global),
             "value": units * args.steps / dt, "unit": "ELBO-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "repeats": len(dts), "ms_per_step_min": 1e3 * dts[0] / args.steps, "ms_per_step_max": 1e3 * dts[-1] / args.steps,
             "config": {"workload": args.workload, "rows_per_gpu": int(Xr.shape[0]), "D": w["D"], "M": w["M"], "S": w["S"],
                        "flow": w["flow"], "global_rows_per_step": n_global, "parallelism": "row-shard x%d" % world,
                        "launch": "eager" if args.no_graph else ("hipgraph, %s steps per graph launch" % ("%d / %d" % (eng.unroll_long, eng.unroll) if getattr(eng, "gL", None) is not None else "%d" % eng.unroll) if many else "hipgraph"), "final_elbo": elbo, "process_group": pg,
-                       "replicas": 1 + len(extra),
-                       "expected": expected_line(args.workload, w, world, args.scaling, eng.fp.n + eng.fp.extra,
-                                                 measured_ms_1gpu=(1e3 * dt / args.steps) if world == 1 else None)},
-            "roofline": {"bound": "mfma", "kernel": kname,
-                         "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic,
-                         "kernel_ms": k_ms, "kernel_ms_min": ks[0], "flop_per_launch": flop},
+                       "replicas": 1 + len(extra)},
         }
-        exp = result["config"]["expected"]
-        if exp is not None:
-            # the prediction beside the measurement: > 1 = faster than predicted.  For one rank the basis IS this run's own step
-            # (ratio 1 by construction on the general-M workloads); the multi-rank entries are what a SCALE record falsifies.
-            exp["measured_value"] = result["value"]
-            exp["measured_over_expected"] = result["value"] / exp["value"]
-            log("expected %.1f %s (%.4f ms/step), measured %.1f (%.4f ms/step): measured / expected = %.3f%s"
-                % (exp["value"], result["unit"], exp["ms_per_step"], result["value"], result["ms_per_step"],
-                   exp["measured_over_expected"], "" if world == 1 else "  [the expectation's collective term is an ESTIMATE, "
-                   "unmeasured on hardware: `bench.py --gpus %d --allreduce-only` measures it]" % world))
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(prob, args.cpu_seconds, mlp=mlp)
+        if args.full:
+            full_extras(args, w, world, eng, Xr, prob, mlp, result)
     if world > 1:
         torch.distributed.barrier()
         torch.cuda.synchronize()
@@ -604,6 +608,61 @@ def run_bench(args, world, rank, dev, backend):
         torch.distributed.destroy_process_group()
     if rank == 0:
         print(json.dumps(result), flush=True)
+
+
+def full_extras(args, w, world, eng, Xr, prob, mlp, result):
+    """`--full`, rank 0, after the timed steps: config.expected, the row kernel's roofline and the CPU baseline."""
+    # ---- roofline of the dominant kernel: HIP events around the row-kernel launch, same stream -----------------
+    eng.elbo(1)
+    n_ev = min(max(args.steps // 4, 50), 500) if w["M"] <= 128 else 5
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+    torch.cuda.synchronize()
+    for a, b in evs:
+        a.record()
+        eng.elbo(2)
+        b.record()
+    torch.cuda.synchronize()
+    ks = sorted(a.elapsed_time(b) for a, b in evs)
+    k_ms = sum(ks) / len(ks)
+    flop = rows_kernel_flops(dict(w, N=int(Xr.shape[0])))      # this rank's rows
+    big = w["M"] > 128
+    kname = ("rows phase of the general-M path: per 16k-row chunk K_NM tile kernel + 6 k_gemm launches (4 triangular, "
+             "SYRK, statistics) + flow quadrature" if big else
+             "k_rows (fused K_NM + 4 triangular GEMMs + flow quadrature + SYRK)")
+    achieved = flop / (k_ms * 1e-3) / 1e12
+    # HBM bytes per launch of the dominant kernel: from a rocprofv3 --pmc pass (separate FETCH_SIZE / WRITE_SIZE passes,
+    # tools/probes/profile_round.sh) of THE SAME SOURCES -- the summary carries the source hash of the library it was
+    # measured on and is rejected when the library loaded now was built from anything else; never a bare constant
+    traffic = None
+    tj = args.traffic_json or os.path.join(ROOT, "profiles", "rows_traffic.json")
+    if os.path.exists(tj):
+        try:
+            from tgp.pytorch_amd import lib as _lib
+            rec = json.load(open(tj))
+            if rec.get("source_hash") == _lib.load().tgp_source_hash().decode():
+                traffic = rec.get("bytes_per_launch", {}).get(args.workload)
+            else:
+                log("note: %s was measured on sources %s, this library is %s: roofline.traffic = null"
+                    % (tj, rec.get("source_hash"), _lib.load().tgp_source_hash().decode()))
+        except Exception:
+            traffic = None
+    result["config"]["expected"] = exp = expected_line(args.workload, w, world, args.scaling, eng.fp.n + eng.fp.extra,
+                                                       measured_ms_1gpu=result["ms_per_step"] if world == 1 else None)
+    result["roofline"] = {"bound": "mfma", "kernel": kname,
+                          "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                          "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": traffic,
+                          "kernel_ms": k_ms, "kernel_ms_min": ks[0], "flop_per_launch": flop}
+    if exp is not None:
+        # the prediction beside the measurement: > 1 = faster than predicted.  For one rank the basis IS this run's own step
+        # (ratio 1 by construction on the general-M workloads); the multi-rank entries are what a SCALE record falsifies.
+        exp["measured_value"] = result["value"]
+        exp["measured_over_expected"] = result["value"] / exp["value"]
+        log("expected %.1f %s (%.4f ms/step), measured %.1f (%.4f ms/step): measured / expected = %.3f%s"
+            % (exp["value"], result["unit"], exp["ms_per_step"], result["value"], result["ms_per_step"],
+               exp["measured_over_expected"], "" if world == 1 else "  [the expectation's collective term is an ESTIMATE, "
+               "unmeasured on hardware: `bench.py --gpus %d --allreduce-only` measures it]" % world))
+    if world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(prob, args.cpu_seconds, mlp=mlp)
 
 
 if __name__ == "__main__":

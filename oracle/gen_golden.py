@@ -277,6 +277,29 @@ def uci_loader_fixtures():
     save("uci_loaders_seed1", out)
 
 
+UCI_FILES = ("boston.csv", "concrete.csv", "energy.csv", "kin8nm.csv", "naval.tsv", "power.csv", "wine-red.csv", "wine-white.csv")
+
+
+def uci_files_fixture():
+    """The reference's UCI data files themselves, for the loader tests (tests/test_real_data.py writes them back into a
+    temporary directory and points the loader at it) -> tests/golden/uci_files_seed1.npz: the bytes of every CSV the
+    loader reads, lzma-compressed, and the seed-1 split of each split pickle (the only split the tests load).  Data, not source."""
+    import lzma
+    import pickle
+    import dsp
+    uci = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(dsp.__file__))), "datasets", "regression", "uci")
+    out = {}
+    for fname in UCI_FILES:
+        with open(os.path.join(uci, fname), "rb") as fh:
+            out["file." + fname] = np.frombuffer(lzma.compress(fh.read(), preset=9 | lzma.PRESET_EXTREME), dtype=np.uint8)
+        stem = fname.split(".")[0]
+        with open(os.path.join(uci, "splits_idx_%s.pkl" % stem), "rb") as fh:
+            sp = pickle.load(fh)["seed_1"]
+        out["split." + stem + ".train"] = np.asarray(sp["train"])
+        out["split." + stem + ".test"] = np.asarray(sp["test"])
+    save("uci_files_seed1", out)
+
+
 def problem_on(dc, Z, flow, S, perturb, seed=0):
     """orc.synthetic_problem's parameter recipe on real rows: same generators, X/Y/Z replaced."""
     N, D = dc["X_tr"].shape
@@ -403,8 +426,12 @@ def real_data_fixtures():
 
 
 def main():
+    if "--uci-files-only" in sys.argv:
+        uci_files_fixture()
+        return
     if "--uci-only" in sys.argv:
         uci_loader_fixtures()
+        uci_files_fixture()
         return
     if "--real-only" in sys.argv:
         real_data_fixtures()

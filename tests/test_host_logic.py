@@ -281,3 +281,29 @@ def test_bench_expected_line_carries_what_it_is_built_from():
     e8 = bench.expected_line("tgp_power_tanh3x2", w, 8, "strong", 10540)
     assert e1["value"] > e8["value"] > 0 and "ESTIMATE" in e8["basis"]
     assert bench.allreduce_estimate_us(1, 10540) == 0.0 and bench.allreduce_estimate_us(8, 10540) > bench.allreduce_estimate_us(2, 10540)
+
+
+def test_bench_dump_writer_keeps_float64_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array in float64; above the cap every array is replaced by the same
+    seeded sample of its entries on every run, and the files stay within the cap."""
+    import numpy as np
+    import bench
+    g = np.random.default_rng(3)
+    arrays = {"elbo_ell_kl": np.array([-1.5, -1.0, 0.5]), "grad_Lam": g.standard_normal((300, 300)),
+              "param_Z": g.standard_normal((100, 4)).astype(np.float32)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays)
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert b.dtype == np.float64 and np.array_equal(b, a.astype(np.float64))
+    cap = 200000
+    for d in ("s1", "s2"):
+        bench.write_outputs(str(tmp_path / d), arrays, cap=cap)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= cap
+    for f in files:
+        a, b = np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "s1" / "elbo_ell_kl.npy"), arrays["elbo_ell_kl"])
+    lam = np.load(tmp_path / "s1" / "grad_Lam.npy")
+    assert 0 < lam.size < arrays["grad_Lam"].size and np.isin(lam, arrays["grad_Lam"]).all()

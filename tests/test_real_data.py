@@ -3,8 +3,9 @@
 * the product loader (tgp/pytorch_amd/data.py) against tests/golden/{power,boston}_seed1.npz, which
   oracle/gen_golden.py produced by calling the reference's own `return_dataset` (code/dsp/data/datasets.py:81,
   uci_datasets.py:62-107, data.py:260-299): split indices bit-exact, z-scored rows and Y_std to 1e-15.
-  Needs the reference's data files (CSV + split pickle: data, not source) -- found through $TGP_DATA_ROOT or
-  /root/reference in the build container; skipped where they do not exist (the GPU box).
+  The reference's data files the loader reads (CSV + split pickle: data, not source) travel as
+  tests/golden/uci_files_seed1.npz (oracle/gen_golden.py --uci-files-only) and are written back into a temporary
+  directory that the loader is pointed at.
 * the oracle against the reference's step 0 / evaluation path / first Adam steps at N=8611, M=100 (Power split 1)
   and N=455, M=5 (Boston): the known answers of SURVEY.md 8(c) included.
 """
@@ -17,9 +18,23 @@ import torch
 from conftest import load_golden, rel_err
 from oracle import tgp_oracle as orc
 
-UCI = os.environ.get("TGP_DATA_ROOT") or "/root/reference/code/datasets/regression/uci"
-needs_data = pytest.mark.skipif(not os.path.exists(os.path.join(UCI, "power.csv")),
-                                reason="the reference's UCI data files are not on this machine")
+
+@pytest.fixture(scope="module")
+def uci(tmp_path_factory):
+    """A directory laid out like the reference's datasets/regression/uci: the stored CSV bytes and, per data set, a split
+    pickle {"seed_1": {"train": idx, "test": idx}} (the layout of the reference's splits_idx_<name>.pkl)."""
+    import lzma
+    import pickle
+    root = tmp_path_factory.mktemp("uci")
+    z = np.load(os.path.join(os.path.dirname(__file__), "golden", "uci_files_seed1.npz"))
+    for k in z.files:
+        if k.startswith("file."):
+            (root / k[5:]).write_bytes(lzma.decompress(z[k].tobytes()))
+        elif k.endswith(".train"):
+            stem = k[6:-6]
+            with open(root / ("splits_idx_%s.pkl" % stem), "wb") as fh:
+                pickle.dump({"seed_1": {"train": z[k], "test": z["split.%s.test" % stem]}}, fh)
+    return str(root)
 
 
 @pytest.fixture()
@@ -33,13 +48,12 @@ def f64():
     cg.device = old_dev
 
 
-@needs_data
 @pytest.mark.parametrize("name", ["power", "boston"])
-def test_product_loader_equals_reference_loader(name, f64):
+def test_product_loader_equals_reference_loader(name, f64, uci):
     from tgp.pytorch_amd.data import return_dataset
     g = load_golden(name + "_seed1")
     loaders, dc = return_dataset(name, 10000, use_validation=None, seed=1,
-                                 options={"shuffle_train": True, "split_from_disk": True, "root": UCI})
+                                 options={"shuffle_train": True, "split_from_disk": True, "root": uci})
     assert len(loaders) == 2                                   # [train, test] (datasets.py:139-142)
     assert np.array_equal(dc["train_idx"], g["train_idx"].numpy()) and np.array_equal(dc["test_idx"], g["test_idx"].numpy())
     assert dc["N_tr"] == int(g["N_tr"]) and dc["N_te"] == int(g["N_te"]) and dc["Dx"] == g["X_tr"].shape[1] and dc["Dy"] == 1
@@ -56,16 +70,15 @@ def test_product_loader_equals_reference_loader(name, f64):
     assert ystd.shape == (1,) and abs(float(ystd[0]) - float(g["Y_std"][0])) <= 1e-15
 
 
-@needs_data
 @pytest.mark.parametrize("name", ["concrete", "kin8nm", "energy", "wine_red", "wine_white", "naval"])
-def test_other_uci_sets_equal_the_reference_loader(name, f64):
+def test_other_uci_sets_equal_the_reference_loader(name, f64, uci):
     """The other regression sets the reference ships with split pickles (uci_datasets.py:186-283: separators ',', ';' and
     three blanks; energy's target is the second-to-last column and the last is dropped) against a compact fixture of the
     reference's own return_dataset: indices bit-exact, shapes, Y_std, every 97th z-scored row of each split to 1e-15."""
     from tgp.pytorch_amd.data import return_dataset
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "uci_loaders_seed1.npz"))
     loaders, dc = return_dataset(name, 10000, use_validation=None, seed=1,
-                                 options={"shuffle_train": True, "split_from_disk": True, "root": UCI})
+                                 options={"shuffle_train": True, "split_from_disk": True, "root": uci})
     assert np.array_equal(dc["train_idx"], g[name + ".train_idx"]) and np.array_equal(dc["test_idx"], g[name + ".test_idx"])
     n_tr, n_te, dx = (int(v) for v in g[name + ".shape"])
     assert (dc["N_tr"], dc["N_te"], dc["Dx"], dc["Dy"]) == (n_tr, n_te, dx, 1)
@@ -76,33 +89,31 @@ def test_other_uci_sets_equal_the_reference_loader(name, f64):
         assert got.shape == ref.shape and np.abs(got - ref).max() <= 1e-15 * max(1.0, np.abs(ref).max()), k
 
 
-def test_unknown_dataset_is_rejected(f64):
+def test_unknown_dataset_is_rejected(f64, uci):
     from tgp.pytorch_amd.data import return_dataset
     with pytest.raises(ValueError):
-        return_dataset("protein", 100, seed=1, options={"root": UCI})      # no split pickle ships for it
+        return_dataset("protein", 100, seed=1, options={"root": uci})      # no split pickle ships for it
     with pytest.raises(ValueError):
         return_dataset("synthetic_concrete", 100, seed=1)
 
 
-@needs_data
-def test_validation_split_follows_the_reference(f64):
+def test_validation_split_follows_the_reference(f64, uci):
     """use_validation = [seed, N_val] (uci_datasets.py:54-56, data.py:216-234): numpy.random.seed permutation, the
     statistics come from the reduced train split."""
     from tgp.pytorch_amd.data import return_dataset
     g = load_golden("power_seed1")
-    loaders, dc = return_dataset("power", 10000, use_validation=[3, 50], seed=1, options={"root": UCI})
+    loaders, dc = return_dataset("power", 10000, use_validation=[3, 50], seed=1, options={"root": uci})
     assert len(loaders) == 3 and dc["N_va"] == 50 and dc["N_tr"] == 8611 - 50
     assert float((dc["X_va"][:8] - g["val_X_va_head"]).abs().max()) <= 1e-15
     assert abs(float(dc["Y_std"][0]) - float(g["val_Y_std"][0])) <= 1e-15
 
 
-@needs_data
-def test_loader_errors(f64):
+def test_loader_errors(f64, uci):
     from tgp.pytorch_amd.data import return_dataset
     with pytest.raises(KeyError):
-        return_dataset("power", 10000, seed=99, options={"root": UCI})
+        return_dataset("power", 10000, seed=99, options={"root": uci})
     with pytest.raises(ValueError):
-        return_dataset("protein", 10000, seed=1, options={"root": UCI})
+        return_dataset("protein", 10000, seed=1, options={"root": uci})
     with pytest.raises(FileNotFoundError):
         return_dataset("power", 10000, seed=1, options={"root": "/nonexistent"})
 

@@ -7,7 +7,7 @@ one() { python -c "import sys,json; s=sys.stdin.read(); r=json.loads(s) if s.str
 for w in "$@"; do
   n=${w%%:*}; rest=${w#*:}; st=${rest%%:*}; wu=${rest#*:}
   for rep in 1 2; do
-    python $R/bench.py --workload $n --steps $st --warmup $wu --no-cpu-baseline 2>/dev/null | one "$n shipped"
-    for d in $R/tools/probes/variants/*/; do v=$(basename $d); python $R/tools/probes/bench_with_lib.py $d/libtgp_hip.so --workload $n --steps $st --warmup $wu --no-cpu-baseline 2>/dev/null | one "$n $v"; done
+    python $R/bench.py --full --workload $n --steps $st --warmup $wu --no-cpu-baseline 2>/dev/null | one "$n shipped"
+    for d in $R/tools/probes/variants/*/; do v=$(basename $d); python $R/tools/probes/bench_with_lib.py $d/libtgp_hip.so --full --workload $n --steps $st --warmup $wu --no-cpu-baseline 2>/dev/null | one "$n $v"; done
   done
 done

@@ -35,20 +35,20 @@ json.dump(rec, open("$O/rows_traffic.json", "w"), indent=1)
 print("k_rows HBM bytes per launch:", rec["bytes_per_launch"])
 PY
 # ---- bench lines (the headline one carries roofline.traffic from the summary above: same sources) ----
-python bench.py --steps 2000 --warmup 100 --cpu-seconds 8 --traffic-json $O/rows_traffic.json > $O/bench_tgp_power_tanh3x2.json 2> $O/bench_tgp_power_tanh3x2.err
+python bench.py --full --steps 2000 --warmup 100 --cpu-seconds 8 --traffic-json $O/rows_traffic.json > $O/bench_tgp_power_tanh3x2.json 2> $O/bench_tgp_power_tanh3x2.err
 cut -c1-330 $O/bench_tgp_power_tanh3x2.json
-python bench.py --steps 20 --warmup 5 --cpu-seconds 8 --traffic-json $O/rows_traffic.json > $O/bench_tgp_power_tanh3x2_driver_cmdline.json 2> /dev/null
+python bench.py --full --steps 20 --warmup 5 --cpu-seconds 8 --traffic-json $O/rows_traffic.json > $O/bench_tgp_power_tanh3x2_driver_cmdline.json 2> /dev/null
 for w in tgp_power_sal2 svgp_power svgp_boston idtgp_power_sal3; do
-  python bench.py --workload $w --cpu-seconds 8 > $O/bench_$w.json 2> $O/bench_$w.err
+  python bench.py --full --workload $w --cpu-seconds 8 > $O/bench_$w.json 2> $O/bench_$w.err
   cut -c1-230 $O/bench_$w.json
 done
-python bench.py --workload tgp_airline_tanh5x6 --steps 20 --warmup 3 --cpu-seconds 8 > $O/bench_tgp_airline_tanh5x6.json 2> $O/bench_airline.err
+python bench.py --full --workload tgp_airline_tanh5x6 --steps 20 --warmup 3 --cpu-seconds 8 > $O/bench_tgp_airline_tanh5x6.json 2> $O/bench_airline.err
 cut -c1-230 $O/bench_tgp_airline_tanh5x6.json
 for w in tgp_airline_mb10k tgp_airline_mb10k_rank8; do
-  python bench.py --workload $w --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
+  python bench.py --full --workload $w --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_$w.json 2> $O/bench_$w.err
   cut -c1-230 $O/bench_$w.json
 done
-TGP_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline 2> /dev/null | grep "^{" > $O/bench_selflaunch_2ranks_1gpu_gloo_strong.json
+TGP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 200 --warmup 20 --no-cpu-baseline 2> /dev/null | grep "^{" > $O/bench_selflaunch_2ranks_1gpu_gloo_strong.json
 cut -c1-230 $O/bench_selflaunch_2ranks_1gpu_gloo_strong.json
 python bench.py --allreduce-only 2> /dev/null | grep "^{" > $O/allreduce_only_1rank.json; cut -c1-300 $O/allreduce_only_1rank.json
 # ---- the same bench lines on the previous round's tree, alternately, on THIS box (a git worktree of its commit under ab_r05/, built there)
