@@ -56,7 +56,7 @@
 extern "C" {
 #endif
 
-#define TGP_VERSION 103
+#define TGP_VERSION 104
 #define TGP_FUSED_MAX_M 128 /* up to here the whole step is 4 fused kernel launches (operators resident in LDS/registers) */
 #define TGP_BIG_MAX_M 4096  /* above: chunked path built on a tiled float64 MFMA GEMM                             */
 
@@ -74,16 +74,23 @@ extern "C" {
  *   kind   TGP_FLOW_AFFINE   g = a f + b                                   (flow.py:330-340)
  *          TGP_FLOW_SAL      g = sinh(b asinh(f) - a), asinh = log(f+sqrt(f^2+1)) (flow.py:904-905,936-977)
  *          TGP_FLOW_STEPTANH g = [f +] sum_k a_k + sp(b_k) tanh((f-c_k)/sp(d_k)) (flow.py:1096-1103,760-771)
+ *          TGP_FLOW_ARCSINH  g = a + b asinh((f-c)/d) [+ f], asinh = log(x+sqrt(x^2+1)) (flow.py:495-521)
+ *          TGP_FLOW_BOXCOX   g = (sgn(f)|f|^lam - 1)/lam [+ f]; lam == 0 is taken as 1e-11 (flow.py:377-417)
+ *          TGP_FLOW_INV_BOXCOX g = sgn(w)|w|^(1/lam) [+ f], w = lam f + 1 (flow.py:424-443)
  *   K      number of tanh steps (STEPTANH only)
  *   poff   offset of the block's parameters in `theta` (shared scalars: AFFINE {a,b}, SAL {a,b},
- *          STEPTANH {a_k,b_k,c_k,d_k}_k) or first column in `rowp` when TGP_FLAG_PER_ROW is set
- *   flags  TGP_FLAG_RESTRICT  set_restrictions=True: softplus on AFFINE.a / SAL.b
+ *          STEPTANH {a_k,b_k,c_k,d_k}_k, ARCSINH {a,b,c,d}, BOXCOX / INV_BOXCOX {lam}) or first column in
+ *          `rowp` when TGP_FLAG_PER_ROW is set (AFFINE and SAL only; the other kinds refuse it)
+ *   flags  TGP_FLAG_RESTRICT  set_restrictions=True: softplus on AFFINE.a / SAL.b / ARCSINH.b and .d
  *          TGP_FLAG_ADD_F0    add_init_f0=True
  *          TGP_FLAG_PER_ROW   input-dependent parameters, one value per data row (flow.py:949-965)
  */
 #define TGP_FLOW_AFFINE 0
 #define TGP_FLOW_SAL 1
 #define TGP_FLOW_STEPTANH 2
+#define TGP_FLOW_ARCSINH 3
+#define TGP_FLOW_BOXCOX 4
+#define TGP_FLOW_INV_BOXCOX 5
 #define TGP_FLAG_RESTRICT 1
 #define TGP_FLAG_ADD_F0 2
 #define TGP_FLAG_PER_ROW 4

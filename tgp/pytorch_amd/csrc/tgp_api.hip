@@ -51,9 +51,11 @@ static int make_prog(const tgp_model* m, bool flow, FlowProg& fp) {
   for (int b = 0; b < m->nblk; ++b) {
     const int kind = m->program[4 * b], K = m->program[4 * b + 1], poff = m->program[4 * b + 2],
               flags = m->program[4 * b + 3];
-    if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_STEPTANH) return -1;
-    const int np = kind == TGP_FLOW_STEPTANH ? 4 * K : 2;
-    if (kind == TGP_FLOW_STEPTANH && (K < 1 || (flags & TGP_FLAG_PER_ROW))) return -1;
+    if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
+    const int np = flow_block_params(kind, K);
+    if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
+    // per-row parameters: AFFINE and SAL only (the reference has no input-dependent tanh-step, arcsinh or Box-Cox flow)
+    if (kind >= TGP_FLOW_STEPTANH && (flags & TGP_FLAG_PER_ROW)) return -1;
     if (poff < 0 || poff + np > ((flags & TGP_FLAG_PER_ROW) ? m->RP : m->P)) return -1;
     for (int j = 0; j < 4; ++j) fp.blk[4 * b + j] = m->program[4 * b + j];
   }

@@ -580,6 +580,39 @@ struct FlowProg {
   int32_t blk[4 * TGP_MAX_BLOCKS];
 };
 
+// Per-kind tables: the ONE source of "parameters per block", "which parameter goes through softplus" and "store-mode stack
+// slots per block" for the host (make_prog) and every kernel.  X = the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX) is
+// compiled in; X = false is the original set (AFFINE, SAL, STEPTANH), for the kernels that never see the new kinds.
+template <bool X = true>
+__host__ __device__ __forceinline__ int flow_block_params(int kind, int K) {
+  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH ? 4 : 1;   // {a, b, c, d} / {lam}
+  return kind == TGP_FLOW_STEPTANH ? 4 * K : 2;
+}
+// parameter j of the block: softplus'ed?  STEPTANH b_k, d_k always (TanhFlow set_restrictions=True, flow.py:1075); with
+// TGP_FLAG_RESTRICT AFFINE.a, SAL.b, ARCSINH.b and .d (flow.py:335, 947, 514-516); BOXCOX lam never (flow.py:396-401)
+template <bool X = true>
+__host__ __device__ __forceinline__ bool flow_param_restricted(int kind, int flags, int j) {
+  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH && (flags & TGP_FLAG_RESTRICT) && (j & 1);
+  if (kind == TGP_FLOW_STEPTANH) return j & 1;
+  return (flags & TGP_FLAG_RESTRICT) && j == (kind == TGP_FLOW_AFFINE ? 0 : 1);
+}
+// store-mode stack slots of a block (see flow_forward_store)
+template <bool X = true>
+__host__ __device__ __forceinline__ int flow_block_slots(int kind, int K) {
+  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH ? 3 : 2;
+  return kind == TGP_FLOW_AFFINE ? 1 : (kind == TGP_FLOW_SAL ? 3 : 1 + K);
+}
+// Template-argument bit of the kernels that have an extended-kind instantiation (k_rows MODE, k_rows4 NW, k_ell_flow NB):
+// set = the flow sweeps are compiled with X = true.  (A bit of an existing argument, not a new argument, so that the
+// instantiations of the original kinds keep their symbols.)
+#define TGP_FLOWX 16
+// does a program need the extended kind set?  (the host picks the X instantiations of the flow kernels on this)
+__host__ __device__ inline bool flow_prog_extended(const int32_t* prog, int nblk) {
+  for (int b = 0; b < nblk; ++b)
+    if (prog[4 * b] >= TGP_FLOW_ARCSINH) return true;
+  return false;
+}
+
 struct FlowDev {
   const int32_t* prog;  // nblk x 4
   int nblk;
@@ -617,7 +650,60 @@ __device__ __forceinline__ double flow_param(const FlowDev& F, const double* rp,
   return a;
 }
 
-// Forward through all blocks (evaluation / prediction).  If dG != nullptr it receives dG/df.
+// The kinds past STEPTANH (shared parameters only) for NB nodes, stage by stage: f <- g(f), gp = dg/df (ADD_F0's + 1
+// included) and the per-node values the reverse sweeps need:
+//   ARCSINH     x = (f - c)/d, s = sqrt(x^2 + 1):  d0 = asinh_ref(x), d1 = x, d2 = b/(d s)   (dg/df = d2 [+ 1];
+//               dg/da = 1, dg/db = d0, dg/dc = -d2, dg/dd = -d2 x)
+//   BOXCOX      p = |f|^lam:       g = (sgn(f) p - 1)/lam, dg/df = |f|^(lam-1) = p/|f|,
+//               d0 = dg/dlam = sgn(f) p log|f|/lam - (sgn(f) p - 1)/lam^2
+//   INV_BOXCOX  w = lam f + 1, q = |w|^(1/lam):  g = sgn(w) q, dg/df = q/|w|,  d0 = dg/dlam = sgn(w) q (f/(lam w) - log|w|/lam^2)
+// |f|^lam is exp_fast(lam log_fast|f|); a lam of exactly 0 is taken as 1e-11 with d(used)/d(raw) = 1 (flow.py:396-401).
+template <int NB>
+__device__ __forceinline__ void flowx_block_n(const FlowDev& F, int kind, int poff, int flags, double (&f)[NB], double (&gp)[NB],
+                                              double (&d0)[NB], double (&d1)[NB], double (&d2)[NB]) {
+  const bool addf = flags & TGP_FLAG_ADD_F0;
+  if (kind == TGP_FLOW_ARCSINH) {
+    const double a = F.tp[poff], b = F.tp[poff + 1], c = F.tp[poff + 2], id = flow_rcp_param(F, poff + 3);
+    double q1[NB], is[NB], s[NB];
+    TGP_EACH(u, NB) d1[u] = (f[u] - c) * id;
+    TGP_EACH(u, NB) q1[u] = d1[u] * d1[u] + 1.0;
+    rsqrt_nr_fwd_n<NB>(q1, is);
+    TGP_EACH(u, NB) s[u] = q1[u] * is[u];
+    TGP_EACH(u, NB) s[u] = fma(fma(-s[u], s[u], q1[u]), 0.5 * is[u], s[u]);
+    TGP_EACH(u, NB) d0[u] = d1[u] + s[u];
+    log_fast_n<NB>(d0);                                   // asinh as the reference writes it (flow.py:504-505)
+    TGP_EACH(u, NB) {
+      d2[u] = b * id * is[u];
+      const double g = a + b * d0[u];
+      gp[u] = addf ? d2[u] + 1.0 : d2[u];
+      f[u] = addf ? g + f[u] : g;
+    }
+  } else {
+    const bool inv = kind == TGP_FLOW_INV_BOXCOX;
+    double lam = F.tp[poff];
+    if (lam == 0.0) lam = 1e-11;
+    const double il = rcp_fast(lam);
+    double w[NB], lw[NB], p[NB], r[NB];
+    TGP_EACH(u, NB) w[u] = inv ? lam * f[u] + 1.0 : f[u];
+    TGP_EACH(u, NB) lw[u] = fabs(w[u]);
+    log_fast_n<NB>(lw);
+    TGP_EACH(u, NB) p[u] = (inv ? il : lam) * lw[u];
+    exp_fast_n<NB>(p);
+    TGP_EACH(u, NB) r[u] = w[u];
+    rcp_fast_n<NB>(r);
+    TGP_EACH(u, NB) {
+      const double sp = copysign(p[u], w[u]), gpu = p[u] * fabs(r[u]);
+      const double g = inv ? sp : (sp - 1.0) * il;
+      d0[u] = inv ? sp * il * (f[u] * r[u] - lw[u] * il) : il * (sp * lw[u] - (sp - 1.0) * il);
+      gp[u] = addf ? gpu + 1.0 : gpu;
+      f[u] = addf ? g + f[u] : g;
+    }
+  }
+}
+
+// Forward through all blocks (evaluation / prediction).  If dG != nullptr it receives dG/df.  One node at a time, every kind
+// at run time: the plain statement of the interpreter for a kernel that evaluates single nodes.  No kernel calls it at present
+// (the evaluation kernels use flow_forward_n), so it adds nothing to any kernel's code.
 __device__ inline double flow_forward(const FlowDev& F, double f, const double* __restrict__ rp, double* stack,
                                       int sstride, double* dG) {
   double der = 1.0;
@@ -641,6 +727,11 @@ __device__ inline double flow_forward(const FlowDev& F, double f, const double* 
       if (flags & TGP_FLAG_ADD_F0) { g += f; gp += 1.0; }
       f = g;
       der *= gp;
+    } else if (kind >= TGP_FLOW_ARCSINH) {  // (shared parameters only)
+      double fv[1] = {f}, gp[1], d0[1], d1[1], d2[1];
+      flowx_block_n<1>(F, kind, poff, flags, fv, gp, d0, d1, d2);
+      f = fv[0];
+      der *= gp[0];
     } else {  // STEPTANH (shared parameters only; the reference raises NotImplementedError for per-row step flows)
       const bool addf = flags & TGP_FLAG_ADD_F0;
       double g = addf ? f : 0.0, gp = addf ? 1.0 : 0.0;
@@ -664,12 +755,21 @@ __device__ inline double flow_forward(const FlowDev& F, double f, const double* 
 // with the library tanh / sinh / cosh / division is ~4x the instructions).  rp[u] = per-row parameters of element u.
 // Unlike the training sweeps (exp clamped to the finite range), an exponent past the float64 range gives +inf here: the
 // reference's evaluation pushes every node through the naive sinh(b asinh f - a) and reports the inf.
-template <int NB, bool DER>
+// X: the extended kind set is compiled in (flowx_block_n).
+template <int NB, bool DER, bool X = false>
 __device__ inline void flow_forward_n(const FlowDev& F, double (&f)[NB], const double* const (&rp)[NB], double (&der)[NB]) {
   TGP_EACH(u, NB) der[u] = 1.0;
   for (int b = 0; b < F.nblk; ++b) {
     const int kind = F.prog[4 * b], K = F.prog[4 * b + 1], poff = F.prog[4 * b + 2], flags = F.prog[4 * b + 3];
     const bool pr = flags & TGP_FLAG_PER_ROW;
+    if constexpr (X) {
+      if (kind >= TGP_FLOW_ARCSINH) {
+        double gp[NB], d0[NB], d1[NB], d2[NB];
+        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        if (DER) { TGP_EACH(u, NB) der[u] *= gp[u]; }
+        continue;
+      }
+    }
     if (kind == TGP_FLOW_AFFINE) {
       TGP_EACH(u, NB) {
         double a = flow_param(F, rp[u], poff, pr);
@@ -734,14 +834,15 @@ __device__ inline void flow_forward_n(const FlowDev& F, double (&f)[NB], const d
 // ---------------------------------------------------------------------------------------------------
 // "store" evaluation: NB quadrature nodes in flight per lane (independent dependency chains for the
 // single-wave-per-SIMD row kernel), forward keeps what the reverse sweep needs so that the reverse sweep
-// contains no transcendental.  Stack slots per block: AFFINE 1 {f_in}; SAL 3 {u, cosh t, g'}; STEPTANH 1+K
-// {f_in, tanh_k}.  Slot s of node u lives at stack[(s*NB + u) * sstride].
+// contains no transcendental.  Stack slots per block (flow_block_slots): AFFINE 1 {f_in}; SAL 3 {u, cosh t, g'}; STEPTANH 1+K
+// {f_in, tanh_k}; ARCSINH 3 {asinh x, x, b/(d s)}; BOXCOX and INV_BOXCOX 2 {dg/dlam, g'} (flowx_block_n).  Slot s of node u
+// lives at stack[(s*NB + u) * sstride].  The kinds past STEPTANH exist only in the X = true instantiations.
 // sinh/cosh/tanh are formed from ONE exp (+1 division): absolute error ~1e-16 * max(1, cosh), which is what the
 // residual y - G(f) needs; asinh keeps the reference's log form.
 // ---------------------------------------------------------------------------------------------------
 __host__ __device__ inline int flow_slots(const int32_t* prog, int nblk) {
   int s = 0;
-  for (int b = 0; b < nblk; ++b) s += prog[4 * b] == TGP_FLOW_AFFINE ? 1 : (prog[4 * b] == TGP_FLOW_SAL ? 3 : 1 + prog[4 * b + 1]);
+  for (int b = 0; b < nblk; ++b) s += flow_block_slots(prog[4 * b], prog[4 * b + 1]);
   return s;
 }
 
@@ -749,7 +850,7 @@ __host__ __device__ inline int flow_slots(const int32_t* prog, int nblk) {
 // rpn[u], an LDS table of the row's TRANSFORMED parameters the caller staged -- entry 2 c = value of column c (softplus
 // already applied where the block restricts it), entry 2 c + 1 = d(value)/d(raw) -- so the sweeps neither wait for global
 // memory nor evaluate a softplus per node.  Supported for SAL blocks (the per-row flows of this package); `rp` is unused.
-template <int NB, bool PN = false>
+template <int NB, bool PN = false, bool X = false>
 __device__ inline void flow_forward_store(const FlowDev& F, double (&f)[NB], const double* __restrict__ rp,
                                           double* stack, int sstride, const double* const* rpn = nullptr) {
   int sl = 0;
@@ -758,6 +859,26 @@ __device__ inline void flow_forward_store(const FlowDev& F, double (&f)[NB], con
     const int kind = nx.kind, K = nx.K, poff = nx.poff, flags = nx.flags;
     nx = flow_blk(F.prog, b + 1 < F.nblk ? b + 1 : b);
     const bool pr = flags & TGP_FLAG_PER_ROW;
+    if constexpr (X) {
+      if (kind >= TGP_FLOW_ARCSINH) {
+        double gp[NB], d0[NB], d1[NB], d2[NB];
+        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        if (kind == TGP_FLOW_ARCSINH) {
+          TGP_EACH(u, NB) {
+            stack[((sl + 0) * NB + u) * sstride] = d0[u];
+            stack[((sl + 1) * NB + u) * sstride] = d1[u];
+            stack[((sl + 2) * NB + u) * sstride] = d2[u];
+          }
+        } else {
+          TGP_EACH(u, NB) {
+            stack[((sl + 0) * NB + u) * sstride] = d0[u];
+            stack[((sl + 1) * NB + u) * sstride] = gp[u];
+          }
+        }
+        sl += flow_block_slots(kind, K);
+        continue;
+      }
+    }
     if (kind == TGP_FLOW_AFFINE) {
       double a = flow_param(F, rp, poff, pr);
       if (pr && (flags & TGP_FLAG_RESTRICT)) a = softplus_d(a);
@@ -883,7 +1004,7 @@ __device__ __forceinline__ double flow_red(double x) {
 // PN (see flow_forward_store): the per-row partials of a SAL block are PER NODE -- each node of a lane belongs to another data
 // row -- and go to the block's own, now dead, stack slots (slot + 0: d/da, slot + 1: d/db of node u) through `gst`, the
 // writable alias of `stack`; the caller gathers them per row afterwards.  accr is unused then.
-template <int NB, int RED = 0, bool PN = false>
+template <int NB, int RED = 0, bool PN = false, bool X = false>
 __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], const double* __restrict__ rp,
                                            const double* stack, int sstride, int nslots, double* accq, int qstride,
                                            bool qlead, double* accr, int rstride, const double* const* rpn = nullptr,
@@ -896,6 +1017,57 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
     const int kind = nx.kind, K = nx.K, poff = nx.poff, flags = nx.flags;
     nx = flow_blk(F.prog, b > 0 ? b - 1 : 0);
     const bool pr = flags & TGP_FLAG_PER_ROW;
+    if constexpr (X) {
+      if (kind == TGP_FLOW_ARCSINH) {
+        sl -= 3;
+        double as[NB], xv[NB], gq[NB];
+        TGP_EACH(u, NB) {
+          as[u] = stack[((sl + 0) * NB + u) * sstride];
+          xv[u] = stack[((sl + 1) * NB + u) * sstride];
+          gq[u] = stack[((sl + 2) * NB + u) * sstride];
+        }
+        const double g1 = F.tg[poff + 1], g3 = F.tg[poff + 3], ad = (flags & TGP_FLAG_ADD_F0) ? 1.0 : 0.0;
+        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+        TGP_EACH(u, NB) {
+          const double cg = c[u] * gq[u];
+          p0 += c[u];
+          p1 += c[u] * as[u];
+          p2 -= cg;
+          p3 -= cg * xv[u];
+          c[u] *= gq[u] + ad;
+        }
+        if constexpr (RED == 2) {
+          const int ln = threadIdx.x & 63;
+          const double vv = wave_sum4(p0, p1 * g1, p2, p3 * g3, ln);
+          if ((ln & 15) == 0) lds_acc(accq + (poff + (ln >> 4)) * qstride, vv);
+        } else {
+          p0 = flow_red<RED>(p0); p1 = flow_red<RED>(p1 * g1); p2 = flow_red<RED>(p2); p3 = flow_red<RED>(p3 * g3);
+          if (qlead) {
+            lds_acc(accq + (poff + 0) * qstride, p0);
+            lds_acc(accq + (poff + 1) * qstride, p1);
+            lds_acc(accq + (poff + 2) * qstride, p2);
+            lds_acc(accq + (poff + 3) * qstride, p3);
+          }
+        }
+        continue;
+      }
+      if (kind >= TGP_FLOW_BOXCOX) {
+        sl -= 2;
+        double dl[NB], gp[NB];
+        TGP_EACH(u, NB) {
+          dl[u] = stack[((sl + 0) * NB + u) * sstride];
+          gp[u] = stack[((sl + 1) * NB + u) * sstride];
+        }
+        double pl = 0.0;
+        TGP_EACH(u, NB) {
+          pl += c[u] * dl[u];
+          c[u] *= gp[u];
+        }
+        pl = flow_red<RED>(pl);
+        if (qlead) lds_acc(accq + poff * qstride, pl);
+        continue;
+      }
+    }
     if (kind == TGP_FLOW_AFFINE) {
       sl -= 1;
       double a, fa, fin[NB];
@@ -1025,7 +1197,7 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
 // Shared-parameter partials: summed over the NB nodes in registers, over the wave by shuffles (fixed tree), added by
 // lane 0 into the wave's own accumulator row accw[param] -- no atomics, fixed order.
 // ---------------------------------------------------------------------------------------------------
-template <int NB>
+template <int NB, bool X = false>
 __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], const double* __restrict__ rp, double* stack,
                                          int sstride) {
   for (int b = 0; b < F.nblk; ++b) {
@@ -1033,6 +1205,13 @@ __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], cons
     const bool pr = flags & TGP_FLAG_PER_ROW;
 #pragma unroll
     for (int u = 0; u < NB; ++u) stack[(b * NB + u) * sstride] = f[u];
+    if constexpr (X) {
+      if (kind >= TGP_FLOW_ARCSINH) {
+        double gp[NB], d0[NB], d1[NB], d2[NB];
+        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        continue;
+      }
+    }
     if (kind == TGP_FLOW_AFFINE) {
       double a = flow_param(F, rp, poff, pr);
       if (pr && (flags & TGP_FLAG_RESTRICT)) a = softplus_d(a);
@@ -1077,7 +1256,7 @@ __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], cons
 }
 
 // c[u] = d(objective)/dG on entry, d(objective)/df0 on exit.  All lanes of the wave must call this together.
-template <int NB>
+template <int NB, bool X = false>
 __device__ inline void flow_backward_ckpt(const FlowDev& F, double (&c)[NB], const double* __restrict__ rp, const double* stack,
                                           int sstride, double* accw, int lane, double* accr, int rstride) {
   for (int b = F.nblk - 1; b >= 0; --b) {
@@ -1086,6 +1265,35 @@ __device__ inline void flow_backward_ckpt(const FlowDev& F, double (&c)[NB], con
     double fin[NB];
 #pragma unroll
     for (int u = 0; u < NB; ++u) fin[u] = stack[(b * NB + u) * sstride];
+    if constexpr (X) {
+      if (kind >= TGP_FLOW_ARCSINH) {
+        // recompute the block from its input (checkpoint mode), then the partials as in flow_backward_store
+        double gp[NB], d0[NB], d1[NB], d2[NB];
+        flowx_block_n<NB>(F, kind, poff, flags, fin, gp, d0, d1, d2);
+        if (kind == TGP_FLOW_ARCSINH) {
+          double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+          TGP_EACH(u, NB) {
+            const double cg = c[u] * d2[u];
+            p0 += c[u];
+            p1 += c[u] * d0[u];
+            p2 -= cg;
+            p3 -= cg * d1[u];
+            c[u] *= gp[u];
+          }
+          const double vv = wave_sum4(p0, p1 * F.tg[poff + 1], p2, p3 * F.tg[poff + 3], lane);
+          if ((lane & 15) == 0) accw[poff + (lane >> 4)] += vv;
+        } else {
+          double pl = 0.0;
+          TGP_EACH(u, NB) {
+            pl += c[u] * d0[u];
+            c[u] *= gp[u];
+          }
+          const double vv = wave_sum(pl);
+          if (lane == 0) accw[poff] += vv;
+        }
+        continue;
+      }
+    }
     if (kind == TGP_FLOW_AFFINE) {
       double a, fa;
       if (pr) {

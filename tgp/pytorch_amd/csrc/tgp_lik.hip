@@ -97,16 +97,16 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
 // transformed shared flow parameters into LDS (same rule as k_prep_a); whole block, ends with a barrier
 // `ti` (optional): 1 / tp[i] for every shared parameter, so that a step-tanh step takes 1 / softplus(d_k) from the table instead of
 // running a reciprocal chain per step and sweep
+// X: the extended kind set (flow_block_params)
+template <bool X = false>
 __device__ inline void flow_params_lds(const tgp_model& md, const FlowProg& fp, double* tp, double* tg, double* ti = nullptr) {
   for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
     const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
     if (flags & TGP_FLAG_PER_ROW) continue;
-    const int np = kind == TGP_FLOW_STEPTANH ? 4 * K : 2;
+    const int np = flow_block_params<X>(kind, K);
     for (int j = 0; j < np; ++j) {
       const double x = md.theta[poff + j];
-      bool res;
-      if (kind == TGP_FLOW_STEPTANH) res = (j & 1);
-      else res = (flags & TGP_FLAG_RESTRICT) && j == (kind == TGP_FLOW_AFFINE ? 0 : 1);
+      const bool res = flow_param_restricted<X>(kind, flags, j);
       const double tv = res ? softplus_d(x) : x;
       tp[poff + j] = tv;
       tg[poff + j] = res ? sigmoid_d(x) : 1.0;
@@ -122,12 +122,15 @@ __device__ inline void flow_params_lds(const tgp_model& md, const FlowProg& fp, 
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
 // lane.  The launcher picks LPR from N so that a chunk of ~16k rows still yields ~1000 workgroups.
-template <int LPR, int NB>
+// NBX = NB | TGP_FLOWX: the flow sweeps know the extended kind set (X; see k_rows)
+template <int LPR, int NBX>
 __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, const double* __restrict__ Y,
                                                    const double* __restrict__ mu, const double* __restrict__ v,
                                                    const double* __restrict__ rowp, double* __restrict__ part,
                                                    double* __restrict__ g_mu, double* __restrict__ g_v,
                                                    double* __restrict__ g_rowp) {
+  constexpr int NB = NBX & (TGP_FLOWX - 1);
+  constexpr bool X = NBX & TGP_FLOWX;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* sm = reinterpret_cast<double*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = md.P, RP = md.RP;
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
   double* tg = tp + (P + 2) / 2 * 2;                        // P+2
   double* ti = tg + (P + 2) / 2 * 2;                        // P+2: reciprocals (flow_rcp_param)
   for (int i = tid; i < 4 * (P > 0 ? P : 1) + RP * 256; i += 256) accw[i] = 0.0;
-  flow_params_lds(md, fp, tp, tg, ti);
+  flow_params_lds<X>(md, fp, tp, tg, ti);
   // lane group q takes the quadrature nodes s = q + LPR (NB j + u).  Every lane runs the same trip count (wave-wide
   // sums inside the reverse sweep); nodes past S and padding rows carry weight 0.
   const int qn = lane / RW;
@@ -168,7 +171,7 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
       wsn[u] = (valid && s < md.S) ? md.wn[sc] : 0.0;
       f[u] = m_ + sq * xsn[u];
     }
-    flow_forward_ckpt<NB>(F, f, rp, stack + tid, 256);
+    flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
       const double r = y - f[u];
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
       etap += wsn[u] * (-0.5 + 0.5 * einv * r * r);
       c[u] = md.scale * einv * wsn[u] * r;
     }
-    flow_backward_ckpt<NB>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
+    flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
 #pragma unroll
     for (int u = 0; u < NB; ++u) { cm += c[u]; cv += c[u] * xsn[u]; }
   }
@@ -255,6 +258,59 @@ __global__ __launch_bounds__(256) void k_flow_eval(tgp_model md, FlowProg fp, co
   }
 }
 
+// k_flow_eval with the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX; the host launches it for programs that hold one).
+// A copy of the body above, not a shared template: k_flow_eval itself compiles exactly as before the new kinds.
+__global__ __launch_bounds__(256) void k_flow_eval_x(tgp_model md, FlowProg fp, const double* __restrict__ f, size_t total, int N,
+                                                    const double* __restrict__ rowp, double* __restrict__ G,
+                                                    double* __restrict__ dG, double* __restrict__ logdG,
+                                                    double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* ti = tg + (md.P + 2) / 2 * 2;
+  __shared__ double redl[4];
+  flow_params_lds<true>(md, fp, tp, tg, ti);
+  FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
+  // four elements per thread, a grid stride apart (coalesced), evaluated stage by stage (flow_forward_n)
+  constexpr int NB = 4;
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  double fv[NB], der[NB];
+  const double* rp[NB];
+  TGP_EACH(u, NB) {
+    const size_t i = i0 + u * stride;
+    const size_t ic = i < total ? i : 0;
+    fv[u] = f[ic];
+    rp[u] = rowp ? rowp + (ic % N) * md.RP : nullptr;
+  }
+  if (dG || logdG || part) flow_forward_n<NB, true, true>(F, fv, rp, der);
+  else flow_forward_n<NB, false, true>(F, fv, rp, der);
+  if (part) {
+    // fused log-Jacobian accumulation: sum of log dG/df over this workgroup's elements, fixed order (lane partials ->
+    // butterfly over the wave -> the four waves in LDS); the launcher's second kernel adds the workgroups' partials
+    double sl = 0.0;
+    TGP_EACH(u, NB) sl += (i0 + u * stride < total) ? log(der[u]) : 0.0;
+    sl = wave_sum(sl);
+    if ((threadIdx.x & 63) == 0) redl[threadIdx.x >> 6] = sl;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (redl[0] + redl[1]) + (redl[2] + redl[3]);
+  }
+  if (logdG) {
+    double lg[NB];
+    TGP_EACH(u, NB) lg[u] = der[u];
+    TGP_EACH(u, NB) {
+      const size_t i = i0 + u * stride;
+      if (i < total) logdG[i] = log(lg[u]);
+    }
+  }
+  TGP_EACH(u, NB) {
+    const size_t i = i0 + u * stride;
+    if (i < total) {
+      if (G) G[i] = fv[u];
+      if (dG) dG[i] = der[u];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // prediction given q(f) moments: m1, m2 and per-row test log-likelihood (without the -0.5 log(pi) constant)
 //   flow : GaussianNonLinearMean.marginal_moments (:176-203) ; sparse_MF_SP.test_log_likelihood (:705-776)
@@ -299,6 +355,65 @@ __global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, cons
       rpn[u] = rp;
     }
     flow_forward_n<NB, false>(F, g, rpn, der);
+    TGP_EACH(u, NB) {
+      if (s0 + u < md.S) {
+        m1 += wsn[u] * g[u];
+        e2 += wsn[u] * g[u] * g[u];
+        if (logp && Y) {
+          // log w_s = log(wn_s) + 0.5 log(pi); the caller adds the reference's constants
+          const double r = yy - Y_std * g[u];
+          const double t = log(wsn[u]) - 0.5 * (TGP_LOG_2PI_REF + lvar + r * r * ivar);
+          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
+          else se += exp(t - mx);
+        }
+      }
+    }
+  }
+  if (m1o) m1o[n] = m1;
+  if (m2o) m2o[n] = noise + e2 - m1 * m1;
+  if (logp && Y) logp[n] = mx + log(se);
+}
+
+// k_predict with the extended kind set (see k_flow_eval_x: a copy, so that k_predict compiles exactly as before)
+__global__ __launch_bounds__(256) void k_predict_x(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                  const double* __restrict__ v, const double* __restrict__ rowp,
+                                                  const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
+                                                  double* __restrict__ m2o, double* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  if (md.lik == TGP_LIK_FLOW) flow_params_lds<true>(md, fp, tp, tg);
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= md.N) return;
+  const double noise = exp(md.log_var_noise[0]);
+  if (md.lik == TGP_LIK_GAUSS) {
+    const double m1 = mu[n], m2 = noise + v[n];
+    if (m1o) m1o[n] = m1;
+    if (m2o) m2o[n] = m2;
+    if (logp && Y) {
+      const double sd = Y_std * sqrt(m2), var = sd * sd, r = Y_std * Y[n] - Y_std * m1;
+      logp[n] = -0.5 * (TGP_LOG_2PI_REF + log(var) + r * r / var);
+    }
+    return;
+  }
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
+  const double m_ = mu[n], sq = sqrt(2.0 * v[n]);
+  const double sdy = Y_std * sqrt(noise), var = sdy * sdy;
+  const double yy = Y ? Y_std * Y[n] : 0.0;
+  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
+  const double lvar = log(var), ivar = 1.0 / var;
+  constexpr int NB = 4;  // quadrature nodes in flight (stage-by-stage evaluation, flow_forward_n)
+  for (int s0 = 0; s0 < md.S; s0 += NB) {
+    double g[NB], der[NB], wsn[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
+      g[u] = m_ + sq * md.xs[s];
+      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, false, true>(F, g, rpn, der);
     TGP_EACH(u, NB) {
       if (s0 + u < md.S) {
         m1 += wsn[u] * g[u];
@@ -448,10 +563,18 @@ int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, co
   const int rows = 256 / LPR;
   const int nb = (md.N + rows - 1) / rows;
   static size_t cur[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-#define ELLF_LAUNCH(lpr, nbv, slot)                                                                                         \
-  do {                                                                                                                      \
-    if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_flow<lpr, nbv>), lds, &cur[slot])) return rc;               \
-    hipLaunchKernelGGL((k_ell_flow<lpr, nbv>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp); \
+  static size_t cur_x[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);   // k_ell_flow<.., NB | TGP_FLOWX>: a kind past STEPTANH
+#define ELLF_LAUNCH(lpr, nbv, slot)                                                                                           \
+  do {                                                                                                                        \
+    if (ext) {                                                                                                                \
+      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_flow<lpr, nbv | TGP_FLOWX>), lds, &cur_x[slot])) return rc;  \
+      hipLaunchKernelGGL((k_ell_flow<lpr, nbv | TGP_FLOWX>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu,    \
+                         g_v, g_rowp);                                                                                        \
+    } else {                                                                                                                  \
+      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_flow<lpr, nbv>), lds, &cur[slot])) return rc;               \
+      hipLaunchKernelGGL((k_ell_flow<lpr, nbv>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp);   \
+    }                                                                                                                         \
   } while (0)
   if (LPR == 4) {
     if (NB == 8) ELLF_LAUNCH(4, 8, 0);
@@ -479,8 +602,11 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
   const size_t total = (size_t)S * N;
   const size_t lds = 3 * (size_t)(md.P + 2) * sizeof(double);
   const unsigned nb = (unsigned)((total + 1023) / 1024);
-  hipLaunchKernelGGL(k_flow_eval, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG,
-                     sum_out != nullptr ? ws : (double*)nullptr);
+  double* part = sum_out != nullptr ? ws : (double*)nullptr;
+  if (flow_prog_extended(fp.blk, fp.nblk))
+    hipLaunchKernelGGL(k_flow_eval_x, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
+  else
+    hipLaunchKernelGGL(k_flow_eval, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
   LAUNCH_CHECK();
   if (sum_out != nullptr) {
     hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(256), 0, st, ws, (int)nb, 1, sum_out, (double*)nullptr, 1);
@@ -492,7 +618,10 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
   const size_t lds = 2 * (size_t)(md.P + 2) * sizeof(double);
-  hipLaunchKernelGGL(k_predict, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
+  if (flow_prog_extended(fp.blk, fp.nblk))
+    hipLaunchKernelGGL(k_predict_x, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
+  else
+    hipLaunchKernelGGL(k_predict, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   LAUNCH_CHECK();
   return 0;
 }

@@ -186,13 +186,11 @@ __device__ __forceinline__ void prep_xform_role(const Plan& p, const tgp_model& 
     for (int b = 0; b < fp.nblk; ++b) {
       const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
       if (flags & TGP_FLAG_PER_ROW) continue;
-      const int np = kind == TGP_FLOW_STEPTANH ? 4 * K : 2;
+      const int np = flow_block_params(kind, K);
       if (t < poff || t >= poff + np) continue;
       const int j = t - poff;
       const double x = md.theta[t];
-      bool res;
-      if (kind == TGP_FLOW_STEPTANH) res = (j & 1);  // b_k, d_k: TanhFlow set_restrictions=True (flow.py:1075)
-      else res = (flags & TGP_FLAG_RESTRICT) && j == (kind == TGP_FLOW_AFFINE ? 0 : 1);
+      const bool res = flow_param_restricted(kind, flags, j);
       st_maybe<SHARED>(ws + p.tp + t, res ? softplus_d(x) : x);
       st_maybe<SHARED>(ws + p.tg + t, res ? sigmoid_d(x) : 1.0);
       break;

@@ -172,8 +172,13 @@ __device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0
 // dealt over ALL 64 lanes (pair p = lane + 64 u: row p % 10, node p / 10) with five nodes in flight per lane instead of two
 // trips of four (row inputs and pair results cross the wave through LDS), and the statistics contract over 40 columns
 // instead of 64.
-template <int MT, int DP, int MODE, int RW = 16>
+// MODEX = MODE | TGP_FLOWX: the instantiation whose flow sweeps know the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX,
+// X = true).  The host launches it only for a program that holds one of those kinds; the instantiations of the original
+// kinds (MODEX = MODE) compile exactly as before.
+template <int MT, int DP, int MODEX, int RW = 16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_rows(RowArgs a) {
+  constexpr int MODE = MODEX & (TGP_FLOWX - 1);
+  constexpr bool X = MODEX & TGP_FLOWX;
   static_assert(RW == 16 || (RW == TGP_RW_SMALL && MODE == 1), "rows per wave: 16, or TGP_RW_SMALL in training mode 1");
   constexpr bool TRAIN = MODE != 0;
   constexpr int RBK = 4 * RW;   // data rows (= statistics columns) per workgroup
@@ -534,7 +539,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         yv[u] = rin[32 + row];
         rpn[u] = rpl + row * RP * 2;
       }
-      flow_forward_store<NB, true>(F, f, nullptr, stack + tid, 256, rpn);
+      flow_forward_store<NB, true, X>(F, f, nullptr, stack + tid, 256, rpn);
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
         const double r = yv[u] - f[u];
@@ -542,7 +547,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         etap += wq[u] * (-0.5 + 0.5 * einv * r * r);
         c[u] = a.scale * einv * wq[u] * r;
       }
-      flow_backward_store<NB, 0, true>(F, c, nullptr, stack + tid, 256, a.prog.nslots, accq, 64, q == 0, accr, 256, rpn, stack + tid);
+      flow_backward_store<NB, 0, true, X>(F, c, nullptr, stack + tid, 256, a.prog.nslots, accq, 64, q == 0, accr, 256, rpn, stack + tid);
 #pragma unroll
       for (int u = 0; u < NB; ++u) cb[lane + 64 * u] = c[u];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -567,7 +572,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
               if (q == 0 && valid) a.g_rowp[(size_t)n * RP + poff + jj] = gsum;
             }
           }
-          sl += kind == TGP_FLOW_AFFINE ? 1 : (kind == TGP_FLOW_SAL ? 3 : 1 + K);
+          sl += flow_block_slots<X>(kind, K);
         }
       }
       // row lane (nl, q): the nodes q, q + 4, ... of row nl (pair index node * RW + row)
@@ -604,7 +609,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             wq[u] = (valid && sn < p.S) ? wnL[sn] : 0.0;
             f[u] = mu + sq * xn[u];
           }
-          flow_forward_store<NB>(F, f, rp, stack + tid, 256);
+          flow_forward_store<NB, false, X>(F, f, rp, stack + tid, 256);
 #pragma unroll
           for (int u = 0; u < NB; ++u) {
             const double r = y - f[u];
@@ -612,7 +617,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             etap += wq[u] * (-0.5 + 0.5 * einv * r * r);
             c[u] = a.scale * einv * wq[u] * r;
           }
-          flow_backward_store<NB>(F, c, rp, stack + tid, 256, a.prog.nslots, accq, 64, q == 0, accr, 256);
+          flow_backward_store<NB, 0, false, X>(F, c, rp, stack + tid, 256, a.prog.nslots, accq, 64, q == 0, accr, 256);
 #pragma unroll
           for (int u = 0; u < NB; ++u) {
             cm += c[u];

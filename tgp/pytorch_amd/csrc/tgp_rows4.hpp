@@ -97,8 +97,11 @@ __device__ __forceinline__ double row4_sum(double x) {
 #endif
 
 // TRAIN = false: moments only (tgp_qf_moments_f64).  NW = waves per workgroup (4 NW data rows; Plan.nblocks = ceil(N / 4 NW)).
-template <int MT, int DP, bool TRAIN, int NW>
-__global__ __launch_bounds__(NW * 64) void k_rows4(RowArgs a) {
+// NWX = NW | TGP_FLOWX: the flow sweeps know the extended kind set (see k_rows, tgp_rows.hpp)
+template <int MT, int DP, bool TRAIN, int NWX>
+__global__ __launch_bounds__((NWX & (TGP_FLOWX - 1)) * 64) void k_rows4(RowArgs a) {
+  constexpr int NW = NWX & (TGP_FLOWX - 1);
+  constexpr bool X = NWX & TGP_FLOWX;
   constexpr int MP = MT * 16, NT = NW * 64, NTRI = MT * (MT + 1) / 2, NIMG = NTRI * 256;
   constexpr int CT = (2 * DP + 1 + 15) / 16, CT16 = CT * 16, RB = 4 * NW;
   typedef double d2v __attribute__((ext_vector_type(2)));
@@ -450,7 +453,7 @@ __global__ __launch_bounds__(NW * 64) void k_rows4(RowArgs a) {
             wq[u] = (valid && sn < p.S) ? wnL[sn] : 0.0;
             f[u] = mu + sq * xn[u];
           }
-          flow_forward_store<NB>(F, f, rp, stack + tid, NT);
+          flow_forward_store<NB, false, X>(F, f, rp, stack + tid, NT);
 #pragma unroll
           for (int u = 0; u < NB; ++u) {
             const double r = y - f[u];
@@ -458,7 +461,7 @@ __global__ __launch_bounds__(NW * 64) void k_rows4(RowArgs a) {
             etap += wq[u] * (-0.5 + 0.5 * einv * r * r);
             c[u] = a.scale * einv * wq[u] * r;
           }
-          flow_backward_store<NB, 2>(F, c, rp, stack + tid, NT, a.prog.nslots, accq, NW, lane == 0, accr, NT);
+          flow_backward_store<NB, 2, false, X>(F, c, rp, stack + tid, NT, a.prog.nslots, accq, NW, lane == 0, accr, NT);
 #pragma unroll
           for (int u = 0; u < NB; ++u) {
             cm += c[u];

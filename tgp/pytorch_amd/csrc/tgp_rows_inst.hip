@@ -1,5 +1,6 @@
 // tgp_rows_inst.hip -- one translation unit per MT (compiled 8x with -DTGP_MT=1..8 so the big unrolled
-// kernels build in parallel); each defines launch_rows_mt<N>().
+// kernels build in parallel); each defines launch_rows_mt<N>().  Compiled another 8x with -DTGP_FLOWX_BUILD=1: the training
+// kernels whose flow sweeps know the extended kind set (the TGP_FLOWX bit set in MODE / NW), launch_rows_mt<N>_x().
 #include "tgp_rows.hpp"
 #include "tgp_rows4.hpp"
 #include "tgp_launch.hpp"
@@ -7,15 +8,34 @@
 #ifndef TGP_MT
 #error "compile with -DTGP_MT=<1..8>"
 #endif
+#ifndef TGP_FLOWX_BUILD
+#define TGP_FLOWX_BUILD 0
+#endif
 #define CAT_(a, b) a##b
 #define CAT(a, b) CAT_(a, b)
+#if TGP_FLOWX_BUILD
+#define TGP_XBIT TGP_FLOWX
+#define TGP_LAUNCH_MT CAT(CAT(launch_rows_mt, TGP_MT), _x)
+#else
+#define TGP_XBIT 0
+#define TGP_LAUNCH_MT CAT(launch_rows_mt, TGP_MT)
+#endif
+// TGP_DP16_APART: this unit leaves the DP = 16 kernels to a unit of their own, compiled with -DTGP_DP16_ONLY, which defines
+// launch_rows_mt<N>[_x]_dp16() (the Makefile uses it where the compiler cannot build those kernels with the others' flags)
+#ifndef TGP_DP16_APART
+#define TGP_DP16_APART 0
+#endif
+#ifndef TGP_DP16_ONLY
+#define TGP_DP16_ONLY 0
+#endif
+#define TGP_LAUNCH_DP16 CAT(TGP_LAUNCH_MT, _dp16)
 
 namespace tgp {
 
 template <int DP, int MODE, int RW = 16>
 static int launch_one(const RowArgs& a, size_t lds, hipStream_t st) {
   constexpr bool TRAIN = MODE != 0;
-  auto kern = k_rows<TGP_MT, DP, MODE, RW>;
+  auto kern = k_rows<TGP_MT, DP, MODE | TGP_XBIT, RW>;
   static size_t lds_cur = 48 * 1024;
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &lds_cur)) return rc;
   // the row blocks, then (training) the MT passenger blocks
@@ -29,7 +49,7 @@ static int launch_one(const RowArgs& a, size_t lds, hipStream_t st) {
 // the 4-rows-per-wave kernel (tgp_rows4.hpp): NW waves per workgroup
 template <int DP, bool TRAIN, int NW>
 static int launch_one4(const RowArgs& a, hipStream_t st) {
-  auto kern = k_rows4<TGP_MT, DP, TRAIN, NW>;
+  auto kern = k_rows4<TGP_MT, DP, TRAIN, NW | TGP_XBIT>;
   const size_t lds = row4_lds(a.p, TRAIN, a.prog.nslots, NW).total * sizeof(double);
   static size_t lds_cur = 48 * 1024;
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &lds_cur)) return rc;
@@ -46,21 +66,36 @@ static int launch_dp(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
     case 150 + 4: return launch_one4<DP, true, 4>(a, st);
     case 150 + 8: return launch_one4<DP, true, 8>(a, st);
     case 200: return launch_one<DP, 1, TGP_RW_SMALL>(a, lds, st);
+#if TGP_FLOWX_BUILD
+    case 0: return TGP_E_UNSUPPORTED;   // (moments only: no flow, the plain kernel serves every program)
+#else
     case 0: return launch_one<DP, 0>(a, lds, st);
+#endif
     case 1: return launch_one<DP, 1>(a, lds, st);
     default: return launch_one<DP, 2>(a, lds, st);
   }
 }
 
-int CAT(launch_rows_mt, TGP_MT)(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
+#if TGP_DP16_ONLY
+int TGP_LAUNCH_DP16(const RowArgs& a, int mode, size_t lds, hipStream_t st) { return launch_dp<16>(a, mode, lds, st); }
+#else
+#if TGP_DP16_APART
+int TGP_LAUNCH_DP16(const RowArgs& a, int mode, size_t lds, hipStream_t st);
+#endif
+int TGP_LAUNCH_MT(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
   switch (a.p.DP) {
     case 4: return launch_dp<4>(a, mode, lds, st);
     case 8: return launch_dp<8>(a, mode, lds, st);
+#if TGP_DP16_APART
+    default: return TGP_LAUNCH_DP16(a, mode, lds, st);
+#else
     default: return launch_dp<16>(a, mode, lds, st);
+#endif
   }
 }
+#endif
 
-#if TGP_MT == 1
+#if TGP_MT == 1 && !TGP_FLOWX_BUILD
 size_t rows4_lds_bytes(const Plan& p, bool train, int nw) {
   const Row4Lds L = row4_lds(p, train, p.nslots, nw);
   return L.nb == 0 ? (size_t)1 << 30 : L.total * sizeof(double);   // (not even one quadrature node per lane fits: not a candidate)

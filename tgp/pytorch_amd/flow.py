@@ -4,8 +4,10 @@
 
 The modules are parameter holders + a compiler to the flow *program* the HIP kernels execute
 (`compile_flow`); `forward()` evaluates the flow on the GPU through tgp_flow_eval_f64 (no autograd: the
-training path differentiates inside the fused kernel, ops.ElboFunction).  Only the flows main.py can
-reach are provided: affine, sinh_arcsinh, tanh (inside step_flow), step_flow, identity.
+training path differentiates inside the fused kernel, ops.ElboFunction).  Provided: affine, sinh_arcsinh,
+tanh (inside step_flow), step_flow, identity -- the flows main.py's default recipes reach -- and arcsinh, boxcox and
+inverseboxcox, the other kinds the reference's generators (flows.py: ArcSL, BoxCoxL, InverseBoxCoxL, build_chain) emit.
+Box-Cox constraints other than the default (a Python callable) cannot run inside a captured step and are refused.
 """
 import torch
 import torch.nn as nn
@@ -29,9 +31,15 @@ def instance_flow(flow_list, is_composite=True):
             fl = TanhFlow(**init_values)
         elif name == "step_flow":
             fl = StepFlow(**init_values)
+        elif name == "arcsinh":
+            fl = ArcsinhFlow(**init_values)
+        elif name == "boxcox":
+            fl = BoxCoxFlow(**init_values)
+        elif name in ("inverseboxcox", "inverse_boxcox"):
+            fl = InverseBoxCoxFlow(**init_values)
         else:
             raise ValueError("Unkown flow identifier {} (this build provides affine, sinh_arcsinh, tanh, step_flow, "
-                             "identity: the flows reachable from main.py)".format(name))
+                             "identity, arcsinh, boxcox, inverseboxcox)".format(name))
         FL.append(fl)
     return CompositeFlow(FL) if is_composite else FL
 
@@ -153,6 +161,36 @@ class Sinh_ArcsinhFlow(Flow):
             self.a = None
             self.b = None
             self.parameters_are_turn_off = True
+
+
+class ArcsinhFlow(Flow):
+    """fk = a + b*asinh((f0-c)/d) [+ f0] (flow.py:495-521); set_restrictions: b, d through softplus (forced by
+    add_init_f0, flow.py:518-520).  Shared parameters only: the reference has no input-dependent arcsinh flow."""
+
+    def __init__(self, init_a, init_b, init_c, init_d, add_init_f0, set_restrictions):
+        super().__init__()
+        for n, v in (("a", init_a), ("b", init_b), ("c", init_c), ("d", init_d)):
+            setattr(self, n, nn.Parameter(torch.tensor(v, dtype=cg.dtype)))
+        self.set_restrictions = True if add_init_f0 else set_restrictions
+        self.add_init_f0 = add_init_f0
+
+
+class BoxCoxFlow(Flow):
+    """fk = (sgn(f0)|f0|^lam - 1)/lam [+ f0] (flow.py:377-417); lam == 0 is taken as 1e-11.  Only the default (identity)
+    parameter transform is provided: a `constraint` callable is arbitrary Python the captured training step cannot run."""
+
+    def __init__(self, init_lam, add_init_f0, constraint=None):
+        super().__init__()
+        if constraint is not None:
+            raise NotImplementedError("{}: a `constraint` callable on lam is not supported (the HIP flow kernels apply the "
+                                      "reference's default transform only; pass constraint=None)".format(type(self).__name__))
+        self.lam = nn.Parameter(torch.tensor(init_lam, dtype=cg.dtype))
+        self.add_init_f0 = add_init_f0
+        self.constraint = None
+
+
+class InverseBoxCoxFlow(BoxCoxFlow):
+    """fk = sgn(w)|w|^(1/lam) [+ f0], w = lam*f0 + 1 (flow.py:424-443)."""
 
 
 class StepFlow(Flow):
@@ -307,6 +345,14 @@ def compile_flow(flow):
             else:
                 blocks.append((L.FLOW_SAL, 0, len(theta), flags))
                 theta += [fl.a, fl.b]
+        elif isinstance(fl, ArcsinhFlow):
+            flags = (L.FLAG_RESTRICT if fl.set_restrictions else 0) | (L.FLAG_ADD_F0 if fl.add_init_f0 else 0)
+            blocks.append((L.FLOW_ARCSINH, 0, len(theta), flags))
+            theta += [fl.a, fl.b, fl.c, fl.d]
+        elif isinstance(fl, BoxCoxFlow):
+            kind = L.FLOW_INV_BOXCOX if isinstance(fl, InverseBoxCoxFlow) else L.FLOW_BOXCOX
+            blocks.append((kind, 0, len(theta), L.FLAG_ADD_F0 if fl.add_init_f0 else 0))
+            theta += [fl.lam]
         elif isinstance(fl, StepFlow):
             K = len(fl.flow_arr)
             blocks.append((L.FLOW_STEPTANH, K, len(theta), L.FLAG_ADD_F0 if fl.add_init_f0 else 0))

@@ -1,5 +1,9 @@
 """Flow *spec generators* with the reference's call signatures and list-of-(name, init_dict) output format
-(code/dsp/flows.py: SAL :115-136, StepTanhL :239-277).  Only the generators main.py can reach are provided."""
+(code/dsp/flows.py: build_chain :79-112, SAL :115-136, BoxCoxL :140-165, InverseBoxCoxL :169-192, ArcSL :197-217,
+Affine :223-235, StepTanhL :239-277).  Same defaults, same init values and the same numpy.random draw order, so a seeded
+call returns the reference's specs.  The step generators other than StepTanhL (StepSAL, StepArcSL, StepBoxCoxL, ...) are
+not provided: their step flows of mixed kinds have no HIP program.  A Box-Cox `constraint` passes through into the spec;
+flow.BoxCoxFlow refuses anything but None."""
 import numpy
 import torch
 
@@ -58,4 +62,97 @@ def StepTanhL(num_blocks, num_steps, **kwargs):
         a_aff, b_aff = numpy.random.randn(2) if init_random else (1.0, 0.0)
         blocks.append(("step_flow", {"flow_arr": steps, "add_init_f0": addf0}))
         blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": False}))
+    return blocks
+
+
+def BoxCoxL(num_blocks, **kwargs):
+    """[boxcox, affine] x num_blocks; default lam = 5 (init_random: randn(1) + 1 and no constraint)."""
+    set_res, addf0, init_random, constraint = _common(kwargs)
+    blocks = []
+    for _ in range(num_blocks):
+        if init_random:
+            a_aff, b_aff = numpy.random.randn(2)
+            init_lam = numpy.random.randn(1) + 1.
+            constraint = None
+        else:
+            a_aff, b_aff = 1.0, 0.0
+            init_lam = 5.0
+        blocks.append(("boxcox", {"init_lam": init_lam, "add_init_f0": addf0, "constraint": constraint}))
+        blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
+    return blocks
+
+
+def InverseBoxCoxL(num_blocks, **kwargs):
+    """[inverseboxcox, affine] x num_blocks; default lam = 5 (init_random: randn(1) + 1; the constraint is kept)."""
+    set_res, addf0, init_random, constraint = _common(kwargs)
+    blocks = []
+    for _ in range(num_blocks):
+        if init_random:
+            a_aff, b_aff = numpy.random.randn(2)
+            init_lam = numpy.random.randn(1) + 1.
+        else:
+            a_aff, b_aff = 1.0, 0.0
+            init_lam = 5.0
+        blocks.append(("inverseboxcox", {"init_lam": init_lam, "add_init_f0": addf0, "constraint": constraint}))
+        blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
+    return blocks
+
+
+def ArcSL(num_blocks, **kwargs):
+    """[arcsinh, affine] x num_blocks.  randn(4) is drawn for the arcsinh parameters with or without init_random."""
+    set_res, addf0, init_random, _ = _common(kwargs)
+    blocks = []
+    for _ in range(num_blocks):
+        if init_random:
+            a_aff, b_aff = numpy.random.randn(2)
+            a_arc, b_arc, c_arc, d_arc = numpy.random.randn(4)
+        else:
+            a_aff, b_aff = 1.0, 0.0
+            a_arc, b_arc, c_arc, d_arc = numpy.random.randn(4)
+            b_arc += 1
+            d_arc += 1
+        blocks.append(("arcsinh", {"init_a": a_arc, "init_b": b_arc, "init_c": c_arc, "init_d": d_arc,
+                                   "add_init_f0": addf0, "set_restrictions": set_res}))
+        blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
+    return blocks
+
+
+def Affine(num_blocks, **kwargs):
+    """[affine] x num_blocks; default a=1, b=0."""
+    set_res, _, init_random, _ = _common(kwargs)
+    blocks = []
+    for _ in range(num_blocks):
+        a, b = numpy.random.randn(2) if init_random else (1.0, 0.0)
+        blocks.append(("affine", {"init_a": a, "init_b": b, "set_restrictions": set_res}))
+    return blocks
+
+
+CHAINS = ("SAL_BCL", "SAL_InvBCL", "SAL_AL", "BCL_AL", "InvBCL_AL")
+
+
+def build_chain(flow_combination, num_blocks, **kwargs):
+    """num_blocks x the pair of generators a chain name lists, one block of each (SAL_BCL = SAL(1) + BoxCoxL(1), ...).
+    The chains with a Box-Cox generator read kwargs['constraint'] (a KeyError without it, as in the reference)."""
+    if flow_combination not in CHAINS:
+        raise ValueError("unknown flow combination {} (one of {})".format(flow_combination, ", ".join(CHAINS)))
+    blocks = []
+    if flow_combination == "SAL_AL":
+        for _ in range(num_blocks):
+            blocks.extend(SAL(1))
+            blocks.extend(ArcSL(1))
+        return blocks
+    constraint = kwargs["constraint"]
+    for _ in range(num_blocks):
+        if flow_combination == "SAL_BCL":
+            blocks.extend(SAL(1))
+            blocks.extend(BoxCoxL(1, constraint=constraint))
+        elif flow_combination == "SAL_InvBCL":
+            blocks.extend(SAL(1))
+            blocks.extend(InverseBoxCoxL(1, constraint=constraint))
+        elif flow_combination == "BCL_AL":
+            blocks.extend(BoxCoxL(1, constraint=constraint))
+            blocks.extend(ArcSL(1))
+        else:
+            blocks.extend(InverseBoxCoxL(1, constraint=constraint))
+            blocks.extend(ArcSL(1))
     return blocks

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtgp_hip.so")
 
 FLOW_AFFINE, FLOW_SAL, FLOW_STEPTANH = 0, 1, 2
+FLOW_ARCSINH, FLOW_BOXCOX, FLOW_INV_BOXCOX = 3, 4, 5
 FLAG_RESTRICT, FLAG_ADD_F0, FLAG_PER_ROW = 1, 2, 4
 LIK_GAUSS, LIK_FLOW = 0, 1
 

@@ -5,7 +5,9 @@ sequence), running on the MI355X kernels:
 
 `--dataset synthetic_power|synthetic_boston` uses seeded data of the same shape (the CSVs are the
 reference's data files; point $TGP_DATA_ROOT at them for the real runs).  `--epochs` shortens the 15000-epoch
-recipe for smoke runs.
+recipe for smoke runs.  `--flow_arch` (with `--num_blocks`, `--num_steps`) replaces the per-dataset flow of the recipe
+by any generator of flows.py -- SAL, StepTanhL, ArcSL, BoxCoxL, InverseBoxCoxL, Affine -- or build_chain name (SAL_BCL,
+SAL_InvBCL, SAL_AL, BCL_AL, InvBCL_AL); left out, each falls back to the recipe's value.
 """
 import argparse
 
@@ -15,7 +17,7 @@ import torch
 from . import config as cg
 from .data import return_dataset
 from .flow import instance_flow
-from .flows import SAL, StepTanhL
+from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
 from .likelihoods import GaussianLinearMean, GaussianNonLinearMean
@@ -30,6 +32,8 @@ HYPER = {
     ("TGP", "boston"): dict(arch="StepTanhL", blocks=10, steps=2),
     ("TGP", "power"): dict(arch="SAL", blocks=2, steps=None),
 }
+FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
+_PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
 
 def main(argv=None):
@@ -39,8 +43,13 @@ def main(argv=None):
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
+    ap.add_argument("--flow_arch", choices=FLOW_ARCHS, default=None, help="flow generator (default: the recipe's)")
+    ap.add_argument("--num_blocks", type=int, default=None, help="flow blocks (default: the recipe's)")
+    ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
+    if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
+        ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
     cg.device = "cuda:0"
     cg.set_maximum_precission()
@@ -51,13 +60,22 @@ def main(argv=None):
 
     flow_specs = None
     if args.model != "SVGP":
-        hp = HYPER[(args.model, base)]
+        hp = dict(HYPER[(args.model, base)])
+        for key, val in (("arch", args.flow_arch), ("blocks", args.num_blocks), ("steps", args.num_steps)):
+            if val is not None:
+                hp[key] = val
+        if hp["arch"] == "StepTanhL" and hp["steps"] is None:
+            ap.error("--flow_arch StepTanhL needs --num_steps")
         rest = {"input_dependent": args.model == "ID_TGP", "input_dim": Dx, "num_hidden_layers": hp.get("layers"),
                 "batch_norm": hp.get("BN"), "dropout": hp.get("DR"), "hidden_dim": hp.get("H"),
                 "hidden_activation": hp.get("act"), "inference": "MC_dropout"}
         rest = {k: v for k, v in rest.items() if v is not None}
         if hp["arch"] == "SAL":
             flow_specs = SAL(hp["blocks"], **rest)
+        elif hp["arch"] in _PLAIN_GENERATORS:
+            flow_specs = _PLAIN_GENERATORS[hp["arch"]](hp["blocks"])
+        elif hp["arch"] in CHAINS:
+            flow_specs = build_chain(hp["arch"], hp["blocks"], constraint=None)
         else:
             def random_flow_fn():
                 return instance_flow(StepTanhL(hp["blocks"], hp["steps"], add_f0=True))
