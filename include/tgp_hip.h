@@ -99,6 +99,11 @@ extern "C" {
 #define TGP_LIK_GAUSS 0 /* GaussianLinearMean.expected_log_prob, likelihoods/GaussianLinearMean.py:60-87       */
 #define TGP_LIK_FLOW 1  /* GaussianNonLinearMean.expected_log_prob, likelihoods/GaussianNonLinearMean.py:64-150 */
 #define TGP_LIK_ADJOINT 2 /* internal to tgp_qf_moments_bwd_f64: no likelihood, the adjoints of mu, v are inputs */
+/* Bernoulli.expected_log_prob / marginal_moments, likelihoods/Bernoulli.py: probit link through the flow,
+ * log p(y | f0) = y log Phi(G(f0)) + (1 - y) log Phi(-G(f0)), y in [0, 1], Gauss-Hermite over q(f0) (S, xs, wn required).
+ * log_var_noise stays a required pointer; its value is ignored and its gradient is written as 0.  The training step always
+ * takes the general-M path.  tgp_predict_f64: m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P). */
+#define TGP_LIK_BERNOULLI 3
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -185,6 +190,10 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 /* Same for a call that passes tgp_model.plan = `plan` (a forced chunk size changes the general-M path's buffers). */
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
+
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI training step runs on the general-M path at every M. */
+size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
+                               int32_t kernel, int32_t plan, int32_t lik);
 
 /* One fused ELBO evaluation with gradients: replaces sparse_MF_SP.ELBO (models/sparse_MF_SP.py:552-598)
  * + loss.backward() (trainers/trainer_base.py:341) for one minibatch shard.
@@ -300,7 +309,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
                       void* stream);
 
 /* TGP Gauss-Hermite expected log-likelihood through the flow (likelihoods/GaussianNonLinearMean.py:64-150),
- * with gradients w.r.t. mu, v, theta, rowp, log_var_noise.  out[0] = ELL, out[1] = dELL/dlog_var_noise. */
+ * with gradients w.r.t. mu, v, theta, rowp, log_var_noise.  out[0] = ELL, out[1] = dELL/dlog_var_noise.
+ * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -322,7 +332,7 @@ int tgp_flow_logdet_f64(const tgp_model* model, const double* f, int32_t S, int3
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written). */
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI: see its #define; Y_std is ignored. */
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream);
 

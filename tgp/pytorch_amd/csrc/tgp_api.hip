@@ -32,7 +32,7 @@ static int check_model(const tgp_model* m, bool need_lik) {
   if (m->M > TGP_BIG_MAX_M) return TGP_E_UNSUPPORTED;
   if (m->kernel != TGP_KERNEL_SCALE_RBF && m->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
   if (!m->Z || !m->raw_ls || !m->raw_os || !m->m || !m->Lam || !m->log_var_noise) return -1;
-  if (need_lik && m->lik == TGP_LIK_FLOW) {
+  if (need_lik && (m->lik == TGP_LIK_FLOW || m->lik == TGP_LIK_BERNOULLI)) {
     if (m->S < 1 || m->nblk < 0 || !m->xs || !m->wn) return -1;
     if (m->nblk > 0 && !m->program) return -1;
     if (m->P > 0 && !m->theta) return -1;
@@ -109,6 +109,15 @@ size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int3
   return d * sizeof(double);
 }
 
+size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
+                               int32_t kernel, int32_t plan, int32_t lik) {
+  if (lik == TGP_LIK_BERNOULLI) {
+    const size_t big = big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan);
+    return big == 0 ? 0 : big * sizeof(double);
+  }
+  return tgp_workspace_bytes_plan(N, D, M, S, nblk, P, RP, kernel, plan);
+}
+
 int tgp_elbo_step_f64(const tgp_model* model, const double* X, const double* Y, const double* rowp, double* out,
                       const tgp_grads* grads, double* mu, double* v, int32_t* status, void* workspace,
                       size_t workspace_bytes, void* stream) {
@@ -125,20 +134,21 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
   if (!out) return -5;
   if (!grads || !grads->Z || !grads->raw_ls || !grads->raw_os || !grads->m || !grads->Lam || !grads->log_var_noise)
     return -6;
-  if (model->P > 0 && model->lik == TGP_LIK_FLOW && !grads->theta) return -6;
+  const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;   // quadrature through the flow
+  if (model->P > 0 && flowed && !grads->theta) return -6;
   if (model->RP > 0 && !grads->rowp) return -6;
   if ((mu == nullptr) != (v == nullptr)) return -7;
   if (!status) return -9;
   if (!workspace) return -10;
-  const int nblk = model->lik == TGP_LIK_FLOW ? model->nblk : 0;
-  const int P = model->lik == TGP_LIK_FLOW ? model->P : 0;
-  const int RP = model->lik == TGP_LIK_FLOW ? model->RP : 0;
+  const int nblk = flowed ? model->nblk : 0;
+  const int P = flowed ? model->P : 0;
+  const int RP = flowed ? model->RP : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* ws = static_cast<double*>(workspace);
   tgp_model md = *model;
   md.nblk = nblk; md.P = P; md.RP = RP;
   FlowProg fp;
-  if (int rc = make_prog(&md, model->lik == TGP_LIK_FLOW, fp)) return rc;
+  if (int rc = make_prog(&md, flowed, fp)) return rc;
   md.program = nullptr;  // kernels use the by-value copy
   AdamDev ad;
   if (adam != nullptr) {
@@ -159,7 +169,8 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
     ad.ln_b1 = log(adam->beta1); ad.ln_b2 = log(adam->beta2); ad.sign = adam->maximize ? -1.0 : 1.0;
     ad.step_dev = adam->step_dev;
   }
-  bool general = model->M > TGP_FUSED_MAX_M || model->kernel != TGP_KERNEL_SCALE_RBF;
+  // (the fused row kernels have no Bernoulli likelihood: those steps take the general-M path at every M, as MATERN32 does)
+  bool general = model->M > TGP_FUSED_MAX_M || model->kernel != TGP_KERNEL_SCALE_RBF || model->lik == TGP_LIK_BERNOULLI;
   if (!general && fp.nslots > 0) {
     // the fused path keeps the flow stack of a row block in LDS beside its operand tiles; a program that does not fit even
     // with one node in flight (TGP_E_LDS until round 5: M > 112 with the 5 x 6 tanh flow) takes the general-M path
@@ -406,6 +417,9 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
   if (int rc = make_prog(model, true, fp)) return rc;
   tgp_model md = *model;
   md.program = nullptr;
+  if (model->lik == TGP_LIK_BERNOULLI)
+    return launch_ell_bern(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
+                           static_cast<hipStream_t>(stream));
   return launch_ell_flow(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
 }
@@ -453,12 +467,13 @@ int tgp_flow_logdet_f64(const tgp_model* model, const double* f, int32_t S, int3
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream) {
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
-  if (model->lik == TGP_LIK_FLOW && (model->S < 1 || !model->xs || !model->wn)) return -1;
+  const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;
+  if (flowed && (model->S < 1 || !model->xs || !model->wn)) return -1;
   if (!mu) return -2;
   if (!v) return -3;
-  if (model->lik == TGP_LIK_FLOW && model->RP > 0 && !rowp) return -4;
+  if (flowed && model->RP > 0 && !rowp) return -4;
   FlowProg fp;
-  if (int rc = make_prog(model, model->lik == TGP_LIK_FLOW, fp)) return rc;
+  if (int rc = make_prog(model, flowed, fp)) return rc;
   tgp_model md = *model;
   md.program = nullptr;
   return launch_predict(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));

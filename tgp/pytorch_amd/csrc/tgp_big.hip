@@ -1991,6 +1991,13 @@ int launch_big_step(const tgp_model& md, const FlowProg& fp, const double* X, co
                                      ws + p.mub + c0, ws + p.vb + c0, slot + 2, g.rowp ? g.rowp + c0 * md.RP : nullptr,
                                      ws + p.likws, sf))
           return rc;
+      } else if (md.lik == TGP_LIK_BERNOULLI) {
+        tgp_model mc = md;
+        mc.N = nrows;
+        if (int rc = launch_ell_bern(mc, fp, Y + c0, ws + p.mu + c0, ws + p.v + c0, rowp ? rowp + c0 * md.RP : nullptr, slot,
+                                     ws + p.mub + c0, ws + p.vb + c0, slot + 2, g.rowp ? g.rowp + c0 * md.RP : nullptr,
+                                     ws + p.likws, sf))
+          return rc;
       } else if (md.lik == TGP_LIK_ADJOINT) {
         // tgp_qf_moments_bwd_f64: the adjoints are the caller's (mu_bar in the Y slot, v_bar in the rowp slot)
         hipError_t e = hipMemcpyAsync(ws + p.mub + c0, Y + c0, (size_t)nrows * sizeof(double), hipMemcpyDeviceToDevice, sf);

@@ -434,6 +434,171 @@ __global__ __launch_bounds__(256) void k_predict_x(tgp_model md, FlowProg fp, co
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Bernoulli likelihood, probit link (likelihoods/Bernoulli.py): log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g), g = G(f0)
+// ---------------------------------------------------------------------------------------------------
+
+// The node term shared by k_ell_bern and k_predict_bern.  With a = |g|, t = a / sqrt 2:
+//   Phi(-a) = erfc(t) / 2 = erfcx(t) exp(-a^2 / 2) / 2      log Phi(-a) = log(erfcx(t) / 2) - a^2 / 2
+//   Phi(a)  = 1 - erfc(t) / 2                                log Phi(a)  = log1p(-erfc(t) / 2)
+//   lambda(z) = phi(z) / Phi(z):  lambda(-a) = sqrt(2 / pi) / erfcx(t),  lambda(a) = phi(a) / Phi(a)
+// Every quantity stays finite and accurate however large |g| is (the reference forms Phi first: its BCELoss clamps the log
+// at -100 once |g| passes ~8).  lp = y log Phi(g) + (1 - y) log Phi(-g), dg = d lp / dg = y lambda(g) - (1 - y) lambda(-g);
+// pp / pm (optional) = Phi(g) / Phi(-g).
+struct BernNode { double lp, dg, pp, pm; };
+__device__ inline BernNode bern_node(double g, double y) {
+  const double a = fabs(g), t = a * 0.70710678118654752440;
+  const double ec = erfc(t), ex = erfcx(t);
+  const double phia = 0.39894228040143267794 * exp(-0.5 * a * a);   // phi(a)
+  const double lp_hi = log1p(-0.5 * ec);                              // log Phi(a)
+  const double lp_lo = log(0.5 * ex) - 0.5 * a * a;                   // log Phi(-a)
+  const double lam_hi = phia / (1.0 - 0.5 * ec);                      // lambda(a)
+  const double lam_lo = 0.79788456080286535588 / ex;                  // lambda(-a)
+  const bool pos = g >= 0.0;
+  BernNode r;
+  r.lp = y * (pos ? lp_hi : lp_lo) + (1.0 - y) * (pos ? lp_lo : lp_hi);
+  r.dg = y * (pos ? lam_hi : lam_lo) - (1.0 - y) * (pos ? lam_lo : lam_hi);
+  r.pp = pos ? 1.0 - 0.5 * ec : 0.5 * ec;
+  r.pm = pos ? 0.5 * ec : 1.0 - 0.5 * ec;
+  return r;
+}
+
+// Expected log-likelihood through the flow with gradients: the lane layout, node batching, checkpointed flow sweeps and
+// partial-sum slots of k_ell_flow; part[1] (the noise adjoint there) is 0.  q(f) variances below 0 count as 0
+// (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0.
+template <int LPR, int NBX>
+__global__ __launch_bounds__(256) void k_ell_bern(tgp_model md, FlowProg fp, const double* __restrict__ Y,
+                                                   const double* __restrict__ mu, const double* __restrict__ v,
+                                                   const double* __restrict__ rowp, double* __restrict__ part,
+                                                   double* __restrict__ g_mu, double* __restrict__ g_v,
+                                                   double* __restrict__ g_rowp) {
+  constexpr int NB = NBX & (TGP_FLOWX - 1);
+  constexpr bool X = NBX & TGP_FLOWX;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* sm = reinterpret_cast<double*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = md.P, RP = md.RP;
+  const int nb = fp.nblk > 0 ? fp.nblk : 1;
+  constexpr int RW = 64 / LPR;                              // rows per wave
+  double* stack = sm;                                       // nblk * NB * 256: block inputs (checkpoint mode)
+  double* accw = stack + (size_t)nb * NB * 256;             // 4 waves x P
+  double* accr = accw + (size_t)4 * (P > 0 ? P : 1);        // RP * 256
+  double* red = accr + (size_t)RP * 256;                    // 16
+  double* tp = red + 16;                                    // P+2
+  double* tg = tp + (P + 2) / 2 * 2;                        // P+2
+  double* ti = tg + (P + 2) / 2 * 2;                        // P+2
+  for (int i = tid; i < 4 * (P > 0 ? P : 1) + RP * 256; i += 256) accw[i] = 0.0;
+  flow_params_lds<X>(md, fp, tp, tg, ti);
+  const int qn = lane / RW;
+  const int n = blockIdx.x * (4 * RW) + wave * RW + (lane % RW);
+  auto group_sum = [&](double x) {
+#pragma unroll
+    for (int o = RW; o < 64; o <<= 1) x += __shfl_xor(x, o);
+    return x;
+  };
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
+  double ellp = 0.0, cm = 0.0, cv = 0.0;
+  const double vn = v[nc] > 0.0 ? v[nc] : 0.0;
+  const double m_ = mu[nc], sq = sqrt(2.0 * vn), y = Y[nc];
+  const double* rp = rowp ? rowp + (size_t)nc * RP : nullptr;
+  double* aw = accw + (size_t)wave * (P > 0 ? P : 1);
+  for (int s0 = 0; s0 < md.S; s0 += LPR * NB) {
+    double f[NB], c[NB], xsn[NB], wsn[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      const int s = s0 + LPR * u + qn, sc = s < md.S ? s : md.S - 1;
+      xsn[u] = md.xs[sc];
+      wsn[u] = (valid && s < md.S) ? md.wn[sc] : 0.0;
+      f[u] = m_ + sq * xsn[u];
+    }
+    flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      const BernNode b = bern_node(f[u], y);
+      ellp += wsn[u] * b.lp;
+      c[u] = md.scale * wsn[u] * b.dg;
+    }
+    flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
+#pragma unroll
+    for (int u = 0; u < NB; ++u) { cm += c[u]; cv += c[u] * xsn[u]; }
+  }
+  cm = group_sum(cm);
+  cv = group_sum(cv);
+  for (int j = 0; j < RP; ++j) {
+    const double a = group_sum(accr[(size_t)j * 256 + tid]);
+    if (valid && qn == 0 && g_rowp) g_rowp[(size_t)n * RP + j] = a;
+  }
+  if (valid && qn == 0) {
+    if (g_mu) g_mu[n] = cm;
+    if (g_v) g_v[n] = vn > 0.0 ? cv / sq : 0.0;
+  }
+  ellp = wave_sum(ellp);
+  if (lane == 0) red[wave] = ellp;
+  __syncthreads();
+  double* pb = part + (size_t)blockIdx.x * (2 + P);
+  if (tid == 0) {
+    pb[0] = md.scale * (red[0] + red[1] + red[2] + red[3]);
+    pb[1] = 0.0;
+  }
+  for (int j = tid; j < P; j += 256) pb[2 + j] = (accw[j] + accw[P + j]) + (accw[2 * P + j] + accw[3 * P + j]);
+}
+
+// Predictive probability per row: P = Phi(mu / sqrt(1 + v)) for the empty program (R&W eq. 3.80, Bernoulli.py
+// marginal_moments), else sum_s w_s Phi(G(mu + sqrt(2 v) x_s)) with the row's own v, clamped to [0, 1].
+// m1 = P, m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (no constant).  X: the extended kind set.
+template <bool X>
+__global__ __launch_bounds__(256) void k_predict_bern(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                       const double* __restrict__ v, const double* __restrict__ rowp,
+                                                       const double* __restrict__ Y, double* __restrict__ m1o,
+                                                       double* __restrict__ m2o, double* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  flow_params_lds<X>(md, fp, tp, tg);
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= md.N) return;
+  const double y = (logp && Y) ? Y[n] : 0.0;
+  double P1 = 0.0, P0 = 0.0;   // P(y = 1), P(y = 0), each summed on its own (no 1 - P cancellation)
+  double lp = 0.0;
+  bool lp_done = false;
+  if (fp.nblk == 0) {
+    // closed form: the node term gives log P and log(1 - P) without forming P (finite however far out mu / sqrt(1 + v) is)
+    const BernNode b = bern_node(mu[n] / sqrt(1.0 + v[n]), y);
+    P1 = b.pp;
+    P0 = b.pm;
+    lp = b.lp;
+    lp_done = true;
+  } else {
+    FlowDev F{fp.blk, fp.nblk, tp, tg};
+    const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
+    const double vn = v[n] > 0.0 ? v[n] : 0.0;
+    const double m_ = mu[n], sq = sqrt(2.0 * vn);
+    constexpr int NB = 4;
+    for (int s0 = 0; s0 < md.S; s0 += NB) {
+      double g[NB], der[NB], wsn[NB];
+      const double* rpn[NB];
+      TGP_EACH(u, NB) {
+        const int s = s0 + u < md.S ? s0 + u : md.S - 1;
+        g[u] = m_ + sq * md.xs[s];
+        wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
+        rpn[u] = rp;
+      }
+      flow_forward_n<NB, false, X>(F, g, rpn, der);
+      TGP_EACH(u, NB) {
+        const BernNode b = bern_node(g[u], 0.0);
+        P1 += wsn[u] * b.pp;
+        P0 += wsn[u] * b.pm;
+      }
+    }
+    P1 = fmin(fmax(P1, 0.0), 1.0);
+    P0 = fmin(fmax(P0, 0.0), 1.0);
+  }
+  if (m1o) m1o[n] = P1;
+  if (m2o) m2o[n] = P1 * P0;
+  if (logp && Y) logp[n] = lp_done ? lp : (y != 0.0 ? y * log(P1) : 0.0) + (y != 1.0 ? (1.0 - y) * log(P0) : 0.0);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics; dsp/trainers/optimizers.py:12)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_adam(double* __restrict__ p, const double* __restrict__ g,
@@ -550,16 +715,24 @@ static int flow_lds(const tgp_model& md, int nblk, int NB, size_t* bytes) {
   return *bytes > 160 * 1024 - 1024 ? TGP_E_LDS : 0;
 }
 
+// lanes per row, nodes in flight per lane and dynamic LDS of k_ell_flow / k_ell_bern
+static int ell_plan(const tgp_model& md, const FlowProg& fp, int* lpr, int* nbn, size_t* lds) {
+  const int LPR = ell_flow_lpr(md.N);
+  int NB = LPR == 4 ? (md.S > 16 ? 8 : 4) : (LPR == 16 ? (md.S > 32 ? 4 : (md.S > 16 ? 2 : 1)) : (md.S > 64 ? 4 : (md.S > 32 ? 2 : 1)));
+  while (NB > 1 && (flow_lds(md, fp.nblk, NB, lds) != 0 || *lds > 120 * 1024)) NB >>= 1;
+  *lpr = LPR;
+  *nbn = NB;
+  return flow_lds(md, fp.nblk, NB, lds);
+}
+
 int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws,
                     hipStream_t st) {
   // nodes in flight per lane: all of the lane's nodes when the checkpoint stack fits (the per-step wave reductions of
   // the shared-parameter partials are then paid once), else fewer
   size_t lds = 0;
-  const int LPR = ell_flow_lpr(md.N);
-  int NB = LPR == 4 ? (md.S > 16 ? 8 : 4) : (LPR == 16 ? (md.S > 32 ? 4 : (md.S > 16 ? 2 : 1)) : (md.S > 64 ? 4 : (md.S > 32 ? 2 : 1)));
-  while (NB > 1 && (flow_lds(md, fp.nblk, NB, &lds) != 0 || lds > 120 * 1024)) NB >>= 1;
-  if (int rc = flow_lds(md, fp.nblk, NB, &lds)) return rc;
+  int LPR = 0, NB = 0;
+  if (int rc = ell_plan(md, fp, &LPR, &NB, &lds)) return rc;
   const int rows = 256 / LPR;
   const int nb = (md.N + rows - 1) / rows;
   static size_t cur[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
@@ -597,6 +770,49 @@ int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, co
   return 0;
 }
 
+// k_ell_bern with launch_ell_flow's choice of lanes per row and nodes in flight (same instantiations)
+int launch_ell_bern(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
+                    double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st) {
+  size_t lds = 0;
+  int LPR = 0, NB = 0;
+  if (int rc = ell_plan(md, fp, &LPR, &NB, &lds)) return rc;
+  const int rows = 256 / LPR;
+  const int nb = (md.N + rows - 1) / rows;
+  static size_t cur[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  static size_t cur_x[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+#define ELLB_LAUNCH(lpr, nbv, slot)                                                                                           \
+  do {                                                                                                                        \
+    if (ext) {                                                                                                                \
+      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_bern<lpr, nbv | TGP_FLOWX>), lds, &cur_x[slot])) return rc;  \
+      hipLaunchKernelGGL((k_ell_bern<lpr, nbv | TGP_FLOWX>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu,    \
+                         g_v, g_rowp);                                                                                        \
+    } else {                                                                                                                  \
+      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_bern<lpr, nbv>), lds, &cur[slot])) return rc;               \
+      hipLaunchKernelGGL((k_ell_bern<lpr, nbv>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp);   \
+    }                                                                                                                         \
+  } while (0)
+  if (LPR == 4) {
+    if (NB == 8) ELLB_LAUNCH(4, 8, 0);
+    else if (NB == 4) ELLB_LAUNCH(4, 4, 1);
+    else if (NB == 2) ELLB_LAUNCH(4, 2, 2);
+    else ELLB_LAUNCH(4, 1, 3);
+  } else if (LPR == 16) {
+    if (NB == 4) ELLB_LAUNCH(16, 4, 4);
+    else if (NB == 2) ELLB_LAUNCH(16, 2, 5);
+    else ELLB_LAUNCH(16, 1, 6);
+  } else {
+    if (NB == 4) ELLB_LAUNCH(32, 4, 7);
+    else if (NB == 2) ELLB_LAUNCH(32, 2, 8);
+    else ELLB_LAUNCH(32, 1, 9);
+  }
+#undef ELLB_LAUNCH
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,
                      double* logdG, hipStream_t st, double* sum_out, double* ws) {
   const size_t total = (size_t)S * N;
@@ -618,7 +834,12 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
   const size_t lds = 2 * (size_t)(md.P + 2) * sizeof(double);
-  if (flow_prog_extended(fp.blk, fp.nblk))
+  if (md.lik == TGP_LIK_BERNOULLI) {
+    if (flow_prog_extended(fp.blk, fp.nblk))
+      hipLaunchKernelGGL(k_predict_bern<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+    else
+      hipLaunchKernelGGL(k_predict_bern<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+  } else if (flow_prog_extended(fp.blk, fp.nblk))
     hipLaunchKernelGGL(k_predict_x, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   else
     hipLaunchKernelGGL(k_predict, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);

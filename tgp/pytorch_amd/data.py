@@ -18,6 +18,7 @@ import torch
 from . import config as cg
 
 SHAPES = {"power": (9568, 4, 8611), "boston": (506, 13, 455)}
+BINARY_SHAPES = ("heart", "banknote")      # synthetic.BINARY_SHAPES: binary labels, see _binary_dataset
 
 
 class DeviceLoader:
@@ -122,6 +123,38 @@ def load_uci_split(base, seed, root):
             tr_idx, te_idx)
 
 
+def _binary_dataset(base, batch_size, use_validation, seed, options):
+    """synthetic_heart / synthetic_banknote (synthetic.binary_dataset): a seeded 90 / 10 split, X standardised by the
+    train split, labels left as they are (Y_std = 1)."""
+    from .synthetic import binary_dataset
+    if not options.get("split_from_disk", True):
+        raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
+    X, Y = binary_dataset(base)
+    n = X.shape[0]
+    perm = numpy.random.default_rng(seed).permutation(n)
+    n_tr = int(round(0.9 * n))
+    tr_idx, te_idx = perm[:n_tr], perm[n_tr:]
+    X_tr, Y_tr, X_te, Y_te = X[tr_idx], Y[tr_idx], X[te_idx], Y[te_idx]
+    X_va = Y_va = None
+    if use_validation is not None:
+        X_tr, Y_tr, X_va, Y_va = random_split_validation(X_tr, Y_tr, use_validation[0], use_validation[1])
+    X_tr, _, X_va, _, X_te, _, _ = standard_normalization(X_tr, Y_tr, X_va, Y_va, X_te, Y_te)
+    Y_std = numpy.ones(1)
+    t = lambda a: None if a is None else torch.tensor(a, dtype=cg.dtype)
+    X_tr, Y_tr, X_va, Y_va, X_te, Y_te = (t(a) for a in (X_tr, Y_tr, X_va, Y_va, X_te, Y_te))
+    shuffle = options.get("shuffle_train", True)
+    train = DeviceLoader(X_tr, Y_tr, batch_size, shuffle=shuffle, seed=cg.config_seed)
+    test = DeviceLoader(X_te, Y_te, batch_size)
+    loaders = [train, test]
+    if use_validation is not None:
+        loaders = [train, DeviceLoader(X_va, Y_va, batch_size, shuffle=shuffle, seed=cg.config_seed), test]
+    data_config = {"X_tr": X_tr, "Y_tr": Y_tr, "X_va": X_va, "Y_va": Y_va, "X_te": X_te, "Y_te": Y_te,
+                   "N_tr": X_tr.shape[0], "N_va": 0 if X_va is None else X_va.shape[0], "N_te": X_te.shape[0],
+                   "Dx": X_tr.shape[1], "Dy": 1, "Y_std": Y_std, "X_all": None, "Y_all": None,
+                   "train_idx": numpy.asarray(tr_idx), "test_idx": numpy.asarray(te_idx)}
+    return loaders, data_config
+
+
 def _synthetic(name, seed):
     n, d, _ = SHAPES[name]
     rng = numpy.random.default_rng(1234)
@@ -135,6 +168,8 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     options = options or {}
     synth = dataset_name.startswith("synthetic_")
     base = dataset_name.replace("synthetic_", "")
+    if synth and base in BINARY_SHAPES:
+        return _binary_dataset(base, batch_size, use_validation, seed, options)
     if (synth and base not in SHAPES) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))
     if not options.get("split_from_disk", True):

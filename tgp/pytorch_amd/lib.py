@@ -15,6 +15,7 @@ FLOW_AFFINE, FLOW_SAL, FLOW_STEPTANH = 0, 1, 2
 FLOW_ARCSINH, FLOW_BOXCOX, FLOW_INV_BOXCOX = 3, 4, 5
 FLAG_RESTRICT, FLAG_ADD_F0, FLAG_PER_ROW = 1, 2, 4
 LIK_GAUSS, LIK_FLOW = 0, 1
+LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 
 _dp = C.c_void_p
 
@@ -70,6 +71,7 @@ _SIGS = {
     "tgp_workspace_bytes": (C.c_size_t, [C.c_int32] * 7),
     "tgp_workspace_bytes_kernel": (C.c_size_t, [C.c_int32] * 8),
     "tgp_workspace_bytes_plan": (C.c_size_t, [C.c_int32] * 9),
+    "tgp_workspace_bytes_lik": (C.c_size_t, [C.c_int32] * 10),
     "tgp_kernel_matrix_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp, C.c_double, _dp, _dp]),
     "tgp_elbo_step_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.POINTER(TgpGrads), _dp, _dp, _dp, _dp,
                                     C.c_size_t, _dp]),

@@ -76,3 +76,41 @@ class GaussianNonLinearMean(_GaussianBase):
         m1, m2, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(),
                                 self._lvn().detach().reshape(-1)[:1].contiguous(), spec, theta, self.quad_points, rowp)
         return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
+
+
+class Bernoulli(nn.Module):
+    """p(y|G(f)) = Phi(G(f))^y Phi(-G(f))^(1-y), probit link, for binary classification (likelihoods/Bernoulli.py).
+    No parameters.  The quadrature over q(f0) runs in float64 on the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with
+    TGP_LIK_BERNOULLI), with log Phi evaluated in the tails instead of through Phi."""
+
+    def __init__(self):
+        super().__init__()
+        self.C = 2
+        self.quad_points = cg.quad_points
+
+    def sample_from_output(self, f, i, **kwargs):
+        probs = torch.special.ndtr(f)
+        return td.Bernoulli(probs=probs).sample().to(cg.dtype)
+
+    def _flow_inputs(self, flow, X, dev, with_grad=False):
+        return GaussianNonLinearMean._flow_inputs(self, flow, X, dev, with_grad)
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[y_n log Phi(G(f0)) + (1 - y_n) log Phi(-G(f0))]; Y (1, MB) labels in [0, 1], moments (1, MB)."""
+        assert len(flow) == 1, "Flow list must be size 1 for Bernoulli likelihood"
+        assert gauss_mean.size(0) == 1, "Binary classification just require one GP for both classes"
+        assert len(X.shape) == 3, 'Bad input X, expected (n_class,MB*S,Dx)'
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllBernoulliFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                              gauss_cov.reshape(-1).contiguous(), theta, rowp, spec, self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """P(y = 1) of shape (MB, 1): Phi(mu / sqrt(1 + v)) for the identity flow, else each row's own quadrature."""
+        assert len(flow) == 1, "Flow list must be size 1 for Bernoulli likelihood"
+        assert gauss_mean.size(0) == 1, "Binary classification just require one GP for both classes"
+        assert len(X.shape) == 3, 'Bad input X, expected (n_class,MB*S,Dx)'
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device)
+        lvn = torch.zeros(1, dtype=torch.float64, device=gauss_mean.device)
+        P, _, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(), lvn, spec, theta,
+                              self.quad_points, rowp, lik=ops.L.LIK_BERNOULLI)
+        return P.reshape(-1, 1)

@@ -8,6 +8,9 @@ reference's data files; point $TGP_DATA_ROOT at them for the real runs).  `--epo
 recipe for smoke runs.  `--flow_arch` (with `--num_blocks`, `--num_steps`) replaces the per-dataset flow of the recipe
 by any generator of flows.py -- SAL, StepTanhL, ArcSL, BoxCoxL, InverseBoxCoxL, Affine -- or build_chain name (SAL_BCL,
 SAL_InvBCL, SAL_AL, BCL_AL, InvBCL_AL); left out, each falls back to the recipe's value.
+`--likelihood bernoulli` trains a binary classifier (SVGP or TGP; the Bernoulli probit likelihood) on
+synthetic_heart / synthetic_banknote with the flows of the reference's classification script, and reports the test
+negative log-likelihood and accuracy.
 """
 import argparse
 
@@ -20,9 +23,9 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .likelihoods import GaussianLinearMean, GaussianNonLinearMean
+from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean
 from .models import sparse_MF_GP, sparse_MF_SP
-from .trainers import Trainer_SP_regression
+from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import KMEANS
 
 # code/exp_config.py:4-86
@@ -31,7 +34,11 @@ HYPER = {
     ("ID_TGP", "power"): dict(arch="SAL", blocks=3, steps=None, act="relu", layers=2, DR=0.25, BN=0, H=50),
     ("TGP", "boston"): dict(arch="StepTanhL", blocks=10, steps=2),
     ("TGP", "power"): dict(arch="SAL", blocks=2, steps=None),
+    # bash_scripts/launch_test_uci_medium-small_classification.sh
+    ("TGP", "heart"): dict(arch="SAL_InvBCL", blocks=1, steps=None),
+    ("TGP", "banknote"): dict(arch="BCL_AL", blocks=5, steps=None),
 }
+CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -39,15 +46,24 @@ _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": Inver
 def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
     ap.add_argument("--model", required=True, help="ID_TGP, TGP or SVGP")
-    ap.add_argument("--dataset", required=True, choices=["boston", "power", "synthetic_boston", "synthetic_power"])
+    ap.add_argument("--dataset", required=True,
+                    choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
     ap.add_argument("--flow_arch", choices=FLOW_ARCHS, default=None, help="flow generator (default: the recipe's)")
     ap.add_argument("--num_blocks", type=int, default=None, help="flow blocks (default: the recipe's)")
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli"], default="gaussian",
+                    help="gaussian: regression (default); bernoulli: binary classification, probit link")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
+    bern = args.likelihood == "bernoulli"
+    if bern and args.model == "ID_TGP":
+        ap.error("--likelihood bernoulli: SVGP or TGP only")
+    if bern != (args.dataset in CLASSIFICATION_DATASETS):
+        ap.error("--likelihood bernoulli goes with the classification data sets (%s), gaussian with the others"
+                 % ", ".join(CLASSIFICATION_DATASETS))
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
         ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
@@ -88,7 +104,9 @@ def main(argv=None):
             T_flow = instance_flow(flow_specs) if isinstance(flow_specs, list) else flow_specs
             flow_specs, _ = find_forward_params_input_dependent_flow(loaders[0], FLOW=T_flow, num_epochs=2000, noise_var=0.0)
 
-    if args.model == "SVGP":
+    if bern:
+        lik = Bernoulli()
+    elif args.model == "SVGP":
         lik = GaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False)
     else:
         lik = GaussianNonLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points)
@@ -111,11 +129,18 @@ def main(argv=None):
         sched.append([lr, 1e-5, "NNets"])
         specs[0].extend(sched)
     Y_std = (torch.ones((Dy,)) * dc["Y_std"]).to(cg.device)
-    trainer = Trainer_SP_regression(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
+    trainer_cls = Trainer_SP_classification if bern else Trainer_SP_regression
+    trainer = trainer_cls(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
                                     track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True)
     trainer.train(epochs=args.epochs, lr_ALL=lr, opt="adam", keep_parameter_groups=True,
                   optimisation_schedule=([1.0], specs), lr_groups=None)
     res = trainer.compute_metrics()
+    if bern:                         # (logL_train, acc_train, logL_valid, acc_valid, logL_test, acc_test)
+        print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, -res[4]))
+        print("Dataset {}, num inducing points {}, model {}, Test Accuracy {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, res[5]))
+        return res
     if args.model == "ID_TGP":       # the reference's result lines (main.py:309-324)
         print("Dataset {}, num inducing points {}, POINT ESTIMATE FLOW , Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
             args.dataset, args.num_inducing, -res[6], res[7]))

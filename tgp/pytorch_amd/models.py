@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
-from .likelihoods import GaussianLinearMean, GaussianNonLinearMean
+from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean
 from .utils import positive_transform
 
 DEFAULT_INIT = {"variational_distribution": {"variance_scale": 1.0, "mean_scale": 0.0}}
@@ -77,7 +77,10 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, GaussianNonLinearMean) else cg.quad_points
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli)) else cg.quad_points
+        if isinstance(likelihood, Bernoulli):
+            # the ABI's noise pointer: read by no Bernoulli kernel, gradient 0; a buffer, so model.parameters() is the reference's
+            self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
         self.is_whiten = is_whiten
 
         # inducing points (sparse_MF_SP.py:140-156)
@@ -124,11 +127,15 @@ class sparse_MF_SP(nn.Module):
             raise ops.L.TgpError("float64 only: call config.set_maximum_precission() before building the model "
                                  "(code/main.py:124)")
 
+    @property
+    def _is_bernoulli(self):
+        return isinstance(self.likelihood, Bernoulli)
+
     def _gp_params(self):
         k = self.covariance_function
+        lvn = self._bern_lvn if self._is_bernoulli else self.likelihood.log_var_noise.reshape(-1)[:1]
         return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.raw_outputscale.reshape(-1),
-                self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0],
-                self.likelihood.log_var_noise.reshape(-1)[:1])
+                self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], lvn)
 
     def _flow_inputs(self, X2d, with_grad, samples=1):
         """(FlowSpec or None, theta, rowp): shared scalars stacked into one vector, per-row parameters from the MLPs on the
@@ -201,7 +208,8 @@ class sparse_MF_SP(nn.Module):
         spec, theta, rowp = self._flow_inputs(X2, with_grad=True)
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
-                   global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel)
+                   global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
+                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else None)
         elbo, ell, kld = ops.ElboFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
         return elbo, ell, kld
 
@@ -237,12 +245,21 @@ class sparse_MF_SP(nn.Module):
                 # tgp_predict_f64 launch, then the mixture moments (:516-531)
                 S, MB = int(S_MC_NNet), X3.shape[1]
                 spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False, samples=S)
+                if self._is_bernoulli:
+                    # P of every (sample, row) in one tgp_predict_f64 launch, the MC mean per row (sparse_MF_SP.py:521-525)
+                    P, _, _ = ops.predict(mean_q_f.reshape(-1).repeat(S), cov_q_f.reshape(-1).repeat(S), self._bern_lvn, spec,
+                                          theta.detach() if theta is not None else None, self.quad_points, rowp,
+                                          lik=ops.L.LIK_BERNOULLI)
+                    self.train()
+                    return P.reshape(S, MB, 1).mean(0), None, mean_q_f, cov_q_f
                 lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
                 mY, cY, _ = ops.predict(mean_q_f.reshape(-1).repeat(S), cov_q_f.reshape(-1).repeat(S), lvn, spec,
                                         theta.detach() if theta is not None else None, self.quad_points, rowp)
                 mY, cY = mY.reshape(1, S, MB), cY.reshape(1, S, MB)       # (Dy, S, MB)
                 m1 = mY.mean(1)
                 m2 = (cY + mY ** 2).mean(1) - m1 ** 2
+            elif self._is_bernoulli:
+                m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X3), None
             else:
                 m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), diagonal=True,
                                                           flow=self.G_matrix, X=X3)
@@ -255,6 +272,18 @@ class sparse_MF_SP(nn.Module):
         MB = X.size(0)
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._require_gpu(X3)
+        if self._is_bernoulli:
+            # sum_n y log P + (1 - y) log(1 - P) in float64 (the reference takes it through float32 and
+            # compute_calibration_measures), P as predictive_distribution returns it (MC mean when fully Bayesian)
+            P, _, _, _ = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
+            assert torch.isfinite(P).all(), "Got saturated probabilities"
+            P = P.reshape(-1)
+            y = Y.reshape(-1).to(P.dtype)
+            with torch.no_grad():
+                lp = torch.where(y != 0, y * torch.log(P), torch.zeros_like(P)) + \
+                    torch.where(y != 1, (1 - y) * torch.log1p(-P), torch.zeros_like(P))
+            self.train()
+            return lp.sum().reshape(1), ([torch.stack((1.0 - P, P), dim=1)] if return_moments else None)
         predictive_params = None
         if return_moments:
             m1, m2, mean_q_f, cov_q_f = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)

@@ -65,11 +65,16 @@ def kernel_id(kernel):
     return int(kernel)
 
 
-def workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0):
+def workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_GAUSS):
     key = (N, D, M, S, nblk, P, RP, str(device), torch.cuda.current_stream().cuda_stream, kernel, int(plan))
+    if lik == L.LIK_BERNOULLI:          # general-M path at every M: its own buffer size (tgp_workspace_bytes_lik)
+        key += (lik,)
     buf = _ws_cache.get(key)
     if buf is None:
-        nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
+        if lik == L.LIK_BERNOULLI:
+            nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
+        else:
+            nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
         if nbytes == 0:
             raise L.TgpError("unsupported problem shape N=%d D=%d M=%d (this build: D<=16, M<=4096)" % (N, D, M))
         buf = torch.empty(nbytes // 8 + 16, dtype=torch.float64, device=device)
@@ -104,7 +109,8 @@ class FlowSpec:
         return FlowSpec(self.blocks, self.P, self.RP, device)
 
 
-def _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel=0, plan=0):
+def _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel=0, plan=0, lik=None):
+    """`lik` None: LIK_GAUSS without a flow, LIK_FLOW with one; LIK_BERNOULLI needs a FlowSpec (empty for SVGP)."""
     md = L.TgpModel()
     md.kernel = kernel_id(kernel)
     md.plan = int(plan)          # lib.PLAN_*: which of the equivalent kernels this call runs; 0 = the library's choice
@@ -119,19 +125,21 @@ def _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, fl
     else:
         xs, wn = gauss_hermite(S, X.device)
         keep += [xs, wn]
-        md.lik, md.S, md.nblk, md.P, md.RP = L.LIK_FLOW, int(S), flow.nblk, flow.P, flow.RP
+        md.lik, md.S, md.nblk, md.P, md.RP = L.LIK_FLOW if lik is None else int(lik), int(S), flow.nblk, flow.P, flow.RP
         md.program, md.xs, md.wn = flow.program_ptr, L.ptr(xs), L.ptr(wn)
         md.theta = L.ptr(theta) if flow.P > 0 else None
     return md, keep
 
 
 def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=None, rowp=None, S=None, jitter=0.0,
-              kl_scale=1.0, mb_global=None, want_moments=False, kernel="scale_rbf", plan=0):
+              kl_scale=1.0, mb_global=None, want_moments=False, kernel="scale_rbf", plan=0, lik=None):
     """One fused ELBO evaluation + all gradients on the GPU.  Returns (out[4], grads dict, status[8], (mu, v)); status[0..2] are the
     Cholesky words of include/tgp_hip.h, status[4..7] the in-launch hand-off words (zero before and after every call).
 
     out = [ELL_shard - KL, ELL_shard, KL, 0]; grads are d(ELL_shard - kl_scale*KL)/d(param).
-    `mb_global` = global minibatch size when X is a row shard (defaults to X.shape[0])."""
+    `mb_global` = global minibatch size when X is a row shard (defaults to X.shape[0]).
+    `lik` = lib.LIK_BERNOULLI: probit likelihood through `flow` (a FlowSpec, possibly empty); lvn is read by no kernel and
+    its gradient is 0."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -141,8 +149,10 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     N, D = X.shape
     M = m.numel()
     scale = float(N_total) / float(mb_global if mb_global is not None else N)
-    md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel, plan)
-    ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan)
+    if lik == L.LIK_BERNOULLI and flow is None:
+        raise L.TgpError("the Bernoulli likelihood needs a FlowSpec (an empty one for the identity flow)")
+    md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
+    ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     status = torch.zeros(8, dtype=torch.int32, device=dev)
     g = {"Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os),
@@ -214,11 +224,12 @@ class ElboFunction(torch.autograd.Function):
         out, g, status, _ = elbo_step_safe(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], flow=cfg.get("flow"),
                                            theta=theta, rowp=rowp, S=cfg.get("S"),
                                            kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
-                                           global_jitter=cfg.get("global_jitter"), kernel=cfg.get("kernel", "scale_rbf")) \
+                                           global_jitter=cfg.get("global_jitter"), kernel=cfg.get("kernel", "scale_rbf"),
+                                           lik=cfg.get("lik")) \
             if cfg.get("check_status", True) else \
             elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], flow=cfg.get("flow"), theta=theta,
                       rowp=rowp, S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
-                      kernel=cfg.get("kernel", "scale_rbf"))
+                      kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"))
         ctx.grads = g
         ctx.shapes = tuple(None if t is None else t.shape for t in (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
         cfg["last_status"] = status
@@ -527,6 +538,45 @@ def ell_flow(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     return {"ell": out[0], "g_lvn": out[1], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "g_rowp": grp}
 
 
+def ell_bernoulli(Y, mu, v, flow, theta, S, rowp=None, scale=1.0):
+    """Bernoulli (probit) quadrature ELL with gradients (likelihoods/Bernoulli.py expected_log_prob; tgp_ell_flow_f64 with
+    TGP_LIK_BERNOULLI).  Returns dict(ell, g_mu, g_v, g_theta, g_rowp)."""
+    lib = L.load()
+    Y, mu, v = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    dev, N = Y.device, Y.numel()
+    lvn = torch.zeros(1, dtype=torch.float64, device=dev)      # required pointer, not read
+    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=L.LIK_BERNOULLI)
+    ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    gmu, gv = torch.empty_like(mu), torch.empty_like(v)
+    gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
+    grp = torch.empty_like(rowp) if rowp is not None else None
+    L.check(lib.tgp_ell_flow_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
+                                 L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
+            "tgp_ell_flow_f64")
+    return {"ell": out[0], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "g_rowp": grp}
+
+
+class EllBernoulliFunction(torch.autograd.Function):
+    """ELL = Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) with autograd in (mu, v, theta, rowp)."""
+
+    @staticmethod
+    def forward(ctx, Y, mu, v, theta, rowp, flow, S):
+        res = ell_bernoulli(Y, mu.detach(), v.detach(), flow, theta.detach() if theta is not None else None, S,
+                            rowp.detach() if rowp is not None else None)
+        ctx.save_for_backward(res["g_mu"], res["g_v"], res["g_theta"],
+                              res["g_rowp"] if res["g_rowp"] is not None else res["g_mu"])
+        ctx.has = (theta is not None, rowp is not None)
+        return res["ell"].reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        gmu, gv, gth, grp = ctx.saved_tensors
+        g = g.reshape(())
+        return (None, g * gmu, g * gv, g * gth if ctx.has[0] else None, g * grp if ctx.has[1] else None, None, None)
+
+
 class EllGaussFunction(torch.autograd.Function):
     """ELL = GaussianLinearMean.expected_log_prob (likelihoods/GaussianLinearMean.py:60-87) with autograd in (mu, v,
     log_var_noise) -- the reference's method is plain torch code, differentiable wherever it is called; tgp_ell_gauss_f64
@@ -600,8 +650,9 @@ def flow_logdet(f, flow, theta, rowp=None, want_G=False):
     return out[0], G
 
 
-def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0):
-    """Predictive moments m1, m2 and per-row test log-likelihood kernel (see tgp_predict_f64)."""
+def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None):
+    """Predictive moments m1, m2 and per-row test log-likelihood kernel (see tgp_predict_f64).  lik = lib.LIK_BERNOULLI:
+    m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (`flow` a FlowSpec, possibly empty)."""
     lib = L.load()
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
@@ -612,7 +663,7 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
         md.log_var_noise = L.ptr(lvn)
         keep = None
     else:
-        md, keep = _flow_model(N, S, flow, theta, lvn, dev)
+        md, keep = _flow_model(N, S, flow, theta, lvn, dev, lik=L.LIK_FLOW if lik is None else int(lik))
     m1, m2 = torch.empty_like(mu), torch.empty_like(mu)
     logp = torch.empty_like(mu) if Y is not None else None
     Yc = _c(Y.reshape(-1), "Y") if Y is not None else None

@@ -62,6 +62,23 @@ def flow_program(flow, seed=0):
     return fp.blocks, fp.vector(), fp.row_cols
 
 
+# binary classification stand-ins of the paper's UCI classification sets: (rows, inputs)
+BINARY_SHAPES = {"heart": (299, 12), "banknote": (1372, 4)}
+
+
+def binary_dataset(name, seed=0):
+    """Seeded binary data set of `name`'s shape: X ~ N(0, 1), latent f = 8 (sin(X w) + 0.5 x0), y ~ Bernoulli(Phi(f)).
+    Returns numpy float64 X (n, d) and Y (n, 1) with labels in {0, 1}."""
+    n, d = BINARY_SHAPES[name]
+    rng = np.random.default_rng(7919 + 31 * seed + n)
+    X = rng.standard_normal((n, d))
+    w = rng.standard_normal(d) / math.sqrt(d)
+    f = 8.0 * (np.sin(X @ w) + 0.5 * X[:, 0])
+    p = 0.5 * np.array([math.erfc(-v / math.sqrt(2.0)) for v in f])
+    Y = (rng.uniform(size=n) < p).astype(np.float64)
+    return X, Y.reshape(-1, 1)
+
+
 def synthetic_problem(N, D, M, seed=0, flow="sal2", S=32, perturb=True):
     """X ~ N(0,1); Y = zscore(sin(Xw) + 0.1 x0^2 + 0.05 eps); Z = M rows of a seeded permutation; lengthscale 2,
     outputscale 2, noise 0.05; q(u): m ~ 0.5 N(0,1), Lq = sqrt(1e-5) I + 0.05 N(0,1) (dense -- the strict upper

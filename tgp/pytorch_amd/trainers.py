@@ -323,3 +323,38 @@ class Trainer_SP_regression:
         out += list(self._loader_metrics(self.valid_loader)) if self.is_valid else [0.0, 0.0, 0.0]
         out += list(self._loader_metrics(self.test_loader)) if self.is_test else [0.0, 0.0, 0.0]
         return tuple(out)
+
+
+class Trainer_SP_classification(Trainer_SP_regression):
+    """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
+    the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood."""
+
+    def _engine_for(self, groups, lr_ALL, opt):
+        from .likelihoods import Bernoulli
+        if isinstance(self.model.likelihood, Bernoulli):
+            return None
+        return super()._engine_for(groups, lr_ALL, opt)
+
+    def performance_metrics(self, X, Y):
+        """(sum_n log p(y_n), number of correct labels): argmax over [1 - P, P], a tie goes to class 0."""
+        self.model.set_is_training(False)
+        logp, (probs,) = self.model.test_log_likelihood(X, Y, return_moments=True, Y_std=self.Y_std.to(X.device),
+                                                        S_MC_NNet=self.S_test if self.model.fully_bayesian else None)
+        pred = probs.argmax(dim=1)                    # first maximum: class 0 on a tie
+        correct = (pred == Y.reshape(-1).to(pred.dtype)).sum().item()
+        return float(logp.reshape(-1)[0]), correct
+
+    def _loader_metrics(self, loader):
+        tot, lp, ok = 0, 0.0, 0
+        for x, y in loader:
+            x, y = x.to(cg.device), y.to(cg.device)
+            a, b = self.performance_metrics(x, y)
+            lp, ok, tot = lp + a, ok + b, tot + x.size(0)
+        return lp / tot, ok / tot
+
+    def compute_metrics(self):
+        """(logL_train, acc_train, logL_valid, acc_valid, logL_test, acc_test): logL is the mean per-row log p(y)."""
+        out = list(self._loader_metrics(self.train_loader))
+        out += list(self._loader_metrics(self.valid_loader)) if self.is_valid else [0.0, 0.0]
+        out += list(self._loader_metrics(self.test_loader)) if self.is_test else [0.0, 0.0]
+        return tuple(out)
