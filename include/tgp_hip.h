@@ -104,6 +104,13 @@ extern "C" {
  * log_var_noise stays a required pointer; its value is ignored and its gradient is written as 0.  The training step always
  * takes the general-M path.  tgp_predict_f64: m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P). */
 #define TGP_LIK_BERNOULLI 3
+/* WarpedGaussianLinearMean (likelihoods/WarpedGaussianLinearMean.py): the flow T is applied to the TARGETS,
+ * log p(y | f) = log N(T(y) | f, exp(log_var_noise)) + log T'(y).  model->program / theta describe T (shared parameters only:
+ * RP must be 0 in the training and likelihood entries, TGP_E_UNSUPPORTED otherwise); S, xs, wn serve prediction only.  The
+ * training step is [t = T(Y)] -> the unchanged Gaussian step on t (either path) -> [theta's gradient, + scale sum log T'(y) on
+ * out[0], out[1]]; tgp_elbo_step_adam_f64 applies the update in ONE separate launch after them.  An empty program gives
+ * TGP_LIK_GAUSS's results bit for bit. */
+#define TGP_LIK_WARPED 4
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -329,10 +336,30 @@ size_t tgp_flow_logdet_workspace_bytes(int32_t S, int32_t N);
 int tgp_flow_logdet_f64(const tgp_model* model, const double* f, int32_t S, int32_t N, const double* rowp, double* G,
                         double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Warped-GP likelihood (likelihoods/WarpedGaussianLinearMean.py:65-85) with gradients, one launch:
+ *   out[0] = scale sum_n [Gaussian closed form at t_n = T(y_n)] + scale sum_n log T'(y_n),
+ *   out[1] = d out[0] / d log_var_noise,   out[2] = scale sum_n log T'(y_n);
+ *   g_mu, g_v (N), g_theta (P), t_out (N) = T(Y): each optional (NULL to skip).  Fixed summation order (per-workgroup partials
+ *   added by the last workgroup to arrive): bit-reproducible.  model: N, nblk, P, program, theta, log_var_noise, scale. */
+size_t tgp_ell_warp_workspace_bytes(int32_t N, int32_t P);
+int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, double* out, double* g_mu,
+                     double* g_v, double* g_theta, double* t_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Inverse of a flow, x = T^-1(t) for t of shape (S,N) (row n uses rowp[n,:]; CompositeFlow.inverse, models/flow.py:160-170):
+ * blocks are inverted last to first, in closed form where there is one (AFFINE, SAL, ARCSINH, BOXCOX <-> INV_BOXCOX, all
+ * without TGP_FLAG_ADD_F0), else by a bracketed Newton iteration on that block (bracket grown by doubling, Newton steps,
+ * bisection whenever a step leaves the bracket, at most 128 evaluations per phase).  status (device int32[1], zeroed by the
+ * caller): the call ADDS the number of elements that did not reach the stopping rule. */
+int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int32_t N, const double* rowp, double* x,
+                         int32_t* status, void* stream);
+
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI: see its #define; Y_std is ignored. */
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI: see its #define; Y_std is ignored.
+ * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
+ * (WarpedGaussianLinearMean.marginal_moments), logp = log N(T(y) | mu, v + noise) + log T'(y) - log Y_std, the exact warped
+ * predictive density WITH its constant (float32 pi as everywhere); rowp is ignored. */
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream);
 

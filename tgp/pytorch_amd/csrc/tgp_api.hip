@@ -115,6 +115,12 @@ size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32
     const size_t big = big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan);
     return big == 0 ? 0 : big * sizeof(double);
   }
+  if (lik == TGP_LIK_WARPED) {
+    // the Gaussian step's workspace, then t = T(Y), mu, v (N each) and the partials of k_ell_warp
+    const size_t g = tgp_workspace_bytes_plan(N, D, M, S, 0, 0, 0, kernel, plan);
+    if (g == 0 || N < 1 || P < 0) return 0;
+    return (rup(g / sizeof(double), 2) + 3 * (size_t)N + warp_workspace_doubles(N, P)) * sizeof(double);
+  }
   return tgp_workspace_bytes_plan(N, D, M, S, nblk, P, RP, kernel, plan);
 }
 
@@ -126,7 +132,74 @@ int tgp_elbo_step_f64(const tgp_model* model, const double* X, const double* Y, 
 
 static int elbo_step_impl(const tgp_model* model, const double* X, const double* Y, const double* rowp, double* out,
                           const tgp_grads* grads, double* mu, double* v, int32_t* status, void* workspace,
+                          size_t workspace_bytes, uint32_t phases, const tgp_adam_args* adam, void* stream);
+
+// TGP_LIK_WARPED: [t = T(Y)] -> the Gaussian step on t, exactly as a TGP_LIK_GAUSS call runs it -> [theta's gradient and the
+// log-Jacobian term] -> (adam) ONE update launch over the flat buffer: theta's gradient does not exist before the post-pass,
+// so the in-launch update of the fused path is not used.  The adjoints of mu, v, log_var_noise given t are the Gaussian ones.
+static int elbo_step_warped(const tgp_model* model, const double* X, const double* Y, double* out, const tgp_grads* grads,
+                            double* mu, double* v, int32_t* status, void* workspace, size_t workspace_bytes, uint32_t phases,
+                            const tgp_adam_args* adam, void* stream) {
+  if (int rc = check_model(model, false)) return rc;
+  if (model->RP != 0) return TGP_E_UNSUPPORTED;
+  if (model->nblk < 0 || model->P < 0) return -1;
+  if (model->nblk == 0 && model->P > 0) return -1;   // parameters of no block: their gradient would never be written
+  if (model->nblk > 0 && !model->program) return -1;
+  if (model->P > 0 && !model->theta) return -1;
+  if (!X) return -2;
+  if (!Y) return -3;
+  if (!out) return -5;
+  if (!grads || !grads->Z || !grads->raw_ls || !grads->raw_os || !grads->m || !grads->Lam || !grads->log_var_noise) return -6;
+  if (model->P > 0 && !grads->theta) return -6;
+  if ((mu == nullptr) != (v == nullptr)) return -7;
+  if (!status) return -9;
+  if (!workspace) return -10;
+  if (adam != nullptr) {
+    if (!adam->params || !adam->grads || !adam->exp_avg || !adam->exp_avg_sq || !adam->step_dev || adam->n < 1) return -12;
+    if (model->P > 0 && (grads->theta < adam->grads || grads->theta + model->P > adam->grads + adam->n)) return -12;
+  }
+  const size_t gbytes = tgp_workspace_bytes_plan(model->N, model->D, model->M, model->S, 0, 0, 0, model->kernel, model->plan);
+  if (gbytes == 0) return TGP_E_UNSUPPORTED;
+  const size_t gd = rup(gbytes / sizeof(double), 2), N = (size_t)model->N;
+  if (workspace_bytes < (gd + 3 * N + warp_workspace_doubles(model->N, model->P)) * sizeof(double)) return TGP_E_WORKSPACE;
+  double* ws = static_cast<double*>(workspace);
+  double* t = ws + gd;
+  double* mu_w = mu ? mu : t + N;
+  double* v_w = v ? v : t + 2 * N;
+  double* part = t + 3 * N;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  FlowProg fp;
+  if (int rc = make_prog(model, true, fp)) return rc;
+  tgp_model mw = *model;
+  mw.program = nullptr;
+  // every argument of the Gaussian step has been checked above: nothing is enqueued for a call that will be refused.
+  // An empty program is the Gaussian step itself on Y: t = Y, log T' = 0, no theta -- neither pass is launched.
+  const bool warp = fp.nblk > 0;
+  if (!warp) t = const_cast<double*>(Y);
+  if (warp && (phases & TGP_PHASE_PREPARE))
+    if (int rc = launch_ell_warp(mw, fp, TGP_WARP_TARGETS, Y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, t, part, st))
+      return rc;
+  tgp_model mg = *model;
+  mg.lik = TGP_LIK_GAUSS; mg.nblk = 0; mg.P = 0; mg.RP = 0; mg.program = nullptr; mg.theta = nullptr;
+  tgp_grads gg = *grads;
+  gg.theta = nullptr; gg.rowp = nullptr;
+  if (int rc = elbo_step_impl(&mg, X, t, nullptr, out, &gg, mu_w, v_w, status, workspace, gbytes, phases, nullptr, stream))
+    return rc;
+  if (!(phases & TGP_PHASE_BACKWARD)) return 0;
+  if (warp)
+    if (int rc = launch_ell_warp(mw, fp, TGP_WARP_STEP, Y, mu_w, v_w, out, nullptr, nullptr, grads->theta, nullptr, part, st))
+      return rc;
+  if (adam != nullptr)
+    return launch_adam_dev(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->n, adam->lr, adam->beta1,
+                           adam->beta2, adam->eps, 0.0, adam->step_dev, adam->maximize, st);
+  return 0;
+}
+
+static int elbo_step_impl(const tgp_model* model, const double* X, const double* Y, const double* rowp, double* out,
+                          const tgp_grads* grads, double* mu, double* v, int32_t* status, void* workspace,
                           size_t workspace_bytes, uint32_t phases, const tgp_adam_args* adam, void* stream) {
+  if (model != nullptr && model->lik == TGP_LIK_WARPED)
+    return elbo_step_warped(model, X, Y, out, grads, mu, v, status, workspace, workspace_bytes, phases, adam, stream);
   if (int rc = check_model(model, true)) return rc;
   if (!X) return -2;
   if (!Y) return -3;
@@ -464,9 +537,65 @@ int tgp_flow_logdet_f64(const tgp_model* model, const double* f, int32_t S, int3
                           static_cast<double*>(workspace));
 }
 
+size_t tgp_ell_warp_workspace_bytes(int32_t N, int32_t P) {
+  if (N < 1 || P < 0) return 0;
+  return warp_workspace_doubles(N, P) * sizeof(double);
+}
+
+int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, double* out, double* g_mu,
+                     double* g_v, double* g_theta, double* t_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!model || model->N < 1 || !model->log_var_noise || model->nblk < 0 || model->P < 0) return -1;
+  if (model->RP != 0) return TGP_E_UNSUPPORTED;
+  if (model->nblk > 0 && !model->program) return -1;
+  if (model->P > 0 && !model->theta) return -1;
+  if (!Y) return -2;
+  if (!mu) return -3;
+  if (!v) return -4;
+  if (!out) return -5;
+  if (!workspace) return -10;
+  if (workspace_bytes < tgp_ell_warp_workspace_bytes(model->N, model->P)) return TGP_E_WORKSPACE;
+  FlowProg fp;
+  if (int rc = make_prog(model, true, fp)) return rc;
+  tgp_model md = *model;
+  md.program = nullptr;
+  return launch_ell_warp(md, fp, TGP_WARP_FULL, Y, mu, v, out, g_mu, g_v, g_theta, t_out, static_cast<double*>(workspace),
+                         static_cast<hipStream_t>(stream));
+}
+
+int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int32_t N, const double* rowp, double* x,
+                         int32_t* status, void* stream) {
+  if (!model || model->nblk < 0 || model->P < 0 || model->RP < 0) return -1;
+  if (model->nblk > 0 && !model->program) return -1;
+  if (model->P > 0 && !model->theta) return -1;
+  if (!t) return -2;
+  if (S < 1) return -3;
+  if (N < 1) return -4;
+  if (model->RP > 0 && !rowp) return -5;
+  if (!x) return -6;
+  if (!status) return -7;
+  FlowProg fp;
+  if (int rc = make_prog(model, true, fp)) return rc;
+  tgp_model md = *model;
+  md.program = nullptr;
+  return launch_flow_inverse(md, fp, t, S, N, rowp, x, status, static_cast<hipStream_t>(stream));
+}
+
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream) {
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
+  if (model->lik == TGP_LIK_WARPED) {
+    if (model->S < 1 || !model->xs || !model->wn || model->nblk < 0 || model->P < 0) return -1;
+    if (model->nblk > 0 && !model->program) return -1;
+    if (model->P > 0 && !model->theta) return -1;
+    if (!mu) return -2;
+    if (!v) return -3;
+    tgp_model mw = *model;
+    mw.RP = 0;   // (rowp is ignored: the warp of the targets has shared parameters only)
+    FlowProg fpw;
+    if (int rc = make_prog(&mw, true, fpw)) return rc;
+    mw.program = nullptr;
+    return launch_predict_warp(mw, fpw, mu, v, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
+  }
   const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;
   if (flowed && (model->S < 1 || !model->xs || !model->wn)) return -1;
   if (!mu) return -2;

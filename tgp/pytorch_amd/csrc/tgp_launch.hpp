@@ -108,4 +108,17 @@ size_t lik_workspace_doubles(int N, int P, int RP);
 int launch_gather_rows(const double* X, const double* Y, int N, int D, const int32_t* index, int32_t* cursor, int offset,
                        int nrows, int advance, int wrap, double* Xb, double* Yb, hipStream_t st);
 
+
+// tgp_warp.hip (warped-GP likelihood: flow on the targets, flow inverse)
+#define TGP_WARP_TARGETS 0 /* t = T(Y) only (pre-pass of the training step; also zeroes the ticket word) */
+#define TGP_WARP_FULL 1    /* the stand-alone likelihood: out[0..2], g_mu, g_v, g_theta, t */
+#define TGP_WARP_STEP 2    /* post-pass of the training step: g_theta written, scale sum log T' added to out[0], out[1] */
+size_t warp_workspace_doubles(int N, int P);
+int launch_ell_warp(const tgp_model& md, const FlowProg& fp, int mode, const double* Y, const double* mu, const double* v,
+                    double* out, double* g_mu, double* g_v, double* g_theta, double* t_out, double* ws, hipStream_t st);
+int launch_flow_inverse(const tgp_model& md, const FlowProg& fp, const double* t, int S, int N, const double* rowp, double* x,
+                        int32_t* status, hipStream_t st);
+int launch_predict_warp(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* Y, double Y_std,
+                        double* m1, double* m2, double* logp, hipStream_t st);
+
 }  // namespace tgp

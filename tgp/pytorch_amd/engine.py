@@ -236,7 +236,7 @@ class ElboEngine:
     def __init__(self, X, Y, params, N_total, flow_blocks=None, S=None, rowp=None, lr=0.01, betas=(0.9, 0.999),
                  eps=1e-8, device="cuda:0", world_size=1, rank=0, mb_global=None, process_group=None,
                  kernel="scale_rbf", mlp=None, mlp_weights=None, nn_weight_decay=1e-5, mlp_training=True,
-                 jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None):
+                 jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None):
         """`mlp` (ops.MlpSpec) + `mlp_weights` (packed, nnets * weights_per_net): input-dependent flow (ID_TGP) whose
         per-row parameters come from the HIP MLP kernels inside the step; `nn_weight_decay` is the reference's Adam
         group for the 'NNets' parameters (main.py:276-288).  `share` = another ElboEngine of the same model whose flat
@@ -244,6 +244,19 @@ class ElboEngine:
         self.lib = L.load()
         self.device = torch.device(device)
         self.world_size, self.rank, self.pg = int(world_size), int(rank), process_group
+        # `likelihood` = "warped": `flow_blocks` / theta describe T applied to the TARGETS (TGP_LIK_WARPED): pre-pass t = T(Y)
+        # -> the Gaussian step on t -> post-pass (theta's gradient, log-Jacobian) -> one Adam launch, captured like the
+        # others.  Full batch on one rank only.
+        if likelihood not in (None, "warped"):
+            raise ValueError("likelihood must be None or 'warped'")
+        self.warped = likelihood == "warped"
+        if self.warped:
+            if int(world_size) > 1 or collective is not None:
+                raise NotImplementedError("the warped likelihood's engine is single-rank (world_size = 1): a data-parallel "
+                                          "warped step is not implemented")
+            if rowp is not None or mlp is not None:
+                raise NotImplementedError("the warped likelihood takes shared flow parameters only")
+            flow_blocks = [] if flow_blocks is None else flow_blocks
         # `collective`: "torch" (default) = torch.distributed.all_reduce between two graphs; "abi" = tgp_allreduce_f64 on the
         # compute stream, INSIDE the captured step (one graph, U steps per launch like a single rank's) -- an RcclComm or
         # the string (a communicator is then created here; torch.distributed only carries its 128-byte id).  With "abi" a
@@ -323,7 +336,8 @@ class ElboEngine:
         fp = self.fp
         self.md, self._keep = ops._model_struct(self.X, fp.view("Z"), fp.view("raw_ls"), fp.view("raw_os"), fp.view("m"),
                                                 fp.view("Lam"), fp.view("lvn"), scale, 0.0, 1.0 / self.world_size,
-                                                self.flow, fp.view("theta") if P else None, self.S, kernel, plan)
+                                                self.flow, fp.view("theta") if P else None, self.S, kernel, plan,
+                                                L.LIK_WARPED if self.warped else None)
         # psd_safe_cholesky's retry ladder (dsp/utils.py:256-269) runs on the device inside the captured step (fused path);
         # `jitter_ladder` is its base value (the reference: 1e-8 in float64, or cg.global_jitter), 0 disables it
         self.md.jitter_ladder = float(jitter_ladder or 0.0)
@@ -336,7 +350,7 @@ class ElboEngine:
         if RP:
             self.gs.rowp = L.ptr(self.g_rowp)
         self.ws = ops.workspace(self.N, self.D, self.M, self.md.S, self.md.nblk, self.md.P, self.md.RP, self.device,
-                                self.md.kernel, plan)
+                                self.md.kernel, plan, self.md.lik)
         self.mlp_ws = None
         if self.mlp is not None:
             d = self.mlp.struct(self.N, True)
@@ -698,6 +712,8 @@ class MinibatchEngine:
     With world_size > 1 each rank gathers and processes its row shard of every batch (one all-reduce per step)."""
 
     def __init__(self, X, Y, params, N_total, batch_size, device="cuda:0", world_size=1, rank=0, **engine_kw):
+        if engine_kw.get("likelihood") == "warped":
+            raise NotImplementedError("the warped likelihood has no minibatch engine: full batch on one rank only (ElboEngine)")
         self.device = torch.device(device)
         self.lib = L.load()
         self.X = X.to(self.device, torch.float64).contiguous()

@@ -91,6 +91,9 @@ class Flow(nn.Module):
     def forward(self, f0, X=None):
         return CompositeFlow([self]).forward(f0, X)
 
+    def inverse(self, f, X=None):
+        return CompositeFlow([self]).inverse(f, X)
+
 
 class IdentityFlow(Flow):
     def forward(self, f0, X=None):
@@ -234,6 +237,20 @@ class CompositeFlow(Flow):
         rowp = nets_rowp(nets, X.reshape(-1, X.shape[-1])) if nets else None     # HIP MLP kernel, one launch for all nets
         flat = f.detach().reshape(-1, f.shape[-1]).contiguous()
         return ops.flow_eval(flat, spec, theta, rowp, want=("G",))["G"].reshape(f.shape)
+
+    def inverse(self, f, X=None):
+        """T^-1(f) on the GPU (no autograd), block by block from the last (flow.py:169-173): closed forms where a block
+        has one, else a bracketed Newton iteration on that block (ops.flow_inverse) -- every kind is inverted, where the
+        reference returns None (Box-Cox), raises (tanh steps) or runs an unbracketed Newton iteration; an element that
+        does not converge raises."""
+        spec, theta_list, nets = compile_flow(self)
+        if spec.nblk == 0:
+            return f
+        dev = f.device
+        theta = torch.stack([p.detach().reshape(()) for p in theta_list]).to(dev) if theta_list else None
+        rowp = nets_rowp(nets, X.reshape(-1, X.shape[-1])) if nets else None
+        flat = f.detach().reshape(-1, f.shape[-1]).contiguous()
+        return ops.flow_inverse(flat, spec, theta, rowp)[0].reshape(f.shape)
 
     def forward_initializer(self, X):
         loss = 0.0

@@ -16,6 +16,7 @@ FLOW_ARCSINH, FLOW_BOXCOX, FLOW_INV_BOXCOX = 3, 4, 5
 FLAG_RESTRICT, FLAG_ADD_F0, FLAG_PER_ROW = 1, 2, 4
 LIK_GAUSS, LIK_FLOW = 0, 1
 LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
+LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 
 _dp = C.c_void_p
 
@@ -104,6 +105,9 @@ _SIGS = {
     "tgp_flow_eval_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     "tgp_flow_logdet_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_flow_logdet_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_ell_warp_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tgp_ell_warp_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_flow_inverse_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "tgp_predict_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     "tgp_kmeans_assign_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]),
     "tgp_kmeans_segsum_f64": (C.c_int, [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp]),

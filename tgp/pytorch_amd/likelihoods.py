@@ -78,6 +78,62 @@ class GaussianNonLinearMean(_GaussianBase):
         return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
 
 
+class WarpedGaussianLinearMean(GaussianLinearMean):
+    """Warped GP: the flow T acts on the targets, p(y|f) = N(T(y)|f, s2) T'(y) (likelihoods/WarpedGaussianLinearMean.py).
+    Constructor signature and attribute names of the reference (`flow` a ModuleList of one, `quad_points`,
+    `log_var_noise`).  The flow has shared parameters only (it never sees X)."""
+
+    def __init__(self, out_dim, noise_init, noise_is_shared, flow, quad_points):
+        super().__init__(out_dim, noise_init, noise_is_shared)
+        from .flow import instance_flow
+        self.flow = nn.ModuleList([instance_flow(flow) if isinstance(flow, list) else flow])
+        self.quad_points = quad_points
+
+    def _flow_inputs(self, dev, with_grad=False):
+        spec, theta_list, nets = compile_flow(self.flow[0])
+        if nets:
+            raise ops.L.TgpError("a warped likelihood takes shared flow parameters only (no input-dependent blocks)")
+        if not theta_list:
+            return spec, None
+        if with_grad:
+            return spec, torch.stack([p.reshape(()) for p in theta_list]).to(dev)
+        return spec, torch.stack([p.detach().reshape(()) for p in theta_list]).to(dev)
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, **kwargs):
+        """Gaussian closed-form ELL at T(Y) plus sum_n log T'(y_n) (:65-85), differentiable in the moments, the noise and
+        the flow's parameters (tgp_ell_warp_f64: value and every gradient in one launch)."""
+        spec, theta = self._flow_inputs(gauss_mean.device, with_grad=True)
+        return ops.EllWarpFunction.apply(Y.reshape(-1), gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(),
+                                         self._lvn().reshape(-1)[:1].contiguous(), theta, spec)
+
+    def unwarped_marginal_moments(self, gauss_mean, gauss_cov, diagonal=True):
+        return super().marginal_moments(gauss_mean, gauss_cov, diagonal)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, diagonal=True, **kwargs):
+        """Gauss-Hermite moments of T^-1(f), f ~ N(mean, cov + s2): (m1, E[.^2] - m1^2) (:93-148)."""
+        assert diagonal, "only diagonal covariances on this path"
+        spec, theta = self._flow_inputs(gauss_mean.device)
+        m1, m2, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(),
+                                self._lvn().detach().reshape(-1)[:1].contiguous(), spec, theta, self.quad_points,
+                                lik=ops.L.LIK_WARPED)
+        return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
+
+    def sample_from_output(self, f, i, **kwargs):
+        """T^-1(f + s eps) (:44-63)."""
+        var = positive_transform(self._lvn()[i]).detach()
+        fs = td.Normal(f, torch.ones_like(f) * torch.sqrt(var)).sample()
+        return self.flow[0].inverse(fs)
+
+    def log_marginal(self, Y, gauss_mean, gauss_cov):
+        """log N(T(Y) | mean, cov + s2 I) + sum log T'(Y) for a full covariance (:151-168, with its `sel.flow` typo fixed).
+        Y, gauss_mean (Dy, MB), gauss_cov (Dy, MB, MB); plain torch on the GPU apart from the flow pass (not a hot path)."""
+        spec, theta = self._flow_inputs(Y.device)
+        ld, t = ops.flow_logdet(Y.reshape(-1).contiguous(), spec, theta, want_G=True) if spec.nblk else (Y.new_zeros(()), Y.reshape(-1))
+        t = t.reshape(Y.shape)
+        C = gauss_cov + torch.diag_embed(positive_transform(self._lvn()).detach().expand(-1, Y.size(1)))
+        return td.MultivariateNormal(gauss_mean, covariance_matrix=C).log_prob(t) + ld
+
+
 class Bernoulli(nn.Module):
     """p(y|G(f)) = Phi(G(f))^y Phi(-G(f))^(1-y), probit link, for binary classification (likelihoods/Bernoulli.py).
     No parameters.  The quadrature over q(f0) runs in float64 on the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with

@@ -8,6 +8,9 @@ reference's data files; point $TGP_DATA_ROOT at them for the real runs).  `--epo
 recipe for smoke runs.  `--flow_arch` (with `--num_blocks`, `--num_steps`) replaces the per-dataset flow of the recipe
 by any generator of flows.py -- SAL, StepTanhL, ArcSL, BoxCoxL, InverseBoxCoxL, Affine -- or build_chain name (SAL_BCL,
 SAL_InvBCL, SAL_AL, BCL_AL, InvBCL_AL); left out, each falls back to the recipe's value.
+`--model WGP` trains the warped GP baseline (likelihoods.WarpedGaussianLinearMean: the same flow generators, applied to
+the targets, shared parameters only: its flow is the data set's TGP recipe or --flow_arch, never ID_TGP's per-row networks,
+which no flag can ask for here; with --likelihood bernoulli it is refused).
 `--likelihood bernoulli` trains a binary classifier (SVGP or TGP; the Bernoulli probit likelihood) on
 synthetic_heart / synthetic_banknote with the flows of the reference's classification script, and reports the test
 negative log-likelihood and accuracy.
@@ -23,7 +26,7 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean
+from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean, WarpedGaussianLinearMean
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import KMEANS
@@ -45,7 +48,7 @@ _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": Inver
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
-    ap.add_argument("--model", required=True, help="ID_TGP, TGP or SVGP")
+    ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
                     choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
@@ -64,6 +67,11 @@ def main(argv=None):
     if bern != (args.dataset in CLASSIFICATION_DATASETS):
         ap.error("--likelihood bernoulli goes with the classification data sets (%s), gaussian with the others"
                  % ", ".join(CLASSIFICATION_DATASETS))
+    wgp = args.model == "WGP"
+    if wgp and bern:
+        ap.error("--model WGP is a regression model: --likelihood gaussian only")
+    if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
+        ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
         ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
@@ -76,7 +84,7 @@ def main(argv=None):
 
     flow_specs = None
     if args.model != "SVGP":
-        hp = dict(HYPER[(args.model, base)])
+        hp = dict(HYPER[("TGP" if wgp else args.model, base)])     # WGP: the data set's TGP recipe (shared parameters only)
         for key, val in (("arch", args.flow_arch), ("blocks", args.num_blocks), ("steps", args.num_steps)):
             if val is not None:
                 hp[key] = val
@@ -106,6 +114,9 @@ def main(argv=None):
 
     if bern:
         lik = Bernoulli()
+    elif wgp:
+        lik = WarpedGaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, flow=flow_specs,
+                                       quad_points=cg.quad_points)
     elif args.model == "SVGP":
         lik = GaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False)
     else:
@@ -116,7 +127,7 @@ def main(argv=None):
     common = dict(model_specs=["zero", K], X=dc["X_tr"], init_Z=init_Z, N=dc["N_tr"], likelihood=lik, num_outputs=Dy,
                   is_whiten=True, K_is_shared=False, mean_is_shared=False, Z_is_shared=False, q_U_is_shared=False,
                   add_noise_inducing=0.0, init_params=ip)
-    if args.model == "SVGP":
+    if args.model == "SVGP" or wgp:
         model = sparse_MF_GP(**common)
     else:
         model = sparse_MF_SP(flow_specs=[flow_specs], flow_connection="single", be_fully_bayesian=False, **common)

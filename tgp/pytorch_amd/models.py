@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
-from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean
+from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean, WarpedGaussianLinearMean
 from .utils import positive_transform
 
 DEFAULT_INIT = {"variational_distribution": {"variance_scale": 1.0, "mean_scale": 0.0}}
@@ -77,7 +77,7 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli)) else cg.quad_points
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, WarpedGaussianLinearMean)) else cg.quad_points
         if isinstance(likelihood, Bernoulli):
             # the ABI's noise pointer: read by no Bernoulli kernel, gradient 0; a buffer, so model.parameters() is the reference's
             self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
@@ -131,6 +131,10 @@ class sparse_MF_SP(nn.Module):
     def _is_bernoulli(self):
         return isinstance(self.likelihood, Bernoulli)
 
+    @property
+    def _is_warped(self):
+        return isinstance(self.likelihood, WarpedGaussianLinearMean)
+
     def _gp_params(self):
         k = self.covariance_function
         lvn = self._bern_lvn if self._is_bernoulli else self.likelihood.log_var_noise.reshape(-1)[:1]
@@ -142,6 +146,11 @@ class sparse_MF_SP(nn.Module):
         HIP kernel (dropout follows the nets' Dropout layers, as in the reference).  `samples` > 1 (fully Bayesian
         evaluation): the rows are evaluated `samples` times in ONE launch, rowp row s * N + n, every (sample, row) with
         its own dropout mask -- the reference's X.repeat to (S_MC, N, Dx), models/sparse_MF_SP.py:753-758."""
+        if self._is_warped:          # the likelihood's own flow, applied to the targets: shared parameters only
+            ctx = torch.enable_grad() if with_grad else torch.no_grad()
+            with ctx:
+                spec, theta = self.likelihood._flow_inputs(X2d.device, with_grad=with_grad)
+            return spec, theta, None
         if isinstance(self.likelihood, GaussianLinearMean):
             return None, None, None
         spec, theta_list, nets = compile_flow(self.G_matrix[0])
@@ -209,7 +218,7 @@ class sparse_MF_SP(nn.Module):
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
-                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else None)
+                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else (ops.L.LIK_WARPED if self._is_warped else None))
         elbo, ell, kld = ops.ElboFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
         return elbo, ell, kld
 
@@ -297,7 +306,14 @@ class sparse_MF_SP(nn.Module):
         mu, v = mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous()
         lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
         with torch.no_grad():
-            if isinstance(self.likelihood, GaussianLinearMean):
+            if self._is_warped:
+                # the exact warped predictive density log N(T(y) | mu, v + s2) + log T'(y) - log Y_std, summed over the rows
+                # (the reference's branch for this class would give log N(y | m1, m2): DESIGN.md 8)
+                spec, theta, _ = self._flow_inputs(X3[0], with_grad=False)
+                _, _, lp = ops.predict(mu, v, lvn, spec, theta, self.quad_points, Y=Y, Y_std=ystd, lik=ops.L.LIK_WARPED,
+                                       want_moments=False)
+                log_p_y = lp.sum().reshape(1)
+            elif isinstance(self.likelihood, GaussianLinearMean):
                 _, _, lp = ops.predict(mu, v, lvn, Y=Y, Y_std=ystd)
                 log_p_y = lp.sum().reshape(1)
             else:

@@ -67,11 +67,12 @@ def kernel_id(kernel):
 
 def workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_GAUSS):
     key = (N, D, M, S, nblk, P, RP, str(device), torch.cuda.current_stream().cuda_stream, kernel, int(plan))
-    if lik == L.LIK_BERNOULLI:          # general-M path at every M: its own buffer size (tgp_workspace_bytes_lik)
+    own = lik in (L.LIK_BERNOULLI, L.LIK_WARPED)
+    if own:          # Bernoulli: general-M path at every M; warped: targets, moments and partials behind the Gaussian step's buffer
         key += (lik,)
     buf = _ws_cache.get(key)
     if buf is None:
-        if lik == L.LIK_BERNOULLI:
+        if own:
             nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
         else:
             nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
@@ -618,6 +619,64 @@ class EllFlowFunction(torch.autograd.Function):
                 g * grp if ctx.has[1] else None, None, None)
 
 
+def ell_warp(Y, mu, v, lvn, flow, theta, scale=1.0, want_t=False):
+    """Warped-GP ELL with gradients (likelihoods/WarpedGaussianLinearMean.py:65-85; tgp_ell_warp_f64, one launch).
+    Returns dict(ell, g_lvn, logdet, g_mu, g_v, g_theta, t)."""
+    lib = L.load()
+    Y, mu, v, lvn = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
+    theta = _c(theta, "theta")
+    dev, N = Y.device, Y.numel()
+    if flow.RP:
+        raise L.TgpError("a warped likelihood takes shared flow parameters only (no input-dependent blocks)")
+    md, keep = _flow_model(N, 1, flow, theta, lvn, dev, scale, lik=L.LIK_WARPED)
+    ws = torch.empty(lib.tgp_ell_warp_workspace_bytes(N, flow.P) // 8 + 16, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    gmu, gv = torch.empty_like(mu), torch.empty_like(v)
+    gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
+    t = torch.empty_like(Y) if want_t else None
+    L.check(lib.tgp_ell_warp_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(out), L.ptr(gmu), L.ptr(gv), L.ptr(gth), L.ptr(t),
+                                 L.ptr(ws), ws.numel() * 8, L.stream_ptr()), "tgp_ell_warp_f64")
+    return {"ell": out[0], "g_lvn": out[1], "logdet": out[2], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "t": t}
+
+
+class EllWarpFunction(torch.autograd.Function):
+    """ELL = WarpedGaussianLinearMean.expected_log_prob with autograd in (mu, v, log_var_noise, theta)."""
+
+    @staticmethod
+    def forward(ctx, Y, mu, v, lvn, theta, flow):
+        res = ell_warp(Y, mu.detach(), v.detach(), lvn.detach(), flow, theta.detach() if theta is not None else None)
+        ctx.save_for_backward(res["g_lvn"], res["g_mu"], res["g_v"], res["g_theta"])
+        ctx.has = theta is not None
+        ctx.lvn_shape = lvn.shape
+        return res["ell"].reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        g_lvn, gmu, gv, gth = ctx.saved_tensors
+        g = g.reshape(())
+        return None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has else None, None
+
+
+def flow_inverse(t, flow, theta, rowp=None, check=True):
+    """x = T^-1(t) for t of shape (S,N) or (N,) (tgp_flow_inverse_f64: closed forms, else a bracketed Newton iteration per
+    block).  Returns (x, status) -- status int32[1] on the device, the number of elements that did not converge; with
+    `check` it is read (one sync) and a non-zero count raises."""
+    lib = L.load()
+    t = _c(t, "t")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    t2 = t.reshape(1, -1) if t.dim() == 1 else t.reshape(t.shape[0], -1)
+    S, N = t2.shape
+    lvn = torch.zeros(1, dtype=torch.float64, device=t.device)
+    md, keep = _flow_model(N, 1, flow, theta, lvn, t.device)
+    x = torch.empty_like(t)
+    status = torch.zeros(1, dtype=torch.int32, device=t.device)
+    L.check(lib.tgp_flow_inverse_f64(md, L.ptr(t2), S, N, L.ptr(rowp) if flow.RP > 0 else None, L.ptr(x), L.ptr(status),
+                                     L.stream_ptr()), "tgp_flow_inverse_f64")
+    if check and int(status[0]) != 0:
+        raise L.TgpError("flow_inverse: %d element(s) did not converge (outside the flow's range?)" % int(status[0]))
+    return x, status
+
+
 def flow_eval(f, flow, theta, rowp=None, want=("G", "dG", "logdG")):
     """G(f), dG/df, log dG/df for f of shape (S,N) or (N,) (CompositeFlow.forward / forward_grad)."""
     lib = L.load()
@@ -650,7 +709,7 @@ def flow_logdet(f, flow, theta, rowp=None, want_G=False):
     return out[0], G
 
 
-def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None):
+def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None, want_moments=True):
     """Predictive moments m1, m2 and per-row test log-likelihood kernel (see tgp_predict_f64).  lik = lib.LIK_BERNOULLI:
     m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (`flow` a FlowSpec, possibly empty)."""
     lib = L.load()
@@ -664,7 +723,8 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
         keep = None
     else:
         md, keep = _flow_model(N, S, flow, theta, lvn, dev, lik=L.LIK_FLOW if lik is None else int(lik))
-    m1, m2 = torch.empty_like(mu), torch.empty_like(mu)
+    # (want_moments=False: logp only -- the warped moments cost S flow inversions per row)
+    m1, m2 = (torch.empty_like(mu), torch.empty_like(mu)) if want_moments else (None, None)
     logp = torch.empty_like(mu) if Y is not None else None
     Yc = _c(Y.reshape(-1), "Y") if Y is not None else None
     L.check(lib.tgp_predict_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), float(Y_std), L.ptr(m1), L.ptr(m2),

@@ -112,7 +112,7 @@ class Trainer_SP_regression:
         from .data import DeviceLoader
         from .engine import ElboEngine, MinibatchEngine
         from .flow import compile_flow, mlp_spec
-        from .likelihoods import GaussianLinearMean
+        from .likelihoods import GaussianLinearMean, WarpedGaussianLinearMean
         if not getattr(cg, "use_step_engine", True) or opt != "adam":
             return None
         ld = self.train_loader
@@ -126,7 +126,15 @@ class Trainer_SP_regression:
         if {id(q) for g in groups for q in g["params"]} != {id(q) for q in model.parameters()}:
             return None
         nets, theta_list, blocks = [], [], None
-        if not isinstance(model.likelihood, GaussianLinearMean):
+        warped = isinstance(model.likelihood, WarpedGaussianLinearMean)
+        if warped:
+            if len(ld) != 1:             # the warped engine is full batch only: minibatches take the eager loop
+                return None
+            spec, theta_list, nets = compile_flow(model.likelihood.flow[0])
+            if nets:
+                return None
+            blocks = spec.blocks
+        elif not isinstance(model.likelihood, GaussianLinearMean):
             spec, theta_list, nets = compile_flow(model.G_matrix[0])
             blocks = spec.blocks
         nn_params = [p for net in nets for p in net.parameters()]
@@ -149,6 +157,8 @@ class Trainer_SP_regression:
         kw = dict(flow_blocks=blocks, S=getattr(model, "quad_points", None), lr=lr_ALL,
                   kernel=model.covariance_function.hip_kernel, mlp=mspec, mlp_weights=W, nn_weight_decay=wd, mlp_training=True,
                   jitter_ladder=cg.global_jitter if cg.global_jitter is not None else 1e-8)
+        if warped:
+            kw["likelihood"] = "warped"
         if len(ld) == 1:
             eng = ElboEngine(ld.X, ld.Y, params, float(model.N), device=ld.X.device, **kw)
         else:
