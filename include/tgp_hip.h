@@ -111,6 +111,11 @@ extern "C" {
  * out[0], out[1]]; tgp_elbo_step_adam_f64 applies the update in ONE separate launch after them.  An empty program gives
  * TGP_LIK_GAUSS's results bit for bit. */
 #define TGP_LIK_WARPED 4
+/* MulticlassCategorical (likelihoods/MulticlassCategorical.py): softmax over C latent GPs, each through its own flow, Monte
+ * Carlo over all C latents of a row.  A documented constant only: the training-step entries are single-output and return
+ * TGP_E_UNSUPPORTED for it (tgp_last_error() names the entry to use).  The likelihood is the stand-alone tgp_ell_softmax_f64;
+ * a C-output step composes it with tgp_qf_moments_f64 / tgp_qf_moments_bwd_f64 / tgp_kl_whitened_f64 per class. */
+#define TGP_LIK_SOFTMAX 5
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -352,6 +357,46 @@ int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, 
  * caller): the call ADDS the number of elements that did not reach the stopping rule. */
 int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int32_t N, const double* rowp, double* x,
                          int32_t* status, void* stream);
+
+/* ---- multi-class likelihood (likelihoods/MulticlassCategorical.py:60-133): C latent GPs, one flow program per class ----
+ *   f0[s,c,n] = mu[c,n] + sqrt(max(v[c,n], 0)) eps[s,c,n],   g[s,c,n] = G_c(f0[s,c,n]),
+ *   ELL = scale/S sum_n sum_s (g[s,y_n,n] - logsumexp_c g[s,c,n])        (max-subtracted: torch's CrossEntropyLoss)
+ * Limits (TGP_E_UNSUPPORTED otherwise): 3 <= C <= TGP_SOFTMAX_MAX_C, 1 <= S <= TGP_SOFTMAX_MAX_S, at most 64 blocks over all
+ * programs, shared flow parameters only (a block with TGP_FLAG_PER_ROW is refused).
+ * eps: the caller's standard normals, (S,C,N) -- the reference's F0 layout -- or NULL: every lane derives its draws from a
+ * splitmix64 hash of (seed, *step_dev, s, c, row0 + n) followed by Box-Muller (exact recipe: csrc/tgp_softmax.hip), nothing of
+ * size S x C x N exists in memory; a row keeps its draws when the rows are sharded over calls (row0 = first row of the shard).
+ * mu, v: (C,N);  Y: (N) float64 holding the class index 0..C-1;  P: (N,C). */
+#define TGP_SOFTMAX_MAX_C 32
+#define TGP_SOFTMAX_MAX_S 256
+typedef struct tgp_softmax {
+  int32_t N;                /* rows in this call                                                              */
+  int32_t C;                /* classes = latent GPs                                                           */
+  int32_t S;                /* Monte-Carlo samples per row                                                    */
+  int32_t reserved0;
+  const int32_t* program;   /* HOST (blk_off[C],4): the C programs one after the other; poff is relative to the
+                               class's own parameters theta + theta_off[c]; NULL if no class has a block      */
+  const int32_t* blk_off;   /* HOST (C+1): blocks of class c are [blk_off[c], blk_off[c+1])                   */
+  const double* theta;      /* (theta_off[C]) shared flow scalars of all programs, or NULL                    */
+  const int32_t* theta_off; /* HOST (C+1)                                                                     */
+  double scale;             /* N_total / MB                                                                   */
+  uint64_t seed;            /* counter mode                                                                   */
+  const int32_t* step_dev;  /* counter mode: device int32 read at launch (e.g. the Adam step counter, so that a
+                               captured graph draws afresh on every replay); NULL = 0                         */
+  int64_t row0;             /* counter mode: global index of this call's first row                            */
+} tgp_softmax;
+size_t tgp_ell_softmax_workspace_bytes(int32_t N, int32_t P);
+/* out[0] = ELL; mu_bar, v_bar (C,N) and theta_bar (theta_off[C]) = its gradients, written in the same launch -- all three
+ * NULL: forward only.  v_bar is 0 on rows with v <= 0.  Fixed summation order, no float atomics: bit-reproducible. */
+int tgp_ell_softmax_f64(const tgp_softmax* d, const double* Y, const double* mu, const double* v, const double* eps,
+                        double* out, double* mu_bar, double* v_bar, double* theta_bar, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* eps (S,C,N) = the draws the counter mode of a call with the same (N, C, S, seed, step_dev, row0) uses. */
+int tgp_mc_normals_f64(const tgp_softmax* d, double* eps, void* stream);
+/* P[n][c] = 1/S sum_s softmax_c(g[s,.,n]) (MulticlassCategorical.marginal_moments); logp[n] = log P[n][y_n] when Y and logp
+ * are given.  eps as above. */
+int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double* v, const double* eps, const double* Y,
+                            double* P, double* logp, void* stream);
 
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the

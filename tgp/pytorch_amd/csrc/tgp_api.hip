@@ -198,6 +198,11 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
 static int elbo_step_impl(const tgp_model* model, const double* X, const double* Y, const double* rowp, double* out,
                           const tgp_grads* grads, double* mu, double* v, int32_t* status, void* workspace,
                           size_t workspace_bytes, uint32_t phases, const tgp_adam_args* adam, void* stream) {
+  if (model != nullptr && model->lik == TGP_LIK_SOFTMAX) {
+    set_error_text("TGP_LIK_SOFTMAX has no single-output training step: use tgp_ell_softmax_f64 with tgp_qf_moments_f64, "
+                   "tgp_qf_moments_bwd_f64 and tgp_kl_whitened_f64 per class");
+    return TGP_E_UNSUPPORTED;
+  }
   if (model != nullptr && model->lik == TGP_LIK_WARPED)
     return elbo_step_warped(model, X, Y, out, grads, mu, v, status, workspace, workspace_bytes, phases, adam, stream);
   if (int rc = check_model(model, true)) return rc;
@@ -560,6 +565,82 @@ int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, 
   md.program = nullptr;
   return launch_ell_warp(md, fp, TGP_WARP_FULL, Y, mu, v, out, g_mu, g_v, g_theta, t_out, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
+}
+
+// descriptor -> by-value kernel arguments: limits, then every block as make_prog checks it, poff made absolute in theta
+static int make_softmax(const tgp_softmax* d, SmxArgs& a, FlowProg& fp) {
+  if (!d || d->N < 1 || !d->blk_off || !d->theta_off) return -1;
+  if (d->C < 3 || d->C > TGP_SOFTMAX_MAX_C || d->S < 1 || d->S > TGP_SOFTMAX_MAX_S) return TGP_E_UNSUPPORTED;
+  if (d->blk_off[0] != 0 || d->theta_off[0] != 0) return -1;
+  for (int c = 0; c < d->C; ++c)
+    if (d->blk_off[c + 1] < d->blk_off[c] || d->theta_off[c + 1] < d->theta_off[c]) return -1;
+  const int nblk = d->blk_off[d->C], P = d->theta_off[d->C];
+  if (nblk > TGP_MAX_BLOCKS) return TGP_E_UNSUPPORTED;
+  if (nblk > 0 && !d->program) return -1;
+  if (P > 0 && !d->theta) return -1;
+  a.N = d->N; a.C = d->C; a.S = d->S; a.P = P;
+  a.scale = d->scale; a.seed = d->seed; a.step_dev = d->step_dev; a.row0 = d->row0;
+  for (int c = 0; c <= TGP_SOFTMAX_MAX_C; ++c) a.blk_off[c] = d->blk_off[c < d->C ? c : d->C];
+  fp.nblk = nblk;
+  for (int c = 0; c < d->C; ++c) {
+    const int Pc = d->theta_off[c + 1] - d->theta_off[c];
+    for (int b = d->blk_off[c]; b < d->blk_off[c + 1]; ++b) {
+      const int kind = d->program[4 * b], K = d->program[4 * b + 1], poff = d->program[4 * b + 2], flags = d->program[4 * b + 3];
+      if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
+      if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
+      if (flags & TGP_FLAG_PER_ROW) return TGP_E_UNSUPPORTED;   // (RP != 0: no input-dependent flows here)
+      if (poff < 0 || poff + flow_block_params(kind, K) > Pc) return -1;
+      fp.blk[4 * b] = kind; fp.blk[4 * b + 1] = K; fp.blk[4 * b + 2] = d->theta_off[c] + poff; fp.blk[4 * b + 3] = flags;
+    }
+  }
+  fp.nslots = flow_slots(fp.blk, fp.nblk);
+  return 0;
+}
+
+size_t tgp_ell_softmax_workspace_bytes(int32_t N, int32_t P) {
+  if (N < 1 || P < 0) return 0;
+  return softmax_workspace_doubles(N, P) * sizeof(double);
+}
+
+int tgp_ell_softmax_f64(const tgp_softmax* d, const double* Y, const double* mu, const double* v, const double* eps,
+                        double* out, double* mu_bar, double* v_bar, double* theta_bar, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+  SmxArgs a;
+  FlowProg fp;
+  if (int rc = make_softmax(d, a, fp)) return rc;
+  if (!Y) return -2;
+  if (!mu) return -3;
+  if (!v) return -4;
+  if (!out) return -6;
+  // forward only: all three adjoints NULL; else mu_bar and v_bar, and theta_bar when there are parameters
+  const bool train = mu_bar || v_bar || theta_bar;
+  if (train && (!mu_bar || !v_bar)) return -7;
+  if (train && a.P > 0 && !theta_bar) return -9;
+  if (!workspace) return -10;
+  if (workspace_bytes < tgp_ell_softmax_workspace_bytes(a.N, a.P)) return TGP_E_WORKSPACE;
+  return launch_ell_softmax(a, fp, d->theta, Y, mu, v, eps, out, mu_bar, v_bar, theta_bar, static_cast<double*>(workspace),
+                            static_cast<hipStream_t>(stream));
+}
+
+int tgp_mc_normals_f64(const tgp_softmax* d, double* eps, void* stream) {
+  if (!d || d->N < 1) return -1;
+  if (d->C < 3 || d->C > TGP_SOFTMAX_MAX_C || d->S < 1 || d->S > TGP_SOFTMAX_MAX_S) return TGP_E_UNSUPPORTED;
+  if (!eps) return -2;
+  SmxArgs a{};
+  a.N = d->N; a.C = d->C; a.S = d->S; a.seed = d->seed; a.step_dev = d->step_dev; a.row0 = d->row0;
+  return launch_mc_normals(a, eps, static_cast<hipStream_t>(stream));
+}
+
+int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double* v, const double* eps, const double* Y,
+                            double* P, double* logp, void* stream) {
+  SmxArgs a;
+  FlowProg fp;
+  if (int rc = make_softmax(d, a, fp)) return rc;
+  if (!mu) return -2;
+  if (!v) return -3;
+  if (!P) return -6;
+  if (logp && !Y) return -5;
+  return launch_predict_softmax(a, fp, d->theta, mu, v, eps, Y, P, logp, static_cast<hipStream_t>(stream));
 }
 
 int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int32_t N, const double* rowp, double* x,

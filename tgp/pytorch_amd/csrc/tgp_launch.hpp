@@ -121,4 +121,21 @@ int launch_flow_inverse(const tgp_model& md, const FlowProg& fp, const double* t
 int launch_predict_warp(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* Y, double Y_std,
                         double* m1, double* m2, double* logp, hipStream_t st);
 
+// tgp_softmax.hip (multi-class likelihood: softmax over C latent GPs, Monte Carlo over all classes of a row)
+struct SmxArgs {                 // by-value kernel argument built from a tgp_softmax descriptor
+  int32_t N, C, S, P;            // P = theta_off[C]: every program's shared scalars
+  int32_t blk_off[TGP_SOFTMAX_MAX_C + 1];
+  double scale;
+  uint64_t seed;
+  const int32_t* step_dev;
+  int64_t row0;
+};
+size_t softmax_workspace_doubles(int N, int P);
+int launch_ell_softmax(const SmxArgs& a, const FlowProg& fp, const double* theta, const double* Y, const double* mu, const double* v,
+                       const double* eps, double* out, double* mu_bar, double* v_bar, double* theta_bar, double* ws,
+                       hipStream_t st);
+int launch_mc_normals(const SmxArgs& a, double* eps, hipStream_t st);
+int launch_predict_softmax(const SmxArgs& a, const FlowProg& fp, const double* theta, const double* mu, const double* v,
+                           const double* eps, const double* Y, double* P, double* logp, hipStream_t st);
+
 }  // namespace tgp

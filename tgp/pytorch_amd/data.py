@@ -124,12 +124,13 @@ def load_uci_split(base, seed, root):
 
 
 def _binary_dataset(base, batch_size, use_validation, seed, options):
-    """synthetic_heart / synthetic_banknote (synthetic.binary_dataset): a seeded 90 / 10 split, X standardised by the
-    train split, labels left as they are (Y_std = 1)."""
-    from .synthetic import binary_dataset
+    """synthetic_heart / synthetic_banknote (synthetic.binary_dataset) and the multi-class synthetic_blobs
+    (synthetic.blobs_dataset; data_config["num_classes"]): a seeded 90 / 10 split, X standardised by the train split, labels
+    left as they are (Y_std = 1)."""
+    from .synthetic import binary_dataset, blobs_dataset
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
-    X, Y = binary_dataset(base)
+    X, Y = blobs_dataset() if base == "blobs" else binary_dataset(base)
     n = X.shape[0]
     perm = numpy.random.default_rng(seed).permutation(n)
     n_tr = int(round(0.9 * n))
@@ -152,6 +153,8 @@ def _binary_dataset(base, batch_size, use_validation, seed, options):
                    "N_tr": X_tr.shape[0], "N_va": 0 if X_va is None else X_va.shape[0], "N_te": X_te.shape[0],
                    "Dx": X_tr.shape[1], "Dy": 1, "Y_std": Y_std, "X_all": None, "Y_all": None,
                    "train_idx": numpy.asarray(tr_idx), "test_idx": numpy.asarray(te_idx)}
+    if base == "blobs":
+        data_config["num_classes"] = int(Y.max()) + 1
     return loaders, data_config
 
 
@@ -168,7 +171,7 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     options = options or {}
     synth = dataset_name.startswith("synthetic_")
     base = dataset_name.replace("synthetic_", "")
-    if synth and base in BINARY_SHAPES:
+    if synth and (base in BINARY_SHAPES or base == "blobs"):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
     if (synth and base not in SHAPES) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))

@@ -17,6 +17,9 @@ FLAG_RESTRICT, FLAG_ADD_F0, FLAG_PER_ROW = 1, 2, 4
 LIK_GAUSS, LIK_FLOW = 0, 1
 LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
+LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
+SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
+E_UNSUPPORTED = -100
 
 _dp = C.c_void_p
 
@@ -57,6 +60,12 @@ class TgpMlp(C.Structure):
     _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("L", C.c_int32), ("nnets", C.c_int32),
                 ("act", C.c_int32), ("training", C.c_int32), ("reserved0", C.c_int32), ("drop_p", C.c_double),
                 ("seed", C.c_uint64)]
+
+
+class TgpSoftmax(C.Structure):
+    _fields_ = [("N", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("reserved0", C.c_int32), ("program", _dp),
+                ("blk_off", _dp), ("theta", _dp), ("theta_off", _dp), ("scale", C.c_double), ("seed", C.c_uint64),
+                ("step_dev", _dp), ("row0", C.c_int64)]
 
 
 class TgpError(RuntimeError):
@@ -107,6 +116,10 @@ _SIGS = {
     "tgp_flow_logdet_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_ell_warp_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_ell_warp_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_ell_softmax_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tgp_ell_softmax_f64": (C.c_int, [C.POINTER(TgpSoftmax), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_mc_normals_f64": (C.c_int, [C.POINTER(TgpSoftmax), _dp, _dp]),
+    "tgp_predict_softmax_f64": (C.c_int, [C.POINTER(TgpSoftmax), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "tgp_flow_inverse_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "tgp_predict_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     "tgp_kmeans_assign_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]),
@@ -169,7 +182,7 @@ def load():
 
 def check(rc, what):
     if rc != 0:
-        msg = load().tgp_last_error().decode() if rc == -103 else ""
+        msg = load().tgp_last_error().decode() if rc in (-103, E_UNSUPPORTED) else ""
         raise TgpError("%s failed with code %d %s" % (what, rc, msg))
 
 

@@ -170,3 +170,82 @@ class Bernoulli(nn.Module):
         P, _, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(), lvn, spec, theta,
                               self.quad_points, rowp, lik=ops.L.LIK_BERNOULLI)
         return P.reshape(-1, 1)
+
+
+class MulticlassCategorical(nn.Module):
+    """p(y|G(f)) = softmax(G_1(f_1), ..., G_C(f_C))[y] over C latent GPs (likelihoods/MulticlassCategorical.py): every integral
+    is a Monte-Carlo mean over `SMC` joint draws of the C latents of a row (tgp_ell_softmax_f64 / tgp_predict_softmax_f64).
+    The draws: `eps` (S, C, MB) standard normals the caller fixes -- here (also (calls, S, C, MB): one set per training call)
+    or per call -- or, by default, the kernels' own
+    counter-based ones, a function of (`seed`, the number of training calls so far, sample, class, row): nothing of size
+    S x C x MB is allocated, and every training call draws afresh."""
+
+    EVAL_SALT = 0x6576616C     # prediction draws come from a stream of their own
+
+    def __init__(self, num_classes: int, eps=None, seed=None):
+        super().__init__()
+        assert num_classes > 2, "If you have a binary classification problem use the Bernouilli"
+        self.C = num_classes
+        self.SMC = cg.quad_points
+        self.eps = eps
+        self.seed = int(cg.config_seed if seed is None else seed)
+        self._step = None            # device int32 counter of the training calls (the draws' step word)
+        self._calls = 0              # training calls served from a 4-d `eps`
+
+    @property
+    def quad_points(self):
+        return self.SMC
+
+    def sample_from_output(self, f, i, **kwargs):
+        assert f.size(0) == self.C, "Bad specified input"
+        return td.Categorical(probs=torch.softmax(f.t(), dim=1)).sample().to(cg.dtype)
+
+    def _flow_inputs(self, flow, dev, with_grad=False):
+        specs, theta = [], []
+        for fl in flow:
+            spec, theta_list, nets = compile_flow(fl)
+            if nets:
+                raise ops.L.TgpError("the multi-class likelihood takes shared flow parameters only (no input-dependent blocks)")
+            specs.append(spec)
+            theta += theta_list
+        if not theta:
+            return ops.SoftmaxSpec(specs), None
+        if with_grad:
+            return ops.SoftmaxSpec(specs), torch.stack([p.reshape(()) for p in theta]).to(dev)
+        return ops.SoftmaxSpec(specs), torch.stack([p.detach().reshape(()) for p in theta]).to(dev)
+
+    def _checks(self, gauss_mean, flow, X):
+        assert len(flow) == self.C, "Flow list must be size {} for MultiClass likelihood".format(self.C)
+        assert gauss_mean.size(0) == self.C, "Multiclass classification requires {} GPs, got {}".format(self.C, gauss_mean.size(0))
+        assert len(X.shape) == 3, 'Bad input X, expected (n_class,MB*S,Dx)'
+        assert X.size(0) == self.C, 'Wrong first dimension in X, expected n_classes'
+
+    def _next_step(self, dev):
+        if self._step is None or self._step.device != dev:
+            self._step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._step += 1
+        return self._step.clone()     # snapshot: a later call must not change the draws this call's graph refers to
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, eps=None, seed=None, row0=0, scale=1.0, **kwargs):
+        """1/S sum_s sum_n log softmax(G(f0_s))[y_n]; Y (1, MB) class indices, moments (C, MB).  Differentiable in the
+        moments and the flows' parameters; `scale` multiplies value and gradients inside the launch."""
+        self._checks(gauss_mean, flow, X)
+        dev = gauss_mean.device
+        spec, theta = self._flow_inputs(flow, dev, with_grad=True)
+        eps = self.eps if eps is None else eps
+        if eps is not None and eps.dim() == 4:       # (calls, S, C, MB): one set of draws per training call, in order
+            eps, self._calls = eps[self._calls], self._calls + 1
+        step = None if eps is not None else self._next_step(dev)
+        return ops.SoftmaxEllFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.contiguous(), gauss_cov.contiguous(),
+                                            theta, spec, self.SMC, eps, self.seed if seed is None else int(seed), step,
+                                            int(row0), float(scale))
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, eps=None, seed=None, row0=0, Y=None, **kwargs):
+        """P (MB, C) = 1/S sum_s softmax(G(f0_s)); with Y also log P[n, y_n] as a second return value.  The draws are `eps`
+        (S, C, MB) when given here, else counter-based (the constructor's `eps` belongs to the training rows)."""
+        self._checks(gauss_mean, flow, X)
+        spec, theta = self._flow_inputs(flow, gauss_mean.device)
+        P, logp = ops.predict_softmax(gauss_mean.detach().contiguous(), gauss_cov.detach().contiguous(), spec, theta, self.SMC,
+                                      eps=eps, seed=(self.seed if seed is None else int(seed)) ^ self.EVAL_SALT,
+                                      step_dev=self._step, row0=row0, Y=Y)
+        return P if Y is None else (P, logp)

@@ -14,6 +14,11 @@ which no flag can ask for here; with --likelihood bernoulli it is refused).
 `--likelihood bernoulli` trains a binary classifier (SVGP or TGP; the Bernoulli probit likelihood) on
 synthetic_heart / synthetic_banknote with the flows of the reference's classification script, and reports the test
 negative log-likelihood and accuracy.
+`--likelihood multiclass` trains a C-class classifier (SVGP: identity flows; TGP: one --flow_arch flow per class, default
+SAL x 2) with the softmax likelihood over C latent GPs on synthetic_blobs, and reports the same two numbers:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood multiclass --dataset synthetic_blobs \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 300
 """
 import argparse
 
@@ -26,7 +31,8 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean, WarpedGaussianLinearMean
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical,
+                          WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import KMEANS
@@ -40,8 +46,10 @@ HYPER = {
     # bash_scripts/launch_test_uci_medium-small_classification.sh
     ("TGP", "heart"): dict(arch="SAL_InvBCL", blocks=1, steps=None),
     ("TGP", "banknote"): dict(arch="BCL_AL", blocks=5, steps=None),
+    ("TGP", "blobs"): dict(arch="SAL", blocks=2, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
+MULTICLASS_DATASETS = ("synthetic_blobs",)
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -50,15 +58,17 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
     ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
-                    choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS))
+                    choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS)
+                    + list(MULTICLASS_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
     ap.add_argument("--flow_arch", choices=FLOW_ARCHS, default=None, help="flow generator (default: the recipe's)")
     ap.add_argument("--num_blocks", type=int, default=None, help="flow blocks (default: the recipe's)")
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli"], default="gaussian",
-                    help="gaussian: regression (default); bernoulli: binary classification, probit link")
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass"], default="gaussian",
+                    help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
+                         "softmax over C latent GPs")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -67,8 +77,13 @@ def main(argv=None):
     if bern != (args.dataset in CLASSIFICATION_DATASETS):
         ap.error("--likelihood bernoulli goes with the classification data sets (%s), gaussian with the others"
                  % ", ".join(CLASSIFICATION_DATASETS))
+    multi = args.likelihood == "multiclass"
+    if multi and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood multiclass: SVGP or TGP only")
+    if multi != (args.dataset in MULTICLASS_DATASETS):
+        ap.error("--likelihood multiclass goes with the multi-class data sets (%s)" % ", ".join(MULTICLASS_DATASETS))
     wgp = args.model == "WGP"
-    if wgp and bern:
+    if wgp and (bern or multi):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
         ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
@@ -112,7 +127,10 @@ def main(argv=None):
             T_flow = instance_flow(flow_specs) if isinstance(flow_specs, list) else flow_specs
             flow_specs, _ = find_forward_params_input_dependent_flow(loaders[0], FLOW=T_flow, num_epochs=2000, noise_var=0.0)
 
-    if bern:
+    if multi:
+        Dy = dc["num_classes"]              # one latent GP (and one flow) per class
+        lik = MulticlassCategorical(Dy)
+    elif bern:
         lik = Bernoulli()
     elif wgp:
         lik = WarpedGaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, flow=flow_specs,
@@ -130,7 +148,9 @@ def main(argv=None):
     if args.model == "SVGP" or wgp:
         model = sparse_MF_GP(**common)
     else:
-        model = sparse_MF_SP(flow_specs=[flow_specs], flow_connection="single", be_fully_bayesian=False, **common)
+        # (multi-class: every class builds its own flow from the same spec list)
+        model = sparse_MF_SP(flow_specs=[flow_specs] * Dy if multi else [flow_specs], flow_connection="single",
+                             be_fully_bayesian=False, **common)
     model.to(cg.device)
 
     lr = 0.01
@@ -140,13 +160,13 @@ def main(argv=None):
         sched.append([lr, 1e-5, "NNets"])
         specs[0].extend(sched)
     Y_std = (torch.ones((Dy,)) * dc["Y_std"]).to(cg.device)
-    trainer_cls = Trainer_SP_classification if bern else Trainer_SP_regression
+    trainer_cls = Trainer_SP_classification if (bern or multi) else Trainer_SP_regression
     trainer = trainer_cls(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
                                     track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True)
     trainer.train(epochs=args.epochs, lr_ALL=lr, opt="adam", keep_parameter_groups=True,
                   optimisation_schedule=([1.0], specs), lr_groups=None)
     res = trainer.compute_metrics()
-    if bern:                         # (logL_train, acc_train, logL_valid, acc_valid, logL_test, acc_test)
+    if bern or multi:                # (logL_train, acc_train, logL_valid, acc_valid, logL_test, acc_test)
         print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}".format(
             args.dataset, args.num_inducing, args.model, -res[4]))
         print("Dataset {}, num inducing points {}, model {}, Test Accuracy {:.3f}".format(

@@ -22,7 +22,8 @@ import torch.nn as nn
 from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
-from .likelihoods import Bernoulli, GaussianLinearMean, GaussianNonLinearMean, WarpedGaussianLinearMean
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical,
+                          WarpedGaussianLinearMean)
 from .utils import positive_transform
 
 DEFAULT_INIT = {"variational_distribution": {"variance_scale": 1.0, "mean_scale": 0.0}}
@@ -60,7 +61,11 @@ class sparse_MF_SP(nn.Module):
                  be_fully_bayesian: bool = False, init_params: dict = {}) -> None:
         super().__init__()
         assert len(model_specs) == 2, "Parameter model_specs should be len 2: mean name and kernel instance"
-        assert int(num_outputs) == 1, "this build implements the single-output path (Dy = 1, every BASELINE config)"
+        # C outputs only as the C latent GPs of the multi-class likelihood (composed step)
+        assert int(num_outputs) == 1 or (isinstance(likelihood, MulticlassCategorical) and int(num_outputs) == likelihood.C), \
+            "this build implements the single-output path (Dy = 1, every BASELINE config)"
+        assert not isinstance(likelihood, MulticlassCategorical) or int(num_outputs) == likelihood.C, \
+            "MulticlassCategorical needs num_outputs = its number of classes"
         assert is_whiten, "only the whitened representation (main.py: whiten = True) has a HIP implementation"
         assert model_specs[0] == "zero", "only the 'zero' mean function (main.py) is provided"
         assert not (K_is_shared or mean_is_shared or Z_is_shared or q_U_is_shared), "sharing flags are False in main.py"
@@ -77,7 +82,7 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, WarpedGaussianLinearMean)) else cg.quad_points
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
         if isinstance(likelihood, Bernoulli):
             # the ABI's noise pointer: read by no Bernoulli kernel, gradient 0; a buffer, so model.parameters() is the reference's
             self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
@@ -135,11 +140,44 @@ class sparse_MF_SP(nn.Module):
     def _is_warped(self):
         return isinstance(self.likelihood, WarpedGaussianLinearMean)
 
-    def _gp_params(self):
+    @property
+    def _is_multiclass(self):
+        return isinstance(self.likelihood, MulticlassCategorical)
+
+    def _gp_params(self, c=None):
         k = self.covariance_function
+        if c is not None:            # latent GP c of a multi-class model: slice c of the batched parameters, no noise
+            D = self.inp_dim
+            return (self.Z[c], k.base_kernel.raw_lengthscale.reshape(-1, D)[c], k.raw_outputscale.reshape(-1)[c:c + 1],
+                    self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c], None)
         lvn = self._bern_lvn if self._is_bernoulli else self.likelihood.log_var_noise.reshape(-1)[:1]
         return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.raw_outputscale.reshape(-1),
                 self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], lvn)
+
+    def _qf_per_class(self, X2):
+        """(mu, v) of shape (C, MB): one tgp_qf_moments_f64 per latent GP, in class order on the current stream;
+        differentiable (tgp_qf_moments_bwd_f64) when a parameter needs it."""
+        mus, vs = [], []
+        for c in range(self.out_dim):
+            Z, rl, ro, m, Lam, _ = self._gp_params(c)
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
+                mu, v = ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
+            else:
+                mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), kernel=self.covariance_function.hip_kernel)
+            mus.append(mu)
+            vs.append(v)
+        return torch.stack(mus), torch.stack(vs)
+
+    def _elbo_multiclass(self, X2, Y, eps=None):
+        """ELL - sum_c KL_c (sparse_MF_SP.py:590-593) composed from the stand-alone differentiable pieces: per class the
+        q(f) moments and the KL, then ONE softmax likelihood launch over all classes.  Each class's row kernel runs twice,
+        once for the moments and once for their adjoint (the known cost of the composed step)."""
+        mu, v = self._qf_per_class(X2)
+        KLD = self.KLD()
+        X3 = X2.unsqueeze(0).expand(self.out_dim, -1, -1)
+        ELL = self.likelihood.expected_log_prob(Y.t(), mu, v, flow=self.G_matrix, X=X3, eps=eps, scale=self.N / Y.size(0)).sum()
+        KLD = KLD.sum()
+        return ELL - KLD, ELL, KLD
 
     def _flow_inputs(self, X2d, with_grad, samples=1):
         """(FlowSpec or None, theta, rowp): shared scalars stacked into one vector, per-row parameters from the MLPs on the
@@ -192,6 +230,9 @@ class sparse_MF_SP(nn.Module):
         assert diagonal and not is_duvenaud, "diagonal=True, is_duvenaud=False on this path"
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
+        if self._is_multiclass:
+            mu, v = self._qf_per_class(X2)
+            return mu.unsqueeze(2), v.unsqueeze(2)
         Z, rl, ro, m, Lam, _ = self._gp_params()
         if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
             # differentiable like the reference's (autograd through :274-396): tgp_qf_moments_bwd_f64 in the backward
@@ -202,6 +243,15 @@ class sparse_MF_SP(nn.Module):
 
     def KLD(self):
         """Whitened KL (sparse_MF_SP.py:406-431), shape (Dy,); differentiable in (m, L_q) like the reference's."""
+        if self._is_multiclass:
+            kls = []
+            for c in range(self.out_dim):
+                m, Lam = self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c]
+                if torch.is_grad_enabled() and (m.requires_grad or Lam.requires_grad):
+                    kls.append(ops.KlFunction.apply(m, Lam).reshape(()))
+                else:
+                    kls.append(ops.kl_whitened(m.detach(), Lam.detach())[0].reshape(()).clone())
+            return torch.stack(kls)
         m, Lam = self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0]
         if torch.is_grad_enabled() and (m.requires_grad or Lam.requires_grad):
             return ops.KlFunction.apply(m, Lam).reshape(1)
@@ -213,6 +263,8 @@ class sparse_MF_SP(nn.Module):
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
+        if self._is_multiclass:
+            return self._elbo_multiclass(X2, Y)
         Z, rl, ro, m, Lam, lvn = self._gp_params()
         spec, theta, rowp = self._flow_inputs(X2, with_grad=True)
         cfg = self._cfg
@@ -231,6 +283,8 @@ class sparse_MF_SP(nn.Module):
     def ELL(self, X, Y, mean, cov):
         """N/MB * E_q(f)[log p(y|G(f))] from given moments (sparse_MF_SP.py:601-626); no autograd."""
         MB = Y.size(0)
+        if self._is_multiclass and X.dim() == 2:
+            X = X.unsqueeze(0).expand(self.out_dim, -1, -1)
         ell = self.likelihood.expected_log_prob(Y.t(), mean.squeeze(dim=2), cov.squeeze(dim=2), flow=self.G_matrix, X=X)
         return self.N / MB * ell
 
@@ -267,7 +321,7 @@ class sparse_MF_SP(nn.Module):
                 mY, cY = mY.reshape(1, S, MB), cY.reshape(1, S, MB)       # (Dy, S, MB)
                 m1 = mY.mean(1)
                 m2 = (cY + mY ** 2).mean(1) - m1 ** 2
-            elif self._is_bernoulli:
+            elif self._is_bernoulli or self._is_multiclass:      # P(y = 1) of shape (MB, 1) / P of shape (MB, C)
                 m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X3), None
             else:
                 m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), diagonal=True,
@@ -281,6 +335,17 @@ class sparse_MF_SP(nn.Module):
         MB = X.size(0)
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._require_gpu(X3)
+        if self._is_multiclass:
+            # sum_n log P[n, y_n] in float64, P and its logarithm from one tgp_predict_softmax_f64 launch (the reference goes
+            # through float32 and compute_calibration_measures)
+            self._eval_mode()
+            with torch.no_grad():
+                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=False)
+                P, lp = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X3,
+                                                         Y=Y.reshape(-1).to(mean_q_f.dtype))
+            assert torch.isfinite(lp).all(), "Got saturated probabilities"
+            self.train()
+            return lp.sum().reshape(1), ([P] if return_moments else None)
         if self._is_bernoulli:
             # sum_n y log P + (1 - y) log(1 - P) in float64 (the reference takes it through float32 and
             # compute_calibration_measures), P as predictive_distribution returns it (MC mean when fully Bayesian)

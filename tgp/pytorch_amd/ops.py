@@ -657,6 +657,111 @@ class EllWarpFunction(torch.autograd.Function):
         return None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has else None, None
 
 
+class SoftmaxSpec:
+    """The C flow programs of a multi-class model, one after the other (tgp_softmax.program / blk_off / theta_off): block
+    offsets stay relative to each class's own parameters; theta is the concatenation of the classes' shared scalars."""
+
+    def __init__(self, flows):
+        self.C = len(flows)
+        if any(f.RP for f in flows):
+            raise L.TgpError("the multi-class likelihood takes shared flow parameters only (no input-dependent blocks)")
+        self.flows = list(flows)
+        blocks = [b for f in flows for b in f.blocks]
+        self.nblk = len(blocks)
+        self.P = sum(f.P for f in flows)
+        self.program = np.ascontiguousarray(np.array(blocks if blocks else [(0, 0, 0, 0)], dtype=np.int32))
+        self.blk_off = np.ascontiguousarray(np.cumsum([0] + [f.nblk for f in flows]), dtype=np.int32)
+        self.theta_off = np.ascontiguousarray(np.cumsum([0] + [f.P for f in flows]), dtype=np.int32)
+
+
+def _softmax_desc(spec, N, S, theta, scale=1.0, seed=0, step_dev=None, row0=0):
+    import ctypes
+    d = L.TgpSoftmax()
+    d.N, d.C, d.S = int(N), int(spec.C), int(S)
+    d.program = ctypes.c_void_p(spec.program.ctypes.data) if spec.nblk else None
+    d.blk_off = ctypes.c_void_p(spec.blk_off.ctypes.data)
+    d.theta_off = ctypes.c_void_p(spec.theta_off.ctypes.data)
+    d.theta = L.ptr(theta) if spec.P > 0 else None
+    d.scale, d.seed, d.row0 = float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0)
+    d.step_dev = L.ptr(step_dev)
+    return d
+
+
+def _softmax_args(Y, mu, v, spec, theta, eps, S):
+    mu, v, theta, eps = _c(mu, "mu"), _c(v, "v"), _c(theta, "theta"), _c(eps, "eps")
+    if mu.dim() != 2 or mu.shape[0] != spec.C or v.shape != mu.shape:
+        raise ValueError("mu, v must be (C, N) with C = %d" % spec.C)
+    N = mu.shape[1]
+    if eps is not None and tuple(eps.shape) != (int(S), spec.C, N):
+        raise ValueError("eps must be (S, C, N) = (%d, %d, %d), got %s" % (S, spec.C, N, tuple(eps.shape)))
+    if Y is not None:
+        Y = _c(Y.reshape(-1).to(torch.float64), "Y")
+        if Y.numel() != N:
+            raise ValueError("Y must have one label per row")
+    if spec.P > 0 and (theta is None or theta.numel() != spec.P):
+        raise ValueError("theta must hold the %d shared scalars of the C programs" % spec.P)
+    return Y, mu, v, theta, eps, N
+
+
+def ell_softmax(Y, mu, v, spec, theta, S, eps=None, seed=0, step_dev=None, row0=0, scale=1.0, want_grads=True):
+    """Multi-class ELL (likelihoods/MulticlassCategorical.py:51-105) and its gradients in one launch (tgp_ell_softmax_f64).
+    mu, v (C,N); Y (N) class indices; eps (S,C,N) standard normals or None: counter-based draws of (seed, step_dev, row0).
+    Returns dict(ell, g_mu, g_v, g_theta)."""
+    lib = L.load()
+    Y, mu, v, theta, eps, N = _softmax_args(Y, mu, v, spec, theta, eps, S)
+    dev = mu.device
+    d = _softmax_desc(spec, N, S, theta, scale, seed, step_dev, row0)
+    ws = torch.empty(lib.tgp_ell_softmax_workspace_bytes(N, spec.P) // 8 + 16, dtype=torch.float64, device=dev)
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    gmu = gv = gth = None
+    if want_grads:
+        gmu, gv = torch.empty_like(mu), torch.empty_like(v)
+        gth = torch.empty(max(spec.P, 1), dtype=torch.float64, device=dev)
+    L.check(lib.tgp_ell_softmax_f64(d, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(eps), L.ptr(out), L.ptr(gmu), L.ptr(gv), L.ptr(gth),
+                                    L.ptr(ws), ws.numel() * 8, L.stream_ptr()), "tgp_ell_softmax_f64")
+    return {"ell": out[0], "g_mu": gmu, "g_v": gv, "g_theta": gth[:spec.P] if gth is not None else None}
+
+
+def mc_normals(S, C, N, seed=0, step_dev=None, row0=0, device="cuda"):
+    """The (S,C,N) standard normals the counter mode of ell_softmax / predict_softmax draws (tgp_mc_normals_f64)."""
+    import ctypes
+    d = L.TgpSoftmax()
+    d.N, d.C, d.S, d.seed, d.row0, d.step_dev = int(N), int(C), int(S), int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), L.ptr(step_dev)
+    eps = torch.empty(int(S), int(C), int(N), dtype=torch.float64, device=device)
+    L.check(L.load().tgp_mc_normals_f64(d, L.ptr(eps), L.stream_ptr()), "tgp_mc_normals_f64")
+    return eps
+
+
+def predict_softmax(mu, v, spec, theta, S, eps=None, seed=0, step_dev=None, row0=0, Y=None):
+    """P (N,C) = Monte-Carlo mean of softmax(G(f0)) (MulticlassCategorical.marginal_moments) and, with Y, log P[n, y_n]."""
+    Y, mu, v, theta, eps, N = _softmax_args(Y, mu, v, spec, theta, eps, S)
+    d = _softmax_desc(spec, N, S, theta, 1.0, seed, step_dev, row0)
+    P = torch.empty(N, spec.C, dtype=torch.float64, device=mu.device)
+    logp = torch.empty(N, dtype=torch.float64, device=mu.device) if Y is not None else None
+    L.check(L.load().tgp_predict_softmax_f64(d, L.ptr(mu), L.ptr(v), L.ptr(eps), L.ptr(Y), L.ptr(P), L.ptr(logp),
+                                             L.stream_ptr()), "tgp_predict_softmax_f64")
+    return P, logp
+
+
+class SoftmaxEllFunction(torch.autograd.Function):
+    """ELL = MulticlassCategorical.expected_log_prob with autograd in (mu, v, theta); mu, v (C,N).  The draws are either
+    `eps` (S,C,N) or the counter-based ones of (seed, step_dev, row0); value and gradients come from one launch."""
+
+    @staticmethod
+    def forward(ctx, Y, mu, v, theta, spec, S, eps, seed, step_dev, row0, scale):
+        res = ell_softmax(Y, mu.detach(), v.detach(), spec, theta.detach() if theta is not None else None, S, eps=eps,
+                          seed=seed, step_dev=step_dev, row0=row0, scale=scale)
+        ctx.save_for_backward(res["g_mu"], res["g_v"], res["g_theta"])
+        ctx.has = theta is not None
+        return res["ell"].reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        gmu, gv, gth = ctx.saved_tensors
+        g = g.reshape(())
+        return (None, g * gmu, g * gv, g * gth if ctx.has else None) + (None,) * 7
+
+
 def flow_inverse(t, flow, theta, rowp=None, check=True):
     """x = T^-1(t) for t of shape (S,N) or (N,) (tgp_flow_inverse_f64: closed forms, else a bracketed Newton iteration per
     block).  Returns (x, status) -- status int32[1] on the device, the number of elements that did not converge; with

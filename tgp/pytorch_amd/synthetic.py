@@ -79,6 +79,21 @@ def binary_dataset(name, seed=0):
     return X, Y.reshape(-1, 1)
 
 
+# multi-class stand-in: (rows, inputs, classes)
+BLOBS_SHAPE = (1200, 4, 4)
+
+
+def blobs_dataset(seed=0):
+    """Seeded `synthetic_blobs`: 4 Gaussian blobs in 4 dimensions, centres ~ 2 N(0, 1), unit noise, balanced labels in a
+    seeded order.  Returns numpy float64 X (n, d) and Y (n, 1) with labels in {0, .., 3}."""
+    n, d, k = BLOBS_SHAPE
+    rng = np.random.default_rng(104729 + 31 * seed)
+    centres = 2.0 * rng.standard_normal((k, d))
+    y = rng.permutation(np.arange(n) % k)
+    X = centres[y] + rng.standard_normal((n, d))
+    return X, y.astype(np.float64).reshape(-1, 1)
+
+
 def synthetic_problem(N, D, M, seed=0, flow="sal2", S=32, perturb=True):
     """X ~ N(0,1); Y = zscore(sin(Xw) + 0.1 x0^2 + 0.05 eps); Z = M rows of a seeded permutation; lengthscale 2,
     outputscale 2, noise 0.05; q(u): m ~ 0.5 N(0,1), Lq = sqrt(1e-5) I + 0.05 N(0,1) (dense -- the strict upper

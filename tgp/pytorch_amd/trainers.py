@@ -337,16 +337,19 @@ class Trainer_SP_regression:
 
 class Trainer_SP_classification(Trainer_SP_regression):
     """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
-    the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood."""
+    the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood.  Multi-class models
+    (MulticlassCategorical, C latent GPs) train on the eager path too, on the composed step of models._elbo_multiclass; their
+    accuracy is the argmax over the C class probabilities (trainers_classification.py:132)."""
 
     def _engine_for(self, groups, lr_ALL, opt):
-        from .likelihoods import Bernoulli
-        if isinstance(self.model.likelihood, Bernoulli):
+        from .likelihoods import Bernoulli, MulticlassCategorical
+        if isinstance(self.model.likelihood, (Bernoulli, MulticlassCategorical)):
             return None
         return super()._engine_for(groups, lr_ALL, opt)
 
     def performance_metrics(self, X, Y):
-        """(sum_n log p(y_n), number of correct labels): argmax over [1 - P, P], a tie goes to class 0."""
+        """(sum_n log p(y_n), number of correct labels): argmax over [1 - P, P] (binary) or over the C class probabilities
+        (multi-class); a tie goes to the lower class."""
         self.model.set_is_training(False)
         logp, (probs,) = self.model.test_log_likelihood(X, Y, return_moments=True, Y_std=self.Y_std.to(X.device),
                                                         S_MC_NNet=self.S_test if self.model.fully_bayesian else None)
