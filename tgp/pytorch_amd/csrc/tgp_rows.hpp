@@ -5,17 +5,19 @@
 // models/flow.py and the autograd replay of all of it, trainers/trainer_base.py:341):
 //   K_n  = sigma^2 exp(-1/2 |xs_n - zs_j|^2)                 never written to HBM
 //   A    = L^-1 K_MN      (forward substitution on MFMA)     reference: triangular_solve :380
-//   B    = L_q^T A        (upper-triangular MFMA GEMM)       reference: S = LqLq^T, matmul(S, rhs) :346,382
-//   mu   = m^T A ;  v = sigma^2 - sum A^2 + sum B^2          reference: :354-355, :376-382
+//   C    = (S - I) A      (full M x M MFMA GEMM, S = LqLq^T from the prepare launch)   reference: matmul(S, rhs) :346,382
+//   mu   = m^T A ;  v = sigma^2 + sum A o C                  reference: :354-355, :376-382
+//     (the moments-only mode, which has no way back, keeps the cheaper triangular product B = L_q^T A and
+//      v = sigma^2 - sum A^2 + sum B^2: 28 tile products instead of 49 at MT = 7)
 //   ell_n, d ell/d mu, d ell/d v, d ell/d theta, d ell/d eta  Gauss-Hermite through the flow (or closed form)
-//   Abar = m mubar^T - 2 A vbar + 2 L_q (B vbar) ; Kbar = L^-T Abar   (triangular MFMA GEMM + back substitution)
+//   Abar = m mubar^T + 2 C diag(vbar) ; Kbar = L^-T Abar    (element-wise on the C tiles + back substitution)
 // The two solves with L are SUBSTITUTIONS over 16-row tiles (round 4): A_i = Dinv_i (K_i - sum_{kb<i} L_i,kb A_kb) and
 // Kbar_i = Dinv_i^T (Abar_i - sum_{kb>i} L_kb,i^T Kbar_kb), the same MT (MT+1)/2 tile products as a product with an
 // explicit J = L^-1 and the reference's own solve shape -- so the prepare launch hands over only L, L^T and the
 // inverses of the 16 x 16 diagonal tiles, and J (which only the backward M x M chain still wants) is formed by this
 // launch's passenger blocks on CUs the row tiles leave idle.
 //   row statistics  G = A diag(vbar) A^T, s = A mubar, T = (Kbar o K) [xs, xs^2, 1]   (MFMA, via LDS transpose)
-// One workgroup = 4 waves = 64 rows; one wave owns 16 rows and keeps K, A, B, Abar, Kbar in registers:
+// One workgroup = 4 waves = 64 rows; one wave owns 16 rows and keeps K, A, C, Abar, Kbar in registers:
 // the accumulator layout of v_mfma_f64_16x16x4 is directly the B-operand layout of the next product.
 // Per-block statistics go to a slab in HBM (deterministic two-pass reduction, no atomics).
 #pragma once
@@ -333,30 +335,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const double s2 = *(ws + p.hdr + H_S2), eta = *(ws + p.hdr + H_ETA),
                einv = *(ws + p.hdr + H_EINV);
 
-  // ---- operand panels: the A operands of the four triangular products (16 columns x up to MP rows of L^T, Lq, Lq^T, L)
+  // ---- operand panels: the A operands of the two substitutions and of the product with S - I (16 columns x up to MP
+  //      rows of L^T, S, L)
   //      are staged by the whole workgroup through two LDS buffers (aliased on the transposition tile, which is
   //      only used after the products): coalesced 128-byte row segments in, conflict-free 512-byte wave reads out.
   //      Panels are prefetched TWO ahead through two register sets (the early panels feed only 4-8 MFMAs, far less
   //      than one L2 round trip), and the first two are requested here, at the top of the kernel: the K tile takes
   //      about 1 us, far less than their round trip.
   //      Panel kinds:  0 = lower-type panel i of L^T (rows [0, 16 i)) closed by -Dinv_i^T as row block i   (A = L^-1 K)
-  //                    1 = upper-type panel i of Lq  (rows [16 i, MP))                                      (B = Lq^T A)
-  //                    2 = lower-type panel i of Lq^T (rows [0, 16 (i+1)))                                  (C = Lq (B vbar))
+  //                    1 = upper-type panel i of Lq  (rows [16 i, MP))                      (moments only: B = Lq^T A)
+  //                    2 = full panel i of S - I (rows [0, MP); S is symmetric: its column panel i, read along
+  //                        the rows, IS row block i; the identity comes off while staging)      (training: C = (S - I) A)
   //                    3 = upper-type panel i of L (rows [16 (i+1), MP)) headed by -Dinv_i as row block i   (Kbar = L^-T Abar)
   const double* __restrict__ LTm = ws + p.LT;
   const double* __restrict__ Lm = ws + p.L;
   const double* __restrict__ nD = ws + p.nD;
-  const double* __restrict__ Lq = ws + p.Lq;
-  const double* __restrict__ LqT = ws + p.LqT;
+  constexpr int KIND2 = TRAIN ? 2 : 1;   // the second product's panels
+  const double* __restrict__ Sm = ws + (TRAIN ? p.S_ : p.Lq);
+  const double dg = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;   // this thread's entry of the identity in a diagonal 16 x 16 block
   double* pan = tile;  // 2 x (MP x 16)
   double stg[2][MT];
   // (row-block u of a panel exists iff u < nb with nb = i+1 (lower) / MT-i (upper): a compile-time predicate once the
   //  tile loops are unrolled -- a `row < r1` test would cost an exec-mask branch around every load and store)
   auto issue = [&](int kind, int i, double (&st)[MT]) {
-    const bool lower = kind == 0 || kind == 2;
-    const double* __restrict__ Mt = (kind == 0 ? LTm : (kind == 1 ? Lq : (kind == 2 ? LqT : Lm))) +
-                                    (size_t)((lower ? 0 : 16 * i) + (tid >> 4)) * MP + 16 * i + (tid & 15);
-    const int nb = lower ? i + 1 : MT - i;
+    const bool upper = kind == 1 || kind == 3;
+    const double* __restrict__ Mt = (kind == 0 ? LTm : (kind == 3 ? Lm : Sm)) +
+                                    (size_t)((upper ? 16 * i : 0) + (tid >> 4)) * MP + 16 * i + (tid & 15);
+    const int nb = kind == 0 ? i + 1 : (kind == 2 ? MT : MT - i);
 #pragma unroll
     for (int u = 0; u < MT; ++u)
       if (u < nb) {
@@ -365,16 +370,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         else st[u] = *(Mt + (size_t)16 * u * MP);
       }
   };
-  auto commit = [&](int par, bool lower, int i, const double (&st)[MT]) {
-    const int nb = lower ? i + 1 : MT - i;
-    double* buf = pan + par * (MP * 16) + ((lower ? 0 : 16 * i) + (tid >> 4)) * 16 + (tid & 15);
+  // (kind: as above; row block u of the panel goes to rows 16 u .. of the buffer, an upper-type panel starts at row 16 i)
+  auto commit = [&](int par, int kind, int i, const double (&st)[MT]) {
+    const bool upper = kind == 1 || kind == 3;
+    const int nb = kind == 0 ? i + 1 : (kind == 2 ? MT : MT - i);
+    double* buf = pan + par * (MP * 16) + ((upper ? 16 * i : 0) + (tid >> 4)) * 16 + (tid & 15);
 #pragma unroll
     for (int u = 0; u < MT; ++u)
-      if (u < nb) buf[16 * u * 16] = st[u];
+      if (u < nb) buf[16 * u * 16] = (kind == 2 && u == i) ? st[u] - dg : st[u];
   };
   // panel sequences of the two phases (pp = 0 .. 2 MT - 1; buffer and register set = pp & 1)
-  auto issue1 = [&](int pp, double (&st)[MT]) { if (pp < MT) issue(0, pp, st); else issue(1, pp - MT, st); };
-  auto issue2 = [&](int pp, double (&st)[MT]) { if (pp < MT) issue(2, pp, st); else issue(3, 2 * MT - 1 - pp, st); };
+  auto issue1 = [&](int pp, double (&st)[MT]) { if (pp < MT) issue(0, pp, st); else issue(KIND2, pp - MT, st); };
+  auto issue2 = [&](int pp, double (&st)[MT]) { issue(3, MT - 1 - pp, st); };   // pp = 0 .. MT - 1
   issue1(0, stg[0]);
   if (MT * 2 > 1) issue1(1, stg[1]);
   // ---- stage the small shared operands ----
@@ -438,13 +445,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
 
   ROW_STAMP(a.ws, p, 2);
-  d4 Aa[MT], Ba[MT];
+  d4 Aa[MT], Ca[MT];
   // ---- A = L^-1 K by forward substitution: A_i = Dinv_i (K_i - sum_{kb < i} L[i,kb] A_kb)  (A operand = rows of L^T,
   //      then of -Dinv_i^T; the running right-hand side starts as -K_i, which already sits in accumulator layout) ----
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const double* buf = pan + (i & 1) * (MP * 16);
-    commit(i & 1, true, i, stg[i & 1]);
+    commit(i & 1, 0, i, stg[i & 1]);
     lds_barrier();
     if (i + 2 < 2 * MT) issue1(i + 2, stg[i & 1]);
     const d4 c0 = {-Kr[4 * i], -Kr[4 * i + 1], -Kr[4 * i + 2], -Kr[4 * i + 3]};
@@ -452,28 +459,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                 [&](int st) { return Aa[st / 4][st % 4]; });
   }
   ROW_STAMP(a.ws, p, 3);
-  // ---- B = Lq^T A : B_i = sum_{kb >= i} Lq[kb,i]^T A_kb ; accumulator register r of A_kb is k-step r ----
+  // ---- C = (S - I) A : C_i = sum_kb (S - I)[kb,i]^T A_kb ; accumulator register r of A_kb is k-step r.  Both
+  //      L_q L_q^T products of the reference's q(f) -- sum (L_q^T A)^2 on the way out, L_q (L_q^T A vbar) on the way
+  //      back -- are this one product: v - sigma^2 = sum A o C and Abar - m mubar^T = 2 C diag(vbar) ----
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const double* buf = pan + ((MT + i) & 1) * (MP * 16);
-    commit((MT + i) & 1, false, i, stg[(MT + i) & 1]);
+    commit((MT + i) & 1, KIND2, i, stg[(MT + i) & 1]);
     lds_barrier();
     if (MT + i + 2 < 2 * MT) issue1(MT + i + 2, stg[(MT + i) & 1]);
-    Ba[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 4 * i, 4 * (MT - i), [&](int st) { return Aa[i + st / 4][st % 4]; });
+    if constexpr (TRAIN) Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 0, 4 * MT, [&](int st) { return Aa[st / 4][st % 4]; });
+    else   // moments only: B_i = sum_{kb >= i} Lq[kb,i]^T A_kb
+      Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 4 * i, 4 * (MT - i), [&](int st) { return Aa[i + st / 4][st % 4]; });
   }
   ROW_STAMP(a.ws, p, 4);
   // ---- mu, v ----
-  double pm = 0.0, pa = 0.0, pb = 0.0;
+  double pm = 0.0, pa = 0.0, pc = 0.0;
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       pm += mv[16 * i + 4 * r + q] * Aa[i][r];
-      pa += Aa[i][r] * Aa[i][r];
-      pb += Ba[i][r] * Ba[i][r];
+      if constexpr (TRAIN) pc += Aa[i][r] * Ca[i][r];
+      else { pa += Aa[i][r] * Aa[i][r]; pc += Ca[i][r] * Ca[i][r]; }
     }
-  pm = quad_sum(pm); pa = quad_sum(pa); pb = quad_sum(pb);
-  const double mu = pm, v = s2 - pa + pb;
+  pm = quad_sum(pm); pc = quad_sum(pc);
+  if constexpr (!TRAIN) pa = quad_sum(pa);
+  const double mu = pm, v = TRAIN ? s2 + pc : s2 - pa + pc;
   if (a.mu != nullptr && q == 0 && valid) { a.mu[n] = mu; a.v[n] = v; }
   if (!TRAIN) return;
 
@@ -633,35 +645,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   if (p.lik != TGP_LIK_FLOW && !valid) { mub = 0.0; vb = 0.0; ellp = 0.0; etap = 0.0; }
 
   ROW_STAMP(a.ws, p, 6);
-  // ---- Abar = m mubar^T - 2 A vbar + 2 Lq (B vbar) ;  Kbar = L^-T Abar ----
-#pragma unroll
-  for (int i = 0; i < MT; ++i) Ba[i] *= vb;
-  d4 Ca[MT];
-  lds_barrier();  // every wave is done with the flow stack / forward panels before the region is overwritten
+  // ---- Abar = m mubar^T + 2 C diag(vbar) (kept negated: the substitution's right-hand side starts as -Abar_i) ;
+  //      Kbar = L^-T Abar ----
   issue2(0, stg[0]);
-  issue2(1, stg[1]);
+  if (MT > 1) issue2(1, stg[1]);
+  {
+    const double nmub = -mub, nvb2 = -2.0 * vb;
 #pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const double* buf = pan + (i & 1) * (MP * 16);
-    commit(i & 1, true, i, stg[i & 1]);
-    lds_barrier();
-    if (i + 2 < 2 * MT) issue2(i + 2, stg[i & 1]);
-    Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 0, 4 * (i + 1), [&](int st) { return Ba[st / 4][st % 4]; });
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Ca[i][r] = mv[16 * i + 4 * r + q] * nmub + nvb2 * Ca[i][r];
   }
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Ca[i][r] = mv[16 * i + 4 * r + q] * mub - 2.0 * Aa[i][r] * vb + 2.0 * Ca[i][r];
+  d4 Ba[MT];
+  lds_barrier();  // every wave is done with the flow stack / forward panels before the region is overwritten
   // back substitution, last tile first: Kbar_i = Dinv_i^T (Abar_i - sum_{kb > i} L[kb,i]^T Kbar_kb), the finished tiles
   // taken in the order kb = MT-1 .. i+1 so that the freshest one is the last operand
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
-    const int i = MT - 1 - t, pp = MT + t;
+    const int i = MT - 1 - t, pp = t;
     const double* buf = pan + (pp & 1) * (MP * 16);
-    commit(pp & 1, false, i, stg[pp & 1]);
+    commit(pp & 1, 3, i, stg[pp & 1]);
     lds_barrier();
-    if (pp + 2 < 2 * MT) issue2(pp + 2, stg[pp & 1]);
-    Ba[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * (MT - 1 - i), 4 * i, -Ca[i],
+    if (pp + 2 < MT) issue2(pp + 2, stg[pp & 1]);
+    Ba[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * (MT - 1 - i), 4 * i, Ca[i],
                                 [&](int st) { return 4 * (MT - 1 - st / 4) + st % 4; },
                                 [&](int st) { return Ba[MT - 1 - st / 4][st % 4]; });  // Kbar
   }
