@@ -255,6 +255,25 @@ int tgp_elbo_step_adam_f64(const tgp_model* model, const double* X, const double
 int tgp_qf_moments_f64(const tgp_model* model, const double* X, double* mu, double* v, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* Full-covariance q(f): sparse_MF_SP.marginal_variational_qf_parameters, models/sparse_MF_SP.py:274-396, whitened,
+ * diagonal=False (:384).  With A = L^-1 K(Z, X), L L^T = K_MM + jitter I, L_q = tril(Lam):
+ *   mu = A^T m,   Sigma = K(X, X) + A^T (L_q L_q^T - I) A      (N x N, dense, no padding; Sigma[i][j] == Sigma[j][i] bit for bit)
+ * Uses model->{N,D,M,kernel,jitter,Z,raw_ls,raw_os,m,Lam}; lik / flow fields ignored.  mu (N), Sigma (N,N) symmetric.
+ * status[0] is tgp_cholesky_f64's (pivot of K_MM; the host runs the jitter ladder as for tgp_qf_moments_f64).
+ * Limits: 1 <= N <= TGP_BIG_MAX_M, 1 <= M <= TGP_BIG_MAX_M, 1 <= D <= 16, else TGP_E_UNSUPPORTED; a workspace below
+ * tgp_qf_cov_workspace_bytes gives TGP_E_WORKSPACE (tgp_last_error() names the entry in both cases).  No float atomics,
+ * fixed reduction orders: two calls on the same input return the same bits. */
+size_t tgp_qf_cov_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* Sigma, int32_t* status,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* Joint draws from N(mu, Sigma): L_Sigma = chol(Sigma + jitter I) (tgp_cholesky_f64's status convention: status[0] = pivot),
+ * F0 (S,N) = mu + eps L_Sigma^T for the caller's standard normals eps (S,N) -- sample-major, the layout X.repeat(1, S, 1)
+ * gives on the diagonal path.  Lsig (N,N): optional output (NULL to skip).  1 <= N <= TGP_BIG_MAX_M, 1 <= S <= 4096. */
+size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S);
+int tgp_qf_joint_sample_f64(const double* mu, const double* Sigma, int32_t N, double jitter, const double* eps, int32_t S,
+                            double* F0, double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Adjoint of tgp_cholesky_f64 (what autograd replays for torch.cholesky inside psd_safe_cholesky, dsp/utils.py:239, when a
  * caller differentiates through the factor outside ELBO()): given L, Linv = L^-1 (both as tgp_cholesky_f64 returns them)
  * and L_bar (M x M; its part on and below the diagonal counts) it writes the SYMMETRIC

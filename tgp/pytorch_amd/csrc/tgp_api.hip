@@ -328,6 +328,44 @@ int tgp_qf_moments_f64(const tgp_model* model, const double* X, double* mu, doub
   return launch_rows(p, md, fp, X, nullptr, nullptr, nullptr, mu, v, ws, false, st);
 }
 
+size_t tgp_qf_cov_workspace_bytes(int32_t N, int32_t D, int32_t M) { return qf_cov_workspace_bytes(N, D, M); }
+
+int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (model->kernel != TGP_KERNEL_SCALE_RBF && model->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (qf_cov_workspace_bytes(model->N, model->D, model->M) == 0) {
+    set_error_text("tgp_qf_cov_f64: N = %d, D = %d, M = %d outside 1 <= N, M <= %d, 1 <= D <= 16", model->N, model->D, model->M,
+                   TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os || !model->m || !model->Lam) return -1;
+  if (!X) return -2;
+  if (!mu) return -3;
+  if (!Sigma) return -4;
+  if (!status) return -5;
+  if (!workspace) return -6;
+  return launch_qf_cov(*model, X, mu, Sigma, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S) { return qf_joint_sample_workspace_bytes(N, S); }
+
+int tgp_qf_joint_sample_f64(const double* mu, const double* Sigma, int32_t N, double jitter, const double* eps, int32_t S,
+                            double* F0, double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (qf_joint_sample_workspace_bytes(N, S) == 0) {
+    set_error_text("tgp_qf_joint_sample_f64: N = %d, S = %d outside 1 <= N <= %d, 1 <= S <= 4096", N, S, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!mu) return -1;
+  if (!Sigma) return -2;
+  if (!eps) return -5;
+  if (!F0) return -7;
+  if (!status) return -9;
+  if (!workspace) return -10;
+  return launch_qf_joint_sample(mu, Sigma, N, jitter, eps, S, F0, Lsig, status, workspace, workspace_bytes,
+                                static_cast<hipStream_t>(stream));
+}
+
 int tgp_qf_moments_bwd_f64(const tgp_model* model, const double* X, const double* mu_bar, const double* v_bar,
                            const tgp_grads* grads, int32_t* status, void* workspace, size_t workspace_bytes,
                            void* stream) {

@@ -1,0 +1,393 @@
+// tgp_cov.hip -- full-covariance q(f) and joint function draws (tgp_qf_cov_f64, tgp_qf_joint_sample_f64).
+//
+// sparse_MF_SP.marginal_variational_qf_parameters with diagonal=False (models/sparse_MF_SP.py:384), whitened q(u):
+//   A = L^-1 K(Z, X*)   (M x N),   L_q = tril(Lam),   W = L_q L_q^T - I
+//   mu = A^T m,   Sigma = K(X*, X*) + A^T W A          (the row kernel's (S - I) A form, for all pairs of rows)
+// and a joint draw  F0 = mu + E chol(Sigma + jitter I)^T  for caller-supplied standard normals E (S x N).
+//
+// Launch sequence of tgp_qf_cov_f64 (one stream, no host sync; operands padded to multiples of 128 in the workspace):
+//   K_MM + jitter I, its factor and L^-1      the existing launchers (launch_kernel_matrix, launch_cholesky / launch_big_cholesky)
+//   k_cov_prep      L_q (tril, zero padded), W := -I,  L^-1 copied into its padded image
+//   W += L_q L_q^T  launch_gemm_plain
+//   k_cov_a         A = L^-1 K(Z, X*), the K(Z, X*) tiles generated in LDS; mu = A^T m in the same pass
+//   C = W A         launch_gemm_plain
+//   k_cov_sigma     Sigma tile (i, j), j <= i: sum_m A[m,i] C[m,j] on the matrix cores + K(x_i, x_j) in the epilogue, mirrored
+// tgp_qf_joint_sample_f64:  k_joint_jit (Sigma + jitter I) -> the existing Cholesky -> k_joint_draw.
+// Every reduction has a fixed order and nothing is accumulated with atomics: two runs on the same input are bit-identical.
+#include "tgp_dev.hpp"
+#include "tgp_launch.hpp"
+
+namespace tgp {
+
+#define LAUNCH_CHECK()                                   \
+  do {                                                   \
+    hipError_t e_ = hipGetLastError();                   \
+    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
+  } while (0)
+
+#define COV_T 64    /* output tile (rows and columns) of k_cov_a, k_cov_sigma and the column tile of k_joint_draw */
+#define COV_KC 16   /* contraction indices staged per step                                                        */
+#define COV_LDN 80  /* LDS stride (f64) of a [16 k][64 n] operand tile: the 4 k rows of one MFMA operand fall in distinct banks */
+#define COV_LDK 18  /* LDS stride (f64) of a [64 r][16 k] operand tile: 16 rows x 2 k of a half wave in distinct banks      */
+#define COV_LDT 65  /* LDS stride (f64) of the 64 x 64 output tile: conflict-free along rows and along columns              */
+
+// L_q = tril(Lam) and L^-1 in their zero-padded (MP x MP) images, W = -I on the first M diagonal entries (the product
+// L_q L_q^T is added by the GEMM that follows).
+__global__ __launch_bounds__(256) void k_cov_prep(const double* __restrict__ Lam, const double* __restrict__ Linv, int M, int MP,
+                                                   double* __restrict__ Lq, double* __restrict__ W, double* __restrict__ LinvP) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int row = (int)(e / MP), col = (int)(e % MP);
+  const bool in = row < M && col <= row;
+  const size_t s = (size_t)row * M + col;
+  Lq[e] = in ? Lam[s] : 0.0;
+  LinvP[e] = in ? Linv[s] : 0.0;
+  W[e] = (row == col && row < M) ? -1.0 : 0.0;
+}
+
+// A = L^-1 K(Z, X*) and mu = A^T m.  One workgroup per block of 64 columns (rows of X*); it walks the rows of A in groups of
+// 64, so that mu is summed in one fixed order.  Per step of 16 contraction indices the tile of L^-1 is staged with 16-byte
+// loads and the 16 x 64 tile of K(Z, X*) is evaluated into LDS from the scaled rows (the element function of tgp_dev.hpp);
+// wave w owns columns 16 w .. 16 w + 15 and the four 16-row tiles of the group.  L^-1 is lower triangular: the contraction
+// stops at the group's last row.  Rows m >= M of A come out as exact zeros (their rows of the padded L^-1 are zero),
+// columns n >= N are written as zeros.
+__global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restrict__ X, int N, const double* __restrict__ Z, int M,
+                                                int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                                const double* __restrict__ LinvP, int MP, const double* __restrict__ mvec,
+                                                double* __restrict__ A, int NP, double* __restrict__ mu) {
+  __shared__ __attribute__((aligned(16))) double Ls[COV_T * COV_LDK];
+  __shared__ double Kt[COV_KC * COV_LDN];
+  __shared__ double xsT[16 * COV_T];  // [d][column]: scaled rows of X*
+  __shared__ double red[256];
+  __shared__ double ils[17];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int n0 = blockIdx.x * COV_T;
+  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
+  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  __syncthreads();
+  for (int i = tid; i < 16 * COV_T; i += 256) {
+    const int d = i >> 6, c = i & 63;
+    const int n = n0 + c < N ? n0 + c : N - 1;  // clamped: columns past N are computed and never stored
+    xsT[i] = d < D ? X[(size_t)n * D + d] * ils[d] : 0.0;
+  }
+  __syncthreads();
+  const double s2 = ils[16];
+  const int gk = tid >> 4, gc = tid & 15;  // generation role: contraction index gk of the step, columns gc + 16 u
+  const int M16 = (M + 15) / 16 * 16;
+  double mup = 0.0;
+  for (int mg = 0; mg < MP; mg += COV_T) {
+    d4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
+    const int kend = mg < M ? (mg + COV_T < M16 ? mg + COV_T : M16) : 0;
+    for (int k0 = 0; k0 < kend; k0 += COV_KC) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {  // 64 rows x 16 k of L^-1: 512 pairs
+        const int idx = tid + 256 * u, r = idx >> 3, c2 = (idx & 7) * 2;
+        *reinterpret_cast<double2*>(Ls + r * COV_LDK + c2) =
+            *reinterpret_cast<const double2*>(LinvP + (size_t)(mg + r) * MP + k0 + c2);
+      }
+      {
+        const int kz = k0 + gk < M ? k0 + gk : M - 1;  // clamped: its row of L^-1 is zero
+        double z[16];
+#pragma unroll
+        for (int d = 0; d < 16; ++d) z[d] = d < D ? Z[(size_t)kz * D + d] * ils[d] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = gc + 16 * u;
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 16; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
+            const double t = xsT[d * COV_T + c] - z[d];
+            d2 += t * t;
+          }
+          Kt[gk * COV_LDN + c] = cov_value(kernel, s2, d2);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const double b = Kt[(kk * 4 + lq) * COV_LDN + 16 * w + lr];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = TGP_MFMA(Ls[(16 * t + lr) * COV_LDK + kk * 4 + lq], b, acc[t]);
+      }
+      __syncthreads();
+    }
+    const int n = n0 + 16 * w + lr;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = mg + 16 * t + lq + 4 * r;
+        const double val = n < N ? acc[t][r] : 0.0;
+        A[(size_t)m * NP + n] = val;
+        mup += val * (m < M ? mvec[m] : 0.0);
+      }
+  }
+  red[tid] = mup;
+  __syncthreads();
+  if (tid < 64) {
+    const int w2 = tid >> 4, c = tid & 15, n = n0 + tid;
+    const double s = ((red[w2 * 64 + c] + red[w2 * 64 + 16 + c]) + red[w2 * 64 + 32 + c]) + red[w2 * 64 + 48 + c];
+    if (n < N) mu[n] = s;
+  }
+}
+
+// Sigma tile (ti, tj), tj <= ti:  sum_m A[m,i] C[m,j]  +  K(x_i, x_j).  The [16 m][64] tiles of A and C are staged through LDS
+// with 16-byte loads (the next step's loads are in flight while this step's MFMAs run); wave w holds rows 16 w .. 16 w + 15 of
+// the tile against all 64 columns in four accumulators.  The epilogue adds the covariance of the two rows, parks the tile in
+// LDS and writes it twice with coalesced stores: as (i, j) and transposed as (j, i).  A diagonal tile writes element (r, c)
+// from the value computed for (max(r, c), min(r, c)): Sigma[i,j] == Sigma[j,i] bit for bit.  Rows and columns past N are masked.
+__global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __restrict__ X, int N, int D,
+                                                    const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                                    const double* __restrict__ A, const double* __restrict__ C, int M16, int NP,
+                                                    double* __restrict__ Sigma) {
+  __shared__ __attribute__((aligned(16))) double buf[COV_T * COV_LDT];  // operand tiles (2 x 16 x 80), then the output tile
+  __shared__ double xiT[16 * COV_T], xjT[16 * COV_T];
+  __shared__ double ils[17];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int t = blockIdx.x;
+  int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+  while (ti * (ti + 1) / 2 > t) --ti;
+  const int tj = t - ti * (ti + 1) / 2;
+  const int i0 = ti * COV_T, j0 = tj * COV_T;
+  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
+  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  __syncthreads();
+  for (int i = tid; i < 16 * COV_T; i += 256) {
+    const int d = i >> 6, c = i & 63;
+    const int ni = i0 + c < N ? i0 + c : N - 1, nj = j0 + c < N ? j0 + c : N - 1;
+    xiT[i] = d < D ? X[(size_t)ni * D + d] * ils[d] : 0.0;
+    xjT[i] = d < D ? X[(size_t)nj * D + d] * ils[d] : 0.0;
+  }
+  const double s2 = ils[16];
+  double* At = buf;
+  double* Ct = buf + COV_KC * COV_LDN;
+  d4 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+  // (element pair u of a thread: row pr + 8 u of the step, columns pc2, pc2 + 1)
+  const int pr = tid >> 5, pc2 = (tid & 31) * 2;
+  const double* Ag = A + (size_t)pr * NP + i0 + pc2;
+  const double* Cg = C + (size_t)pr * NP + j0 + pc2;
+  const size_t half = (size_t)8 * NP;
+  double2 pa0 = *reinterpret_cast<const double2*>(Ag), pa1 = *reinterpret_cast<const double2*>(Ag + half);
+  double2 pc0 = *reinterpret_cast<const double2*>(Cg), pc1 = *reinterpret_cast<const double2*>(Cg + half);
+  for (int k0 = 0; k0 < M16; k0 += COV_KC) {
+    *reinterpret_cast<double2*>(At + pr * COV_LDN + pc2) = pa0;
+    *reinterpret_cast<double2*>(At + (pr + 8) * COV_LDN + pc2) = pa1;
+    *reinterpret_cast<double2*>(Ct + pr * COV_LDN + pc2) = pc0;
+    *reinterpret_cast<double2*>(Ct + (pr + 8) * COV_LDN + pc2) = pc1;
+    __syncthreads();
+    if (k0 + COV_KC < M16) {
+      Ag += (size_t)COV_KC * NP;
+      Cg += (size_t)COV_KC * NP;
+      pa0 = *reinterpret_cast<const double2*>(Ag);
+      pa1 = *reinterpret_cast<const double2*>(Ag + half);
+      pc0 = *reinterpret_cast<const double2*>(Cg);
+      pc1 = *reinterpret_cast<const double2*>(Cg + half);
+    }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const double a = At[(kk * 4 + lq) * COV_LDN + 16 * w + lr];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Ct[(kk * 4 + lq) * COV_LDN + 16 * c + lr], acc[c]);
+    }
+    __syncthreads();
+  }
+  // epilogue: + K(x_i, x_j), tile to LDS
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int il = 16 * w + lq + 4 * r, jl = 16 * c + lr;
+      double d2 = 0.0;
+#pragma unroll
+      for (int d = 0; d < 16; ++d) {
+        const double u = xiT[d * COV_T + il] - xjT[d * COV_T + jl];
+        d2 += u * u;
+      }
+      buf[il * COV_LDT + jl] = cov_value(kernel, s2, d2) + acc[c][r];
+    }
+  __syncthreads();
+  if (ti != tj) {
+    for (int e = tid; e < COV_T * COV_T; e += 256) {
+      const int r = e >> 6, c = e & 63;
+      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(i0 + r) * N + j0 + c] = buf[r * COV_LDT + c];
+    }
+    for (int e = tid; e < COV_T * COV_T; e += 256) {
+      const int c = e >> 6, r = e & 63;
+      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(j0 + c) * N + i0 + r] = buf[r * COV_LDT + c];
+    }
+  } else {
+    for (int e = tid; e < COV_T * COV_T; e += 256) {
+      const int r = e >> 6, c = e & 63;
+      const int hi = r > c ? r : c, lo = r > c ? c : r;
+      if (i0 + r < N && i0 + c < N) Sigma[(size_t)(i0 + r) * N + i0 + c] = buf[hi * COV_LDT + lo];
+    }
+  }
+}
+
+// Sj = Sigma + jitter I (the matrix the joint draw factorises)
+__global__ __launch_bounds__(256) void k_joint_jit(const double* __restrict__ Sigma, int N, double jitter, double* __restrict__ Sj) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)N * N) return;
+  Sj[e] = Sigma[e] + ((int)(e / N) == (int)(e % N) ? jitter : 0.0);
+}
+
+// F0 = mu + E L^T, E (S, N) standard normals, L (N, N) lower, F0 (S, N).  Workgroup = 16 samples x 64 columns, wave w the columns
+// 16 w .. 16 w + 15; L is lower triangular, so the contraction stops at the tile's last column.  Tails in S, N and k are zero
+// filled when the operands are staged.
+__global__ __launch_bounds__(256) void k_joint_draw(const double* __restrict__ mu, const double* __restrict__ L, int N,
+                                                     const double* __restrict__ E, int S, double* __restrict__ F0) {
+  __shared__ double Et[16 * COV_LDK];
+  __shared__ double Lt[COV_T * COV_LDK];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int n0 = blockIdx.x * COV_T, s0 = blockIdx.y * 16;
+  const int kend = n0 + COV_T < N ? n0 + COV_T : N;
+  d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < kend; k0 += COV_KC) {
+    {
+      const int r = tid >> 4, c = tid & 15, s = s0 + r, k = k0 + c;
+      Et[r * COV_LDK + c] = (s < S && k < N) ? E[(size_t)s * N + k] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = tid + 256 * u, r = idx >> 4, c = idx & 15, n = n0 + r, k = k0 + c;
+      Lt[r * COV_LDK + c] = (n < N && k <= n) ? L[(size_t)n * N + k] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+      acc = TGP_MFMA(Et[lr * COV_LDK + kk * 4 + lq], Lt[(16 * w + lr) * COV_LDK + kk * 4 + lq], acc);
+    __syncthreads();
+  }
+  const int n = n0 + 16 * w + lr;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int s = s0 + lq + 4 * r;
+    if (s < S && n < N) F0[(size_t)s * N + n] = mu[n] + acc[r];
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+namespace {
+struct CovPlan {  // offsets in doubles, every section a multiple of 64 doubles
+  int MP, NP;
+  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, Lq, W, A, C, total;
+};
+bool cov_plan(CovPlan& p, int N, int D, int M) {
+  if (N < 1 || N > TGP_BIG_MAX_M || M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
+  p.MP = (int)rup((size_t)M, 128);
+  p.NP = (int)rup((size_t)N, 128);
+  const size_t mm = rup((size_t)M * M, 64), pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
+  p.chol_len = M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0;
+  size_t o = 0;
+  p.Kmm = o; o += mm;
+  p.Lf = o; o += mm;
+  p.Linv = o; o += mm;
+  p.chol = o; o += p.chol_len;
+  p.LinvP = o; o += pp;
+  p.Lq = o; o += pp;
+  p.W = o; o += pp;
+  p.A = o; o += pn;
+  p.C = o; o += pn;
+  p.total = o;
+  return true;
+}
+struct DrawPlan {
+  size_t Sj, Lf, chol, chol_len, total;
+};
+bool draw_plan(DrawPlan& p, int N, int S) {
+  if (N < 1 || N > TGP_BIG_MAX_M || S < 1 || S > 4096) return false;
+  const size_t nn = rup((size_t)N * N, 64);
+  p.chol_len = N > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(N), 64) : 0;
+  size_t o = 0;
+  p.Sj = o; o += nn;
+  p.Lf = o; o += nn;
+  p.chol = o; o += p.chol_len;
+  p.total = o;
+  return true;
+}
+// the workspace's first 16-byte aligned double (the byte counts below include the slack)
+double* align16(void* ws, size_t bytes, size_t* doubles) {
+  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
+  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
+  *doubles = bytes > skip ? (bytes - skip) / sizeof(double) : 0;
+  return reinterpret_cast<double*>(a);
+}
+int factorise(const double* A, int M, double* Lo, double* Jo, int32_t* status, double* cws, size_t cws_len, hipStream_t st) {
+  if (M > TGP_FUSED_MAX_M) return launch_big_cholesky(A, M, Lo, Jo, status, cws, cws_len, st);
+  return launch_cholesky(A, M, Lo, Jo, status, st);
+}
+}  // namespace
+
+size_t qf_cov_workspace_bytes(int N, int D, int M) {
+  CovPlan p;
+  if (!cov_plan(p, N, D, M)) return 0;
+  return p.total * sizeof(double) + 16;
+}
+
+size_t qf_joint_sample_workspace_bytes(int N, int S) {
+  DrawPlan p;
+  if (!draw_plan(p, N, S)) return 0;
+  return p.total * sizeof(double) + 16;
+}
+
+int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
+                  size_t workspace_bytes, hipStream_t st) {
+  CovPlan p;
+  if (!cov_plan(p, md.N, md.D, md.M)) {
+    set_error_text("tgp_qf_cov_f64: N = %d, D = %d, M = %d outside 1 <= N, M <= %d, 1 <= D <= 16", md.N, md.D, md.M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  size_t have = 0;
+  double* ws = align16(workspace, workspace_bytes, &have);
+  if (have < p.total) {
+    set_error_text("tgp_qf_cov_f64: workspace of %zu bytes, tgp_qf_cov_workspace_bytes gives %zu", workspace_bytes,
+                   p.total * sizeof(double) + 16);
+    return TGP_E_WORKSPACE;
+  }
+  const int N = md.N, D = md.D, M = md.M, MP = p.MP, NP = p.NP;
+  if (int rc = launch_kernel_matrix(md.kernel, md.Z, M, nullptr, 0, D, md.raw_ls, md.raw_os, md.jitter, ws + p.Kmm, st)) return rc;
+  if (int rc = factorise(ws + p.Kmm, M, ws + p.Lf, ws + p.Linv, status, ws + p.chol, p.chol_len, st)) return rc;
+  hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, md.Lam, ws + p.Linv, M, MP, ws + p.Lq,
+                     ws + p.W, ws + p.LinvP);
+  LAUNCH_CHECK();
+  if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.Lq, MP, ws + p.Lq, MP, 1.0, ws + p.W, MP, st)) return rc;
+  hipLaunchKernelGGL(k_cov_a, dim3((unsigned)(NP / COV_T)), dim3(256), 0, st, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os,
+                     ws + p.LinvP, MP, md.m, ws + p.A, NP, mu);
+  LAUNCH_CHECK();
+  if (int rc = launch_gemm_plain(false, false, 0, MP, NP, MP, 1.0, ws + p.W, MP, ws + p.A, NP, 0.0, ws + p.C, NP, st)) return rc;
+  const int nt = (N + COV_T - 1) / COV_T;
+  hipLaunchKernelGGL(k_cov_sigma, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, md.kernel, X, N, D, md.raw_ls, md.raw_os,
+                     ws + p.A, ws + p.C, (M + 15) / 16 * 16, NP, Sigma);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double jitter, const double* eps, int S, double* F0,
+                           double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  DrawPlan p;
+  if (!draw_plan(p, N, S)) {
+    set_error_text("tgp_qf_joint_sample_f64: N = %d, S = %d outside 1 <= N <= %d, 1 <= S <= 4096", N, S, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  size_t have = 0;
+  double* ws = align16(workspace, workspace_bytes, &have);
+  if (have < p.total) {
+    set_error_text("tgp_qf_joint_sample_f64: workspace of %zu bytes, tgp_qf_joint_sample_workspace_bytes gives %zu",
+                   workspace_bytes, p.total * sizeof(double) + 16);
+    return TGP_E_WORKSPACE;
+  }
+  double* Lf = Lsig != nullptr ? Lsig : ws + p.Lf;
+  hipLaunchKernelGGL(k_joint_jit, dim3((unsigned)(((size_t)N * N + 255) / 256)), dim3(256), 0, st, Sigma, N, jitter, ws + p.Sj);
+  LAUNCH_CHECK();
+  if (int rc = factorise(ws + p.Sj, N, Lf, nullptr, status, ws + p.chol, p.chol_len, st)) return rc;
+  hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((N + COV_T - 1) / COV_T), (unsigned)((S + 15) / 16)), dim3(256), 0, st, mu, Lf, N,
+                     eps, S, F0);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace tgp

@@ -138,4 +138,12 @@ int launch_mc_normals(const SmxArgs& a, double* eps, hipStream_t st);
 int launch_predict_softmax(const SmxArgs& a, const FlowProg& fp, const double* theta, const double* mu, const double* v,
                            const double* eps, const double* Y, double* P, double* logp, hipStream_t st);
 
+// tgp_cov.hip (full-covariance q(f): Sigma = K(X*, X*) + A^T W A, and joint draws mu + E chol(Sigma + jitter I)^T)
+size_t qf_cov_workspace_bytes(int N, int D, int M);
+int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
+                  size_t workspace_bytes, hipStream_t st);
+size_t qf_joint_sample_workspace_bytes(int N, int S);
+int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double jitter, const double* eps, int S, double* F0,
+                           double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st);
+
 }  // namespace tgp

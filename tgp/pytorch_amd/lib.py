@@ -20,6 +20,7 @@ LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 E_UNSUPPORTED = -100
+E_WORKSPACE = -101
 
 _dp = C.c_void_p
 
@@ -90,6 +91,10 @@ _SIGS = {
     "tgp_elbo_step_adam_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.POINTER(TgpGrads), _dp, _dp, _dp, _dp,
                                          C.c_size_t, C.POINTER(TgpAdamArgs), _dp]),
     "tgp_qf_moments_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_qf_cov_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "tgp_qf_cov_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_qf_joint_sample_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tgp_qf_joint_sample_f64": (C.c_int, [_dp, _dp, C.c_int32, C.c_double, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_mlp_backward_adam_f64": (C.c_int, [C.POINTER(TgpMlp), _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, C.POINTER(TgpAdamArgs),
                                             C.c_double, _dp]),
     "tgp_comm_load": (C.c_int, [C.c_char_p]),
@@ -182,7 +187,7 @@ def load():
 
 def check(rc, what):
     if rc != 0:
-        msg = load().tgp_last_error().decode() if rc in (-103, E_UNSUPPORTED) else ""
+        msg = load().tgp_last_error().decode() if rc in (-103, E_UNSUPPORTED, E_WORKSPACE) else ""
         raise TgpError("%s failed with code %d %s" % (what, rc, msg))
 
 

@@ -226,10 +226,24 @@ class sparse_MF_SP(nn.Module):
 
     # ---- model computations ------------------------------------------------------------------------
     def marginal_variational_qf_parameters(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None):
-        """q(f) marginals (sparse_MF_SP.py:274-396): returns mu, cov of shape (Dy, MB, 1)."""
-        assert diagonal and not is_duvenaud, "diagonal=True, is_duvenaud=False on this path"
+        """q(f) marginals (sparse_MF_SP.py:274-396): returns mu of shape (Dy, MB, 1) and cov of shape (Dy, MB, 1), or
+        (Dy, MB, MB) with diagonal=False -- the full covariance K_xx - K_xz K_zz^-1 K_zx + rhs^T S rhs (:384), from
+        tgp_qf_cov_f64.  The full covariance is evaluated WITHOUT autograd and both tensors come back detached; when
+        gradients are enabled and a parameter requires them the call raises (diagonal=True is the differentiable path).
+        MB <= 4096, single-output models only."""
+        assert not is_duvenaud, "is_duvenaud=False on this path"
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
+        if not diagonal:
+            if self._is_multiclass:
+                raise NotImplementedError("diagonal=False is not built for multi-class models (num_outputs = C latent GPs)")
+            Z, rl, ro, m, Lam, _ = self._gp_params()
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
+                raise NotImplementedError("the full covariance (diagonal=False) has no backward: call it under torch.no_grad(); "
+                                          "diagonal=True is the differentiable path")
+            mu, cov = ops.qf_cov(X2.detach(), *(t.detach() for t in (Z, rl, ro, m, Lam)),
+                                 kernel=self.covariance_function.hip_kernel)
+            return mu.reshape(1, -1, 1), cov.unsqueeze(0)
         if self._is_multiclass:
             mu, v = self._qf_per_class(X2)
             return mu.unsqueeze(2), v.unsqueeze(2)
@@ -404,35 +418,50 @@ class sparse_MF_SP(nn.Module):
         return log_p_y, predictive_params
 
     # ---- sampling (sparse_MF_SP.py:837-992) --------------------------------------------------------
-    def sample_from_variational_marginal_base(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None):
-        if not diagonal:
-            raise NotImplementedError("This function only works with diagonal=True")
+    def sample_from_variational_marginal_base(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None, S: int = 1):
+        """diagonal=True: one independent draw per row of X (the caller has repeated the rows S times).  diagonal=False:
+        S JOINT draws over the MB rows of X (not repeated): Sigma is formed once, eps = randn(S, MB) on the device, the draw
+        kernel gives f0 = mu + eps chol(Sigma + jitter I)^T under psd_safe_cholesky's jitter ladder (first try: jitter 0).
+        Returns f0 of shape (Dy, S * MB) in the diagonal path's sample-major layout, mean (Dy, MB, 1), cov (Dy, MB, MB)."""
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         Dy, SMB, _ = X3.shape
+        if not diagonal:
+            with torch.no_grad():
+                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=False, is_duvenaud=is_duvenaud)
+                e = torch.randn(int(S), SMB, dtype=mean_q_f.dtype, device=mean_q_f.device)
+                f0 = ops.qf_joint_sample_safe(mean_q_f.reshape(-1), cov_q_f[0], e, jitter=cg.global_jitter)
+            return f0.reshape(1, -1), mean_q_f, cov_q_f
         mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=is_duvenaud)
         e = torch.randn(Dy, SMB, 1, dtype=mean_q_f.dtype, device=mean_q_f.device)
         f = (e * cov_q_f.sqrt() + mean_q_f).squeeze(dim=2)
         return f, mean_q_f, cov_q_f
 
     def sample_from_variational_marginal(self, X, S: int, diagonal: bool, is_duvenaud: bool, init_Z=None):
+        """S function samples on the rows of X: f (Dy, S * MB) after the flows, the q(f0) moments and f0.  diagonal=False
+        draws each sample jointly over the rows (coherent functions) and returns cov_q_f0 of shape (Dy, MB, MB)."""
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
+        X1 = X3
         X3 = X3.repeat(1, S, 1)
         if self.is_training:
             self.train()
         else:
             self._eval_mode()
         with torch.no_grad():
-            f0, mean_q_f0, cov_q_f0 = self.sample_from_variational_marginal_base(X3, diagonal, is_duvenaud, init_Z)
+            if diagonal:
+                f0, mean_q_f0, cov_q_f0 = self.sample_from_variational_marginal_base(X3, diagonal, is_duvenaud, init_Z)
+            else:
+                f0, mean_q_f0, cov_q_f0 = self.sample_from_variational_marginal_base(X1, diagonal, is_duvenaud, init_Z, S=S)
             f = torch.stack([g(f0[i], X3[i]) for i, g in enumerate(self.G_matrix)], 0)
         self.train()
         return f, mean_q_f0, cov_q_f0, f0
 
-    def sample_from_predictive_distribution(self, X, S: int) -> List[torch.tensor]:
+    def sample_from_predictive_distribution(self, X, S: int, diagonal: bool = True) -> List[torch.tensor]:
+        """diagonal=False: the likelihood's noise is added to JOINT function draws (one coherent function per sample)."""
         assert not self.is_training, "This method only works in eval mode"
         assert X.dim() == 2, "Invalid input X.shape"
         N, _ = X.shape
         with torch.no_grad():
-            f_k, _, _, f_0 = self.sample_from_variational_marginal(X, S, diagonal=True, is_duvenaud=False)
+            f_k, _, _, f_0 = self.sample_from_variational_marginal(X, S, diagonal=diagonal, is_duvenaud=False)
             samples = [self.likelihood.sample_from_output(f_k, i).view(S, N, 1) for i in range(self.out_dim)]
         self.train()
         return torch.stack(samples, dim=0), f_k, f_0
@@ -451,7 +480,9 @@ class sparse_MF_GP(sparse_MF_SP):
 
     def sample_from_variational_marginal(self, X, S: int, diagonal: bool, is_duvenaud: bool, init_Z=None):
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
-        X3 = X3.repeat(1, S, 1)
         with torch.no_grad():
-            f, mean_q_f, cov_q_f = self.sample_from_variational_marginal_base(X3, diagonal, is_duvenaud, init_Z)
+            if diagonal:
+                f, mean_q_f, cov_q_f = self.sample_from_variational_marginal_base(X3.repeat(1, S, 1), diagonal, is_duvenaud, init_Z)
+            else:
+                f, mean_q_f, cov_q_f = self.sample_from_variational_marginal_base(X3, diagonal, is_duvenaud, init_Z, S=S)
         return f, mean_q_f, cov_q_f, f

@@ -286,6 +286,84 @@ def qf_moments(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="sca
     return mu, v
 
 
+def qf_cov(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_rbf", info=None, workspace_bytes=None):
+    """Full-covariance q(f) (models/sparse_MF_SP.py:274-396, diagonal=False; tgp_qf_cov_f64): returns mu (N,) and the
+    symmetric Sigma (N, N) = K(X, X) + A^T (L_q L_q^T - I) A.  No autograd.  `check`: the jitter ladder of
+    psd_safe_cholesky on K_MM, as in qf_moments; `info["jitter"]` receives the value the factorisation ended with.
+    `workspace_bytes` overrides the size of the workspace handed to the library (tests of its refusal)."""
+    lib = L.load()
+    X = _c(X, "X")
+    Z, raw_ls, raw_os, m, Lam = (_c(t, "param") for t in (Z, raw_ls, raw_os, m, Lam))
+    dev = X.device
+    N, D = X.shape
+    lvn = torch.zeros(1, dtype=torch.float64, device=dev)
+    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 1.0, None, None, None, kernel)
+    nbytes = lib.tgp_qf_cov_workspace_bytes(N, D, m.numel()) if workspace_bytes is None else int(workspace_bytes)
+    if N > 4096:       # refused by the library before anything is allocated for an N x N result
+        L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), None, None, None, None, 0, L.stream_ptr()), "tgp_qf_cov_f64")
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    mu = torch.empty(N, dtype=torch.float64, device=dev)
+    Sigma = torch.empty(N, N, dtype=torch.float64, device=dev)
+    status = torch.zeros(8, dtype=torch.int32, device=dev)
+
+    def call():
+        L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), L.ptr(mu), L.ptr(Sigma), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()),
+                "tgp_qf_cov_f64")
+    call()
+    if info is not None:
+        info["jitter"] = float(jitter)
+    if check and raise_for_status(status.cpu()):
+        for jit in jitter_ladder():
+            md.jitter = jit
+            call()
+            if not raise_for_status(status.cpu()):
+                warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
+                if info is not None:
+                    info["jitter"] = float(jit)
+                return mu, Sigma
+        raise NotPSDError("K_MM not positive definite")
+    return mu, Sigma
+
+
+def qf_joint_sample(mu, Sigma, eps, jitter=0.0, want_L=False, workspace_bytes=None):
+    """Joint draws F0 (S, N) = mu + eps chol(Sigma + jitter I)^T (tgp_qf_joint_sample_f64); eps (S, N) standard normals.
+    Returns (F0, L_Sigma or None, status): status[0] is the Cholesky's pivot (no ladder here: see qf_joint_sample_safe)."""
+    lib = L.load()
+    mu, Sigma, eps = _c(mu.reshape(-1), "mu"), _c(Sigma, "Sigma"), _c(eps, "eps")
+    N = mu.numel()
+    if Sigma.shape != (N, N) or eps.dim() != 2 or eps.shape[1] != N:
+        raise ValueError("qf_joint_sample: mu (N), Sigma (N, N), eps (S, N)")
+    S = eps.shape[0]
+    dev = mu.device
+    nbytes = lib.tgp_qf_joint_sample_workspace_bytes(N, S) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    F0 = torch.empty(S, N, dtype=torch.float64, device=dev)
+    Ls = torch.empty(N, N, dtype=torch.float64, device=dev) if want_L else None
+    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    L.check(lib.tgp_qf_joint_sample_f64(L.ptr(mu), L.ptr(Sigma), N, float(jitter), L.ptr(eps), S, L.ptr(F0), L.ptr(Ls),
+                                        L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()), "tgp_qf_joint_sample_f64")
+    return F0, Ls, status
+
+
+def qf_joint_sample_safe(mu, Sigma, eps, jitter=None, info=None):
+    """qf_joint_sample under psd_safe_cholesky's protocol (dsp/utils.py:222-270): the first factorisation with jitter 0,
+    then jitter * 10^i, i = 0..2 (1e-8 in float64 unless given).  Returns F0; `info["jitter"]` = the value that succeeded."""
+    F0, _, status = qf_joint_sample(mu, Sigma, eps, 0.0)
+    used = 0.0
+    if raise_for_status(status.cpu()):
+        for jit in jitter_ladder(jitter=jitter):
+            F0, _, status = qf_joint_sample(mu, Sigma, eps, jit)
+            if not raise_for_status(status.cpu()):
+                warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
+                used = jit
+                break
+        else:
+            raise NotPSDError("Sigma not positive definite even with jitter %g (pivot %d)" % (jit, int(status[0])))
+    if info is not None:
+        info["jitter"] = float(used)
+    return F0
+
+
 def qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, mu_bar, v_bar, jitter=0.0, kernel="scale_rbf", plan=0):
     """Adjoint of qf_moments (tgp_qf_moments_bwd_f64): d(sum mu_bar*mu + v_bar*v)/d{Z, raw_ls, raw_os, m, Lam} as a dict."""
     lib = L.load()
