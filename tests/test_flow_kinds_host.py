@@ -148,4 +148,6 @@ def test_ell_flow_instantiations():
     for lpr, nbs in ((4, (8, 4, 2, 1)), (16, (4, 2, 1)), (32, (4, 2, 1))):
         for nb in nbs:
             for x in (0, FLOWX):
-                assert any(s.startswith("_ZN3tgp10k_ell_flowILi%dELi%dEEE" % (lpr, nb | x)) for s in syms), (lpr, nb, x)
+                for lik in ("8EllGauss", "7EllBern"):       # k_ell_quad<Lik, LPR, NB | X>: both likelihoods, both kind sets
+                    assert any(s.startswith("_ZN3tgp10k_ell_quadINS_%sELi%dELi%dEEE" % (lik, lpr, nb | x)) for s in syms), \
+                        (lik, lpr, nb, x)

@@ -38,9 +38,11 @@ def _spec(program, P, RP=0):
 CASES = ["empty", "bern_med_sal_invbcl1", "bern_med_bcl_al2", "bern_med_arcsl2", "idsal"]
 
 
-@pytest.mark.parametrize("N", [300, 4000, 13000])      # 32, 16 and 4 lanes per row
+# 32, 16 and 4 lanes per row; then four nodes in flight per lane at 32 and at 16 lanes per row
+@pytest.mark.parametrize("N,S", [(300, 32), (4000, 32), (13000, 32), (300, 80), (4000, 40)],
+                         ids=["300", "4000", "13000", "300-S80", "4000-S40"])
 @pytest.mark.parametrize("case", CASES)
-def test_ell_kernel_matches_autograd(case, N):
+def test_ell_kernel_matches_autograd(case, N, S):
     from tgp.pytorch_amd import ops
     g = torch.Generator().manual_seed(N)
     mu = 1.2 * torch.randn(N, generator=g, dtype=F64)
@@ -48,7 +50,6 @@ def test_ell_kernel_matches_autograd(case, N):
     v[:7] = -1e-12                                      # clamped to 0 (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0)
     Y = (torch.rand(N, generator=g, dtype=F64) < 0.5).to(F64)
     Y[-5:] = torch.tensor([0.3, 0.5, 0.9, 0.0, 1.0])      # soft labels behave as in BCELoss
-    S = 32
     xs, ws = (torch.tensor(a) for a in np.polynomial.hermite.hermgauss(S))
     theta = rowp = None
     program, P, RP = [], 0, 0

@@ -333,7 +333,7 @@ def test_device_jitter_ladder_on_the_general_path():
 
 
 def test_big_path_ragged_last_chunk_in_the_small_problem_likelihood_mode():
-    """Chunks of 4224 rows at N = 8224: 4224 rows (4 lanes per row in k_ell_flow, 67 partials) and a ragged last chunk
+    """Chunks of 4224 rows at N = 8224: 4224 rows (4 lanes per row in k_ell_quad, 67 partials) and a ragged last chunk
     of 4000 rows (<= 4096: 16 lanes per row, 250 partials) -- the likelihood workspace is sized for either mode."""
     _chunked_cases([(8224, 4, 130, "sal2", 16)], 4224)
 

@@ -123,11 +123,12 @@ def test_boxcox_lambda_zero_is_taken_as_1e_minus_11():
 
 
 @pytest.mark.parametrize("name", ["arcsinh_r", "boxcox_f0", "invboxcox", "chain"])
-@pytest.mark.parametrize("N", [300, 5000, 20000])     # the 32-, 16- and 4-lanes-per-row variants of k_ell_flow
-def test_ell_flow_gradients_match_autograd(name, N):
+# the 32-, 16- and 4-lanes-per-row variants of k_ell_quad; then four nodes in flight per lane at 32 and at 16 lanes per row
+@pytest.mark.parametrize("N,S", [(300, 16), (5000, 16), (20000, 16), (300, 80), (4000, 40)],
+                         ids=["300", "5000", "20000", "300-S80", "4000-S40"])
+def test_ell_flow_gradients_match_autograd(name, N, S):
     from tgp.pytorch_amd import ops
     prog, th = PROGRAMS[name], torch.tensor(THETA[name], dtype=torch.float64)
-    S = 16
     g = torch.Generator().manual_seed(N)
     mu = 0.5 * torch.randn(N, generator=g, dtype=torch.float64)
     v = 0.05 + 0.1 * torch.rand(N, generator=g, dtype=torch.float64)

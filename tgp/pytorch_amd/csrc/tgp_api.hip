@@ -533,10 +533,7 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
   if (int rc = make_prog(model, true, fp)) return rc;
   tgp_model md = *model;
   md.program = nullptr;
-  if (model->lik == TGP_LIK_BERNOULLI)
-    return launch_ell_bern(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
-                           static_cast<hipStream_t>(stream));
-  return launch_ell_flow(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
+  return launch_ell_quad(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
 }
 

@@ -9,7 +9,7 @@
 //   row chunks: rows are processed NC (<= 16384) at a time; the chunk matrices are the TRANSPOSES of the DESIGN.md
 //               operands, laid out [NC][MP] (one data row = 8 KB contiguous), so that the triangular GEMMs stream
 //               contiguous 1 MB row blocks and the two reductions over rows (G, T) read k-major, fully coalesced:
-//               K' = K_NM -> A' = K' J^T -> B' = A' Lq -> (mu, v) -> likelihood (k_ell_gauss / k_ell_flow) ->
+//               K' = K_NM -> A' = K' J^T -> B' = A' Lq -> (mu, v) -> likelihood (k_ell_gauss / k_ell_quad) ->
 //               Abar' = vbar o (2 B' Lq^T - 2 A') + mubar m^T (GEMM epilogue) -> Kbar' = Abar' J ->
 //               T += (Kbar' o K')^T [xs, xs^2, 1] (split-K)   G += A'^T diag(vbar) A' (split-K SYRK)   s += A'^T mubar
 //   backward  : Lbar = -tril(w s^T + 2 H' G), Lambar = 2 tril(G Lq) - kl(...), Q = Phi(L^T Lbar) + Phi(.)^T,
@@ -21,12 +21,6 @@
 #include "tgp_prep.hpp"   // hand-off primitives (sync_wait / sync_add / st_agent / ld_agent)
 
 namespace tgp {
-
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
 
 #define BIG_XW 128    /* width of the augmented coordinate matrices [xs, xs^2, 1, 0...] */
 #define BIG_KST 32    /* split-K slabs of the T statistics GEMM */
@@ -1984,17 +1978,10 @@ int launch_big_step(const tgp_model& md, const FlowProg& fp, const double* X, co
       if (int rc = big_chunk_forward(pc, X + c0 * p.D, nrows, ws, ws + p.mu + c0, ws + p.v + c0, true, sf, early_k && ci == 0)) return rc;
       // likelihood of the chunk: partial (scale*ELL, scale*eta_bar, theta_bar) into this chunk's slot
       double* slot = ws + p.likslot + (size_t)ci * p.LS;
-      if (md.lik == TGP_LIK_FLOW) {
+      if (md.lik == TGP_LIK_FLOW || md.lik == TGP_LIK_BERNOULLI) {
         tgp_model mc = md;
         mc.N = nrows;
-        if (int rc = launch_ell_flow(mc, fp, Y + c0, ws + p.mu + c0, ws + p.v + c0, rowp ? rowp + c0 * md.RP : nullptr, slot,
-                                     ws + p.mub + c0, ws + p.vb + c0, slot + 2, g.rowp ? g.rowp + c0 * md.RP : nullptr,
-                                     ws + p.likws, sf))
-          return rc;
-      } else if (md.lik == TGP_LIK_BERNOULLI) {
-        tgp_model mc = md;
-        mc.N = nrows;
-        if (int rc = launch_ell_bern(mc, fp, Y + c0, ws + p.mu + c0, ws + p.v + c0, rowp ? rowp + c0 * md.RP : nullptr, slot,
+        if (int rc = launch_ell_quad(mc, fp, Y + c0, ws + p.mu + c0, ws + p.v + c0, rowp ? rowp + c0 * md.RP : nullptr, slot,
                                      ws + p.mub + c0, ws + p.vb + c0, slot + 2, g.rowp ? g.rowp + c0 * md.RP : nullptr,
                                      ws + p.likws, sf))
           return rc;

@@ -19,12 +19,6 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                   \
-  do {                                                   \
-    hipError_t e_ = hipGetLastError();                   \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 #define COV_T 64    /* output tile (rows and columns) of k_cov_a, k_cov_sigma and the column tile of k_joint_draw */
 #define COV_KC 16   /* contraction indices staged per step                                                        */
 #define COV_LDN 80  /* LDS stride (f64) of a [16 k][64 n] operand tile: the 4 k rows of one MFMA operand fall in distinct banks */

@@ -49,6 +49,15 @@ namespace tgp {
 __device__ __forceinline__ void st_wt(double* p, double v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Data that crosses workgroups inside one launch (the hand-offs of tgp_prep.hpp; the workgroup partials that the last
+// workgroup to take a ticket adds up in k_ell_warp / k_ell_softmax): coherent for the whole device, never through the
+// scalar cache.
+__device__ __forceinline__ double ld_agent(const double* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent(double* p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // problem plan: derived sizes + workspace offsets (in doubles).  Host and device agree through this.
@@ -602,7 +611,7 @@ __host__ __device__ __forceinline__ int flow_block_slots(int kind, int K) {
   if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH ? 3 : 2;
   return kind == TGP_FLOW_AFFINE ? 1 : (kind == TGP_FLOW_SAL ? 3 : 1 + K);
 }
-// Template-argument bit of the kernels that have an extended-kind instantiation (k_rows MODE, k_rows4 NW, k_ell_flow NB):
+// Template-argument bit of the kernels that have an extended-kind instantiation (k_rows MODE, k_rows4 NW, k_ell_quad NB):
 // set = the flow sweeps are compiled with X = true.  (A bit of an existing argument, not a new argument, so that the
 // instantiations of the original kinds keep their symbols.)
 #define TGP_FLOWX 16
@@ -631,6 +640,29 @@ __device__ __forceinline__ FlowBlk flow_blk(const int32_t* prog, int b) {
 // 1 / tp[i]: from the caller's table when there is one (the row kernel: one reciprocal chain less per tanh step)
 __device__ __forceinline__ double flow_rcp_param(const FlowDev& F, int i) {
   return F.ti != nullptr ? F.ti[i] : rcp_fast(F.tp[i]);
+}
+// Shared flow parameters into LDS for the stand-alone kernels (same rule as k_prep_a): tp = after the positivity transform,
+// tg = d(tp)/d(raw); whole block, ends with a barrier.  Per-row blocks have no shared parameters and are skipped (a softmax
+// program never holds one -- the API refuses them -- so the skip is a no-op there).
+// `ti` (optional): 1 / tp[i] for every shared parameter, so that a step-tanh step takes 1 / softplus(d_k) from the table instead of
+// running a reciprocal chain per step and sweep
+// X: the extended kind set (flow_block_params)
+template <bool X>
+__device__ inline void flow_params_lds(const double* theta, const FlowProg& fp, double* tp, double* tg, double* ti = nullptr) {
+  for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
+    const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
+    if (flags & TGP_FLAG_PER_ROW) continue;
+    const int np = flow_block_params<X>(kind, K);
+    for (int j = 0; j < np; ++j) {
+      const double x = theta[poff + j];
+      const bool res = flow_param_restricted<X>(kind, flags, j);
+      const double tv = res ? softplus_d(x) : x;
+      tp[poff + j] = tv;
+      tg[poff + j] = res ? sigmoid_d(x) : 1.0;
+      if (ti != nullptr) ti[poff + j] = rcp_fast(tv);
+    }
+  }
+  __syncthreads();
 }
 // accumulator update in LDS without the read round trip of `*p += v` (ds_add_f64; one wave per SIMD has nothing to
 // hide that latency with).  Each address is only ever touched by one lane: the sum order stays fixed.

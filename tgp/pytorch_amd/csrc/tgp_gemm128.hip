@@ -9,12 +9,6 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 template <bool TA, bool TB, bool MOD, bool EPI>
 static int launch_gemm_t(const GemmArgs& g, hipStream_t st) {
   static bool attr_done = false;

@@ -8,12 +8,6 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 // E-step: label_n = argmin_k |x_n - c_k|^2 (first minimum wins, like np.argmin), mind2_n = that distance.
 // One thread per row; centres stream through LDS in chunks of KC.
 #define KM_KC 256

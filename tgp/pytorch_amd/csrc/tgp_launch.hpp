@@ -7,6 +7,13 @@ namespace tgp {
 int set_error(hipError_t e, const char* file, int line);  // records tgp_last_error(), returns TGP_E_LAUNCH
 void set_error_text(const char* fmt, ...);                // records tgp_last_error()
 
+// after a kernel launch, in a launcher that returns the ABI's int: a failed launch is recorded and returned
+#define LAUNCH_CHECK()                                              \
+  do {                                                              \
+    hipError_t e_ = hipGetLastError();                              \
+    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
+  } while (0)
+
 // tgp_comm.hip (RCCL bound at run time)
 int comm_load(const char* path);
 int comm_unique_id(void* id128);
@@ -90,10 +97,8 @@ int launch_mlp_backward(const tgp_mlp& d, const double* X, const double* W, cons
 // tgp_lik.hip
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* log_var_noise,
                      double scale, double* out, double* g_mu, double* g_v, double* ws, hipStream_t st);
-int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
-                    double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws,
-                    hipStream_t st);
-int launch_ell_bern(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
+// the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, else Gaussian (TGP_LIK_FLOW)
+int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st);
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,
                      double* logdG, hipStream_t st, double* sum_out = nullptr, double* ws = nullptr);

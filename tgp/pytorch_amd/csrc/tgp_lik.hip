@@ -9,20 +9,14 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
-// k_ell_flow: lanes per data row.  4 by default (64 rows per workgroup); 16 for small problems (16 rows per workgroup): a
+// k_ell_quad: lanes per data row.  4 by default (64 rows per workgroup); 16 for small problems (16 rows per workgroup): a
 // rank's 1 250 rows of an 8-GPU minibatch were 20 workgroups, each lane walking 8 quadrature nodes through 30 tanh steps
 // and back -- 91 us of one dependent chain, whatever N; with 16 lanes per row a lane has 2 nodes and 79 workgroups run.
 // Round 6: 32 lanes per row (8 rows per workgroup, one node per lane at S = 32) below 2 560 rows -- the 1 250-row share again: 79
 // workgroups leave three quarters of the SIMDs without a wave, and a lane's chain is as long as its nodes.
 #define ELL_LPR16_MAXN 12288
 #define ELL_LPR32_MAXN 2560
-static int ell_flow_lpr(int N) { return N <= ELL_LPR32_MAXN ? 32 : (N <= ELL_LPR16_MAXN ? 16 : 4); }
+static int ell_lpr(int N) { return N <= ELL_LPR32_MAXN ? 32 : (N <= ELL_LPR16_MAXN ? 16 : 4); }
 
 // Sized for ANY call with at most N rows: a caller that sizes once for its largest chunk (the general-M path) may
 // launch a ragged last chunk that falls into the 16-lanes-per-row mode and then has MORE workgroups than the largest one.
@@ -30,7 +24,7 @@ size_t lik_workspace_doubles(int N, int P, int RP) {
   const size_t nb16 = (size_t)((N < ELL_LPR16_MAXN ? N : ELL_LPR16_MAXN) + 15) / 16, nb64 = (size_t)(N + 63) / 64;
   const size_t nb32 = (size_t)((N < ELL_LPR32_MAXN ? N : ELL_LPR32_MAXN) + 7) / 8;
   const size_t nbm = nb16 > nb64 ? nb16 : nb64;
-  const size_t nb = (nbm > nb32 ? nbm : nb32) + 1;  // k_ell_flow: one partial per workgroup
+  const size_t nb = (nbm > nb32 ? nbm : nb32) + 1;  // k_ell_quad: one partial per workgroup
   return nb * (size_t)(2 + P) + 2 * (size_t)P + 64;
 }
 
@@ -94,37 +88,65 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
   }
 }
 
-// transformed shared flow parameters into LDS (same rule as k_prep_a); whole block, ends with a barrier
-// `ti` (optional): 1 / tp[i] for every shared parameter, so that a step-tanh step takes 1 / softplus(d_k) from the table instead of
-// running a reciprocal chain per step and sweep
-// X: the extended kind set (flow_block_params)
-template <bool X = false>
-__device__ inline void flow_params_lds(const tgp_model& md, const FlowProg& fp, double* tp, double* tg, double* ti = nullptr) {
-  for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
-    const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
-    if (flags & TGP_FLAG_PER_ROW) continue;
-    const int np = flow_block_params<X>(kind, K);
-    for (int j = 0; j < np; ++j) {
-      const double x = md.theta[poff + j];
-      const bool res = flow_param_restricted<X>(kind, flags, j);
-      const double tv = res ? softplus_d(x) : x;
-      tp[poff + j] = tv;
-      tg[poff + j] = res ? sigmoid_d(x) : 1.0;
-      if (ti != nullptr) ti[poff + j] = rcp_fast(tv);
-    }
-  }
-  __syncthreads();
+// ---------------------------------------------------------------------------------------------------
+// Quadrature likelihoods through the flow with gradients, E_q(f0)[log p(y | G(f0))] by Gauss-Hermite:
+//   Gaussian  (likelihoods/GaussianNonLinearMean.py:64-150)
+//   Bernoulli (likelihoods/Bernoulli.py), probit link: log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g)
+// ---------------------------------------------------------------------------------------------------
+
+// The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
+//   Phi(-a) = erfc(t) / 2 = erfcx(t) exp(-a^2 / 2) / 2      log Phi(-a) = log(erfcx(t) / 2) - a^2 / 2
+//   Phi(a)  = 1 - erfc(t) / 2                                log Phi(a)  = log1p(-erfc(t) / 2)
+//   lambda(z) = phi(z) / Phi(z):  lambda(-a) = sqrt(2 / pi) / erfcx(t),  lambda(a) = phi(a) / Phi(a)
+// Every quantity stays finite and accurate however large |g| is (the reference forms Phi first: its BCELoss clamps the log
+// at -100 once |g| passes ~8).  lp = y log Phi(g) + (1 - y) log Phi(-g), dg = d lp / dg = y lambda(g) - (1 - y) lambda(-g);
+// pp / pm (optional) = Phi(g) / Phi(-g).
+struct BernNode { double lp, dg, pp, pm; };
+__device__ inline BernNode bern_node(double g, double y) {
+  const double a = fabs(g), t = a * 0.70710678118654752440;
+  const double ec = erfc(t), ex = erfcx(t);
+  const double phia = 0.39894228040143267794 * exp(-0.5 * a * a);   // phi(a)
+  const double lp_hi = log1p(-0.5 * ec);                              // log Phi(a)
+  const double lp_lo = log(0.5 * ex) - 0.5 * a * a;                   // log Phi(-a)
+  const double lam_hi = phia / (1.0 - 0.5 * ec);                      // lambda(a)
+  const double lam_lo = 0.79788456080286535588 / ex;                  // lambda(-a)
+  const bool pos = g >= 0.0;
+  BernNode r;
+  r.lp = y * (pos ? lp_hi : lp_lo) + (1.0 - y) * (pos ? lp_lo : lp_hi);
+  r.dg = y * (pos ? lam_hi : lam_lo) - (1.0 - y) * (pos ? lam_lo : lam_hi);
+  r.pp = pos ? 1.0 - 0.5 * ec : 0.5 * ec;
+  r.pm = pos ? 0.5 * ec : 1.0 - 0.5 * ec;
+  return r;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// TGP quadrature likelihood with gradients (likelihoods/GaussianNonLinearMean.py:64-150), four lanes per row
-// ---------------------------------------------------------------------------------------------------
+// What a likelihood supplies to k_ell_quad, per quadrature node with g = G(f0): at(g, y) = whatever the three terms share, then
+//   log_p = log p(y | g),  dlog_p_deta = its derivative in eta = log noise variance (kNoise only),
+//   adjoint = scale w d log p / dg for the node's normalised weight w, which starts the reverse sweep.
+// eta and einv = exp(-eta) are read once per launch, and only where kNoise is set.
+struct EllGauss {
+  static constexpr bool kNoise = true;    // partial slot 1 carries the noise adjoint
+  static constexpr bool kClampV = false;
+  static __device__ __forceinline__ double at(double g, double y) { return y - g; }   // the residual
+  static __device__ __forceinline__ double log_p(double r, double eta, double einv) {
+    return -0.5 * TGP_LOG_2PI_REF - 0.5 * eta - 0.5 * einv * r * r;
+  }
+  static __device__ __forceinline__ double dlog_p_deta(double r, double einv) { return -0.5 + 0.5 * einv * r * r; }
+  static __device__ __forceinline__ double adjoint(double r, double scale, double w, double einv) { return scale * einv * w * r; }
+};
+struct EllBern {
+  static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
+  // q(f) variances below 0 count as 0 (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0
+  static constexpr bool kClampV = true;
+  static __device__ __forceinline__ BernNode at(double g, double y) { return bern_node(g, y); }
+  static __device__ __forceinline__ double log_p(const BernNode& b, double, double) { return b.lp; }
+  static __device__ __forceinline__ double adjoint(const BernNode& b, double scale, double w, double) { return scale * w * b.dg; }
+};
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
 // lane.  The launcher picks LPR from N so that a chunk of ~16k rows still yields ~1000 workgroups.
 // NBX = NB | TGP_FLOWX: the flow sweeps know the extended kind set (X; see k_rows)
-template <int LPR, int NBX>
-__global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, const double* __restrict__ Y,
+template <class Lik, int LPR, int NBX>
+__global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, const double* __restrict__ Y,
                                                    const double* __restrict__ mu, const double* __restrict__ v,
                                                    const double* __restrict__ rowp, double* __restrict__ part,
                                                    double* __restrict__ g_mu, double* __restrict__ g_v,
@@ -144,7 +166,7 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
   double* tg = tp + (P + 2) / 2 * 2;                        // P+2
   double* ti = tg + (P + 2) / 2 * 2;                        // P+2: reciprocals (flow_rcp_param)
   for (int i = tid; i < 4 * (P > 0 ? P : 1) + RP * 256; i += 256) accw[i] = 0.0;
-  flow_params_lds<X>(md, fp, tp, tg, ti);
+  flow_params_lds<X>(md.theta, fp, tp, tg, ti);
   // lane group q takes the quadrature nodes s = q + LPR (NB j + u).  Every lane runs the same trip count (wave-wide
   // sums inside the reverse sweep); nodes past S and padding rows carry weight 0.
   const int qn = lane / RW;
@@ -156,10 +178,11 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
   };
   const bool valid = n < md.N;
   const int nc = valid ? n : md.N - 1;
-  const double eta = md.log_var_noise[0], einv = exp(-eta);
+  const double eta = Lik::kNoise ? md.log_var_noise[0] : 0.0, einv = Lik::kNoise ? exp(-eta) : 0.0;
   FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
   double ellp = 0.0, etap = 0.0, cm = 0.0, cv = 0.0;
-  const double m_ = mu[nc], sq = sqrt(2.0 * v[nc]), y = Y[nc];
+  const double m_ = mu[nc], vn = Lik::kClampV ? (v[nc] > 0.0 ? v[nc] : 0.0) : v[nc];
+  const double sq = sqrt(2.0 * vn), y = Y[nc];
   const double* rp = rowp ? rowp + (size_t)nc * RP : nullptr;
   double* aw = accw + (size_t)wave * (P > 0 ? P : 1);
   for (int s0 = 0; s0 < md.S; s0 += LPR * NB) {
@@ -174,10 +197,10 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
     flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-      const double r = y - f[u];
-      ellp += wsn[u] * (-0.5 * TGP_LOG_2PI_REF - 0.5 * eta - 0.5 * einv * r * r);
-      etap += wsn[u] * (-0.5 + 0.5 * einv * r * r);
-      c[u] = md.scale * einv * wsn[u] * r;
+      const auto t = Lik::at(f[u], y);
+      ellp += wsn[u] * Lik::log_p(t, eta, einv);
+      if constexpr (Lik::kNoise) etap += wsn[u] * Lik::dlog_p_deta(t, einv);
+      c[u] = Lik::adjoint(t, md.scale, wsn[u], einv);
     }
     flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
 #pragma unroll
@@ -191,22 +214,28 @@ __global__ __launch_bounds__(256) void k_ell_flow(tgp_model md, FlowProg fp, con
   }
   if (valid && qn == 0) {
     if (g_mu) g_mu[n] = cm;
-    if (g_v) g_v[n] = cv / sq;
+    if (g_v) g_v[n] = (!Lik::kClampV || vn > 0.0) ? cv / sq : 0.0;
   }
-  ellp = wave_sum(ellp); etap = wave_sum(etap);
-  if (lane == 0) { red[wave] = ellp; red[4 + wave] = etap; }
+  ellp = wave_sum(ellp);
+  if constexpr (Lik::kNoise) etap = wave_sum(etap);
+  if (lane == 0) {
+    red[wave] = ellp;
+    if constexpr (Lik::kNoise) red[4 + wave] = etap;
+  }
   __syncthreads();
   double* pb = part + (size_t)blockIdx.x * (2 + P);
   if (tid == 0) {
     pb[0] = md.scale * (red[0] + red[1] + red[2] + red[3]);
-    pb[1] = md.scale * (red[4] + red[5] + red[6] + red[7]);
+    pb[1] = Lik::kNoise ? md.scale * (red[4] + red[5] + red[6] + red[7]) : 0.0;
   }
   for (int j = tid; j < P; j += 256) pb[2 + j] = (accw[j] + accw[P + j]) + (accw[2 * P + j] + accw[3 * P + j]);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // flow evaluation: G, dG/df, log dG/df over an (S,N) array (row n = idx % N)
+// X: the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX; the host picks it for programs that hold one)
 // ---------------------------------------------------------------------------------------------------
+template <bool X>
 __global__ __launch_bounds__(256) void k_flow_eval(tgp_model md, FlowProg fp, const double* __restrict__ f, size_t total, int N,
                                                     const double* __restrict__ rowp, double* __restrict__ G,
                                                     double* __restrict__ dG, double* __restrict__ logdG,
@@ -216,7 +245,7 @@ __global__ __launch_bounds__(256) void k_flow_eval(tgp_model md, FlowProg fp, co
   double* tg = tp + (md.P + 2) / 2 * 2;
   double* ti = tg + (md.P + 2) / 2 * 2;
   __shared__ double redl[4];
-  flow_params_lds(md, fp, tp, tg, ti);
+  flow_params_lds<X>(md.theta, fp, tp, tg, ti);
   FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
   // four elements per thread, a grid stride apart (coalesced), evaluated stage by stage (flow_forward_n)
   constexpr int NB = 4;
@@ -229,61 +258,8 @@ __global__ __launch_bounds__(256) void k_flow_eval(tgp_model md, FlowProg fp, co
     fv[u] = f[ic];
     rp[u] = rowp ? rowp + (ic % N) * md.RP : nullptr;
   }
-  if (dG || logdG || part) flow_forward_n<NB, true>(F, fv, rp, der);
-  else flow_forward_n<NB, false>(F, fv, rp, der);
-  if (part) {
-    // fused log-Jacobian accumulation: sum of log dG/df over this workgroup's elements, fixed order (lane partials ->
-    // butterfly over the wave -> the four waves in LDS); the launcher's second kernel adds the workgroups' partials
-    double sl = 0.0;
-    TGP_EACH(u, NB) sl += (i0 + u * stride < total) ? log(der[u]) : 0.0;
-    sl = wave_sum(sl);
-    if ((threadIdx.x & 63) == 0) redl[threadIdx.x >> 6] = sl;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (redl[0] + redl[1]) + (redl[2] + redl[3]);
-  }
-  if (logdG) {
-    double lg[NB];
-    TGP_EACH(u, NB) lg[u] = der[u];
-    TGP_EACH(u, NB) {
-      const size_t i = i0 + u * stride;
-      if (i < total) logdG[i] = log(lg[u]);
-    }
-  }
-  TGP_EACH(u, NB) {
-    const size_t i = i0 + u * stride;
-    if (i < total) {
-      if (G) G[i] = fv[u];
-      if (dG) dG[i] = der[u];
-    }
-  }
-}
-
-// k_flow_eval with the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX; the host launches it for programs that hold one).
-// A copy of the body above, not a shared template: k_flow_eval itself compiles exactly as before the new kinds.
-__global__ __launch_bounds__(256) void k_flow_eval_x(tgp_model md, FlowProg fp, const double* __restrict__ f, size_t total, int N,
-                                                    const double* __restrict__ rowp, double* __restrict__ G,
-                                                    double* __restrict__ dG, double* __restrict__ logdG,
-                                                    double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  double* ti = tg + (md.P + 2) / 2 * 2;
-  __shared__ double redl[4];
-  flow_params_lds<true>(md, fp, tp, tg, ti);
-  FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
-  // four elements per thread, a grid stride apart (coalesced), evaluated stage by stage (flow_forward_n)
-  constexpr int NB = 4;
-  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  double fv[NB], der[NB];
-  const double* rp[NB];
-  TGP_EACH(u, NB) {
-    const size_t i = i0 + u * stride;
-    const size_t ic = i < total ? i : 0;
-    fv[u] = f[ic];
-    rp[u] = rowp ? rowp + (ic % N) * md.RP : nullptr;
-  }
-  if (dG || logdG || part) flow_forward_n<NB, true, true>(F, fv, rp, der);
-  else flow_forward_n<NB, false, true>(F, fv, rp, der);
+  if (dG || logdG || part) flow_forward_n<NB, true, X>(F, fv, rp, der);
+  else flow_forward_n<NB, false, X>(F, fv, rp, der);
   if (part) {
     // fused log-Jacobian accumulation: sum of log dG/df over this workgroup's elements, fixed order (lane partials ->
     // butterfly over the wave -> the four waves in LDS); the launcher's second kernel adds the workgroups' partials
@@ -315,7 +291,9 @@ __global__ __launch_bounds__(256) void k_flow_eval_x(tgp_model md, FlowProg fp, 
 // prediction given q(f) moments: m1, m2 and per-row test log-likelihood (without the -0.5 log(pi) constant)
 //   flow : GaussianNonLinearMean.marginal_moments (:176-203) ; sparse_MF_SP.test_log_likelihood (:705-776)
 //   gauss: GaussianLinearMean.marginal_moments (:89-118)     ; sparse_MF_SP.py:786-799
+// X: the extended kind set
 // ---------------------------------------------------------------------------------------------------
+template <bool X>
 __global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, const double* __restrict__ mu,
                                                   const double* __restrict__ v, const double* __restrict__ rowp,
                                                   const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
@@ -323,7 +301,7 @@ __global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, cons
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* tp = reinterpret_cast<double*>(smem_raw);
   double* tg = tp + (md.P + 2) / 2 * 2;
-  if (md.lik == TGP_LIK_FLOW) flow_params_lds(md, fp, tp, tg);
+  if (md.lik == TGP_LIK_FLOW) flow_params_lds<X>(md.theta, fp, tp, tg);
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= md.N) return;
   const double noise = exp(md.log_var_noise[0]);
@@ -354,7 +332,7 @@ __global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, cons
       wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
       rpn[u] = rp;
     }
-    flow_forward_n<NB, false>(F, g, rpn, der);
+    flow_forward_n<NB, false, X>(F, g, rpn, der);
     TGP_EACH(u, NB) {
       if (s0 + u < md.S) {
         m1 += wsn[u] * g[u];
@@ -372,175 +350,6 @@ __global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, cons
   if (m1o) m1o[n] = m1;
   if (m2o) m2o[n] = noise + e2 - m1 * m1;
   if (logp && Y) logp[n] = mx + log(se);
-}
-
-// k_predict with the extended kind set (see k_flow_eval_x: a copy, so that k_predict compiles exactly as before)
-__global__ __launch_bounds__(256) void k_predict_x(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                  const double* __restrict__ v, const double* __restrict__ rowp,
-                                                  const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
-                                                  double* __restrict__ m2o, double* __restrict__ logp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  if (md.lik == TGP_LIK_FLOW) flow_params_lds<true>(md, fp, tp, tg);
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= md.N) return;
-  const double noise = exp(md.log_var_noise[0]);
-  if (md.lik == TGP_LIK_GAUSS) {
-    const double m1 = mu[n], m2 = noise + v[n];
-    if (m1o) m1o[n] = m1;
-    if (m2o) m2o[n] = m2;
-    if (logp && Y) {
-      const double sd = Y_std * sqrt(m2), var = sd * sd, r = Y_std * Y[n] - Y_std * m1;
-      logp[n] = -0.5 * (TGP_LOG_2PI_REF + log(var) + r * r / var);
-    }
-    return;
-  }
-  FlowDev F{fp.blk, fp.nblk, tp, tg};
-  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-  const double m_ = mu[n], sq = sqrt(2.0 * v[n]);
-  const double sdy = Y_std * sqrt(noise), var = sdy * sdy;
-  const double yy = Y ? Y_std * Y[n] : 0.0;
-  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
-  const double lvar = log(var), ivar = 1.0 / var;
-  constexpr int NB = 4;  // quadrature nodes in flight (stage-by-stage evaluation, flow_forward_n)
-  for (int s0 = 0; s0 < md.S; s0 += NB) {
-    double g[NB], der[NB], wsn[NB];
-    const double* rpn[NB];
-    TGP_EACH(u, NB) {
-      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-      g[u] = m_ + sq * md.xs[s];
-      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-      rpn[u] = rp;
-    }
-    flow_forward_n<NB, false, true>(F, g, rpn, der);
-    TGP_EACH(u, NB) {
-      if (s0 + u < md.S) {
-        m1 += wsn[u] * g[u];
-        e2 += wsn[u] * g[u] * g[u];
-        if (logp && Y) {
-          // log w_s = log(wn_s) + 0.5 log(pi); the caller adds the reference's constants
-          const double r = yy - Y_std * g[u];
-          const double t = log(wsn[u]) - 0.5 * (TGP_LOG_2PI_REF + lvar + r * r * ivar);
-          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
-          else se += exp(t - mx);
-        }
-      }
-    }
-  }
-  if (m1o) m1o[n] = m1;
-  if (m2o) m2o[n] = noise + e2 - m1 * m1;
-  if (logp && Y) logp[n] = mx + log(se);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Bernoulli likelihood, probit link (likelihoods/Bernoulli.py): log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g), g = G(f0)
-// ---------------------------------------------------------------------------------------------------
-
-// The node term shared by k_ell_bern and k_predict_bern.  With a = |g|, t = a / sqrt 2:
-//   Phi(-a) = erfc(t) / 2 = erfcx(t) exp(-a^2 / 2) / 2      log Phi(-a) = log(erfcx(t) / 2) - a^2 / 2
-//   Phi(a)  = 1 - erfc(t) / 2                                log Phi(a)  = log1p(-erfc(t) / 2)
-//   lambda(z) = phi(z) / Phi(z):  lambda(-a) = sqrt(2 / pi) / erfcx(t),  lambda(a) = phi(a) / Phi(a)
-// Every quantity stays finite and accurate however large |g| is (the reference forms Phi first: its BCELoss clamps the log
-// at -100 once |g| passes ~8).  lp = y log Phi(g) + (1 - y) log Phi(-g), dg = d lp / dg = y lambda(g) - (1 - y) lambda(-g);
-// pp / pm (optional) = Phi(g) / Phi(-g).
-struct BernNode { double lp, dg, pp, pm; };
-__device__ inline BernNode bern_node(double g, double y) {
-  const double a = fabs(g), t = a * 0.70710678118654752440;
-  const double ec = erfc(t), ex = erfcx(t);
-  const double phia = 0.39894228040143267794 * exp(-0.5 * a * a);   // phi(a)
-  const double lp_hi = log1p(-0.5 * ec);                              // log Phi(a)
-  const double lp_lo = log(0.5 * ex) - 0.5 * a * a;                   // log Phi(-a)
-  const double lam_hi = phia / (1.0 - 0.5 * ec);                      // lambda(a)
-  const double lam_lo = 0.79788456080286535588 / ex;                  // lambda(-a)
-  const bool pos = g >= 0.0;
-  BernNode r;
-  r.lp = y * (pos ? lp_hi : lp_lo) + (1.0 - y) * (pos ? lp_lo : lp_hi);
-  r.dg = y * (pos ? lam_hi : lam_lo) - (1.0 - y) * (pos ? lam_lo : lam_hi);
-  r.pp = pos ? 1.0 - 0.5 * ec : 0.5 * ec;
-  r.pm = pos ? 0.5 * ec : 1.0 - 0.5 * ec;
-  return r;
-}
-
-// Expected log-likelihood through the flow with gradients: the lane layout, node batching, checkpointed flow sweeps and
-// partial-sum slots of k_ell_flow; part[1] (the noise adjoint there) is 0.  q(f) variances below 0 count as 0
-// (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0.
-template <int LPR, int NBX>
-__global__ __launch_bounds__(256) void k_ell_bern(tgp_model md, FlowProg fp, const double* __restrict__ Y,
-                                                   const double* __restrict__ mu, const double* __restrict__ v,
-                                                   const double* __restrict__ rowp, double* __restrict__ part,
-                                                   double* __restrict__ g_mu, double* __restrict__ g_v,
-                                                   double* __restrict__ g_rowp) {
-  constexpr int NB = NBX & (TGP_FLOWX - 1);
-  constexpr bool X = NBX & TGP_FLOWX;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* sm = reinterpret_cast<double*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = md.P, RP = md.RP;
-  const int nb = fp.nblk > 0 ? fp.nblk : 1;
-  constexpr int RW = 64 / LPR;                              // rows per wave
-  double* stack = sm;                                       // nblk * NB * 256: block inputs (checkpoint mode)
-  double* accw = stack + (size_t)nb * NB * 256;             // 4 waves x P
-  double* accr = accw + (size_t)4 * (P > 0 ? P : 1);        // RP * 256
-  double* red = accr + (size_t)RP * 256;                    // 16
-  double* tp = red + 16;                                    // P+2
-  double* tg = tp + (P + 2) / 2 * 2;                        // P+2
-  double* ti = tg + (P + 2) / 2 * 2;                        // P+2
-  for (int i = tid; i < 4 * (P > 0 ? P : 1) + RP * 256; i += 256) accw[i] = 0.0;
-  flow_params_lds<X>(md, fp, tp, tg, ti);
-  const int qn = lane / RW;
-  const int n = blockIdx.x * (4 * RW) + wave * RW + (lane % RW);
-  auto group_sum = [&](double x) {
-#pragma unroll
-    for (int o = RW; o < 64; o <<= 1) x += __shfl_xor(x, o);
-    return x;
-  };
-  const bool valid = n < md.N;
-  const int nc = valid ? n : md.N - 1;
-  FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
-  double ellp = 0.0, cm = 0.0, cv = 0.0;
-  const double vn = v[nc] > 0.0 ? v[nc] : 0.0;
-  const double m_ = mu[nc], sq = sqrt(2.0 * vn), y = Y[nc];
-  const double* rp = rowp ? rowp + (size_t)nc * RP : nullptr;
-  double* aw = accw + (size_t)wave * (P > 0 ? P : 1);
-  for (int s0 = 0; s0 < md.S; s0 += LPR * NB) {
-    double f[NB], c[NB], xsn[NB], wsn[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int s = s0 + LPR * u + qn, sc = s < md.S ? s : md.S - 1;
-      xsn[u] = md.xs[sc];
-      wsn[u] = (valid && s < md.S) ? md.wn[sc] : 0.0;
-      f[u] = m_ + sq * xsn[u];
-    }
-    flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const BernNode b = bern_node(f[u], y);
-      ellp += wsn[u] * b.lp;
-      c[u] = md.scale * wsn[u] * b.dg;
-    }
-    flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) { cm += c[u]; cv += c[u] * xsn[u]; }
-  }
-  cm = group_sum(cm);
-  cv = group_sum(cv);
-  for (int j = 0; j < RP; ++j) {
-    const double a = group_sum(accr[(size_t)j * 256 + tid]);
-    if (valid && qn == 0 && g_rowp) g_rowp[(size_t)n * RP + j] = a;
-  }
-  if (valid && qn == 0) {
-    if (g_mu) g_mu[n] = cm;
-    if (g_v) g_v[n] = vn > 0.0 ? cv / sq : 0.0;
-  }
-  ellp = wave_sum(ellp);
-  if (lane == 0) red[wave] = ellp;
-  __syncthreads();
-  double* pb = part + (size_t)blockIdx.x * (2 + P);
-  if (tid == 0) {
-    pb[0] = md.scale * (red[0] + red[1] + red[2] + red[3]);
-    pb[1] = 0.0;
-  }
-  for (int j = tid; j < P; j += 256) pb[2 + j] = (accw[j] + accw[P + j]) + (accw[2 * P + j] + accw[3 * P + j]);
 }
 
 // Predictive probability per row: P = Phi(mu / sqrt(1 + v)) for the empty program (R&W eq. 3.80, Bernoulli.py
@@ -554,7 +363,7 @@ __global__ __launch_bounds__(256) void k_predict_bern(tgp_model md, FlowProg fp,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* tp = reinterpret_cast<double*>(smem_raw);
   double* tg = tp + (md.P + 2) / 2 * 2;
-  flow_params_lds<X>(md, fp, tp, tg);
+  flow_params_lds<X>(md.theta, fp, tp, tg);
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= md.N) return;
   const double y = (logp && Y) ? Y[n] : 0.0;
@@ -715,9 +524,9 @@ static int flow_lds(const tgp_model& md, int nblk, int NB, size_t* bytes) {
   return *bytes > 160 * 1024 - 1024 ? TGP_E_LDS : 0;
 }
 
-// lanes per row, nodes in flight per lane and dynamic LDS of k_ell_flow / k_ell_bern
+// lanes per row, nodes in flight per lane and dynamic LDS of k_ell_quad
 static int ell_plan(const tgp_model& md, const FlowProg& fp, int* lpr, int* nbn, size_t* lds) {
-  const int LPR = ell_flow_lpr(md.N);
+  const int LPR = ell_lpr(md.N);
   int NB = LPR == 4 ? (md.S > 16 ? 8 : 4) : (LPR == 16 ? (md.S > 32 ? 4 : (md.S > 16 ? 2 : 1)) : (md.S > 64 ? 4 : (md.S > 32 ? 2 : 1)));
   while (NB > 1 && (flow_lds(md, fp.nblk, NB, lds) != 0 || *lds > 120 * 1024)) NB >>= 1;
   *lpr = LPR;
@@ -725,9 +534,38 @@ static int ell_plan(const tgp_model& md, const FlowProg& fp, int* lpr, int* nbn,
   return flow_lds(md, fp.nblk, NB, lds);
 }
 
-int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
-                    double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws,
-                    hipStream_t st) {
+// one launch of k_ell_quad<Lik, LPR, NB> or, for a program with a kind past STEPTANH (ext), k_ell_quad<Lik, LPR, NB | TGP_FLOWX>;
+// each of the two kernel functions has its own dynamic-LDS high-water mark (ensure_lds)
+template <class Lik, int LPR, int NB, class... Args>
+static int ell_launch_one(bool ext, int nb, size_t lds, hipStream_t st, Args... args) {
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_ell_quad<Lik, LPR, NB | TGP_FLOWX> : k_ell_quad<Lik, LPR, NB>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, st, args...);
+  LAUNCH_CHECK();
+  return 0;
+}
+// the instantiation for ell_plan's (LPR, NB)
+template <class Lik, class... Args>
+static int ell_launch(int LPR, int NB, Args... args) {
+  if (LPR == 4) {
+    if (NB == 8) return ell_launch_one<Lik, 4, 8>(args...);
+    if (NB == 4) return ell_launch_one<Lik, 4, 4>(args...);
+    if (NB == 2) return ell_launch_one<Lik, 4, 2>(args...);
+    return ell_launch_one<Lik, 4, 1>(args...);
+  }
+  if (LPR == 16) {
+    if (NB == 4) return ell_launch_one<Lik, 16, 4>(args...);
+    if (NB == 2) return ell_launch_one<Lik, 16, 2>(args...);
+    return ell_launch_one<Lik, 16, 1>(args...);
+  }
+  if (NB == 4) return ell_launch_one<Lik, 32, 4>(args...);
+  if (NB == 2) return ell_launch_one<Lik, 32, 2>(args...);
+  return ell_launch_one<Lik, 32, 1>(args...);
+}
+
+int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
+                    double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st) {
   // nodes in flight per lane: all of the lane's nodes when the checkpoint stack fits (the per-step wave reductions of
   // the shared-parameter partials are then paid once), else fewer
   size_t lds = 0;
@@ -735,79 +573,11 @@ int launch_ell_flow(const tgp_model& md, const FlowProg& fp, const double* Y, co
   if (int rc = ell_plan(md, fp, &LPR, &NB, &lds)) return rc;
   const int rows = 256 / LPR;
   const int nb = (md.N + rows - 1) / rows;
-  static size_t cur[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-  static size_t cur_x[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-  const bool ext = flow_prog_extended(fp.blk, fp.nblk);   // k_ell_flow<.., NB | TGP_FLOWX>: a kind past STEPTANH
-#define ELLF_LAUNCH(lpr, nbv, slot)                                                                                           \
-  do {                                                                                                                        \
-    if (ext) {                                                                                                                \
-      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_flow<lpr, nbv | TGP_FLOWX>), lds, &cur_x[slot])) return rc;  \
-      hipLaunchKernelGGL((k_ell_flow<lpr, nbv | TGP_FLOWX>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu,    \
-                         g_v, g_rowp);                                                                                        \
-    } else {                                                                                                                  \
-      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_flow<lpr, nbv>), lds, &cur[slot])) return rc;               \
-      hipLaunchKernelGGL((k_ell_flow<lpr, nbv>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp);   \
-    }                                                                                                                         \
-  } while (0)
-  if (LPR == 4) {
-    if (NB == 8) ELLF_LAUNCH(4, 8, 0);
-    else if (NB == 4) ELLF_LAUNCH(4, 4, 1);
-    else if (NB == 2) ELLF_LAUNCH(4, 2, 2);
-    else ELLF_LAUNCH(4, 1, 3);
-  } else if (LPR == 16) {
-    if (NB == 4) ELLF_LAUNCH(16, 4, 4);
-    else if (NB == 2) ELLF_LAUNCH(16, 2, 5);
-    else ELLF_LAUNCH(16, 1, 6);
-  } else {
-    if (NB == 4) ELLF_LAUNCH(32, 4, 7);
-    else if (NB == 2) ELLF_LAUNCH(32, 2, 8);
-    else ELLF_LAUNCH(32, 1, 9);
-  }
-#undef ELLF_LAUNCH
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
-  LAUNCH_CHECK();
-  return 0;
-}
-
-// k_ell_bern with launch_ell_flow's choice of lanes per row and nodes in flight (same instantiations)
-int launch_ell_bern(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
-                    double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st) {
-  size_t lds = 0;
-  int LPR = 0, NB = 0;
-  if (int rc = ell_plan(md, fp, &LPR, &NB, &lds)) return rc;
-  const int rows = 256 / LPR;
-  const int nb = (md.N + rows - 1) / rows;
-  static size_t cur[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-  static size_t cur_x[10] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-#define ELLB_LAUNCH(lpr, nbv, slot)                                                                                           \
-  do {                                                                                                                        \
-    if (ext) {                                                                                                                \
-      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_bern<lpr, nbv | TGP_FLOWX>), lds, &cur_x[slot])) return rc;  \
-      hipLaunchKernelGGL((k_ell_bern<lpr, nbv | TGP_FLOWX>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu,    \
-                         g_v, g_rowp);                                                                                        \
-    } else {                                                                                                                  \
-      if (int rc = ensure_lds(reinterpret_cast<const void*>(k_ell_bern<lpr, nbv>), lds, &cur[slot])) return rc;               \
-      hipLaunchKernelGGL((k_ell_bern<lpr, nbv>), dim3(nb), dim3(256), lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp);   \
-    }                                                                                                                         \
-  } while (0)
-  if (LPR == 4) {
-    if (NB == 8) ELLB_LAUNCH(4, 8, 0);
-    else if (NB == 4) ELLB_LAUNCH(4, 4, 1);
-    else if (NB == 2) ELLB_LAUNCH(4, 2, 2);
-    else ELLB_LAUNCH(4, 1, 3);
-  } else if (LPR == 16) {
-    if (NB == 4) ELLB_LAUNCH(16, 4, 4);
-    else if (NB == 2) ELLB_LAUNCH(16, 2, 5);
-    else ELLB_LAUNCH(16, 1, 6);
-  } else {
-    if (NB == 4) ELLB_LAUNCH(32, 4, 7);
-    else if (NB == 2) ELLB_LAUNCH(32, 2, 8);
-    else ELLB_LAUNCH(32, 1, 9);
-  }
-#undef ELLB_LAUNCH
-  LAUNCH_CHECK();
+  if (int rc = md.lik == TGP_LIK_BERNOULLI
+                   ? ell_launch<EllBern>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
+                   : ell_launch<EllGauss>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp))
+    return rc;
   hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
   LAUNCH_CHECK();
   return 0;
@@ -820,9 +590,9 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
   const unsigned nb = (unsigned)((total + 1023) / 1024);
   double* part = sum_out != nullptr ? ws : (double*)nullptr;
   if (flow_prog_extended(fp.blk, fp.nblk))
-    hipLaunchKernelGGL(k_flow_eval_x, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
+    hipLaunchKernelGGL(k_flow_eval<true>, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
   else
-    hipLaunchKernelGGL(k_flow_eval, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
+    hipLaunchKernelGGL(k_flow_eval<false>, dim3(nb), dim3(256), lds, st, md, fp, f, total, N, rowp, G, dG, logdG, part);
   LAUNCH_CHECK();
   if (sum_out != nullptr) {
     hipLaunchKernelGGL(k_sum_parts, dim3(1), dim3(256), 0, st, ws, (int)nb, 1, sum_out, (double*)nullptr, 1);
@@ -840,9 +610,9 @@ int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, co
     else
       hipLaunchKernelGGL(k_predict_bern<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
   } else if (flow_prog_extended(fp.blk, fp.nblk))
-    hipLaunchKernelGGL(k_predict_x, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
+    hipLaunchKernelGGL(k_predict<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   else
-    hipLaunchKernelGGL(k_predict, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
+    hipLaunchKernelGGL(k_predict<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   LAUNCH_CHECK();
   return 0;
 }

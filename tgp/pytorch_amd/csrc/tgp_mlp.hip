@@ -26,12 +26,6 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 #define MLP_T 64       /* rows per chunk = 4 waves x 16 rows */
 #define MLP_NT 256
 #define MLP_ST 66      /* row stride of a strip [unit][row]: the transposed fragment reads (lane = unit, q = row) of the

@@ -1222,12 +1222,6 @@ __global__ __launch_bounds__(PREP_THREADS) void k_chol_only(const double* __rest
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
-#define LAUNCH_CHECK()                                   \
-  do {                                                   \
-    hipError_t e_ = hipGetLastError();                   \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 int launch_prepare(const Plan& p_in, const tgp_model& md, const FlowProg& fp, double* ws, int32_t* status,
                    hipStream_t st) {
   Plan p = p_in;

@@ -45,14 +45,7 @@ __device__ __forceinline__ void sync_add(int32_t* p, int v) {
   asm volatile("" ::: "memory");
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// data that crosses workgroups inside one launch (see the header): coherent for the whole device, never through the
-// scalar cache
-__device__ __forceinline__ double ld_agent(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// (ld_agent / st_agent, the accessors for data that crosses workgroups inside one launch, see the header: tgp_dev.hpp)
 // two consecutive doubles (16-byte aligned) in ONE store instruction: a wave's global stores cost ~32 ns each whatever
 // their width (tools/probes/sc1_rate.hip), so the write-out of the factor is counted in instructions.  There is no
 // 128-bit atomic, so the coherent 16-byte store is a raw buffer store with the sc1 cache-policy bit (aux = 16 on

@@ -26,16 +26,7 @@
 
 namespace tgp {
 
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
-
 #define SMX_ROWS 64   // data rows per workgroup (one per lane)
-
-__device__ __forceinline__ double smx_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void smx_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ uint64_t smx_fin(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -51,21 +42,11 @@ __device__ __forceinline__ double smx_normal(uint64_t seed, uint32_t step, int s
   return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
 }
 
-// the program into LDS (the sweeps read their block descriptors from there) and the shared parameters after their positivity
-// transform (tp) with d(tp)/d(raw) (tg); whole block, ends with a barrier
+// the program into LDS (the sweeps read their block descriptors from there), then the shared parameters (flow_params_lds, whose
+// barrier also covers the program copy)
 __device__ inline void smx_setup_lds(const FlowProg& fp, const double* __restrict__ theta, int32_t* prog, double* tp, double* tg) {
   for (int i = threadIdx.x; i < 4 * fp.nblk; i += blockDim.x) prog[i] = fp.blk[i];
-  for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
-    const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
-    const int np = flow_block_params(kind, K);
-    for (int j = 0; j < np; ++j) {
-      const double x = theta[poff + j];
-      const bool res = flow_param_restricted(kind, flags, j);
-      tp[poff + j] = res ? softplus_d(x) : x;
-      tg[poff + j] = res ? sigmoid_d(x) : 1.0;
-    }
-  }
-  __syncthreads();
+  flow_params_lds<true>(theta, fp, tp, tg);
 }
 
 __device__ __forceinline__ FlowDev smx_flow(const SmxArgs& a, const int32_t* prog, const double* tp, const double* tg, int c) {
@@ -163,12 +144,12 @@ __global__ __launch_bounds__(256) void k_ell_softmax(SmxArgs a, FlowProg fp, con
   if (tid == 0) {
     double sacc = red[0];
     for (int w = 1; w < nw; ++w) sacc += red[w];
-    smx_st(pb, wsc * sacc);
+    st_agent(pb, wsc * sacc);
   }
   for (int j = tid; j < P; j += nt) {
     double sacc = accw[j];
     for (int w = 1; w < nw; ++w) sacc += accw[(size_t)w * Pp + j];
-    smx_st(pb + 1 + j, sacc);
+    st_agent(pb + 1 + j, sacc);
   }
   // ---- the last workgroup to arrive adds the partials in a fixed order
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's partial stores have landed
@@ -184,11 +165,11 @@ __global__ __launch_bounds__(256) void k_ell_softmax(SmxArgs a, FlowProg fp, con
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     int b = 0;
     for (; b + 3 < nb; b += 4) {
-      const double t0 = smx_ld(part + (size_t)b * len + j), t1 = smx_ld(part + (size_t)(b + 1) * len + j);
-      const double t2 = smx_ld(part + (size_t)(b + 2) * len + j), t3 = smx_ld(part + (size_t)(b + 3) * len + j);
+      const double t0 = ld_agent(part + (size_t)b * len + j), t1 = ld_agent(part + (size_t)(b + 1) * len + j);
+      const double t2 = ld_agent(part + (size_t)(b + 2) * len + j), t3 = ld_agent(part + (size_t)(b + 3) * len + j);
       s0 += t0; s1 += t1; s2 += t2; s3 += t3;
     }
-    for (; b < nb; ++b) s0 += smx_ld(part + (size_t)b * len + j);
+    for (; b < nb; ++b) s0 += ld_agent(part + (size_t)b * len + j);
     const double sacc = (s0 + s1) + (s2 + s3);
     if (j == 0) out[0] = sacc;
     else theta_bar[j - 1] = sacc;

@@ -5,18 +5,12 @@
 // The blocks are evaluated one element at a time with the library's exp / log / sinh / cosh / tanh (this is N rows x B blocks,
 // no quadrature loop and no MFMA: launch- and latency-bound), with the reference's quirks the interpreter of
 // tgp_dev.hpp keeps: asinh(x) = log(x + sqrt(x^2 + 1)), softplus with threshold 20, float32 pi in the Gaussian constant.
-// Nothing here is shared with the existing kernels but the tables of tgp_dev.hpp (parameters per block, which one is
-// softplus'ed), so none of them changes.
+// Shared with the other kernels through tgp_dev.hpp: the per-kind tables (parameters per block, which one is softplus'ed) and
+// the staging of the shared parameters into LDS (flow_params_lds); warp_block is this file's own, for its second derivative.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 
 namespace tgp {
-
-#define LAUNCH_CHECK()                                              \
-  do {                                                              \
-    hipError_t e_ = hipGetLastError();                              \
-    if (e_ != hipSuccess) return set_error(e_, __FILE__, __LINE__); \
-  } while (0)
 
 // one data row per lane.  64-lane workgroups up to this many rows (Power: 8 611 rows = 135 workgroups on 256 CUs instead of
 // 34), 256-lane workgroups above (fewer partials for the last workgroup to add up)
@@ -27,25 +21,6 @@ static int warp_blocks(int N) { const int t = warp_threads(N); return (N + t - 1
 size_t warp_workspace_doubles(int N, int P) {
   const size_t nb64 = (size_t)((N < WARP_SMALL_MAXN ? N : WARP_SMALL_MAXN) + 63) / 64, nb256 = (size_t)(N + 255) / 256;
   return (nb64 > nb256 ? nb64 : nb256) * (size_t)(3 + P) + 2;
-}
-
-__device__ __forceinline__ double warp_ld(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void warp_st(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// shared parameters after their positivity transform (tp) and d(tp)/d(raw) (tg) into LDS; whole block, ends with a barrier
-__device__ inline void warp_params_lds(const tgp_model& md, const FlowProg& fp, double* tp, double* tg) {
-  for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
-    const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
-    if (flags & TGP_FLAG_PER_ROW) continue;
-    const int np = flow_block_params(kind, K);
-    for (int j = 0; j < np; ++j) {
-      const double x = md.theta[poff + j];
-      const bool res = flow_param_restricted(kind, flags, j);
-      tp[poff + j] = res ? softplus_d(x) : x;
-      tg[poff + j] = res ? sigmoid_d(x) : 1.0;
-    }
-  }
-  __syncthreads();
 }
 
 // One block at x: value g, derivative g1 = dg/dx and (D2) g2 = d2g/dx2.  pa, pb: the two parameters of an AFFINE / SAL block
@@ -138,7 +113,7 @@ __global__ __launch_bounds__(256) void k_ell_warp(tgp_model md, FlowProg fp, int
   double* red = accw + (size_t)nw * Pp;         // 3 x 4 wave sums, then 8 x 32 words of the final reduction
   double* stack = red + 12 + 8 * 33;            // nblk x nt: block inputs
   __shared__ int s_last;
-  warp_params_lds(md, fp, tp, tg);
+  flow_params_lds<true>(md.theta, fp, tp, tg);
   const int n = blockIdx.x * nt + tid;
   const bool valid = n < md.N;
   const int nc = valid ? n : md.N - 1;
@@ -232,12 +207,12 @@ __global__ __launch_bounds__(256) void k_ell_warp(tgp_model md, FlowProg fp, int
   if (tid < 3) {
     double s = red[4 * tid];
     for (int w = 1; w < nw; ++w) s += red[4 * tid + w];
-    warp_st(pb + tid, c * s);
+    st_agent(pb + tid, c * s);
   }
   for (int j = tid; j < P; j += nt) {
     double s = accw[j];
     for (int w = 1; w < nw; ++w) s += accw[(size_t)w * Pp + j];
-    warp_st(pb + 3 + j, s);
+    st_agent(pb + 3 + j, s);
   }
   // ---- the last workgroup to arrive adds the partials in a fixed order
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave's partial stores have landed
@@ -255,11 +230,11 @@ __global__ __launch_bounds__(256) void k_ell_warp(tgp_model md, FlowProg fp, int
     if (j < len) {
       int b = grp;
       for (; b + 3 * ng < nb; b += 4 * ng) {
-        const double t0 = warp_ld(part + (size_t)b * len + j), t1 = warp_ld(part + (size_t)(b + ng) * len + j);
-        const double t2 = warp_ld(part + (size_t)(b + 2 * ng) * len + j), t3 = warp_ld(part + (size_t)(b + 3 * ng) * len + j);
+        const double t0 = ld_agent(part + (size_t)b * len + j), t1 = ld_agent(part + (size_t)(b + ng) * len + j);
+        const double t2 = ld_agent(part + (size_t)(b + 2 * ng) * len + j), t3 = ld_agent(part + (size_t)(b + 3 * ng) * len + j);
         s0 += t0; s1 += t1; s2 += t2; s3 += t3;
       }
-      for (; b < nb; b += ng) s0 += warp_ld(part + (size_t)b * len + j);
+      for (; b < nb; b += ng) s0 += ld_agent(part + (size_t)b * len + j);
     }
     __syncthreads();
     fin[grp * 33 + cidx] = (s0 + s1) + (s2 + s3);
@@ -366,7 +341,7 @@ __global__ __launch_bounds__(256) void k_flow_inverse(tgp_model md, FlowProg fp,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* tp = reinterpret_cast<double*>(smem_raw);
   double* tg = tp + (md.P > 0 ? md.P : 1);
-  warp_params_lds(md, fp, tp, tg);
+  flow_params_lds<true>(md.theta, fp, tp, tg);
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   bool fail = false;
@@ -385,7 +360,7 @@ __global__ __launch_bounds__(256) void k_predict_warp(tgp_model md, FlowProg fp,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* tp = reinterpret_cast<double*>(smem_raw);
   double* tg = tp + (md.P > 0 ? md.P : 1);
-  warp_params_lds(md, fp, tp, tg);
+  flow_params_lds<true>(md.theta, fp, tp, tg);
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= md.N) return;
   const double var = v[n] + exp(md.log_var_noise[0]), m_ = mu[n];

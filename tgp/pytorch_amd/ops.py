@@ -598,14 +598,13 @@ def _flow_model(N, S, flow, theta, lvn, dev, scale=1.0, lik=L.LIK_FLOW):
     return md, (xs, wn)
 
 
-def ell_flow(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
-    """TGP quadrature ELL with gradients (likelihoods/GaussianNonLinearMean.py:64-150).
-    Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp)."""
+def _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, lik):
+    """tgp_ell_flow_f64 for either quadrature likelihood: dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp)."""
     lib = L.load()
     Y, mu, v, lvn = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     dev, N = Y.device, Y.numel()
-    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale)
+    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=lik)
     ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
     out = torch.empty(2, dtype=torch.float64, device=dev)
     gmu, gv = torch.empty_like(mu), torch.empty_like(v)
@@ -617,24 +616,19 @@ def ell_flow(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     return {"ell": out[0], "g_lvn": out[1], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "g_rowp": grp}
 
 
+def ell_flow(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
+    """TGP quadrature ELL with gradients (likelihoods/GaussianNonLinearMean.py:64-150).
+    Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp)."""
+    return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_FLOW)
+
+
 def ell_bernoulli(Y, mu, v, flow, theta, S, rowp=None, scale=1.0):
     """Bernoulli (probit) quadrature ELL with gradients (likelihoods/Bernoulli.py expected_log_prob; tgp_ell_flow_f64 with
     TGP_LIK_BERNOULLI).  Returns dict(ell, g_mu, g_v, g_theta, g_rowp)."""
-    lib = L.load()
-    Y, mu, v = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v")
-    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
-    dev, N = Y.device, Y.numel()
-    lvn = torch.zeros(1, dtype=torch.float64, device=dev)      # required pointer, not read
-    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=L.LIK_BERNOULLI)
-    ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    gmu, gv = torch.empty_like(mu), torch.empty_like(v)
-    gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
-    grp = torch.empty_like(rowp) if rowp is not None else None
-    L.check(lib.tgp_ell_flow_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
-                                 L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
-            "tgp_ell_flow_f64")
-    return {"ell": out[0], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "g_rowp": grp}
+    lvn = torch.zeros(1, dtype=torch.float64, device=Y.device)      # required pointer, not read
+    res = _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_BERNOULLI)
+    del res["g_lvn"]
+    return res
 
 
 class EllBernoulliFunction(torch.autograd.Function):

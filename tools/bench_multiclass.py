@@ -5,7 +5,7 @@ workload.  Shape: N = 8611, D = 4, M = 100, C = 4, S = 32, SAL x 2 per class, co
     python tools/bench_multiclass.py --kernels --steps 50                 # the two likelihood launches alone, for a kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/bench_multiclass.py --kernels --steps 50
 
-`--kernels` launches k_ell_softmax (S * C = 128 flow evaluations per row) and the stand-alone k_ell_flow at the same N with
+`--kernels` launches k_ell_softmax (S * C = 128 flow evaluations per row) and the stand-alone k_ell_quad at the same N with
 S = 128 nodes (the same number of flow evaluations per row), `--steps` times each.
 """
 import argparse

@@ -5,7 +5,7 @@ The roof of a flow kernel is f64 VALU issue, not HBM: one SIMD issue
    valu_issue_frac = SQ_INSTS_VALU * 4 / (GRBM_GUI_ACTIVE / 8 XCDs * 1024 SIMDs)
 is the share of the chip's f64 vector issue slots the kernel's VALU instructions took if every one of them cost an f64 slot
 (an upper bound: 32-bit integer / move instructions cost half), and SQ_ACTIVE_INST_VALU (quad-cycles, MI355X_MICROARCH.md) * 4
-the cycles the vector pipes were actually busy.  `kernel=units` (e.g. k_ell_flow=64000000) adds instructions per unit."""
+the cycles the vector pipes were actually busy.  `kernel=units` (e.g. k_ell_quad=64000000) adds instructions per unit."""
 import csv
 import sys
 from collections import defaultdict
