@@ -284,6 +284,30 @@ size_t tgp_cholesky_bwd_workspace_bytes(int32_t M);
 int tgp_cholesky_bwd_f64(const double* L, const double* Linv, const double* L_bar, int32_t M, double* A_bar, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* Unwhitened q(u) (is_whiten=False, models/sparse_MF_SP.py:352-391 and :433-453): the caller's (m, L_q) describe
+ * q(u) = N(m, L_q L_q^T) on the inducing values.  With L L^T = K_ZZ + jitter I and the zero mean function
+ *   m_w = L^-1 m,   Lam_w = L^-1 tril(L_q)        (lower x lower = lower; the strict upper triangle of Lam_w is exact zeros,
+ *                                                  the strict upper triangle of L_q is never read)
+ * is the whitened model with the same q(f) and the same KL against N(0, L L^T): every whitened entry of this header then
+ * serves the unwhitened model at (m_w, Lam_w).  Z (M,D), m (M), L_q (M,M); outputs m_w (M), Lam_w, L, Linv (M,M);
+ * status[0] is tgp_cholesky_f64's (the host runs the jitter ladder).
+ * tgp_unwhiten_bwd_f64: given the forward's L, Linv, m_w, Lam_w and the cotangents m_w_bar (M), Lam_w_bar (M,M; its part on
+ * and below the diagonal counts) it writes
+ *   m_bar = L^-T m_w_bar,   L_q_bar = tril(L^-T Lam_w_bar),   L_bar = -tril(L^-T (m_w_bar m_w^T + Lam_w_bar Lam_w^T)),
+ *   K_bar = tgp_cholesky_bwd_f64(L_bar),  and  Z_bar (M,D), raw_ls_bar (D), raw_os_bar (1) = K_bar + K_bar^T contracted with
+ *   the derivative of the kernel matrix (the jitter and the diagonal carry no gradient with respect to Z).
+ * Limits: 1 <= M <= TGP_BIG_MAX_M, 1 <= D <= 16, else TGP_E_UNSUPPORTED; a workspace below the *_workspace_bytes value gives
+ * TGP_E_WORKSPACE (tgp_last_error() names the entry).  No float atomics, fixed reduction orders: same input, same bits. */
+size_t tgp_unwhiten_workspace_bytes(int32_t M, int32_t D);
+int tgp_unwhiten_f64(int32_t kernel, const double* Z, const double* raw_ls, const double* raw_os, int32_t M, int32_t D,
+                     double jitter, const double* m, const double* L_q, double* m_w, double* Lam_w, double* L, double* Linv,
+                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t tgp_unwhiten_bwd_workspace_bytes(int32_t M, int32_t D);
+int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, const double* raw_os, int32_t M, int32_t D,
+                         const double* L, const double* Linv, const double* m_w, const double* Lam_w, const double* m_w_bar,
+                         const double* Lam_w_bar, double* m_bar, double* L_q_bar, double* Z_bar, double* raw_ls_bar,
+                         double* raw_os_bar, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Adjoint of tgp_qf_moments_f64 (what autograd replays for models/sparse_MF_SP.py:274-396 when a caller differentiates
  * the q(f) marginals outside ELBO(): predictive moments with respect to the inducing points, hyper-parameters or q(u)).
  * Given mu_bar, v_bar (N) it writes d(sum_n mu_bar_n mu_n + v_bar_n v_n)/d{Z, raw_ls, raw_os, m, Lam} into `grads`

@@ -478,6 +478,59 @@ int tgp_cholesky_bwd_f64(const double* L, const double* Linv, const double* L_ba
 
 size_t tgp_cholesky_bwd_workspace_bytes(int32_t M) { return big_cholesky_workspace_doubles(M) * sizeof(double); }
 
+size_t tgp_unwhiten_workspace_bytes(int32_t M, int32_t D) { return unwhiten_workspace_bytes(M, D); }
+
+int tgp_unwhiten_f64(int32_t kernel, const double* Z, const double* raw_ls, const double* raw_os, int32_t M, int32_t D,
+                     double jitter, const double* m, const double* L_q, double* m_w, double* Lam_w, double* L, double* Linv,
+                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) {
+    set_error_text("tgp_unwhiten_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!Z) return -2;
+  if (!raw_ls) return -3;
+  if (!raw_os) return -4;
+  if (!m) return -8;
+  if (!L_q) return -9;
+  if (!m_w) return -10;
+  if (!Lam_w) return -11;
+  if (!L) return -12;
+  if (!Linv) return -13;
+  if (!status) return -14;
+  return launch_unwhiten(kernel, Z, raw_ls, raw_os, M, D, jitter, m, L_q, m_w, Lam_w, L, Linv, status, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream));
+}
+
+size_t tgp_unwhiten_bwd_workspace_bytes(int32_t M, int32_t D) { return unwhiten_bwd_workspace_bytes(M, D); }
+
+int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, const double* raw_os, int32_t M, int32_t D,
+                         const double* L, const double* Linv, const double* m_w, const double* Lam_w, const double* m_w_bar,
+                         const double* Lam_w_bar, double* m_bar, double* L_q_bar, double* Z_bar, double* raw_ls_bar,
+                         double* raw_os_bar, void* workspace, size_t workspace_bytes, void* stream) {
+  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) {
+    set_error_text("tgp_unwhiten_bwd_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!Z) return -2;
+  if (!raw_ls) return -3;
+  if (!raw_os) return -4;
+  if (!L) return -7;
+  if (!Linv) return -8;
+  if (!m_w) return -9;
+  if (!Lam_w) return -10;
+  if (!m_w_bar) return -11;
+  if (!Lam_w_bar) return -12;
+  if (!m_bar) return -13;
+  if (!L_q_bar) return -14;
+  if (!Z_bar) return -15;
+  if (!raw_ls_bar) return -16;
+  if (!raw_os_bar) return -17;
+  return launch_unwhiten_bwd(kernel, Z, raw_ls, raw_os, M, D, L, Linv, m_w, Lam_w, m_w_bar, Lam_w_bar, m_bar, L_q_bar, Z_bar,
+                             raw_ls_bar, raw_os_bar, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 int tgp_gemm_f64(int32_t trans_a, int32_t trans_b, int32_t tri, int32_t m, int32_t n, int32_t k, double alpha,
                  const double* A, int32_t lda, const double* B, int32_t ldb, double beta, double* C, int32_t ldc,
                  void* stream) {

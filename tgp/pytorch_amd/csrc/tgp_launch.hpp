@@ -151,4 +151,15 @@ size_t qf_joint_sample_workspace_bytes(int N, int S);
 int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double jitter, const double* eps, int S, double* F0,
                            double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// tgp_unwhiten.hip (unwhitened q(u): m_w = L^-1 m, Lam_w = L^-1 tril(L_q), and the adjoint down to Z and the kernel parameters)
+size_t unwhiten_workspace_bytes(int M, int D);
+int launch_unwhiten(int kernel, const double* Z, const double* raw_ls, const double* raw_os, int M, int D, double jitter,
+                    const double* m, const double* Lq, double* m_w, double* Lam_w, double* L, double* Linv, int32_t* status,
+                    void* workspace, size_t workspace_bytes, hipStream_t st);
+size_t unwhiten_bwd_workspace_bytes(int M, int D);
+int launch_unwhiten_bwd(int kernel, const double* Z, const double* raw_ls, const double* raw_os, int M, int D, const double* L,
+                        const double* Linv, const double* m_w, const double* Lam_w, const double* m_w_bar, const double* Lam_w_bar,
+                        double* m_bar, double* Lq_bar, double* Z_bar, double* raw_ls_bar, double* raw_os_bar, void* workspace,
+                        size_t workspace_bytes, hipStream_t st);
+
 }  // namespace tgp

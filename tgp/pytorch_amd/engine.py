@@ -236,11 +236,17 @@ class ElboEngine:
     def __init__(self, X, Y, params, N_total, flow_blocks=None, S=None, rowp=None, lr=0.01, betas=(0.9, 0.999),
                  eps=1e-8, device="cuda:0", world_size=1, rank=0, mb_global=None, process_group=None,
                  kernel="scale_rbf", mlp=None, mlp_weights=None, nn_weight_decay=1e-5, mlp_training=True,
-                 jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None):
+                 jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None,
+                 is_whiten=True):
         """`mlp` (ops.MlpSpec) + `mlp_weights` (packed, nnets * weights_per_net): input-dependent flow (ID_TGP) whose
         per-row parameters come from the HIP MLP kernels inside the step; `nn_weight_decay` is the reference's Adam
         group for the 'NNets' parameters (main.py:276-288).  `share` = another ElboEngine of the same model whose flat
         parameter / gradient / Adam buffers and step counter this one uses (two batch sizes of one training run)."""
+        if not is_whiten:
+            # `params` of an unwhitened model describe q(u) itself; the captured step (one rank or world_size > 1) has no
+            # transform in it
+            raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
+                                      "the eager path (Trainer_SP), on one rank")
         self.lib = L.load()
         self.device = torch.device(device)
         self.world_size, self.rank, self.pg = int(world_size), int(rank), process_group
@@ -712,6 +718,9 @@ class MinibatchEngine:
     With world_size > 1 each rank gathers and processes its row shard of every batch (one all-reduce per step)."""
 
     def __init__(self, X, Y, params, N_total, batch_size, device="cuda:0", world_size=1, rank=0, **engine_kw):
+        if not engine_kw.pop("is_whiten", True):
+            raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
+                                      "the eager path (Trainer_SP), on one rank")
         if engine_kw.get("likelihood") == "warped":
             raise NotImplementedError("the warped likelihood has no minibatch engine: full batch on one rank only (ElboEngine)")
         self.device = torch.device(device)

@@ -66,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--flow_arch", choices=FLOW_ARCHS, default=None, help="flow generator (default: the recipe's)")
     ap.add_argument("--num_blocks", type=int, default=None, help="flow blocks (default: the recipe's)")
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
+    ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
+                    help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
     ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs")
@@ -143,7 +145,7 @@ def main(argv=None):
                         init_params={"length_scale": 2.0, "kernel_scale": 2.0, "noisy_variance": 1e-6})
     ip = {"variational_distribution": {"variance_scale": 1e-5, "mean_scale": 0.0}}
     common = dict(model_specs=["zero", K], X=dc["X_tr"], init_Z=init_Z, N=dc["N_tr"], likelihood=lik, num_outputs=Dy,
-                  is_whiten=True, K_is_shared=False, mean_is_shared=False, Z_is_shared=False, q_U_is_shared=False,
+                  is_whiten=bool(args.whiten), K_is_shared=False, mean_is_shared=False, Z_is_shared=False, q_U_is_shared=False,
                   add_noise_inducing=0.0, init_params=ip)
     if args.model == "SVGP" or wgp:
         model = sparse_MF_GP(**common)

@@ -10,8 +10,9 @@ What differs is underneath: every number is produced by the HIP kernels of libtg
 blocked Cholesky, hand-derived adjoints, the MLP kernel for the input-dependent flows' networks in training AND in
 every evaluation method).  There is NO CPU fallback: calling these methods with CPU tensors
 raises (the oracle in oracle/ is the CPU restatement, and it is test infrastructure only).
-Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs), whitened q(u),
-zero mean, 'scale_rbf' kernel, float64.
+Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs), zero mean, 'scale_rbf' /
+'scale_matern32' kernel, float64.  Both q(u) parameterisations: with is_whiten=False the parameters (m, L_q) describe
+q(u) = N(m, L_q L_q^T) and every method runs the whitened kernels at m_w = L^-1 m, Lam_w = L^-1 tril(L_q) (tgp_unwhiten_f64).
 """
 from typing import List
 
@@ -66,7 +67,6 @@ class sparse_MF_SP(nn.Module):
             "this build implements the single-output path (Dy = 1, every BASELINE config)"
         assert not isinstance(likelihood, MulticlassCategorical) or int(num_outputs) == likelihood.C, \
             "MulticlassCategorical needs num_outputs = its number of classes"
-        assert is_whiten, "only the whitened representation (main.py: whiten = True) has a HIP implementation"
         assert model_specs[0] == "zero", "only the 'zero' mean function (main.py) is provided"
         assert not (K_is_shared or mean_is_shared or Z_is_shared or q_U_is_shared), "sharing flags are False in main.py"
         self.out_dim = int(num_outputs)
@@ -86,7 +86,7 @@ class sparse_MF_SP(nn.Module):
         if isinstance(likelihood, Bernoulli):
             # the ABI's noise pointer: read by no Bernoulli kernel, gradient 0; a buffer, so model.parameters() is the reference's
             self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
-        self.is_whiten = is_whiten
+        self.is_whiten = bool(is_whiten)
 
         # inducing points (sparse_MF_SP.py:140-156)
         Z = torch.zeros(self.out_dim, self.M, self.inp_dim, dtype=cg.dtype)
@@ -144,7 +144,28 @@ class sparse_MF_SP(nn.Module):
     def _is_multiclass(self):
         return isinstance(self.likelihood, MulticlassCategorical)
 
-    def _gp_params(self, c=None):
+    def _gp_params(self, c=None, jitter=0.0, ladder=None, info=None):
+        """What the whitened kernels consume: (Z, raw_ls, raw_os, m, Lam, lvn).  Whitened: the parameters themselves.
+        Unwhitened (sparse_MF_SP.py:357-360, :386-391): m_w = L^-1 m, Lam_w = L^-1 tril(L_q) with L L^T = K_ZZ + jitter I, the
+        factorisation under psd_safe_cholesky's ladder (or `ladder`); differentiable in Z, the kernel parameters, m and L_q
+        when one of them needs it.  `info["jitter"]` receives the jitter the transform ended with."""
+        p = self._raw_params(c)
+        if self.is_whiten:
+            if info is not None:
+                info["jitter"] = 0.0
+            return p
+        Z, rl, ro, m, Lq, lvn = p
+        kern = self.covariance_function.hip_kernel
+        if ladder is None and cg.global_jitter is not None:      # config.global_jitter: the ladder's base, as for the step
+            ladder = ops.jitter_ladder(jitter=cg.global_jitter)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lq)):
+            m_w, Lam_w = ops.UnwhitenFunction.apply(Z, rl, ro, m, Lq, kern, float(jitter), ladder, info)
+        else:
+            m_w, Lam_w, _, _ = ops.unwhiten(*(t.detach() for t in (Z, rl, ro, m, Lq)), jitter=float(jitter), kernel=kern,
+                                            info=info, ladder=ladder)
+        return Z, rl, ro, m_w, Lam_w, lvn
+
+    def _raw_params(self, c=None):
         k = self.covariance_function
         if c is not None:            # latent GP c of a multi-class model: slice c of the batched parameters, no noise
             D = self.inp_dim
@@ -159,11 +180,13 @@ class sparse_MF_SP(nn.Module):
         differentiable (tgp_qf_moments_bwd_f64) when a parameter needs it."""
         mus, vs = [], []
         for c in range(self.out_dim):
-            Z, rl, ro, m, Lam, _ = self._gp_params(c)
+            info = {}
+            Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
             if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
                 mu, v = ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
             else:
-                mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), kernel=self.covariance_function.hip_kernel)
+                mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
+                                       kernel=self.covariance_function.hip_kernel)
             mus.append(mu)
             vs.append(v)
         return torch.stack(mus), torch.stack(vs)
@@ -237,26 +260,46 @@ class sparse_MF_SP(nn.Module):
         if not diagonal:
             if self._is_multiclass:
                 raise NotImplementedError("diagonal=False is not built for multi-class models (num_outputs = C latent GPs)")
-            Z, rl, ro, m, Lam, _ = self._gp_params()
+            info = {}
+            Z, rl, ro, m, Lam, _ = self._gp_params(info=info)
             if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
                 raise NotImplementedError("the full covariance (diagonal=False) has no backward: call it under torch.no_grad(); "
                                           "diagonal=True is the differentiable path")
-            mu, cov = ops.qf_cov(X2.detach(), *(t.detach() for t in (Z, rl, ro, m, Lam)),
+            # (unwhitened: the factor behind Sigma starts at the jitter the transform ended with; whitened: 0)
+            mu, cov = ops.qf_cov(X2.detach(), *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
                                  kernel=self.covariance_function.hip_kernel)
             return mu.reshape(1, -1, 1), cov.unsqueeze(0)
         if self._is_multiclass:
             mu, v = self._qf_per_class(X2)
             return mu.unsqueeze(2), v.unsqueeze(2)
-        Z, rl, ro, m, Lam, _ = self._gp_params()
+        info = {}
+        Z, rl, ro, m, Lam, _ = self._gp_params(info=info)
         if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
             # differentiable like the reference's (autograd through :274-396): tgp_qf_moments_bwd_f64 in the backward
+            # (its own ladder from jitter 0: with an unwhitened q(u) it ends where the transform's did, same matrix, same ladder)
             mu, v = ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
         else:
-            mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), kernel=self.covariance_function.hip_kernel)
+            mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
+                                   kernel=self.covariance_function.hip_kernel)
         return mu.reshape(1, -1, 1), v.reshape(1, -1, 1)
 
+    def _kld_unwhitened(self, c=None):
+        """KL(q(u) || p(u)) of sparse_MF_SP.py:433-453: p(u) = N(0, K_ZZ + j I) from add_jitter_MultivariateNormal, which adds
+        at least 1e-8 (ladder 1e-8 * 10^i, i < 5).  Equal to the whitened KL at unwhiten(m, L_q; j); differentiable in Z,
+        the kernel parameters, m and L_q."""
+        Z, rl, ro, m_w, Lam_w, _ = self._gp_params(c, jitter=ops.KL_PRIOR_JITTERS[0], ladder=ops.KL_PRIOR_JITTERS)
+        if torch.is_grad_enabled() and (m_w.requires_grad or Lam_w.requires_grad):
+            return ops.KlFunction.apply(m_w, Lam_w).reshape(())
+        return ops.kl_whitened(m_w.detach(), Lam_w.detach())[0].reshape(()).clone()
+
     def KLD(self):
-        """Whitened KL (sparse_MF_SP.py:406-431), shape (Dy,); differentiable in (m, L_q) like the reference's."""
+        """KL(q(u) || p(u)), shape (Dy,): the whitened form (sparse_MF_SP.py:406-431), differentiable in (m, L_q) like the
+        reference's, or with is_whiten=False the KL against N(0, K_ZZ + j I) (:433-453), differentiable in Z and the kernel
+        parameters too."""
+        if not self.is_whiten:
+            if self._is_multiclass:
+                return torch.stack([self._kld_unwhitened(c) for c in range(self.out_dim)])
+            return self._kld_unwhitened().reshape(1)
         if self._is_multiclass:
             kls = []
             for c in range(self.out_dim):
@@ -279,12 +322,20 @@ class sparse_MF_SP(nn.Module):
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
         if self._is_multiclass:
             return self._elbo_multiclass(X2, Y)
-        Z, rl, ro, m, Lam, lvn = self._gp_params()
+        info = {}
+        Z, rl, ro, m, Lam, lvn = self._gp_params(info=info)
         spec, theta, rowp = self._flow_inputs(X2, with_grad=True)
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
                    lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else (ops.L.LIK_WARPED if self._is_warped else None))
+        if not self.is_whiten:
+            # the step's likelihood term at (m_w, Lam_w) and the jitter their factor was formed with (0 unless the ladder
+            # raised it), its own KL switched off; the KL against the reference's jittered prior is added apart
+            cfg["jitter"] = info["jitter"]
+            ell = ops.EllStepFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
+            kld = self.KLD().sum()
+            return ell - kld, ell, kld
         elbo, ell, kld = ops.ElboFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
         return elbo, ell, kld
 

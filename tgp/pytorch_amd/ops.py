@@ -432,6 +432,148 @@ class KlFunction(torch.autograd.Function):
         return (g * gm).reshape(ctx.shapes[0]), (g * gL).reshape(ctx.shapes[1])
 
 
+# ---------------------------------------------------------------------------------------------------
+# unwhitened q(u) (is_whiten=False): the change of variables to the whitened kernels
+# ---------------------------------------------------------------------------------------------------
+KL_PRIOR_JITTERS = tuple(1e-8 * (10 ** i) for i in range(5))     # add_jitter_MultivariateNormal (dsp/utils.py:200-218), float64
+
+
+def run_jitter_ladder(attempt, jitter=0.0, ladder=None, info=None):
+    """psd_safe_cholesky's retry protocol around one factorising call.  `attempt(jit)` runs the call at jitter `jit` and returns
+    True when the factorisation FAILED.  The first try is at `jitter`; after a failure the values of `ladder` (default:
+    jitter_ladder()) above `jitter` are tried in turn, each success after a failure warns (NumericalWarning).  Returns the jitter
+    it ended with (also in `info["jitter"]`); NotPSDError when every value failed."""
+    jitter = float(jitter)
+    if info is not None:
+        info["jitter"] = jitter
+    if not attempt(jitter):
+        return jitter
+    last = jitter
+    for jit in (jitter_ladder() if ladder is None else ladder):
+        jit = float(jit)
+        if jit <= jitter:
+            continue
+        last = jit
+        if not attempt(jit):
+            warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
+            if info is not None:
+                info["jitter"] = jit
+            return jit
+    raise NotPSDError("K_MM not positive definite even with jitter %g" % last)
+
+
+def unwhiten(Z, raw_ls, raw_os, m, L_q, jitter=0.0, check=True, kernel="scale_rbf", info=None, ladder=None,
+             workspace_bytes=None):
+    """(m_w, Lam_w, L, Linv) with L L^T = K_ZZ + jitter I, m_w = L^-1 m, Lam_w = L^-1 tril(L_q) (tgp_unwhiten_f64): the
+    whitened parameters with the same q(f) and KL as q(u) = N(m, L_q L_q^T).  `check`: the status word is read after every
+    call (one host sync each; the model's two transforms per ELBO always check, whatever config.status_check says) and a failed
+    factorisation goes through run_jitter_ladder with `ladder` (default: psd_safe_cholesky's, as in qf_moments);
+    `info["jitter"]` receives the value it ended with.  `workspace_bytes` overrides the size of the workspace handed to the
+    library (tests of its refusal)."""
+    lib = L.load()
+    Z, raw_ls, raw_os, m, L_q = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"), (L_q, "L_q")))
+    M, D = Z.shape
+    dev = Z.device
+    kid = kernel_id(kernel)
+    nbytes = lib.tgp_unwhiten_workspace_bytes(M, D)
+    if nbytes == 0:              # outside the library's limits: let it say so, before anything is allocated
+        L.check(lib.tgp_unwhiten_f64(kid, L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, float(jitter), None, None, None, None,
+                                     None, None, None, None, 0, L.stream_ptr()), "tgp_unwhiten_f64")
+    if m.numel() != M or tuple(L_q.shape) != (M, M):
+        raise ValueError("unwhiten: Z (M, D), m (M), L_q (M, M)")
+    if workspace_bytes is not None:
+        nbytes = int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    m_w = torch.empty(M, dtype=torch.float64, device=dev)
+    Lam_w, Lo, Li = (torch.empty(M, M, dtype=torch.float64, device=dev) for _ in range(3))
+    status = torch.zeros(8, dtype=torch.int32, device=dev)
+
+    def attempt(jit):
+        L.check(lib.tgp_unwhiten_f64(kid, L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, float(jit), L.ptr(m), L.ptr(L_q),
+                                     L.ptr(m_w), L.ptr(Lam_w), L.ptr(Lo), L.ptr(Li), L.ptr(status), L.ptr(ws), nbytes,
+                                     L.stream_ptr()), "tgp_unwhiten_f64")
+        return check and raise_for_status(status.cpu())
+    run_jitter_ladder(attempt, jitter, ladder, info)
+    return m_w, Lam_w, Lo, Li
+
+
+def unwhiten_bwd(Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w, m_w_bar, Lam_w_bar, kernel="scale_rbf", workspace_bytes=None):
+    """Adjoint of `unwhiten` (tgp_unwhiten_bwd_f64): dict(m, L_q, Z, raw_ls, raw_os) for the cotangents of (m_w, Lam_w)."""
+    lib = L.load()
+    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    Lo, Li, m_w, Lam_w = _c(Lo, "L"), _c(Li, "Linv"), _c(m_w, "m_w"), _c(Lam_w, "Lam_w")
+    m_w_bar, Lam_w_bar = _c(m_w_bar.reshape(-1), "m_w_bar"), _c(Lam_w_bar, "Lam_w_bar")
+    M, D = Z.shape
+    if m_w_bar.numel() != M or tuple(Lam_w_bar.shape) != (M, M):
+        raise ValueError("unwhiten_bwd: m_w_bar (M), Lam_w_bar (M, M)")
+    dev = Z.device
+    nbytes = lib.tgp_unwhiten_bwd_workspace_bytes(M, D) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    g = {"m": torch.empty(M, dtype=torch.float64, device=dev), "L_q": torch.empty(M, M, dtype=torch.float64, device=dev),
+         "Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os)}
+    L.check(lib.tgp_unwhiten_bwd_f64(kernel_id(kernel), L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, L.ptr(Lo), L.ptr(Li),
+                                     L.ptr(m_w), L.ptr(Lam_w), L.ptr(m_w_bar), L.ptr(Lam_w_bar), L.ptr(g["m"]), L.ptr(g["L_q"]),
+                                     L.ptr(g["Z"]), L.ptr(g["raw_ls"]), L.ptr(g["raw_os"]), L.ptr(ws), nbytes, L.stream_ptr()),
+            "tgp_unwhiten_bwd_f64")
+    return g
+
+
+class UnwhitenFunction(torch.autograd.Function):
+    """(m_w, Lam_w) = unwhiten(Z, raw_ls, raw_os, m, L_q) with autograd in all five.  `jitter`: the value the factorisation
+    starts from; `ladder`: the values tried when it fails (None: psd_safe_cholesky's); `info["jitter"]`: what it ended with."""
+
+    @staticmethod
+    def forward(ctx, Z, raw_ls, raw_os, m, L_q, kernel, jitter, ladder, info):
+        if info is None:
+            info = {}
+        m_w, Lam_w, Lo, Li = unwhiten(Z.detach(), raw_ls.detach(), raw_os.detach(), m.detach(), L_q.detach(), jitter=jitter,
+                                      kernel=kernel, info=info, ladder=ladder)
+        ctx.save_for_backward(Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w)
+        ctx.kernel = kernel
+        ctx.shapes = (Z.shape, raw_ls.shape, raw_os.shape, m.shape, L_q.shape)
+        return m_w, Lam_w
+
+    @staticmethod
+    def backward(ctx, g_m, g_Lam):
+        Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w = ctx.saved_tensors
+        if g_m is None:
+            g_m = torch.zeros_like(m_w)
+        if g_Lam is None:
+            g_Lam = torch.zeros_like(Lam_w)
+        g = unwhiten_bwd(Z.detach(), raw_ls.detach(), raw_os.detach(), Lo, Li, m_w, Lam_w, g_m, g_Lam, kernel=ctx.kernel)
+        return tuple(g[k].reshape(s) for k, s in zip(("Z", "raw_ls", "raw_os", "m", "L_q"), ctx.shapes)) + (None,) * 4
+
+
+class EllStepFunction(torch.autograd.Function):
+    """The likelihood term of the training step alone: ELL = out[1] of elbo_step with kl_scale = 0, so that the gradients are
+    those of ELL only, at a caller-chosen jitter (the unwhitened ELBO evaluates the step at the jitter its transform used and
+    adds its own KL).  A factorisation that fails at that jitter raises NotPSDError."""
+
+    @staticmethod
+    def forward(ctx, X, Y, Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp, cfg):
+        out, g, status, _ = elbo_step(X, Y, Z.detach(), raw_ls.detach(), raw_os.detach(), m.detach(), Lam.detach(), lvn.detach(),
+                                      cfg["N_total"], flow=cfg.get("flow"), theta=theta.detach() if theta is not None else None,
+                                      rowp=rowp.detach() if rowp is not None else None, S=cfg.get("S"),
+                                      jitter=cfg.get("jitter", 0.0), kl_scale=0.0, mb_global=cfg.get("mb_global"),
+                                      kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"))
+        cfg["last_status"] = status
+        if cfg.get("check_status", True) and raise_for_status(status.cpu()):
+            raise NotPSDError("K_MM not positive definite in the step at jitter %g (pivot %d)" % (cfg.get("jitter", 0.0),
+                                                                                                  int(status[0])))
+        ctx.grads = g
+        ctx.shapes = tuple(None if t is None else t.shape for t in (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
+        return out[1].clone()
+
+    @staticmethod
+    def backward(ctx, g_ell):
+        g = ctx.grads
+        keys = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "rowp")
+        res = []
+        for k, shp in zip(keys, ctx.shapes):
+            res.append(None if shp is None or k not in g else (g[k] * g_ell).reshape(shp))
+        return (None, None) + tuple(res) + (None,)
+
+
 def kernel_matrix(X1, X2, raw_ls, raw_os, kernel="scale_rbf", jitter=0.0):
     """K(X1, X2) (X2 None: K(X1, X1) + jitter I) for 'scale_rbf' / 'scale_matern32' (tgp_kernel_matrix_f64)."""
     lib = L.load()

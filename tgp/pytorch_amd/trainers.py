@@ -121,6 +121,8 @@ class Trainer_SP_regression:
         model = self.model
         if not hasattr(model, "_gp_params") or any(g["lr"] != lr_ALL for g in groups):
             return None
+        if not getattr(model, "is_whiten", True):      # unwhitened q(u): the eager loop (the engines take is_whiten=True only)
+            return None
         # the engine updates EVERY parameter of its flat buffer: a stage that freezes some (lr = 0.0 entries,
         # trainer_base.py:155-179) or leaves some to a later stage must take the torch optimiser
         if {id(q) for g in groups for q in g["params"]} != {id(q) for q in model.parameters()}:
