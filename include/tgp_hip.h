@@ -451,6 +451,31 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream);
 
+/* Exact CDF and quantiles of the predictive distribution tgp_predict_f64 integrates (TGP_LIK_GAUSS and TGP_LIK_FLOW; model
+ * fields as for tgp_predict_f64, everything in the model's standardised units):
+ *   p(y | x_n) = sum_s wn_s N(y | g_ns, sig^2),  g_ns = G(mu_n + sqrt(2 v_n) xs_s),  sig^2 = exp(log_var_noise)
+ *   F_n(t) = sum_s wn_s Phi((t - g_ns) / sig),   strictly increasing, F_n' = the density above.
+ * tgp_predict_cdf_f64: cdf[n] = F_n(Y[n]) (the PIT values of a calibration plot) and, when sf is given, the upper tail
+ * sf[n] = sum_s wn_s Phi(-(Y[n] - g_ns) / sig) from its own sum; Phi through erfc on the side where it is small.
+ * tgp_predict_quantile_f64: t[q,n] = the root of F_n(t) = probs[q];  probs[q] in (0,1) in any order, zq[q] = Phi^-1(probs[q])
+ * from the host.  TGP_LIK_GAUSS or an empty program: t = mu + zq sqrt(max(v, 0) + sig^2), no iteration (the CDF: one term).
+ * A row with v <= 0 counts as v = 0: t = G(mu) + zq sig.  Else the row's S node values are computed once (the sweeps of
+ * tgp_predict_f64; TGP_FLAG_PER_ROW programs included) and kept in LDS for all Q roots; each root starts at
+ * t0 = G(mu + zq sqrt v) + zq sig, grows a bracket by doubling steps of max(sig, |t0| 2^-20), takes Newton steps with F',
+ * bisects whenever a step leaves the bracket, and stops at an exact hit or a step <= 2^-50 max(1, |t|); at most 128 evaluations
+ * of F per phase.  probs[q] <= 0.5 solves sum wn Phi(z) = p, probs[q] > 0.5 the upper-tail equation sum wn Phi(-z) = 1 - p, so
+ * both tails are resolved to relative accuracy.  status (device int32[1], zeroed by the caller): the call ADDS the number of
+ * roots that ran out of evaluations; their t is NaN.
+ * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED and TGP_LIK_SOFTMAX are
+ * refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
+ * over s: same input, same bits. */
+#define TGP_QUANTILE_MAX_S 256
+#define TGP_QUANTILE_MAX_Q 32
+int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* probs,
+                             const double* zq, int32_t Q, double* t /* (Q,N) */, int32_t* status, void* stream);
+int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
+                        double* cdf /* (N) */, double* sf /* (N), optional */, void* stream);
+
 /* Inducing-point initialisation: the numerical kernels behind utils.KMEANS, which replaces
  * sklearn.cluster.KMeans(init='k-means++', n_init, random_state) of dsp/utils.py:143-159.  Random draws, the stopping
  * rule and the restarts stay on the host (tgp/pytorch_amd/utils.py); D <= 16.

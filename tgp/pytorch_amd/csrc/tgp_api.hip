@@ -777,6 +777,63 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
   return launch_predict(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
 }
 
+// the checks the two quantile entries share: likelihood, limits, the pointers the kernels read
+static int check_quantile_model(const tgp_model* model, const double* mu, const double* v, const double* rowp, const char* entry,
+                                bool* flowed) {
+  if (!model || model->N < 1 || !model->log_var_noise) return -1;
+  if (model->lik == TGP_LIK_BERNOULLI || model->lik == TGP_LIK_WARPED || model->lik == TGP_LIK_SOFTMAX) {
+    set_error_text("%s: no quantiles for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only; a warped model's are "
+                   "T^-1(mu + z sqrt(v + noise)) through tgp_flow_inverse_f64)", entry, model->lik);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW) return -1;
+  *flowed = model->lik == TGP_LIK_FLOW;
+  if (*flowed) {
+    if (model->S < 1 || model->S > TGP_QUANTILE_MAX_S) {
+      set_error_text("%s: S = %d outside 1..%d", entry, model->S, TGP_QUANTILE_MAX_S);
+      return TGP_E_UNSUPPORTED;
+    }
+    if (!model->xs || !model->wn || model->nblk < 0 || model->P < 0 || model->RP < 0) return -1;
+    if (model->P > 0 && !model->theta) return -1;
+  }
+  if (!mu) return -2;
+  if (!v) return -3;
+  if (*flowed && model->RP > 0 && !rowp) return -4;
+  return 0;
+}
+
+int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* probs,
+                             const double* zq, int32_t Q, double* t, int32_t* status, void* stream) {
+  bool flowed = false;
+  if (int rc = check_quantile_model(model, mu, v, rowp, "tgp_predict_quantile_f64", &flowed)) return rc;
+  if (Q < 1 || Q > TGP_QUANTILE_MAX_Q) {
+    set_error_text("tgp_predict_quantile_f64: Q = %d outside 1..%d", Q, TGP_QUANTILE_MAX_Q);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!probs) return -5;
+  if (!zq) return -6;
+  if (!t) return -8;
+  if (!status) return -9;
+  FlowProg fp;
+  if (int rc = make_prog(model, flowed, fp)) return rc;
+  tgp_model md = *model;
+  md.program = nullptr;
+  return launch_predict_quantile(md, fp, mu, v, rowp, probs, zq, Q, t, status, static_cast<hipStream_t>(stream));
+}
+
+int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
+                        double* cdf, double* sf, void* stream) {
+  bool flowed = false;
+  if (int rc = check_quantile_model(model, mu, v, rowp, "tgp_predict_cdf_f64", &flowed)) return rc;
+  if (!Y) return -5;
+  if (!cdf) return -6;
+  FlowProg fp;
+  if (int rc = make_prog(model, flowed, fp)) return rc;
+  tgp_model md = *model;
+  md.program = nullptr;
+  return launch_predict_cdf(md, fp, mu, v, rowp, Y, cdf, sf, static_cast<hipStream_t>(stream));
+}
+
 int tgp_kmeans_assign_f64(const double* X, int32_t N, int32_t D, const double* C, int32_t K, int32_t* labels, double* mind2,
                           void* stream) {
   if (!X) return -1;

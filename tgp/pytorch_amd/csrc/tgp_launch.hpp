@@ -126,6 +126,12 @@ int launch_flow_inverse(const tgp_model& md, const FlowProg& fp, const double* t
 int launch_predict_warp(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* Y, double Y_std,
                         double* m1, double* m2, double* logp, hipStream_t st);
 
+// tgp_quantile.hip (exact CDF and quantiles of the Gauss-Hermite predictive; TGP_LIK_GAUSS / TGP_LIK_FLOW)
+int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                            const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st);
+int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                       const double* Y, double* cdf, double* sf, hipStream_t st);
+
 // tgp_softmax.hip (multi-class likelihood: softmax over C latent GPs, Monte Carlo over all classes of a row)
 struct SmxArgs {                 // by-value kernel argument built from a tgp_softmax descriptor
   int32_t N, C, S, P;            // P = theta_off[C]: every program's shared scalars

@@ -1,0 +1,252 @@
+// tgp_quantile.hip -- exact predictive CDF and quantiles of the Gauss-Hermite predictive of tgp_predict_f64:
+//   p(y | x_n) = sum_s wn_s N(y | g_ns, sig^2),  g_ns = G(mu_n + sqrt(2 v_n) xs_s),  sig^2 = exp(log_var_noise)
+//   F_n(t) = sum_s wn_s Phi((t - g_ns) / sig),   F_n'(t) = sum_s wn_s phi((t - g_ns) / sig) / sig   (the density above)
+//   k_pred_cdf<X>       cdf = F_n(Y_n) and the upper tail 1 - F_n from its own sum
+//   k_pred_quantile<X>  t = the root of F_n(t) = p for Q probabilities per row, a bracketed Newton iteration on the S node values
+//   k_quantile_gauss    TGP_LIK_GAUSS / the empty program: one Gaussian, closed forms for both
+// QLPR = 16 lanes share a data row (4 rows per wave, one wave per workgroup): the lanes sweep the row's S nodes -- and the Q
+// starting points G(mu + zq sqrt v) -- through the flow once (flow_forward_n, 4 elements in flight per lane) into LDS, and
+// every evaluation of F afterwards reads those S numbers only: lane l adds the nodes l, l + 16, ... in that order, the 16
+// partial sums are added by a DPP butterfly (every lane of the row ends with the same bits).  No float atomics, fixed
+// summation order: same input, same bits.  The loops are uniform over the wave (a row that is done keeps evaluating at its
+// root until the wave's last row is done), so the cross-lane adds always run with every lane on.
+// X: the extended flow kind set, as in k_predict<X>.
+#include "tgp_dev.hpp"
+#include "tgp_launch.hpp"
+
+namespace tgp {
+
+#define QLPR 16                       /* lanes per data row */
+#define QROWS (64 / QLPR)             /* rows per workgroup (one wave) */
+#define Q_MAXIT 128                   /* evaluations of F per phase */
+#define Q_SQRT1_2 0.70710678118654752440
+#define Q_INV_SQRT_2PI 0.39894228040143267794
+
+// row stride (doubles) of the node table: >= n and = 16 mod 32, so that the 16-double windows the two rows of a 32-lane half
+// read together fall on different banks
+static int q_row_stride(int n) { return (n + 15) / 32 * 32 + 16; }
+
+// sum over the 16 lanes of a row, every lane gets the total (ror_sum: x[l] + x[l ^ R] once x is 2R-periodic)
+__device__ __forceinline__ double row16_sum(double x) { return ror_sum<1>(ror_sum<2>(ror_sum<4>(ror_sum<8>(x)))); }
+
+// lower = sum_s wn_s Phi(z_s), upper = sum_s wn_s Phi(-z_s), dens = sum_s wn_s phi(z_s) / sig at t, z_s = (t - g_s) / sig.
+// Phi through erfc on the side where it is small (bern_node's rule): Phi(-|z|) = erfc(|z| / sqrt 2) / 2, Phi(|z|) = 1 - that.
+struct QSum { double lower, upper, dens; };
+template <bool DENS>
+__device__ __forceinline__ QSum q_eval(const double* __restrict__ g, const double* __restrict__ wn, int S, int l16, double t,
+                                       double sig) {
+  double lo = 0.0, up = 0.0, dn = 0.0;
+  for (int s0 = 0; s0 < S; s0 += QLPR) {
+    const int s = s0 + l16, sc = s < S ? s : S - 1;
+    const double w = s < S ? wn[sc] : 0.0;
+    const double z = (t - g[sc]) / sig, a = fabs(z);
+    const double small = 0.5 * erfc(a * Q_SQRT1_2), big = 1.0 - small;
+    lo += w * (z < 0.0 ? small : big);
+    up += w * (z < 0.0 ? big : small);
+    if (DENS) dn += w * exp(-0.5 * z * z);
+  }
+  QSum r;
+  r.lower = row16_sum(lo);
+  r.upper = row16_sum(up);
+  r.dens = DENS ? row16_sum(dn) * Q_INV_SQRT_2PI / sig : 0.0;
+  return r;
+}
+
+// The row's elements e = 0 .. S + Q - 1 through the flow into gs[e]: the quadrature nodes mu + sqrt(2 v) xs_e (the argument
+// k_predict forms), then the Q starting points mu + zq_q sqrt(v).  Lane l16 takes e = l16 + 16 j, four at a time.
+template <bool X>
+__device__ __forceinline__ void q_sweep(const FlowDev& F, const tgp_model& md, const double* __restrict__ rp, double m_, double vn,
+                                        const double* __restrict__ zq, int Q, int l16, double* __restrict__ gs) {
+  constexpr int NB = 4;
+  const int ne = md.S + Q;
+  const double sq2 = sqrt(2.0 * vn), sq1 = sqrt(vn);
+  for (int e0 = 0; e0 < ne; e0 += NB * QLPR) {
+    double f[NB], der[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16, ec = e < ne ? e : ne - 1;
+      f[u] = ec < md.S ? m_ + sq2 * md.xs[ec] : m_ + zq[ec - md.S] * sq1;
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, false, X>(F, f, rpn, der);
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16;
+      if (e < ne) gs[e] = f[u];
+    }
+  }
+}
+
+// dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), wn (S rounded up to even), then QROWS node tables of q_row_stride(S + Q)
+template <bool X>
+__global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                      const double* __restrict__ v, const double* __restrict__ rowp,
+                                                      const double* __restrict__ probs, const double* __restrict__ zq, int Q,
+                                                      int stride, double* __restrict__ t_out, int32_t* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int lane = threadIdx.x, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S;
+  double* gs = wl + (S + 1) / 2 * 2 + (size_t)r * stride;
+  for (int s = lane; s < S; s += 64) wl[s] = md.wn[s];
+  flow_params_lds<X>(md.theta, fp, tp, tg);   // (ends with a barrier: wl is staged too)
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double m_ = mu[nc], vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
+  const double sig = sqrt(exp(md.log_var_noise[0]));
+  q_sweep<X>(F, md, rp, m_, vn, zq, Q, l16, gs);
+  __syncthreads();
+  for (int q = 0; q < Q; ++q) {
+    const double p = probs[q];
+    const bool upper = p > 0.5;
+    const double tgt = upper ? 1.0 - p : p;
+    // fx = F(x) - p, taken from the tail that is small: increasing in x on both sides, derivative = the density
+    double x = gs[S + q] + zq[q] * sig;
+    QSum e = q_eval<true>(gs, wl, S, l16, x, sig);
+    double fx = upper ? tgt - e.upper : e.lower - tgt, dn = e.dens;
+    // a row without variance has one node value: the start is its closed form G(mu) + zq sig
+    bool done = !(vr > 0.0) || fx == 0.0, fail = false;
+    // ---- bracket: doubling steps from the start
+    double step = fmax(sig, fabs(x) * 9.5367431640625e-07);
+    const bool grow_up = fx < 0.0;
+    double lo = grow_up ? x : x - step, hi = grow_up ? x + step : x;
+    bool ok = done;
+    for (int it = 0; it < Q_MAXIT; ++it) {
+      if (__ballot(!ok) == 0ull) break;
+      const double probe = ok ? x : (grow_up ? hi : lo);
+      const QSum eb = q_eval<false>(gs, wl, S, l16, probe, sig);
+      const double fb = upper ? tgt - eb.upper : eb.lower - tgt;
+      if (!ok) {
+        if (grow_up ? fb >= 0.0 : fb <= 0.0) {
+          ok = true;
+        } else {
+          step *= 2.0;
+          if (grow_up) { lo = hi; hi = lo + step; } else { hi = lo; lo = hi - step; }
+        }
+      }
+    }
+    if (!ok) { fail = true; done = true; }
+    // ---- Newton steps with the density, bisection whenever a step leaves the open bracket
+    for (int it = 0; it < Q_MAXIT; ++it) {
+      if (!done) {
+        if (fx == 0.0) {
+          done = true;
+        } else {
+          if (fx < 0.0) lo = x; else hi = x;
+          double xn = x - fx / dn;
+          if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+          const double dx = fabs(xn - x);
+          x = xn;
+          if (dx <= 8.8817841970012523e-16 * fmax(1.0, fabs(x))) done = true;
+        }
+      }
+      if (__ballot(!done) == 0ull) break;
+      e = q_eval<true>(gs, wl, S, l16, x, sig);
+      if (!done) { fx = upper ? tgt - e.upper : e.lower - tgt; dn = e.dens; }
+    }
+    if (!done) fail = true;
+    if (valid && l16 == 0) {
+      t_out[(size_t)q * md.N + n] = fail ? NAN : x;
+      if (fail) atomicAdd(status, 1);
+    }
+  }
+}
+
+template <bool X>
+__global__ __launch_bounds__(64) void k_pred_cdf(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                 const double* __restrict__ v, const double* __restrict__ rowp,
+                                                 const double* __restrict__ Y, int stride, double* __restrict__ cdf,
+                                                 double* __restrict__ sf) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int lane = threadIdx.x, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S;
+  double* gs = wl + (S + 1) / 2 * 2 + (size_t)r * stride;
+  for (int s = lane; s < S; s += 64) wl[s] = md.wn[s];
+  flow_params_lds<X>(md.theta, fp, tp, tg);
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
+  const double sig = sqrt(exp(md.log_var_noise[0]));
+  q_sweep<X>(F, md, rp, mu[nc], vn, nullptr, 0, l16, gs);
+  __syncthreads();
+  const QSum e = q_eval<false>(gs, wl, S, l16, Y[nc], sig);
+  if (valid && l16 == 0) {
+    cdf[n] = e.lower;
+    if (sf) sf[n] = e.upper;
+  }
+}
+
+// TGP_LIK_GAUSS / the empty program: y ~ N(mu, max(v, 0) + sig^2).  Y == nullptr: quantiles t (Q,N); else cdf / sf (N).
+__global__ __launch_bounds__(256) void k_quantile_gauss(int N, const double* __restrict__ mu, const double* __restrict__ v,
+                                                        const double* __restrict__ lvn, const double* __restrict__ zq, int Q,
+                                                        double* __restrict__ t_out, const double* __restrict__ Y,
+                                                        double* __restrict__ cdf, double* __restrict__ sf) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const double sd = sqrt(fmax(v[n], 0.0) + exp(lvn[0])), m_ = mu[n];
+  if (Y == nullptr) {
+    for (int q = 0; q < Q; ++q) t_out[(size_t)q * N + n] = m_ + zq[q] * sd;
+    return;
+  }
+  const double z = (Y[n] - m_) / sd;
+  const double small = 0.5 * erfc(fabs(z) * Q_SQRT1_2), big = 1.0 - small;
+  cdf[n] = z < 0.0 ? small : big;
+  if (sf) sf[n] = z < 0.0 ? big : small;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// host launchers
+// ---------------------------------------------------------------------------------------------------
+static size_t q_lds_bytes(const tgp_model& md, int Q, int* stride) {
+  *stride = q_row_stride(md.S + Q);
+  return (2 * (size_t)((md.P + 2) / 2 * 2) + (size_t)((md.S + 1) / 2 * 2) + (size_t)QROWS * *stride) * sizeof(double);
+}
+
+int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                            const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st) {
+  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+    hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise, zq, Q, t,
+                       (const double*)nullptr, (double*)nullptr, (double*)nullptr);
+    LAUNCH_CHECK();
+    return 0;
+  }
+  int stride = 0;
+  const size_t lds = q_lds_bytes(md, Q, &stride);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_pred_quantile<true> : k_pred_quantile<false>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, probs, zq, Q, stride, t,
+                     status);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                       const double* Y, double* cdf, double* sf, hipStream_t st) {
+  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+    hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise,
+                       (const double*)nullptr, 0, (double*)nullptr, Y, cdf, sf);
+    LAUNCH_CHECK();
+    return 0;
+  }
+  int stride = 0;
+  const size_t lds = q_lds_bytes(md, 0, &stride);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_pred_cdf<true> : k_pred_cdf<false>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, stride, cdf, sf);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace tgp

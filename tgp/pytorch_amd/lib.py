@@ -19,6 +19,7 @@ LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
+QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
 E_UNSUPPORTED = -100
 E_WORKSPACE = -101
 
@@ -132,6 +133,8 @@ _SIGS = {
     "tgp_predict_softmax_f64": (C.c_int, [C.POINTER(TgpSoftmax), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "tgp_flow_inverse_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "tgp_predict_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp]),
+    "tgp_predict_quantile_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]),
+    "tgp_predict_cdf_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "tgp_kmeans_assign_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]),
     "tgp_kmeans_segsum_f64": (C.c_int, [_dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp]),
     "tgp_kmeans_pp_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp]),

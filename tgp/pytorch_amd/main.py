@@ -71,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs")
+    ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
+                    help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
+                         "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -164,7 +167,8 @@ def main(argv=None):
     Y_std = (torch.ones((Dy,)) * dc["Y_std"]).to(cg.device)
     trainer_cls = Trainer_SP_classification if (bern or multi) else Trainer_SP_regression
     trainer = trainer_cls(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
-                                    track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True)
+                                    track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True,
+                                    coverage=args.coverage)
     trainer.train(epochs=args.epochs, lr_ALL=lr, opt="adam", keep_parameter_groups=True,
                   optimisation_schedule=([1.0], specs), lr_groups=None)
     res = trainer.compute_metrics()

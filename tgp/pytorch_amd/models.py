@@ -468,6 +468,65 @@ class sparse_MF_SP(nn.Module):
         self.train()
         return log_p_y, predictive_params
 
+    # ---- exact quantiles and CDF of the predictive / posterior marginals -----------------------------------
+    def _quantile_inputs(self, X, what):
+        """Eval-mode q(f) moments (mu, v of shape (N,)), the noise and the flow inputs of the rows of X, under no_grad."""
+        if self._is_bernoulli or self._is_multiclass:
+            raise NotImplementedError("%s: a %s model has no quantiles" % (what, type(self.likelihood).__name__))
+        if self.fully_bayesian:
+            raise NotImplementedError("%s: the fully Bayesian model (an MC-dropout mixture over parameter draws) is out of "
+                                      "scope; use the sampled intervals" % what)
+        assert X.dim() == 2, "Invalid input X.shape"
+        self._eval_mode()
+        with torch.no_grad():
+            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X.repeat(self.out_dim, 1, 1), diagonal=True,
+                                                                        is_duvenaud=False)
+            spec, theta, rowp = self._flow_inputs(X, with_grad=False)
+        lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
+        theta = theta.detach() if theta is not None else None
+        return mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous(), lvn, spec, theta, rowp
+
+    def predictive_quantiles(self, X, probs):
+        """Exact quantiles of p(y* | x*) at the rows of X, shape (Dy, Q, N), in the model's standardised units: the roots of
+        the Gauss-Hermite predictive CDF (ops.predict_quantiles); the Gaussian likelihood's closed form; a warped model's
+        T^-1(mu + zq sqrt(v + noise)).  probs: any order, each strictly inside (0, 1)."""
+        mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "predictive_quantiles")
+        with torch.no_grad():
+            if self._is_warped:
+                _, zq = ops.quantile_probs(probs, mu.device)
+                t = mu.unsqueeze(0) + zq.unsqueeze(1) * torch.sqrt(v.clamp_min(0.0) + torch.exp(lvn)).unsqueeze(0)
+                q, _ = ops.flow_inverse(t, spec, theta)
+            else:
+                q = ops.predict_quantiles(mu, v, lvn, probs, spec, theta, self.quad_points, rowp)
+        self.train()
+        return q.unsqueeze(0)
+
+    def posterior_quantiles(self, X, probs):
+        """Quantiles of G(f0) under q(f0) at the rows of X, shape (Dy, Q, N): exact, G is increasing, so they are
+        G(mu + zq sqrt(v)).  (A warped model's latent function carries no flow: mu + zq sqrt(v).)"""
+        mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "posterior_quantiles")
+        with torch.no_grad():
+            _, zq = ops.quantile_probs(probs, mu.device)
+            f = mu.unsqueeze(0) + zq.unsqueeze(1) * torch.sqrt(v.clamp_min(0.0)).unsqueeze(0)
+            if spec is not None and spec.nblk > 0 and not self._is_warped:
+                f = ops.flow_eval(f.contiguous(), spec, theta, rowp, want=("G",))["G"]
+        self.train()
+        return f.unsqueeze(0)
+
+    def predictive_cdf(self, X, Y):
+        """The predictive CDF at the targets Y (N,1), standardised units: the PIT values of a calibration plot, shape (Dy, N).
+        A warped model's is Phi((T(y) - mu) / sqrt(v + noise))."""
+        mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "predictive_cdf")
+        with torch.no_grad():
+            y = Y.reshape(-1).to(mu.dtype)
+            if self._is_warped:
+                t = ops.flow_eval(y.contiguous(), spec, theta, want=("G",))["G"] if spec.nblk > 0 else y
+                cdf, _ = ops.predict_cdf(mu, v, lvn, t)
+            else:
+                cdf, _ = ops.predict_cdf(mu, v, lvn, y, spec, theta, self.quad_points, rowp)
+        self.train()
+        return cdf.unsqueeze(0)
+
     # ---- sampling (sparse_MF_SP.py:837-992) --------------------------------------------------------
     def sample_from_variational_marginal_base(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None, S: int = 1):
         """diagonal=True: one independent draw per row of X (the caller has repeated the rows S times).  diagonal=False:

@@ -1051,6 +1051,65 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     return m1, m2, logp
 
 
+def quantile_probs(probs, device=None):
+    """probs (a float, a sequence or a tensor, any order) -> (probs, zq = Phi^-1(probs)) as float64 (Q,) tensors on `device`.
+    Checked on the host, before any launch: every entry strictly inside (0, 1).  (Their number, 1 <= Q <= lib.QUANTILE_MAX_Q,
+    is the library's to refuse.)"""
+    p = torch.as_tensor(probs, dtype=torch.float64).detach().to("cpu").reshape(-1)
+    if not bool(((p > 0.0) & (p < 1.0)).all()):      # (a NaN fails both comparisons)
+        raise ValueError("probabilities must lie strictly inside (0, 1), got %s" % p.tolist())
+    zq = torch.special.ndtri(p)
+    return (p, zq) if device is None else (p.to(device), zq.to(device))
+
+
+def _quantile_model(mu, lvn, flow, theta, S):
+    if flow is None:
+        md = L.TgpModel()
+        md.N, md.D, md.M, md.S, md.lik = mu.numel(), 1, 1, 1, L.LIK_GAUSS
+        md.log_var_noise = L.ptr(lvn)
+        return md, None
+    if S is None:
+        raise ValueError("a flow needs S, the number of Gauss-Hermite nodes")
+    return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device, lik=L.LIK_FLOW)
+
+
+def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=None, check=True):
+    """Exact quantiles of the predictive distribution ops.predict integrates (tgp_predict_quantile_f64): t of shape (Q,N), in
+    the model's standardised units, t[q,n] the root of sum_s wn_s Phi((t - G(mu_n + sqrt(2 v_n) xs_s)) / sigma) = probs[q].
+    flow=None: the Gaussian likelihood's closed form.  With `check` the status word is read (one sync) and a root that did
+    not converge raises; check=False returns (t, status) and leaves NaN in its place."""
+    lib = L.load()
+    mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    p, zq = quantile_probs(probs, mu.device)
+    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    t = torch.empty(p.numel(), mu.numel(), dtype=torch.float64, device=mu.device)
+    status = torch.zeros(1, dtype=torch.int32, device=mu.device)
+    L.check(lib.tgp_predict_quantile_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(p), L.ptr(zq), p.numel(), L.ptr(t),
+                                         L.ptr(status), L.stream_ptr()), "tgp_predict_quantile_f64")
+    if not check:
+        return t, status
+    if int(status[0]) != 0:
+        raise L.TgpError("predict_quantiles: %d root(s) did not converge" % int(status[0]))
+    return t
+
+
+def predict_cdf(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None):
+    """(cdf, sf): the predictive CDF at Y per row -- the PIT values of a calibration plot -- and the upper tail 1 - cdf from
+    its own sum (tgp_predict_cdf_f64); Y in the model's standardised units."""
+    lib = L.load()
+    mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    Yc = _c(Y.reshape(-1), "Y")
+    if Yc.numel() != mu.numel():
+        raise ValueError("Y must hold one value per row (%d), got %d" % (mu.numel(), Yc.numel()))
+    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    cdf, sf = torch.empty_like(mu), torch.empty_like(mu)
+    L.check(lib.tgp_predict_cdf_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), L.ptr(cdf), L.ptr(sf), L.stream_ptr()),
+            "tgp_predict_cdf_f64")
+    return cdf, sf
+
+
 # ---------------------------------------------------------------------------------------------------
 # per-row parameter networks of the input-dependent flows (models/flow.py:836-897)
 # ---------------------------------------------------------------------------------------------------

@@ -30,8 +30,14 @@ def return_optimizer(opt, parameters, lr):
 
 class Trainer_SP_regression:
     def __init__(self, model, data_loaders, validate_each, plot, track, Y_std, plot_each, S_test,
-                 inference_in_cpu=False):
+                 inference_in_cpu=False, coverage="sampled"):
         self.model = model
+        # coverage of the 95 % interval: "sampled" = order statistics of S_test predictive draws per row, on the host (the
+        # reference, trainers_regression.py:171); "exact" = the 2.5 % / 97.5 % roots of the predictive CDF, on the device
+        if coverage not in ("sampled", "exact"):
+            raise ValueError("coverage must be 'sampled' or 'exact', got %r" % (coverage,))
+        self.coverage = coverage
+        self._coverage_fallback_said = False
         # [train], [train, test] or [train, valid, test] (trainer_base.py:50-59)
         dl = list(data_loaders)
         self.train_loader, self.valid_loader, self.test_loader = dl[0], None, None
@@ -313,10 +319,22 @@ class Trainer_SP_regression:
         self.model.set_is_training(False)
         logp, (m1, _m2) = self.model.test_log_likelihood(X, Y, return_moments=True, Y_std=self.Y_std.to(X.device),
                                                          S_MC_NNet=self.S_test if self.model.fully_bayesian else None)
-        samples, _, _ = self.model.sample_from_predictive_distribution(X, S=self.S_test)      # (Dy,S,N,1)
-        q = numpy.quantile(samples.to("cpu").numpy(), [0.025, 0.975], axis=1)                  # (2,Dy,N,1)
-        y = Y[:, 0].to("cpu")
-        cover = ((y >= torch.tensor(q[0, 0, :, 0])) & (y <= torch.tensor(q[1, 0, :, 0]))).float().sum().item()
+        exact = self.coverage == "exact"
+        if exact and self.model.fully_bayesian:
+            # an MC-dropout mixture over parameter draws has no closed CDF here: the sampled recipe, said once
+            if not self._coverage_fallback_said:
+                print("[tgp.pytorch_amd] coverage='exact' is not built for the fully Bayesian model: sampled coverage instead")
+                self._coverage_fallback_said = True
+            exact = False
+        if exact:
+            q = self.model.predictive_quantiles(X, [0.025, 0.975])[0]                              # (2,N), stays on the device
+            cover = ((Y[:, 0] >= q[0]) & (Y[:, 0] <= q[1])).sum().item()
+            cover = float(cover)
+        else:
+            samples, _, _ = self.model.sample_from_predictive_distribution(X, S=self.S_test)      # (Dy,S,N,1)
+            q = numpy.quantile(samples.to("cpu").numpy(), [0.025, 0.975], axis=1)                  # (2,Dy,N,1)
+            y = Y[:, 0].to("cpu")
+            cover = ((y >= torch.tensor(q[0, 0, :, 0])) & (y <= torch.tensor(q[1, 0, :, 0]))).float().sum().item()
         se = ((m1.reshape(-1) - Y[:, 0]) ** 2).sum().item()
         return float(logp.reshape(-1)[0]), se, cover
 

@@ -160,3 +160,42 @@ def psd_safe_cholesky(A, upper=False, out=None, jitter=None):
     if upper:
         L = L.transpose(-1, -2)
     return (L.unsqueeze(0), Ap.unsqueeze(0)) if squeeze else (L, Ap)
+
+
+# ---------------------------------------------------------------------------------------------------
+# confidence intervals (dsp/models/utils_models.py:33-140)
+# ---------------------------------------------------------------------------------------------------
+def confidence_intervals(model, X, intervals, S, distribution, is_deep, exact=False):
+    """Point-wise intervals at the rows of X: a list over the outputs of a list over `intervals` of (N,1) numpy arrays, in the
+    model's standardised units.  exact=False is the reference's recipe: S samples of the predictive distribution
+    ('predictive') or of the flowed posterior marginal ('posterior') per row, numpy.quantile over them.  exact=True takes the
+    quantiles themselves (model.predictive_quantiles / model.posterior_quantiles) and ignores S; a warped model's predictive
+    intervals are then the reference's 'special case' T^-1(mu + z sqrt(v + noise)), for any `intervals`."""
+    import numpy
+    if is_deep:
+        raise NotImplementedError("is_deep=True: this package has no deep (DGP) models")
+    if distribution not in ("predictive", "posterior"):
+        raise ValueError("Invalid arguments")
+    N = X.shape[0]
+    with torch.no_grad():
+        if exact:
+            fn = model.predictive_quantiles if distribution == "predictive" else model.posterior_quantiles
+            q = fn(X, list(intervals)).detach().to("cpu").numpy()                     # (Dy, Q, N)
+            return [[q[l, i].reshape(N, 1) for i in range(len(intervals))] for l in range(model.out_dim)]
+        if distribution == "predictive":
+            samples = model.sample_from_predictive_distribution(X, S)[0]              # (Dy, S, N, 1)
+        else:
+            samples, _, _, _ = model.sample_from_variational_marginal(X, S, diagonal=True, is_duvenaud=False, init_Z=None)
+            samples = samples.view(model.out_dim, S, N, 1)
+        found = []
+        for l in range(model.out_dim):
+            s_l = samples[l].detach().to("cpu").numpy()
+            found.append([numpy.quantile(s_l, interval, axis=0) for interval in intervals])
+    return found
+
+
+def compute_95_and_median_confidence_intervals(model, X, S, distribution, is_deep, exact=False):
+    """The [0.025, 0.5, 0.975] intervals at X: median and the 95 % band (dsp/models/utils_models.py:123-140)."""
+    assert distribution in ["posterior", "predictive"], \
+        "Invalid arguments for distribution. Got {}, expected one of [posterior, predictive]".format(distribution)
+    return confidence_intervals(model, X, [0.025, 0.5, 0.975], S, distribution, is_deep, exact=exact)
