@@ -25,6 +25,15 @@ void set_error_text(const char* fmt, ...) {
   va_end(ap);
 }
 
+// the flow fields of a model: a program for its blocks and the shared scalars they index; with `counts`, no negative count
+// (`program` false: the entry leaves a missing program to make_prog, after its own argument checks)
+static int check_flow_args(const tgp_model* m, bool counts = false, bool program = true) {
+  if (counts && (m->nblk < 0 || m->P < 0 || m->RP < 0)) return -1;
+  if (program && m->nblk > 0 && !m->program) return -1;
+  if (m->P > 0 && !m->theta) return -1;
+  return 0;
+}
+
 static int check_model(const tgp_model* m, bool need_lik) {
   if (m == nullptr) return -1;
   if (m->N < 1 || m->D < 1 || m->D > 16) return -1;
@@ -32,11 +41,29 @@ static int check_model(const tgp_model* m, bool need_lik) {
   if (m->M > TGP_BIG_MAX_M) return TGP_E_UNSUPPORTED;
   if (m->kernel != TGP_KERNEL_SCALE_RBF && m->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
   if (!m->Z || !m->raw_ls || !m->raw_os || !m->m || !m->Lam || !m->log_var_noise) return -1;
-  if (need_lik && (m->lik == TGP_LIK_FLOW || m->lik == TGP_LIK_BERNOULLI)) {
-    if (m->S < 1 || m->nblk < 0 || !m->xs || !m->wn) return -1;
-    if (m->nblk > 0 && !m->program) return -1;
-    if (m->P > 0 && !m->theta) return -1;
-  }
+  if (need_lik && (m->lik == TGP_LIK_FLOW || m->lik == TGP_LIK_BERNOULLI))
+    if (m->S < 1 || m->nblk < 0 || !m->xs || !m->wn || check_flow_args(m)) return -1;
+  return 0;
+}
+
+// the arguments tgp_flow_eval_f64, tgp_flow_logdet_f64 and tgp_flow_inverse_f64 open with, under the same codes
+static int check_flow_points(const tgp_model* m, bool counts, const double* f, int S, int N, const double* rowp) {
+  if (!m || check_flow_args(m, counts)) return -1;
+  if (!f) return -2;
+  if (S < 1) return -3;
+  if (N < 1) return -4;
+  if (m->RP > 0 && !rowp) return -5;
+  return 0;
+}
+
+// one block of a program against the `limit` parameters of the vector it indexes (`per_row_ok` false: shared parameters only)
+static int check_block(int kind, int K, int poff, int flags, int limit, bool per_row_ok = true) {
+  if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
+  if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
+  if ((flags & TGP_FLAG_PER_ROW) && !per_row_ok) return TGP_E_UNSUPPORTED;
+  // per-row parameters: AFFINE and SAL only (the reference has no input-dependent tanh-step, arcsinh or Box-Cox flow)
+  if (kind >= TGP_FLOW_STEPTANH && (flags & TGP_FLAG_PER_ROW)) return -1;
+  if (poff < 0 || poff + flow_block_params(kind, K) > limit) return -1;
   return 0;
 }
 
@@ -49,18 +76,59 @@ static int make_prog(const tgp_model* m, bool flow, FlowProg& fp) {
   if (!m->program) return -1;
   fp.nblk = m->nblk;
   for (int b = 0; b < m->nblk; ++b) {
-    const int kind = m->program[4 * b], K = m->program[4 * b + 1], poff = m->program[4 * b + 2],
-              flags = m->program[4 * b + 3];
-    if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
-    const int np = flow_block_params(kind, K);
-    if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
-    // per-row parameters: AFFINE and SAL only (the reference has no input-dependent tanh-step, arcsinh or Box-Cox flow)
-    if (kind >= TGP_FLOW_STEPTANH && (flags & TGP_FLAG_PER_ROW)) return -1;
-    if (poff < 0 || poff + np > ((flags & TGP_FLAG_PER_ROW) ? m->RP : m->P)) return -1;
-    for (int j = 0; j < 4; ++j) fp.blk[4 * b + j] = m->program[4 * b + j];
+    const int32_t* blk = m->program + 4 * b;
+    if (int rc = check_block(blk[0], blk[1], blk[2], blk[3], (blk[3] & TGP_FLAG_PER_ROW) ? m->RP : m->P)) return rc;
+    for (int j = 0; j < 4; ++j) fp.blk[4 * b + j] = blk[j];
   }
   fp.nslots = flow_slots(fp.blk, fp.nblk);
   return 0;
+}
+
+static const FlowProg no_flow{};   // the empty program of the q(f) entries
+
+// what a flow kernel takes by value: the program in `fp`, the model without its host program pointer in `md` (may be *m itself)
+static int flow_args(const tgp_model* m, bool flow, FlowProg& fp, tgp_model& md) {
+  const int rc = make_prog(m, flow, fp);
+  md = *m;
+  md.program = nullptr;
+  return rc;
+}
+
+// `m` as the plain Gaussian model with the same q(f): no flow, no parameters of one
+static tgp_model gauss_copy(const tgp_model& m, int lik = TGP_LIK_GAUSS) {
+  tgp_model g = m;
+  g.lik = lik; g.nblk = 0; g.P = 0; g.RP = 0; g.program = nullptr; g.theta = nullptr;
+  return g;
+}
+
+static int check_adam(const tgp_adam_args* a) {
+  return a && a->params && a->grads && a->exp_avg && a->exp_avg_sq && a->step_dev && a->n >= 1 ? 0 : -1;
+}
+static AdamDev adam_dev_of(const tgp_adam_args* a) {
+  AdamDev ad;
+  ad.p = a->params; ad.g = a->grads; ad.m = a->exp_avg; ad.v = a->exp_avg_sq; ad.n = (long)a->n;
+  ad.lr = a->lr; ad.b1 = a->beta1; ad.b2 = a->beta2; ad.eps = a->eps;
+  ad.ln_b1 = log(a->beta1); ad.ln_b2 = log(a->beta2); ad.sign = a->maximize ? -1.0 : 1.0;
+  ad.step_dev = a->step_dev;   // (lam_off, lam_n: the step's own)
+  return ad;
+}
+
+// the chunked GEMM pipeline of tgp_big.hip: every M the fused kernels do not hold, and every kernel but the RBF
+static bool takes_general_path(int M, int kernel) { return M > TGP_FUSED_MAX_M || kernel != TGP_KERNEL_SCALE_RBF; }
+static bool takes_general_path(const tgp_model& m) { return takes_general_path(m.M, m.kernel); }
+
+// the Plan the fused path runs, planned again for the row kernel that choose_rows4 / rows_per_wave pick; TGP_E_WORKSPACE when
+// the caller's buffer does not hold it
+static int fused_plan(Plan& p, const tgp_model& m, int S, int nblk, int P, int RP, int lik, bool train, const FlowProg& fp,
+                      size_t workspace_bytes) {
+  if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik)) return rc;
+  p.nslots = fp.nslots;
+  const int nw4 = choose_rows4(p, train, m.plan), rw = nw4 ? 16 : rows_per_wave(p, fp, train, m.plan);
+  if (nw4 != 0 || rw != 16) {
+    if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik, nw4, rw)) return rc;
+    p.nslots = fp.nslots;
+  }
+  return workspace_bytes < p.total * sizeof(double) ? TGP_E_WORKSPACE : 0;
 }
 
 }  // namespace tgp
@@ -89,8 +157,7 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan) {
-  if (M > TGP_FUSED_MAX_M || kernel != TGP_KERNEL_SCALE_RBF)
-    return big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan) * sizeof(double);
+  if (takes_general_path(M, kernel)) return big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan) * sizeof(double);
   Plan p;
   if (make_plan(p, N, D, M, S, nblk, P, RP, TGP_LIK_FLOW) != 0) return 0;
   size_t d = p.total + (size_t)(plan_alloc_blocks(N) - p.nblocks) * p.slab_len;   // slabs for whichever row kernel runs
@@ -142,10 +209,8 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
                             const tgp_adam_args* adam, void* stream) {
   if (int rc = check_model(model, false)) return rc;
   if (model->RP != 0) return TGP_E_UNSUPPORTED;
-  if (model->nblk < 0 || model->P < 0) return -1;
+  if (int rc = check_flow_args(model, true)) return rc;
   if (model->nblk == 0 && model->P > 0) return -1;   // parameters of no block: their gradient would never be written
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
   if (!X) return -2;
   if (!Y) return -3;
   if (!out) return -5;
@@ -155,7 +220,7 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
   if (!status) return -9;
   if (!workspace) return -10;
   if (adam != nullptr) {
-    if (!adam->params || !adam->grads || !adam->exp_avg || !adam->exp_avg_sq || !adam->step_dev || adam->n < 1) return -12;
+    if (check_adam(adam)) return -12;
     if (model->P > 0 && (grads->theta < adam->grads || grads->theta + model->P > adam->grads + adam->n)) return -12;
   }
   const size_t gbytes = tgp_workspace_bytes_plan(model->N, model->D, model->M, model->S, 0, 0, 0, model->kernel, model->plan);
@@ -169,9 +234,8 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
   double* part = t + 3 * N;
   hipStream_t st = static_cast<hipStream_t>(stream);
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model mw = *model;
-  mw.program = nullptr;
+  tgp_model mw;
+  if (int rc = flow_args(model, true, fp, mw)) return rc;
   // every argument of the Gaussian step has been checked above: nothing is enqueued for a call that will be refused.
   // An empty program is the Gaussian step itself on Y: t = Y, log T' = 0, no theta -- neither pass is launched.
   const bool warp = fp.nblk > 0;
@@ -179,8 +243,7 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
   if (warp && (phases & TGP_PHASE_PREPARE))
     if (int rc = launch_ell_warp(mw, fp, TGP_WARP_TARGETS, Y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, t, part, st))
       return rc;
-  tgp_model mg = *model;
-  mg.lik = TGP_LIK_GAUSS; mg.nblk = 0; mg.P = 0; mg.RP = 0; mg.program = nullptr; mg.theta = nullptr;
+  const tgp_model mg = gauss_copy(*model);
   tgp_grads gg = *grads;
   gg.theta = nullptr; gg.rowp = nullptr;
   if (int rc = elbo_step_impl(&mg, X, t, nullptr, out, &gg, mu_w, v_w, status, workspace, gbytes, phases, nullptr, stream))
@@ -226,14 +289,12 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
   tgp_model md = *model;
   md.nblk = nblk; md.P = P; md.RP = RP;
   FlowProg fp;
-  if (int rc = make_prog(&md, flowed, fp)) return rc;
-  md.program = nullptr;  // kernels use the by-value copy
+  if (int rc = flow_args(&md, flowed, fp, md)) return rc;   // kernels use the by-value copy
   AdamDev ad;
   if (adam != nullptr) {
-    if (!adam->params || !adam->grads || !adam->exp_avg || !adam->exp_avg_sq || !adam->step_dev || adam->n < 1) return -12;
+    if (check_adam(adam)) return -12;
     // every gradient of the call must be a view of adam->grads
-    const double* lo = adam->grads;
-    const double* hi = adam->grads + adam->n;
+    const double *lo = adam->grads, *hi = lo + adam->n;
     // ... START AND EXTENT: the update kernels index params / exp_avg / exp_avg_sq with the gradients' offsets, so a block
     // that ran past adam->n would be written past the caller's buffers
     const double* gp[7] = {grads->Z, grads->raw_ls, grads->raw_os, grads->m, grads->Lam, grads->log_var_noise, grads->theta};
@@ -241,14 +302,11 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
                           (size_t)P};
     for (int k = 0; k < 7; ++k)
       if (gp[k] != nullptr && gn[k] > 0 && (gp[k] < lo || gp[k] + gn[k] > hi)) return -12;
-    ad.p = adam->params; ad.g = adam->grads; ad.m = adam->exp_avg; ad.v = adam->exp_avg_sq; ad.n = (long)adam->n;
+    ad = adam_dev_of(adam);
     ad.lam_off = (long)(grads->Lam - adam->grads); ad.lam_n = (long)model->M * model->M;
-    ad.lr = adam->lr; ad.b1 = adam->beta1; ad.b2 = adam->beta2; ad.eps = adam->eps;
-    ad.ln_b1 = log(adam->beta1); ad.ln_b2 = log(adam->beta2); ad.sign = adam->maximize ? -1.0 : 1.0;
-    ad.step_dev = adam->step_dev;
   }
   // (the fused row kernels have no Bernoulli likelihood: those steps take the general-M path at every M, as MATERN32 does)
-  bool general = model->M > TGP_FUSED_MAX_M || model->kernel != TGP_KERNEL_SCALE_RBF || model->lik == TGP_LIK_BERNOULLI;
+  bool general = takes_general_path(*model) || model->lik == TGP_LIK_BERNOULLI;
   if (!general && fp.nslots > 0) {
     // the fused path keeps the flow stack of a row block in LDS beside its operand tiles; a program that does not fit even
     // with one node in flight (TGP_E_LDS until round 5: M > 112 with the 5 x 6 tanh flow) takes the general-M path
@@ -269,16 +327,7 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
     return 0;
   }
   Plan p;
-  if (int rc = make_plan(p, model->N, model->D, model->M, model->S, nblk, P, RP, model->lik)) return rc;
-  p.nslots = fp.nslots;
-  if (const int nw4 = choose_rows4(p, true, model->plan)) {
-    if (int rc = make_plan(p, model->N, model->D, model->M, model->S, nblk, P, RP, model->lik, nw4)) return rc;
-    p.nslots = fp.nslots;
-  } else if (const int rw = rows_per_wave(p, fp, true, model->plan); rw != 16) {
-    if (int rc = make_plan(p, model->N, model->D, model->M, model->S, nblk, P, RP, model->lik, 0, rw)) return rc;
-    p.nslots = fp.nslots;
-  }
-  if (workspace_bytes < p.total * sizeof(double)) return TGP_E_WORKSPACE;
+  if (int rc = fused_plan(p, *model, model->S, nblk, P, RP, model->lik, true, fp, workspace_bytes)) return rc;
   if (phases & TGP_PHASE_PREPARE)
     if (int rc = launch_prepare(p, md, fp, ws, status, st)) return rc;
   if (phases & TGP_PHASE_ROWS)
@@ -314,18 +363,12 @@ int tgp_qf_moments_f64(const tgp_model* model, const double* X, double* mu, doub
   if (!workspace) return -6;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* ws = static_cast<double*>(workspace);
-  tgp_model md = *model;
-  md.nblk = 0; md.P = 0; md.RP = 0; md.lik = TGP_LIK_GAUSS; md.program = nullptr;
-  if (model->M > TGP_FUSED_MAX_M || model->kernel != TGP_KERNEL_SCALE_RBF) return launch_big_moments(md, X, mu, v, status, ws, workspace_bytes / sizeof(double), st);
+  const tgp_model md = gauss_copy(*model);
+  if (takes_general_path(md)) return launch_big_moments(md, X, mu, v, status, ws, workspace_bytes / sizeof(double), st);
   Plan p;
-  if (int rc = make_plan(p, model->N, model->D, model->M, 1, 0, 0, 0, TGP_LIK_GAUSS)) return rc;
-  if (const int nw4 = choose_rows4(p, false, model->plan))
-    if (int rc = make_plan(p, model->N, model->D, model->M, 1, 0, 0, 0, TGP_LIK_GAUSS, nw4)) return rc;
-  if (workspace_bytes < p.total * sizeof(double)) return TGP_E_WORKSPACE;
-  FlowProg fp;
-  fp.nblk = 0; fp.nslots = 0;
-  if (int rc = launch_prepare(p, md, fp, ws, status, st)) return rc;
-  return launch_rows(p, md, fp, X, nullptr, nullptr, nullptr, mu, v, ws, false, st);
+  if (int rc = fused_plan(p, md, 1, 0, 0, 0, TGP_LIK_GAUSS, false, no_flow, workspace_bytes)) return rc;
+  if (int rc = launch_prepare(p, md, no_flow, ws, status, st)) return rc;
+  return launch_rows(p, md, no_flow, X, nullptr, nullptr, nullptr, mu, v, ws, false, st);
 }
 
 size_t tgp_qf_cov_workspace_bytes(int32_t N, int32_t D, int32_t M) { return qf_cov_workspace_bytes(N, D, M); }
@@ -378,24 +421,19 @@ int tgp_qf_moments_bwd_f64(const tgp_model* model, const double* X, const double
   if (!workspace) return -7;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* ws = static_cast<double*>(workspace);
-  tgp_model md = *model;
-  md.nblk = 0; md.P = 0; md.RP = 0; md.S = 1; md.lik = TGP_LIK_ADJOINT; md.program = nullptr;
-  md.scale = 1.0; md.kl_scale = 0.0;
+  tgp_model md = gauss_copy(*model, TGP_LIK_ADJOINT);
+  md.S = 1; md.scale = 1.0; md.kl_scale = 0.0;
   tgp_grads g = *grads;
   g.theta = nullptr; g.rowp = nullptr;
-  FlowProg fp;
-  fp.nblk = 0; fp.nslots = 0;
+  const FlowProg& fp = no_flow;
   const uint32_t all = TGP_PHASE_PREPARE | TGP_PHASE_ROWS | TGP_PHASE_BACKWARD;
-  if (model->M > TGP_FUSED_MAX_M || model->kernel != TGP_KERNEL_SCALE_RBF) {
+  if (takes_general_path(md)) {
     // (the scalars of the step go to the header words the general-M plan reserves as well: its hdr is the first block)
     return launch_big_step(md, fp, X, mu_bar, v_bar, ws + H_OUT, g, nullptr, nullptr, status, ws, workspace_bytes / sizeof(double),
                            all, st);
   }
   Plan p;
-  if (int rc = make_plan(p, model->N, model->D, model->M, 1, 0, 0, 0, TGP_LIK_ADJOINT)) return rc;
-  if (const int nw4 = choose_rows4(p, true, model->plan))
-    if (int rc = make_plan(p, model->N, model->D, model->M, 1, 0, 0, 0, TGP_LIK_ADJOINT, nw4)) return rc;
-  if (workspace_bytes < p.total * sizeof(double)) return TGP_E_WORKSPACE;
+  if (int rc = fused_plan(p, md, 1, 0, 0, 0, TGP_LIK_ADJOINT, true, fp, workspace_bytes)) return rc;
   if (int rc = launch_prepare(p, md, fp, ws, status, st)) return rc;
   if (int rc = launch_rows(p, md, fp, X, mu_bar, v_bar, nullptr, nullptr, nullptr, ws, true, st)) return rc;
   return launch_backward_mm(p, md, g, ws + p.hdr + H_OUT, ws, status, st);
@@ -573,8 +611,7 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream) {
   if (!model || model->N < 1 || model->S < 1 || !model->xs || !model->wn || !model->log_var_noise) return -1;
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
+  if (check_flow_args(model)) return -1;
   if (!Y) return -2;
   if (!mu) return -3;
   if (!v) return -4;
@@ -583,26 +620,18 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
   if (!workspace) return -11;
   if (workspace_bytes < lik_workspace_doubles(model->N, model->P, model->RP) * sizeof(double)) return TGP_E_WORKSPACE;
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_ell_quad(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
 }
 
 int tgp_flow_eval_f64(const tgp_model* model, const double* f, int32_t S, int32_t N, const double* rowp, double* G,
                       double* dG, double* logdG, void* stream) {
-  if (!model) return -1;
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
-  if (!f) return -2;
-  if (S < 1) return -3;
-  if (N < 1) return -4;
-  if (model->RP > 0 && !rowp) return -5;
+  if (int rc = check_flow_points(model, false, f, S, N, rowp)) return rc;
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_flow_eval(md, fp, f, S, N, rowp, G, dG, logdG, static_cast<hipStream_t>(stream));
 }
 
@@ -612,20 +641,13 @@ size_t tgp_flow_logdet_workspace_bytes(int32_t S, int32_t N) {
 
 int tgp_flow_logdet_f64(const tgp_model* model, const double* f, int32_t S, int32_t N, const double* rowp, double* G,
                         double* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!model) return -1;
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
-  if (!f) return -2;
-  if (S < 1) return -3;
-  if (N < 1) return -4;
-  if (model->RP > 0 && !rowp) return -5;
+  if (int rc = check_flow_points(model, false, f, S, N, rowp)) return rc;
   if (!out) return -7;
   if (!workspace) return -8;
   if (workspace_bytes < tgp_flow_logdet_workspace_bytes(S, N)) return TGP_E_WORKSPACE;
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_flow_eval(md, fp, f, S, N, rowp, G, nullptr, nullptr, static_cast<hipStream_t>(stream), out,
                           static_cast<double*>(workspace));
 }
@@ -639,8 +661,7 @@ int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, 
                      double* g_v, double* g_theta, double* t_out, void* workspace, size_t workspace_bytes, void* stream) {
   if (!model || model->N < 1 || !model->log_var_noise || model->nblk < 0 || model->P < 0) return -1;
   if (model->RP != 0) return TGP_E_UNSUPPORTED;
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
+  if (check_flow_args(model)) return -1;
   if (!Y) return -2;
   if (!mu) return -3;
   if (!v) return -4;
@@ -648,9 +669,8 @@ int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, 
   if (!workspace) return -10;
   if (workspace_bytes < tgp_ell_warp_workspace_bytes(model->N, model->P)) return TGP_E_WORKSPACE;
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_ell_warp(md, fp, TGP_WARP_FULL, Y, mu, v, out, g_mu, g_v, g_theta, t_out, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
 }
@@ -674,10 +694,7 @@ static int make_softmax(const tgp_softmax* d, SmxArgs& a, FlowProg& fp) {
     const int Pc = d->theta_off[c + 1] - d->theta_off[c];
     for (int b = d->blk_off[c]; b < d->blk_off[c + 1]; ++b) {
       const int kind = d->program[4 * b], K = d->program[4 * b + 1], poff = d->program[4 * b + 2], flags = d->program[4 * b + 3];
-      if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
-      if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
-      if (flags & TGP_FLAG_PER_ROW) return TGP_E_UNSUPPORTED;   // (RP != 0: no input-dependent flows here)
-      if (poff < 0 || poff + flow_block_params(kind, K) > Pc) return -1;
+      if (int rc = check_block(kind, K, poff, flags, Pc, false)) return rc;   // (RP != 0: no input-dependent flows here)
       fp.blk[4 * b] = kind; fp.blk[4 * b + 1] = K; fp.blk[4 * b + 2] = d->theta_off[c] + poff; fp.blk[4 * b + 3] = flags;
     }
   }
@@ -733,19 +750,12 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 
 int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int32_t N, const double* rowp, double* x,
                          int32_t* status, void* stream) {
-  if (!model || model->nblk < 0 || model->P < 0 || model->RP < 0) return -1;
-  if (model->nblk > 0 && !model->program) return -1;
-  if (model->P > 0 && !model->theta) return -1;
-  if (!t) return -2;
-  if (S < 1) return -3;
-  if (N < 1) return -4;
-  if (model->RP > 0 && !rowp) return -5;
+  if (int rc = check_flow_points(model, true, t, S, N, rowp)) return rc;
   if (!x) return -6;
   if (!status) return -7;
   FlowProg fp;
-  if (int rc = make_prog(model, true, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_flow_inverse(md, fp, t, S, N, rowp, x, status, static_cast<hipStream_t>(stream));
 }
 
@@ -753,16 +763,13 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
                     double Y_std, double* m1, double* m2, double* logp, void* stream) {
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
   if (model->lik == TGP_LIK_WARPED) {
-    if (model->S < 1 || !model->xs || !model->wn || model->nblk < 0 || model->P < 0) return -1;
-    if (model->nblk > 0 && !model->program) return -1;
-    if (model->P > 0 && !model->theta) return -1;
-    if (!mu) return -2;
-    if (!v) return -3;
     tgp_model mw = *model;
     mw.RP = 0;   // (rowp is ignored: the warp of the targets has shared parameters only)
+    if (model->S < 1 || !model->xs || !model->wn || check_flow_args(&mw, true)) return -1;
+    if (!mu) return -2;
+    if (!v) return -3;
     FlowProg fpw;
-    if (int rc = make_prog(&mw, true, fpw)) return rc;
-    mw.program = nullptr;
+    if (int rc = flow_args(&mw, true, fpw, mw)) return rc;
     return launch_predict_warp(mw, fpw, mu, v, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
   }
   const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;
@@ -771,9 +778,8 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
   if (!v) return -3;
   if (flowed && model->RP > 0 && !rowp) return -4;
   FlowProg fp;
-  if (int rc = make_prog(model, flowed, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
   return launch_predict(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
 }
 
@@ -793,8 +799,7 @@ static int check_quantile_model(const tgp_model* model, const double* mu, const 
       set_error_text("%s: S = %d outside 1..%d", entry, model->S, TGP_QUANTILE_MAX_S);
       return TGP_E_UNSUPPORTED;
     }
-    if (!model->xs || !model->wn || model->nblk < 0 || model->P < 0 || model->RP < 0) return -1;
-    if (model->P > 0 && !model->theta) return -1;
+    if (!model->xs || !model->wn || check_flow_args(model, true, false)) return -1;
   }
   if (!mu) return -2;
   if (!v) return -3;
@@ -815,9 +820,8 @@ int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const dou
   if (!t) return -8;
   if (!status) return -9;
   FlowProg fp;
-  if (int rc = make_prog(model, flowed, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
   return launch_predict_quantile(md, fp, mu, v, rowp, probs, zq, Q, t, status, static_cast<hipStream_t>(stream));
 }
 
@@ -828,9 +832,8 @@ int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* 
   if (!Y) return -5;
   if (!cdf) return -6;
   FlowProg fp;
-  if (int rc = make_prog(model, flowed, fp)) return rc;
-  tgp_model md = *model;
-  md.program = nullptr;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
   return launch_predict_cdf(md, fp, mu, v, rowp, Y, cdf, sf, static_cast<hipStream_t>(stream));
 }
 
@@ -956,19 +959,15 @@ int tgp_mlp_backward_adam_f64(const tgp_mlp* mlp, const double* X, double* W, co
   if (!g_out) return -5;
   if (!g_W) return -6;
   if (!workspace) return -7;
-  if (!adam || adam->params != W || adam->grads != g_W || !adam->exp_avg || !adam->exp_avg_sq || !adam->step_dev) return -9;
+  if (check_adam(adam) || adam->params != W || adam->grads != g_W) return -9;
   // the optimiser state must cover every weight the kernel updates (nnets x weights per net)
   {
     size_t per = (size_t)mlp->H * mlp->D + mlp->H;
     for (int l = 1; l < mlp->L; ++l) per += (size_t)mlp->H * mlp->H + mlp->H;
     per += (size_t)mlp->H + 1;
-    if (adam->n < 1 || (size_t)adam->n != per * (size_t)mlp->nnets) return -9;
+    if ((size_t)adam->n != per * (size_t)mlp->nnets) return -9;
   }
-  AdamDev ad;
-  ad.p = adam->params; ad.g = adam->grads; ad.m = adam->exp_avg; ad.v = adam->exp_avg_sq; ad.n = (long)adam->n;
-  ad.lr = adam->lr; ad.b1 = adam->beta1; ad.b2 = adam->beta2; ad.eps = adam->eps;
-  ad.ln_b1 = log(adam->beta1); ad.ln_b2 = log(adam->beta2); ad.sign = adam->maximize ? -1.0 : 1.0;
-  ad.step_dev = adam->step_dev;
+  const AdamDev ad = adam_dev_of(adam);
   return launch_mlp_backward(*mlp, X, W, step_dev, g_out, g_W, static_cast<double*>(workspace),
                              workspace_bytes / sizeof(double), static_cast<hipStream_t>(stream), &ad, weight_decay);
 }

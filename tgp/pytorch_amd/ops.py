@@ -184,7 +184,7 @@ def jitter_ladder(dtype=torch.float64, jitter=None):
     return [jitter * (10 ** i) for i in range(3)]
 
 
-def raise_for_status(status, retrying=False):
+def raise_for_status(status):
     """Translate the device status words into the reference's exceptions; returns True if a retry with more
     jitter is needed."""
     info, nan = int(status[0]), int(status[1])
@@ -201,18 +201,72 @@ def raise_for_status(status, retrying=False):
     return info != 0
 
 
+def run_jitter_ladder(attempt, jitter=0.0, ladder=None, info=None, what="K_MM"):
+    """psd_safe_cholesky's retry protocol (dsp/utils.py:222-270) around one factorising call: the only retry loop of this module.
+    `attempt(jit)` runs the call at jitter `jit` and returns a true value when the factorisation FAILED -- the failing pivot
+    as an int where it is known.  The first try is at `jitter`; after a failure the values of `ladder` (default:
+    jitter_ladder()) above `jitter` are tried in turn, each success after a failure warns (NumericalWarning).  Returns the jitter
+    it ended with (also in `info["jitter"]`); NotPSDError, naming `what`, when every value failed."""
+    jitter = float(jitter)
+    if info is not None:
+        info["jitter"] = jitter
+    bad = attempt(jitter)
+    if not bad:
+        return jitter
+    last = jitter
+    for jit in (jitter_ladder() if ladder is None else ladder):
+        jit = float(jit)
+        if jit <= jitter:
+            continue
+        last = jit
+        bad = attempt(jit)
+        if not bad:
+            warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
+            if info is not None:
+                info["jitter"] = jit
+            return jit
+    pivot = " (pivot %d)" % bad if isinstance(bad, int) and not isinstance(bad, bool) else ""
+    raise NotPSDError("%s not positive definite even with jitter %g%s" % (what, last, pivot))
+
+
+def _failed_pivot(status):
+    """An `attempt` result from the status words of a call (one device sync): False, or the failing pivot."""
+    status = status.cpu()
+    return raise_for_status(status) and int(status[0])
+
+
 def elbo_step_safe(*args, global_jitter=None, **kw):
-    """elbo_step + the reference's psd_safe_cholesky protocol (one device sync to read the status)."""
-    res = elbo_step(*args, **kw)
-    if not raise_for_status(res[2].cpu()):
-        return res
-    for jit in jitter_ladder(jitter=global_jitter):
+    """elbo_step + the reference's psd_safe_cholesky protocol (one device sync per call to read the status)."""
+    res = None
+
+    def attempt(jit):
+        nonlocal res
         kw["jitter"] = jit
         res = elbo_step(*args, **kw)
-        if not raise_for_status(res[2].cpu()):
-            warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-            return res
-    raise NotPSDError("K_MM not positive definite even with jitter %g (pivot %d)" % (jit, int(res[2][0])))
+        return _failed_pivot(res[2])
+    run_jitter_ladder(attempt, kw.get("jitter", 0.0), jitter_ladder(jitter=global_jitter))
+    return res
+
+
+_STEP_PARAMS = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "rowp")
+
+
+def _step_kwargs(cfg):
+    """The keyword arguments of elbo_step a model's `cfg` dict stands for."""
+    return dict(flow=cfg.get("flow"), S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
+                kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"), jitter=cfg.get("jitter", 0.0))
+
+
+def _step_save(ctx, grads, params):
+    ctx.grads = grads
+    ctx.shapes = tuple(None if t is None else t.shape for t in params)
+
+
+def _step_backward(ctx, g_out):
+    """The saved gradients of a step times the cotangent of its differentiable output, one per argument of forward."""
+    res = tuple(None if shp is None or k not in ctx.grads else (ctx.grads[k] * g_out).reshape(shp)
+                for k, shp in zip(_STEP_PARAMS, ctx.shapes))
+    return (None, None) + res + (None,)
 
 
 class ElboFunction(torch.autograd.Function):
@@ -222,17 +276,11 @@ class ElboFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, Y, Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp, cfg):
-        out, g, status, _ = elbo_step_safe(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], flow=cfg.get("flow"),
-                                           theta=theta, rowp=rowp, S=cfg.get("S"),
-                                           kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
-                                           global_jitter=cfg.get("global_jitter"), kernel=cfg.get("kernel", "scale_rbf"),
-                                           lik=cfg.get("lik")) \
-            if cfg.get("check_status", True) else \
-            elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], flow=cfg.get("flow"), theta=theta,
-                      rowp=rowp, S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
-                      kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"))
-        ctx.grads = g
-        ctx.shapes = tuple(None if t is None else t.shape for t in (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
+        step, kw = elbo_step, _step_kwargs(cfg)
+        if cfg.get("check_status", True):
+            step, kw["global_jitter"] = elbo_step_safe, cfg.get("global_jitter")
+        out, g, status, _ = step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp, **kw)
+        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
         cfg["last_status"] = status
         elbo, ell, kld = out[0].clone(), out[1].clone(), out[2].clone()
         ctx.mark_non_differentiable(ell, kld)
@@ -240,49 +288,40 @@ class ElboFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_elbo, g_ell, g_kld):
-        g = ctx.grads
-        keys = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "rowp")
-        res = []
-        for k, shp in zip(keys, ctx.shapes):
-            if shp is None or k not in g:
-                res.append(None)
-            else:
-                res.append((g[k] * g_elbo).reshape(shp))
-        return (None, None) + tuple(res) + (None,)
+        return _step_backward(ctx, g_elbo)
 
 
 # ---------------------------------------------------------------------------------------------------
 # stand-alone operators
 # ---------------------------------------------------------------------------------------------------
+def _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, kl_scale, kernel, plan=0):
+    """What the q(f) operators open with: (TgpModel, X, (Z, raw_ls, raw_os, m, Lam), lvn) -- the contiguous float64 operands,
+    a zero log_var_noise (a required pointer their kernels do not read) and the Gaussian model over them."""
+    X = _c(X, "X")
+    par = tuple(_c(t, "param") for t in (Z, raw_ls, raw_os, m, Lam))
+    lvn = torch.zeros(1, dtype=torch.float64, device=X.device)
+    md, _ = _model_struct(X, *par, lvn, 1.0, jitter, kl_scale, None, None, None, kernel, plan)
+    return md, X, par, lvn
+
+
 def qf_moments(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_rbf", info=None, plan=0):
     """q(f) marginals (models/sparse_MF_SP.py:274-396): returns mu, v of shape (N,).  `info` (a dict) receives the
-    jitter the factorisation ended with (info["jitter"]: the ladder of psd_safe_cholesky may have raised it)."""
+    jitter the factorisation ended with (info["jitter"]: the ladder of psd_safe_cholesky may have raised it).  `check` False:
+    one call, the status is not read (no host sync)."""
     lib = L.load()
-    X = _c(X, "X")
-    Z, raw_ls, raw_os, m, Lam = (_c(t, "param") for t in (Z, raw_ls, raw_os, m, Lam))
+    md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 1.0, kernel, plan)
     dev = X.device
-    lvn = torch.zeros(1, dtype=torch.float64, device=dev)
-    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 1.0, None, None, None, kernel, plan)
-    ws = workspace(X.shape[0], X.shape[1], m.numel(), 1, 0, 0, 0, dev, md.kernel, plan)
+    ws = workspace(X.shape[0], X.shape[1], md.M, 1, 0, 0, 0, dev, md.kernel, plan)
     mu = torch.empty(X.shape[0], dtype=torch.float64, device=dev)
     v = torch.empty_like(mu)
     status = torch.zeros(8, dtype=torch.int32, device=dev)
-    rc = lib.tgp_qf_moments_f64(md, L.ptr(X), L.ptr(mu), L.ptr(v), L.ptr(status), L.ptr(ws), ws.numel() * 8,
-                                L.stream_ptr())
-    L.check(rc, "tgp_qf_moments_f64")
-    if info is not None:
-        info["jitter"] = float(jitter)
-    if check and raise_for_status(status.cpu()):
-        for jit in jitter_ladder():
-            md.jitter = jit
-            L.check(lib.tgp_qf_moments_f64(md, L.ptr(X), L.ptr(mu), L.ptr(v), L.ptr(status), L.ptr(ws),
-                                           ws.numel() * 8, L.stream_ptr()), "tgp_qf_moments_f64")
-            if not raise_for_status(status.cpu()):
-                warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-                if info is not None:
-                    info["jitter"] = float(jit)
-                return mu, v
-        raise NotPSDError("K_MM not positive definite")
+
+    def attempt(jit):
+        md.jitter = jit
+        L.check(lib.tgp_qf_moments_f64(md, L.ptr(X), L.ptr(mu), L.ptr(v), L.ptr(status), L.ptr(ws), ws.numel() * 8,
+                                       L.stream_ptr()), "tgp_qf_moments_f64")
+        return check and raise_for_status(status.cpu())
+    run_jitter_ladder(attempt, jitter, info=info)
     return mu, v
 
 
@@ -292,13 +331,10 @@ def qf_cov(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_r
     psd_safe_cholesky on K_MM, as in qf_moments; `info["jitter"]` receives the value the factorisation ended with.
     `workspace_bytes` overrides the size of the workspace handed to the library (tests of its refusal)."""
     lib = L.load()
-    X = _c(X, "X")
-    Z, raw_ls, raw_os, m, Lam = (_c(t, "param") for t in (Z, raw_ls, raw_os, m, Lam))
+    md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 1.0, kernel)
     dev = X.device
     N, D = X.shape
-    lvn = torch.zeros(1, dtype=torch.float64, device=dev)
-    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 1.0, None, None, None, kernel)
-    nbytes = lib.tgp_qf_cov_workspace_bytes(N, D, m.numel()) if workspace_bytes is None else int(workspace_bytes)
+    nbytes = lib.tgp_qf_cov_workspace_bytes(N, D, md.M) if workspace_bytes is None else int(workspace_bytes)
     if N > 4096:       # refused by the library before anything is allocated for an N x N result
         L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), None, None, None, None, 0, L.stream_ptr()), "tgp_qf_cov_f64")
     ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
@@ -306,22 +342,12 @@ def qf_cov(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_r
     Sigma = torch.empty(N, N, dtype=torch.float64, device=dev)
     status = torch.zeros(8, dtype=torch.int32, device=dev)
 
-    def call():
+    def attempt(jit):
+        md.jitter = jit
         L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), L.ptr(mu), L.ptr(Sigma), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()),
                 "tgp_qf_cov_f64")
-    call()
-    if info is not None:
-        info["jitter"] = float(jitter)
-    if check and raise_for_status(status.cpu()):
-        for jit in jitter_ladder():
-            md.jitter = jit
-            call()
-            if not raise_for_status(status.cpu()):
-                warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-                if info is not None:
-                    info["jitter"] = float(jit)
-                return mu, Sigma
-        raise NotPSDError("K_MM not positive definite")
+        return check and raise_for_status(status.cpu())
+    run_jitter_ladder(attempt, jitter, info=info)
     return mu, Sigma
 
 
@@ -348,36 +374,26 @@ def qf_joint_sample(mu, Sigma, eps, jitter=0.0, want_L=False, workspace_bytes=No
 def qf_joint_sample_safe(mu, Sigma, eps, jitter=None, info=None):
     """qf_joint_sample under psd_safe_cholesky's protocol (dsp/utils.py:222-270): the first factorisation with jitter 0,
     then jitter * 10^i, i = 0..2 (1e-8 in float64 unless given).  Returns F0; `info["jitter"]` = the value that succeeded."""
-    F0, _, status = qf_joint_sample(mu, Sigma, eps, 0.0)
-    used = 0.0
-    if raise_for_status(status.cpu()):
-        for jit in jitter_ladder(jitter=jitter):
-            F0, _, status = qf_joint_sample(mu, Sigma, eps, jit)
-            if not raise_for_status(status.cpu()):
-                warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-                used = jit
-                break
-        else:
-            raise NotPSDError("Sigma not positive definite even with jitter %g (pivot %d)" % (jit, int(status[0])))
-    if info is not None:
-        info["jitter"] = float(used)
+    F0 = None
+
+    def attempt(jit):
+        nonlocal F0
+        F0, _, status = qf_joint_sample(mu, Sigma, eps, jit)
+        return _failed_pivot(status)
+    run_jitter_ladder(attempt, 0.0, jitter_ladder(jitter=jitter), info, what="Sigma")
     return F0
 
 
 def qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, mu_bar, v_bar, jitter=0.0, kernel="scale_rbf", plan=0):
     """Adjoint of qf_moments (tgp_qf_moments_bwd_f64): d(sum mu_bar*mu + v_bar*v)/d{Z, raw_ls, raw_os, m, Lam} as a dict."""
     lib = L.load()
-    X = _c(X, "X")
-    Z, raw_ls, raw_os, m, Lam = (_c(t, "param") for t in (Z, raw_ls, raw_os, m, Lam))
+    md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 0.0, kernel, plan)
     mu_bar, v_bar = _c(mu_bar.reshape(-1), "mu_bar"), _c(v_bar.reshape(-1), "v_bar")
     if mu_bar.numel() != X.shape[0] or v_bar.numel() != X.shape[0]:
         raise ValueError("mu_bar / v_bar must have one entry per row of X")
     dev = X.device
-    lvn = torch.zeros(1, dtype=torch.float64, device=dev)
-    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 0.0, None, None, None, kernel, plan)
-    ws = workspace(X.shape[0], X.shape[1], m.numel(), 1, 0, 0, 0, dev, md.kernel, plan)
-    g = {"Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os),
-         "m": torch.empty_like(m), "Lam": torch.empty_like(Lam)}
+    ws = workspace(X.shape[0], X.shape[1], md.M, 1, 0, 0, 0, dev, md.kernel, plan)
+    g = {k: torch.empty_like(t) for k, t in zip(("Z", "raw_ls", "raw_os", "m", "Lam"), par)}
     glvn = torch.empty_like(lvn)
     gs = L.TgpGrads()
     gs.Z, gs.raw_ls, gs.raw_os, gs.m, gs.Lam = (L.ptr(g[k]) for k in ("Z", "raw_ls", "raw_os", "m", "Lam"))
@@ -436,30 +452,6 @@ class KlFunction(torch.autograd.Function):
 # unwhitened q(u) (is_whiten=False): the change of variables to the whitened kernels
 # ---------------------------------------------------------------------------------------------------
 KL_PRIOR_JITTERS = tuple(1e-8 * (10 ** i) for i in range(5))     # add_jitter_MultivariateNormal (dsp/utils.py:200-218), float64
-
-
-def run_jitter_ladder(attempt, jitter=0.0, ladder=None, info=None):
-    """psd_safe_cholesky's retry protocol around one factorising call.  `attempt(jit)` runs the call at jitter `jit` and returns
-    True when the factorisation FAILED.  The first try is at `jitter`; after a failure the values of `ladder` (default:
-    jitter_ladder()) above `jitter` are tried in turn, each success after a failure warns (NumericalWarning).  Returns the jitter
-    it ended with (also in `info["jitter"]`); NotPSDError when every value failed."""
-    jitter = float(jitter)
-    if info is not None:
-        info["jitter"] = jitter
-    if not attempt(jitter):
-        return jitter
-    last = jitter
-    for jit in (jitter_ladder() if ladder is None else ladder):
-        jit = float(jit)
-        if jit <= jitter:
-            continue
-        last = jit
-        if not attempt(jit):
-            warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-            if info is not None:
-                info["jitter"] = jit
-            return jit
-    raise NotPSDError("K_MM not positive definite even with jitter %g" % last)
 
 
 def unwhiten(Z, raw_ls, raw_os, m, L_q, jitter=0.0, check=True, kernel="scale_rbf", info=None, ladder=None,
@@ -551,27 +543,17 @@ class EllStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, Y, Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp, cfg):
-        out, g, status, _ = elbo_step(X, Y, Z.detach(), raw_ls.detach(), raw_os.detach(), m.detach(), Lam.detach(), lvn.detach(),
-                                      cfg["N_total"], flow=cfg.get("flow"), theta=theta.detach() if theta is not None else None,
-                                      rowp=rowp.detach() if rowp is not None else None, S=cfg.get("S"),
-                                      jitter=cfg.get("jitter", 0.0), kl_scale=0.0, mb_global=cfg.get("mb_global"),
-                                      kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"))
+        kw = dict(_step_kwargs(cfg), kl_scale=0.0)
+        out, g, status, _ = elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp, **kw)
         cfg["last_status"] = status
         if cfg.get("check_status", True) and raise_for_status(status.cpu()):
-            raise NotPSDError("K_MM not positive definite in the step at jitter %g (pivot %d)" % (cfg.get("jitter", 0.0),
-                                                                                                  int(status[0])))
-        ctx.grads = g
-        ctx.shapes = tuple(None if t is None else t.shape for t in (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
+            raise NotPSDError("K_MM not positive definite in the step at jitter %g (pivot %d)" % (kw["jitter"], int(status[0])))
+        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
         return out[1].clone()
 
     @staticmethod
     def backward(ctx, g_ell):
-        g = ctx.grads
-        keys = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "rowp")
-        res = []
-        for k, shp in zip(keys, ctx.shapes):
-            res.append(None if shp is None or k not in g else (g[k] * g_ell).reshape(shp))
-        return (None, None) + tuple(res) + (None,)
+        return _step_backward(ctx, g_ell)
 
 
 def kernel_matrix(X1, X2, raw_ls, raw_os, kernel="scale_rbf", jitter=0.0):
@@ -658,29 +640,25 @@ def psd_safe_cholesky(A, jitter=None):
     """dsp/utils.py:222-270 on the GPU: returns (L, A_used).  With autograd on and A requiring grad the factor carries a
     gradient to A (CholeskyFunction), as the reference's torch.cholesky does."""
     diff = torch.is_grad_enabled() and A.requires_grad
+    Ax, prev, Lo = A, 0.0, None
 
-    def attempt(Ax):
+    def attempt(jit):
+        nonlocal Ax, prev, Lo
+        if jit != 0.0:
+            if Ax is A:
+                Ax = A.clone()          # (a non-leaf copy: the in-place diagonal updates below are autograd-safe)
+            Ax.diagonal().add_(jit - prev)     # (from one rung to the next, as the reference's loop adds them)
+            prev = jit
         if diff:
             try:
-                return CholeskyFunction.apply(Ax), False
+                Lo = CholeskyFunction.apply(Ax)
             except NotPSDError:
-                return None, True
+                return True
+            return False
         Lo, _, status = cholesky(Ax)
-        return Lo, raise_for_status(status.cpu())
-
-    Lo, bad = attempt(A)
-    if not bad:
-        return Lo, A
-    Ap = A.clone()          # (a non-leaf copy: the in-place diagonal updates below are autograd-safe)
-    prev = 0.0
-    for jit in jitter_ladder(A.dtype, jitter):
-        Ap.diagonal().add_(jit - prev)
-        prev = jit
-        Lo, bad = attempt(Ap)
-        if not bad:
-            warnings.warn("A not p.d., added jitter of %g to the diagonal" % jit, NumericalWarning)
-            return Lo, Ap
-    raise NotPSDError("matrix not positive definite even with jitter %g" % prev)
+        return raise_for_status(status.cpu())
+    run_jitter_ladder(attempt, 0.0, jitter_ladder(A.dtype, jitter), what="matrix")
+    return Lo, Ax
 
 
 TRI_A_LOWER, TRI_A_UPPER, TRI_B_LOWER, TRI_B_UPPER, TRI_C_LOWER = 1, 2, 4, 8, 16
@@ -728,15 +706,20 @@ def ell_gauss(Y, mu, v, lvn, scale=1.0):
     return out[0], out[1], gmu, gv
 
 
-def _flow_model(N, S, flow, theta, lvn, dev, scale=1.0, lik=L.LIK_FLOW):
+def _flow_model(N, S, flow, theta, lvn, dev, scale=1.0, lik=None):
+    """(TgpModel, tensors to keep referenced until the call returns) for the row-wise likelihood kernels, which read no GP
+    field.  `flow` None: the Gaussian likelihood; else `lik` (None: LIK_FLOW) through `flow` at S Gauss-Hermite nodes."""
     md = L.TgpModel()
-    md.N, md.D, md.M, md.S = N, 1, 1, int(S)
-    md.nblk, md.P, md.RP, md.lik = flow.nblk, flow.P, flow.RP, lik
+    md.N, md.D, md.M, md.S, md.lik = N, 1, 1, 1, L.LIK_GAUSS
     md.scale, md.jitter, md.kl_scale = float(scale), 0.0, 1.0
+    md.log_var_noise = L.ptr(lvn)
+    if flow is None:
+        return md, ()
+    md.S, md.lik = int(S), L.LIK_FLOW if lik is None else int(lik)
+    md.nblk, md.P, md.RP = flow.nblk, flow.P, flow.RP
     xs, wn = gauss_hermite(S, dev)
     md.program, md.xs, md.wn = flow.program_ptr, L.ptr(xs), L.ptr(wn)
     md.theta = L.ptr(theta) if flow.P > 0 else None
-    md.log_var_noise = L.ptr(lvn)
     return md, (xs, wn)
 
 
@@ -1035,13 +1018,7 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     dev, N = mu.device, mu.numel()
-    if flow is None:
-        md = L.TgpModel()
-        md.N, md.D, md.M, md.S, md.lik = N, 1, 1, 1, L.LIK_GAUSS
-        md.log_var_noise = L.ptr(lvn)
-        keep = None
-    else:
-        md, keep = _flow_model(N, S, flow, theta, lvn, dev, lik=L.LIK_FLOW if lik is None else int(lik))
+    md, keep = _flow_model(N, S, flow, theta, lvn, dev, lik=lik)
     # (want_moments=False: logp only -- the warped moments cost S flow inversions per row)
     m1, m2 = (torch.empty_like(mu), torch.empty_like(mu)) if want_moments else (None, None)
     logp = torch.empty_like(mu) if Y is not None else None
@@ -1063,14 +1040,9 @@ def quantile_probs(probs, device=None):
 
 
 def _quantile_model(mu, lvn, flow, theta, S):
-    if flow is None:
-        md = L.TgpModel()
-        md.N, md.D, md.M, md.S, md.lik = mu.numel(), 1, 1, 1, L.LIK_GAUSS
-        md.log_var_noise = L.ptr(lvn)
-        return md, None
-    if S is None:
+    if flow is not None and S is None:
         raise ValueError("a flow needs S, the number of Gauss-Hermite nodes")
-    return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device, lik=L.LIK_FLOW)
+    return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device)
 
 
 def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=None, check=True):
