@@ -132,6 +132,10 @@ extern "C" {
  *     TGP_PLAN_ROWS4_NW4 / TGP_PLAN_ROWS4_NW8  k_rows4 with 4 / 8 waves per workgroup (ignored where its LDS plan or the
  *                          workspace's slab count does not allow it)
  *   bit 4     TGP_PLAN_NO_CHUNK_OVERLAP  general-M path: one set of chunk buffers, forward and backward of the chunks in line
+ *   bit 5     TGP_PLAN_FULL_PAD  fused path (M <= 128): the M x M backward launch contracts over all MP / 4 k-steps of M padded
+ *             to the next multiple of 16 instead of the ceil(M / 4) that carry data.  Same results bit for bit (the padding
+ *             holds exact zeros); exists for A/B timing and for the tests that compare the two.  The workspace size does not
+ *             depend on it.
  *   bits 8-23 TGP_PLAN_CHUNK_ROWS(n)     general-M path: row chunks of at most n rows (rounded up to 128; 0 = 16 384) */
 #define TGP_PLAN_ROWS_AUTO 0
 #define TGP_PLAN_ROWS_K16 1
@@ -140,6 +144,7 @@ extern "C" {
 #define TGP_PLAN_ROWS4_NW8 4
 #define TGP_PLAN_ROWS_MASK 15
 #define TGP_PLAN_NO_CHUNK_OVERLAP 16
+#define TGP_PLAN_FULL_PAD 32
 #define TGP_PLAN_CHUNK_ROWS(n) (((((n) + 127) / 128) & 0xffff) << 8)
 #define TGP_PLAN_CHUNK_OF(plan) ((((plan) >> 8) & 0xffff) * 128)
 

@@ -121,11 +121,12 @@ static bool takes_general_path(const tgp_model& m) { return takes_general_path(m
 // the caller's buffer does not hold it
 static int fused_plan(Plan& p, const tgp_model& m, int S, int nblk, int P, int RP, int lik, bool train, const FlowProg& fp,
                       size_t workspace_bytes) {
-  if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik)) return rc;
+  const bool full_pad = (m.plan & TGP_PLAN_FULL_PAD) != 0;   // A/B switch: compute on the padding of M as well
+  if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik, 0, 16, full_pad)) return rc;
   p.nslots = fp.nslots;
   const int nw4 = choose_rows4(p, train, m.plan), rw = nw4 ? 16 : rows_per_wave(p, fp, train, m.plan);
   if (nw4 != 0 || rw != 16) {
-    if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik, nw4, rw)) return rc;
+    if (int rc = make_plan(p, m.N, m.D, m.M, S, nblk, P, RP, lik, nw4, rw, full_pad)) return rc;
     p.nslots = fp.nslots;
   }
   return workspace_bytes < p.total * sizeof(double) ? TGP_E_WORKSPACE : 0;

@@ -65,6 +65,8 @@ __device__ __forceinline__ void st_agent(double* p, double v) {
 struct Plan {
   int N, D, M, S, nblk, P, RP, lik;
   int MT, MP, DP, CT, CT16, ntri, nblocks;
+  int MR;      // real rows of the last 16-row tile of M, M - 16 (MT - 1); 16 under TGP_PLAN_FULL_PAD
+  int KL;      // k-steps of that tile that carry data, ceil(MR / 4): what k_bwd's products issue of its four
   int nw4;     // 0: the 16-rows-per-wave row kernel (k_rows, 64 rows per block); else k_rows4 with nw4 waves per block
   int rw;      // data rows per wave of k_rows: 16, or 10 (tgp_rows.hpp, RW) -- meaningful when nw4 == 0
   int rpb;     // data rows per row block (= per slab): 4 * rw or 4 * nw4
@@ -120,11 +122,13 @@ inline int plan_alloc_blocks(int N) {
   return nb < 1 ? 1 : nb;
 }
 
-inline int make_plan(Plan& p, int N, int D, int M, int S, int nblk, int P, int RP, int lik, int nw4 = 0, int rw = 16) {
+inline int make_plan(Plan& p, int N, int D, int M, int S, int nblk, int P, int RP, int lik, int nw4 = 0, int rw = 16,
+                     bool full_pad = false) {
   if (D < 1 || D > 16) return -2;
   if (M < 1 || M > 16 * TGP_MAX_MT) return TGP_E_UNSUPPORTED;
   p.N = N; p.D = D; p.M = M; p.S = S; p.nblk = nblk; p.P = P; p.RP = RP; p.lik = lik; p.nslots = 0; p.zs_lds = 0;
   p.MT = (M + 15) / 16; p.MP = p.MT * 16;
+  p.MR = full_pad ? 16 : M - 16 * (p.MT - 1); p.KL = (p.MR + 3) / 4;
   p.DP = D <= 4 ? 4 : (D <= 8 ? 8 : 16);
   p.CT = (2 * p.DP + 1 + 15) / 16; p.CT16 = p.CT * 16;
   p.ntri = p.MT * (p.MT + 1) / 2;

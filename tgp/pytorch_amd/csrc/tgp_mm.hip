@@ -561,6 +561,11 @@ __device__ __forceinline__ void bwd_g_commit(const Plan& p, double* Gs, double* 
   if (tid < 16) svL[tid] = sv0;
 }
 
+// k-steps of a contraction over M that carry data: every row of G, Lbar, Q and every column of Y past them is an exact zero
+// (the row kernel's A is zero on the padding of M, and Lq, S, w are), so the M x M products stop there -- and never request
+// the fragments of the other operand (finite: identity / zero rows of L, J, H').  MP / 4 under TGP_PLAN_FULL_PAD.
+__device__ __forceinline__ int bwd_ksteps(const Plan& p) { return 4 * (p.MT - 1) + p.KL; }
+
 // 16 x 16 tile product on one wave: A fragments `a` (registers, k-step s_ = a[s_]), B fragments from LDS through fb(s_);
 // SWAP: the register fragments are the B operand, the LDS ones the A operand
 template <int PF, bool SWAP = false, class FB>
@@ -599,7 +604,7 @@ __device__ __forceinline__ void bwd_lam_role(const Plan& p, const tgp_model& md,
   const double* __restrict__ Lq = ws + p.Lq;
   const int j = wave, j0 = 16 * j;
   const bool has = j < MT;
-  const int n = has && j <= c ? (MP - j0) / 4 : 0;
+  const int n = has && j <= c ? bwd_ksteps(p) - j0 / 4 : 0;
   double lq[PF];
 #pragma unroll
   for (int s_ = 0; s_ < PF; ++s_) lq[s_] = s_ < n ? Lq[(size_t)(j0 + 4 * s_ + q) * MP + j0 + r] : 0.0;
@@ -659,7 +664,7 @@ __device__ __forceinline__ void bwd_q_role(const Plan& p, double* __restrict__ w
   const bool has = wave < MT - c;
   const bool spare = MT - c < BWD_THREADS / 64, tw = spare && wave == MT - c;
   const int i0 = tw ? c0 : 16 * (c + wave);
-  const int n1 = has ? MP / 4 : 0, n2 = has || tw ? (MP - i0) / 4 : 0;
+  const int n1 = has ? bwd_ksteps(p) : 0, n2 = has || tw ? bwd_ksteps(p) - i0 / 4 : 0;
   double hp[PF], pq[PF], wv[4];
 #pragma unroll
   for (int s_ = 0; s_ < PF; ++s_) hp[s_] = s_ < n1 ? HpT[(size_t)(4 * s_ + q) * MP + i0 + r] : 0.0;
@@ -743,8 +748,8 @@ __device__ __forceinline__ void bwd_row_role(const Plan& p, double* __restrict__
   if (tid < 16 * DP) zsL[tid] = (ws + p.Zs)[(size_t)i0 * DP + tid];
   for (int e = tid; e < (MP - i0) * 16; e += BWD_THREADS) Ja[e] = J[(size_t)(i0 + (e >> 4)) * MP + i0 + (e & 15)];
   // second product of wave j: k over the rows of this half's column tiles at or below tile j (J[k, j] = 0 for k < j)
-  const int ks0 = 16 * (jbw > kb0 ? jbw : kb0), ks1 = 16 * kb1;
-  const int n1 = wave < nk ? (MP - i0) / 4 : 0, n2 = wave < MT && ks1 > ks0 ? (ks1 - ks0) / 4 : 0;
+  const int ks0 = 16 * (jbw > kb0 ? jbw : kb0), ks1 = 16 * kb1 < 4 * bwd_ksteps(p) ? 16 * kb1 : 4 * bwd_ksteps(p);
+  const int n1 = wave < nk ? bwd_ksteps(p) - i0 / 4 : 0, n2 = wave < MT && ks1 > ks0 ? (ks1 - ks0) / 4 : 0;
   constexpr int PF = TGP_PF2, PFH = 2 * TGP_MAX_MT;      // k-steps of a full column / of half of the tile rows
   double jb2[PFH];
 #pragma unroll
