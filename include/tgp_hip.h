@@ -313,6 +313,28 @@ int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, 
                          const double* Lam_w_bar, double* m_bar, double* L_q_bar, double* Z_bar, double* raw_ls_bar,
                          double* raw_os_bar, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mean functions (models/means.py, chosen by model_specs[0], models/utils_models.py:285-294): 'linear' m(x) = x a + b with a (D)
+ * and b (1) trainable, 'identity' m(x) = x W with W (D) fixed (b = NULL).  One output GP: a is a vector.  The reference adds
+ * m(X) to the q(f) mean (models/sparse_MF_SP.py:314,355,360), subtracts m(Z) from the unwhitened variational mean (:359) and uses
+ * it as the prior mean of the unwhitened KL (:446).
+ * tgp_mean_forward_f64:   out[n ld + col] = alpha (sum_d X[n,d] a[d] + b[0]) + (in ? in[n] : 0),  n < N, the sum in the order
+ *   d = 0 .. D-1; b == NULL counts as 0; one_col >= 0 also writes 1.0 to out[n ld + one_col].  No other element of out is
+ *   touched.  With ld = 2, col = 1, one_col = 0 it fills the (N, 2) rowp columns (a_n, b_n) = (1, m(x_n)) of a per-row
+ *   TGP_FLOW_AFFINE block at the head of a flow program, which turns G(f) into G(f + m(x_n)); with alpha = -1, in = Y it forms
+ *   Y - m(X); with in = mu it forms mu + m(X).  in may alias out when ld = 1.
+ * tgp_mean_backward_f64:  with g_n = g[n ldg + colg] (read in place from a column of g_rowp, or a vector with ldg = 1, colg = 0)
+ *   g_a[d] = sum_n g_n X[n,d],   g_b[0] = sum_n g_n (g_b == NULL: skipped),   g_X[n,d] = g_n a[d] (g_X == NULL: skipped, and a
+ *   may then be NULL).  Summation order, fixed: a lane sums rows 1024 w + t + 256 i (i = 0 .. 3) of workgroup w, the wave
+ *   butterfly, the four waves in order, the workgroups in order by a second launch.  The grid depends on N only.  No float
+ *   atomics: same input, same bits on any device.  workspace: tgp_mean_backward_workspace_bytes(N, D) bytes, 8-byte aligned.
+ * Limits: N >= 1, 1 <= D <= 16 (else TGP_E_UNSUPPORTED, tgp_last_error() names the entry), 0 <= col < ld, one_col < ld and
+ * != col, 0 <= colg < ldg: otherwise the negative index of the offending argument; a small workspace gives TGP_E_WORKSPACE. */
+int tgp_mean_forward_f64(const double* X, int32_t N, int32_t D, const double* a, const double* b, double alpha, const double* in,
+                         double* out, int32_t ld, int32_t col, int32_t one_col, void* stream);
+size_t tgp_mean_backward_workspace_bytes(int32_t N, int32_t D);
+int tgp_mean_backward_f64(const double* X, int32_t N, int32_t D, const double* a, const double* g, int32_t ldg, int32_t colg,
+                          double* g_a, double* g_b, double* g_X, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Adjoint of tgp_qf_moments_f64 (what autograd replays for models/sparse_MF_SP.py:274-396 when a caller differentiates
  * the q(f) marginals outside ELBO(): predictive moments with respect to the inducing points, hyper-parameters or q(u)).
  * Given mu_bar, v_bar (N) it writes d(sum_n mu_bar_n mu_n + v_bar_n v_n)/d{Z, raw_ls, raw_os, m, Lam} into `grads`

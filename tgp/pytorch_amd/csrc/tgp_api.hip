@@ -570,6 +570,47 @@ int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, 
                              raw_ls_bar, raw_os_bar, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+int tgp_mean_forward_f64(const double* X, int32_t N, int32_t D, const double* a, const double* b, double alpha, const double* in,
+                         double* out, int32_t ld, int32_t col, int32_t one_col, void* stream) {
+  if (!X) return -1;
+  if (N < 1) return -2;
+  if (D < 1 || D > 16) {
+    set_error_text("tgp_mean_forward_f64: D = %d outside 1 <= D <= 16", D);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!a) return -4;
+  if (!out) return -8;
+  if (ld < 1) return -9;
+  if (col < 0 || col >= ld) return -10;
+  if (one_col >= ld || one_col == col) return -11;
+  return launch_mean_forward(X, N, D, a, b, alpha, in, out, ld, col, one_col < 0 ? -1 : one_col, static_cast<hipStream_t>(stream));
+}
+
+size_t tgp_mean_backward_workspace_bytes(int32_t N, int32_t D) { return mean_backward_workspace_bytes(N, D); }
+
+int tgp_mean_backward_f64(const double* X, int32_t N, int32_t D, const double* a, const double* g, int32_t ldg, int32_t colg,
+                          double* g_a, double* g_b, double* g_X, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!X) return -1;
+  if (N < 1) return -2;
+  if (D < 1 || D > 16) {
+    set_error_text("tgp_mean_backward_f64: D = %d outside 1 <= D <= 16", D);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!a && g_X) return -4;
+  if (!g) return -5;
+  if (ldg < 1) return -6;
+  if (colg < 0 || colg >= ldg) return -7;
+  if (!g_a) return -8;
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7)) return -11;
+  if (workspace_bytes < mean_backward_workspace_bytes(N, D)) {
+    set_error_text("tgp_mean_backward_f64: workspace of %zu bytes, tgp_mean_backward_workspace_bytes gives %zu", workspace_bytes,
+                   mean_backward_workspace_bytes(N, D));
+    return TGP_E_WORKSPACE;
+  }
+  return launch_mean_backward(X, N, D, a, g, ldg, colg, g_a, g_b, g_X, static_cast<double*>(workspace),
+                              static_cast<hipStream_t>(stream));
+}
+
 int tgp_gemm_f64(int32_t trans_a, int32_t trans_b, int32_t tri, int32_t m, int32_t n, int32_t k, double alpha,
                  const double* A, int32_t lda, const double* B, int32_t ldb, double beta, double* C, int32_t ldc,
                  void* stream) {

@@ -168,4 +168,11 @@ int launch_unwhiten_bwd(int kernel, const double* Z, const double* raw_ls, const
                         double* m_bar, double* Lq_bar, double* Z_bar, double* raw_ls_bar, double* raw_os_bar, void* workspace,
                         size_t workspace_bytes, hipStream_t st);
 
+// tgp_mean.hip (linear / identity mean function: m(x) = x a + b on the rows of X, and its adjoint)
+size_t mean_backward_workspace_bytes(int N, int D);
+int launch_mean_forward(const double* X, int N, int D, const double* a, const double* b, double alpha, const double* in,
+                        double* out, int ld, int col, int one_col, hipStream_t st);
+int launch_mean_backward(const double* X, int N, int D, const double* a, const double* g, int ldg, int colg, double* g_a,
+                         double* g_b, double* g_X, double* part, hipStream_t st);
+
 }  // namespace tgp

@@ -28,7 +28,8 @@ CAPTURE_MODE = os.environ.get("TGP_CAPTURE_MODE", "thread_local")   # the overri
 from . import lib as L
 from . import ops
 
-ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "nn")   # "nn" (packed MLP weights) last: the weight-decay group
+# "mean_a" / "mean_b": a linear mean function's parameters; "nn" (packed MLP weights) last: the weight-decay group
+ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "mean_a", "mean_b", "nn")
 
 
 def allreduce_flat(grad, n, world_size, group=None):
@@ -237,8 +238,15 @@ class ElboEngine:
                  eps=1e-8, device="cuda:0", world_size=1, rank=0, mb_global=None, process_group=None,
                  kernel="scale_rbf", mlp=None, mlp_weights=None, nn_weight_decay=1e-5, mlp_training=True,
                  jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None,
-                 is_whiten=True):
-        """`mlp` (ops.MlpSpec) + `mlp_weights` (packed, nnets * weights_per_net): input-dependent flow (ID_TGP) whose
+                 is_whiten=True, mean=None):
+        """`mean` = ("linear", a, b) or ("identity", W, None): m(x) = x a + b enters the step as a per-row affine block
+        (a_n, b_n) = (1, m(x_n)) at the head of the flow program, G(f) -> G(f + m(x_n)).  Linear: a (D) and b (1) are segments
+        of the flat buffer; a step is tgp_mean_forward_f64 -> the ELBO step (all phases) -> tgp_mean_backward_f64 from
+        g_rowp[:, 1] into the flat gradient -> the separate Adam launch, all captured.  Identity: W is fixed, the rows'
+        parameters are written once.  With the Gaussian likelihood (flow_blocks None) the step runs TGP_LIK_FLOW over the
+        otherwise empty program: Gauss-Hermite integrates the quadratic integrand exactly, so the result differs from the
+        closed form by rounding only.  One rank, full batch.
+        `mlp` (ops.MlpSpec) + `mlp_weights` (packed, nnets * weights_per_net): input-dependent flow (ID_TGP) whose
         per-row parameters come from the HIP MLP kernels inside the step; `nn_weight_decay` is the reference's Adam
         group for the 'NNets' parameters (main.py:276-288).  `share` = another ElboEngine of the same model whose flat
         parameter / gradient / Adam buffers and step counter this one uses (two batch sizes of one training run)."""
@@ -247,6 +255,21 @@ class ElboEngine:
             # transform in it
             raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
                                       "the eager path (Trainer_SP), on one rank")
+        self.mean = None
+        if mean is not None:
+            kind = mean[0]
+            if kind not in ("linear", "identity"):
+                raise ValueError("mean must be ('linear', a, b) or ('identity', W, None), got %r" % (kind,))
+            if int(world_size) > 1 or collective is not None:
+                raise NotImplementedError("the '%s' mean function's engine is single-rank (world_size = 1): a data-parallel "
+                                          "step with a mean is not implemented" % kind)
+            if likelihood == "warped" or mlp is not None or rowp is not None:
+                raise NotImplementedError("the '%s' mean function is not built for the warped likelihood or input-dependent "
+                                          "flows" % kind)
+            self.mean = kind
+            rowp = torch.zeros(X.shape[0], 2, dtype=torch.float64)
+            flow_blocks = [(L.FLOW_AFFINE, 0, 0, L.FLAG_PER_ROW)] + [tuple(b) for b in (flow_blocks or [])]
+            S = S if S else 8
         self.lib = L.load()
         self.device = torch.device(device)
         self.world_size, self.rank, self.pg = int(world_size), int(rank), process_group
@@ -322,6 +345,13 @@ class ElboEngine:
         tensors["raw_ls"] = tensors["raw_ls"].reshape(-1)
         tensors["raw_os"] = tensors["raw_os"].reshape(-1)
         tensors["lvn"] = tensors["lvn"].reshape(-1)
+        self.mean_W = None
+        if self.mean == "linear":
+            tensors["mean_a"], tensors["mean_b"] = mean[1].detach().reshape(-1), mean[2].detach().reshape(-1)
+            assert tensors["mean_a"].numel() == self.D and tensors["mean_b"].numel() == 1
+        elif self.mean == "identity":
+            self.mean_W = mean[1].detach().reshape(-1).to(self.device, torch.float64).contiguous()
+            assert self.mean_W.numel() == self.D
         self.fp = FlatParams(tensors, self.device) if share is None else share.fp
         self.M = self.fp.sizes["m"]
         self.flow = None
@@ -357,13 +387,19 @@ class ElboEngine:
             self.gs.rowp = L.ptr(self.g_rowp)
         self.ws = ops.workspace(self.N, self.D, self.M, self.md.S, self.md.nblk, self.md.P, self.md.RP, self.device,
                                 self.md.kernel, plan, self.md.lik)
+        self.mean_ws = None
+        if self.mean == "linear":
+            self.mean_ws = torch.empty(max(self.lib.tgp_mean_backward_workspace_bytes(self.N, self.D), 8) // 8,
+                                       dtype=torch.float64, device=self.device)
+        elif self.mean == "identity":
+            self.mean_forward()      # W is fixed: the rows' parameters are written once
         self.mlp_ws = None
         if self.mlp is not None:
             d = self.mlp.struct(self.N, True)
             self.mlp_ws = torch.empty(self.lib.tgp_mlp_workspace_bytes(d) // 8 + 16, dtype=torch.float64, device=self.device)
         # One rank, shared flow parameters only: ELBO step + Adam in ONE C-ABI call (tgp_elbo_step_adam_f64: on the fused
         # path the update rides in the last two backward launches -- one launch and one pass over the buffers less)
-        self.fused_adam = (self.world_size == 1 and self.comm is None and self.mlp is None
+        self.fused_adam = (self.world_size == 1 and self.comm is None and self.mlp is None and self.mean is None
                            and os.environ.get("TGP_FUSED_ADAM", "1") != "0")
         self.ad = L.TgpAdamArgs()
         self.ad.params, self.ad.grads = L.ptr(fp.data), L.ptr(fp.grad)
@@ -449,6 +485,20 @@ class ElboEngine:
                                               L.ptr(self.step_dev), 1, L.stream_ptr())
         L.check(rc, "tgp_adam_dev_groups_f64")
 
+    def mean_forward(self):
+        """rowp[:, 0] = 1, rowp[:, 1] = m(x_n) from the flat buffer's a, b (or the fixed W)."""
+        a = self.fp.view("mean_a") if self.mean == "linear" else self.mean_W
+        b = self.fp.view("mean_b") if self.mean == "linear" else None
+        L.check(self.lib.tgp_mean_forward_f64(L.ptr(self.X), self.N, self.D, L.ptr(a), L.ptr(b), 1.0, None, L.ptr(self.rowp), 2,
+                                              1, 0, L.stream_ptr()), "tgp_mean_forward_f64")
+
+    def mean_backward(self):
+        """a_bar, b_bar from g_rowp[:, 1] (read in place) into the flat gradient."""
+        fp = self.fp
+        L.check(self.lib.tgp_mean_backward_f64(L.ptr(self.X), self.N, self.D, None, L.ptr(self.g_rowp), 2, 1,
+                                               L.ptr(fp.gview("mean_a")), L.ptr(fp.gview("mean_b")), None, L.ptr(self.mean_ws),
+                                               self.mean_ws.numel() * 8, L.stream_ptr()), "tgp_mean_backward_f64")
+
     def mlp_forward(self, step=None):
         if self.mlp is not None:
             d = self.mlp.struct(self.N, self.mlp_training)
@@ -493,6 +543,11 @@ class ElboEngine:
         With MLPs the two halves that do not depend on each other run on a side stream: the MLP forward (needs X and
         the weights only) under the M x M prepare phase (K_MM, Cholesky, KL), and the MLP backward (needs d/d rowp from
         the row kernel only) under the M x M adjoint.  Fork and join are event waits, valid under graph capture."""
+        if self.mean == "linear":
+            self.mean_forward()
+            self.elbo()
+            self.mean_backward()
+            return
         if self.mlp is None:
             self.elbo()
             return
@@ -721,6 +776,9 @@ class MinibatchEngine:
         if not engine_kw.pop("is_whiten", True):
             raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
                                       "the eager path (Trainer_SP), on one rank")
+        if engine_kw.get("mean") is not None:
+            raise NotImplementedError("the '%s' mean function has no minibatch engine: full batch on one rank only (ElboEngine), "
+                                      "or the eager loop" % engine_kw["mean"][0])
         if engine_kw.get("likelihood") == "warped":
             raise NotImplementedError("the warped likelihood has no minibatch engine: full batch on one rank only (ElboEngine)")
         self.device = torch.device(device)

@@ -71,6 +71,9 @@ def main(argv=None):
     ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs")
+    ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
+                    help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
+                         "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP, gaussian or bernoulli)")
     ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
                     help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
                          "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
@@ -92,6 +95,8 @@ def main(argv=None):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
         ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
+    if args.mean != "zero" and (wgp or multi or args.model == "ID_TGP"):
+        ap.error("--mean %s: SVGP or TGP with the gaussian or bernoulli likelihood only" % args.mean)
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
         ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
@@ -147,7 +152,7 @@ def main(argv=None):
     K = instance_kernel("scale_rbf", ard_num_dim=Dx, num_multioutput=Dy, kernel_is_shared=False,
                         init_params={"length_scale": 2.0, "kernel_scale": 2.0, "noisy_variance": 1e-6})
     ip = {"variational_distribution": {"variance_scale": 1e-5, "mean_scale": 0.0}}
-    common = dict(model_specs=["zero", K], X=dc["X_tr"], init_Z=init_Z, N=dc["N_tr"], likelihood=lik, num_outputs=Dy,
+    common = dict(model_specs=[args.mean, K], X=dc["X_tr"], init_Z=init_Z, N=dc["N_tr"], likelihood=lik, num_outputs=Dy,
                   is_whiten=bool(args.whiten), K_is_shared=False, mean_is_shared=False, Z_is_shared=False, q_U_is_shared=False,
                   add_noise_inducing=0.0, init_params=ip)
     if args.model == "SVGP" or wgp:

@@ -10,8 +10,9 @@ What differs is underneath: every number is produced by the HIP kernels of libtg
 blocked Cholesky, hand-derived adjoints, the MLP kernel for the input-dependent flows' networks in training AND in
 every evaluation method).  There is NO CPU fallback: calling these methods with CPU tensors
 raises (the oracle in oracle/ is the CPU restatement, and it is test infrastructure only).
-Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs), zero mean, 'scale_rbf' /
-'scale_matern32' kernel, float64.  Both q(u) parameterisations: with is_whiten=False the parameters (m, L_q) describe
+Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs), 'scale_rbf' / 'scale_matern32' kernel,
+float64.  Mean functions 'zero', 'linear' and 'identity' (means.py; a non-zero mean with the multi-class, warped and
+input-dependent models raises NotImplementedError).  Both q(u) parameterisations: with is_whiten=False the parameters (m, L_q) describe
 q(u) = N(m, L_q L_q^T) and every method runs the whitened kernels at m_w = L^-1 m, Lam_w = L^-1 tril(L_q) (tgp_unwhiten_f64).
 """
 from typing import List
@@ -23,6 +24,7 @@ import torch.nn as nn
 from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
+from .means import MEAN_NAMES, ZeroMean, return_mean, return_projection_matrix
 from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical,
                           WarpedGaussianLinearMean)
 from .utils import positive_transform
@@ -38,11 +40,6 @@ class CholeskyVariationalDistribution(nn.Module):
         self.variational_mean = nn.Parameter(torch.zeros(*batch_shape, num_inducing_points, dtype=cg.dtype))
         eye = torch.eye(num_inducing_points, dtype=cg.dtype).repeat(*batch_shape, 1, 1)
         self.chol_variational_covar = nn.Parameter(eye)
-
-
-class ZeroMean(nn.Module):
-    def forward(self, x):
-        return torch.zeros(x.shape[:-1], dtype=x.dtype, device=x.device)
 
 
 def enable_eval_dropout(modules):
@@ -67,8 +64,10 @@ class sparse_MF_SP(nn.Module):
             "this build implements the single-output path (Dy = 1, every BASELINE config)"
         assert not isinstance(likelihood, MulticlassCategorical) or int(num_outputs) == likelihood.C, \
             "MulticlassCategorical needs num_outputs = its number of classes"
-        assert model_specs[0] == "zero", "only the 'zero' mean function (main.py) is provided"
-        assert not (K_is_shared or mean_is_shared or Z_is_shared or q_U_is_shared), "sharing flags are False in main.py"
+        assert model_specs[0] in MEAN_NAMES, "mean function must be one of %s, got %r" % (", ".join(MEAN_NAMES), model_specs[0])
+        assert not (K_is_shared or Z_is_shared or q_U_is_shared), "sharing flags are False in main.py"
+        assert not mean_is_shared or model_specs[0] == "linear", \
+            "mean_is_shared = True only with Linear mean function, got {}".format(model_specs[0])
         self.out_dim = int(num_outputs)
         self.inp_dim = int(init_Z.size(1))
         self.kernel_is_shared, self.mean_is_shared = K_is_shared, mean_is_shared
@@ -103,7 +102,6 @@ class sparse_MF_SP(nn.Module):
         q_U.chol_variational_covar.data = torch.eye(self.M, dtype=cg.dtype).view(1, self.M, self.M).repeat(self.out_dim, 1, 1) * numpy.sqrt(vs)
         q_U.variational_mean.data = torch.ones(self.out_dim, self.M, dtype=cg.dtype) * ms
         self.q_U = q_U
-        self.mean_function = ZeroMean()
         self.covariance_function = model_specs[1]
         # flows (sparse_MF_SP.py:232-266)
         assert flow_connection == "single", "flow_connection must be 'single'"
@@ -113,6 +111,16 @@ class sparse_MF_SP(nn.Module):
             G.append(instance_flow(fl) if isinstance(fl, list) else fl)
         self.G_matrix = nn.ModuleList(G)
         self.G_flow_connection = flow_connection
+        # mean function (sparse_MF_SP.py:184-206); mean_is_shared: one mean for all outputs, at Dy = 1 the same object
+        name = model_specs[0]
+        if name != "zero":
+            what = ("the multi-class model" if self._is_multiclass else "the warped likelihood" if self._is_warped else
+                    "input-dependent flows (ID_TGP)" if any(getattr(fl, "input_dependent", False) for g in self.G_matrix
+                                                             for fl in getattr(g, "flow_arr", [])) else None)
+            if what is not None:
+                raise NotImplementedError("the '%s' mean function is not built for %s: use the 'zero' mean" % (name, what))
+        W = return_projection_matrix(self.inp_dim, self.out_dim, X.reshape(-1, self.inp_dim)) if name == "identity" else None
+        self.mean_function = return_mean(name, self.inp_dim, 1 if mean_is_shared else self.out_dim, W)
         self.l2_regularize = False
         self._cfg = {}
 
@@ -131,6 +139,10 @@ class sparse_MF_SP(nn.Module):
         if t.dtype != torch.float64:
             raise ops.L.TgpError("float64 only: call config.set_maximum_precission() before building the model "
                                  "(code/main.py:124)")
+
+    @property
+    def _has_mean(self):
+        return not isinstance(self.mean_function, ZeroMean)
 
     @property
     def _is_bernoulli(self):
@@ -158,6 +170,14 @@ class sparse_MF_SP(nn.Module):
         kern = self.covariance_function.hip_kernel
         if ladder is None and cg.global_jitter is not None:      # config.global_jitter: the ladder's base, as for the step
             ladder = ops.jitter_ladder(jitter=cg.global_jitter)
+        if self._has_mean:
+            # m - m(Z): the mean of q(u) against the prior mean m(Z) (sparse_MF_SP.py:359) -- and the KL against
+            # p(u) = N(m(Z), K_ZZ) (:446) depends on m - m(Z) only, so the same transform serves it.  The gradient reaches the
+            # mean's parameters and Z through MeanFunction on Z (tgp_mean_backward_f64's g_X).
+            if torch.is_grad_enabled():
+                m = m - self.mean_function.vector(Z)
+            else:
+                m = self.mean_function.vector(Z, alpha=-1.0, inp=m.detach().contiguous())
         if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lq)):
             m_w, Lam_w = ops.UnwhitenFunction.apply(Z, rl, ro, m, Lq, kern, float(jitter), ladder, info)
         else:
@@ -265,9 +285,14 @@ class sparse_MF_SP(nn.Module):
             if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
                 raise NotImplementedError("the full covariance (diagonal=False) has no backward: call it under torch.no_grad(); "
                                           "diagonal=True is the differentiable path")
+            if self._has_mean and torch.is_grad_enabled() and any(q.requires_grad for q in self.mean_function.parameters()):
+                raise NotImplementedError("the full covariance (diagonal=False) has no backward: call it under torch.no_grad(); "
+                                          "diagonal=True is the differentiable path")
             # (unwhitened: the factor behind Sigma starts at the jitter the transform ended with; whitened: 0)
             mu, cov = ops.qf_cov(X2.detach(), *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
                                  kernel=self.covariance_function.hip_kernel)
+            if self._has_mean:       # mu + m(X) (sparse_MF_SP.py:355,360), in place
+                mu = self.mean_function.vector(X2.detach(), inp=mu).detach()
             return mu.reshape(1, -1, 1), cov.unsqueeze(0)
         if self._is_multiclass:
             mu, v = self._qf_per_class(X2)
@@ -281,6 +306,11 @@ class sparse_MF_SP(nn.Module):
         else:
             mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
                                    kernel=self.covariance_function.hip_kernel)
+        if self._has_mean:           # mu + m(X) (sparse_MF_SP.py:355,360): every method downstream of (mu, v) gets it from here
+            if torch.is_grad_enabled() and (mu.requires_grad or any(q.requires_grad for q in self.mean_function.parameters())):
+                mu = mu + self.mean_function.vector(X2.detach())
+            else:
+                mu = self.mean_function.vector(X2.detach(), inp=mu)
         return mu.reshape(1, -1, 1), v.reshape(1, -1, 1)
 
     def _kld_unwhitened(self, c=None):
@@ -328,7 +358,20 @@ class sparse_MF_SP(nn.Module):
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
-                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else (ops.L.LIK_WARPED if self._is_warped else None))
+                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else (ops.L.LIK_WARPED if self._is_warped else None),
+                   grad_Y=False)
+        if self._has_mean:
+            if spec is None:
+                # Gaussian likelihood: the unchanged closed-form step on Y - m(X); the step hands back the targets' adjoint
+                # -scale e^-eta (Y - m(X) - mu), which MeanFunction (alpha = -1) turns into the mean's
+                Y = self.mean_function.vector(X2, alpha=-1.0, inp=Y.detach().reshape(-1).contiguous()).reshape(-1, 1)
+                cfg["grad_Y"] = True
+            else:
+                # flow likelihoods: a per-row affine block (a_n, b_n) = (1, m(x_n)) at the head of the program turns G(f) into
+                # G(f + m(x_n)); the step's g_rowp[:, 1] is dELBO/dm(x_n)
+                rowp = self.mean_function.rowp(X2)
+                spec = ops.FlowSpec([(ops.L.FLOW_AFFINE, 0, 0, ops.L.FLAG_PER_ROW)] + list(spec.blocks), spec.P, 2, X2.device)
+                cfg["flow"] = spec
         if not self.is_whiten:
             # the step's likelihood term at (m_w, Lam_w) and the jitter their factor was formed with (0 unless the ladder
             # raised it), its own KL switched off; the KL against the reference's jittered prior is added apart

@@ -257,16 +257,26 @@ def _step_kwargs(cfg):
                 kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"), jitter=cfg.get("jitter", 0.0))
 
 
-def _step_save(ctx, grads, params):
+def _step_save(ctx, grads, params, g_Y=None):
     ctx.grads = grads
     ctx.shapes = tuple(None if t is None else t.shape for t in params)
+    ctx.g_Y = g_Y
+
+
+def _gauss_target_adjoint(cfg, Y, lvn, mu):
+    """d ELL / d Y of the Gaussian likelihood's closed form, -scale e^-eta (Y - mu), shape of Y: what the residual route of a
+    mean function (the step runs on Y - m(X), cfg["grad_Y"]) sends back to m(X) with the sign turned."""
+    if cfg.get("flow") is not None or cfg.get("lik") is not None:
+        raise L.TgpError("grad_Y: the adjoint of the targets exists for the Gaussian likelihood's closed form only")
+    scale = float(cfg["N_total"]) / float(cfg.get("mb_global") or Y.shape[0])
+    return (mu - Y.detach().reshape(-1)).mul_(scale * torch.exp(-lvn.detach().reshape(-1)[0])).reshape(Y.shape)
 
 
 def _step_backward(ctx, g_out):
     """The saved gradients of a step times the cotangent of its differentiable output, one per argument of forward."""
     res = tuple(None if shp is None or k not in ctx.grads else (ctx.grads[k] * g_out).reshape(shp)
                 for k, shp in zip(_STEP_PARAMS, ctx.shapes))
-    return (None, None) + res + (None,)
+    return (None, None if ctx.g_Y is None else ctx.g_Y * g_out) + res + (None,)
 
 
 class ElboFunction(torch.autograd.Function):
@@ -279,8 +289,10 @@ class ElboFunction(torch.autograd.Function):
         step, kw = elbo_step, _step_kwargs(cfg)
         if cfg.get("check_status", True):
             step, kw["global_jitter"] = elbo_step_safe, cfg.get("global_jitter")
-        out, g, status, _ = step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp, **kw)
-        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
+        want_gy = bool(cfg.get("grad_Y"))
+        out, g, status, (mu, _) = step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp,
+                                       want_moments=want_gy, **kw)
+        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp), _gauss_target_adjoint(cfg, Y, lvn, mu) if want_gy else None)
         cfg["last_status"] = status
         elbo, ell, kld = out[0].clone(), out[1].clone(), out[2].clone()
         ctx.mark_non_differentiable(ell, kld)
@@ -544,16 +556,88 @@ class EllStepFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, Y, Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp, cfg):
         kw = dict(_step_kwargs(cfg), kl_scale=0.0)
-        out, g, status, _ = elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp, **kw)
+        want_gy = bool(cfg.get("grad_Y"))
+        out, g, status, (mu, _) = elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, cfg["N_total"], theta=theta, rowp=rowp,
+                                            want_moments=want_gy, **kw)
         cfg["last_status"] = status
         if cfg.get("check_status", True) and raise_for_status(status.cpu()):
             raise NotPSDError("K_MM not positive definite in the step at jitter %g (pivot %d)" % (kw["jitter"], int(status[0])))
-        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp))
+        _step_save(ctx, g, (Z, raw_ls, raw_os, m, Lam, lvn, theta, rowp), _gauss_target_adjoint(cfg, Y, lvn, mu) if want_gy else None)
         return out[1].clone()
 
     @staticmethod
     def backward(ctx, g_ell):
         return _step_backward(ctx, g_ell)
+
+
+# ---------------------------------------------------------------------------------------------------
+# mean functions (models/means.py): m(x) = x a + b on the rows of X, and its adjoint
+# ---------------------------------------------------------------------------------------------------
+def mean_forward(X, a, b=None, alpha=1.0, inp=None, out=None, col=0, one_col=-1):
+    """out[:, col] = alpha (X a + b) + inp (tgp_mean_forward_f64); b None counts as 0, inp None as 0; one_col >= 0 also writes 1.0
+    to out[:, one_col].  `out` None: a fresh (N,) vector, or with one_col >= 0 a fresh (N, 2) tensor; otherwise a contiguous
+    (N,) or (N, ld) tensor of which no other column is touched.  Returns out."""
+    lib = L.load()
+    X, a, b, inp = _c(X, "X"), _c(a.reshape(-1), "a"), _c(None if b is None else b.reshape(-1), "b"), _c(inp, "in")
+    N, D = X.shape
+    if a.numel() != D or (b is not None and b.numel() != 1) or (inp is not None and inp.numel() != N):
+        raise ValueError("mean_forward: X (N, D), a (D), b (1), in (N)")
+    if out is None:
+        out = torch.empty((N, 2) if one_col >= 0 else (N,), dtype=torch.float64, device=X.device)
+    if out.dtype != torch.float64 or not out.is_contiguous() or out.shape[0] != N or out.dim() > 2:
+        raise ValueError("mean_forward: out must be a contiguous float64 (N,) or (N, ld) tensor")
+    ld = out.shape[1] if out.dim() == 2 else 1
+    L.check(lib.tgp_mean_forward_f64(L.ptr(X), N, D, L.ptr(a), L.ptr(b), float(alpha), L.ptr(inp), L.ptr(out), ld, int(col),
+                                     int(one_col), L.stream_ptr()), "tgp_mean_forward_f64")
+    return out
+
+
+def mean_backward(X, g, a=None, col=0, want_b=True, want_X=False):
+    """(g_a (D), g_b (1) or None, g_X (N, D) or None) = (X^T g_n, sum g_n, g_n a^T) with g_n = g[n] or g[n, col], read in place
+    (tgp_mean_backward_f64).  Fixed summation order: two calls give the same bits."""
+    lib = L.load()
+    X, g, a = _c(X, "X"), _c(g, "g"), _c(None if a is None else a.reshape(-1), "a")
+    N, D = X.shape
+    if g.shape[0] != N or g.dim() > 2 or (want_X and (a is None or a.numel() != D)):
+        raise ValueError("mean_backward: X (N, D), g (N) or (N, ld), a (D) when g_X is wanted")
+    ldg = g.shape[1] if g.dim() == 2 else 1
+    dev = X.device
+    nbytes = lib.tgp_mean_backward_workspace_bytes(N, D)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    g_a = torch.empty(D, dtype=torch.float64, device=dev)
+    g_b = torch.empty(1, dtype=torch.float64, device=dev) if want_b else None
+    g_X = torch.empty(N, D, dtype=torch.float64, device=dev) if want_X else None
+    L.check(lib.tgp_mean_backward_f64(L.ptr(X), N, D, L.ptr(a), L.ptr(g), ldg, int(col), L.ptr(g_a), L.ptr(g_b), L.ptr(g_X),
+                                      L.ptr(ws), nbytes, L.stream_ptr()), "tgp_mean_backward_f64")
+    return g_a, g_b, g_X
+
+
+class MeanFunction(torch.autograd.Function):
+    """m(X) = X a + b with autograd in a, b and (when it requires grad: the inducing points) X.  `rowp` True: the (N, 2) row
+    parameters (1, m(x_n)) of the per-row TGP_FLOW_AFFINE block that turns G(f) into G(f + m(x_n)); the backward reads column 1
+    of the incoming gradient in place (column 0, the adjoint of the constant 1, is ignored).  `rowp` False: the (N,) vector
+    alpha m(X) + inp (inp without gradient).  b None: no offset (identity mean)."""
+
+    @staticmethod
+    def forward(ctx, X, a, b, rowp, alpha, inp):
+        Xd, ad = X.detach(), a.detach()
+        out = mean_forward(Xd, ad, None if b is None else b.detach(), alpha=1.0 if rowp else alpha, inp=None if rowp else inp,
+                           col=1 if rowp else 0, one_col=0 if rowp else -1)
+        ctx.save_for_backward(Xd, ad)
+        ctx.cfg = (bool(rowp), float(alpha), a.shape, None if b is None else b.shape, X.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        X, a = ctx.saved_tensors
+        rowp, alpha, a_shape, b_shape, X_shape = ctx.cfg
+        if not rowp and alpha != 1.0:
+            g = g * alpha
+        g_a, g_b, g_X = mean_backward(X, g.contiguous(), a, col=1 if rowp else 0, want_b=b_shape is not None and ctx.needs_input_grad[2],
+                                      want_X=ctx.needs_input_grad[0])
+        return (None if g_X is None else g_X.reshape(X_shape), g_a.reshape(a_shape) if ctx.needs_input_grad[1] else None,
+                None if g_b is None else g_b.reshape(b_shape), None, None, None)
+
 
 
 def kernel_matrix(X1, X2, raw_ls, raw_os, kernel="scale_rbf", jitter=0.0):

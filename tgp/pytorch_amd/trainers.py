@@ -133,6 +133,9 @@ class Trainer_SP_regression:
         # trainer_base.py:155-179) or leaves some to a later stage must take the torch optimiser
         if {id(q) for g in groups for q in g["params"]} != {id(q) for q in model.parameters()}:
             return None
+        mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
+        if mean_fn is not None and len(ld) != 1:     # a mean function's engine is full batch only: minibatches take the eager loop
+            return None
         nets, theta_list, blocks = [], [], None
         warped = isinstance(model.likelihood, WarpedGaussianLinearMean)
         if warped:
@@ -167,6 +170,11 @@ class Trainer_SP_regression:
                   jitter_ladder=cg.global_jitter if cg.global_jitter is not None else 1e-8)
         if warped:
             kw["likelihood"] = "warped"
+        if mean_fn is not None:
+            a, b = mean_fn._ab()
+            kw["mean"] = (mean_fn.name, a.detach(), None if b is None else b.detach())
+            if blocks is None:           # Gaussian likelihood: the engine's quadrature over the affine block alone, exact at any S >= 2
+                kw["S"] = None
         if len(ld) == 1:
             eng = ElboEngine(ld.X, ld.Y, params, float(model.N), device=ld.X.device, **kw)
         else:
@@ -185,6 +193,9 @@ class Trainer_SP_regression:
             model.likelihood.log_var_noise.data = fp.view("lvn").view_as(model.likelihood.log_var_noise)
             for i, p in enumerate(theta_list):
                 p.data = fp.view("theta")[i:i + 1].view_as(p)
+            if mean_fn is not None and mean_fn.name == "linear":
+                mean_fn.a.data = fp.view("mean_a").view_as(mean_fn.a)
+                mean_fn.b.data = fp.view("mean_b").view_as(mean_fn.b)
             o = 0
             for p in nn_params:
                 p.data = fp.view("nn")[o:o + p.numel()].view_as(p)
