@@ -157,8 +157,13 @@ def test_abi_constants():
 def test_trainer_and_model_surface():
     from tgp.pytorch_amd import trainers
     assert issubclass(trainers.Trainer_SP_classification, trainers.Trainer_SP_regression)
-    for m in ("compute_metrics", "performance_metrics", "_engine_for"):
+    for m in ("compute_metrics", "performance_metrics"):
         assert m in trainers.Trainer_SP_classification.__dict__
+    # the resident engine is kept off Bernoulli models by the engines' one statement of coverage, which the inherited
+    # _engine_for consults -- not by an override with a list of its own
+    from tgp.pytorch_amd.engine import engine_refusal
+    assert trainers.Trainer_SP_classification._engine_for is trainers.Trainer_SP_regression._engine_for
+    assert "Bernoulli" in engine_refusal(likelihood="bernoulli") and "multi-class" in engine_refusal(likelihood="multiclass")
 
 
 @pytest.mark.parametrize("name,shape", [("heart", (299, 12)), ("banknote", (1372, 4))])

@@ -15,13 +15,12 @@ sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
 
-def _engine(N, D, M, flow, seed, stream=None):
-    from tgp.pytorch_amd import ops, synthetic
+def _engine(N, D, M, flow, seed, stream=None, S=32, **kw):
+    from tgp.pytorch_amd import synthetic
     from tgp.pytorch_amd.engine import ElboEngine
-    prob = synthetic.synthetic_problem(N, D, M, seed=seed, flow=flow, S=32)
-    ops._ws_cache.clear()
-    return ElboEngine(prob["X"], prob["Y"], prob["params"], N_total=float(N), flow_blocks=prob["program"], S=32,
-                      rowp=prob["rowp"], device=torch.device("cuda:0"))
+    prob = synthetic.synthetic_problem(N, D, M, seed=seed, flow=flow, S=S)
+    return ElboEngine(prob["X"], prob["Y"], prob["params"], N_total=float(N), flow_blocks=prob["program"], S=S,
+                      rowp=prob["rowp"], device=torch.device("cuda:0"), **kw)
 
 
 @pytest.mark.parametrize("flow,M,D", [("tanh3x2", 100, 4), ("idsal3", 100, 4), (None, 100, 4),
@@ -67,6 +66,54 @@ def test_two_engines_on_two_streams():
         st = e.status.cpu().tolist()
         assert st[0] == 0 and st[4:] == [0, 0, 0, 0], st
     assert dt < 0.5, "2 x 30 concurrent steps took %.2f s" % dt
+
+
+@pytest.mark.parametrize("N,M", [(300, 20),       # fused path, MT = 2, more than one row block
+                                 (200, 150)])     # general-M path (M > 128)
+def test_an_engine_owns_its_workspace(N, M):
+    """Two live engines of one shape, built on one stream: a step of B between the phases of A's step must not reach A's
+    intermediates (B's prepare used to overwrite A's L in the cached workspace both held).  No concurrency, no timing: A's
+    gradients and scalars are those of a solo engine of A's seed, bit for bit; and the same with the roles swapped."""
+    def solo(seed):
+        e = _engine(N, 3, M, "sal2", seed, S=8)
+        e.elbo(1)
+        e.elbo(6)
+        torch.cuda.synchronize()
+        return e.fp.grad.clone()
+    ref = {seed: solo(seed) for seed in (11, 12)}
+    for a, b in ((11, 12), (12, 11)):
+        A, B = _engine(N, 3, M, "sal2", a, S=8), _engine(N, 3, M, "sal2", b, S=8)
+        assert A.ws.data_ptr() != B.ws.data_ptr()
+        A.elbo(1)
+        B.step()
+        A.elbo(6)
+        torch.cuda.synchronize()
+        n = A.fp.n
+        assert torch.equal(A.fp.grad[:n], ref[a][:n]), "gradients of seed %d with seed %d stepped in between" % (a, b)
+        assert torch.equal(A.fp.out, ref[a][n:]), "scalars of seed %d with seed %d stepped in between" % (a, b)
+        assert A.status.cpu().tolist()[4:] == [0, 0, 0, 0] and B.status.cpu().tolist()[4:] == [0, 0, 0, 0]
+
+
+def test_environment_variables_do_not_reach_the_engine(monkeypatch):
+    """The engine's switches are arguments: the variables it used to read change nothing, fused_adam=False is how Adam becomes a
+    launch of its own, and that engine's three steps equal the fused engine's (1e-13 relative, as in the test below)."""
+    monkeypatch.setenv("TGP_FUSED_ADAM", "0")
+    monkeypatch.setenv("TGP_GRAPH_UNROLL", "3")
+    monkeypatch.setenv("TGP_COLLECTIVE", "abi")
+    a = _engine(300, 3, 20, "sal2", seed=5, S=8)
+    assert a.fused_adam and a.collective_info["collective"] == "torch" and a.comm is None
+    b = _engine(300, 3, 20, "sal2", seed=5, S=8, fused_adam=False)
+    assert not b.fused_adam
+    for e in (a, b):
+        for _ in range(3):
+            e.step()
+    torch.cuda.synchronize()
+    for x, y, what in ((a.fp.data, b.fp.data, "parameters"), (a.fp.exp_avg, b.fp.exp_avg, "exp_avg"),
+                       (a.fp.exp_avg_sq, b.fp.exp_avg_sq, "exp_avg_sq"), (a.fp.out[:3], b.fp.out[:3], "scalars")):
+        err = float((x - y).abs().max() / (y.abs().max() + 1e-300))
+        assert err < 1e-13, (what, err)
+    a.capture()
+    assert a.unroll == 10 and a.gU is not None
 
 
 @pytest.mark.parametrize("N,D,M,flow", [(2153, 13, 128, "sal2"),      # 1 792 assembly items, 1 815 parameters outside Lam: the loops

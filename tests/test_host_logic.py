@@ -274,6 +274,65 @@ def test_rccl_comm_without_a_carrier_for_the_id_raises_instead_of_hanging():
         RcclComm(world_size=2, rank=1)
 
 
+# engine.engine_refusal: (description, word the message must carry) for everything the engines refuse ...
+ENGINE_REFUSES = [(dict(is_whiten=False), "is_whiten=True"),
+                  (dict(is_whiten=False, world_size=2), "is_whiten=True"),
+                  (dict(is_whiten=False, minibatch=True), "is_whiten=True"),
+                  (dict(likelihood="bernoulli"), "Bernoulli"),
+                  (dict(likelihood="bernoulli", minibatch=True), "Bernoulli"),
+                  (dict(likelihood="multiclass"), "multi-class"),
+                  (dict(likelihood="multiclass", minibatch=True), "multi-class"),
+                  (dict(likelihood="warped", world_size=2), "warped"),
+                  (dict(likelihood="warped", collective="abi"), "warped"),
+                  (dict(likelihood="warped", per_row=True), "warped"),
+                  (dict(likelihood="warped", minibatch=True), "warped.*minibatch")]
+ENGINE_REFUSES += [case for mean in ("linear", "identity") for case in (
+    (dict(mean=mean, world_size=2), "'%s' mean function.*single-rank" % mean),
+    (dict(mean=mean, collective="torch"), "'%s' mean function.*single-rank" % mean),
+    (dict(mean=mean, likelihood="warped"), "'%s' mean function.*warped" % mean),
+    (dict(mean=mean, per_row=True), "'%s' mean function.*input-dependent" % mean),
+    (dict(mean=mean, minibatch=True), "'%s' mean function.*minibatch" % mean))]
+# ... and what they accept: every remaining combination of one or no feature with one or more ranks, full batch or minibatches
+ENGINE_ACCEPTS = [dict(), dict(per_row=True), dict(minibatch=True), dict(minibatch=True, per_row=True),
+                  dict(world_size=8), dict(world_size=8, collective="abi"), dict(world_size=1, collective="abi"),
+                  dict(world_size=8, per_row=True), dict(world_size=2, minibatch=True), dict(world_size=2, minibatch=True, per_row=True),
+                  dict(likelihood="warped"), dict(mean="linear"), dict(mean="identity")]
+
+
+def test_engine_coverage_is_one_pure_function(monkeypatch):
+    """What the step engines cover is engine.engine_refusal: a message naming the feature for every combination they refuse,
+    None for every one they accept; and both engines raise it before they load the library (lib.load is made to fail here)."""
+    import re
+    from tgp.pytorch_amd import engine, lib
+    for kw, word in ENGINE_REFUSES:
+        msg = engine.engine_refusal(**kw)
+        assert msg is not None and re.search(word, msg), (kw, msg)
+    for kw in ENGINE_ACCEPTS:
+        assert engine.engine_refusal(**kw) is None, kw
+
+    def no_library(*a, **k):
+        raise AssertionError("the library was loaded before the refusal")
+    monkeypatch.setattr(lib, "load", no_library)
+    X, Y, spec = torch.zeros(8, 2), torch.zeros(8), ("linear", torch.zeros(2), torch.zeros(1))
+    for cls, args in ((engine.ElboEngine, (X, Y, {}, 8.0)), (engine.MinibatchEngine, (X, Y, {}, 8.0, 4))):
+        with pytest.raises(NotImplementedError, match="is_whiten=True"):
+            cls(*args, is_whiten=False)
+        with pytest.raises(NotImplementedError, match="Bernoulli"):
+            cls(*args, likelihood="bernoulli")
+        with pytest.raises(NotImplementedError, match="multi-class"):
+            cls(*args, likelihood="multiclass")
+        with pytest.raises(NotImplementedError, match="'linear' mean function.*warped|'linear' mean function.*minibatch"):
+            cls(*args, likelihood="warped", mean=spec)
+    with pytest.raises(NotImplementedError, match=re.escape(engine.engine_refusal(likelihood="warped", world_size=2))):
+        engine.ElboEngine(X, Y, {}, 8.0, likelihood="warped", world_size=2)
+    with pytest.raises(NotImplementedError, match=re.escape(engine.engine_refusal(mean="identity", per_row=True))):
+        engine.ElboEngine(X, Y, {}, 8.0, mean=("identity", torch.zeros(2), None), rowp=torch.zeros(8, 1))
+    with pytest.raises(NotImplementedError, match=re.escape(engine.engine_refusal(likelihood="warped", minibatch=True))):
+        engine.MinibatchEngine(X, Y, {}, 8.0, 4, likelihood="warped")
+    with pytest.raises(engine.RcclUnavailable):
+        engine.RcclComm(world_size=2, rank=1)
+
+
 def test_bench_expected_line_carries_what_it_is_built_from():
     import bench
     w = bench.WORKLOADS["tgp_power_tanh3x2"]

@@ -3,9 +3,11 @@ ELBO -> (-ELBO).backward() -> Adam.step()) with everything resident on the GPU.
 
 * every trainable tensor is a view into ONE flat float64 buffer (parameters, gradients, Adam moments),
   so the optimiser is a single launch and the multi-GPU exchange is a single all-reduce;
-* the C-ABI argument structs are built once (pointers never change), so one step is
+* the C-ABI model and gradient structs are built once (pointers never change), so one step is
   `tgp_elbo_step_adam_f64` = 4 kernel launches (M <= 128) with no host synchronisation, plus
   the MLP forward/backward launches for input-dependent flows;
+* an engine owns its workspace; what the engines cover is `engine_refusal`, the step sequence is
+  `ElboEngine._one_step`, and every switch is an argument (no environment variable is read here);
 * `capture()` records that sequence into a HIP graph (torch.cuda.CUDAGraph is only the stream/graph
   plumbing) and `replay()` re-launches it;
 * multi-GPU (one process per GPU): rows are sharded, every rank runs the same M x M work, and ONE
@@ -13,23 +15,59 @@ ELBO -> (-ELBO).backward() -> Adam.step()) with everything resident on the GPU.
   (SURVEY.md 8e); the KL gradient enters each rank with weight 1/world so the sum counts it once.
 """
 import ctypes as C
-
-import os
+import os.path
+import warnings
 
 import torch
+
+from . import lib as L
+from . import ops
 
 # Stream-capture mode of every graph this package records.  "thread_local", not torch's default "global": with an NCCL
 # (= RCCL) process group alive, its watchdog thread polls the events of earlier collectives with hipEventQuery, which the
 # global mode forbids while ANY stream of the process captures -- measured on this stack (ROCm 7.0 / RCCL 2.26,
 # tools/probes/rccl_smoke.py): the process dies with hipErrorStreamCaptureUnsupported; thread-local capture records the
 # same graph (collective included) and replays it.
-CAPTURE_MODE = os.environ.get("TGP_CAPTURE_MODE", "thread_local")   # the override exists to reproduce the failure
-
-from . import lib as L
-from . import ops
+CAPTURE_MODE = "thread_local"
 
 # "mean_a" / "mean_b": a linear mean function's parameters; "nn" (packed MLP weights) last: the weight-decay group
 ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "mean_a", "mean_b", "nn")
+
+
+def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, collective=None, per_row=False, minibatch=False):
+    """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
+    combination, else the message both refuse it with (_refuse) before they load the library or touch the device; the
+    trainers take the eager loop on a message.  A pure function of the description: `mean` = None / "linear" / "identity",
+    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "multiclass", `collective` as passed to the engine (asking
+    for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`)."""
+    multi_rank = int(world_size) > 1 or collective is not None
+    if not is_whiten:      # `params` of an unwhitened model describe q(u) itself; the captured step has no transform in it
+        return "the step engines need is_whiten=True: an unwhitened q(u) trains on the eager path (Trainer_SP), on one rank"
+    if likelihood == "bernoulli":
+        return "the step engines have no Bernoulli likelihood: it trains on the eager path (ops.ElboFunction)"
+    if likelihood == "multiclass":
+        return "the step engines have no multi-class likelihood: its C latent GPs train on the eager path's composed step"
+    if mean is not None:
+        if minibatch:
+            return "the '%s' mean function has no minibatch engine: full batch on one rank (ElboEngine), or the eager loop" % mean
+        if multi_rank:
+            return "the '%s' mean function's engine is single-rank (world_size = 1): no data-parallel step with a mean" % mean
+        if likelihood == "warped" or per_row:
+            return "the '%s' mean function is not built for the warped likelihood or input-dependent flows" % mean
+    if likelihood == "warped":
+        if minibatch:
+            return "the warped likelihood has no minibatch engine: full batch on one rank only (ElboEngine)"
+        if multi_rank:
+            return "the warped likelihood's engine is single-rank (world_size = 1): no data-parallel warped step"
+        if per_row:
+            return "the warped likelihood takes shared flow parameters only"
+    return None
+
+
+def _refuse(**description):
+    why = engine_refusal(**description)
+    if why is not None:
+        raise NotImplementedError(why)
 
 
 def allreduce_flat(grad, n, world_size, group=None):
@@ -81,18 +119,17 @@ class RcclComm:
     (tgp_last_error() in the message) instead of hanging -- the caller exits non-zero, nothing re-execs."""
 
     def __init__(self, world_size=1, rank=0, group=None, timeout_s=None, uid=None):
-        import ctypes as C
         import threading
         timeout_s = COMM_TIMEOUT_S if timeout_s is None else float(timeout_s)
         self.comm = None
-        self.lib = L.load()
         dist = torch.distributed
         multi = world_size > 1 and dist.is_initialized() and uid is None
         if world_size > 1 and not multi and uid is None:
             # (ADVICE r5) a hand-made world: nothing here can carry rank 0's id to the others, and ncclCommInitRank with an
-            # all-zero id never returns -- say so instead of hanging
+            # all-zero id never returns -- say so instead of hanging (and before the library is loaded: no build needed to test)
             raise RcclUnavailable("RcclComm(world_size=%d) needs torch.distributed initialised (the id travels through its "
                                   "object broadcast) or the 128-byte id of rank 0 passed as `uid`" % world_size)
+        self.lib = L.load()
         given = uid
         uid = (C.c_char * 128)()
         if given is not None:
@@ -238,7 +275,7 @@ class ElboEngine:
                  eps=1e-8, device="cuda:0", world_size=1, rank=0, mb_global=None, process_group=None,
                  kernel="scale_rbf", mlp=None, mlp_weights=None, nn_weight_decay=1e-5, mlp_training=True,
                  jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None,
-                 is_whiten=True, mean=None):
+                 is_whiten=True, mean=None, fused_adam=True):
         """`mean` = ("linear", a, b) or ("identity", W, None): m(x) = x a + b enters the step as a per-row affine block
         (a_n, b_n) = (1, m(x_n)) at the head of the flow program, G(f) -> G(f + m(x_n)).  Linear: a (D) and b (1) are segments
         of the flat buffer; a step is tgp_mean_forward_f64 -> the ELBO step (all phases) -> tgp_mean_backward_f64 from
@@ -246,105 +283,110 @@ class ElboEngine:
         parameters are written once.  With the Gaussian likelihood (flow_blocks None) the step runs TGP_LIK_FLOW over the
         otherwise empty program: Gauss-Hermite integrates the quadratic integrand exactly, so the result differs from the
         closed form by rounding only.  One rank, full batch.
+        `likelihood` = "warped": `flow_blocks` / theta describe T applied to the TARGETS (TGP_LIK_WARPED): pre-pass t = T(Y)
+        -> the Gaussian step on t -> post-pass (theta's gradient, log-Jacobian) -> one Adam launch, captured like the
+        others.  Full batch on one rank only.
         `mlp` (ops.MlpSpec) + `mlp_weights` (packed, nnets * weights_per_net): input-dependent flow (ID_TGP) whose
         per-row parameters come from the HIP MLP kernels inside the step; `nn_weight_decay` is the reference's Adam
         group for the 'NNets' parameters (main.py:276-288).  `share` = another ElboEngine of the same model whose flat
-        parameter / gradient / Adam buffers and step counter this one uses (two batch sizes of one training run)."""
-        if not is_whiten:
-            # `params` of an unwhitened model describe q(u) itself; the captured step (one rank or world_size > 1) has no
-            # transform in it
-            raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
-                                      "the eager path (Trainer_SP), on one rank")
-        self.mean = None
-        if mean is not None:
-            kind = mean[0]
-            if kind not in ("linear", "identity"):
-                raise ValueError("mean must be ('linear', a, b) or ('identity', W, None), got %r" % (kind,))
-            if int(world_size) > 1 or collective is not None:
-                raise NotImplementedError("the '%s' mean function's engine is single-rank (world_size = 1): a data-parallel "
-                                          "step with a mean is not implemented" % kind)
-            if likelihood == "warped" or mlp is not None or rowp is not None:
-                raise NotImplementedError("the '%s' mean function is not built for the warped likelihood or input-dependent "
-                                          "flows" % kind)
-            self.mean = kind
-            rowp = torch.zeros(X.shape[0], 2, dtype=torch.float64)
-            flow_blocks = [(L.FLOW_AFFINE, 0, 0, L.FLAG_PER_ROW)] + [tuple(b) for b in (flow_blocks or [])]
-            S = S if S else 8
+        parameter / gradient / Adam buffers, step counter and status words this one uses (two batch sizes of one training
+        run).  The workspace is never shared: every engine allocates its own, so that two live engines of one shape cannot read
+        each other's intermediates.  `fused_adam` False: Adam stays a launch of its own where the update could ride in the
+        backward launches.  What is refused, and why, is engine_refusal()."""
+        _refuse(is_whiten=is_whiten, mean=None if mean is None else mean[0], likelihood=likelihood, world_size=world_size,
+                collective=collective, per_row=mlp is not None or rowp is not None)
+        if likelihood not in (None, "warped"):
+            raise ValueError("likelihood must be None or 'warped'")
+        if mean is not None and mean[0] not in ("linear", "identity"):
+            raise ValueError("mean must be ('linear', a, b) or ('identity', W, None), got %r" % (mean[0],))
         self.lib = L.load()
         self.device = torch.device(device)
         self.world_size, self.rank, self.pg = int(world_size), int(rank), process_group
-        # `likelihood` = "warped": `flow_blocks` / theta describe T applied to the TARGETS (TGP_LIK_WARPED): pre-pass t = T(Y)
-        # -> the Gaussian step on t -> post-pass (theta's gradient, log-Jacobian) -> one Adam launch, captured like the
-        # others.  Full batch on one rank only.
-        if likelihood not in (None, "warped"):
-            raise ValueError("likelihood must be None or 'warped'")
-        self.warped = likelihood == "warped"
-        if self.warped:
-            if int(world_size) > 1 or collective is not None:
-                raise NotImplementedError("the warped likelihood's engine is single-rank (world_size = 1): a data-parallel "
-                                          "warped step is not implemented")
-            if rowp is not None or mlp is not None:
-                raise NotImplementedError("the warped likelihood takes shared flow parameters only")
-            flow_blocks = [] if flow_blocks is None else flow_blocks
-        # `collective`: "torch" (default) = torch.distributed.all_reduce between two graphs; "abi" = tgp_allreduce_f64 on the
-        # compute stream, INSIDE the captured step (one graph, U steps per launch like a single rank's) -- an RcclComm or
-        # the string (a communicator is then created here; torch.distributed only carries its 128-byte id).  With "abi" a
-        # 1-rank engine runs the collective too (sum over one rank): the path the GPU tests can reach on one GPU.
-        # Default (None / "auto"): with more than one rank over RCCL the engine builds the ABI communicator, reduces a seeded
-        # buffer through BOTH paths and keeps the ABI collective only if every rank saw the same sums (choose_collective,
-        # _selfcheck_collective); any other situation keeps torch.distributed.  `collective_info` records the decision.
-        collective = collective if collective is not None else os.environ.get("TGP_COLLECTIVE") or None
+        self.warped, self.mean = likelihood == "warped", None if mean is None else mean[0]
+        self.mlp, self.mlp_training, self.nn_wd = mlp, bool(mlp_training), float(nn_weight_decay)
+        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
+        if self.mean is not None:
+            rowp = torch.zeros(X.shape[0], 2, dtype=torch.float64)
+            flow_blocks = [(L.FLOW_AFFINE, 0, 0, L.FLAG_PER_ROW)] + [tuple(b) for b in (flow_blocks or [])]
+            S = S if S else 8
+        if self.warped and flow_blocks is None:
+            flow_blocks = []
+        self._open_collective(collective, comm_timeout_s)
+        self._flat_buffers(X, Y, params, rowp, mean, mlp_weights, share)
+        self._abi_structs(flow_blocks, S, float(N_total) / float(mb_global if mb_global is not None else self.N), kernel, plan,
+                          jitter_ladder)
+        self._feature_scratch(plan)
+        # One rank, shared flow parameters only: ELBO step + Adam in ONE C-ABI call (tgp_elbo_step_adam_f64: on the fused path the
+        # update rides in the last two backward launches -- one launch and one pass over the buffers less).  `fused_update` is the
+        # caller's choice (all the rotated ID_TGP unit goes by), `fused_adam` whether the WHOLE step is that one call.
+        self.fused_update = bool(fused_adam)
+        self.fused_adam = (self.fused_update and self.world_size == 1 and self.comm is None and self.mlp is None
+                           and self.mean is None)
+        self.pre_step = self.post_step = None   # callables launched (and captured) before / after the step: the minibatch gather
+        self.pipeline_steps = True      # ID_TGP, one rank: capture the rotated unit (see capture())
+        self._out = None                # redirected scalar output while the unrolled graph is being captured
+        self.unroll, self.gU, self.hist_u = 1, None, None           # steps per replay of self.gU (capture())
+        self.unroll_long, self.gL, self.hist_l = 1, None, None      # a longer unrolled graph for long runs (capture())
+        self.graph, self._side, self._warm, self._warned_jitter = None, None, False, 0
+
+    def _open_collective(self, collective, comm_timeout_s):
+        """`collective`: "torch" = torch.distributed.all_reduce between two graphs; "abi" = tgp_allreduce_f64 on the
+        compute stream, INSIDE the captured step (one graph, U steps per launch like a single rank's) -- an RcclComm or
+        the string (a communicator is then created here; torch.distributed only carries its 128-byte id).  With "abi" a
+        1-rank engine runs the collective too (sum over one rank): the path the GPU tests can reach on one GPU.
+        Default (None / "auto"): with more than one rank over RCCL the engine builds the ABI communicator, reduces a seeded
+        buffer through BOTH paths and keeps the ABI collective only if every rank saw the same sums (choose_collective,
+        _selfcheck_collective); any other situation keeps torch.distributed.  `collective_info` records the decision."""
         self.comm, self._own_comm = None, False
-        self.collective_info = {"collective": "torch", "selfcheck": "skipped", "why": "one rank"}
         if isinstance(collective, RcclComm):
             self.comm = collective
             self.collective_info = {"collective": "abi", "selfcheck": "skipped", "why": "communicator passed in"}
-        else:
-            backend = torch.distributed.get_backend(process_group) if torch.distributed.is_initialized() else None
-            cand, check = choose_collective(collective, self.world_size, backend)
-            self.collective_info = {"collective": cand, "selfcheck": "skipped",
-                                    "why": "requested" if collective in ("torch", "abi") else "backend %s, %d rank(s)" % (backend, self.world_size)}
-            if cand == "abi":
-                # (RCCL binds the communicator and the stream to the CURRENT device: make that this engine's)
-                with torch.cuda.device(self.device):
-                    # (the communicator spans the process group that carries its id, whatever `world_size` weights KL with)
-                    cw = torch.distributed.get_world_size(process_group) if torch.distributed.is_initialized() else self.world_size
-                    cr = torch.distributed.get_rank(process_group) if torch.distributed.is_initialized() else self.rank
-                    try:
-                        self.comm = RcclComm(cw, cr, process_group, timeout_s=comm_timeout_s)
-                        self._own_comm = True
-                    except RcclUnavailable as e:
-                        # every rank raised together (RcclComm's agreement step): with the automatic choice all of them
-                        # keep torch.distributed; an explicit "abi" request is an error
-                        if not check:
-                            raise
-                        import warnings
-                        warnings.warn("ABI collective unavailable (%s): keeping torch.distributed.all_reduce" % e)
-                        self.comm, self._own_comm = None, False
-                        self.collective_info.update(collective="torch", selfcheck="skipped", why="bootstrap failed: %s" % e)
-                    if check and self.comm is not None:
-                        ok, why = self._selfcheck_collective(process_group)
-                        self.collective_info.update(selfcheck="pass" if ok else "fail", why=why)
-                        if not ok:
-                            import warnings
-                            warnings.warn("tgp_allreduce_f64 failed its self-check (%s): keeping torch.distributed.all_reduce" % why)
-                            self.close()
-                            self.collective_info["collective"] = "torch"
+            return
+        dist, group = torch.distributed, self.pg
+        backend = dist.get_backend(group) if dist.is_initialized() else None
+        cand, check = choose_collective(collective, self.world_size, backend)
+        self.collective_info = {"collective": cand, "selfcheck": "skipped",
+                                "why": "requested" if collective in ("torch", "abi") else "backend %s, %d rank(s)" % (backend, self.world_size)}
+        if cand != "abi":
+            return
+        # (RCCL binds the communicator and the stream to the CURRENT device: make that this engine's)
+        with torch.cuda.device(self.device):
+            # (the communicator spans the process group that carries its id, whatever `world_size` weights KL with)
+            cw = dist.get_world_size(group) if dist.is_initialized() else self.world_size
+            cr = dist.get_rank(group) if dist.is_initialized() else self.rank
+            try:
+                self.comm, self._own_comm = RcclComm(cw, cr, group, timeout_s=comm_timeout_s), True
+            except RcclUnavailable as e:
+                # every rank raised together (RcclComm's agreement step): with the automatic choice all of them
+                # keep torch.distributed; an explicit "abi" request is an error
+                if not check:
+                    raise
+                warnings.warn("ABI collective unavailable (%s): keeping torch.distributed.all_reduce" % e)
+                self.collective_info.update(collective="torch", selfcheck="skipped", why="bootstrap failed: %s" % e)
+                return
+            if check:
+                ok, why = self._selfcheck_collective(group)
+                self.collective_info.update(selfcheck="pass" if ok else "fail", why=why)
+                if not ok:
+                    warnings.warn("tgp_allreduce_f64 failed its self-check (%s): keeping torch.distributed.all_reduce" % why)
+                    self.close()
+                    self.collective_info["collective"] = "torch"
+
+    def _flat_buffers(self, X, Y, params, rowp, mean, mlp_weights, share):
+        """The data; every trainable tensor as a segment of ONE flat buffer (`share`'s where given); step counter, status words."""
         self.X = X.to(self.device, torch.float64).contiguous()
         self.Y = Y.reshape(-1).to(self.device, torch.float64).contiguous()
         self.N, self.D = self.X.shape
         names = {"Z": "Z", "raw_ls": "raw_lengthscale", "raw_os": "raw_outputscale", "m": "m", "Lam": "Lam",
                  "lvn": "log_var_noise", "theta": "theta"}
         tensors = {k: params.get(v, params.get(k)) for k, v in names.items()}
-        self.mlp, self.mlp_training, self.nn_wd = mlp, bool(mlp_training), float(nn_weight_decay)
-        if mlp is not None:
+        for k in ("raw_ls", "raw_os", "lvn"):
+            tensors[k] = tensors[k].reshape(-1)
+        if self.mlp is not None:
             tensors["nn"] = mlp_weights.reshape(-1)
-            assert tensors["nn"].numel() == mlp.nnets * mlp.weights_per_net
+            assert tensors["nn"].numel() == self.mlp.nnets * self.mlp.weights_per_net
             assert rowp is None, "per-row parameters come from the MLPs"
-            rowp = torch.zeros(self.N, mlp.nnets, dtype=torch.float64)
-        tensors["raw_ls"] = tensors["raw_ls"].reshape(-1)
-        tensors["raw_os"] = tensors["raw_os"].reshape(-1)
-        tensors["lvn"] = tensors["lvn"].reshape(-1)
+            rowp = torch.zeros(self.N, self.mlp.nnets, dtype=torch.float64)
         self.mean_W = None
         if self.mean == "linear":
             tensors["mean_a"], tensors["mean_b"] = mean[1].detach().reshape(-1), mean[2].detach().reshape(-1)
@@ -354,22 +396,20 @@ class ElboEngine:
             assert self.mean_W.numel() == self.D
         self.fp = FlatParams(tensors, self.device) if share is None else share.fp
         self.M = self.fp.sizes["m"]
-        self.flow = None
-        self.S = int(S) if S else 1
-        P = self.fp.sizes.get("theta", 0)
+        # (with per-row networks the flat buffer's tail is their weights: an Adam group of its own -- weight decay, second stream)
+        self.n_plain = self.fp.offsets["nn"] if self.mlp is not None else self.fp.n
         self.rowp = rowp.to(self.device, torch.float64).contiguous() if rowp is not None else None
-        RP = self.rowp.shape[1] if self.rowp is not None else 0
-        if flow_blocks is not None:
-            self.flow = ops.FlowSpec(flow_blocks, P, RP, self.device)
         self.g_rowp = torch.zeros_like(self.rowp) if self.rowp is not None else None
-        self.lr, self.betas, self.eps = float(lr), betas, float(eps)
         self.step_dev = torch.zeros(2, dtype=torch.int32, device=self.device) if share is None else share.step_dev
         self.status = torch.zeros(8, dtype=torch.int32, device=self.device) if share is None else share.status
-        self.pre_step = None        # callables launched (and captured) before / after the step: the minibatch gather
-        self.post_step = None
-        mbg = mb_global if mb_global is not None else self.N
-        scale = float(N_total) / float(mbg)
+
+    def _abi_structs(self, flow_blocks, S, scale, kernel, plan, jitter_ladder):
+        """tgp_model and tgp_grads, built once: the pointers never change."""
         fp = self.fp
+        P = fp.sizes.get("theta", 0)
+        RP = self.rowp.shape[1] if self.rowp is not None else 0
+        self.S = int(S) if S else 1
+        self.flow = ops.FlowSpec(flow_blocks, P, RP, self.device) if flow_blocks is not None else None
         self.md, self._keep = ops._model_struct(self.X, fp.view("Z"), fp.view("raw_ls"), fp.view("raw_os"), fp.view("m"),
                                                 fp.view("Lam"), fp.view("lvn"), scale, 0.0, 1.0 / self.world_size,
                                                 self.flow, fp.view("theta") if P else None, self.S, kernel, plan,
@@ -377,7 +417,6 @@ class ElboEngine:
         # psd_safe_cholesky's retry ladder (dsp/utils.py:256-269) runs on the device inside the captured step (fused path);
         # `jitter_ladder` is its base value (the reference: 1e-8 in float64, or cg.global_jitter), 0 disables it
         self.md.jitter_ladder = float(jitter_ladder or 0.0)
-        self._warned_jitter = 0
         self.gs = L.TgpGrads()
         self.gs.Z, self.gs.raw_ls, self.gs.raw_os = (L.ptr(fp.gview(k)) for k in ("Z", "raw_ls", "raw_os"))
         self.gs.m, self.gs.Lam, self.gs.log_var_noise = (L.ptr(fp.gview(k)) for k in ("m", "Lam", "lvn"))
@@ -385,38 +424,21 @@ class ElboEngine:
             self.gs.theta = L.ptr(fp.gview("theta"))
         if RP:
             self.gs.rowp = L.ptr(self.g_rowp)
-        self.ws = ops.workspace(self.N, self.D, self.M, self.md.S, self.md.nblk, self.md.P, self.md.RP, self.device,
-                                self.md.kernel, plan, self.md.lik)
-        self.mean_ws = None
+
+    def _feature_scratch(self, plan):
+        """Device scratch of this engine alone: the step's workspace (NOT ops.workspace()'s cached buffer, which every
+        one-shot ops.* call of the same shape on the same stream shares), the mean's and the MLPs' partial sums."""
+        md = self.md
+        self.ws = ops.new_workspace(self.N, self.D, self.M, md.S, md.nblk, md.P, md.RP, self.device, md.kernel, plan, md.lik)
+        self.mean_ws = self.mlp_ws = None
         if self.mean == "linear":
             self.mean_ws = torch.empty(max(self.lib.tgp_mean_backward_workspace_bytes(self.N, self.D), 8) // 8,
                                        dtype=torch.float64, device=self.device)
         elif self.mean == "identity":
             self.mean_forward()      # W is fixed: the rows' parameters are written once
-        self.mlp_ws = None
         if self.mlp is not None:
             d = self.mlp.struct(self.N, True)
             self.mlp_ws = torch.empty(self.lib.tgp_mlp_workspace_bytes(d) // 8 + 16, dtype=torch.float64, device=self.device)
-        # One rank, shared flow parameters only: ELBO step + Adam in ONE C-ABI call (tgp_elbo_step_adam_f64: on the fused
-        # path the update rides in the last two backward launches -- one launch and one pass over the buffers less)
-        self.fused_adam = (self.world_size == 1 and self.comm is None and self.mlp is None and self.mean is None
-                           and os.environ.get("TGP_FUSED_ADAM", "1") != "0")
-        self.ad = L.TgpAdamArgs()
-        self.ad.params, self.ad.grads = L.ptr(fp.data), L.ptr(fp.grad)
-        self.ad.exp_avg, self.ad.exp_avg_sq = L.ptr(fp.exp_avg), L.ptr(fp.exp_avg_sq)
-        # (with per-row networks the flat buffer's tail is their weights: a group of its own -- weight decay, second stream;
-        #  the call then updates the prefix only, from the rotated unit's backward phase)
-        self.ad.n = fp.offsets["nn"] if self.mlp is not None else fp.n
-        self.ad.step_dev, self.ad.maximize = L.ptr(self.step_dev), 1
-        self._side = None
-        self.pipeline_steps = True      # ID_TGP, one rank: capture the rotated unit (see capture())
-        self._out = None                # redirected scalar output while the unrolled graph is being captured
-        self.unroll = 1                 # steps per replay of self.gU (capture())
-        self.gU = None
-        self.hist_u = None
-        self.unroll_long, self.gL, self.hist_l = 1, None, None      # a longer unrolled graph for long runs (capture())
-        self.graph = None
-        self._warm = False
 
     def _selfcheck_collective(self, group, n=4099, seed=1234):
         """First contact with the node: the same seeded buffer (different on every rank) summed through tgp_allreduce_f64
@@ -447,7 +469,7 @@ class ElboEngine:
         except Exception:
             pass
 
-    # ---- one step, eager launches ------------------------------------------------------------------
+    # ---- the launches of a step --------------------------------------------------------------------
     def elbo(self, phases=7):
         out = self.fp.out if self._out is None else self._out      # (ELBO, ELL, KL) of this step: see capture(unroll)
         rc = self.lib.tgp_elbo_step_phases_f64(self.md, L.ptr(self.X), L.ptr(self.Y), L.ptr(self.rowp),
@@ -460,29 +482,33 @@ class ElboEngine:
         """forward_backward() + adam() as one call (fused_adam engines): same kernels' arithmetic, same results.
         `phases` != 0: only those phases (the update rides in the backward phase)."""
         out = self.fp.out if self._out is None else self._out
-        self.ad.lr, self.ad.beta1, self.ad.beta2, self.ad.eps = self.lr, self.betas[0], self.betas[1], self.eps
-        self.ad.phases = phases
+        ad = L.TgpAdamArgs(*self._adam_args(0, self.n_plain), L.ptr(self.step_dev), 1, phases)      # (maximize = 1)
         rc = self.lib.tgp_elbo_step_adam_f64(self.md, L.ptr(self.X), L.ptr(self.Y), L.ptr(self.rowp), L.ptr(out), self.gs,
-                                             None, None, L.ptr(self.status), L.ptr(self.ws), self.ws.numel() * 8, self.ad,
+                                             None, None, L.ptr(self.status), L.ptr(self.ws), self.ws.numel() * 8, ad,
                                              L.stream_ptr())
         L.check(rc, "tgp_elbo_step_adam_f64")
         self._warm = True
 
     def allreduce(self):
-        if self.comm is not None:
-            pre_reduce(self.fp.grad, self.fp.n, self.world_size)
-            with torch.cuda.device(self.device):
-                self.comm.allreduce(self.fp.grad, self.fp.n + self.fp.extra)
-            post_reduce(self.fp.grad, self.fp.n)
-            return
-        allreduce_flat(self.fp.grad, self.fp.n, self.world_size, self.pg)
+        """allreduce_flat(), through the ABI's collective on this stream where the engine has one (it sums over one rank too)."""
+        if self.comm is None:
+            return allreduce_flat(self.fp.grad, self.fp.n, self.world_size, self.pg)
+        pre_reduce(self.fp.grad, self.fp.n, self.world_size)
+        with torch.cuda.device(self.device):
+            self.comm.allreduce(self.fp.grad, self.fp.n + self.fp.extra)
+        post_reduce(self.fp.grad, self.fp.n)
+
+    def _adam_args(self, lo, hi):
+        """Segment [lo, hi) of the flat buffer as the leading arguments of every Adam entry point, which are also the
+        leading fields of tgp_adam_args: params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps."""
+        fp = self.fp
+        return (L.ptr(fp.data[lo:hi]), L.ptr(fp.grad[lo:hi]), L.ptr(fp.exp_avg[lo:hi]), L.ptr(fp.exp_avg_sq[lo:hi]), hi - lo,
+                self.lr, self.betas[0], self.betas[1], self.eps)
 
     def adam(self):
-        n_plain = self.fp.offsets["nn"] if self.mlp is not None else self.fp.n
-        rc = self.lib.tgp_adam_dev_groups_f64(L.ptr(self.fp.data), L.ptr(self.fp.grad), L.ptr(self.fp.exp_avg),
-                                              L.ptr(self.fp.exp_avg_sq), self.fp.n, self.lr, self.betas[0], self.betas[1],
-                                              self.eps, n_plain, self.nn_wd if self.mlp is not None else 0.0,
-                                              L.ptr(self.step_dev), 1, L.stream_ptr())
+        rc = self.lib.tgp_adam_dev_groups_f64(*self._adam_args(0, self.fp.n), self.n_plain,
+                                              self.nn_wd if self.mlp is not None else 0.0, L.ptr(self.step_dev), 1,
+                                              L.stream_ptr())
         L.check(rc, "tgp_adam_dev_groups_f64")
 
     def mean_forward(self):
@@ -519,22 +545,14 @@ class ElboEngine:
         reduces the weight gradients (tgp_mlp_backward_adam_f64): one launch less on the side chain of the rotated unit."""
         fp = self.fp
         lo, hi = fp.offsets["nn"], fp.n
-        ad = L.TgpAdamArgs()
-        ad.params, ad.grads = L.ptr(fp.data[lo:hi]), L.ptr(fp.grad[lo:hi])
-        ad.exp_avg, ad.exp_avg_sq = L.ptr(fp.exp_avg[lo:hi]), L.ptr(fp.exp_avg_sq[lo:hi])
-        ad.n = hi - lo
-        ad.lr, ad.beta1, ad.beta2, ad.eps = self.lr, self.betas[0], self.betas[1], self.eps
-        ad.step_dev, ad.maximize, ad.phases = L.ptr(step), 1, 0
+        ad = L.TgpAdamArgs(*self._adam_args(lo, hi), L.ptr(step), 1, 0)
         d = self.mlp.struct(self.N, self.mlp_training)
         L.check(self.lib.tgp_mlp_backward_adam_f64(d, L.ptr(self.X), L.ptr(fp.data[lo:hi]), L.ptr(step), L.ptr(self.g_rowp),
                                                    L.ptr(fp.grad[lo:hi]), L.ptr(self.mlp_ws), self.mlp_ws.numel() * 8, ad,
                                                    float(self.nn_wd), L.stream_ptr()), "tgp_mlp_backward_adam_f64")
 
     def _adam_segment(self, lo, hi, weight_decay, step):
-        fp = self.fp
-        rc = self.lib.tgp_adam_dev_f64(L.ptr(fp.data[lo:hi]), L.ptr(fp.grad[lo:hi]), L.ptr(fp.exp_avg[lo:hi]),
-                                       L.ptr(fp.exp_avg_sq[lo:hi]), hi - lo, self.lr, self.betas[0], self.betas[1], self.eps,
-                                       float(weight_decay), L.ptr(step), 1, L.stream_ptr())
+        rc = self.lib.tgp_adam_dev_f64(*self._adam_args(lo, hi), float(weight_decay), L.ptr(step), 1, L.stream_ptr())
         L.check(rc, "tgp_adam_dev_f64")
 
     def forward_backward(self):
@@ -551,125 +569,117 @@ class ElboEngine:
         if self.mlp is None:
             self.elbo()
             return
+        self._forked(lambda: self.elbo(1), self.mlp_forward)     # prepare
+        self.elbo(2)                                             # rows: consumes rowp, produces g_rowp
+        self._forked(lambda: self.elbo(4), self.mlp_backward)    # M x M adjoint + gradient assembly
+
+    def _forked(self, main_chain, side_chain):
+        """main_chain() on the current stream with side_chain() beside it on the side stream, joined at the end.  The main
+        chain is issued first: it is the longer one, and under graph replay ready nodes are dispatched in creation order --
+        see _rotated_unit()."""
         main = torch.cuda.current_stream()
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
-        side = self._side
-        # (the main chain of each fork is issued first: it is the longer one, and under graph replay ready nodes are
-        #  dispatched in creation order -- see capture())
         forked = torch.cuda.Event()
         forked.record(main)
-        self.elbo(1)                 # prepare
-        side.wait_event(forked)
-        with torch.cuda.stream(side):
-            self.mlp_forward()
-        main.wait_stream(side)
-        self.elbo(2)                 # rows: consumes rowp, produces g_rowp
-        forked = torch.cuda.Event()
-        forked.record(main)
-        self.elbo(4)                 # M x M adjoint + gradient assembly
-        side.wait_event(forked)
-        with torch.cuda.stream(side):
-            self.mlp_backward()
-        main.wait_stream(side)
+        main_chain()
+        self._side.wait_event(forked)
+        with torch.cuda.stream(self._side):
+            side_chain()
+        main.wait_stream(self._side)
 
-    def step(self):
-        if self.graph == "rotated":      # the captured unit straddles two steps: eager steps would repeat half of one
-            return self.replay()
+    # ---- THE step: pre -> (step_adam | forward_backward -> all-reduce -> adam) -> post, stated once, in two halves that meet
+    # at the all-reduce.  step(), the "full" and the unrolled graphs run _one_step(); "split" records the halves as two graphs.
+    def _to_the_reduce(self, split=False):
         if self.pre_step is not None:
             self.pre_step()
-        if self.fused_adam:
-            self.step_adam()
-        else:
-            self.forward_backward()
-            self.allreduce()
+        (self.step_adam if self.fused_adam else self.forward_backward)()     # step_adam: the whole step, update included
+        if split:
+            pre_reduce(self.fp.grad, self.fp.n, self.world_size)
+
+    def _from_the_reduce(self, split=False):
+        if split:
+            post_reduce(self.fp.grad, self.fp.n)
+        if not self.fused_adam:
             self.adam()
         if self.post_step is not None:
             self.post_step()
 
+    def _one_step(self):
+        self._to_the_reduce()
+        if not self.fused_adam:
+            self.allreduce()
+        self._from_the_reduce()
+
+    def step(self):
+        # ("rotated": the captured unit straddles two steps: eager steps would repeat half of one)
+        return self.replay() if self.graph == "rotated" else self._one_step()
+
     # ---- HIP graph ----------------------------------------------------------------------------------
-    def capture(self, with_allreduce=None, unroll=None):
+    def _graph_of(self, fn):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
+            fn()
+        return g
+
+    def capture(self, with_allreduce=None, unroll=None, unroll_long=None):
         """Capture one full step.  With world_size > 1 the all-reduce stays outside (two graphs) unless
-        with_allreduce=True."""
+        with_allreduce=True.  `unroll` / `unroll_long`: steps per launch of the unrolled graphs (_capture_unrolled)."""
         if not self._warm:
             self.forward_backward()          # first launch sets kernel attributes; must happen outside capture
         torch.cuda.synchronize()
-        pre = self.pre_step if self.pre_step is not None else (lambda: None)
-        post = self.post_step if self.post_step is not None else (lambda: None)
         if (self.mlp is not None and self.world_size == 1 and self.comm is None and self.pipeline_steps
                 and self.pre_step is None):
-            # Rotated unit.  The long pole of an ID_TGP step is the MLP backward (97 us), and nothing of step t depends on it
-            # except the network weights' own Adam update and the NEXT step's MLP forward.  So the captured unit starts
-            # at the row kernel:   main: rows(t) -> M x M adjoint(t) -> Adam(GP params) -> prepare(t+1)
-            #                      side:            MLP backward(t) -> Adam(network weights) -> MLP forward(t+1)
-            # joined at the end.  Same operations in the same per-step order as step(); prepare(0) and MLP forward(0)
-            # run here, eagerly, once.  Two device step counters (one per Adam group; the dropout masks follow the
-            # network group's) keep both launches graph-replayable.
-            n_plain = self.fp.offsets["nn"]
             self.step_nn = self.step_dev.clone()
-            self.elbo(1)
+            self.elbo(1)                     # prepare(0) and MLP forward(0) run here, eagerly, once
             self.mlp_forward(self.step_nn)
             torch.cuda.synchronize()
-            def unit():
-                main = torch.cuda.current_stream()
-                side = self._side
-                self.elbo(2)
-                # The main chain is issued BEFORE the side branch: graph replay dispatches ready nodes in creation order,
-                # and with the MLP backward (408 workgroups) created first the slab reduction that heads the critical
-                # chain found every CU taken (5 -> 12 us; the whole step 172 -> 150 us with this order).
-                forked = torch.cuda.Event()
-                forked.record(main)
-                if os.environ.get("TGP_FUSED_ADAM", "1") != "0":
-                    self.step_adam(4)            # M x M adjoint + gradient assembly + Adam on the GP / flow parameters
-                else:
-                    self.elbo(4)
-                    self._adam_segment(0, n_plain, 0.0, self.step_dev)
-                self.elbo(1)
-                side.wait_event(forked)
-                with torch.cuda.stream(side):
-                    if os.environ.get("TGP_FUSED_ADAM", "1") != "0":
-                        self.mlp_backward_adam(self.step_nn)     # backward + Adam on the network weights, one launch less
-                    else:
-                        self.mlp_backward(self.step_nn)
-                        self._adam_segment(n_plain, self.fp.n, self.nn_wd, self.step_nn)
-                    self.mlp_forward(self.step_nn)
-                main.wait_stream(side)
-            self.g1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g1, capture_error_mode=CAPTURE_MODE):
-                unit()
-            self._capture_unrolled(unit, unroll)
+            self.g1 = self._graph_of(self._rotated_unit)
+            self._capture_unrolled(self._rotated_unit, unroll, unroll_long)
             self.graph = "rotated"
-            return
-        if self.world_size > 1 and not with_allreduce and self.comm is None:
+        elif self.world_size > 1 and not with_allreduce and self.comm is None:
             # [graph 1: step kernels + KL pre-division] -> RCCL all-reduce -> [graph 2: ELBO fix-up + Adam]
-            self.g1, self.g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g1, capture_error_mode=CAPTURE_MODE):
-                pre()
-                self.forward_backward()
-                pre_reduce(self.fp.grad, self.fp.n, self.world_size)
-            with torch.cuda.graph(self.g2, capture_error_mode=CAPTURE_MODE):
-                post_reduce(self.fp.grad, self.fp.n)
-                self.adam()
-                post()
+            self.g1 = self._graph_of(lambda: self._to_the_reduce(split=True))
+            self.g2 = self._graph_of(lambda: self._from_the_reduce(split=True))
             self.graph = "split"
         else:
-            def unit():
-                pre()
-                if self.fused_adam:
-                    self.step_adam()
-                else:
-                    self.forward_backward()
-                    self.allreduce()
-                    self.adam()
-                post()
-            self.g1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g1, capture_error_mode=CAPTURE_MODE):
-                unit()
+            self.g1 = self._graph_of(self._one_step)
             if self.world_size == 1 or self.comm is not None:   # (the ABI's all-reduce is a node of the graph like any kernel)
-                self._capture_unrolled(unit, unroll)
+                self._capture_unrolled(self._one_step, unroll, unroll_long)
             self.graph = "full"
 
-    def _capture_unrolled(self, unit, unroll):
+    def _rotated_unit(self):
+        """ID_TGP on one rank: a different SCHEDULE of the step's operations, not a restatement of _one_step().  The long pole
+        of an ID_TGP step is the MLP backward (97 us), and nothing of step t depends on it except the network weights' own Adam
+        update and the NEXT step's MLP forward.  So the captured unit starts
+        at the row kernel:   main: rows(t) -> M x M adjoint(t) -> Adam(GP params) -> prepare(t+1)
+                             side:            MLP backward(t) -> Adam(network weights) -> MLP forward(t+1)
+        joined at the end.  Same operations in the same per-step order as _one_step(); capture() runs prepare(0) and MLP
+        forward(0).  Two device step counters (one per Adam group; the dropout masks follow the network group's) keep both
+        launches graph-replayable."""
+        self.elbo(2)
+
+        # The main chain is issued BEFORE the side branch: graph replay dispatches ready nodes in creation order,
+        # and with the MLP backward (408 workgroups) created first the slab reduction that heads the critical
+        # chain found every CU taken (5 -> 12 us; the whole step 172 -> 150 us with this order).
+        def main_chain():
+            if self.fused_update:
+                self.step_adam(4)            # M x M adjoint + gradient assembly + Adam on the GP / flow parameters
+            else:
+                self.elbo(4)
+                self._adam_segment(0, self.n_plain, 0.0, self.step_dev)
+            self.elbo(1)
+
+        def side_chain():
+            if self.fused_update:
+                self.mlp_backward_adam(self.step_nn)     # backward + Adam on the network weights, one launch less
+            else:
+                self.mlp_backward(self.step_nn)
+                self._adam_segment(self.n_plain, self.fp.n, self.nn_wd, self.step_nn)
+            self.mlp_forward(self.step_nn)
+        self._forked(main_chain, side_chain)
+
+    def _capture_unrolled(self, unit, unroll, unroll_long=None):
         """A second graph of U consecutive steps (one rank only).  Launching a graph costs ~5 us of idle GPU between two
         replays of the launch chain (14 us with the two-stream ID_TGP unit): U steps per launch pay it once (Power TGP
         129.5 -> 125 us per step at U = 8-10, ID_TGP 148 -> 141).  The same kernels in the same order: results are
@@ -678,7 +688,7 @@ class ElboEngine:
         With the default U (no explicit `unroll`) a THIRD graph of 4 U steps serves long runs (round 5, Power TGP at 96 us per
         step: 10 406 steps/s at 10 steps per launch, 10 470 at 40); replay_many uses the longest graph that still fits, so a
         20-step run is two replays of the U-step graph as before."""
-        U = int(unroll if unroll is not None else os.environ.get("TGP_GRAPH_UNROLL", "10"))
+        U = int(unroll if unroll is not None else 10)
         self.unroll, self.gU = 1, None
         self.unroll_long, self.gL, self.hist_l = 1, None, None
         if U < 2 or (unroll is None and self.M > 128):      # general-M steps take milliseconds: nothing to gain, ~100 nodes each
@@ -690,21 +700,21 @@ class ElboEngine:
 
         def capture_steps(nsteps):
             hist = torch.zeros(nsteps - 1, 4, dtype=torch.float64, device=self.device)
-            g = torch.cuda.CUDAGraph()
+
+            def steps():
+                for u in range(nsteps):
+                    self._out = hist[u] if (u < nsteps - 1 and not reduced) else None
+                    unit()
+                    if reduced and u < nsteps - 1:
+                        hist[u].copy_(self.fp.out)
             try:
-                with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
-                    for u in range(nsteps):
-                        self._out = hist[u] if (u < nsteps - 1 and not reduced) else None
-                        unit()
-                        if reduced and u < nsteps - 1:
-                            hist[u].copy_(self.fp.out)
+                return self._graph_of(steps), hist
             finally:
                 self._out = None        # a failed capture must not leave later steps writing their scalars into the history
-            return g, hist
 
         self.gU, self.hist_u = capture_steps(U)
         self.unroll = U
-        UL = int(os.environ.get("TGP_GRAPH_UNROLL_LONG", str(4 * U))) if unroll is None else 0
+        UL = int(unroll_long) if unroll_long is not None else (4 * U if unroll is None else 0)
         if UL > U and not reduced:
             self.gL, self.hist_l = capture_steps(UL)
             self.unroll_long = UL
@@ -727,10 +737,8 @@ class ElboEngine:
             k += 1
 
     def replay(self):
-        if self.graph in ("full", "rotated"):
-            self.g1.replay()
-        else:
-            self.g1.replay()
+        self.g1.replay()
+        if self.graph == "split":
             torch.distributed.all_reduce(self.fp.grad, op=torch.distributed.ReduceOp.SUM, group=self.pg)
             self.g2.replay()
 
@@ -738,16 +746,12 @@ class ElboEngine:
     def check_status(self):
         """Lazy Cholesky check (one sync): raises like the reference's psd_safe_cholesky would."""
         st = self.status.cpu()
-        if int(st[0]) == ops.STATUS_SYNC_TIMEOUT or int(st[3]):    # st[3]: sticky count, survives the later steps of a replayed graph
-            ops.raise_for_status(st)
-        if int(st[1]):
-            raise ops.NanError("cholesky: K_MM contains NaN")
+        failed = ops.raise_for_status(st)       # an expired hand-off wait (sticky across a replayed graph's steps), NaN in K_MM
         if int(st[2]) > self._warned_jitter:
-            import warnings
             self._warned_jitter = int(st[2])
             warnings.warn("A not p.d., added jitter of %g to the diagonal" % (self.md.jitter_ladder * 10 ** (int(st[2]) - 1)),
                           ops.NumericalWarning)
-        if int(st[0]):
+        if failed:
             raise ops.NotPSDError("K_MM not positive definite at pivot %d even with the largest jitter of the ladder "
                                   "(%g), like psd_safe_cholesky's final raise (dsp/utils.py:268-269)"
                                   % (int(st[0]), self.md.jitter_ladder * 100))
@@ -767,20 +771,16 @@ class MinibatchEngine:
     * X, Y stay on the device; one epoch's row order is an int32 index buffer written once per epoch (`set_order`);
     * a captured step = [tgp_gather_rows_f64: batch rows -> fixed batch buffers, device cursor advanced by the launch]
       -> the ElboEngine step (ELBO + backward + Adam) on those buffers;
-    * the ragged last batch of an epoch (N mod B rows) has its own engine + graph on the same flat parameter / Adam
-      buffers (the ELL scale N_total / MB follows the batch's own size, sparse_MF_SP.py:623-626);
+    * the ragged last batch of an epoch (N mod B rows) has its own engine + graph (and workspace) on the same flat
+      parameter / Adam buffers (the ELL scale N_total / MB follows the batch's own size, sparse_MF_SP.py:623-626);
     * the three logged scalars of every step are copied device-to-device into a history buffer; nothing syncs.
     With world_size > 1 each rank gathers and processes its row shard of every batch (one all-reduce per step)."""
 
     def __init__(self, X, Y, params, N_total, batch_size, device="cuda:0", world_size=1, rank=0, **engine_kw):
-        if not engine_kw.pop("is_whiten", True):
-            raise NotImplementedError("the step engines need is_whiten=True: an unwhitened q(u) (is_whiten=False) trains on "
-                                      "the eager path (Trainer_SP), on one rank")
-        if engine_kw.get("mean") is not None:
-            raise NotImplementedError("the '%s' mean function has no minibatch engine: full batch on one rank only (ElboEngine), "
-                                      "or the eager loop" % engine_kw["mean"][0])
-        if engine_kw.get("likelihood") == "warped":
-            raise NotImplementedError("the warped likelihood has no minibatch engine: full batch on one rank only (ElboEngine)")
+        mean = engine_kw.get("mean")
+        _refuse(is_whiten=engine_kw.get("is_whiten", True), mean=None if mean is None else mean[0],
+                likelihood=engine_kw.get("likelihood"), world_size=world_size, collective=engine_kw.get("collective"),
+                per_row=engine_kw.get("mlp") is not None or engine_kw.get("rowp") is not None, minibatch=True)
         self.device = torch.device(device)
         self.lib = L.load()
         self.X = X.to(self.device, torch.float64).contiguous()

@@ -65,21 +65,32 @@ def kernel_id(kernel):
     return int(kernel)
 
 
+def workspace_bytes(N, D, M, S, nblk, P, RP, kernel=0, plan=0, lik=L.LIK_GAUSS):
+    """Bytes of device workspace one ELBO step of this shape needs: the one place the library is asked."""
+    if lik in (L.LIK_BERNOULLI, L.LIK_WARPED):
+        # Bernoulli: general-M path at every M; warped: targets, moments and partials behind the Gaussian step's buffer
+        nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
+    else:
+        nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
+    if nbytes == 0:
+        raise L.TgpError("unsupported problem shape N=%d D=%d M=%d (this build: D<=16, M<=4096)" % (N, D, M))
+    return nbytes
+
+
+def new_workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_GAUSS):
+    """A workspace of the caller's own (engine.ElboEngine: a step split into phases keeps its intermediates there)."""
+    return torch.empty(workspace_bytes(N, D, M, S, nblk, P, RP, kernel, plan, lik) // 8 + 16, dtype=torch.float64, device=device)
+
+
 def workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_GAUSS):
+    """The cached workspace of the stateless one-shot calls of this module: one buffer per shape and stream, valid for the
+    duration of ONE call -- nothing that keeps state between calls may hold it."""
     key = (N, D, M, S, nblk, P, RP, str(device), torch.cuda.current_stream().cuda_stream, kernel, int(plan))
-    own = lik in (L.LIK_BERNOULLI, L.LIK_WARPED)
-    if own:          # Bernoulli: general-M path at every M; warped: targets, moments and partials behind the Gaussian step's buffer
+    if lik in (L.LIK_BERNOULLI, L.LIK_WARPED):
         key += (lik,)
     buf = _ws_cache.get(key)
     if buf is None:
-        if own:
-            nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
-        else:
-            nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
-        if nbytes == 0:
-            raise L.TgpError("unsupported problem shape N=%d D=%d M=%d (this build: D<=16, M<=4096)" % (N, D, M))
-        buf = torch.empty(nbytes // 8 + 16, dtype=torch.float64, device=device)
-        _ws_cache[key] = buf
+        buf = _ws_cache[key] = new_workspace(N, D, M, S, nblk, P, RP, device, kernel, plan, lik)
     return buf
 
 

@@ -114,40 +114,39 @@ class Trainer_SP_regression:
         launch captured in a HIP graph, no host synchronisation per step) when the run is what main.py sets up: Adam with
         one learning rate, weight decay on the 'NNets' group only, one full batch per epoch from a data.DeviceLoader.
         The model's nn.Parameters are re-pointed at the engine's flat buffer, so the modules stay the parameter holders
-        and everything downstream (metrics, prediction, state_dict) sees the trained values.  Returns None otherwise."""
+        and everything downstream (metrics, prediction, state_dict) sees the trained values.  Returns None otherwise: what
+        the engines themselves do not cover is engine.engine_refusal's to say (this trainer is one rank); the conditions here
+        are the run's -- optimiser, groups, frozen parameters, loader."""
         from .data import DeviceLoader
-        from .engine import ElboEngine, MinibatchEngine
+        from .engine import ElboEngine, MinibatchEngine, engine_refusal
         from .flow import compile_flow, mlp_spec
-        from .likelihoods import GaussianLinearMean, WarpedGaussianLinearMean
+        from .likelihoods import Bernoulli, GaussianLinearMean, MulticlassCategorical, WarpedGaussianLinearMean
         if not getattr(cg, "use_step_engine", True) or opt != "adam":
             return None
         ld = self.train_loader
         if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1:
             return None
         model = self.model
-        if not hasattr(model, "_gp_params") or any(g["lr"] != lr_ALL for g in groups):
+        mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
+        lik = next((name for cls, name in ((WarpedGaussianLinearMean, "warped"), (Bernoulli, "bernoulli"),
+                                           (MulticlassCategorical, "multiclass")) if isinstance(model.likelihood, cls)), None)
+        cover = dict(is_whiten=getattr(model, "is_whiten", True), mean=None if mean_fn is None else mean_fn.name, likelihood=lik,
+                     minibatch=len(ld) != 1)
+        if engine_refusal(**cover) is not None:        # (before the flow is compiled: whether it is input-dependent comes below)
             return None
-        if not getattr(model, "is_whiten", True):      # unwhitened q(u): the eager loop (the engines take is_whiten=True only)
+        if not hasattr(model, "_gp_params") or any(g["lr"] != lr_ALL for g in groups):
             return None
         # the engine updates EVERY parameter of its flat buffer: a stage that freezes some (lr = 0.0 entries,
         # trainer_base.py:155-179) or leaves some to a later stage must take the torch optimiser
         if {id(q) for g in groups for q in g["params"]} != {id(q) for q in model.parameters()}:
             return None
-        mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
-        if mean_fn is not None and len(ld) != 1:     # a mean function's engine is full batch only: minibatches take the eager loop
-            return None
         nets, theta_list, blocks = [], [], None
-        warped = isinstance(model.likelihood, WarpedGaussianLinearMean)
-        if warped:
-            if len(ld) != 1:             # the warped engine is full batch only: minibatches take the eager loop
-                return None
-            spec, theta_list, nets = compile_flow(model.likelihood.flow[0])
-            if nets:
-                return None
+        warped = lik == "warped"
+        if warped or not isinstance(model.likelihood, GaussianLinearMean):
+            spec, theta_list, nets = compile_flow(model.likelihood.flow[0] if warped else model.G_matrix[0])
             blocks = spec.blocks
-        elif not isinstance(model.likelihood, GaussianLinearMean):
-            spec, theta_list, nets = compile_flow(model.G_matrix[0])
-            blocks = spec.blocks
+        if engine_refusal(per_row=bool(nets), **cover) is not None:
+            return None
         nn_params = [p for net in nets for p in net.parameters()]
         nn_ids = {id(p) for p in nn_params}
         wd = 0.0
@@ -368,15 +367,9 @@ class Trainer_SP_regression:
 
 class Trainer_SP_classification(Trainer_SP_regression):
     """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
-    the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood.  Multi-class models
+    the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood (engine.engine_refusal).  Multi-class models
     (MulticlassCategorical, C latent GPs) train on the eager path too, on the composed step of models._elbo_multiclass; their
     accuracy is the argmax over the C class probabilities (trainers_classification.py:132)."""
-
-    def _engine_for(self, groups, lr_ALL, opt):
-        from .likelihoods import Bernoulli, MulticlassCategorical
-        if isinstance(self.model.likelihood, (Bernoulli, MulticlassCategorical)):
-            return None
-        return super()._engine_for(groups, lr_ALL, opt)
 
     def performance_metrics(self, X, Y):
         """(sum_n log p(y_n), number of correct labels): argmax over [1 - P, P] (binary) or over the C class probabilities

@@ -7,7 +7,6 @@ ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path.insert(0, ROOT)
 from oracle import tgp_oracle as orc       # checker only
 from tgp.pytorch_amd.engine import ElboEngine
-from tgp.pytorch_amd import ops
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 flows = [None, "sal1", "sal2", "tanh1x1", "tanh3x2", "tanh5x6"]
@@ -35,7 +34,6 @@ for c in range(n_cases):
             opt.zero_grad(); (-elbo).backward(); opt.step()
     except Exception as e:
         print("case %2d N=%5d D=%2d M=%3d S=%2d flow=%-8s oracle raised %s (cond %.1e): skipped" % (c, N, D, M, S, flow, type(e).__name__, cond)); continue
-    ops._ws_cache.clear()
     eng = ElboEngine(prob["X"], prob["Y"], prob["params"], float(prob["N_total"]), flow_blocks=prob["program"], S=S, device="cuda:0")
     eng.capture()
     hist = []
