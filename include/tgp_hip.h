@@ -313,6 +313,30 @@ int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, 
                          const double* Lam_w_bar, double* m_bar, double* L_q_bar, double* Z_bar, double* raw_ls_bar,
                          double* raw_os_bar, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Closed-form optimal q(u) of the Gaussian likelihood (the maximiser behind Titsias' collapsed bound), whitened, zero prior
+ * mean.  With K = K_ZZ + jitter I = L L^T, sigma^2 = exp(log_var_noise[0]) and c = model->scale:
+ *   C = K_ZX K_XZ (M,M),   b = K_ZX y (M)        one pass over the rows, K_ZX generated on chip and never stored
+ *   B = I + (c / sigma^2) L^-1 C L^-T,   S* = B^-1 = Lam* Lam*^T (Lam* lower, positive diagonal),   m* = (c / sigma^2) S* L^-1 b
+ * (m*, Lam*) maximise what tgp_elbo_step_f64 computes for TGP_LIK_GAUSS over (m, Lam); at c = 1 its value there is the collapsed
+ * bound log N(y | 0, Q + sigma^2 I) - tr(K_XX - Q) / (2 sigma^2), Q = K_XZ K^-1 K_ZX.  Lam* comes from ONE factorisation: the
+ * index-reversed J B J = L' L'^T gives Lam* = J L'^-T J.
+ * Uses model->{N,D,M,kernel,scale,jitter,Z,raw_ls,raw_os,log_var_noise}; m, Lam, lik and the flow fields are ignored.
+ * X (N,D), Y (N); outputs m_out (M) and Lam_out (M,M; exact zeros above the diagonal) -- they may be the model's own m / Lam.
+ * status[0] is tgp_cholesky_f64's for K (the host runs the jitter ladder); a failure of the second factorisation (B is
+ * I + a positive semi-definite matrix: NaNs only) is reported there as well when K's succeeded.
+ * tgp_kxxk_f64 is the first stage alone: C (M,M; C[i][j] == C[j][i] bit for bit) and b (M); Y == NULL or b == NULL skips b.
+ * The rows are split into groups whose size depends on N and M only; the groups are summed in order by a second launch.  No
+ * float atomics: two calls on the same input return the same bits on any device.
+ * Limits: 1 <= M <= TGP_BIG_MAX_M, 1 <= D <= 16, N >= 1, else TGP_E_UNSUPPORTED; a workspace below the *_workspace_bytes value
+ * gives TGP_E_WORKSPACE (tgp_last_error() names the entry in both cases). */
+size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out,
+                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t tgp_kxxk_workspace_bytes(int32_t N, int32_t M);
+int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, int32_t M, int32_t D, const double* raw_ls,
+                 const double* raw_os, const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 /* Mean functions (models/means.py, chosen by model_specs[0], models/utils_models.py:285-294): 'linear' m(x) = x a + b with a (D)
  * and b (1) trainable, 'identity' m(x) = x W with W (D) fixed (b = NULL).  One output GP: a is a vector.  The reference adds
  * m(X) to the q(f) mean (models/sparse_MF_SP.py:314,355,360), subtracts m(Z) from the unwhitened variational mean (:359) and uses

@@ -392,6 +392,44 @@ int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* 
   return launch_qf_cov(*model, X, mu, Sigma, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return optimal_qu_workspace_bytes(N, D, M); }
+
+int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (model->kernel != TGP_KERNEL_SCALE_RBF && model->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (optimal_qu_workspace_bytes(model->N, model->D, model->M) == 0) {
+    set_error_text("tgp_optimal_qu_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", model->N, model->D,
+                   model->M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os || !model->log_var_noise) return -1;
+  if (!X) return -2;
+  if (!Y) return -3;
+  if (!m_out) return -4;
+  if (!Lam_out) return -5;
+  if (!status) return -6;
+  if (!workspace) return -7;
+  return launch_optimal_qu(*model, X, Y, m_out, Lam_out, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t tgp_kxxk_workspace_bytes(int32_t N, int32_t M) { return kxxk_workspace_bytes(N, M); }
+
+int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, int32_t M, int32_t D, const double* raw_ls,
+                 const double* raw_os, const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes,
+                 void* stream) {
+  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (D < 1 || D > 16 || kxxk_workspace_bytes(N, M) == 0) {
+    set_error_text("tgp_kxxk_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", N, D, M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!X) return -2;
+  if (!Z || !raw_ls || !raw_os) return -4;
+  if (!C) return -10;
+  if (!workspace) return -12;
+  return launch_kxxk(kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S) { return qf_joint_sample_workspace_bytes(N, S); }
 
 int tgp_qf_joint_sample_f64(const double* mu, const double* Sigma, int32_t N, double jitter, const double* eps, int32_t S,

@@ -175,4 +175,12 @@ int launch_mean_forward(const double* X, int N, int D, const double* a, const do
 int launch_mean_backward(const double* X, int N, int D, const double* a, const double* g, int ldg, int colg, double* g_a,
                          double* g_b, double* g_X, double* part, hipStream_t st);
 
+// tgp_optqu.hip (closed-form optimal whitened q(u) of the Gaussian likelihood: C = K_ZX K_XZ, b = K_ZX y, then the M x M chain)
+size_t kxxk_workspace_bytes(int N, int M);
+int launch_kxxk(int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls, const double* raw_os,
+                const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes, hipStream_t st);
+size_t optimal_qu_workspace_bytes(int N, int D, int M);
+int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
+                      void* workspace, size_t workspace_bytes, hipStream_t st);
+
 }  // namespace tgp

@@ -1,0 +1,382 @@
+// tgp_optqu.hip -- closed-form optimal q(u) of the Gaussian likelihood (tgp_optimal_qu_f64, tgp_kxxk_f64).
+//
+// Whitened q(u) = N(m, Lam Lam^T), zero prior mean, sigma^2 = exp(log_var_noise), c = N_total / MB (model->scale).  With
+// K = K_ZZ + jitter I = L L^T the maximiser of the Gaussian ELBO over (m, Lam) -- the q(u) behind Titsias' collapsed bound -- is
+//   C = K_ZX K_XZ (M x M),   b = K_ZX y (M)
+//   B = I + (c / sigma^2) L^-1 C L^-T,   S* = B^-1 = Lam* Lam*^T,   m* = (c / sigma^2) S* L^-1 b
+// and a LOWER factor of B^-1 comes from one factorisation of the index-reversed matrix: J B J = L' L'^T gives
+// B^-1 = (J L'^-T J)(J L'^-T J)^T with J L'^-T J lower triangular and a positive diagonal.
+//
+// Launch sequence of tgp_optimal_qu_f64 (one stream, no host sync):
+//   K, its factor and L^-1     the existing launchers (launch_kernel_matrix, launch_cholesky / launch_big_cholesky); status[0]
+//   k_kxxk                     per (64 x 64 tile of the lower block triangle, row group): the partial tile of C on the matrix
+//                              cores, both operand tiles of K_ZX generated in LDS from the scaled rows (never in HBM); the
+//                              partial of b rides on tile column 0
+//   k_kxxk_fin                 the groups summed in order, C mirrored to the upper triangle, b finished
+//   k_optqu_pad                L^-1 and C into zero-padded (MP x MP) images, MP a multiple of 128
+//   T = L^-1 C,  Phi = T L^-T  launch_gemm_plain (twice)
+//   k_optqu_b                  J B J from the lower triangle of Phi (exactly symmetric), sigma^2 read on the device
+//   L', L'^-1                  the existing launchers again, on status words of the workspace
+//   k_optqu_lam                Lam* = J L'^-T J (zeros above the diagonal) and its transpose
+//   k_optqu_mv (three times)   v1 = L^-1 b,  v2 = Lam*^T v1,  m* = (c / sigma^2) Lam* v2
+// The row groups' size is a function of N and M alone, every sum has a fixed order and nothing is accumulated with atomics:
+// two runs on the same input are bit-identical, on any device.
+#include "tgp_dev.hpp"
+#include "tgp_launch.hpp"
+
+namespace tgp {
+
+#define OQ_T 64      /* output tile (rows and columns) of k_kxxk                                                             */
+#define OQ_KC 16     /* data rows (the contraction index) generated per step                                                  */
+#define OQ_LDN 80    /* LDS stride (f64) of a [16 n][64 i] operand tile: the 4 n rows of one MFMA operand fall in distinct banks */
+#define OQ_LDT 65    /* LDS stride (f64) of the 64 x 64 output tile in k_kxxk_fin                                             */
+#define OQ_MIN_G 128 /* smallest row group                                                                                    */
+#define OQ_WGS 1024  /* workgroups k_kxxk aims at when it splits the rows (a constant: the split must not depend on the device) */
+
+// tile t of the lower block triangle, row major: (ti, tj), tj <= ti
+__device__ __forceinline__ void oq_tile(int t, int& ti, int& tj) {
+  ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+  while (ti * (ti + 1) / 2 > t) --ti;
+  tj = t - ti * (ti + 1) / 2;
+}
+
+// Partial tile (ti, tj) of C = K_ZX K_XZ over the rows [g G, min(N, (g + 1) G)) and, on tile column 0, the partial of b = K_ZX y.
+// Per step of 16 rows thread (gk, gc) evaluates K(z_i, x_n) for row n = gk of the step against the inducing points gc + 16 u of
+// both tile sides into the [16 n][64 i] LDS operand tiles (a diagonal tile has one); rows past the group's end give exact
+// zeros.  Wave w holds rows 16 w .. 16 w + 15 of the tile against all 64 columns in four accumulators (k_cov_sigma's
+// layout).  Inducing points past M are clamped to M - 1: their rows and columns are computed and never read by k_kxxk_fin.
+template <int DP>
+__global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restrict__ X, int N, const double* __restrict__ Z, int M,
+                                               int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                               const double* __restrict__ Y, int G, int ntile, int nti, double* __restrict__ part,
+                                               double* __restrict__ bpart) {
+  __shared__ double Ki[OQ_KC * OQ_LDN], Kj[OQ_KC * OQ_LDN];
+  __shared__ double ziT[DP * OQ_T], zjT[DP * OQ_T];  // [d][inducing point]: scaled rows of Z
+  __shared__ double red[16 * OQ_T];
+  __shared__ double ils[17];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int t = blockIdx.x, g = blockIdx.y;
+  int ti, tj;
+  oq_tile(t, ti, tj);
+  const int i0 = ti * OQ_T, j0 = tj * OQ_T;
+  const bool diag = ti == tj, want_b = tj == 0 && Y != nullptr && bpart != nullptr;
+  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
+  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  __syncthreads();
+  for (int i = tid; i < DP * OQ_T; i += 256) {
+    const int d = i >> 6, c = i & 63;
+    const int mi = i0 + c < M ? i0 + c : M - 1, mj = j0 + c < M ? j0 + c : M - 1;
+    ziT[i] = d < D ? Z[(size_t)mi * D + d] * ils[d] : 0.0;
+    zjT[i] = d < D ? Z[(size_t)mj * D + d] * ils[d] : 0.0;
+  }
+  __syncthreads();
+  const double s2 = ils[16];
+  const int gk = tid >> 4, gc = tid & 15;  // generation role: row gk of the step, inducing points gc + 16 u
+  const int n_begin = g * G, n_end = n_begin + G < N ? n_begin + G : N;
+  const double* Bt = diag ? Ki : Kj;
+  d4 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
+  double bp[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int n0 = n_begin; n0 < n_end; n0 += OQ_KC) {
+    {
+      const int n = n0 + gk;
+      const bool valid = n < n_end;
+      const int nc = valid ? n : N - 1;  // clamped: the row is read and its covariances are replaced by zeros
+      double x[DP];
+#pragma unroll
+      for (int d = 0; d < DP; ++d) x[d] = d < D ? X[(size_t)nc * D + d] * ils[d] : 0.0;
+      const double yv = (want_b && valid) ? Y[nc] : 0.0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = gc + 16 * u;
+        double d2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
+          const double q = ziT[d * OQ_T + c] - x[d];
+          d2 += q * q;
+        }
+        const double kv = valid ? cov_value(kernel, s2, d2) : 0.0;
+        Ki[gk * OQ_LDN + c] = kv;
+        bp[u] += kv * yv;
+      }
+      if (!diag) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = gc + 16 * u;
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < DP; ++d) {
+            const double q = zjT[d * OQ_T + c] - x[d];
+            d2 += q * q;
+          }
+          Kj[gk * OQ_LDN + c] = valid ? cov_value(kernel, s2, d2) : 0.0;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const double a = Ki[(kk * 4 + lq) * OQ_LDN + 16 * w + lr];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Bt[(kk * 4 + lq) * OQ_LDN + 16 * c + lr], acc[c]);
+    }
+    __syncthreads();
+  }
+  double* pt = part + ((size_t)g * ntile + t) * (OQ_T * OQ_T);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pt[(16 * w + lq + 4 * r) * OQ_T + 16 * c + lr] = acc[c][r];
+  if (want_b) {  // (uniform over the workgroup)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) red[gk * OQ_T + gc + 16 * u] = bp[u];
+    __syncthreads();
+    if (tid < OQ_T) {
+      double s = 0.0;
+      for (int k = 0; k < 16; ++k) s += red[k * OQ_T + tid];
+      bpart[((size_t)g * nti + ti) * OQ_T + tid] = s;
+    }
+  }
+}
+
+// C tile (ti, tj) = the groups' partial tiles summed in the order g = 0, 1, ..., written as (i, j) and mirrored as (j, i); a
+// diagonal tile writes element (r, c) from the value summed for (max(r, c), min(r, c)): C[i][j] == C[j][i] bit for bit.  Tile
+// column 0 finishes b the same way.  Rows and columns past M are masked.
+__global__ __launch_bounds__(256) void k_kxxk_fin(const double* __restrict__ part, const double* __restrict__ bpart, int ngroup,
+                                                   int ntile, int nti, int M, double* __restrict__ C, int ldc, double* __restrict__ b) {
+  __shared__ double buf[OQ_T * OQ_LDT];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  int ti, tj;
+  oq_tile(t, ti, tj);
+  const int i0 = ti * OQ_T, j0 = tj * OQ_T;
+  for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+    double s = 0.0;
+    for (int g = 0; g < ngroup; ++g) s += part[((size_t)g * ntile + t) * (OQ_T * OQ_T) + e];
+    buf[(e >> 6) * OQ_LDT + (e & 63)] = s;
+  }
+  if (tj == 0 && b != nullptr && bpart != nullptr && tid < OQ_T) {
+    double s = 0.0;
+    for (int g = 0; g < ngroup; ++g) s += bpart[((size_t)g * nti + ti) * OQ_T + tid];
+    if (i0 + tid < M) b[i0 + tid] = s;
+  }
+  __syncthreads();
+  if (ti != tj) {
+    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+      const int r = e >> 6, c = e & 63;
+      if (i0 + r < M && j0 + c < M) C[(size_t)(i0 + r) * ldc + j0 + c] = buf[r * OQ_LDT + c];
+    }
+    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+      const int c = e >> 6, r = e & 63;
+      if (i0 + r < M && j0 + c < M) C[(size_t)(j0 + c) * ldc + i0 + r] = buf[r * OQ_LDT + c];
+    }
+  } else {
+    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+      const int r = e >> 6, c = e & 63;
+      const int hi = r > c ? r : c, lo = r > c ? c : r;
+      if (i0 + r < M && i0 + c < M) C[(size_t)(i0 + r) * ldc + i0 + c] = buf[hi * OQ_LDT + lo];
+    }
+  }
+}
+
+// L^-1 (its lower triangle) and C in their zero-padded (MP x MP) images; the second factorisation's status words zeroed
+__global__ __launch_bounds__(256) void k_optqu_pad(const double* __restrict__ Linv, const double* __restrict__ C, int M, int MP,
+                                                    double* __restrict__ LinvP, double* __restrict__ CP, int32_t* __restrict__ st2) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int row = (int)(e / MP), col = (int)(e % MP);
+  const size_t s = (size_t)row * M + col;
+  LinvP[e] = (row < M && col <= row) ? Linv[s] : 0.0;
+  CP[e] = (row < M && col < M) ? C[s] : 0.0;
+  if (e < 8) st2[e] = 0;
+}
+
+// c / sigma^2 of the model, on the device
+__device__ __forceinline__ double oq_prec(const double* __restrict__ lvn, double scale) { return scale * exp(-lvn[0]); }
+
+// Bm = J B J, B = I + (c / sigma^2) Phi, from the lower triangle of Phi: exactly symmetric
+__global__ __launch_bounds__(256) void k_optqu_b(const double* __restrict__ Phi, int MP, int M, const double* __restrict__ lvn,
+                                                  double scale, double* __restrict__ Bm) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)M * M) return;
+  const int i = (int)(e / M), j = (int)(e % M);
+  const int ri = M - 1 - i, rj = M - 1 - j;
+  const int hi = ri > rj ? ri : rj, lo = ri > rj ? rj : ri;
+  Bm[e] = oq_prec(lvn, scale) * Phi[(size_t)hi * MP + lo] + (i == j ? 1.0 : 0.0);
+}
+
+// Lam* = J L'^-T J: Lam*[i][j] = L'^-1[M-1-j][M-1-i] for j <= i, zeros above; LamT its transpose.  A failure of the second
+// factorisation is reported in status[0] when K's succeeded.
+__global__ __launch_bounds__(256) void k_optqu_lam(const double* __restrict__ Lpinv, int M, double* __restrict__ Lam,
+                                                    double* __restrict__ LamT, const int32_t* __restrict__ st2,
+                                                    int32_t* __restrict__ status) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e == 0) {
+    if (st2[0] != 0 && status[0] == 0) status[0] = st2[0];
+    if (st2[1] != 0) status[1] = st2[1];
+  }
+  if (e >= (size_t)M * M) return;
+  const int i = (int)(e / M), j = (int)(e % M);
+  const double v = j <= i ? Lpinv[(size_t)(M - 1 - j) * M + (M - 1 - i)] : 0.0;
+  Lam[e] = v;
+  LamT[(size_t)j * M + i] = v;
+}
+
+// y = alpha A x, A (M x M, row stride ld), alpha = c / sigma^2 with lvn, else 1.  One wave per row: lane l sums the columns
+// l, l + 64, ... in order, then the wave butterfly.
+__global__ __launch_bounds__(256) void k_optqu_mv(const double* __restrict__ A, int ld, int M, const double* __restrict__ x,
+                                                   const double* __restrict__ lvn, double scale, double* __restrict__ y) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;  // (whole waves)
+  double s = 0.0;
+  for (int k = lane; k < M; k += 64) s += A[(size_t)row * ld + k] * x[k];
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) y[row] = (lvn != nullptr ? oq_prec(lvn, scale) : 1.0) * s;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+namespace {
+struct KxPlan {  // the row split of k_kxxk: a function of N and M alone
+  int nti, ntile, G, ngroup;
+  size_t part, bpart, total;  // offsets in doubles
+};
+bool kx_plan(KxPlan& p, int N, int M) {
+  if (N < 1 || M < 1 || M > TGP_BIG_MAX_M) return false;
+  p.nti = (M + OQ_T - 1) / OQ_T;
+  p.ntile = p.nti * (p.nti + 1) / 2;
+  const int want = OQ_WGS / p.ntile > 1 ? OQ_WGS / p.ntile : 1;
+  const size_t g = rup(((size_t)N + want - 1) / want, OQ_KC);
+  p.G = g > OQ_MIN_G ? (int)g : OQ_MIN_G;
+  p.ngroup = (N + p.G - 1) / p.G;  // <= want <= OQ_WGS
+  p.part = 0;
+  p.bpart = rup((size_t)p.ngroup * p.ntile * OQ_T * OQ_T, 64);
+  p.total = p.bpart + rup((size_t)p.ngroup * p.nti * OQ_T, 64);
+  return true;
+}
+struct OqPlan {  // offsets in doubles, every section a multiple of 64 doubles
+  int MP;
+  // Kmm is J B J later, Lf is L', CP is Lam*^T and T is L'^-1 once their first contents have been consumed
+  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, CP, T, Phi, C, b, v1, v2, st2, kx, total;
+  KxPlan k;
+};
+bool oq_plan(OqPlan& p, int N, int D, int M) {
+  if (D < 1 || D > 16 || !kx_plan(p.k, N, M)) return false;
+  p.MP = (int)rup((size_t)M, 128);
+  const size_t mm = rup((size_t)M * M, 64), pp = (size_t)p.MP * p.MP, mv = rup((size_t)M, 64);
+  p.chol_len = M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0;
+  size_t o = 0;
+  p.Kmm = o; o += mm;
+  p.Lf = o; o += mm;
+  p.Linv = o; o += mm;
+  p.chol = o; o += p.chol_len;
+  p.LinvP = o; o += pp;
+  p.CP = o; o += pp;
+  p.T = o; o += pp;
+  p.Phi = o; o += pp;
+  p.C = o; o += mm;
+  p.b = o; o += mv;
+  p.v1 = o; o += mv;
+  p.v2 = o; o += mv;
+  p.st2 = o; o += 64;
+  p.kx = o; o += p.k.total;
+  p.total = o;
+  return true;
+}
+double* oq_align16(void* ws, size_t bytes, size_t* doubles) {
+  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
+  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
+  *doubles = bytes > skip ? (bytes - skip) / sizeof(double) : 0;
+  return reinterpret_cast<double*>(a);
+}
+int oq_factorise(const double* A, int M, double* Lo, double* Jo, int32_t* status, double* cws, size_t cws_len, hipStream_t st) {
+  if (M > TGP_FUSED_MAX_M) return launch_big_cholesky(A, M, Lo, Jo, status, cws, cws_len, st);
+  return launch_cholesky(A, M, Lo, Jo, status, st);
+}
+int run_kxxk(const KxPlan& k, int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls,
+             const double* raw_os, const double* Y, double* C, double* b, double* ws, hipStream_t st) {
+  const dim3 grid((unsigned)k.ntile, (unsigned)k.ngroup), block(256);
+  double* bpart = (Y != nullptr && b != nullptr) ? ws + k.bpart : nullptr;
+  if (D <= 4)
+    hipLaunchKernelGGL(k_kxxk<4>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
+  else if (D <= 8)
+    hipLaunchKernelGGL(k_kxxk<8>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
+  else
+    hipLaunchKernelGGL(k_kxxk<16>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_kxxk_fin, dim3((unsigned)k.ntile), block, 0, st, ws + k.part, bpart, k.ngroup, k.ntile, k.nti, M, C, M, b);
+  LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace
+
+size_t kxxk_workspace_bytes(int N, int M) {
+  KxPlan k;
+  if (!kx_plan(k, N, M)) return 0;
+  return k.total * sizeof(double) + 16;
+}
+
+size_t optimal_qu_workspace_bytes(int N, int D, int M) {
+  OqPlan p;
+  if (!oq_plan(p, N, D, M)) return 0;
+  return p.total * sizeof(double) + 16;
+}
+
+int launch_kxxk(int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls, const double* raw_os,
+                const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  KxPlan k;
+  if (D < 1 || D > 16 || !kx_plan(k, N, M)) {
+    set_error_text("tgp_kxxk_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", N, D, M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  size_t have = 0;
+  double* ws = oq_align16(workspace, workspace_bytes, &have);
+  if (have < k.total) {
+    set_error_text("tgp_kxxk_f64: workspace of %zu bytes, tgp_kxxk_workspace_bytes gives %zu", workspace_bytes,
+                   k.total * sizeof(double) + 16);
+    return TGP_E_WORKSPACE;
+  }
+  return run_kxxk(k, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, ws, st);
+}
+
+int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
+                      void* workspace, size_t workspace_bytes, hipStream_t st) {
+  OqPlan p;
+  if (!oq_plan(p, md.N, md.D, md.M)) {
+    set_error_text("tgp_optimal_qu_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", md.N, md.D, md.M,
+                   TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  size_t have = 0;
+  double* ws = oq_align16(workspace, workspace_bytes, &have);
+  if (have < p.total) {
+    set_error_text("tgp_optimal_qu_f64: workspace of %zu bytes, tgp_optimal_qu_workspace_bytes gives %zu", workspace_bytes,
+                   p.total * sizeof(double) + 16);
+    return TGP_E_WORKSPACE;
+  }
+  const int N = md.N, D = md.D, M = md.M, MP = p.MP;
+  const unsigned gmm = (unsigned)(((size_t)M * M + 255) / 256), gpp = (unsigned)((size_t)MP * MP / 256), gmv = (unsigned)((M + 3) / 4);
+  int32_t* st2 = reinterpret_cast<int32_t*>(ws + p.st2);
+  double *Bm = ws + p.Kmm, *Lp = ws + p.Lf, *Lpinv = ws + p.T, *LamT = ws + p.CP;  // second lives of consumed sections
+  if (int rc = launch_kernel_matrix(md.kernel, md.Z, M, nullptr, 0, D, md.raw_ls, md.raw_os, md.jitter, ws + p.Kmm, st)) return rc;
+  if (int rc = oq_factorise(ws + p.Kmm, M, ws + p.Lf, ws + p.Linv, status, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = run_kxxk(p.k, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os, Y, ws + p.C, ws + p.b, ws + p.kx, st)) return rc;
+  hipLaunchKernelGGL(k_optqu_pad, dim3(gpp), dim3(256), 0, st, ws + p.Linv, ws + p.C, M, MP, ws + p.LinvP, ws + p.CP, st2);
+  LAUNCH_CHECK();
+  if (int rc = launch_gemm_plain(false, false, 0, MP, MP, MP, 1.0, ws + p.LinvP, MP, ws + p.CP, MP, 0.0, ws + p.T, MP, st)) return rc;
+  if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.T, MP, ws + p.LinvP, MP, 0.0, ws + p.Phi, MP, st)) return rc;
+  hipLaunchKernelGGL(k_optqu_b, dim3(gmm), dim3(256), 0, st, ws + p.Phi, MP, M, md.log_var_noise, md.scale, Bm);
+  LAUNCH_CHECK();
+  if (int rc = oq_factorise(Bm, M, Lp, Lpinv, st2, ws + p.chol, p.chol_len, st)) return rc;
+  hipLaunchKernelGGL(k_optqu_lam, dim3(gmm), dim3(256), 0, st, Lpinv, M, Lam_out, LamT, st2, status);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_optqu_mv, dim3(gmv), dim3(256), 0, st, ws + p.LinvP, MP, M, ws + p.b, nullptr, 1.0, ws + p.v1);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_optqu_mv, dim3(gmv), dim3(256), 0, st, LamT, M, M, ws + p.v1, nullptr, 1.0, ws + p.v2);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_optqu_mv, dim3(gmv), dim3(256), 0, st, Lam_out, M, M, ws + p.v2, md.log_var_noise, md.scale, m_out);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace tgp

@@ -64,6 +64,23 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
     return None
 
 
+def collapsed_refusal(flow_blocks=None, likelihood=None, mean=None, world_size=1, collective=None, per_row=False,
+                      minibatch=False):
+    """What ElboEngine(collapsed=True) does not cover, or None: the closed-form optimal q(u) is built into the captured step
+    for the Gaussian likelihood with a zero mean, full batch, on one rank."""
+    if flow_blocks is not None or per_row:
+        return "the collapsed engine has no flow: q(u) has a closed-form optimum for a likelihood that is Gaussian in f only"
+    if likelihood is not None:
+        return "the collapsed engine takes the Gaussian likelihood only (got %r): set_optimal_qu serves the eager loop" % (likelihood,)
+    if mean is not None:
+        return "the collapsed engine takes the zero mean only (got %r): qu='optimal' with a mean trains on the eager loop" % (mean[0],)
+    if int(world_size) > 1 or collective is not None:
+        return "the collapsed engine is single-rank (world_size = 1): no data-parallel collapsed step"
+    if minibatch:
+        return "the collapsed engine is full batch: the optimum of q(u) belongs to the rows it was computed from"
+    return None
+
+
 def _refuse(**description):
     why = engine_refusal(**description)
     if why is not None:
@@ -275,8 +292,18 @@ class ElboEngine:
                  eps=1e-8, device="cuda:0", world_size=1, rank=0, mb_global=None, process_group=None,
                  kernel="scale_rbf", mlp=None, mlp_weights=None, nn_weight_decay=1e-5, mlp_training=True,
                  jitter_ladder=1e-8, share=None, collective=None, plan=0, comm_timeout_s=None, likelihood=None,
-                 is_whiten=True, mean=None, fused_adam=True):
-        """`mean` = ("linear", a, b) or ("identity", W, None): m(x) = x a + b enters the step as a per-row affine block
+                 is_whiten=True, mean=None, fused_adam=True, collapsed=False):
+        """`collapsed` True: q(u) is not trained but set to its closed-form optimum inside every step (Titsias' collapsed
+        bound).  A step is tgp_optimal_qu_f64 into the flat buffer's m / Lam segments -> tgp_elbo_step_phases_f64 (the unchanged
+        step: its gradients for the hyper-parameters are the collapsed bound's, d ELBO / d q(u) vanishes at the optimum) -> Adam
+        on the segments other than m and Lam (in front of them under the step counter, behind them under a twin counter that
+        moves in lock step: the step counter advances once per step).  The scalars of a step are the bound at the
+        hyper-parameters the step started from; after the last step q(u) belongs to those, so call refresh_qu() before the
+        model is evaluated.  The optimum and the step factorise K at the same jitter (0) in the normal case; if the step's
+        device ladder raises it, the step is still a valid ELBO, at a marginally sub-optimal q(u) -- the optimum itself has no
+        device ladder, a failed factorisation of its own surfaces in check_status().  Full batch, one rank, Gaussian
+        likelihood, zero mean: everything else raises NotImplementedError here (engine_refusal speaks for the Adam engines).
+        `mean` = ("linear", a, b) or ("identity", W, None): m(x) = x a + b enters the step as a per-row affine block
         (a_n, b_n) = (1, m(x_n)) at the head of the flow program, G(f) -> G(f + m(x_n)).  Linear: a (D) and b (1) are segments
         of the flat buffer; a step is tgp_mean_forward_f64 -> the ELBO step (all phases) -> tgp_mean_backward_f64 from
         g_rowp[:, 1] into the flat gradient -> the separate Adam launch, all captured.  Identity: W is fixed, the rows'
@@ -297,6 +324,13 @@ class ElboEngine:
                 collective=collective, per_row=mlp is not None or rowp is not None)
         if likelihood not in (None, "warped"):
             raise ValueError("likelihood must be None or 'warped'")
+        self.collapsed = bool(collapsed)
+        if self.collapsed:
+            why = collapsed_refusal(flow_blocks=flow_blocks, likelihood=likelihood, mean=mean, world_size=world_size,
+                                    collective=collective, per_row=mlp is not None or rowp is not None,
+                                    minibatch=mb_global is not None or share is not None)
+            if why is not None:
+                raise NotImplementedError(why)
         if mean is not None and mean[0] not in ("linear", "identity"):
             raise ValueError("mean must be ('linear', a, b) or ('identity', W, None), got %r" % (mean[0],))
         self.lib = L.load()
@@ -321,7 +355,12 @@ class ElboEngine:
         # caller's choice (all the rotated ID_TGP unit goes by), `fused_adam` whether the WHOLE step is that one call.
         self.fused_update = bool(fused_adam)
         self.fused_adam = (self.fused_update and self.world_size == 1 and self.comm is None and self.mlp is None
-                           and self.mean is None)
+                           and self.mean is None and not self.collapsed)
+        if self.collapsed:
+            self.qu_ws = torch.empty(max(self.lib.tgp_optimal_qu_workspace_bytes(self.N, self.D, self.M), 8) // 8 + 2,
+                                     dtype=torch.float64, device=self.device)
+            self.qu_status = torch.zeros(8, dtype=torch.int32, device=self.device)
+            self.step_tail = torch.zeros(2, dtype=torch.int32, device=self.device)    # the twin counter of the segments behind Lam
         self.pre_step = self.post_step = None   # callables launched (and captured) before / after the step: the minibatch gather
         self.pipeline_steps = True      # ID_TGP, one rank: capture the rotated unit (see capture())
         self._out = None                # redirected scalar output while the unrolled graph is being captured
@@ -505,7 +544,26 @@ class ElboEngine:
         return (L.ptr(fp.data[lo:hi]), L.ptr(fp.grad[lo:hi]), L.ptr(fp.exp_avg[lo:hi]), L.ptr(fp.exp_avg_sq[lo:hi]), hi - lo,
                 self.lr, self.betas[0], self.betas[1], self.eps)
 
+    def optimal_qu(self):
+        """m, Lam of the flat buffer <- the closed-form optimum at the buffer's hyper-parameters (tgp_optimal_qu_f64)."""
+        fp = self.fp
+        L.check(self.lib.tgp_optimal_qu_f64(self.md, L.ptr(self.X), L.ptr(self.Y), L.ptr(fp.view("m")), L.ptr(fp.view("Lam")),
+                                            L.ptr(self.qu_status), L.ptr(self.qu_ws), self.qu_ws.numel() * 8, L.stream_ptr()),
+                "tgp_optimal_qu_f64")
+
+    def refresh_qu(self):
+        """Collapsed engine: recompute the optimum for the hyper-parameters the last step left (outside the graph)."""
+        if not self.collapsed:
+            raise NotImplementedError("refresh_qu() belongs to ElboEngine(collapsed=True): an Adam engine trains q(u)")
+        self.optimal_qu()
+
     def adam(self):
+        if self.collapsed:          # every segment but m and Lam: [0, m) and [end of Lam, n), one counter each, in lock step
+            fp = self.fp
+            lo, hi = fp.offsets["m"], fp.offsets["Lam"] + fp.sizes["Lam"]
+            self._adam_segment(0, lo, 0.0, self.step_dev)
+            self._adam_segment(hi, fp.n, 0.0, self.step_tail)
+            return
         rc = self.lib.tgp_adam_dev_groups_f64(*self._adam_args(0, self.fp.n), self.n_plain,
                                               self.nn_wd if self.mlp is not None else 0.0, L.ptr(self.step_dev), 1,
                                               L.stream_ptr())
@@ -565,6 +623,10 @@ class ElboEngine:
             self.mean_forward()
             self.elbo()
             self.mean_backward()
+            return
+        if self.collapsed:
+            self.optimal_qu()
+            self.elbo()
             return
         if self.mlp is None:
             self.elbo()
@@ -745,6 +807,11 @@ class ElboEngine:
     # ---- bookkeeping ---------------------------------------------------------------------------------
     def check_status(self):
         """Lazy Cholesky check (one sync): raises like the reference's psd_safe_cholesky would."""
+        if self.collapsed:
+            sq = self.qu_status.cpu()
+            if ops.raise_for_status(sq):
+                raise ops.NotPSDError("K_MM not positive definite at pivot %d in the optimal q(u) of the last step (no jitter "
+                                      "ladder there): train q(u) by Adam, or raise the model's jitter" % int(sq[0]))
         st = self.status.cpu()
         failed = ops.raise_for_status(st)       # an expired hand-off wait (sticky across a replayed graph's steps), NaN in K_MM
         if int(st[2]) > self._warned_jitter:

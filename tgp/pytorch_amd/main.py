@@ -77,6 +77,10 @@ def main(argv=None):
     ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
                     help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
                          "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
+    ap.add_argument("--qu", choices=["adam", "optimal"], default="adam",
+                    help="q(u): adam = m and Lam trained by Adam like every other parameter (the reference); optimal = set to "
+                         "their closed-form optimum before every step and evaluation, the hyper-parameters train on the "
+                         "collapsed bound (SVGP and WGP, --whiten 1, data sets of one full batch)")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -97,6 +101,8 @@ def main(argv=None):
         ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
     if args.mean != "zero" and (wgp or multi or args.model == "ID_TGP"):
         ap.error("--mean %s: SVGP or TGP with the gaussian or bernoulli likelihood only" % args.mean)
+    if args.qu == "optimal" and (args.model not in ("SVGP", "WGP") or args.likelihood != "gaussian" or not args.whiten):
+        ap.error("--qu optimal: SVGP or WGP with the gaussian likelihood and --whiten 1 (the likelihood must be Gaussian in f)")
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
         ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
@@ -173,7 +179,7 @@ def main(argv=None):
     trainer_cls = Trainer_SP_classification if (bern or multi) else Trainer_SP_regression
     trainer = trainer_cls(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
                                     track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True,
-                                    coverage=args.coverage)
+                                    coverage=args.coverage, qu=args.qu)
     trainer.train(epochs=args.epochs, lr_ALL=lr, opt="adam", keep_parameter_groups=True,
                   optimisation_schedule=([1.0], specs), lr_groups=None)
     res = trainer.compute_metrics()

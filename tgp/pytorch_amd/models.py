@@ -345,8 +345,9 @@ class sparse_MF_SP(nn.Module):
         kl, _, _ = ops.kl_whitened(m.detach(), Lam.detach())
         return kl.reshape(1)
 
-    def ELBO(self, X, Y):
-        """Returns (ELBO, ELL, KLD): positive ELBO with autograd, the trainer negates (sparse_MF_SP.py:552-598)."""
+    def ELBO(self, X, Y, _qu_jitter=None):
+        """Returns (ELBO, ELL, KLD): positive ELBO with autograd, the trainer negates (sparse_MF_SP.py:552-598).
+        `_qu_jitter` (collapsed_bound only): q(u) enters as a constant and the step starts at this jitter."""
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
@@ -354,6 +355,8 @@ class sparse_MF_SP(nn.Module):
             return self._elbo_multiclass(X2, Y)
         info = {}
         Z, rl, ro, m, Lam, lvn = self._gp_params(info=info)
+        if _qu_jitter is not None:
+            m, Lam = m.detach(), Lam.detach()
         spec, theta, rowp = self._flow_inputs(X2, with_grad=True)
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
@@ -379,8 +382,66 @@ class sparse_MF_SP(nn.Module):
             ell = ops.EllStepFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
             kld = self.KLD().sum()
             return ell - kld, ell, kld
+        if _qu_jitter is not None:
+            cfg["jitter"] = float(_qu_jitter)
+            try:
+                return ops.ElboFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
+            finally:
+                del cfg["jitter"]
         elbo, ell, kld = ops.ElboFunction.apply(X2, Y, Z, rl, ro, m, Lam, lvn, theta, rowp, cfg)
         return elbo, ell, kld
+
+    # ---- closed-form optimal q(u): the collapsed bound ----------------------------------------------
+    def _qu_refusal(self):
+        """Why this model has no closed-form optimal q(u), or None.  The closed form needs a likelihood that is Gaussian in f
+        (on the targets themselves, on Y - m(X), or on the warped targets T(Y)) and the whitened parameterisation."""
+        if self._is_multiclass:
+            return "the multi-class (softmax) likelihood is not Gaussian in f: q(u) has no closed-form optimum"
+        if self._is_bernoulli:
+            return "the Bernoulli likelihood is not Gaussian in f: q(u) has no closed-form optimum"
+        if not isinstance(self.likelihood, GaussianLinearMean):
+            if any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", [])):
+                return "input-dependent flows (ID_TGP) act on f: the likelihood is not Gaussian in f and q(u) has no closed-form optimum"
+            return "a flow on f (TGP) makes the likelihood non-Gaussian in f: q(u) has no closed-form optimum (SVGP and WGP have one)"
+        if not self.is_whiten:
+            return "is_whiten=False: the closed form is built for the whitened q(u) only"
+        return None
+
+    def set_optimal_qu(self, X, Y):
+        """Write the maximiser of the ELBO over q(u), at the current hyper-parameters and for these rows, into q_U
+        (ops.optimal_qu / tgp_optimal_qu_f64; no autograd).  The targets are Y for the Gaussian likelihood, Y - m(X) with a linear
+        or identity mean and T(Y) for the warped likelihood -- what the unchanged Gaussian step is run on.  Returns the `info`
+        dict of the factorisation (info["jitter"]).  NotImplementedError, naming the reason, where no closed form exists."""
+        why = self._qu_refusal()
+        if why is not None:
+            raise NotImplementedError("set_optimal_qu: " + why)
+        X2 = X[0] if X.dim() == 3 else X
+        self._require_gpu(X2)
+        info = {}
+        with torch.no_grad():
+            Z, rl, ro, _, _, lvn = self._raw_params()
+            t = Y.detach().reshape(-1).contiguous()
+            if self._is_warped:
+                spec, theta, _ = self._flow_inputs(X2, with_grad=False)
+                if spec.nblk > 0:
+                    t = ops.flow_eval(t, spec, None if theta is None else theta.detach(), want=("G",))["G"]
+            elif self._has_mean:
+                t = self.mean_function.vector(X2.detach(), alpha=-1.0, inp=t)
+            m, Lam = ops.optimal_qu(X2.detach(), t, Z.detach(), rl.detach(), ro.detach(), lvn.detach(), self.N,
+                                    kernel=self.covariance_function.hip_kernel, info=info,
+                                    ladder=ops.jitter_ladder(jitter=cg.global_jitter))
+            self.q_U.variational_mean.data[0].copy_(m)
+            self.q_U.chol_variational_covar.data[0].copy_(Lam)
+        return info
+
+    def collapsed_bound(self, X, Y):
+        """(ELBO, ELL, KLD) at the optimal q(u) of the current hyper-parameters: Titsias' collapsed bound as a differentiable
+        function of Z, the kernel parameters, the noise and (where present) the mean's and the warp's parameters.  Forward:
+        set_optimal_qu, then the unchanged step at the jitter the optimum ended with.  Backward: the step's gradients for the
+        hyper-parameters; d ELBO / d q(u) vanishes at the optimum, so these ARE the collapsed bound's gradients (envelope
+        theorem) and q_U, a constant of the step here, receives none.  q_U holds the optimum afterwards."""
+        info = self.set_optimal_qu(X, Y)
+        return self.ELBO(X, Y, _qu_jitter=info["jitter"])
 
     def check_status(self):
         """Lazy Cholesky status check (cg.status_check = 'lazy'): raises like psd_safe_cholesky would have."""

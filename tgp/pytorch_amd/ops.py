@@ -582,6 +582,60 @@ class EllStepFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------------
+# closed-form optimal q(u) of the Gaussian likelihood (the maximiser behind the collapsed bound)
+# ---------------------------------------------------------------------------------------------------
+def kxxk(X, Z, raw_ls, raw_os, Y=None, kernel="scale_rbf", workspace_bytes=None):
+    """(C, b) = (K_ZX K_XZ (M, M), K_ZX y (M) or None) in one pass over the rows of X, K_ZX generated on chip (tgp_kxxk_f64).
+    C is exactly symmetric; fixed summation order: two calls give the same bits."""
+    lib = L.load()
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    Y = _c(None if Y is None else Y.reshape(-1), "Y")
+    N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape[1] != D or (Y is not None and Y.numel() != N):
+        raise ValueError("kxxk: X (N, D), Z (M, D), Y (N)")
+    dev = X.device
+    nbytes = lib.tgp_kxxk_workspace_bytes(N, M) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    C = torch.empty(M, M, dtype=torch.float64, device=dev)
+    b = torch.empty(M, dtype=torch.float64, device=dev) if Y is not None else None
+    L.check(lib.tgp_kxxk_f64(kernel_id(kernel), L.ptr(X), N, L.ptr(Z), M, D, L.ptr(raw_ls), L.ptr(raw_os), L.ptr(Y), L.ptr(C),
+                             L.ptr(b), L.ptr(ws), nbytes, L.stream_ptr()), "tgp_kxxk_f64")
+    return C, b
+
+
+def optimal_qu(X, Y, Z, raw_ls, raw_os, lvn, N_total, jitter=0.0, kernel="scale_rbf", info=None, check=True, ladder=None,
+               out=None, workspace_bytes=None):
+    """(m*, Lam*): the whitened q(u) = N(m*, Lam* Lam*^T) that maximises the Gaussian ELBO of `elbo_step` at these
+    hyper-parameters -- the q(u) behind the collapsed bound (tgp_optimal_qu_f64).  With K_ZZ + jitter I = L L^T,
+    c = N_total / N and sigma^2 = exp(lvn):  B = I + (c / sigma^2) L^-1 K_ZX K_XZ L^-T,  Lam* Lam*^T = B^-1,
+    m* = (c / sigma^2) B^-1 L^-1 K_ZX y.  The factorisation of K runs under psd_safe_cholesky's ladder as in qf_moments;
+    `info["jitter"]` receives the value it ended with.  `out` = (m, Lam): written in place.  No autograd."""
+    lib = L.load()
+    X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
+    Z, raw_ls, raw_os, lvn = _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os"), _c(lvn, "log_var_noise")
+    N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape[1] != D or Y.numel() != N:
+        raise ValueError("optimal_qu: X (N, D), Y (N), Z (M, D)")
+    dev = X.device
+    m, Lam = out if out is not None else (torch.empty(M, dtype=torch.float64, device=dev),
+                                          torch.empty(M, M, dtype=torch.float64, device=dev))
+    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, float(N_total) / float(N), jitter, 1.0, None, None, None, kernel)
+    nbytes = lib.tgp_optimal_qu_workspace_bytes(N, D, M) if workspace_bytes is None else int(workspace_bytes)
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    status = torch.zeros(8, dtype=torch.int32, device=dev)
+
+    def attempt(jit):
+        md.jitter = jit
+        L.check(lib.tgp_optimal_qu_f64(md, L.ptr(X), L.ptr(Y), L.ptr(m), L.ptr(Lam), L.ptr(status), L.ptr(ws), nbytes,
+                                       L.stream_ptr()), "tgp_optimal_qu_f64")
+        return check and _failed_pivot(status)
+    run_jitter_ladder(attempt, jitter, ladder, info=info)
+    return m, Lam
+
+
+# ---------------------------------------------------------------------------------------------------
 # mean functions (models/means.py): m(x) = x a + b on the rows of X, and its adjoint
 # ---------------------------------------------------------------------------------------------------
 def mean_forward(X, a, b=None, alpha=1.0, inp=None, out=None, col=0, one_col=-1):

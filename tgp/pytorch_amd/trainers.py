@@ -30,8 +30,21 @@ def return_optimizer(opt, parameters, lr):
 
 class Trainer_SP_regression:
     def __init__(self, model, data_loaders, validate_each, plot, track, Y_std, plot_each, S_test,
-                 inference_in_cpu=False, coverage="sampled"):
+                 inference_in_cpu=False, coverage="sampled", qu="adam"):
         self.model = model
+        # q(u): "adam" = m and Lam are trained like every other parameter (the reference); "optimal" = they are set to their
+        # closed-form optimum before every step and every evaluation and the optimiser trains the hyper-parameters on the
+        # collapsed bound (models.collapsed_bound: Gaussian and warped likelihoods, whitened, one full batch per epoch)
+        if qu not in ("adam", "optimal"):
+            raise ValueError("qu must be 'adam' or 'optimal', got %r" % (qu,))
+        self.qu = qu
+        if qu == "optimal":
+            why = model._qu_refusal() if hasattr(model, "_qu_refusal") else "the model has no set_optimal_qu"
+            if why is not None:
+                raise NotImplementedError("qu='optimal': " + why)
+            if len(data_loaders[0]) != 1:
+                raise NotImplementedError("qu='optimal' takes one full batch per epoch: the optimum of q(u) belongs to the rows "
+                                          "it was computed from (minibatch collapsed steps are not built)")
         # coverage of the 95 % interval: "sampled" = order statistics of S_test predictive draws per row, on the host (the
         # reference, trainers_regression.py:171); "exact" = the 2.5 % / 97.5 % roots of the predictive CDF, on the device
         if coverage not in ("sampled", "exact"):
@@ -70,6 +83,8 @@ class Trainer_SP_regression:
         holds already (keep_parameter_groups=True) -- skipped, and naming one again is an error like in the reference.
         Returns (groups, names placed in them)."""
         named = OrderedDict(self.model.named_parameters())
+        if self.qu == "optimal":         # q(u) is a function of the other parameters here: no optimiser holds it
+            named = OrderedDict((n, q) for n, q in named.items() if not n.startswith("q_U."))
         taken, frozen, groups, placed = set(), set(), [], []
         seen_keys = set()
         for sp in (specs or []):
@@ -123,6 +138,8 @@ class Trainer_SP_regression:
         from .likelihoods import Bernoulli, GaussianLinearMean, MulticlassCategorical, WarpedGaussianLinearMean
         if not getattr(cg, "use_step_engine", True) or opt != "adam":
             return None
+        if self.qu == "optimal":
+            return self._collapsed_engine_for(groups, lr_ALL)
         ld = self.train_loader
         if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1:
             return None
@@ -202,6 +219,52 @@ class Trainer_SP_regression:
         eng.capture()
         return eng
 
+    def _collapsed_engine_for(self, groups, lr_ALL):
+        """qu="optimal": the collapsed step engine (engine.ElboEngine(collapsed=True): optimal q(u) -> the unchanged step -> Adam
+        on the hyper-parameters, captured) for the Gaussian likelihood with a zero mean on one full batch from a
+        data.DeviceLoader, every parameter but q(u) trained at one learning rate.  None otherwise: the eager loop
+        (models.collapsed_bound + the torch optimiser) then serves the run."""
+        from .data import DeviceLoader
+        from .engine import ElboEngine, collapsed_refusal
+        ld, model = self.train_loader, self.model
+        if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1 or len(ld) != 1:
+            return None
+        mean_fn = model.mean_function if model._has_mean else None
+        if collapsed_refusal(likelihood="warped" if model._is_warped else None,
+                             mean=None if mean_fn is None else (mean_fn.name,)) is not None:
+            return None
+        if any(g["lr"] != lr_ALL or g["weight_decay"] != 0.0 for g in groups):
+            return None
+        if {id(q) for g in groups for q in g["params"]} != {id(q) for n, q in model.named_parameters() if not n.startswith("q_U.")}:
+            return None
+        Z, rl, ro, m, Lam, lvn = model._raw_params()
+        params = {"Z": Z.detach(), "raw_lengthscale": rl.detach(), "raw_outputscale": ro.detach(), "m": m.detach(),
+                  "Lam": Lam.detach(), "log_var_noise": lvn.detach()}
+        eng = ElboEngine(ld.X, ld.Y, params, float(model.N), device=ld.X.device, lr=lr_ALL,
+                         kernel=model.covariance_function.hip_kernel,
+                         jitter_ladder=cg.global_jitter if cg.global_jitter is not None else 1e-8, collapsed=True)
+        fp, k = eng.fp, model.covariance_function
+        with torch.no_grad():
+            model.Z.data = fp.view("Z").view_as(model.Z)
+            k.base_kernel.raw_lengthscale.data = fp.view("raw_ls").view_as(k.base_kernel.raw_lengthscale)
+            k.raw_outputscale.data = fp.view("raw_os").view_as(k.raw_outputscale)
+            model.q_U.variational_mean.data = fp.view("m").view_as(model.q_U.variational_mean)
+            model.q_U.chol_variational_covar.data = fp.view("Lam").view_as(model.q_U.chol_variational_covar)
+            model.likelihood.log_var_noise.data = fp.view("lvn").view_as(model.likelihood.log_var_noise)
+        eng.capture()
+        return eng
+
+    def refresh_qu(self):
+        """qu="optimal": q(u) <- its optimum at the current hyper-parameters, on the training rows (before every evaluation; the
+        last training step left the optimum of the hyper-parameters it started from)."""
+        if self.qu != "optimal":
+            return
+        if self._engine is not None:
+            self._engine.refresh_qu()
+            return
+        for x, y in self.train_loader:
+            self.model.set_optimal_qu(x.to(cg.device), y.to(cg.device))
+
     def _train_resident(self, eng, n_epochs, epochs_total):
         from .engine import MinibatchEngine
         mb = isinstance(eng, MinibatchEngine)
@@ -236,7 +299,7 @@ class Trainer_SP_regression:
         self.KLD_arr += h[:, 2].tolist()
 
     def ELBO_call(self, x, y):
-        loss, elogl, kld = self.model.ELBO(x, y)
+        loss, elogl, kld = self.model.collapsed_bound(x, y) if self.qu == "optimal" else self.model.ELBO(x, y)
         loss = -loss
         self.param_elbo = [loss, elogl, kld]
         return loss
@@ -291,6 +354,7 @@ class Trainer_SP_regression:
                     self.optimizer.add_param_group(g)
                 self._names_added += placed
             self._train_eager(n_ep, epochs)
+        self.refresh_qu()
         if not keep_parameter_groups:
             self.optimizer = None
             self._engine = None
@@ -359,6 +423,7 @@ class Trainer_SP_regression:
 
     def compute_metrics(self):
         """(logL, rmse, coverage) for train, valid, test -- nine floats like the reference."""
+        self.refresh_qu()
         out = list(self._loader_metrics(self.train_loader))
         out += list(self._loader_metrics(self.valid_loader)) if self.is_valid else [0.0, 0.0, 0.0]
         out += list(self._loader_metrics(self.test_loader)) if self.is_test else [0.0, 0.0, 0.0]
