@@ -177,18 +177,25 @@ size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int3
   return d * sizeof(double);
 }
 
+// The workspace of a TGP_LIK_WARPED step: the Gaussian step's (gauss_bytes, gauss_doubles of it rounded to 2), then t = T(Y),
+// mu, v (N each) and the partials of k_ell_warp.  All zero when the Gaussian step has no plan for the shape.
+struct WarpedLayout {
+  size_t gauss_bytes, gauss_doubles, total_bytes;
+};
+static WarpedLayout warped_layout(int N, int D, int M, int S, int P, int kernel, int plan) {
+  const size_t g = tgp_workspace_bytes_plan(N, D, M, S, 0, 0, 0, kernel, plan);
+  if (g == 0) return {0, 0, 0};
+  const size_t gd = rup(g / sizeof(double), 2);
+  return {g, gd, (gd + 3 * (size_t)N + warp_workspace_doubles(N, P)) * sizeof(double)};
+}
+
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik) {
   if (lik == TGP_LIK_BERNOULLI) {
     const size_t big = big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan);
     return big == 0 ? 0 : big * sizeof(double);
   }
-  if (lik == TGP_LIK_WARPED) {
-    // the Gaussian step's workspace, then t = T(Y), mu, v (N each) and the partials of k_ell_warp
-    const size_t g = tgp_workspace_bytes_plan(N, D, M, S, 0, 0, 0, kernel, plan);
-    if (g == 0 || N < 1 || P < 0) return 0;
-    return (rup(g / sizeof(double), 2) + 3 * (size_t)N + warp_workspace_doubles(N, P)) * sizeof(double);
-  }
+  if (lik == TGP_LIK_WARPED) return N < 1 || P < 0 ? 0 : warped_layout(N, D, M, S, P, kernel, plan).total_bytes;
   return tgp_workspace_bytes_plan(N, D, M, S, nblk, P, RP, kernel, plan);
 }
 
@@ -224,12 +231,11 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
     if (check_adam(adam)) return -12;
     if (model->P > 0 && (grads->theta < adam->grads || grads->theta + model->P > adam->grads + adam->n)) return -12;
   }
-  const size_t gbytes = tgp_workspace_bytes_plan(model->N, model->D, model->M, model->S, 0, 0, 0, model->kernel, model->plan);
-  if (gbytes == 0) return TGP_E_UNSUPPORTED;
-  const size_t gd = rup(gbytes / sizeof(double), 2), N = (size_t)model->N;
-  if (workspace_bytes < (gd + 3 * N + warp_workspace_doubles(model->N, model->P)) * sizeof(double)) return TGP_E_WORKSPACE;
-  double* ws = static_cast<double*>(workspace);
-  double* t = ws + gd;
+  const WarpedLayout wl = warped_layout(model->N, model->D, model->M, model->S, model->P, model->kernel, model->plan);
+  if (wl.total_bytes == 0) return TGP_E_UNSUPPORTED;
+  if (workspace_bytes < wl.total_bytes) return TGP_E_WORKSPACE;
+  const size_t N = (size_t)model->N;
+  double* t = static_cast<double*>(workspace) + wl.gauss_doubles;
   double* mu_w = mu ? mu : t + N;
   double* v_w = v ? v : t + 2 * N;
   double* part = t + 3 * N;
@@ -247,7 +253,7 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
   const tgp_model mg = gauss_copy(*model);
   tgp_grads gg = *grads;
   gg.theta = nullptr; gg.rowp = nullptr;
-  if (int rc = elbo_step_impl(&mg, X, t, nullptr, out, &gg, mu_w, v_w, status, workspace, gbytes, phases, nullptr, stream))
+  if (int rc = elbo_step_impl(&mg, X, t, nullptr, out, &gg, mu_w, v_w, status, workspace, wl.gauss_bytes, phases, nullptr, stream))
     return rc;
   if (!(phases & TGP_PHASE_BACKWARD)) return 0;
   if (warp)
@@ -532,12 +538,9 @@ int tgp_cholesky_f64(const double* A, int32_t M, double* L, double* Linv, int32_
   if (M > TGP_BIG_MAX_M) return TGP_E_UNSUPPORTED;
   if (!L) return -3;
   if (!status) return -5;
-  if (M > TGP_FUSED_MAX_M) {  // blocked multi-kernel factorisation of the general-M path; needs tgp_cholesky_workspace_bytes(M)
-    if (!workspace) return -6;
-    return launch_big_cholesky(A, M, L, Linv, status, static_cast<double*>(workspace), workspace_bytes / sizeof(double),
-                               static_cast<hipStream_t>(stream));
-  }
-  return launch_cholesky(A, M, L, Linv, status, static_cast<hipStream_t>(stream));
+  if (M > TGP_FUSED_MAX_M && !workspace) return -6;  // the blocked factorisation needs tgp_cholesky_workspace_bytes(M)
+  return launch_cholesky_any(A, M, L, Linv, status, static_cast<double*>(workspace), workspace_bytes / sizeof(double),
+                             static_cast<hipStream_t>(stream));
 }
 
 int tgp_cholesky_bwd_f64(const double* L, const double* Linv, const double* L_bar, int32_t M, double* A_bar, void* workspace,

@@ -266,85 +266,60 @@ __global__ __launch_bounds__(256) void k_joint_draw(const double* __restrict__ m
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
-struct CovPlan {  // offsets in doubles, every section a multiple of 64 doubles
+struct CovPlan : Layout {
   int MP, NP;
-  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, Lq, W, A, C, total;
+  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, Lq, W, A, C;
 };
 bool cov_plan(CovPlan& p, int N, int D, int M) {
   if (N < 1 || N > TGP_BIG_MAX_M || M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
   p.MP = (int)rup((size_t)M, 128);
   p.NP = (int)rup((size_t)N, 128);
-  const size_t mm = rup((size_t)M * M, 64), pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
-  p.chol_len = M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0;
-  size_t o = 0;
-  p.Kmm = o; o += mm;
-  p.Lf = o; o += mm;
-  p.Linv = o; o += mm;
-  p.chol = o; o += p.chol_len;
-  p.LinvP = o; o += pp;
-  p.Lq = o; o += pp;
-  p.W = o; o += pp;
-  p.A = o; o += pn;
-  p.C = o; o += pn;
-  p.total = o;
+  const size_t mm = (size_t)M * M, pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
+  p.chol_len = chol_ws_doubles(M);
+  p.Kmm = p.take(mm);
+  p.Lf = p.take(mm);
+  p.Linv = p.take(mm);
+  p.chol = p.take(p.chol_len);
+  p.LinvP = p.take(pp);
+  p.Lq = p.take(pp);
+  p.W = p.take(pp);
+  p.A = p.take(pn);
+  p.C = p.take(pn);
   return true;
 }
-struct DrawPlan {
-  size_t Sj, Lf, chol, chol_len, total;
+struct DrawPlan : Layout {
+  size_t Sj, Lf, chol, chol_len;
 };
 bool draw_plan(DrawPlan& p, int N, int S) {
   if (N < 1 || N > TGP_BIG_MAX_M || S < 1 || S > 4096) return false;
-  const size_t nn = rup((size_t)N * N, 64);
-  p.chol_len = N > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(N), 64) : 0;
-  size_t o = 0;
-  p.Sj = o; o += nn;
-  p.Lf = o; o += nn;
-  p.chol = o; o += p.chol_len;
-  p.total = o;
+  p.chol_len = chol_ws_doubles(N);
+  p.Sj = p.take((size_t)N * N);
+  p.Lf = p.take((size_t)N * N);
+  p.chol = p.take(p.chol_len);
   return true;
-}
-// the workspace's first 16-byte aligned double (the byte counts below include the slack)
-double* align16(void* ws, size_t bytes, size_t* doubles) {
-  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
-  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
-  *doubles = bytes > skip ? (bytes - skip) / sizeof(double) : 0;
-  return reinterpret_cast<double*>(a);
-}
-int factorise(const double* A, int M, double* Lo, double* Jo, int32_t* status, double* cws, size_t cws_len, hipStream_t st) {
-  if (M > TGP_FUSED_MAX_M) return launch_big_cholesky(A, M, Lo, Jo, status, cws, cws_len, st);
-  return launch_cholesky(A, M, Lo, Jo, status, st);
 }
 }  // namespace
 
 size_t qf_cov_workspace_bytes(int N, int D, int M) {
   CovPlan p;
-  if (!cov_plan(p, N, D, M)) return 0;
-  return p.total * sizeof(double) + 16;
+  return cov_plan(p, N, D, M) ? p.bytes() : 0;
 }
 
 size_t qf_joint_sample_workspace_bytes(int N, int S) {
   DrawPlan p;
-  if (!draw_plan(p, N, S)) return 0;
-  return p.total * sizeof(double) + 16;
+  return draw_plan(p, N, S) ? p.bytes() : 0;
 }
 
 int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
                   size_t workspace_bytes, hipStream_t st) {
   CovPlan p;
-  if (!cov_plan(p, md.N, md.D, md.M)) {
-    set_error_text("tgp_qf_cov_f64: N = %d, D = %d, M = %d outside 1 <= N, M <= %d, 1 <= D <= 16", md.N, md.D, md.M, TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = align16(workspace, workspace_bytes, &have);
-  if (have < p.total) {
-    set_error_text("tgp_qf_cov_f64: workspace of %zu bytes, tgp_qf_cov_workspace_bytes gives %zu", workspace_bytes,
-                   p.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
+  if (!cov_plan(p, md.N, md.D, md.M)) return TGP_E_UNSUPPORTED;  // (tgp_qf_cov_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_qf_cov_f64", "tgp_qf_cov_workspace_bytes", workspace, workspace_bytes, p.total, &ws)) return rc;
   const int N = md.N, D = md.D, M = md.M, MP = p.MP, NP = p.NP;
-  if (int rc = launch_kernel_matrix(md.kernel, md.Z, M, nullptr, 0, D, md.raw_ls, md.raw_os, md.jitter, ws + p.Kmm, st)) return rc;
-  if (int rc = factorise(ws + p.Kmm, M, ws + p.Lf, ws + p.Linv, status, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, M, D, md.jitter, ws + p.Kmm, ws + p.Lf, ws + p.Linv, status,
+                                 ws + p.chol, p.chol_len, st))
+    return rc;
   hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, md.Lam, ws + p.Linv, M, MP, ws + p.Lq,
                      ws + p.W, ws + p.LinvP);
   LAUNCH_CHECK();
@@ -363,21 +338,15 @@ int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigm
 int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double jitter, const double* eps, int S, double* F0,
                            double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st) {
   DrawPlan p;
-  if (!draw_plan(p, N, S)) {
-    set_error_text("tgp_qf_joint_sample_f64: N = %d, S = %d outside 1 <= N <= %d, 1 <= S <= 4096", N, S, TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = align16(workspace, workspace_bytes, &have);
-  if (have < p.total) {
-    set_error_text("tgp_qf_joint_sample_f64: workspace of %zu bytes, tgp_qf_joint_sample_workspace_bytes gives %zu",
-                   workspace_bytes, p.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
+  if (!draw_plan(p, N, S)) return TGP_E_UNSUPPORTED;  // (tgp_qf_joint_sample_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_qf_joint_sample_f64", "tgp_qf_joint_sample_workspace_bytes", workspace, workspace_bytes, p.total,
+                              &ws))
+    return rc;
   double* Lf = Lsig != nullptr ? Lsig : ws + p.Lf;
   hipLaunchKernelGGL(k_joint_jit, dim3((unsigned)(((size_t)N * N + 255) / 256)), dim3(256), 0, st, Sigma, N, jitter, ws + p.Sj);
   LAUNCH_CHECK();
-  if (int rc = factorise(ws + p.Sj, N, Lf, nullptr, status, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = launch_cholesky_any(ws + p.Sj, N, Lf, nullptr, status, ws + p.chol, p.chol_len, st)) return rc;
   hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((N + COV_T - 1) / COV_T), (unsigned)((S + 15) / 16)), dim3(256), 0, st, mu, Lf, N,
                      eps, S, F0);
   LAUNCH_CHECK();

@@ -81,6 +81,45 @@ int launch_big_cholesky_bwd(const double* L, const double* Linv, const double* L
 int launch_gemm_plain(bool ta, bool tb, int tri, int m, int n, int k, double alpha, const double* A, int lda, const double* B,
                       int ldb, double beta, double* C, int ldc, hipStream_t st);
 
+// One factorisation for every M <= TGP_BIG_MAX_M: the single-workgroup kernel up to TGP_FUSED_MAX_M, above it the blocked one,
+// which alone needs scratch -- chol_ws_doubles(M) doubles at `cws`, a whole number of 64-double sections.
+inline size_t chol_ws_doubles(int M) { return M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0; }
+inline int launch_cholesky_any(const double* A, int M, double* L, double* Linv, int32_t* status, double* cws, size_t cws_len,
+                               hipStream_t st) {
+  if (M > TGP_FUSED_MAX_M) return launch_big_cholesky(A, M, L, Linv, status, cws, cws_len, st);
+  return launch_cholesky(A, M, L, Linv, status, st);
+}
+// Kmm = K_ZZ + jitter I, then its factor L and L^-1 with `status`: how every operator on the inducing points opens
+inline int launch_kzz_factor(int kernel, const double* Z, const double* raw_ls, const double* raw_os, int M, int D, double jitter,
+                             double* Kmm, double* L, double* Linv, int32_t* status, double* cws, size_t cws_len, hipStream_t st) {
+  if (int rc = launch_kernel_matrix(kernel, Z, M, nullptr, 0, D, raw_ls, raw_os, jitter, Kmm, st)) return rc;
+  return launch_cholesky_any(Kmm, M, L, Linv, status, cws, cws_len, st);
+}
+
+// The workspace of a stand-alone operator (tgp_cov.hip, tgp_unwhiten.hip, tgp_optqu.hip): sections of whole 64-double blocks,
+// laid out in the order they are taken.  Its byte count carries 16 bytes of slack for open_workspace.
+struct Layout {
+  size_t total = 0;  // doubles
+  size_t take(size_t n_doubles) {
+    const size_t o = total;
+    total += rup(n_doubles, 64);
+    return o;
+  }
+  size_t bytes() const { return total * sizeof(double) + 16; }
+};
+// *first = the first 16-byte aligned double of the caller's workspace `ws`; refused when fewer than need_doubles follow it
+inline int open_workspace(const char* entry, const char* sizer, void* ws, size_t ws_bytes, size_t need_doubles, double** first) {
+  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
+  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
+  const size_t have = ws_bytes > skip ? (ws_bytes - skip) / sizeof(double) : 0;
+  if (have < need_doubles) {
+    set_error_text("%s: workspace of %zu bytes, %s gives %zu", entry, ws_bytes, sizer, need_doubles * sizeof(double) + 16);
+    return TGP_E_WORKSPACE;
+  }
+  *first = reinterpret_cast<double*>(a);
+  return 0;
+}
+
 // tgp_kmeans.hip
 int launch_kmeans_assign(const double* X, int N, int D, const double* C, int K, int32_t* labels, double* mind2, hipStream_t st);
 int launch_kmeans_segsum(const double* X, int D, const int64_t* order, const int64_t* offs, int K, double* sums, hipStream_t st);

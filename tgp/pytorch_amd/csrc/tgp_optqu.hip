@@ -237,9 +237,9 @@ __global__ __launch_bounds__(256) void k_optqu_mv(const double* __restrict__ A, 
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
-struct KxPlan {  // the row split of k_kxxk: a function of N and M alone
+struct KxPlan : Layout {  // the row split of k_kxxk: a function of N and M alone
   int nti, ntile, G, ngroup;
-  size_t part, bpart, total;  // offsets in doubles
+  size_t part, bpart;
 };
 bool kx_plan(KxPlan& p, int N, int M) {
   if (N < 1 || M < 1 || M > TGP_BIG_MAX_M) return false;
@@ -249,49 +249,36 @@ bool kx_plan(KxPlan& p, int N, int M) {
   const size_t g = rup(((size_t)N + want - 1) / want, OQ_KC);
   p.G = g > OQ_MIN_G ? (int)g : OQ_MIN_G;
   p.ngroup = (N + p.G - 1) / p.G;  // <= want <= OQ_WGS
-  p.part = 0;
-  p.bpart = rup((size_t)p.ngroup * p.ntile * OQ_T * OQ_T, 64);
-  p.total = p.bpart + rup((size_t)p.ngroup * p.nti * OQ_T, 64);
+  p.part = p.take((size_t)p.ngroup * p.ntile * OQ_T * OQ_T);
+  p.bpart = p.take((size_t)p.ngroup * p.nti * OQ_T);
   return true;
 }
-struct OqPlan {  // offsets in doubles, every section a multiple of 64 doubles
+struct OqPlan : Layout {
   int MP;
   // Kmm is J B J later, Lf is L', CP is Lam*^T and T is L'^-1 once their first contents have been consumed
-  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, CP, T, Phi, C, b, v1, v2, st2, kx, total;
+  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, CP, T, Phi, C, b, v1, v2, st2, kx;
   KxPlan k;
 };
 bool oq_plan(OqPlan& p, int N, int D, int M) {
   if (D < 1 || D > 16 || !kx_plan(p.k, N, M)) return false;
   p.MP = (int)rup((size_t)M, 128);
-  const size_t mm = rup((size_t)M * M, 64), pp = (size_t)p.MP * p.MP, mv = rup((size_t)M, 64);
-  p.chol_len = M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0;
-  size_t o = 0;
-  p.Kmm = o; o += mm;
-  p.Lf = o; o += mm;
-  p.Linv = o; o += mm;
-  p.chol = o; o += p.chol_len;
-  p.LinvP = o; o += pp;
-  p.CP = o; o += pp;
-  p.T = o; o += pp;
-  p.Phi = o; o += pp;
-  p.C = o; o += mm;
-  p.b = o; o += mv;
-  p.v1 = o; o += mv;
-  p.v2 = o; o += mv;
-  p.st2 = o; o += 64;
-  p.kx = o; o += p.k.total;
-  p.total = o;
+  const size_t mm = (size_t)M * M, pp = (size_t)p.MP * p.MP;
+  p.chol_len = chol_ws_doubles(M);
+  p.Kmm = p.take(mm);
+  p.Lf = p.take(mm);
+  p.Linv = p.take(mm);
+  p.chol = p.take(p.chol_len);
+  p.LinvP = p.take(pp);
+  p.CP = p.take(pp);
+  p.T = p.take(pp);
+  p.Phi = p.take(pp);
+  p.C = p.take(mm);
+  p.b = p.take(M);
+  p.v1 = p.take(M);
+  p.v2 = p.take(M);
+  p.st2 = p.take(64);
+  p.kx = p.take(p.k.total);
   return true;
-}
-double* oq_align16(void* ws, size_t bytes, size_t* doubles) {
-  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
-  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
-  *doubles = bytes > skip ? (bytes - skip) / sizeof(double) : 0;
-  return reinterpret_cast<double*>(a);
-}
-int oq_factorise(const double* A, int M, double* Lo, double* Jo, int32_t* status, double* cws, size_t cws_len, hipStream_t st) {
-  if (M > TGP_FUSED_MAX_M) return launch_big_cholesky(A, M, Lo, Jo, status, cws, cws_len, st);
-  return launch_cholesky(A, M, Lo, Jo, status, st);
 }
 int run_kxxk(const KxPlan& k, int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls,
              const double* raw_os, const double* Y, double* C, double* b, double* ws, hipStream_t st) {
@@ -312,54 +299,37 @@ int run_kxxk(const KxPlan& k, int kernel, const double* X, int N, const double* 
 
 size_t kxxk_workspace_bytes(int N, int M) {
   KxPlan k;
-  if (!kx_plan(k, N, M)) return 0;
-  return k.total * sizeof(double) + 16;
+  return kx_plan(k, N, M) ? k.bytes() : 0;
 }
 
 size_t optimal_qu_workspace_bytes(int N, int D, int M) {
   OqPlan p;
-  if (!oq_plan(p, N, D, M)) return 0;
-  return p.total * sizeof(double) + 16;
+  return oq_plan(p, N, D, M) ? p.bytes() : 0;
 }
 
 int launch_kxxk(int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls, const double* raw_os,
                 const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes, hipStream_t st) {
   KxPlan k;
-  if (D < 1 || D > 16 || !kx_plan(k, N, M)) {
-    set_error_text("tgp_kxxk_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", N, D, M, TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = oq_align16(workspace, workspace_bytes, &have);
-  if (have < k.total) {
-    set_error_text("tgp_kxxk_f64: workspace of %zu bytes, tgp_kxxk_workspace_bytes gives %zu", workspace_bytes,
-                   k.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
+  if (D < 1 || D > 16 || !kx_plan(k, N, M)) return TGP_E_UNSUPPORTED;  // (tgp_kxxk_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_kxxk_f64", "tgp_kxxk_workspace_bytes", workspace, workspace_bytes, k.total, &ws)) return rc;
   return run_kxxk(k, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, ws, st);
 }
 
 int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
                       void* workspace, size_t workspace_bytes, hipStream_t st) {
   OqPlan p;
-  if (!oq_plan(p, md.N, md.D, md.M)) {
-    set_error_text("tgp_optimal_qu_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", md.N, md.D, md.M,
-                   TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = oq_align16(workspace, workspace_bytes, &have);
-  if (have < p.total) {
-    set_error_text("tgp_optimal_qu_f64: workspace of %zu bytes, tgp_optimal_qu_workspace_bytes gives %zu", workspace_bytes,
-                   p.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
+  if (!oq_plan(p, md.N, md.D, md.M)) return TGP_E_UNSUPPORTED;  // (tgp_optimal_qu_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_optimal_qu_f64", "tgp_optimal_qu_workspace_bytes", workspace, workspace_bytes, p.total, &ws))
+    return rc;
   const int N = md.N, D = md.D, M = md.M, MP = p.MP;
   const unsigned gmm = (unsigned)(((size_t)M * M + 255) / 256), gpp = (unsigned)((size_t)MP * MP / 256), gmv = (unsigned)((M + 3) / 4);
   int32_t* st2 = reinterpret_cast<int32_t*>(ws + p.st2);
   double *Bm = ws + p.Kmm, *Lp = ws + p.Lf, *Lpinv = ws + p.T, *LamT = ws + p.CP;  // second lives of consumed sections
-  if (int rc = launch_kernel_matrix(md.kernel, md.Z, M, nullptr, 0, D, md.raw_ls, md.raw_os, md.jitter, ws + p.Kmm, st)) return rc;
-  if (int rc = oq_factorise(ws + p.Kmm, M, ws + p.Lf, ws + p.Linv, status, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, M, D, md.jitter, ws + p.Kmm, ws + p.Lf, ws + p.Linv, status,
+                                 ws + p.chol, p.chol_len, st))
+    return rc;
   if (int rc = run_kxxk(p.k, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os, Y, ws + p.C, ws + p.b, ws + p.kx, st)) return rc;
   hipLaunchKernelGGL(k_optqu_pad, dim3(gpp), dim3(256), 0, st, ws + p.Linv, ws + p.C, M, MP, ws + p.LinvP, ws + p.CP, st2);
   LAUNCH_CHECK();
@@ -367,7 +337,7 @@ int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, dou
   if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.T, MP, ws + p.LinvP, MP, 0.0, ws + p.Phi, MP, st)) return rc;
   hipLaunchKernelGGL(k_optqu_b, dim3(gmm), dim3(256), 0, st, ws + p.Phi, MP, M, md.log_var_noise, md.scale, Bm);
   LAUNCH_CHECK();
-  if (int rc = oq_factorise(Bm, M, Lp, Lpinv, st2, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = launch_cholesky_any(Bm, M, Lp, Lpinv, st2, ws + p.chol, p.chol_len, st)) return rc;
   hipLaunchKernelGGL(k_optqu_lam, dim3(gmm), dim3(256), 0, st, Lpinv, M, Lam_out, LamT, st2, status);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_optqu_mv, dim3(gmv), dim3(256), 0, st, ws + p.LinvP, MP, M, ws + p.b, nullptr, 1.0, ws + p.v1);

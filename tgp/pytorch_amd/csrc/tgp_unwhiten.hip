@@ -189,40 +189,28 @@ __global__ __launch_bounds__(64) void k_kmm_bwd_fin(const double* __restrict__ p
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
-struct UwPlan {  // offsets in doubles, every section a multiple of 64 doubles
-  size_t Kmm, chol, chol_len, total;
+struct UwPlan : Layout {
+  size_t Kmm, chol, chol_len;
 };
 bool uw_plan(UwPlan& p, int M, int D) {
   if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
-  p.chol_len = M > TGP_FUSED_MAX_M ? rup(big_cholesky_workspace_doubles(M), 64) : 0;
-  size_t o = 0;
-  p.Kmm = o; o += rup((size_t)M * M, 64);
-  p.chol = o; o += p.chol_len;
-  p.total = o;
+  p.chol_len = chol_ws_doubles(M);
+  p.Kmm = p.take((size_t)M * M);
+  p.chol = p.take(p.chol_len);
   return true;
 }
-struct UwBwdPlan {
-  size_t P, Lbar, Kbar, part, chol, chol_len, total;
+struct UwBwdPlan : Layout {
+  size_t P, Lbar, Kbar, part, chol, chol_len;
 };
 bool uw_bwd_plan(UwBwdPlan& p, int M, int D) {
   if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
-  const size_t mm = rup((size_t)M * M, 64);
-  p.chol_len = rup(big_cholesky_workspace_doubles(M), 64);
-  size_t o = 0;
-  p.P = o; o += mm;
-  p.Lbar = o; o += mm;
-  p.Kbar = o; o += mm;
-  p.part = o; o += rup((size_t)M * 17, 64);
-  p.chol = o; o += p.chol_len;
-  p.total = o;
+  p.chol_len = rup(big_cholesky_workspace_doubles(M), 64);  // (the adjoint runs the blocked path at every M)
+  p.P = p.take((size_t)M * M);
+  p.Lbar = p.take((size_t)M * M);
+  p.Kbar = p.take((size_t)M * M);
+  p.part = p.take((size_t)M * 17);
+  p.chol = p.take(p.chol_len);
   return true;
-}
-// the workspace's first 16-byte aligned double (the byte counts below include the slack)
-double* uw_align16(void* ws, size_t bytes, size_t* doubles) {
-  const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
-  const size_t skip = a - reinterpret_cast<uintptr_t>(ws);
-  *doubles = bytes > skip ? (bytes - skip) / sizeof(double) : 0;
-  return reinterpret_cast<double*>(a);
 }
 template <int MODE>
 int launch_tri(const double* A, const double* B, int M, double alpha, double* C, const double* vin, double* vout, const double* ru,
@@ -236,37 +224,24 @@ int launch_tri(const double* A, const double* B, int M, double alpha, double* C,
 
 size_t unwhiten_workspace_bytes(int M, int D) {
   UwPlan p;
-  if (!uw_plan(p, M, D)) return 0;
-  return p.total * sizeof(double) + 16;
+  return uw_plan(p, M, D) ? p.bytes() : 0;
 }
 
 size_t unwhiten_bwd_workspace_bytes(int M, int D) {
   UwBwdPlan p;
-  if (!uw_bwd_plan(p, M, D)) return 0;
-  return p.total * sizeof(double) + 16;
+  return uw_bwd_plan(p, M, D) ? p.bytes() : 0;
 }
 
 int launch_unwhiten(int kernel, const double* Z, const double* raw_ls, const double* raw_os, int M, int D, double jitter,
                     const double* m, const double* Lq, double* m_w, double* Lam_w, double* L, double* Linv, int32_t* status,
                     void* workspace, size_t workspace_bytes, hipStream_t st) {
   UwPlan p;
-  if (!uw_plan(p, M, D)) {
-    set_error_text("tgp_unwhiten_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = uw_align16(workspace, workspace_bytes, &have);
-  if (have < p.total) {
-    set_error_text("tgp_unwhiten_f64: workspace of %zu bytes, tgp_unwhiten_workspace_bytes gives %zu", workspace_bytes,
-                   p.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
-  if (int rc = launch_kernel_matrix(kernel, Z, M, nullptr, 0, D, raw_ls, raw_os, jitter, ws + p.Kmm, st)) return rc;
-  if (M > TGP_FUSED_MAX_M) {
-    if (int rc = launch_big_cholesky(ws + p.Kmm, M, L, Linv, status, ws + p.chol, p.chol_len, st)) return rc;
-  } else {
-    if (int rc = launch_cholesky(ws + p.Kmm, M, L, Linv, status, st)) return rc;
-  }
+  if (!uw_plan(p, M, D)) return TGP_E_UNSUPPORTED;  // (tgp_unwhiten_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_unwhiten_f64", "tgp_unwhiten_workspace_bytes", workspace, workspace_bytes, p.total, &ws))
+    return rc;
+  if (int rc = launch_kzz_factor(kernel, Z, raw_ls, raw_os, M, D, jitter, ws + p.Kmm, L, Linv, status, ws + p.chol, p.chol_len, st))
+    return rc;
   return launch_tri<UW_FWD>(Linv, Lq, M, 1.0, Lam_w, m, m_w, nullptr, nullptr, st);
 }
 
@@ -275,17 +250,10 @@ int launch_unwhiten_bwd(int kernel, const double* Z, const double* raw_ls, const
                         double* m_bar, double* Lq_bar, double* Z_bar, double* raw_ls_bar, double* raw_os_bar, void* workspace,
                         size_t workspace_bytes, hipStream_t st) {
   UwBwdPlan p;
-  if (!uw_bwd_plan(p, M, D)) {
-    set_error_text("tgp_unwhiten_bwd_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
-    return TGP_E_UNSUPPORTED;
-  }
-  size_t have = 0;
-  double* ws = uw_align16(workspace, workspace_bytes, &have);
-  if (have < p.total) {
-    set_error_text("tgp_unwhiten_bwd_f64: workspace of %zu bytes, tgp_unwhiten_bwd_workspace_bytes gives %zu", workspace_bytes,
-                   p.total * sizeof(double) + 16);
-    return TGP_E_WORKSPACE;
-  }
+  if (!uw_bwd_plan(p, M, D)) return TGP_E_UNSUPPORTED;  // (tgp_unwhiten_bwd_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_unwhiten_bwd_f64", "tgp_unwhiten_bwd_workspace_bytes", workspace, workspace_bytes, p.total, &ws))
+    return rc;
   if (int rc = launch_tri<UW_ATB>(Linv, Lam_w_bar, M, 1.0, Lq_bar, m_w_bar, m_bar, nullptr, nullptr, st)) return rc;
   if (int rc = launch_tri<UW_ABT>(Lam_w_bar, Lam_w, M, 1.0, ws + p.P, nullptr, nullptr, m_w_bar, m_w, st)) return rc;
   if (int rc = launch_tri<UW_ATB>(Linv, ws + p.P, M, -1.0, ws + p.Lbar, nullptr, nullptr, nullptr, nullptr, st)) return rc;

@@ -357,9 +357,9 @@ class ElboEngine:
         self.fused_adam = (self.fused_update and self.world_size == 1 and self.comm is None and self.mlp is None
                            and self.mean is None and not self.collapsed)
         if self.collapsed:
-            self.qu_ws = torch.empty(max(self.lib.tgp_optimal_qu_workspace_bytes(self.N, self.D, self.M), 8) // 8 + 2,
-                                     dtype=torch.float64, device=self.device)
-            self.qu_status = torch.zeros(8, dtype=torch.int32, device=self.device)
+            # (16 bytes = 2 doubles of slack over what the sizer gives)
+            self.qu_ws, _ = ops._scratch(self.lib.tgp_optimal_qu_workspace_bytes(self.N, self.D, self.M) + 16, self.device)
+            self.qu_status = ops._status(self.device)
             self.step_tail = torch.zeros(2, dtype=torch.int32, device=self.device)    # the twin counter of the segments behind Lam
         self.pre_step = self.post_step = None   # callables launched (and captured) before / after the step: the minibatch gather
         self.pipeline_steps = True      # ID_TGP, one rank: capture the rotated unit (see capture())
@@ -440,7 +440,7 @@ class ElboEngine:
         self.rowp = rowp.to(self.device, torch.float64).contiguous() if rowp is not None else None
         self.g_rowp = torch.zeros_like(self.rowp) if self.rowp is not None else None
         self.step_dev = torch.zeros(2, dtype=torch.int32, device=self.device) if share is None else share.step_dev
-        self.status = torch.zeros(8, dtype=torch.int32, device=self.device) if share is None else share.status
+        self.status = ops._status(self.device) if share is None else share.status
 
     def _abi_structs(self, flow_blocks, S, scale, kernel, plan, jitter_ladder):
         """tgp_model and tgp_grads, built once: the pointers never change."""
@@ -471,8 +471,7 @@ class ElboEngine:
         self.ws = ops.new_workspace(self.N, self.D, self.M, md.S, md.nblk, md.P, md.RP, self.device, md.kernel, plan, md.lik)
         self.mean_ws = self.mlp_ws = None
         if self.mean == "linear":
-            self.mean_ws = torch.empty(max(self.lib.tgp_mean_backward_workspace_bytes(self.N, self.D), 8) // 8,
-                                       dtype=torch.float64, device=self.device)
+            self.mean_ws, _ = ops._scratch(self.lib.tgp_mean_backward_workspace_bytes(self.N, self.D), self.device)
         elif self.mean == "identity":
             self.mean_forward()      # W is fixed: the rows' parameters are written once
         if self.mlp is not None:

@@ -67,11 +67,7 @@ def kernel_id(kernel):
 
 def workspace_bytes(N, D, M, S, nblk, P, RP, kernel=0, plan=0, lik=L.LIK_GAUSS):
     """Bytes of device workspace one ELBO step of this shape needs: the one place the library is asked."""
-    if lik in (L.LIK_BERNOULLI, L.LIK_WARPED):
-        # Bernoulli: general-M path at every M; warped: targets, moments and partials behind the Gaussian step's buffer
-        nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
-    else:
-        nbytes = L.load().tgp_workspace_bytes_plan(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan))
+    nbytes = L.load().tgp_workspace_bytes_lik(N, D, M, max(S, 1), nblk, P, RP, kernel, int(plan), int(lik))
     if nbytes == 0:
         raise L.TgpError("unsupported problem shape N=%d D=%d M=%d (this build: D<=16, M<=4096)" % (N, D, M))
     return nbytes
@@ -85,13 +81,23 @@ def new_workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_G
 def workspace(N, D, M, S, nblk, P, RP, device, kernel=0, plan=0, lik=L.LIK_GAUSS):
     """The cached workspace of the stateless one-shot calls of this module: one buffer per shape and stream, valid for the
     duration of ONE call -- nothing that keeps state between calls may hold it."""
-    key = (N, D, M, S, nblk, P, RP, str(device), torch.cuda.current_stream().cuda_stream, kernel, int(plan))
-    if lik in (L.LIK_BERNOULLI, L.LIK_WARPED):
-        key += (lik,)
+    key = (N, D, M, S, nblk, P, RP, str(device), torch.cuda.current_stream().cuda_stream, kernel, int(plan), int(lik))
     buf = _ws_cache.get(key)
     if buf is None:
         buf = _ws_cache[key] = new_workspace(N, D, M, S, nblk, P, RP, device, kernel, plan, lik)
     return buf
+
+
+def _scratch(nbytes, device, override=None):
+    """(workspace, its byte count for the library) of a stand-alone operator whose sizer gave `nbytes`; `override` replaces
+    that count (tests of the library's refusal).  Never an empty tensor: the library wants an address."""
+    nbytes = int(nbytes if override is None else override)
+    return torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device), nbytes
+
+
+def _status(device):
+    """The zeroed status words of one call (include/tgp_hip.h: [0] pivot, [1] NaN, [3] expired waits, [4..7] hand-off words)."""
+    return torch.zeros(8, dtype=torch.int32, device=device)
 
 
 def _c(t, name):
@@ -166,7 +172,7 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
     ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
     g = {"Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os),
          "m": torch.empty_like(m), "Lam": torch.empty_like(Lam), "lvn": torch.empty_like(lvn)}
     gs = L.TgpGrads()
@@ -244,6 +250,15 @@ def _failed_pivot(status):
     """An `attempt` result from the status words of a call (one device sync): False, or the failing pivot."""
     status = status.cpu()
     return raise_for_status(status) and int(status[0])
+
+
+def _laddered(call, status, jitter, ladder=None, info=None, check=True, what="K_MM"):
+    """run_jitter_ladder around the library call `call(jit)` that factorises with `status`: the words are read after every
+    launch (one host sync each) unless `check` is false -- then there is one launch and no retry."""
+    def attempt(jit):
+        call(jit)
+        return check and raise_for_status(status.cpu())
+    return run_jitter_ladder(attempt, jitter, ladder, info, what)
 
 
 def elbo_step_safe(*args, global_jitter=None, **kw):
@@ -337,14 +352,13 @@ def qf_moments(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="sca
     ws = workspace(X.shape[0], X.shape[1], md.M, 1, 0, 0, 0, dev, md.kernel, plan)
     mu = torch.empty(X.shape[0], dtype=torch.float64, device=dev)
     v = torch.empty_like(mu)
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
 
-    def attempt(jit):
+    def call(jit):
         md.jitter = jit
         L.check(lib.tgp_qf_moments_f64(md, L.ptr(X), L.ptr(mu), L.ptr(v), L.ptr(status), L.ptr(ws), ws.numel() * 8,
                                        L.stream_ptr()), "tgp_qf_moments_f64")
-        return check and raise_for_status(status.cpu())
-    run_jitter_ladder(attempt, jitter, info=info)
+    _laddered(call, status, jitter, info=info, check=check)
     return mu, v
 
 
@@ -357,20 +371,18 @@ def qf_cov(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_r
     md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 1.0, kernel)
     dev = X.device
     N, D = X.shape
-    nbytes = lib.tgp_qf_cov_workspace_bytes(N, D, md.M) if workspace_bytes is None else int(workspace_bytes)
     if N > 4096:       # refused by the library before anything is allocated for an N x N result
         L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), None, None, None, None, 0, L.stream_ptr()), "tgp_qf_cov_f64")
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(lib.tgp_qf_cov_workspace_bytes(N, D, md.M), dev, workspace_bytes)
     mu = torch.empty(N, dtype=torch.float64, device=dev)
     Sigma = torch.empty(N, N, dtype=torch.float64, device=dev)
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
 
-    def attempt(jit):
+    def call(jit):
         md.jitter = jit
         L.check(lib.tgp_qf_cov_f64(md, L.ptr(X), L.ptr(mu), L.ptr(Sigma), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()),
                 "tgp_qf_cov_f64")
-        return check and raise_for_status(status.cpu())
-    run_jitter_ladder(attempt, jitter, info=info)
+    _laddered(call, status, jitter, info=info, check=check)
     return mu, Sigma
 
 
@@ -384,11 +396,10 @@ def qf_joint_sample(mu, Sigma, eps, jitter=0.0, want_L=False, workspace_bytes=No
         raise ValueError("qf_joint_sample: mu (N), Sigma (N, N), eps (S, N)")
     S = eps.shape[0]
     dev = mu.device
-    nbytes = lib.tgp_qf_joint_sample_workspace_bytes(N, S) if workspace_bytes is None else int(workspace_bytes)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(lib.tgp_qf_joint_sample_workspace_bytes(N, S), dev, workspace_bytes)
     F0 = torch.empty(S, N, dtype=torch.float64, device=dev)
     Ls = torch.empty(N, N, dtype=torch.float64, device=dev) if want_L else None
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
     L.check(lib.tgp_qf_joint_sample_f64(L.ptr(mu), L.ptr(Sigma), N, float(jitter), L.ptr(eps), S, L.ptr(F0), L.ptr(Ls),
                                         L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()), "tgp_qf_joint_sample_f64")
     return F0, Ls, status
@@ -421,7 +432,7 @@ def qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, mu_bar, v_bar, jitter=0.0, kern
     gs = L.TgpGrads()
     gs.Z, gs.raw_ls, gs.raw_os, gs.m, gs.Lam = (L.ptr(g[k]) for k in ("Z", "raw_ls", "raw_os", "m", "Lam"))
     gs.log_var_noise = L.ptr(glvn)
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
     rc = lib.tgp_qf_moments_bwd_f64(md, L.ptr(X), L.ptr(mu_bar), L.ptr(v_bar), gs, L.ptr(status), L.ptr(ws), ws.numel() * 8,
                                     L.stream_ptr())
     L.check(rc, "tgp_qf_moments_bwd_f64")
@@ -496,19 +507,16 @@ def unwhiten(Z, raw_ls, raw_os, m, L_q, jitter=0.0, check=True, kernel="scale_rb
                                      None, None, None, None, 0, L.stream_ptr()), "tgp_unwhiten_f64")
     if m.numel() != M or tuple(L_q.shape) != (M, M):
         raise ValueError("unwhiten: Z (M, D), m (M), L_q (M, M)")
-    if workspace_bytes is not None:
-        nbytes = int(workspace_bytes)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(nbytes, dev, workspace_bytes)
     m_w = torch.empty(M, dtype=torch.float64, device=dev)
     Lam_w, Lo, Li = (torch.empty(M, M, dtype=torch.float64, device=dev) for _ in range(3))
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    status = _status(dev)
 
-    def attempt(jit):
+    def call(jit):
         L.check(lib.tgp_unwhiten_f64(kid, L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, float(jit), L.ptr(m), L.ptr(L_q),
                                      L.ptr(m_w), L.ptr(Lam_w), L.ptr(Lo), L.ptr(Li), L.ptr(status), L.ptr(ws), nbytes,
                                      L.stream_ptr()), "tgp_unwhiten_f64")
-        return check and raise_for_status(status.cpu())
-    run_jitter_ladder(attempt, jitter, ladder, info)
+    _laddered(call, status, jitter, ladder, info, check)
     return m_w, Lam_w, Lo, Li
 
 
@@ -522,8 +530,7 @@ def unwhiten_bwd(Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w, m_w_bar, Lam_w_bar, kern
     if m_w_bar.numel() != M or tuple(Lam_w_bar.shape) != (M, M):
         raise ValueError("unwhiten_bwd: m_w_bar (M), Lam_w_bar (M, M)")
     dev = Z.device
-    nbytes = lib.tgp_unwhiten_bwd_workspace_bytes(M, D) if workspace_bytes is None else int(workspace_bytes)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(lib.tgp_unwhiten_bwd_workspace_bytes(M, D), dev, workspace_bytes)
     g = {"m": torch.empty(M, dtype=torch.float64, device=dev), "L_q": torch.empty(M, M, dtype=torch.float64, device=dev),
          "Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os)}
     L.check(lib.tgp_unwhiten_bwd_f64(kernel_id(kernel), L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, L.ptr(Lo), L.ptr(Li),
@@ -595,8 +602,7 @@ def kxxk(X, Z, raw_ls, raw_os, Y=None, kernel="scale_rbf", workspace_bytes=None)
     if Z.shape[1] != D or (Y is not None and Y.numel() != N):
         raise ValueError("kxxk: X (N, D), Z (M, D), Y (N)")
     dev = X.device
-    nbytes = lib.tgp_kxxk_workspace_bytes(N, M) if workspace_bytes is None else int(workspace_bytes)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(lib.tgp_kxxk_workspace_bytes(N, M), dev, workspace_bytes)
     C = torch.empty(M, M, dtype=torch.float64, device=dev)
     b = torch.empty(M, dtype=torch.float64, device=dev) if Y is not None else None
     L.check(lib.tgp_kxxk_f64(kernel_id(kernel), L.ptr(X), N, L.ptr(Z), M, D, L.ptr(raw_ls), L.ptr(raw_os), L.ptr(Y), L.ptr(C),
@@ -622,9 +628,8 @@ def optimal_qu(X, Y, Z, raw_ls, raw_os, lvn, N_total, jitter=0.0, kernel="scale_
     m, Lam = out if out is not None else (torch.empty(M, dtype=torch.float64, device=dev),
                                           torch.empty(M, M, dtype=torch.float64, device=dev))
     md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, float(N_total) / float(N), jitter, 1.0, None, None, None, kernel)
-    nbytes = lib.tgp_optimal_qu_workspace_bytes(N, D, M) if workspace_bytes is None else int(workspace_bytes)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
-    status = torch.zeros(8, dtype=torch.int32, device=dev)
+    ws, nbytes = _scratch(lib.tgp_optimal_qu_workspace_bytes(N, D, M), dev, workspace_bytes)
+    status = _status(dev)
 
     def attempt(jit):
         md.jitter = jit
@@ -667,8 +672,7 @@ def mean_backward(X, g, a=None, col=0, want_b=True, want_X=False):
         raise ValueError("mean_backward: X (N, D), g (N) or (N, ld), a (D) when g_X is wanted")
     ldg = g.shape[1] if g.dim() == 2 else 1
     dev = X.device
-    nbytes = lib.tgp_mean_backward_workspace_bytes(N, D)
-    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = _scratch(lib.tgp_mean_backward_workspace_bytes(N, D), dev)
     g_a = torch.empty(D, dtype=torch.float64, device=dev)
     g_b = torch.empty(1, dtype=torch.float64, device=dev) if want_b else None
     g_X = torch.empty(N, D, dtype=torch.float64, device=dev) if want_X else None
@@ -746,7 +750,7 @@ def cholesky(A, want_inverse=False):
     M = A.shape[0]
     Lo = torch.empty_like(A)
     Li = torch.empty_like(A) if want_inverse else None
-    status = torch.zeros(8, dtype=torch.int32, device=A.device)
+    status = _status(A.device)
     nws = lib.tgp_cholesky_workspace_bytes(M)
     ws = torch.empty(nws // 8 + 16, dtype=torch.float64, device=A.device) if nws else None
     L.check(lib.tgp_cholesky_f64(L.ptr(A), M, L.ptr(Lo), L.ptr(Li), L.ptr(status), L.ptr(ws),
