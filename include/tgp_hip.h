@@ -337,6 +337,31 @@ int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, in
                  const double* raw_os, const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes,
                  void* stream);
 
+/* Greedy conditional-variance selection of inducing points: the pivoted Cholesky factorisation of K_XX (Burt, Rasmussen, van der
+ * Wilk 2020, "Convergence of sparse variational inference in Gaussian processes regression").  It picks the M rows of X that most
+ * reduce tr(K_XX - Q_XX), Q_XX = K_XZ K_ZZ^-1 K_ZX, and returns that residual trace after every pick.  With s2 the kernel's
+ * variance, start with d_n = s2 for all rows and no picked rows.  For j = 0 .. M-1:
+ *   1. p_j = argmax_n d_n over rows not yet picked; ties go to the smallest index (step 0 is an exact tie: p_0 = 0)
+ *   2. if d_{p_j} <= min_var, stop: M_eff = j
+ *   3. c_n = (k(x_n, x_{p_j}) - sum_{l<j} C[l,n] C[l,p_j]) / sqrt(d_{p_j}), the sum in the order of l
+ *   4. C[j,n] = c_n
+ *   5. d_n <- max(d_n - c_n^2, 0)
+ *   6. row p_j is marked picked: it never competes again and adds nothing to the trace
+ *   7. trace[j+1] = sum_{n not picked} d_n;  trace[0] = N s2
+ * Outputs: idx (M, int32), Z (M,D) = X[idx] bit for bit, trace (M+1), count[0] = M_eff; the unused tails idx[M_eff..] = -1,
+ * trace[M_eff+1..] = NaN, Z[M_eff..] = NaN.  X (N,D), raw_ls (D), raw_os (1), kernel TGP_KERNEL_*.
+ * M + 1 launches on the stream (one per step, one closing), nothing read back; a stop is sticky: the later launches return at
+ * once.  The arg-max and the trace reduce in a fixed order (wave butterfly, the waves in order, the workgroups' records in order),
+ * the grid depends on N only, no float atomics: same input, same bits on any device.
+ * workspace: tgp_greedy_inducing_workspace_bytes(N, D, M) bytes = C (M,N), d (N), two sets of workgroup records and the stop
+ * word, each section a whole number of 64 doubles, + 16; C starts at the first 16-byte aligned address of the workspace.
+ * Limits: 1 <= M <= min(N, TGP_BIG_MAX_M), 1 <= D <= 16, a known kernel, else TGP_E_UNSUPPORTED; a workspace below the sizer's
+ * value gives TGP_E_WORKSPACE before any launch (tgp_last_error() names the entry in both cases); min_var < 0 or NaN: -8. */
+size_t tgp_greedy_inducing_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double* raw_ls, const double* raw_os, int32_t kernel,
+                            int32_t M, double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Mean functions (models/means.py, chosen by model_specs[0], models/utils_models.py:285-294): 'linear' m(x) = x a + b with a (D)
  * and b (1) trainable, 'identity' m(x) = x W with W (D) fixed (b = NULL).  One output GP: a is a vector.  The reference adds
  * m(X) to the q(f) mean (models/sparse_MF_SP.py:314,355,360), subtracts m(Z) from the unwhitened variational mean (:359) and uses

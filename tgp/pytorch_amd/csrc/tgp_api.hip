@@ -436,6 +436,29 @@ int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, in
   return launch_kxxk(kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_greedy_inducing_workspace_bytes(int32_t N, int32_t D, int32_t M) { return greedy_inducing_workspace_bytes(N, D, M); }
+
+int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double* raw_ls, const double* raw_os, int32_t kernel,
+                            int32_t M, double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if ((kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) || greedy_inducing_workspace_bytes(N, D, M) == 0) {
+    set_error_text("tgp_greedy_inducing_f64: N = %d, D = %d, M = %d, kernel = %d outside 1 <= M <= min(N, %d), 1 <= D <= 16, "
+                   "kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, kernel, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!X) return -1;
+  if (!raw_ls) return -4;
+  if (!raw_os) return -5;
+  if (!(min_var >= 0.0)) return -8;
+  if (!idx) return -9;
+  if (!Z) return -10;
+  if (!trace) return -11;
+  if (!count) return -12;
+  if (!workspace) return -13;
+  return launch_greedy_inducing(X, N, D, raw_ls, raw_os, kernel, M, min_var, idx, Z, trace, count, workspace, workspace_bytes,
+                                static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S) { return qf_joint_sample_workspace_bytes(N, S); }
 
 int tgp_qf_joint_sample_f64(const double* mu, const double* Sigma, int32_t N, double jitter, const double* eps, int32_t S,

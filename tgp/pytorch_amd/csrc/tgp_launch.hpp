@@ -222,4 +222,10 @@ size_t optimal_qu_workspace_bytes(int N, int D, int M);
 int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
                       void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// tgp_greedy.hip (greedy conditional-variance selection of inducing points: the pivoted Cholesky factorisation of K_XX)
+size_t greedy_inducing_workspace_bytes(int N, int D, int M);
+int launch_greedy_inducing(const double* X, int N, int D, const double* raw_ls, const double* raw_os, int kernel, int M,
+                           double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
+                           size_t workspace_bytes, hipStream_t st);
+
 }  // namespace tgp

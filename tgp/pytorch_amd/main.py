@@ -35,7 +35,7 @@ from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, 
                           WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
-from .utils import KMEANS
+from .utils import GREEDY_VARIANCE, KMEANS
 
 # code/exp_config.py:4-86
 HYPER = {
@@ -81,6 +81,10 @@ def main(argv=None):
                     help="q(u): adam = m and Lam trained by Adam like every other parameter (the reference); optimal = set to "
                          "their closed-form optimum before every step and evaluation, the hyper-parameters train on the "
                          "collapsed bound (SVGP and WGP, --whiten 1, data sets of one full batch)")
+    ap.add_argument("--init_Z", choices=["kmeans", "greedy"], default="kmeans",
+                    help="inducing inputs at the start: kmeans = centroids of k-means++ / Lloyd, best of 10 (the reference); greedy = "
+                         "the training rows picked by greedy conditional-variance selection (pivoted Cholesky of K_XX) under the "
+                         "kernel at its initial hyper-parameters; prints the share of tr(K_XX) they leave unexplained")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -103,6 +107,8 @@ def main(argv=None):
         ap.error("--mean %s: SVGP or TGP with the gaussian or bernoulli likelihood only" % args.mean)
     if args.qu == "optimal" and (args.model not in ("SVGP", "WGP") or args.likelihood != "gaussian" or not args.whiten):
         ap.error("--qu optimal: SVGP or WGP with the gaussian likelihood and --whiten 1 (the likelihood must be Gaussian in f)")
+    if args.init_Z == "greedy" and args.likelihood == "multiclass":
+        ap.error("--init_Z greedy: one latent GP only (not --likelihood multiclass)")
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
         ap.error("ID_TGP uses input-dependent SAL flows: --flow_arch SAL only")
 
@@ -111,7 +117,7 @@ def main(argv=None):
     loaders, dc = return_dataset(args.dataset, 10000, use_validation=None, seed=args.train_test_seed_split,
                                  options={"shuffle_train": True})
     Dx, Dy = dc["Dx"], dc["Dy"]
-    init_Z = KMEANS(dc["X_tr"], args.num_inducing, n_init=10, seed=cg.config_seed)
+    init_Z = KMEANS(dc["X_tr"], args.num_inducing, n_init=10, seed=cg.config_seed) if args.init_Z == "kmeans" else None
 
     flow_specs = None
     if args.model != "SVGP":
@@ -157,6 +163,9 @@ def main(argv=None):
         lik = GaussianNonLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points)
     K = instance_kernel("scale_rbf", ard_num_dim=Dx, num_multioutput=Dy, kernel_is_shared=False,
                         init_params={"length_scale": 2.0, "kernel_scale": 2.0, "noisy_variance": 1e-6})
+    if args.init_Z == "greedy":
+        init_Z, sel = GREEDY_VARIANCE(dc["X_tr"], args.num_inducing, K, return_info=True)
+        print("init_Z greedy: trace[M]/trace[0] = %.6e" % float(sel["trace"][-1] / sel["trace"][0]))
     ip = {"variational_distribution": {"variance_scale": 1e-5, "mean_scale": 0.0}}
     common = dict(model_specs=[args.mean, K], X=dc["X_tr"], init_Z=init_Z, N=dc["N_tr"], likelihood=lik, num_outputs=Dy,
                   is_whiten=bool(args.whiten), K_is_shared=False, mean_is_shared=False, Z_is_shared=False, q_U_is_shared=False,

@@ -641,6 +641,35 @@ def optimal_qu(X, Y, Z, raw_ls, raw_os, lvn, N_total, jitter=0.0, kernel="scale_
 
 
 # ---------------------------------------------------------------------------------------------------
+# greedy conditional-variance selection of inducing points (the pivoted Cholesky factorisation of K_XX)
+# ---------------------------------------------------------------------------------------------------
+def greedy_inducing(X, M, raw_ls, raw_os, kernel="scale_rbf", min_var=1e-8, workspace_bytes=None):
+    """(idx (M_eff,) int64, Z (M_eff, D) = X[idx] bit for bit, trace (M_eff + 1,), M_eff): the M rows of X that greedily most reduce
+    tr(K_XX - Q_XX), Q_XX = K_XZ K_ZZ^-1 K_ZX, and that trace after every pick (tgp_greedy_inducing_f64).  With d_n = s2 at the
+    start, step j picks p_j = argmax_n d_n over the rows not yet picked (ties: the smallest index, so p_0 = 0), stops with
+    M_eff = j if d_{p_j} <= min_var, else c_n = (k(x_n, x_{p_j}) - sum_{l<j} C[l,n] C[l,p_j]) / sqrt(d_{p_j}), C[j,n] = c_n,
+    d_n <- max(d_n - c_n^2, 0), trace[j+1] = sum of d over the rows not picked; trace[0] = N s2.  M + 1 launches and one host
+    read, at the end.  Fixed reduction orders: two calls give the same bits."""
+    lib = L.load()
+    X, raw_ls, raw_os = _c(X, "X"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
+    if X.dim() != 2 or raw_ls.numel() != X.shape[1] or raw_os.numel() != 1:
+        raise ValueError("greedy_inducing: X (N, D), raw_ls (D), raw_os (1)")
+    N, D = X.shape
+    M = int(M)
+    dev = X.device
+    ws, nbytes = _scratch(lib.tgp_greedy_inducing_workspace_bytes(N, D, M), dev, workspace_bytes)
+    idx = torch.empty(max(M, 1), dtype=torch.int32, device=dev)
+    Z = torch.empty(max(M, 1), D, dtype=torch.float64, device=dev)
+    trace = torch.empty(max(M, 1) + 1, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    L.check(lib.tgp_greedy_inducing_f64(L.ptr(X), N, D, L.ptr(raw_ls), L.ptr(raw_os), kernel_id(kernel), M, float(min_var),
+                                        L.ptr(idx), L.ptr(Z), L.ptr(trace), L.ptr(count), L.ptr(ws), nbytes, L.stream_ptr()),
+            "tgp_greedy_inducing_f64")
+    m_eff = int(count.item())
+    return idx[:m_eff].to(torch.int64), Z[:m_eff], trace[:m_eff + 1], m_eff
+
+
+# ---------------------------------------------------------------------------------------------------
 # mean functions (models/means.py): m(x) = x a + b on the rows of X, and its adjoint
 # ---------------------------------------------------------------------------------------------------
 def mean_forward(X, a, b=None, alpha=1.0, inp=None, out=None, col=0, one_col=-1):

@@ -141,6 +141,55 @@ def KMEANS(X, num_Z, n_init=1, seed=None, backend="hip", max_iter=300, tol=1e-4,
     return Z
 
 
+def _hip_device(X, who):
+    """The device a selection on X runs on: X's own when it lives on one, else the current HIP device."""
+    from . import lib as L
+    if X.is_cuda:
+        return X.device
+    if not torch.cuda.is_available():
+        raise L.TgpError("%s needs a HIP device" % who)
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def GREEDY_VARIANCE(X, num_Z, kernel, min_var=1e-8, return_info=False):
+    """Inducing-point initialisation by greedy conditional-variance selection, the pivoted Cholesky factorisation of K_XX (Burt,
+    Rasmussen, van der Wilk 2020): the num_Z rows of X that greedily most reduce tr(K_XX - Q_XX) under `kernel`, a
+    kernels.ScaleKernel whose name and raw parameters (output 0) are read as they stand (ops.greedy_inducing on the GPU).
+    Returns Z (num_Z, D), rows of X bit for bit; with return_info=True also {"idx": (num_Z,) int64, "trace": (num_Z + 1,)},
+    trace[j] = tr(K_XX - Q_XX) with the first j rows picked -- the term of the collapsed bound that Z controls.  A model needs
+    exactly num_Z rows: ValueError when fewer clear min_var (the jitter K_ZZ gets anyway: such a row conditions K_ZZ + jitter I
+    no better than a duplicate would)."""
+    from . import kernels
+    from . import lib as L
+    from . import ops
+    if not isinstance(kernel, kernels.ScaleKernel):
+        raise TypeError("GREEDY_VARIANCE: kernel must be a kernels.ScaleKernel (instance_kernel builds one), got %s"
+                        % type(kernel).__name__)
+    if X.dim() != 2:
+        raise ValueError("GREEDY_VARIANCE: X (N, D), got shape %s" % (tuple(X.shape),))
+    N, D = X.shape
+    num_Z = int(num_Z)
+    if not 1 <= num_Z <= N:
+        raise ValueError("GREEDY_VARIANCE: 1 <= num_Z <= N = %d, got %d" % (N, num_Z))
+    raw_ls, raw_os = kernel._params()
+    if raw_ls.numel() not in (1, D):
+        raise ValueError("GREEDY_VARIANCE: the kernel has %d length-scales, X has %d columns" % (raw_ls.numel(), D))
+    if not min_var >= 0.0:
+        raise ValueError("GREEDY_VARIANCE: min_var >= 0, got %r" % (min_var,))
+    dev = _hip_device(X, "GREEDY_VARIANCE")
+    Xd = X.detach().to(dev, torch.float64).contiguous()
+    raw_ls = raw_ls.to(dev, torch.float64).expand(D).contiguous()
+    idx, Z, trace, m_eff = ops.greedy_inducing(Xd, num_Z, raw_ls, raw_os.to(dev, torch.float64), kernel=kernel.hip_kernel,
+                                               min_var=min_var)
+    if m_eff < num_Z:
+        raise ValueError("GREEDY_VARIANCE: M_eff = %d of the %d rows asked for have a conditional variance above min_var = %g; "
+                         "ask for at most M_eff inducing points or lower min_var" % (m_eff, num_Z, min_var))
+    Z = Z.to(cg.dtype).to(cg.device)
+    if return_info:
+        return Z, {"idx": idx, "trace": trace}
+    return Z
+
+
 def _same_clustering(a, b, K):
     """sklearn _is_same_clustering: equal up to a permutation of the labels."""
     m = torch.full((K,), -1, dtype=torch.int64, device=a.device)
