@@ -362,6 +362,35 @@ int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double*
                             int32_t M, double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Pathwise posterior function draws (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors") of the
+ * whitened sparse GP: a draw is a weight vector over 2 R2 random Fourier features of the prior and the M kernel columns at the
+ * inducing points, and can then be evaluated on any rows, in any batches, consistently, in O(N (R2 + M) S).  With
+ * l = softplus(raw_ls), s2 = softplus(raw_os), K = K_ZZ + jitter I = L L^T, Lam = tril(Lam), amp = sqrt(s2 / R2) and
+ * a_j(x) = sum_d omega[j,d] x_d / l_d (in the order of d):
+ *   phi_j(x) = amp cos a_j(x),   phi_{R2+j}(x) = amp sin a_j(x)      (j < R2; sum_j phi_j(x)^2 = s2 at every x)
+ *   nu_s     = L^-T (m + Lam eps_s - L^-1 Phi_Z W_s^T)               (the inducing-point update is exact)
+ *   f0_s(x)  = sum_{j < 2 R2} phi_j(x) W[s,j] + sum_{i < M} k(x, z_i) nu_s[i]
+ * The kernels draw no random numbers: omega (R2,D) are frequencies of the unit-length-scale kernel (N(0, I) for the RBF, the
+ * multivariate Student-t with 3 degrees of freedom for Matern-3/2), W (S, 2 R2) and eps (S,M) standard normals.
+ * tgp_pathwise_coeff_f64: coef (2 R2 + M, S) row-major; rows [0, 2 R2) = amp W[s,j], rows [2 R2, 2 R2 + M) = nu_s[i].  Uses
+ *   model->{D,M,kernel,jitter,Z,raw_ls,raw_os,m,Lam}; status[0] is tgp_cholesky_f64's (the host runs the jitter ladder, as for
+ *   tgp_qf_cov_f64).  Phi_Z is generated on chip and never stored.  workspace: tgp_pathwise_workspace_bytes(N, D, M, R2, S) bytes
+ *   (N any value >= 1: it does not change the size), sections of whole 64 doubles, + 16.
+ * tgp_pathwise_eval_f64: F0 (S,N) = the draws of coef on the rows X (N,D).  A value of F0 depends on its row of X and on coef
+ *   only (fixed contraction order): X evaluated in one call or in pieces gives the same bits.  S * N may exceed 2^31.
+ * No float atomics, fixed summation orders: two calls on the same input return the same bits.
+ * Limits: N >= 1, 1 <= D <= 16, 1 <= M <= TGP_BIG_MAX_M, 1 <= R2 <= TGP_PATHWISE_MAX_R2, 1 <= S <= TGP_PATHWISE_MAX_S, one of
+ * the two kernels, else TGP_E_UNSUPPORTED; a workspace below the sizer's value gives TGP_E_WORKSPACE (tgp_last_error() names the
+ * entry in both cases); a null pointer gives the negative index of its argument.  Every refusal happens before any launch. */
+#define TGP_PATHWISE_MAX_R2 8192
+#define TGP_PATHWISE_MAX_S 256
+size_t tgp_pathwise_workspace_bytes(int32_t N, int32_t D, int32_t M, int32_t R2, int32_t S);
+int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t R2, const double* W, const double* eps, int32_t S,
+                           double* coef, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
+                          const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S, double* F0,
+                          void* stream);
+
 /* Mean functions (models/means.py, chosen by model_specs[0], models/utils_models.py:285-294): 'linear' m(x) = x a + b with a (D)
  * and b (1) trainable, 'identity' m(x) = x W with W (D) fixed (b = NULL).  One output GP: a is a vector.  The reference adds
  * m(X) to the q(f) mean (models/sparse_MF_SP.py:314,355,360), subtracts m(Z) from the unwhitened variational mean (:359) and uses

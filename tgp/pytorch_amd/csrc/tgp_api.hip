@@ -459,6 +459,50 @@ int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double*
                                 static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_pathwise_workspace_bytes(int32_t N, int32_t D, int32_t M, int32_t R2, int32_t S) {
+  return pathwise_workspace_bytes(N, D, M, R2, S);
+}
+
+static bool pathwise_known_kernel(int32_t kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
+
+int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t R2, const double* W, const double* eps, int32_t S,
+                           double* coef, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (!pathwise_known_kernel(model->kernel) || pathwise_workspace_bytes(1, model->D, model->M, R2, S) == 0) {
+    set_error_text("tgp_pathwise_coeff_f64: D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside 1 <= D <= 16, 1 <= M <= %d, "
+                   "1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", model->D, model->M, R2, S,
+                   model->kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os || !model->m || !model->Lam) return -1;
+  if (!omega) return -2;
+  if (!W) return -4;
+  if (!eps) return -5;
+  if (!coef) return -7;
+  if (!status) return -8;
+  if (!workspace) return -9;
+  return launch_pathwise_coeff(*model, omega, R2, W, eps, S, coef, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
+                          const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S, double* F0,
+                          void* stream) {
+  if (!pathwise_known_kernel(kernel) || pathwise_workspace_bytes(N, D, M, R2, S) == 0) {
+    set_error_text("tgp_pathwise_eval_f64: N = %d, D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside N >= 1, 1 <= D <= 16, "
+                   "1 <= M <= %d, 1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, R2, S,
+                   kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!X) return -2;
+  if (!Z) return -5;
+  if (!raw_ls) return -7;
+  if (!raw_os) return -8;
+  if (!omega) return -9;
+  if (!coef) return -11;
+  if (!F0) return -13;
+  return launch_pathwise_eval(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S) { return qf_joint_sample_workspace_bytes(N, S); }
 
 int tgp_qf_joint_sample_f64(const double* mu, const double* Sigma, int32_t N, double jitter, const double* eps, int32_t S,

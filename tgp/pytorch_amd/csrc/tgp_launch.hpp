@@ -228,4 +228,11 @@ int launch_greedy_inducing(const double* X, int N, int D, const double* raw_ls, 
                            double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
                            size_t workspace_bytes, hipStream_t st);
 
+// tgp_pathwise.hip (pathwise posterior function draws: Fourier features of the prior + kernel columns at the inducing points)
+size_t pathwise_workspace_bytes(int N, int D, int M, int R2, int S);
+int launch_pathwise_coeff(const tgp_model& md, const double* omega, int R2, const double* W, const double* eps, int S, double* coef,
+                          int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st);
+int launch_pathwise_eval(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls,
+                         const double* raw_os, const double* omega, int R2, const double* coef, int S, double* F0, hipStream_t st);
+
 }  // namespace tgp

@@ -20,6 +20,7 @@ LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
+PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64
 E_UNSUPPORTED = -100
 E_WORKSPACE = -101
 
@@ -126,6 +127,10 @@ _SIGS = {
     "tgp_greedy_inducing_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "tgp_greedy_inducing_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _dp, _dp,
                                           _dp, C.c_size_t, _dp]),
+    "tgp_pathwise_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "tgp_pathwise_coeff_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_pathwise_eval_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
+                                        C.c_int32, _dp, _dp]),
     "tgp_mean_forward_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, _dp, C.c_double, _dp, _dp, C.c_int32, C.c_int32, C.c_int32,
                                        _dp]),
     "tgp_mean_backward_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

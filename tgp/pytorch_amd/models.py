@@ -669,6 +669,25 @@ class sparse_MF_SP(nn.Module):
         self.train()
         return f, mean_q_f0, cov_q_f0, f0
 
+    def posterior_paths(self, S: int, num_frequencies: int = 1024, generator=None):
+        """S coherent posterior function draws as a pathwise.PosteriorPaths (Wilson et al. 2020): `paths.f0(X)` and `paths(X)`
+        evaluate the SAME S functions on any rows, in any batches, in O(N (num_frequencies + M) S) -- no N x N covariance and no
+        4096-row cap.  The draw is fixed at the current parameters (detached copies).  `generator`: a seeded CPU torch.Generator
+        behind the frequencies and the normals.  Unwhitened models go through the transform of `_gp_params`, as for the full
+        covariance."""
+        if self._is_multiclass:
+            raise NotImplementedError("posterior_paths is not built for multi-class models (num_outputs = C latent GPs)")
+        if self.fully_bayesian:
+            raise NotImplementedError("posterior_paths is not built for be_fully_bayesian models: the MC-dropout flows have "
+                                      "no fixed per-row parameters, so a draw would not be one function")
+        from .pathwise import draw_paths
+        with torch.no_grad():
+            info = {}
+            Z, rl, ro, m, Lam, _ = self._gp_params(info=info)
+            return draw_paths(*(t.detach() for t in (Z, rl, ro, m, Lam)), self.covariance_function.hip_kernel, S,
+                              num_frequencies=num_frequencies, generator=generator, jitter=info["jitter"],
+                              mean_function=self.mean_function if self._has_mean else None, flow=self.G_matrix[0])
+
     def sample_from_predictive_distribution(self, X, S: int, diagonal: bool = True) -> List[torch.tensor]:
         """diagonal=False: the likelihood's noise is added to JOINT function draws (one coherent function per sample)."""
         assert not self.is_training, "This method only works in eval mode"

@@ -670,6 +670,73 @@ def greedy_inducing(X, M, raw_ls, raw_os, kernel="scale_rbf", min_var=1e-8, work
 
 
 # ---------------------------------------------------------------------------------------------------
+# pathwise posterior function draws (Wilson et al. 2020): Fourier features of the prior + kernel columns at the inducing points
+# ---------------------------------------------------------------------------------------------------
+def pathwise_coeff(Z, raw_ls, raw_os, m, Lam, omega, W, eps, jitter=0.0, kernel="scale_rbf", check=True, info=None,
+                   workspace_bytes=None):
+    """coef (2 R2 + M, S) of S pathwise draws of the whitened sparse GP (tgp_pathwise_coeff_f64): rows [0, 2 R2) hold
+    amp W[s, j], amp = sqrt(s2 / R2), rows [2 R2, 2 R2 + M) hold nu_s = L^-T (m + Lam eps_s - L^-1 Phi_Z W_s^T) with
+    K_ZZ + jitter I = L L^T.  omega (R2, D): frequencies of the unit-length-scale kernel (pathwise.spectral_frequencies);
+    W (S, 2 R2), eps (S, M): standard normals.  The factorisation runs under psd_safe_cholesky's ladder as in qf_cov;
+    `info["jitter"]` receives the value it ended with.  Fixed summation orders: two calls give the same bits.  No autograd."""
+    lib = L.load()
+    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
+    m, Lam, omega, W, eps = _c(m.reshape(-1), "m"), _c(Lam, "Lam"), _c(omega, "omega"), _c(W, "W"), _c(eps, "eps")
+    M, D = Z.shape
+    if omega.dim() != 2 or W.dim() != 2 or eps.dim() != 2:
+        raise ValueError("pathwise_coeff: omega (R2, D), W (S, 2 R2), eps (S, M)")
+    R2, S = omega.shape[0], W.shape[0]
+    if (omega.shape[1] != D or W.shape[1] != 2 * R2 or eps.shape != (S, M) or m.numel() != M or Lam.shape != (M, M)
+            or raw_ls.numel() != D or raw_os.numel() != 1):
+        raise ValueError("pathwise_coeff: Z (M, D), raw_ls (D), raw_os (1), m (M), Lam (M, M), omega (R2, D), W (S, 2 R2), "
+                         "eps (S, M)")
+    dev = Z.device
+    lvn = torch.zeros(1, dtype=torch.float64, device=dev)
+    md, _ = _model_struct(Z, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 1.0, None, None, None, kernel)
+    ws, nbytes = _scratch(lib.tgp_pathwise_workspace_bytes(1, D, M, R2, S), dev, workspace_bytes)
+    coef = torch.empty(max(2 * R2 + M, 1), max(S, 1), dtype=torch.float64, device=dev)
+    status = _status(dev)
+
+    def call(jit):
+        md.jitter = jit
+        L.check(lib.tgp_pathwise_coeff_f64(md, L.ptr(omega), R2, L.ptr(W), L.ptr(eps), S, L.ptr(coef), L.ptr(status), L.ptr(ws),
+                                           nbytes, L.stream_ptr()), "tgp_pathwise_coeff_f64")
+    _laddered(call, status, jitter, info=info, check=check)
+    return coef
+
+
+def pathwise_eval(X, Z, raw_ls, raw_os, omega, coef, kernel="scale_rbf", batch_rows=None):
+    """F0 (S, N): the draws of `coef` (pathwise_coeff) on the rows of X (tgp_pathwise_eval_f64).  A value depends on its row of
+    X and on coef only: `batch_rows` evaluates X in pieces of that many rows (bounded operands) and returns the same bits."""
+    lib = L.load()
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
+    omega, coef = _c(omega, "omega"), _c(coef, "coef")
+    if X.dim() != 2 or Z.dim() != 2 or omega.dim() != 2 or coef.dim() != 2:
+        raise ValueError("pathwise_eval: X (N, D), Z (M, D), omega (R2, D), coef (2 R2 + M, S)")
+    (N, D), M, R2, S = X.shape, Z.shape[0], omega.shape[0], coef.shape[1]
+    if Z.shape[1] != D or omega.shape[1] != D or coef.shape[0] != 2 * R2 + M or raw_ls.numel() != D or raw_os.numel() != 1:
+        raise ValueError("pathwise_eval: X (N, D), Z (M, D), raw_ls (D), raw_os (1), omega (R2, D), coef (2 R2 + M, S)")
+    if batch_rows is not None and int(batch_rows) < 1:
+        raise ValueError("pathwise_eval: batch_rows >= 1")
+    kid = kernel_id(kernel)
+    dev = X.device
+
+    def piece(Xp):
+        n = Xp.shape[0]
+        F = torch.empty(max(S, 1), max(n, 1), dtype=torch.float64, device=dev)
+        L.check(lib.tgp_pathwise_eval_f64(kid, L.ptr(Xp), n, D, L.ptr(Z), M, L.ptr(raw_ls), L.ptr(raw_os), L.ptr(omega), R2,
+                                          L.ptr(coef), S, L.ptr(F), L.stream_ptr()), "tgp_pathwise_eval_f64")
+        return F
+    if batch_rows is None or int(batch_rows) >= N:
+        return piece(X)
+    F0 = torch.empty(S, N, dtype=torch.float64, device=dev)
+    for a in range(0, N, int(batch_rows)):
+        b = min(N, a + int(batch_rows))
+        F0[:, a:b] = piece(X[a:b])
+    return F0
+
+
+# ---------------------------------------------------------------------------------------------------
 # mean functions (models/means.py): m(x) = x a + b on the rows of X, and its adjoint
 # ---------------------------------------------------------------------------------------------------
 def mean_forward(X, a, b=None, alpha=1.0, inp=None, out=None, col=0, one_col=-1):
