@@ -25,7 +25,7 @@ def f64():
 
 
 # ---- 1. C = K_ZX K_XZ and b = K_ZX y ---------------------------------------------------------------------------------
-MS, NS, DS = (1, 16, 63, 64, 65, 100, 128, 129, 200), (1, 15, 17, 257, 1100, 5000), (1, 4, 13, 16)
+MS, NS, DS = (1, 16, 63, 64, 65, 100, 128, 129, 200), (1, 15, 17, 257, 1100, 5000), (1, 4, 5, 8, 9, 13, 16)
 
 
 @functools.lru_cache(maxsize=None)

@@ -39,7 +39,7 @@ static int check_model(const tgp_model* m, bool need_lik) {
   if (m->N < 1 || m->D < 1 || m->D > 16) return -1;
   if (m->M < 1) return -1;
   if (m->M > TGP_BIG_MAX_M) return TGP_E_UNSUPPORTED;
-  if (m->kernel != TGP_KERNEL_SCALE_RBF && m->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (!known_kernel(m->kernel)) return -1;
   if (!m->Z || !m->raw_ls || !m->raw_os || !m->m || !m->Lam || !m->log_var_noise) return -1;
   if (need_lik && (m->lik == TGP_LIK_FLOW || m->lik == TGP_LIK_BERNOULLI))
     if (m->S < 1 || m->nblk < 0 || !m->xs || !m->wn || check_flow_args(m)) return -1;
@@ -383,7 +383,7 @@ size_t tgp_qf_cov_workspace_bytes(int32_t N, int32_t D, int32_t M) { return qf_c
 int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
                    size_t workspace_bytes, void* stream) {
   if (model == nullptr) return -1;
-  if (model->kernel != TGP_KERNEL_SCALE_RBF && model->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (!known_kernel(model->kernel)) return -1;
   if (qf_cov_workspace_bytes(model->N, model->D, model->M) == 0) {
     set_error_text("tgp_qf_cov_f64: N = %d, D = %d, M = %d outside 1 <= N, M <= %d, 1 <= D <= 16", model->N, model->D, model->M,
                    TGP_BIG_MAX_M);
@@ -403,7 +403,7 @@ size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return 
 int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream) {
   if (model == nullptr) return -1;
-  if (model->kernel != TGP_KERNEL_SCALE_RBF && model->kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (!known_kernel(model->kernel)) return -1;
   if (optimal_qu_workspace_bytes(model->N, model->D, model->M) == 0) {
     set_error_text("tgp_optimal_qu_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", model->N, model->D,
                    model->M, TGP_BIG_MAX_M);
@@ -424,7 +424,7 @@ size_t tgp_kxxk_workspace_bytes(int32_t N, int32_t M) { return kxxk_workspace_by
 int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, int32_t M, int32_t D, const double* raw_ls,
                  const double* raw_os, const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes,
                  void* stream) {
-  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (!known_kernel(kernel)) return -1;
   if (D < 1 || D > 16 || kxxk_workspace_bytes(N, M) == 0) {
     set_error_text("tgp_kxxk_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", N, D, M, TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
@@ -441,7 +441,7 @@ size_t tgp_greedy_inducing_workspace_bytes(int32_t N, int32_t D, int32_t M) { re
 int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double* raw_ls, const double* raw_os, int32_t kernel,
                             int32_t M, double min_var, int32_t* idx, double* Z, double* trace, int32_t* count, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  if ((kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) || greedy_inducing_workspace_bytes(N, D, M) == 0) {
+  if (!known_kernel(kernel) || greedy_inducing_workspace_bytes(N, D, M) == 0) {
     set_error_text("tgp_greedy_inducing_f64: N = %d, D = %d, M = %d, kernel = %d outside 1 <= M <= min(N, %d), 1 <= D <= 16, "
                    "kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, kernel, TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
@@ -463,12 +463,10 @@ size_t tgp_pathwise_workspace_bytes(int32_t N, int32_t D, int32_t M, int32_t R2,
   return pathwise_workspace_bytes(N, D, M, R2, S);
 }
 
-static bool pathwise_known_kernel(int32_t kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
-
 int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t R2, const double* W, const double* eps, int32_t S,
                            double* coef, int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
   if (model == nullptr) return -1;
-  if (!pathwise_known_kernel(model->kernel) || pathwise_workspace_bytes(1, model->D, model->M, R2, S) == 0) {
+  if (!known_kernel(model->kernel) || pathwise_workspace_bytes(1, model->D, model->M, R2, S) == 0) {
     set_error_text("tgp_pathwise_coeff_f64: D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside 1 <= D <= 16, 1 <= M <= %d, "
                    "1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", model->D, model->M, R2, S,
                    model->kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
@@ -487,7 +485,7 @@ int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t 
 int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
                           const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S, double* F0,
                           void* stream) {
-  if (!pathwise_known_kernel(kernel) || pathwise_workspace_bytes(N, D, M, R2, S) == 0) {
+  if (!known_kernel(kernel) || pathwise_workspace_bytes(N, D, M, R2, S) == 0) {
     set_error_text("tgp_pathwise_eval_f64: N = %d, D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside N >= 1, 1 <= D <= 16, "
                    "1 <= M <= %d, 1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, R2, S,
                    kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
@@ -564,7 +562,7 @@ int tgp_kmm_f64(const double* Z, const double* raw_ls, const double* raw_os, int
 
 int tgp_kernel_matrix_f64(int32_t kernel, const double* X1, int32_t N1, const double* X2, int32_t N2, int32_t D,
                           const double* raw_ls, const double* raw_os, double jitter, double* K, void* stream) {
-  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
+  if (!known_kernel(kernel)) return -1;
   if (!X1) return -2;
   if (N1 < 1) return -3;
   if (X2 && N2 < 1) return -5;
@@ -630,8 +628,8 @@ size_t tgp_unwhiten_workspace_bytes(int32_t M, int32_t D) { return unwhiten_work
 int tgp_unwhiten_f64(int32_t kernel, const double* Z, const double* raw_ls, const double* raw_os, int32_t M, int32_t D,
                      double jitter, const double* m, const double* L_q, double* m_w, double* Lam_w, double* L, double* Linv,
                      int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
-  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
-  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) {
+  if (!known_kernel(kernel)) return -1;
+  if (!inducing_limits(M, D)) {
     set_error_text("tgp_unwhiten_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
   }
@@ -655,8 +653,8 @@ int tgp_unwhiten_bwd_f64(int32_t kernel, const double* Z, const double* raw_ls, 
                          const double* L, const double* Linv, const double* m_w, const double* Lam_w, const double* m_w_bar,
                          const double* Lam_w_bar, double* m_bar, double* L_q_bar, double* Z_bar, double* raw_ls_bar,
                          double* raw_os_bar, void* workspace, size_t workspace_bytes, void* stream) {
-  if (kernel != TGP_KERNEL_SCALE_RBF && kernel != TGP_KERNEL_SCALE_MATERN32) return -1;
-  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) {
+  if (!known_kernel(kernel)) return -1;
+  if (!inducing_limits(M, D)) {
     set_error_text("tgp_unwhiten_bwd_f64: M = %d, D = %d outside 1 <= M <= %d, 1 <= D <= 16", M, D, TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
   }

@@ -16,14 +16,9 @@
 // Every reduction has a fixed order and nothing is accumulated with atomics: two runs on the same input are bit-identical.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_tile.hpp"
 
 namespace tgp {
-
-#define COV_T 64    /* output tile (rows and columns) of k_cov_a, k_cov_sigma and the column tile of k_joint_draw */
-#define COV_KC 16   /* contraction indices staged per step                                                        */
-#define COV_LDN 80  /* LDS stride (f64) of a [16 k][64 n] operand tile: the 4 k rows of one MFMA operand fall in distinct banks */
-#define COV_LDK 18  /* LDS stride (f64) of a [64 r][16 k] operand tile: 16 rows x 2 k of a half wave in distinct banks      */
-#define COV_LDT 65  /* LDS stride (f64) of the 64 x 64 output tile: conflict-free along rows and along columns              */
 
 // L_q = tril(Lam) and L^-1 in their zero-padded (MP x MP) images, W = -I on the first M diagonal entries (the product
 // L_q L_q^T is added by the GEMM that follows).
@@ -48,17 +43,16 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
                                                 int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
                                                 const double* __restrict__ LinvP, int MP, const double* __restrict__ mvec,
                                                 double* __restrict__ A, int NP, double* __restrict__ mu) {
-  __shared__ __attribute__((aligned(16))) double Ls[COV_T * COV_LDK];
-  __shared__ double Kt[COV_KC * COV_LDN];
-  __shared__ double xsT[16 * COV_T];  // [d][column]: scaled rows of X*
+  __shared__ __attribute__((aligned(16))) double Ls[TL_T * TL_LDK];
+  __shared__ double Kt[TL_KC * TL_LDN];
+  __shared__ double xsT[16 * TL_T];  // [d][column]: scaled rows of X*
   __shared__ double red[256];
   __shared__ double ils[17];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  const int n0 = blockIdx.x * COV_T;
-  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  const int n0 = blockIdx.x * TL_T;
+  tile_scales(D, raw_ls, raw_os, ils);
   __syncthreads();
-  for (int i = tid; i < 16 * COV_T; i += 256) {
+  for (int i = tid; i < 16 * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
     const int n = n0 + c < N ? n0 + c : N - 1;  // clamped: columns past N are computed and never stored
     xsT[i] = d < D ? X[(size_t)n * D + d] * ils[d] : 0.0;
@@ -68,16 +62,16 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
   const int gk = tid >> 4, gc = tid & 15;  // generation role: contraction index gk of the step, columns gc + 16 u
   const int M16 = (M + 15) / 16 * 16;
   double mup = 0.0;
-  for (int mg = 0; mg < MP; mg += COV_T) {
+  for (int mg = 0; mg < MP; mg += TL_T) {
     d4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
-    const int kend = mg < M ? (mg + COV_T < M16 ? mg + COV_T : M16) : 0;
-    for (int k0 = 0; k0 < kend; k0 += COV_KC) {
+    const int kend = mg < M ? (mg + TL_T < M16 ? mg + TL_T : M16) : 0;
+    for (int k0 = 0; k0 < kend; k0 += TL_KC) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {  // 64 rows x 16 k of L^-1: 512 pairs
         const int idx = tid + 256 * u, r = idx >> 3, c2 = (idx & 7) * 2;
-        *reinterpret_cast<double2*>(Ls + r * COV_LDK + c2) =
+        *reinterpret_cast<double2*>(Ls + r * TL_LDK + c2) =
             *reinterpret_cast<const double2*>(LinvP + (size_t)(mg + r) * MP + k0 + c2);
       }
       {
@@ -91,18 +85,18 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
           double d2 = 0.0;
 #pragma unroll
           for (int d = 0; d < 16; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
-            const double t = xsT[d * COV_T + c] - z[d];
+            const double t = xsT[d * TL_T + c] - z[d];
             d2 += t * t;
           }
-          Kt[gk * COV_LDN + c] = cov_value(kernel, s2, d2);
+          Kt[gk * TL_LDN + c] = cov_value(kernel, s2, d2);
         }
       }
       __syncthreads();
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
-        const double b = Kt[(kk * 4 + lq) * COV_LDN + 16 * w + lr];
+        const double b = Kt[(kk * 4 + lq) * TL_LDN + 16 * w + lr];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = TGP_MFMA(Ls[(16 * t + lr) * COV_LDK + kk * 4 + lq], b, acc[t]);
+        for (int t = 0; t < 4; ++t) acc[t] = TGP_MFMA(Ls[(16 * t + lr) * TL_LDK + kk * 4 + lq], b, acc[t]);
       }
       __syncthreads();
     }
@@ -135,20 +129,16 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
                                                     const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
                                                     const double* __restrict__ A, const double* __restrict__ C, int M16, int NP,
                                                     double* __restrict__ Sigma) {
-  __shared__ __attribute__((aligned(16))) double buf[COV_T * COV_LDT];  // operand tiles (2 x 16 x 80), then the output tile
-  __shared__ double xiT[16 * COV_T], xjT[16 * COV_T];
+  __shared__ __attribute__((aligned(16))) double buf[TL_T * TL_LDT];  // operand tiles (2 x 16 x 80), then the output tile
+  __shared__ double xiT[16 * TL_T], xjT[16 * TL_T];
   __shared__ double ils[17];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  const int t = blockIdx.x;
-  int ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-  while (ti * (ti + 1) / 2 > t) --ti;
-  const int tj = t - ti * (ti + 1) / 2;
-  const int i0 = ti * COV_T, j0 = tj * COV_T;
-  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  int ti, tj;
+  tile_lower(blockIdx.x, ti, tj);
+  const int i0 = ti * TL_T, j0 = tj * TL_T;
+  tile_scales(D, raw_ls, raw_os, ils);
   __syncthreads();
-  for (int i = tid; i < 16 * COV_T; i += 256) {
+  for (int i = tid; i < 16 * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
     const int ni = i0 + c < N ? i0 + c : N - 1, nj = j0 + c < N ? j0 + c : N - 1;
     xiT[i] = d < D ? X[(size_t)ni * D + d] * ils[d] : 0.0;
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
   }
   const double s2 = ils[16];
   double* At = buf;
-  double* Ct = buf + COV_KC * COV_LDN;
+  double* Ct = buf + TL_KC * TL_LDN;
   d4 acc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
@@ -167,15 +157,15 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
   const size_t half = (size_t)8 * NP;
   double2 pa0 = *reinterpret_cast<const double2*>(Ag), pa1 = *reinterpret_cast<const double2*>(Ag + half);
   double2 pc0 = *reinterpret_cast<const double2*>(Cg), pc1 = *reinterpret_cast<const double2*>(Cg + half);
-  for (int k0 = 0; k0 < M16; k0 += COV_KC) {
-    *reinterpret_cast<double2*>(At + pr * COV_LDN + pc2) = pa0;
-    *reinterpret_cast<double2*>(At + (pr + 8) * COV_LDN + pc2) = pa1;
-    *reinterpret_cast<double2*>(Ct + pr * COV_LDN + pc2) = pc0;
-    *reinterpret_cast<double2*>(Ct + (pr + 8) * COV_LDN + pc2) = pc1;
+  for (int k0 = 0; k0 < M16; k0 += TL_KC) {
+    *reinterpret_cast<double2*>(At + pr * TL_LDN + pc2) = pa0;
+    *reinterpret_cast<double2*>(At + (pr + 8) * TL_LDN + pc2) = pa1;
+    *reinterpret_cast<double2*>(Ct + pr * TL_LDN + pc2) = pc0;
+    *reinterpret_cast<double2*>(Ct + (pr + 8) * TL_LDN + pc2) = pc1;
     __syncthreads();
-    if (k0 + COV_KC < M16) {
-      Ag += (size_t)COV_KC * NP;
-      Cg += (size_t)COV_KC * NP;
+    if (k0 + TL_KC < M16) {
+      Ag += (size_t)TL_KC * NP;
+      Cg += (size_t)TL_KC * NP;
       pa0 = *reinterpret_cast<const double2*>(Ag);
       pa1 = *reinterpret_cast<const double2*>(Ag + half);
       pc0 = *reinterpret_cast<const double2*>(Cg);
@@ -183,9 +173,9 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
     }
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const double a = At[(kk * 4 + lq) * COV_LDN + 16 * w + lr];
+      const double a = At[(kk * 4 + lq) * TL_LDN + 16 * w + lr];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Ct[(kk * 4 + lq) * COV_LDN + 16 * c + lr], acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Ct[(kk * 4 + lq) * TL_LDN + 16 * c + lr], acc[c]);
     }
     __syncthreads();
   }
@@ -198,26 +188,26 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
       double d2 = 0.0;
 #pragma unroll
       for (int d = 0; d < 16; ++d) {
-        const double u = xiT[d * COV_T + il] - xjT[d * COV_T + jl];
+        const double u = xiT[d * TL_T + il] - xjT[d * TL_T + jl];
         d2 += u * u;
       }
-      buf[il * COV_LDT + jl] = cov_value(kernel, s2, d2) + acc[c][r];
+      buf[il * TL_LDT + jl] = cov_value(kernel, s2, d2) + acc[c][r];
     }
   __syncthreads();
   if (ti != tj) {
-    for (int e = tid; e < COV_T * COV_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int r = e >> 6, c = e & 63;
-      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(i0 + r) * N + j0 + c] = buf[r * COV_LDT + c];
+      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(i0 + r) * N + j0 + c] = buf[r * TL_LDT + c];
     }
-    for (int e = tid; e < COV_T * COV_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int c = e >> 6, r = e & 63;
-      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(j0 + c) * N + i0 + r] = buf[r * COV_LDT + c];
+      if (i0 + r < N && j0 + c < N) Sigma[(size_t)(j0 + c) * N + i0 + r] = buf[r * TL_LDT + c];
     }
   } else {
-    for (int e = tid; e < COV_T * COV_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int r = e >> 6, c = e & 63;
       const int hi = r > c ? r : c, lo = r > c ? c : r;
-      if (i0 + r < N && i0 + c < N) Sigma[(size_t)(i0 + r) * N + i0 + c] = buf[hi * COV_LDT + lo];
+      if (i0 + r < N && i0 + c < N) Sigma[(size_t)(i0 + r) * N + i0 + c] = buf[hi * TL_LDT + lo];
     }
   }
 }
@@ -234,26 +224,26 @@ __global__ __launch_bounds__(256) void k_joint_jit(const double* __restrict__ Si
 // filled when the operands are staged.
 __global__ __launch_bounds__(256) void k_joint_draw(const double* __restrict__ mu, const double* __restrict__ L, int N,
                                                      const double* __restrict__ E, int S, double* __restrict__ F0) {
-  __shared__ double Et[16 * COV_LDK];
-  __shared__ double Lt[COV_T * COV_LDK];
+  __shared__ double Et[16 * TL_LDK];
+  __shared__ double Lt[TL_T * TL_LDK];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
-  const int n0 = blockIdx.x * COV_T, s0 = blockIdx.y * 16;
-  const int kend = n0 + COV_T < N ? n0 + COV_T : N;
+  const int n0 = blockIdx.x * TL_T, s0 = blockIdx.y * 16;
+  const int kend = n0 + TL_T < N ? n0 + TL_T : N;
   d4 acc = d4{0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < kend; k0 += COV_KC) {
+  for (int k0 = 0; k0 < kend; k0 += TL_KC) {
     {
       const int r = tid >> 4, c = tid & 15, s = s0 + r, k = k0 + c;
-      Et[r * COV_LDK + c] = (s < S && k < N) ? E[(size_t)s * N + k] : 0.0;
+      Et[r * TL_LDK + c] = (s < S && k < N) ? E[(size_t)s * N + k] : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int idx = tid + 256 * u, r = idx >> 4, c = idx & 15, n = n0 + r, k = k0 + c;
-      Lt[r * COV_LDK + c] = (n < N && k <= n) ? L[(size_t)n * N + k] : 0.0;
+      Lt[r * TL_LDK + c] = (n < N && k <= n) ? L[(size_t)n * N + k] : 0.0;
     }
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk)
-      acc = TGP_MFMA(Et[lr * COV_LDK + kk * 4 + lq], Lt[(16 * w + lr) * COV_LDK + kk * 4 + lq], acc);
+      acc = TGP_MFMA(Et[lr * TL_LDK + kk * 4 + lq], Lt[(16 * w + lr) * TL_LDK + kk * 4 + lq], acc);
     __syncthreads();
   }
   const int n = n0 + 16 * w + lr;
@@ -268,18 +258,15 @@ __global__ __launch_bounds__(256) void k_joint_draw(const double* __restrict__ m
 namespace {
 struct CovPlan : Layout {
   int MP, NP;
-  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, Lq, W, A, C;
+  KzzSections kzz;
+  size_t LinvP, Lq, W, A, C;
 };
 bool cov_plan(CovPlan& p, int N, int D, int M) {
-  if (N < 1 || N > TGP_BIG_MAX_M || M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
+  if (N < 1 || N > TGP_BIG_MAX_M || !inducing_limits(M, D)) return false;
   p.MP = (int)rup((size_t)M, 128);
   p.NP = (int)rup((size_t)N, 128);
-  const size_t mm = (size_t)M * M, pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
-  p.chol_len = chol_ws_doubles(M);
-  p.Kmm = p.take(mm);
-  p.Lf = p.take(mm);
-  p.Linv = p.take(mm);
-  p.chol = p.take(p.chol_len);
+  const size_t pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
+  p.kzz.take(p, M);
   p.LinvP = p.take(pp);
   p.Lq = p.take(pp);
   p.W = p.take(pp);
@@ -317,18 +304,16 @@ int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigm
   double* ws;
   if (int rc = open_workspace("tgp_qf_cov_f64", "tgp_qf_cov_workspace_bytes", workspace, workspace_bytes, p.total, &ws)) return rc;
   const int N = md.N, D = md.D, M = md.M, MP = p.MP, NP = p.NP;
-  if (int rc = launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, M, D, md.jitter, ws + p.Kmm, ws + p.Lf, ws + p.Linv, status,
-                                 ws + p.chol, p.chol_len, st))
-    return rc;
-  hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, md.Lam, ws + p.Linv, M, MP, ws + p.Lq,
+  if (int rc = p.kzz.factor(md, ws, status, st)) return rc;
+  hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, md.Lam, ws + p.kzz.Linv, M, MP, ws + p.Lq,
                      ws + p.W, ws + p.LinvP);
   LAUNCH_CHECK();
   if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.Lq, MP, ws + p.Lq, MP, 1.0, ws + p.W, MP, st)) return rc;
-  hipLaunchKernelGGL(k_cov_a, dim3((unsigned)(NP / COV_T)), dim3(256), 0, st, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os,
+  hipLaunchKernelGGL(k_cov_a, dim3((unsigned)(NP / TL_T)), dim3(256), 0, st, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os,
                      ws + p.LinvP, MP, md.m, ws + p.A, NP, mu);
   LAUNCH_CHECK();
   if (int rc = launch_gemm_plain(false, false, 0, MP, NP, MP, 1.0, ws + p.W, MP, ws + p.A, NP, 0.0, ws + p.C, NP, st)) return rc;
-  const int nt = (N + COV_T - 1) / COV_T;
+  const int nt = (N + TL_T - 1) / TL_T;
   hipLaunchKernelGGL(k_cov_sigma, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, md.kernel, X, N, D, md.raw_ls, md.raw_os,
                      ws + p.A, ws + p.C, (M + 15) / 16 * 16, NP, Sigma);
   LAUNCH_CHECK();
@@ -347,7 +332,7 @@ int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double 
   hipLaunchKernelGGL(k_joint_jit, dim3((unsigned)(((size_t)N * N + 255) / 256)), dim3(256), 0, st, Sigma, N, jitter, ws + p.Sj);
   LAUNCH_CHECK();
   if (int rc = launch_cholesky_any(ws + p.Sj, N, Lf, nullptr, status, ws + p.chol, p.chol_len, st)) return rc;
-  hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((N + COV_T - 1) / COV_T), (unsigned)((S + 15) / 16)), dim3(256), 0, st, mu, Lf, N,
+  hipLaunchKernelGGL(k_joint_draw, dim3((unsigned)((N + TL_T - 1) / TL_T), (unsigned)((S + 15) / 16)), dim3(256), 0, st, mu, Lf, N,
                      eps, S, F0);
   LAUNCH_CHECK();
   return 0;

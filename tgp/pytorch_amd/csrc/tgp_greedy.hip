@@ -22,6 +22,7 @@
 
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_tile.hpp"
 
 namespace tgp {
 
@@ -184,7 +185,7 @@ struct GrPlan : Layout {
   size_t C, d, part, stop;  // C [M][N], d [N], part [2][nwg][GR_REC], the stop word (int32) in a section of its own
 };
 bool gr_plan(GrPlan& p, int N, int D, int M) {
-  if (N < 1 || D < 1 || D > 16 || M < 1 || M > TGP_BIG_MAX_M || M > N) return false;
+  if (N < 1 || !inducing_limits(M, D) || M > N) return false;
   p.nwg = (unsigned)(((size_t)N + GR_WG - 1) / GR_WG);
   p.C = p.take((size_t)M * (size_t)N);
   p.d = p.take((size_t)N);
@@ -212,15 +213,10 @@ int launch_greedy_inducing(const double* X, int N, int D, const double* raw_ls, 
   const dim3 grid(p.nwg), block(GR_WG);
   for (int j = 0; j < M; ++j) {
     const size_t lds = (size_t)(GR_HEAD + j) * sizeof(double);  // <= 33 144 bytes: under the default ceiling
-    if (D <= 4)
-      hipLaunchKernelGGL(k_greedy_step<4>, grid, block, lds, st, kernel, X, N, D, raw_ls, raw_os, j, min_var, ws + p.C, ws + p.d,
-                         ws + p.part, p.nwg, stop, idx, trace);
-    else if (D <= 8)
-      hipLaunchKernelGGL(k_greedy_step<8>, grid, block, lds, st, kernel, X, N, D, raw_ls, raw_os, j, min_var, ws + p.C, ws + p.d,
-                         ws + p.part, p.nwg, stop, idx, trace);
-    else
-      hipLaunchKernelGGL(k_greedy_step<16>, grid, block, lds, st, kernel, X, N, D, raw_ls, raw_os, j, min_var, ws + p.C, ws + p.d,
-                         ws + p.part, p.nwg, stop, idx, trace);
+    dispatch_dp(D, [&](auto dp) {
+      hipLaunchKernelGGL(k_greedy_step<decltype(dp)::value>, grid, block, lds, st, kernel, X, N, D, raw_ls, raw_os, j, min_var,
+                         ws + p.C, ws + p.d, ws + p.part, p.nwg, stop, idx, trace);
+    });
     LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_greedy_fin, dim3(1), block, 0, st, X, D, M, ws + p.part, p.nwg, stop, idx, Z, trace, count);

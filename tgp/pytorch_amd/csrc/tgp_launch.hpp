@@ -107,6 +107,23 @@ struct Layout {
   }
   size_t bytes() const { return total * sizeof(double) + 16; }
 };
+// The sections of launch_kzz_factor in a Layout (K_ZZ + jitter I, L, L^-1, the factorisation's scratch) and the call on them
+struct KzzSections {
+  size_t Kmm, Lf, Linv, chol, chol_len;
+  void take(Layout& l, int M) {
+    chol_len = chol_ws_doubles(M);
+    Kmm = l.take((size_t)M * M);
+    Lf = l.take((size_t)M * M);
+    Linv = l.take((size_t)M * M);
+    chol = l.take(chol_len);
+  }
+  int factor(const tgp_model& md, double* ws, int32_t* status, hipStream_t st) const {
+    return launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, md.M, md.D, md.jitter, ws + Kmm, ws + Lf, ws + Linv, status,
+                             ws + chol, chol_len, st);
+  }
+};
+inline bool inducing_limits(int M, int D) { return M >= 1 && M <= TGP_BIG_MAX_M && D >= 1 && D <= 16; }
+inline bool known_kernel(int kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
 // *first = the first 16-byte aligned double of the caller's workspace `ws`; refused when fewer than need_doubles follow it
 inline int open_workspace(const char* entry, const char* sizer, void* ws, size_t ws_bytes, size_t need_doubles, double** first) {
   const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;

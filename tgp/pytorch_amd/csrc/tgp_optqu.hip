@@ -23,23 +23,12 @@
 // two runs on the same input are bit-identical, on any device.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_tile.hpp"
 
 namespace tgp {
 
-#define OQ_T 64      /* output tile (rows and columns) of k_kxxk                                                             */
-#define OQ_KC 16     /* data rows (the contraction index) generated per step                                                  */
-#define OQ_LDN 80    /* LDS stride (f64) of a [16 n][64 i] operand tile: the 4 n rows of one MFMA operand fall in distinct banks */
-#define OQ_LDT 65    /* LDS stride (f64) of the 64 x 64 output tile in k_kxxk_fin                                             */
 #define OQ_MIN_G 128 /* smallest row group                                                                                    */
 #define OQ_WGS 1024  /* workgroups k_kxxk aims at when it splits the rows (a constant: the split must not depend on the device) */
-
-// tile t of the lower block triangle, row major: (ti, tj), tj <= ti
-__device__ __forceinline__ void oq_tile(int t, int& ti, int& tj) {
-  ti = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-  while (ti * (ti + 1) / 2 > t) --ti;
-  tj = t - ti * (ti + 1) / 2;
-}
 
 // Partial tile (ti, tj) of C = K_ZX K_XZ over the rows [g G, min(N, (g + 1) G)) and, on tile column 0, the partial of b = K_ZX y.
 // Per step of 16 rows thread (gk, gc) evaluates K(z_i, x_n) for row n = gk of the step against the inducing points gc + 16 u of
@@ -51,20 +40,19 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
                                                int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
                                                const double* __restrict__ Y, int G, int ntile, int nti, double* __restrict__ part,
                                                double* __restrict__ bpart) {
-  __shared__ double Ki[OQ_KC * OQ_LDN], Kj[OQ_KC * OQ_LDN];
-  __shared__ double ziT[DP * OQ_T], zjT[DP * OQ_T];  // [d][inducing point]: scaled rows of Z
-  __shared__ double red[16 * OQ_T];
+  __shared__ double Ki[TL_KC * TL_LDN], Kj[TL_KC * TL_LDN];
+  __shared__ double ziT[DP * TL_T], zjT[DP * TL_T];  // [d][inducing point]: scaled rows of Z
+  __shared__ double red[16 * TL_T];
   __shared__ double ils[17];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const int t = blockIdx.x, g = blockIdx.y;
   int ti, tj;
-  oq_tile(t, ti, tj);
-  const int i0 = ti * OQ_T, j0 = tj * OQ_T;
+  tile_lower(t, ti, tj);
+  const int i0 = ti * TL_T, j0 = tj * TL_T;
   const bool diag = ti == tj, want_b = tj == 0 && Y != nullptr && bpart != nullptr;
-  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  tile_scales(D, raw_ls, raw_os, ils);
   __syncthreads();
-  for (int i = tid; i < DP * OQ_T; i += 256) {
+  for (int i = tid; i < DP * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
     const int mi = i0 + c < M ? i0 + c : M - 1, mj = j0 + c < M ? j0 + c : M - 1;
     ziT[i] = d < D ? Z[(size_t)mi * D + d] * ils[d] : 0.0;
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
 #pragma unroll
   for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
   double bp[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int n0 = n_begin; n0 < n_end; n0 += OQ_KC) {
+  for (int n0 = n_begin; n0 < n_end; n0 += TL_KC) {
     {
       const int n = n0 + gk;
       const bool valid = n < n_end;
@@ -94,11 +82,11 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
         double d2 = 0.0;
 #pragma unroll
         for (int d = 0; d < DP; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
-          const double q = ziT[d * OQ_T + c] - x[d];
+          const double q = ziT[d * TL_T + c] - x[d];
           d2 += q * q;
         }
         const double kv = valid ? cov_value(kernel, s2, d2) : 0.0;
-        Ki[gk * OQ_LDN + c] = kv;
+        Ki[gk * TL_LDN + c] = kv;
         bp[u] += kv * yv;
       }
       if (!diag) {
@@ -108,35 +96,35 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
           double d2 = 0.0;
 #pragma unroll
           for (int d = 0; d < DP; ++d) {
-            const double q = zjT[d * OQ_T + c] - x[d];
+            const double q = zjT[d * TL_T + c] - x[d];
             d2 += q * q;
           }
-          Kj[gk * OQ_LDN + c] = valid ? cov_value(kernel, s2, d2) : 0.0;
+          Kj[gk * TL_LDN + c] = valid ? cov_value(kernel, s2, d2) : 0.0;
         }
       }
     }
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const double a = Ki[(kk * 4 + lq) * OQ_LDN + 16 * w + lr];
+      const double a = Ki[(kk * 4 + lq) * TL_LDN + 16 * w + lr];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Bt[(kk * 4 + lq) * OQ_LDN + 16 * c + lr], acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Bt[(kk * 4 + lq) * TL_LDN + 16 * c + lr], acc[c]);
     }
     __syncthreads();
   }
-  double* pt = part + ((size_t)g * ntile + t) * (OQ_T * OQ_T);
+  double* pt = part + ((size_t)g * ntile + t) * (TL_T * TL_T);
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pt[(16 * w + lq + 4 * r) * OQ_T + 16 * c + lr] = acc[c][r];
+    for (int r = 0; r < 4; ++r) pt[(16 * w + lq + 4 * r) * TL_T + 16 * c + lr] = acc[c][r];
   if (want_b) {  // (uniform over the workgroup)
 #pragma unroll
-    for (int u = 0; u < 4; ++u) red[gk * OQ_T + gc + 16 * u] = bp[u];
+    for (int u = 0; u < 4; ++u) red[gk * TL_T + gc + 16 * u] = bp[u];
     __syncthreads();
-    if (tid < OQ_T) {
+    if (tid < TL_T) {
       double s = 0.0;
-      for (int k = 0; k < 16; ++k) s += red[k * OQ_T + tid];
-      bpart[((size_t)g * nti + ti) * OQ_T + tid] = s;
+      for (int k = 0; k < 16; ++k) s += red[k * TL_T + tid];
+      bpart[((size_t)g * nti + ti) * TL_T + tid] = s;
     }
   }
 }
@@ -146,36 +134,36 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
 // column 0 finishes b the same way.  Rows and columns past M are masked.
 __global__ __launch_bounds__(256) void k_kxxk_fin(const double* __restrict__ part, const double* __restrict__ bpart, int ngroup,
                                                    int ntile, int nti, int M, double* __restrict__ C, int ldc, double* __restrict__ b) {
-  __shared__ double buf[OQ_T * OQ_LDT];
+  __shared__ double buf[TL_T * TL_LDT];
   const int tid = threadIdx.x, t = blockIdx.x;
   int ti, tj;
-  oq_tile(t, ti, tj);
-  const int i0 = ti * OQ_T, j0 = tj * OQ_T;
-  for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+  tile_lower(t, ti, tj);
+  const int i0 = ti * TL_T, j0 = tj * TL_T;
+  for (int e = tid; e < TL_T * TL_T; e += 256) {
     double s = 0.0;
-    for (int g = 0; g < ngroup; ++g) s += part[((size_t)g * ntile + t) * (OQ_T * OQ_T) + e];
-    buf[(e >> 6) * OQ_LDT + (e & 63)] = s;
+    for (int g = 0; g < ngroup; ++g) s += part[((size_t)g * ntile + t) * (TL_T * TL_T) + e];
+    buf[(e >> 6) * TL_LDT + (e & 63)] = s;
   }
-  if (tj == 0 && b != nullptr && bpart != nullptr && tid < OQ_T) {
+  if (tj == 0 && b != nullptr && bpart != nullptr && tid < TL_T) {
     double s = 0.0;
-    for (int g = 0; g < ngroup; ++g) s += bpart[((size_t)g * nti + ti) * OQ_T + tid];
+    for (int g = 0; g < ngroup; ++g) s += bpart[((size_t)g * nti + ti) * TL_T + tid];
     if (i0 + tid < M) b[i0 + tid] = s;
   }
   __syncthreads();
   if (ti != tj) {
-    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int r = e >> 6, c = e & 63;
-      if (i0 + r < M && j0 + c < M) C[(size_t)(i0 + r) * ldc + j0 + c] = buf[r * OQ_LDT + c];
+      if (i0 + r < M && j0 + c < M) C[(size_t)(i0 + r) * ldc + j0 + c] = buf[r * TL_LDT + c];
     }
-    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int c = e >> 6, r = e & 63;
-      if (i0 + r < M && j0 + c < M) C[(size_t)(j0 + c) * ldc + i0 + r] = buf[r * OQ_LDT + c];
+      if (i0 + r < M && j0 + c < M) C[(size_t)(j0 + c) * ldc + i0 + r] = buf[r * TL_LDT + c];
     }
   } else {
-    for (int e = tid; e < OQ_T * OQ_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int r = e >> 6, c = e & 63;
       const int hi = r > c ? r : c, lo = r > c ? c : r;
-      if (i0 + r < M && i0 + c < M) C[(size_t)(i0 + r) * ldc + i0 + c] = buf[hi * OQ_LDT + lo];
+      if (i0 + r < M && i0 + c < M) C[(size_t)(i0 + r) * ldc + i0 + c] = buf[hi * TL_LDT + lo];
     }
   }
 }
@@ -243,31 +231,28 @@ struct KxPlan : Layout {  // the row split of k_kxxk: a function of N and M alon
 };
 bool kx_plan(KxPlan& p, int N, int M) {
   if (N < 1 || M < 1 || M > TGP_BIG_MAX_M) return false;
-  p.nti = (M + OQ_T - 1) / OQ_T;
+  p.nti = (M + TL_T - 1) / TL_T;
   p.ntile = p.nti * (p.nti + 1) / 2;
   const int want = OQ_WGS / p.ntile > 1 ? OQ_WGS / p.ntile : 1;
-  const size_t g = rup(((size_t)N + want - 1) / want, OQ_KC);
+  const size_t g = rup(((size_t)N + want - 1) / want, TL_KC);
   p.G = g > OQ_MIN_G ? (int)g : OQ_MIN_G;
   p.ngroup = (N + p.G - 1) / p.G;  // <= want <= OQ_WGS
-  p.part = p.take((size_t)p.ngroup * p.ntile * OQ_T * OQ_T);
-  p.bpart = p.take((size_t)p.ngroup * p.nti * OQ_T);
+  p.part = p.take((size_t)p.ngroup * p.ntile * TL_T * TL_T);
+  p.bpart = p.take((size_t)p.ngroup * p.nti * TL_T);
   return true;
 }
 struct OqPlan : Layout {
   int MP;
-  // Kmm is J B J later, Lf is L', CP is Lam*^T and T is L'^-1 once their first contents have been consumed
-  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, CP, T, Phi, C, b, v1, v2, st2, kx;
+  // kzz.Kmm is J B J later, kzz.Lf is L', CP is Lam*^T and T is L'^-1 once their first contents have been consumed
+  KzzSections kzz;
+  size_t LinvP, CP, T, Phi, C, b, v1, v2, st2, kx;
   KxPlan k;
 };
 bool oq_plan(OqPlan& p, int N, int D, int M) {
-  if (D < 1 || D > 16 || !kx_plan(p.k, N, M)) return false;
+  if (!inducing_limits(M, D) || !kx_plan(p.k, N, M)) return false;
   p.MP = (int)rup((size_t)M, 128);
   const size_t mm = (size_t)M * M, pp = (size_t)p.MP * p.MP;
-  p.chol_len = chol_ws_doubles(M);
-  p.Kmm = p.take(mm);
-  p.Lf = p.take(mm);
-  p.Linv = p.take(mm);
-  p.chol = p.take(p.chol_len);
+  p.kzz.take(p, M);
   p.LinvP = p.take(pp);
   p.CP = p.take(pp);
   p.T = p.take(pp);
@@ -284,12 +269,10 @@ int run_kxxk(const KxPlan& k, int kernel, const double* X, int N, const double* 
              const double* raw_os, const double* Y, double* C, double* b, double* ws, hipStream_t st) {
   const dim3 grid((unsigned)k.ntile, (unsigned)k.ngroup), block(256);
   double* bpart = (Y != nullptr && b != nullptr) ? ws + k.bpart : nullptr;
-  if (D <= 4)
-    hipLaunchKernelGGL(k_kxxk<4>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
-  else if (D <= 8)
-    hipLaunchKernelGGL(k_kxxk<8>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
-  else
-    hipLaunchKernelGGL(k_kxxk<16>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti, ws + k.part, bpart);
+  dispatch_dp(D, [&](auto dp) {
+    hipLaunchKernelGGL(k_kxxk<decltype(dp)::value>, grid, block, 0, st, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, k.G, k.ntile, k.nti,
+                       ws + k.part, bpart);
+  });
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_kxxk_fin, dim3((unsigned)k.ntile), block, 0, st, ws + k.part, bpart, k.ngroup, k.ntile, k.nti, M, C, M, b);
   LAUNCH_CHECK();
@@ -310,7 +293,7 @@ size_t optimal_qu_workspace_bytes(int N, int D, int M) {
 int launch_kxxk(int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls, const double* raw_os,
                 const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes, hipStream_t st) {
   KxPlan k;
-  if (D < 1 || D > 16 || !kx_plan(k, N, M)) return TGP_E_UNSUPPORTED;  // (tgp_kxxk_f64 has named the limits)
+  if (!inducing_limits(M, D) || !kx_plan(k, N, M)) return TGP_E_UNSUPPORTED;  // (tgp_kxxk_f64 has named the limits)
   double* ws;
   if (int rc = open_workspace("tgp_kxxk_f64", "tgp_kxxk_workspace_bytes", workspace, workspace_bytes, k.total, &ws)) return rc;
   return run_kxxk(k, kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, ws, st);
@@ -326,18 +309,16 @@ int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, dou
   const int N = md.N, D = md.D, M = md.M, MP = p.MP;
   const unsigned gmm = (unsigned)(((size_t)M * M + 255) / 256), gpp = (unsigned)((size_t)MP * MP / 256), gmv = (unsigned)((M + 3) / 4);
   int32_t* st2 = reinterpret_cast<int32_t*>(ws + p.st2);
-  double *Bm = ws + p.Kmm, *Lp = ws + p.Lf, *Lpinv = ws + p.T, *LamT = ws + p.CP;  // second lives of consumed sections
-  if (int rc = launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, M, D, md.jitter, ws + p.Kmm, ws + p.Lf, ws + p.Linv, status,
-                                 ws + p.chol, p.chol_len, st))
-    return rc;
+  double *Bm = ws + p.kzz.Kmm, *Lp = ws + p.kzz.Lf, *Lpinv = ws + p.T, *LamT = ws + p.CP;  // second lives of consumed sections
+  if (int rc = p.kzz.factor(md, ws, status, st)) return rc;
   if (int rc = run_kxxk(p.k, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os, Y, ws + p.C, ws + p.b, ws + p.kx, st)) return rc;
-  hipLaunchKernelGGL(k_optqu_pad, dim3(gpp), dim3(256), 0, st, ws + p.Linv, ws + p.C, M, MP, ws + p.LinvP, ws + p.CP, st2);
+  hipLaunchKernelGGL(k_optqu_pad, dim3(gpp), dim3(256), 0, st, ws + p.kzz.Linv, ws + p.C, M, MP, ws + p.LinvP, ws + p.CP, st2);
   LAUNCH_CHECK();
   if (int rc = launch_gemm_plain(false, false, 0, MP, MP, MP, 1.0, ws + p.LinvP, MP, ws + p.CP, MP, 0.0, ws + p.T, MP, st)) return rc;
   if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.T, MP, ws + p.LinvP, MP, 0.0, ws + p.Phi, MP, st)) return rc;
   hipLaunchKernelGGL(k_optqu_b, dim3(gmm), dim3(256), 0, st, ws + p.Phi, MP, M, md.log_var_noise, md.scale, Bm);
   LAUNCH_CHECK();
-  if (int rc = launch_cholesky_any(Bm, M, Lp, Lpinv, st2, ws + p.chol, p.chol_len, st)) return rc;
+  if (int rc = launch_cholesky_any(Bm, M, Lp, Lpinv, st2, ws + p.kzz.chol, p.kzz.chol_len, st)) return rc;
   hipLaunchKernelGGL(k_optqu_lam, dim3(gmm), dim3(256), 0, st, Lpinv, M, Lam_out, LamT, st2, status);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(k_optqu_mv, dim3(gmv), dim3(256), 0, st, ws + p.LinvP, MP, M, ws + p.b, nullptr, 1.0, ws + p.v1);

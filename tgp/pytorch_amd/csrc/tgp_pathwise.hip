@@ -30,21 +30,20 @@
 // Every sum has a fixed order and nothing is accumulated with atomics: two calls on the same input are bit-identical.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_tile.hpp"
 
 namespace tgp {
 
 #define PW_SMALL_N 16384 /* up to here a workgroup owns 16 data rows, above it 64: 256 workgroups of 64 rows fill the chip once */
-#define PW_KC 16   /* contraction rows generated per step: 8 frequencies (cos, sin) or 16 inducing points                   */
-#define PW_LDN 80  /* LDS stride (f64) of the [16 k][64 n] operand tile: the 4 k rows of one MFMA operand fall in distinct banks */
 
-// LDS stride (f64) of the [16 k][16 NT] coefficient tile: 16 mod 32, the same bank argument as PW_LDN
+// LDS stride (f64) of the [16 k][16 NT] coefficient tile: 16 mod 32, the same bank argument as TL_LDN
 template <int NT>
 struct PwLdc {
   static constexpr int v = NT == 1 ? 16 : 16 * NT + 16;
 };
 
 // One step's product: D[s][n] += sum_k Ct[k][s] Ft[k][n] for the wave's row tile (offset rt in Ft) and its NTW sample tiles
-// t0, t0 + tstep, ...
+// t0, t0 + tstep, ...  (Inline like the staging and the distances: from shared functions k_pw_eval measured 0.5 % slower.)
 template <int NTW, int LDN, int LDC>
 __device__ __forceinline__ void pw_mma(const double* Ft, const double* Ct, int rt, int t0, int tstep, int lr, int lq, d4* acc) {
 #pragma unroll
@@ -69,10 +68,10 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
                                                   double* __restrict__ F0, size_t ldf) {
   static_assert(RW == 64 || RW == 16, "row tile");
   constexpr int LDC = PwLdc<NT>::v;
-  constexpr int LDN = RW == 64 ? PW_LDN : 16;                   // (16: the same bank argument, a tile of one MFMA operand)
+  constexpr int LDN = RW == 64 ? TL_LDN : 16;                   // (16: the same bank argument, a tile of one MFMA operand)
   constexpr int NTW = RW == 64 ? NT : (NT >= 4 ? NT / 4 : 1);   // sample tiles of a wave
-  __shared__ double Ft[PW_KC * LDN];
-  __shared__ double Ct[PW_KC * LDC];
+  __shared__ double Ft[TL_KC * LDN];
+  __shared__ double Ct[TL_KC * LDC];
   __shared__ double xsT[DP * RW];    // [d][data row]: scaled rows of X
   __shared__ double omS[2][8 * 16];  // [step parity][frequency of the step][d]: the step's rows of omega
   __shared__ double zS[2][16 * 16];  // [step parity][inducing point of the step][d]: the step's scaled rows of Z
@@ -83,8 +82,7 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
   // the wave's part of the product (wave-uniform): with RW = 16 and one sample tile only wave 0 multiplies
   const int rt = RW == 64 ? 16 * w : 0, t0 = RW == 64 ? 0 : w, tstep = RW == 64 ? 1 : 4;
   const bool mma = RW == 64 || NT >= 4 || w == 0;
-  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  tile_scales(D, raw_ls, raw_os, ils);
   __syncthreads();
   for (int i = tid; i < DP * RW; i += 256) {
     const int d = i / RW, c = i % RW;
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
 #pragma unroll
   for (int u = 0; u < NTW; ++u) acc[u] = d4{0.0, 0.0, 0.0, 0.0};
   // coefficient tile roles: element u of a thread is element tid + 256 u of the step's [16][16 NT] tile, row major
-  constexpr int CW = 16 * NT, CPT = PW_KC * CW / 256;  // CPT = NT elements per thread
+  constexpr int CW = 16 * NT, CPT = TL_KC * CW / 256;  // CPT = NT elements per thread
   double cv[CPT];
 
   // ---- Fourier rows: step = frequencies j0 .. j0 + 7; tile rows 0..7 are their cos rows, 8..15 their sin rows
@@ -150,9 +148,9 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
   // ---- kernel columns: step = inducing points i0 .. i0 + 15
   {
     const int gk = tid >> 4, gc = tid & 15;  // generation role: inducing point gk of the step, data rows gc + 16 u
-    for (int i0 = 0, par = 0; i0 < M; i0 += PW_KC, par ^= 1) {
+    for (int i0 = 0, par = 0; i0 < M; i0 += TL_KC, par ^= 1) {
       double pre = 0.0;  // the next step's element of Z (inducing points past M clamped: their coefficient rows are zeros)
-      if (pd < D) pre = Z[(size_t)(i0 + PW_KC + pk < M ? i0 + PW_KC + pk : M - 1) * D + pd] * ils[pd];
+      if (pd < D) pre = Z[(size_t)(i0 + TL_KC + pk < M ? i0 + TL_KC + pk : M - 1) * D + pd] * ils[pd];
 #pragma unroll
       for (int u = 0; u < CPT; ++u) {
         const int idx = tid + 256 * u, r = idx / CW, c = idx - r * CW;
@@ -244,22 +242,18 @@ __global__ __launch_bounds__(256) void k_pw_out(const double* __restrict__ Nu, i
 namespace {
 struct PwPlan : Layout {
   int MP, SP;
-  size_t Kmm, Lf, Linv, chol, chol_len, LinvP, LinvTP, LamP, Pt, EpsT, G, T, V, Nu;
+  KzzSections kzz;
+  size_t LinvP, LinvTP, LamP, Pt, EpsT, G, T, V, Nu;
 };
 bool pw_limits(int N, int D, int M, int R2, int S) {
-  return N >= 1 && D >= 1 && D <= 16 && M >= 1 && M <= TGP_BIG_MAX_M && R2 >= 1 && R2 <= TGP_PATHWISE_MAX_R2 && S >= 1 &&
-         S <= TGP_PATHWISE_MAX_S;
+  return N >= 1 && inducing_limits(M, D) && R2 >= 1 && R2 <= TGP_PATHWISE_MAX_R2 && S >= 1 && S <= TGP_PATHWISE_MAX_S;
 }
 bool pw_plan(PwPlan& p, int N, int D, int M, int R2, int S) {
   if (!pw_limits(N, D, M, R2, S)) return false;
   p.MP = (int)rup((size_t)M, 128);
   p.SP = (int)rup((size_t)S, 128);
-  const size_t mm = (size_t)M * M, pp = (size_t)p.MP * p.MP, ps = (size_t)p.MP * p.SP;
-  p.chol_len = chol_ws_doubles(M);
-  p.Kmm = p.take(mm);
-  p.Lf = p.take(mm);
-  p.Linv = p.take(mm);
-  p.chol = p.take(p.chol_len);
+  const size_t pp = (size_t)p.MP * p.MP, ps = (size_t)p.MP * p.SP;
+  p.kzz.take(p, M);
   p.LinvP = p.take(pp);
   p.LinvTP = p.take(pp);
   p.LamP = p.take(pp);
@@ -276,12 +270,10 @@ template <int NT, int RW>
 int run_eval_rw(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls, const double* raw_os,
                 const double* omega, int R2, const double* coef, int S, double* F0, size_t ldf, hipStream_t st) {
   const dim3 grid((unsigned)(((size_t)N + RW - 1) / RW)), block(256);
-  if (D <= 4)
-    hipLaunchKernelGGL((k_pw_eval<NT, 4, RW>), grid, block, 0, st, kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, ldf);
-  else if (D <= 8)
-    hipLaunchKernelGGL((k_pw_eval<NT, 8, RW>), grid, block, 0, st, kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, ldf);
-  else
-    hipLaunchKernelGGL((k_pw_eval<NT, 16, RW>), grid, block, 0, st, kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, ldf);
+  dispatch_dp(D, [&](auto dp) {
+    hipLaunchKernelGGL((k_pw_eval<NT, decltype(dp)::value, RW>), grid, block, 0, st, kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2,
+                       coef, S, F0, ldf);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -323,10 +315,8 @@ int launch_pathwise_coeff(const tgp_model& md, const double* omega, int R2, cons
   const int D = md.D, M = md.M, MP = p.MP, SP = p.SP;
   const size_t pp = (size_t)MP * MP, ps = (size_t)MP * SP, fs = (size_t)2 * R2 * S;
   const size_t most = pp > ps ? (pp > fs ? pp : fs) : (ps > fs ? ps : fs);
-  if (int rc = launch_kzz_factor(md.kernel, md.Z, md.raw_ls, md.raw_os, M, D, md.jitter, ws + p.Kmm, ws + p.Lf, ws + p.Linv, status,
-                                 ws + p.chol, p.chol_len, st))
-    return rc;
-  hipLaunchKernelGGL(k_pw_prep, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, st, md.Lam, ws + p.Linv, eps, W, md.raw_os, M, MP,
+  if (int rc = p.kzz.factor(md, ws, status, st)) return rc;
+  hipLaunchKernelGGL(k_pw_prep, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, st, md.Lam, ws + p.kzz.Linv, eps, W, md.raw_os, M, MP,
                      S, SP, R2, ws + p.LinvP, ws + p.LinvTP, ws + p.LamP, ws + p.Pt, ws + p.EpsT, coef);
   LAUNCH_CHECK();
   if (int rc = run_eval(md.kernel, md.Z, M, D, md.Z, 0, md.raw_ls, md.raw_os, omega, R2, coef, S, ws + p.Pt, (size_t)MP, st)) return rc;

@@ -17,13 +17,9 @@
 // all three sides.  Every reduction has a fixed order and nothing is accumulated with atomics: same input, same bits.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_tile.hpp"
 
 namespace tgp {
-
-#define UW_T 64    /* output tile (rows and columns)                                                                 */
-#define UW_KC 16   /* contraction indices staged per step                                                            */
-#define UW_LDK 18  /* LDS stride (f64) of the [64 r][16 k] operand tile: 16 rows x 2 k of a half wave in distinct banks */
-#define UW_LDN 80  /* LDS stride (f64) of the [16 k][64 c] operand tile: the 4 k rows of one MFMA operand in distinct banks */
 
 #define UW_FWD 0 /* C = tril(A B),                 A, B lower: k in [j, i]                                      */
 #define UW_ATB 1 /* C = alpha tril(A^T B),         A, B lower: k >= i                                           */
@@ -40,28 +36,28 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_unwhiten(const double* __restrict__ A, const double* __restrict__ B, int M, double alpha,
                                                    double* __restrict__ C, const double* __restrict__ vin, double* __restrict__ vout,
                                                    const double* __restrict__ ru, const double* __restrict__ rw) {
-  __shared__ double As[UW_T * UW_LDK];
-  __shared__ double Bs[UW_KC * UW_LDN];
-  __shared__ double vs[UW_KC];
+  __shared__ double As[TL_T * TL_LDK];
+  __shared__ double Bs[TL_KC * TL_LDN];
+  __shared__ double vs[TL_KC];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const int ti = blockIdx.y, tj = blockIdx.x;
-  const int i0 = ti * UW_T, j0 = tj * UW_T;
+  const int i0 = ti * TL_T, j0 = tj * TL_T;
   if (tj > ti) {
-    for (int e = tid; e < UW_T * UW_T; e += 256) {
+    for (int e = tid; e < TL_T * TL_T; e += 256) {
       const int row = i0 + (e >> 6), col = j0 + (e & 63);
       if (row < M && col < M) C[(size_t)row * M + col] = 0.0;
     }
     return;
   }
   const bool mv = vin != nullptr && tj == 0;
-  const int iend = i0 + UW_T < M ? i0 + UW_T : M, jend = j0 + UW_T < M ? j0 + UW_T : M;
+  const int iend = i0 + TL_T < M ? i0 + TL_T : M, jend = j0 + TL_T < M ? j0 + TL_T : M;
   const int kb = MODE == UW_FWD ? j0 : (MODE == UW_ATB ? i0 : 0);
   const int ke = MODE == UW_FWD ? iend : (MODE == UW_ATB ? M : jend);
   d4 acc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) acc[c] = d4{0.0, 0.0, 0.0, 0.0};
   double vacc = 0.0;
-  for (int k0 = kb; k0 < ke; k0 += UW_KC) {
+  for (int k0 = kb; k0 < ke; k0 += TL_KC) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int idx = tid + 256 * u;
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(256) void k_unwhiten(const double* __restrict__ A, 
           val = (kk < M && row <= kk) ? A[(size_t)kk * M + row] : 0.0;
         else
           val = (row < M && kk <= row) ? A[(size_t)row * M + kk] : 0.0;
-        As[r * UW_LDK + k] = val;
+        As[r * TL_LDK + k] = val;
       }
       {  // op(B): element (k, c) of the step
         const int c = MODE == UW_ABT ? (idx >> 4) : (idx & 63), k = MODE == UW_ABT ? (idx & 15) : (idx >> 6);
@@ -83,20 +79,20 @@ __global__ __launch_bounds__(256) void k_unwhiten(const double* __restrict__ A, 
           val = (col < M && kk <= col) ? B[(size_t)col * M + kk] : 0.0;
         else
           val = (kk < M && col <= kk) ? B[(size_t)kk * M + col] : 0.0;
-        Bs[k * UW_LDN + c] = val;
+        Bs[k * TL_LDN + c] = val;
       }
     }
-    if (mv && tid < UW_KC) vs[tid] = k0 + tid < M ? vin[k0 + tid] : 0.0;
+    if (mv && tid < TL_KC) vs[tid] = k0 + tid < M ? vin[k0 + tid] : 0.0;
     __syncthreads();
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const double a = As[(16 * w + lr) * UW_LDK + kk * 4 + lq];
+      const double a = As[(16 * w + lr) * TL_LDK + kk * 4 + lq];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Bs[(kk * 4 + lq) * UW_LDN + 16 * c + lr], acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = TGP_MFMA(a, Bs[(kk * 4 + lq) * TL_LDN + 16 * c + lr], acc[c]);
     }
-    if (mv && tid < UW_T) {
+    if (mv && tid < TL_T) {
 #pragma unroll
-      for (int k = 0; k < UW_KC; ++k) vacc += As[tid * UW_LDK + k] * vs[k];
+      for (int k = 0; k < TL_KC; ++k) vacc += As[tid * TL_LDK + k] * vs[k];
     }
     __syncthreads();
   }
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(256) void k_unwhiten(const double* __restrict__ A, 
         C[(size_t)row * M + col] = col <= row ? val : 0.0;
       }
     }
-  if (mv && tid < UW_T && i0 + tid < M) vout[i0 + tid] = vacc;
+  if (mv && tid < TL_T && i0 + tid < M) vout[i0 + tid] = vacc;
 }
 
 // Adjoint of K_ZZ = s2 f(d2), d2_ij = |(z_i - z_j) / l|^2, for a (symmetric) K_bar: with S = K_bar + K_bar^T and the derivative
@@ -128,8 +124,7 @@ __global__ __launch_bounds__(256) void k_kmm_bwd(int kernel, const double* __res
                                                   double* __restrict__ part) {
   __shared__ double ils[17];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  tile_scales(D, raw_ls, raw_os, ils);
   __syncthreads();
   const int i = blockIdx.x * 4 + w;
   if (i >= M) return;
@@ -193,7 +188,7 @@ struct UwPlan : Layout {
   size_t Kmm, chol, chol_len;
 };
 bool uw_plan(UwPlan& p, int M, int D) {
-  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
+  if (!inducing_limits(M, D)) return false;
   p.chol_len = chol_ws_doubles(M);
   p.Kmm = p.take((size_t)M * M);
   p.chol = p.take(p.chol_len);
@@ -203,7 +198,7 @@ struct UwBwdPlan : Layout {
   size_t P, Lbar, Kbar, part, chol, chol_len;
 };
 bool uw_bwd_plan(UwBwdPlan& p, int M, int D) {
-  if (M < 1 || M > TGP_BIG_MAX_M || D < 1 || D > 16) return false;
+  if (!inducing_limits(M, D)) return false;
   p.chol_len = rup(big_cholesky_workspace_doubles(M), 64);  // (the adjoint runs the blocked path at every M)
   p.P = p.take((size_t)M * M);
   p.Lbar = p.take((size_t)M * M);
@@ -215,7 +210,7 @@ bool uw_bwd_plan(UwBwdPlan& p, int M, int D) {
 template <int MODE>
 int launch_tri(const double* A, const double* B, int M, double alpha, double* C, const double* vin, double* vout, const double* ru,
                const double* rw, hipStream_t st) {
-  const unsigned nt = (unsigned)((M + UW_T - 1) / UW_T);
+  const unsigned nt = (unsigned)((M + TL_T - 1) / TL_T);
   hipLaunchKernelGGL(k_unwhiten<MODE>, dim3(nt, nt), dim3(256), 0, st, A, B, M, alpha, C, vin, vout, ru, rw);
   LAUNCH_CHECK();
   return 0;
