@@ -9,6 +9,18 @@ namespace tgp {
   int launch_rows_mt##n##_x(const RowArgs& a, int mode, size_t lds, hipStream_t st);
 DECL(1) DECL(2) DECL(3) DECL(4) DECL(5) DECL(6) DECL(7) DECL(8)
 #undef DECL
+// the units of the trimmed training kernels, k_rows<MT, .., MODE | TGP_ROWS_KT(KT), ..> with KT = Plan::KL < 4 (tgp_rows_inst.hip
+// with -DTGP_KT)
+#define DECL(n)                                                                         \
+  int launch_rows_mt##n##_kt1(const RowArgs& a, int mode, size_t lds, hipStream_t st); \
+  int launch_rows_mt##n##_kt2(const RowArgs& a, int mode, size_t lds, hipStream_t st); \
+  int launch_rows_mt##n##_kt3(const RowArgs& a, int mode, size_t lds, hipStream_t st);
+DECL(1) DECL(2) DECL(3) DECL(4) DECL(5) DECL(6) DECL(7) DECL(8)
+#undef DECL
+typedef int (*LaunchRowsFn)(const RowArgs&, int, size_t, hipStream_t);
+#define ROW(n) {launch_rows_mt##n##_kt1, launch_rows_mt##n##_kt2, launch_rows_mt##n##_kt3}
+static const LaunchRowsFn kLaunchRowsKt[8][3] = {ROW(1), ROW(2), ROW(3), ROW(4), ROW(5), ROW(6), ROW(7), ROW(8)};
+#undef ROW
 size_t rows4_lds_bytes(const Plan& p, bool train, int nw);   // tgp_rows_inst.hip (needs tgp_rows4.hpp)
 
 // Which row kernel: the 4-rows-per-wave kernel (tgp_rows4.hpp) where it measured faster -- a training launch (any
@@ -82,6 +94,10 @@ int launch_rows(const Plan& p, const tgp_model& md, const FlowProg& fp, const do
     }
     return TGP_E_UNSUPPORTED;
   }
+  // M no multiple of 16 (Plan::KL < 4; TGP_PLAN_FULL_PAD sets it to 4): the training kernel compiled for that many k-steps of the
+  // last tile (modes 1 and 200, every MT and DP; the other modes run the untrimmed kernel)
+  if ((mode == 1 || mode == 200) && p.KL >= 1 && p.KL < 4 && p.MT >= 1 && p.MT <= 8)
+    return kLaunchRowsKt[p.MT - 1][p.KL - 1](a, mode, lds, st);
   switch (p.MT) {
     case 1: return launch_rows_mt1(a, mode, lds, st);
     case 2: return launch_rows_mt2(a, mode, lds, st);

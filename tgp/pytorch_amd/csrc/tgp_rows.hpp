@@ -20,6 +20,7 @@
 // One workgroup = 4 waves = 64 rows; one wave owns 16 rows and keeps K, A, C, Abar, Kbar in registers:
 // the accumulator layout of v_mfma_f64_16x16x4 is directly the B-operand layout of the next product.
 // Per-block statistics go to a slab in HBM (deterministic two-pass reduction, no atomics).
+// The padding of M up to 16 MT rows is not multiplied by the training kernels: see KT at k_rows.
 #pragma once
 #include "tgp_dev.hpp"
 #include "tgp_prep.hpp"
@@ -129,8 +130,9 @@ __device__ __forceinline__ d4 mfma_chain(const double* a0, int step0, int nsteps
 // IS the B-operand layout), then the tile closes with the four k-steps of the diagonal block at panel k-step dstep0,
 // whose B operand is c itself:  out = Dblock * c.  With c = -(rhs tile), the panel holding +L and the diagonal block
 // holding -Dinv this is out = Dinv (rhs - sum L x).  Operand reads batched eight ahead of their MFMAs as in mfma_chain.
+// (nclose < 4: registers nclose .. 3 of c are exact zeros -- the padding of M in the last tile -- and their k-steps are left out.)
 template <int MAXSTEPS, class FA, class FB>
-__device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0, d4 c, FA fa, FB fb) {
+__device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0, d4 c, int nclose, FA fa, FB fb) {
   d4 out = {0, 0, 0, 0};
 #pragma unroll
   for (int s0 = 0; s0 < MAXSTEPS; s0 += 8) {
@@ -139,13 +141,13 @@ __device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0
     for (int u = 0; u < 8; ++u) {
       const int s = s0 + u;
       if (s < nsum) av[u] = a0[fa(s) * 64];
-      else if (s < nsum + 4) av[u] = a0[(dstep0 + s - nsum) * 64];
+      else if (s < nsum + nclose) av[u] = a0[(dstep0 + s - nsum) * 64];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int s = s0 + u;
       if (s < nsum) c = TGP_MFMA(av[u], fb(s), c);
-      else if (s < nsum + 4) out = TGP_MFMA(av[u], c[s - nsum], out);
+      else if (s < nsum + nclose) out = TGP_MFMA(av[u], c[s - nsum], out);
     }
     __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
@@ -177,12 +179,27 @@ __device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0
 // MODEX = MODE | TGP_FLOWX: the instantiation whose flow sweeps know the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX,
 // X = true).  The host launches it only for a program that holds one of those kinds; the instantiations of the original
 // kinds (MODEX = MODE) compile exactly as before.
+// KT = k-steps of tile MT - 1 that carry data (Plan::KL; round 10).  M that is no multiple of 16 leaves MR = M - 16 (MT - 1) real
+// rows in the last 16-row tile; registers r >= KT of that tile of K, A, C, Abar and Kbar (rows 16 (MT - 1) + 4 r + q >= M) are
+// exact zeros in the untrimmed kernel -- k_prep_a leaves L, L^T, -Dinv as identity and S, m as zeros on the padding -- so the
+// KT < 4 instantiations hold them as the literal 0.0 and leave out every k-step that would multiply them: NKS = 4 (MT - 1) + KT
+// k-steps per full contraction instead of 4 MT.  A compile-time value: the chains stay straight-line code (the run-time form
+// of round 9 split them into basic blocks and lost what the trim gave).  KT = 4 is the untrimmed kernel, instruction for
+// instruction; KT < 4 exists for the training mode 1 only.  Like the kind set, KT travels in MODEX -- MODEX = MODE | TGP_FLOWX |
+// TGP_ROWS_KT(KT), bits 5-6 holding 4 - KT -- so that every untrimmed instantiation keeps the name it always had.
+#define TGP_ROWS_KT(kt) ((4 - (kt)) << 5)
 template <int MT, int DP, int MODEX, int RW = 16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_rows(RowArgs a) {
+  constexpr int KT = 4 - ((MODEX >> 5) & 3);
+  static_assert((MODEX & ~((TGP_FLOWX - 1) | TGP_FLOWX | TGP_ROWS_KT(1))) == 0, "MODEX = MODE | TGP_FLOWX | TGP_ROWS_KT(KT)");
   constexpr int MODE = MODEX & (TGP_FLOWX - 1);
   constexpr bool X = MODEX & TGP_FLOWX;
   static_assert(RW == 16 || (RW == TGP_RW_SMALL && MODE == 1), "rows per wave: 16, or TGP_RW_SMALL in training mode 1");
+  static_assert(KT == 4 || (KT >= 1 && KT < 4 && MODE == 1), "k-steps of the last tile: 4, or 1 .. 3 in training mode 1");
   constexpr bool TRAIN = MODE != 0;
+  constexpr int NKS = 4 * (MT - 1) + KT;   // k-steps (4 rows of M each) that carry data
+// register r of tile i <-> k-step 4 i + r: does it carry data?  (KT = 4: true before the compiler sees a loop variable)
+#define TGP_ROWS_LIVE(ks) (KT == 4 || (ks) < NKS)
   constexpr int RBK = 4 * RW;   // data rows (= statistics columns) per workgroup
   constexpr int MP = MT * 16;
   constexpr int CT = (2 * DP + 1 + 15) / 16, CT16 = CT * 16;
@@ -425,7 +442,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // ---- K tile in B-operand layout: Kr[ks] = K[m = 4 ks + q][row nl] ----
   double Kr[4 * MT];
   // (four tiles' worth of exponentials at a time, stage by stage: independent chains for the single wave of this SIMD;
-  //  padding rows mm >= M are computed from the zero-filled Zs rows and multiplied by 0)
+  //  padding rows mm >= M are computed from the zero-filled Zs rows and multiplied by 0; a k-step past NKS is the literal
+  //  zero, and with its result unused its distances and its exponential are not emitted)
 #pragma unroll
   for (int k0 = 0; k0 < 4 * MT; k0 += 4) {
     double e[4];
@@ -441,7 +459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     exp_fast_n<4>(e);
     // (a masked multiplier, not a select: hipcc turns `cond ? s2 * e : 0` back into a branch around the whole chain)
-    TGP_EACH(u, 4) Kr[k0 + u] = (4 * (k0 + u) + q < M ? s2 : 0.0) * e[u];
+    TGP_EACH(u, 4) Kr[k0 + u] = TGP_ROWS_LIVE(k0 + u) ? (4 * (k0 + u) + q < M ? s2 : 0.0) * e[u] : 0.0;
   }
 
   ROW_STAMP(a.ws, p, 2);
@@ -455,8 +473,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     lds_barrier();
     if (i + 2 < 2 * MT) issue1(i + 2, stg[i & 1]);
     const d4 c0 = {-Kr[4 * i], -Kr[4 * i + 1], -Kr[4 * i + 2], -Kr[4 * i + 3]};
-    Aa[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * i, 4 * i, c0, [&](int st) { return st; },
+    Aa[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * i, 4 * i, c0, (KT == 4 || i < MT - 1) ? 4 : KT, [&](int st) { return st; },
                                 [&](int st) { return Aa[st / 4][st % 4]; });
+    if constexpr (KT < 4) TGP_EACH(r, 4) if (4 * i + r >= NKS) Aa[i][r] = 0.0;
   }
   ROW_STAMP(a.ws, p, 3);
   // ---- C = (S - I) A : C_i = sum_kb (S - I)[kb,i]^T A_kb ; accumulator register r of A_kb is k-step r.  Both
@@ -468,7 +487,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     commit((MT + i) & 1, KIND2, i, stg[(MT + i) & 1]);
     lds_barrier();
     if (MT + i + 2 < 2 * MT) issue1(MT + i + 2, stg[(MT + i) & 1]);
-    if constexpr (TRAIN) Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 0, 4 * MT, [&](int st) { return Aa[st / 4][st % 4]; });
+    if constexpr (TRAIN) {
+      Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 0, NKS, [&](int st) { return Aa[st / 4][st % 4]; });
+      if constexpr (KT < 4) TGP_EACH(r, 4) if (4 * i + r >= NKS) Ca[i][r] = 0.0;   // (-A on the padding, S - I being -I there)
+    }
     else   // moments only: B_i = sum_{kb >= i} Lq[kb,i]^T A_kb
       Ca[i] = mfma_chain<4 * MT>(buf + q * 16 + nl, 4 * i, 4 * (MT - i), [&](int st) { return Aa[i + st / 4][st % 4]; });
   }
@@ -479,6 +501,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
+      if (!TGP_ROWS_LIVE(4 * i + r)) continue;
       pm += mv[16 * i + 4 * r + q] * Aa[i][r];
       if constexpr (TRAIN) pc += Aa[i][r] * Ca[i][r];
       else { pa += Aa[i][r] * Aa[i][r]; pc += Ca[i][r] * Ca[i][r]; }
@@ -654,12 +677,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Ca[i][r] = mv[16 * i + 4 * r + q] * nmub + nvb2 * Ca[i][r];
+      for (int r = 0; r < 4; ++r)
+        if (TGP_ROWS_LIVE(4 * i + r)) Ca[i][r] = mv[16 * i + 4 * r + q] * nmub + nvb2 * Ca[i][r];
   }
   d4 Ba[MT];
   lds_barrier();  // every wave is done with the flow stack / forward panels before the region is overwritten
   // back substitution, last tile first: Kbar_i = Dinv_i^T (Abar_i - sum_{kb > i} L[kb,i]^T Kbar_kb), the finished tiles
-  // taken in the order kb = MT-1 .. i+1 so that the freshest one is the last operand
+  // taken in the order kb = MT-1 .. i+1 so that the freshest one is the last operand (of tile MT - 1 only its KT k-steps:
+  // fa and fb first renumber sum step st to its place in that order with the 4 - KT dead k-steps counted in)
 #pragma unroll
   for (int t = 0; t < MT; ++t) {
     const int i = MT - 1 - t, pp = t;
@@ -667,9 +692,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     commit(pp & 1, 3, i, stg[pp & 1]);
     lds_barrier();
     if (pp + 2 < MT) issue2(pp + 2, stg[pp & 1]);
-    Ba[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * (MT - 1 - i), 4 * i, Ca[i],
-                                [&](int st) { return 4 * (MT - 1 - st / 4) + st % 4; },
-                                [&](int st) { return Ba[MT - 1 - st / 4][st % 4]; });  // Kbar
+    Ba[i] = subst_chain<4 * MT>(buf + q * 16 + nl, 4 * (MT - 1 - i) - ((KT == 4 || t == 0) ? 0 : 4 - KT), 4 * i, Ca[i],
+                                (KT == 4 || t > 0) ? 4 : KT,
+                                [&](int st) { if constexpr (KT < 4) st = st < KT ? st : st + 4 - KT; return 4 * (MT - 1 - st / 4) + st % 4; },
+                                [&](int st) { if constexpr (KT < 4) st = st < KT ? st : st + 4 - KT; return Ba[MT - 1 - st / 4][st % 4]; });  // Kbar
+    if constexpr (KT < 4) TGP_EACH(r, 4) if (4 * i + r >= NKS) Ba[i][r] = 0.0;
   }
   lds_barrier();  // panels dead: the region becomes the transposition tile
 
@@ -678,11 +705,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int col = wave * RW + nl;   // this lane's data row among the workgroup's RBK statistics columns (nl < RW)
 
   // ---- phase 1: E = Kbar o K through LDS (transposed), T = E [xs, xs^2, 1] on MFMA ----
+  if (RW == 16 || nl < RW) {
 #pragma unroll
-  for (int i = 0; i < MT; ++i)
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (RW == 16 || nl < RW) tile[(16 * i + 4 * r + q) * LD + col] = Ba[i][r] * Kr[4 * i + r];
+      for (int r = 0; r < 4; ++r) tile[(16 * i + 4 * r + q) * LD + col] = TGP_ROWS_LIVE(4 * i + r) ? Ba[i][r] * Kr[4 * i + r] : 0.0;
+  }
 #pragma unroll
   for (int c = 0; c < CT16; ++c) {
     if ((c & 3) == q && (RW == 16 || nl < RW)) {
@@ -706,11 +734,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   ROW_STAMP(a.ws, p, 8);
   // ---- phase 2: A through LDS, G = A diag(vbar) A^T (lower tiles), s = A mubar ----
+  if (RW == 16 || nl < RW) {
 #pragma unroll
-  for (int i = 0; i < MT; ++i)
+    for (int i = 0; i < MT; ++i)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (RW == 16 || nl < RW) tile[(16 * i + 4 * r + q) * LD + col] = Aa[i][r];
+      for (int r = 0; r < 4; ++r) tile[(16 * i + 4 * r + q) * LD + col] = Aa[i][r];   // (the literal 0.0 past NKS)
+  }
   if (q == 0 && (RW == 16 || nl < RW)) { vbs[col] = vb; mbs[col] = mub; }
   lds_barrier();
   ROW_STAMP(a.ws, p, 17);
@@ -797,6 +826,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       a.g_rowp[(size_t)n * RP + jr] = ap[0] + ap[16] + ap[32] + ap[48];
     }
   }
+#undef TGP_ROWS_LIVE
 }
 
 }  // namespace tgp

@@ -1,6 +1,8 @@
 // tgp_rows_inst.hip -- one translation unit per MT (compiled 8x with -DTGP_MT=1..8 so the big unrolled
 // kernels build in parallel); each defines launch_rows_mt<N>().  Compiled another 8x with -DTGP_FLOWX_BUILD=1: the training
 // kernels whose flow sweeps know the extended kind set (the TGP_FLOWX bit set in MODE / NW), launch_rows_mt<N>_x().
+// Compiled another 8 x 3 times with -DTGP_KT=1..3: the training kernels (mode 1 at 16 and at 10 rows per wave, plain kind set)
+ // that leave out the padded k-steps of M's last tile (k_rows<.., MODE | TGP_ROWS_KT(KT), ..>), launch_rows_mt<N>_kt<K>().
 #include "tgp_rows.hpp"
 #include "tgp_rows4.hpp"
 #include "tgp_launch.hpp"
@@ -29,13 +31,20 @@
 #define TGP_DP16_ONLY 0
 #endif
 #define TGP_LAUNCH_DP16 CAT(TGP_LAUNCH_MT, _dp16)
+#ifndef TGP_KT
+#define TGP_KT 4
+#endif
+#if TGP_KT != 4 && TGP_FLOWX_BUILD
+#error "the trimmed units hold the plain kind set only"
+#endif
+#define TGP_LAUNCH_KT CAT(CAT(CAT(launch_rows_mt, TGP_MT), _kt), TGP_KT)
 
 namespace tgp {
 
 template <int DP, int MODE, int RW = 16>
 static int launch_one(const RowArgs& a, size_t lds, hipStream_t st) {
   constexpr bool TRAIN = MODE != 0;
-  auto kern = k_rows<TGP_MT, DP, MODE | TGP_XBIT, RW>;
+  auto kern = k_rows<TGP_MT, DP, MODE | TGP_XBIT | TGP_ROWS_KT(TGP_KT), RW>;
   static size_t lds_cur = 48 * 1024;
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &lds_cur)) return rc;
   // the row blocks, then (training) the MT passenger blocks
@@ -46,6 +55,21 @@ static int launch_one(const RowArgs& a, size_t lds, hipStream_t st) {
   return 0;
 }
 
+#if TGP_KT != 4
+// mode: 1 (16 rows per wave) or 200 (10), the two the dispatch sends here
+template <int DP>
+static int launch_kt(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
+  if (mode == 200) return launch_one<DP, 1, TGP_RW_SMALL>(a, lds, st);
+  return launch_one<DP, 1>(a, lds, st);
+}
+int TGP_LAUNCH_KT(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
+  switch (a.p.DP) {
+    case 4: return launch_kt<4>(a, mode, lds, st);
+    case 8: return launch_kt<8>(a, mode, lds, st);
+    default: return launch_kt<16>(a, mode, lds, st);
+  }
+}
+#else
 // the 4-rows-per-wave kernel (tgp_rows4.hpp): NW waves per workgroup
 template <int DP, bool TRAIN, int NW>
 static int launch_one4(const RowArgs& a, hipStream_t st) {
@@ -95,7 +119,9 @@ int TGP_LAUNCH_MT(const RowArgs& a, int mode, size_t lds, hipStream_t st) {
 }
 #endif
 
-#if TGP_MT == 1 && !TGP_FLOWX_BUILD
+#endif   // TGP_KT == 4
+
+#if TGP_MT == 1 && !TGP_FLOWX_BUILD && TGP_KT == 4
 size_t rows4_lds_bytes(const Plan& p, bool train, int nw) {
   const Row4Lds L = row4_lds(p, train, p.nslots, nw);
   return L.nb == 0 ? (size_t)1 << 30 : L.total * sizeof(double);   // (not even one quadrature node per lane fits: not a candidate)
