@@ -116,6 +116,16 @@ extern "C" {
  * TGP_E_UNSUPPORTED for it (tgp_last_error() names the entry to use).  The likelihood is the stand-alone tgp_ell_softmax_f64;
  * a C-output step composes it with tgp_qf_moments_f64 / tgp_qf_moments_bwd_f64 / tgp_kl_whitened_f64 per class. */
 #define TGP_LIK_SOFTMAX 5
+/* Poisson counts with the flow as the log-rate, y ~ Poisson(exp(G(f0))):
+ * log p(y | f0) = y G(f0) - exp(G(f0)) - lgamma(y + 1), y any real >= 0 (the library does not ask for integers), Gauss-Hermite
+ * over q(f0) (S, xs, wn required); v <= 0 counts as 0 and its adjoint is 0.  log_var_noise stays a required pointer; its value
+ * is ignored and its gradient is written as 0.  The training step always takes the general-M path.  G is not clamped: the
+ * results are the float64 formula, and a node whose exp overflows gives -inf as it would in torch.
+ * tgp_predict_f64: m1 = E[y] = sum_s wn_s exp(g_s), m2 = Var[y] = m1 + sum_s wn_s exp(2 g_s) - m1^2 (the empty program: the
+ * log-normal closed forms), logp = log sum_s wn_s Poisson(y | exp(g_s)), the log predictive pmf, formed as a log-sum-exp so
+ * that it stays finite where every term underflows; Y_std is ignored.  The predictive is discrete: the quantile and CDF
+ * entries refuse it (TGP_E_UNSUPPORTED). */
+#define TGP_LIK_POISSON 6
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -208,7 +218,8 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
 
-/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI training step runs on the general-M path at every M. */
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI or TGP_LIK_POISSON training step runs on the
+ * general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -470,7 +481,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
 
 /* TGP Gauss-Hermite expected log-likelihood through the flow (likelihoods/GaussianNonLinearMean.py:64-150),
  * with gradients w.r.t. mu, v, theta, rowp, log_var_noise.  out[0] = ELL, out[1] = dELL/dlog_var_noise.
- * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0. */
+ * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0.
+ * model->lik == TGP_LIK_POISSON: the Poisson expected log-likelihood of its #define, out[1] = 0. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -549,7 +561,7 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI: see its #define; Y_std is ignored.
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON: see their #defines; Y_std is ignored.
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
  * (WarpedGaussianLinearMean.marginal_moments), logp = log N(T(y) | mu, v + noise) + log T'(y) - log Y_std, the exact warped
  * predictive density WITH its constant (float32 pi as everywhere); rowp is ignored. */
@@ -571,8 +583,8 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
  * of F per phase.  probs[q] <= 0.5 solves sum wn Phi(z) = p, probs[q] > 0.5 the upper-tail equation sum wn Phi(-z) = 1 - p, so
  * both tails are resolved to relative accuracy.  status (device int32[1], zeroed by the caller): the call ADDS the number of
  * roots that ran out of evaluations; their t is NaN.
- * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED and TGP_LIK_SOFTMAX are
- * refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
+ * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX and
+ * TGP_LIK_POISSON are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
  * over s: same input, same bits. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32

@@ -41,7 +41,7 @@ static int check_model(const tgp_model* m, bool need_lik) {
   if (m->M > TGP_BIG_MAX_M) return TGP_E_UNSUPPORTED;
   if (!known_kernel(m->kernel)) return -1;
   if (!m->Z || !m->raw_ls || !m->raw_os || !m->m || !m->Lam || !m->log_var_noise) return -1;
-  if (need_lik && (m->lik == TGP_LIK_FLOW || m->lik == TGP_LIK_BERNOULLI))
+  if (need_lik && lik_is_quadrature(m->lik))
     if (m->S < 1 || m->nblk < 0 || !m->xs || !m->wn || check_flow_args(m)) return -1;
   return 0;
 }
@@ -191,7 +191,7 @@ static WarpedLayout warped_layout(int N, int D, int M, int S, int P, int kernel,
 
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik) {
-  if (lik == TGP_LIK_BERNOULLI) {
+  if (lik_general_only(lik)) {
     const size_t big = big_workspace_doubles(N, D, M, S, nblk, P, RP, kernel, plan);
     return big == 0 ? 0 : big * sizeof(double);
   }
@@ -282,7 +282,7 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
   if (!out) return -5;
   if (!grads || !grads->Z || !grads->raw_ls || !grads->raw_os || !grads->m || !grads->Lam || !grads->log_var_noise)
     return -6;
-  const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;   // quadrature through the flow
+  const bool flowed = lik_is_quadrature(model->lik);
   if (model->P > 0 && flowed && !grads->theta) return -6;
   if (model->RP > 0 && !grads->rowp) return -6;
   if ((mu == nullptr) != (v == nullptr)) return -7;
@@ -312,8 +312,7 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
     ad = adam_dev_of(adam);
     ad.lam_off = (long)(grads->Lam - adam->grads); ad.lam_n = (long)model->M * model->M;
   }
-  // (the fused row kernels have no Bernoulli likelihood: those steps take the general-M path at every M, as MATERN32 does)
-  bool general = takes_general_path(*model) || model->lik == TGP_LIK_BERNOULLI;
+  bool general = takes_general_path(*model) || lik_general_only(model->lik);
   if (!general && fp.nslots > 0) {
     // the fused path keeps the flow stack of a row block in LDS beside its operand tiles; a program that does not fit even
     // with one node in flight (TGP_E_LDS until round 5: M > 112 with the 5 x 6 tanh flow) takes the general-M path
@@ -920,7 +919,7 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
     if (int rc = flow_args(&mw, true, fpw, mw)) return rc;
     return launch_predict_warp(mw, fpw, mu, v, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
   }
-  const bool flowed = model->lik == TGP_LIK_FLOW || model->lik == TGP_LIK_BERNOULLI;
+  const bool flowed = lik_is_quadrature(model->lik);
   if (flowed && (model->S < 1 || !model->xs || !model->wn)) return -1;
   if (!mu) return -2;
   if (!v) return -3;
@@ -935,6 +934,11 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
 static int check_quantile_model(const tgp_model* model, const double* mu, const double* v, const double* rowp, const char* entry,
                                 bool* flowed) {
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
+  if (model->lik == TGP_LIK_POISSON) {
+    set_error_text("%s: no quantiles for TGP_LIK_POISSON: the predictive is discrete (its pmf is tgp_predict_f64's logp, one row "
+                   "per count)", entry);
+    return TGP_E_UNSUPPORTED;
+  }
   if (model->lik == TGP_LIK_BERNOULLI || model->lik == TGP_LIK_WARPED || model->lik == TGP_LIK_SOFTMAX) {
     set_error_text("%s: no quantiles for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only; a warped model's are "
                    "T^-1(mu + z sqrt(v + noise)) through tgp_flow_inverse_f64)", entry, model->lik);

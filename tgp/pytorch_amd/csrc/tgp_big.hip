@@ -1978,7 +1978,7 @@ int launch_big_step(const tgp_model& md, const FlowProg& fp, const double* X, co
       if (int rc = big_chunk_forward(pc, X + c0 * p.D, nrows, ws, ws + p.mu + c0, ws + p.v + c0, true, sf, early_k && ci == 0)) return rc;
       // likelihood of the chunk: partial (scale*ELL, scale*eta_bar, theta_bar) into this chunk's slot
       double* slot = ws + p.likslot + (size_t)ci * p.LS;
-      if (md.lik == TGP_LIK_FLOW || md.lik == TGP_LIK_BERNOULLI) {
+      if (lik_is_quadrature(md.lik)) {
         tgp_model mc = md;
         mc.N = nrows;
         if (int rc = launch_ell_quad(mc, fp, Y + c0, ws + p.mu + c0, ws + p.v + c0, rowp ? rowp + c0 * md.RP : nullptr, slot,

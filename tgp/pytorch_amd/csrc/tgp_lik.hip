@@ -92,6 +92,7 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
 // Quadrature likelihoods through the flow with gradients, E_q(f0)[log p(y | G(f0))] by Gauss-Hermite:
 //   Gaussian  (likelihoods/GaussianNonLinearMean.py:64-150)
 //   Bernoulli (likelihoods/Bernoulli.py), probit link: log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g)
+//   Poisson   (no counterpart in the reference), log link: log p(y | g) = y g - exp(g) - lgamma(y + 1)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
@@ -123,9 +124,11 @@ __device__ inline BernNode bern_node(double g, double y) {
 //   log_p = log p(y | g),  dlog_p_deta = its derivative in eta = log noise variance (kNoise only),
 //   adjoint = scale w d log p / dg for the node's normalised weight w, which starts the reverse sweep.
 // eta and einv = exp(-eta) are read once per launch, and only where kNoise is set.
+// kRowTerm: log p has a part that depends on y alone, row_term(y), which the kernel adds once per row instead of once per node.
 struct EllGauss {
   static constexpr bool kNoise = true;    // partial slot 1 carries the noise adjoint
   static constexpr bool kClampV = false;
+  static constexpr bool kRowTerm = false;
   static __device__ __forceinline__ double at(double g, double y) { return y - g; }   // the residual
   static __device__ __forceinline__ double log_p(double r, double eta, double einv) {
     return -0.5 * TGP_LOG_2PI_REF - 0.5 * eta - 0.5 * einv * r * r;
@@ -137,9 +140,23 @@ struct EllBern {
   static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
   // q(f) variances below 0 count as 0 (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0
   static constexpr bool kClampV = true;
+  static constexpr bool kRowTerm = false;
   static __device__ __forceinline__ BernNode at(double g, double y) { return bern_node(g, y); }
   static __device__ __forceinline__ double log_p(const BernNode& b, double, double) { return b.lp; }
   static __device__ __forceinline__ double adjoint(const BernNode& b, double scale, double w, double) { return scale * w * b.dg; }
+};
+// Poisson counts, the flow as the log-rate: log p(y | g) = y g - exp(g) - lgamma(y + 1), d log p / dg = y - exp(g).  g is not
+// clamped: a node whose exp overflows gives -inf, as the float64 formula does.  The exponential is taken once per node and
+// shared by the value and the adjoint; lgamma once per row (row_term).
+struct PoisNode { double g, e, y; };
+struct EllPois {
+  static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
+  static constexpr bool kClampV = true;   // as EllBern
+  static constexpr bool kRowTerm = true;
+  static __device__ __forceinline__ PoisNode at(double g, double y) { return {g, exp(g), y}; }
+  static __device__ __forceinline__ double log_p(const PoisNode& t, double, double) { return t.y * t.g - t.e; }
+  static __device__ __forceinline__ double adjoint(const PoisNode& t, double scale, double w, double) { return scale * w * (t.y - t.e); }
+  static __device__ __forceinline__ double row_term(double y) { return -lgamma(y + 1.0); }
 };
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
@@ -205,6 +222,9 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
     flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
 #pragma unroll
     for (int u = 0; u < NB; ++u) { cm += c[u]; cv += c[u] * xsn[u]; }
+  }
+  if constexpr (Lik::kRowTerm) {   // the weights sum to 1: the part of log p that is constant over the nodes, once per row
+    if (valid && qn == 0) ellp += Lik::row_term(y);
   }
   cm = group_sum(cm);
   cv = group_sum(cv);
@@ -407,6 +427,65 @@ __global__ __launch_bounds__(256) void k_predict_bern(tgp_model md, FlowProg fp,
   if (logp && Y) logp[n] = lp_done ? lp : (y != 0.0 ? y * log(P1) : 0.0) + (y != 1.0 ? (1.0 - y) * log(P0) : 0.0);
 }
 
+// Poisson predictive per row, g_s = G(mu + sqrt(2 v) x_s) the log-rate at node s (v <= 0 counts as 0):
+//   m1 = E[y] = sum_s w_s exp(g_s),  m2 = Var[y] = m1 + sum_s w_s exp(2 g_s) - m1^2   (law of total variance; the empty
+//   program: the log-normal closed forms m1 = exp(mu + v / 2), m2 = m1 + (exp(v) - 1) m1^2),
+//   logp = log sum_s w_s Poisson(y | exp(g_s)) = logsumexp_s(log w_s + y g_s - exp(g_s)) - lgamma(y + 1),
+// the log predictive pmf with its constant.  The sum is kept relative to its running maximum (rescaled when a larger term
+// arrives), so logp is finite where every single term underflows -- y = 10^4 at a rate of e^2: terms near -10^5.  Nodes past S
+// and nodes of weight 0 do not enter.  X: the extended kind set.
+template <bool X>
+__global__ __launch_bounds__(256) void k_predict_pois(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                       const double* __restrict__ v, const double* __restrict__ rowp,
+                                                       const double* __restrict__ Y, double* __restrict__ m1o,
+                                                       double* __restrict__ m2o, double* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  flow_params_lds<X>(md.theta, fp, tp, tg);
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= md.N) return;
+  const bool want_lp = logp && Y;
+  const double y = want_lp ? Y[n] : 0.0;
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
+  const double vn = v[n] > 0.0 ? v[n] : 0.0;
+  const double m_ = mu[n], sq = sqrt(2.0 * vn);
+  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
+  constexpr int NB = 4;
+  for (int s0 = 0; s0 < md.S; s0 += NB) {
+    double g[NB], der[NB], wsn[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
+      g[u] = m_ + sq * md.xs[s];
+      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, false, X>(F, g, rpn, der);
+    TGP_EACH(u, NB) {
+      if (wsn[u] > 0.0) {
+        const double e = exp(g[u]);
+        m1 += wsn[u] * e;
+        e2 += wsn[u] * e * e;
+        if (want_lp) {
+          const double t = log(wsn[u]) + y * g[u] - e;
+          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
+          else if (t > -INFINITY) se += exp(t - mx);
+        }
+      }
+    }
+  }
+  double m2 = m1 + e2 - m1 * m1;
+  if (fp.nblk == 0) {
+    m1 = exp(m_ + 0.5 * vn);
+    m2 = m1 + expm1(vn) * m1 * m1;
+  }
+  if (m1o) m1o[n] = m1;
+  if (m2o) m2o[n] = m2;
+  if (want_lp) logp[n] = mx + log(se) - lgamma(y + 1.0);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics; dsp/trainers/optimizers.py:12)
 // ---------------------------------------------------------------------------------------------------
@@ -576,6 +655,8 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
   if (int rc = md.lik == TGP_LIK_BERNOULLI
                    ? ell_launch<EllBern>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
+               : md.lik == TGP_LIK_POISSON
+                   ? ell_launch<EllPois>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                    : ell_launch<EllGauss>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp))
     return rc;
   hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
@@ -609,6 +690,11 @@ int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, co
       hipLaunchKernelGGL(k_predict_bern<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
     else
       hipLaunchKernelGGL(k_predict_bern<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+  } else if (md.lik == TGP_LIK_POISSON) {
+    if (flow_prog_extended(fp.blk, fp.nblk))
+      hipLaunchKernelGGL(k_predict_pois<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+    else
+      hipLaunchKernelGGL(k_predict_pois<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
   } else if (flow_prog_extended(fp.blk, fp.nblk))
     hipLaunchKernelGGL(k_predict<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   else

@@ -18,6 +18,7 @@ LIK_GAUSS, LIK_FLOW = 0, 1
 LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
+LIK_POISSON = 6             # counts, the flow as the log-rate (TGP_LIK_POISSON)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
 PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64

@@ -172,6 +172,51 @@ class Bernoulli(nn.Module):
         return P.reshape(-1, 1)
 
 
+class Poisson(nn.Module):
+    """p(y|G(f)) = Poisson(y | exp(G(f))) for count targets: the flow of the latent GP is the log-rate (the identity flow
+    gives the log-Gaussian Cox / Poisson GP model, a learned flow learns the link).  No parameters.  The quadrature over q(f0)
+    runs in float64 on the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with TGP_LIK_POISSON); the predictive log-pmf is a
+    log-sum-exp over the nodes.  The reference has no such class; the interface is Bernoulli's."""
+
+    def __init__(self):
+        super().__init__()
+        self.quad_points = cg.quad_points
+
+    def sample_from_output(self, f, i, **kwargs):
+        return torch.poisson(torch.exp(f))
+
+    def _flow_inputs(self, flow, X, dev, with_grad=False):
+        return GaussianNonLinearMean._flow_inputs(self, flow, X, dev, with_grad)
+
+    @staticmethod
+    def check_targets(Y):
+        """ValueError unless every target is a count: an integer >= 0 (the kernels take any real >= 0 and do not look)."""
+        Yd = Y.detach()
+        if not bool(((Yd >= 0) & (Yd == torch.round(Yd))).all()):     # (a NaN fails both comparisons)
+            raise ValueError("the Poisson likelihood takes counts: every target must be an integer >= 0")
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[y_n G(f0) - exp(G(f0))] - lgamma(y_n + 1); Y (1, MB) counts, moments (1, MB)."""
+        self.check_targets(Y)
+        assert len(flow) == 1, "Flow list must be size 1 for Poisson likelihood"
+        assert gauss_mean.size(0) == 1, "Count regression on this path has one output GP"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllPoissonFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                            gauss_cov.reshape(-1).contiguous(), theta, rowp, spec, self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """(m1, m2) = (E[y], Var[y]) of the predictive, in counts, each of gauss_mean's shape (1, MB)."""
+        assert len(flow) == 1, "Flow list must be size 1 for Poisson likelihood"
+        assert gauss_mean.size(0) == 1, "Count regression on this path has one output GP"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device)
+        lvn = torch.zeros(1, dtype=torch.float64, device=gauss_mean.device)
+        m1, m2, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(), lvn, spec, theta,
+                                self.quad_points, rowp, lik=ops.L.LIK_POISSON)
+        return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
+
+
 class MulticlassCategorical(nn.Module):
     """p(y|G(f)) = softmax(G_1(f_1), ..., G_C(f_C))[y] over C latent GPs (likelihoods/MulticlassCategorical.py): every integral
     is a Monte-Carlo mean over `SMC` joint draws of the C latents of a row (tgp_ell_softmax_f64 / tgp_predict_softmax_f64).

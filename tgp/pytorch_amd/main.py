@@ -19,6 +19,10 @@ SAL x 2) with the softmax likelihood over C latent GPs on synthetic_blobs, and r
 
     python -m tgp.pytorch_amd.main --model TGP --likelihood multiclass --dataset synthetic_blobs \\
         --train_test_seed_split 1 --num_inducing 20 --epochs 300
+
+`--likelihood poisson` trains a count regression (SVGP: the log-Gaussian Poisson model; TGP: the flow, default SAL x 1, is
+the learned link to the log-rate) on synthetic_counts, and reports the test negative log-likelihood (of the observed counts,
+under the predictive pmf) and RMSE in counts beside those of the constant-rate baseline, a Poisson at the training mean.
 """
 import argparse
 
@@ -31,7 +35,7 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical,
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson,
                           WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
@@ -47,9 +51,11 @@ HYPER = {
     ("TGP", "heart"): dict(arch="SAL_InvBCL", blocks=1, steps=None),
     ("TGP", "banknote"): dict(arch="BCL_AL", blocks=5, steps=None),
     ("TGP", "blobs"): dict(arch="SAL", blocks=2, steps=None),
+    ("TGP", "counts"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
+COUNT_DATASETS = ("synthetic_counts",)
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -59,7 +65,7 @@ def main(argv=None):
     ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
                     choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS)
-                    + list(MULTICLASS_DATASETS))
+                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
@@ -68,12 +74,12 @@ def main(argv=None):
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass"], default="gaussian",
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
-                         "softmax over C latent GPs")
+                         "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
                     help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
-                         "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP, gaussian or bernoulli)")
+                         "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli or poisson)")
     ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
                     help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
                          "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
@@ -88,6 +94,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
+    pois = args.likelihood == "poisson"
+    if pois and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood poisson: SVGP or TGP only")
+    if pois != (args.dataset in COUNT_DATASETS):
+        ap.error("--likelihood poisson goes with the count data sets (%s)" % ", ".join(COUNT_DATASETS))
     if bern and args.model == "ID_TGP":
         ap.error("--likelihood bernoulli: SVGP or TGP only")
     if bern != (args.dataset in CLASSIFICATION_DATASETS):
@@ -104,7 +115,7 @@ def main(argv=None):
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
         ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
     if args.mean != "zero" and (wgp or multi or args.model == "ID_TGP"):
-        ap.error("--mean %s: SVGP or TGP with the gaussian or bernoulli likelihood only" % args.mean)
+        ap.error("--mean %s: SVGP or TGP with the gaussian, bernoulli or poisson likelihood only" % args.mean)
     if args.qu == "optimal" and (args.model not in ("SVGP", "WGP") or args.likelihood != "gaussian" or not args.whiten):
         ap.error("--qu optimal: SVGP or WGP with the gaussian likelihood and --whiten 1 (the likelihood must be Gaussian in f)")
     if args.init_Z == "greedy" and args.likelihood == "multiclass":
@@ -154,6 +165,8 @@ def main(argv=None):
         lik = MulticlassCategorical(Dy)
     elif bern:
         lik = Bernoulli()
+    elif pois:
+        lik = Poisson()
     elif wgp:
         lik = WarpedGaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, flow=flow_specs,
                                        quad_points=cg.quad_points)
@@ -197,6 +210,16 @@ def main(argv=None):
             args.dataset, args.num_inducing, args.model, -res[4]))
         print("Dataset {}, num inducing points {}, model {}, Test Accuracy {:.3f}".format(
             args.dataset, args.num_inducing, args.model, res[5]))
+        return res
+    if pois:
+        # the constant-rate baseline: a Poisson at the mean of the training counts, its NLL and RMSE on the test counts
+        rate, y_te = dc["Y_tr"].mean(), dc["Y_te"].reshape(-1)
+        base_nll = -(y_te * torch.log(rate) - rate - torch.lgamma(y_te + 1.0)).mean().item()
+        base_rmse = ((y_te - rate) ** 2).mean().sqrt().item()
+        print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, -res[6], res[7]))
+        print("Dataset {}, constant rate {:.3f}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, rate.item(), base_nll, base_rmse))
         return res
     if args.model == "ID_TGP":       # the reference's result lines (main.py:309-324)
         print("Dataset {}, num inducing points {}, POINT ESTIMATE FLOW , Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(

@@ -25,7 +25,7 @@ from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
 from .means import MEAN_NAMES, ZeroMean, return_mean, return_projection_matrix
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical,
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson,
                           WarpedGaussianLinearMean)
 from .utils import positive_transform
 
@@ -81,9 +81,10 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
-        if isinstance(likelihood, Bernoulli):
-            # the ABI's noise pointer: read by no Bernoulli kernel, gradient 0; a buffer, so model.parameters() is the reference's
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
+        if isinstance(likelihood, (Bernoulli, Poisson)):
+            # the ABI's noise pointer: read by no Bernoulli or Poisson kernel, gradient 0; a buffer, so model.parameters() is the
+            # reference's (Bernoulli) and holds no noise parameter (Poisson)
             self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
         self.is_whiten = bool(is_whiten)
 
@@ -111,6 +112,9 @@ class sparse_MF_SP(nn.Module):
             G.append(instance_flow(fl) if isinstance(fl, list) else fl)
         self.G_matrix = nn.ModuleList(G)
         self.G_flow_connection = flow_connection
+        if self._is_poisson and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
+                                    for fl in getattr(g, "flow_arr", [])):
+            raise NotImplementedError("the Poisson likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
         # mean function (sparse_MF_SP.py:184-206); mean_is_shared: one mean for all outputs, at Dy = 1 the same object
         name = model_specs[0]
         if name != "zero":
@@ -147,6 +151,16 @@ class sparse_MF_SP(nn.Module):
     @property
     def _is_bernoulli(self):
         return isinstance(self.likelihood, Bernoulli)
+
+    @property
+    def _is_poisson(self):
+        return isinstance(self.likelihood, Poisson)
+
+    @property
+    def _lik_id(self):
+        """The `lik` of the ops calls: a lib.LIK_* for the likelihoods that are not told by the presence of a flow, else None."""
+        return (ops.L.LIK_BERNOULLI if self._is_bernoulli else ops.L.LIK_POISSON if self._is_poisson else
+                ops.L.LIK_WARPED if self._is_warped else None)
 
     @property
     def _is_warped(self):
@@ -191,7 +205,7 @@ class sparse_MF_SP(nn.Module):
             D = self.inp_dim
             return (self.Z[c], k.base_kernel.raw_lengthscale.reshape(-1, D)[c], k.raw_outputscale.reshape(-1)[c:c + 1],
                     self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c], None)
-        lvn = self._bern_lvn if self._is_bernoulli else self.likelihood.log_var_noise.reshape(-1)[:1]
+        lvn = self._bern_lvn if self._is_bernoulli or self._is_poisson else self.likelihood.log_var_noise.reshape(-1)[:1]
         return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.raw_outputscale.reshape(-1),
                 self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], lvn)
 
@@ -353,6 +367,8 @@ class sparse_MF_SP(nn.Module):
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
         if self._is_multiclass:
             return self._elbo_multiclass(X2, Y)
+        if self._is_poisson:
+            self.likelihood.check_targets(Y)      # counts only (ValueError); the kernels themselves take any real >= 0
         info = {}
         Z, rl, ro, m, Lam, lvn = self._gp_params(info=info)
         if _qu_jitter is not None:
@@ -361,7 +377,7 @@ class sparse_MF_SP(nn.Module):
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
-                   lik=ops.L.LIK_BERNOULLI if self._is_bernoulli else (ops.L.LIK_WARPED if self._is_warped else None),
+                   lik=self._lik_id,
                    grad_Y=False)
         if self._has_mean:
             if spec is None:
@@ -399,6 +415,8 @@ class sparse_MF_SP(nn.Module):
             return "the multi-class (softmax) likelihood is not Gaussian in f: q(u) has no closed-form optimum"
         if self._is_bernoulli:
             return "the Bernoulli likelihood is not Gaussian in f: q(u) has no closed-form optimum"
+        if self._is_poisson:
+            return "the Poisson likelihood is not Gaussian in f: q(u) has no closed-form optimum"
         if not isinstance(self.likelihood, GaussianLinearMean):
             if any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", [])):
                 return "input-dependent flows (ID_TGP) act on f: the likelihood is not Gaussian in f and q(u) has no closed-form optimum"
@@ -527,6 +545,11 @@ class sparse_MF_SP(nn.Module):
                     torch.where(y != 1, (1 - y) * torch.log1p(-P), torch.zeros_like(P))
             self.train()
             return lp.sum().reshape(1), ([torch.stack((1.0 - P, P), dim=1)] if return_moments else None)
+        if self._is_poisson:
+            # sum_n log p(y_n | x_n), the log predictive pmf of the observed counts, with [m1, m2] from the same launch; counts
+            # have no scale: Y_std is not used (no log Y_std is subtracted)
+            lp, m1, m2 = self._poisson_predict(X3[0], Y.reshape(-1), want_moments=return_moments)
+            return lp.sum().reshape(1), ([m1.reshape(1, MB), m2.reshape(1, MB)] if return_moments else None)
         predictive_params = None
         if return_moments:
             m1, m2, mean_q_f, cov_q_f = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
@@ -572,11 +595,52 @@ class sparse_MF_SP(nn.Module):
         self.train()
         return log_p_y, predictive_params
 
+    # ---- count models: the predictive pmf -----------------------------------------------------------------
+    def _poisson_predict(self, X2, Y, want_moments=True):
+        """ONE tgp_predict_f64 launch of a Poisson model over B blocks of the N rows of X2, block b with the counts
+        Y[b * N:(b + 1) * N] (the q(f) moments repeated B times): (logp (B * N,), m1 (N,), m2 (N,)), the moments None unless
+        asked for.  Eval mode, no autograd.  A Poisson model has no input-dependent flow, so there are no per-row parameters
+        (a mean function is part of mu) and no MC-dropout mixture."""
+        if self.fully_bayesian:
+            raise NotImplementedError("a Poisson model has no input-dependent flows, so no fully Bayesian (MC-dropout) mode")
+        self._require_gpu(X2)
+        N = X2.shape[0]
+        B = Y.numel() // N
+        assert B * N == Y.numel(), "Y must hold a whole number of blocks of X's rows"
+        self._eval_mode()
+        with torch.no_grad():
+            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X2.unsqueeze(0), diagonal=True, is_duvenaud=False)
+            spec, theta, rowp = self._flow_inputs(X2, with_grad=False)
+            assert rowp is None
+            m1, m2, lp = ops.predict(mean_q_f.reshape(-1).repeat(B), cov_q_f.reshape(-1).repeat(B), self._bern_lvn, spec,
+                                     theta.detach() if theta is not None else None, self.quad_points, None,
+                                     Y=Y.to(mean_q_f.dtype), lik=ops.L.LIK_POISSON, want_moments=want_moments)
+        self.train()
+        return (lp, m1[:N], m2[:N]) if want_moments else (lp, None, None)
+
+    def predictive_pmf(self, X, kmax: int):
+        """The predictive pmf of a count model at the rows of X (N, Dx): P of shape (N, kmax + 1), P[n, k] = p(y_n = k | x_n),
+        the exponential of tgp_predict_f64's log pmf from one launch over N (kmax + 1) rows (block k asks for the count k).
+        Rows sum to 1 once kmax is past the mass; P.cumsum(1) is the predictive CDF, from which count intervals are read."""
+        if not self._is_poisson:
+            raise NotImplementedError("predictive_pmf: a count likelihood (Poisson) only; %s models have predictive_quantiles "
+                                      "or class probabilities" % type(self.likelihood).__name__)
+        assert X.dim() == 2, "Invalid input X.shape"
+        kmax = int(kmax)
+        assert kmax >= 0, "kmax must be >= 0"
+        N = X.shape[0]
+        k = torch.arange(kmax + 1, dtype=X.dtype, device=X.device).repeat_interleave(N)
+        lp, _, _ = self._poisson_predict(X, k, want_moments=False)
+        return torch.exp(lp).reshape(kmax + 1, N).t().contiguous()
+
     # ---- exact quantiles and CDF of the predictive / posterior marginals -----------------------------------
     def _quantile_inputs(self, X, what):
         """Eval-mode q(f) moments (mu, v of shape (N,)), the noise and the flow inputs of the rows of X, under no_grad."""
         if self._is_bernoulli or self._is_multiclass:
             raise NotImplementedError("%s: a %s model has no quantiles" % (what, type(self.likelihood).__name__))
+        if self._is_poisson and what != "posterior_quantiles":
+            raise NotImplementedError("%s: the predictive of a Poisson model is discrete; predictive_pmf(X, kmax) gives its pmf "
+                                      "(cumsum: the CDF) and posterior_quantiles the quantiles of the log-rate" % what)
         if self.fully_bayesian:
             raise NotImplementedError("%s: the fully Bayesian model (an MC-dropout mixture over parameter draws) is out of "
                                       "scope; use the sampled intervals" % what)
@@ -586,7 +650,7 @@ class sparse_MF_SP(nn.Module):
             mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X.repeat(self.out_dim, 1, 1), diagonal=True,
                                                                         is_duvenaud=False)
             spec, theta, rowp = self._flow_inputs(X, with_grad=False)
-        lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
+        lvn = self._raw_params()[5].detach().reshape(-1)[:1].contiguous()
         theta = theta.detach() if theta is not None else None
         return mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous(), lvn, spec, theta, rowp
 

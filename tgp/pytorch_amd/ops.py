@@ -157,7 +157,7 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     out = [ELL_shard - KL, ELL_shard, KL, 0]; grads are d(ELL_shard - kl_scale*KL)/d(param).
     `mb_global` = global minibatch size when X is a row shard (defaults to X.shape[0]).
     `lik` = lib.LIK_BERNOULLI: probit likelihood through `flow` (a FlowSpec, possibly empty); lvn is read by no kernel and
-    its gradient is 0."""
+    its gradient is 0.  `lik` = lib.LIK_POISSON: counts Y with the flow as the log-rate, the same conventions."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -167,8 +167,9 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     N, D = X.shape
     M = m.numel()
     scale = float(N_total) / float(mb_global if mb_global is not None else N)
-    if lik == L.LIK_BERNOULLI and flow is None:
-        raise L.TgpError("the Bernoulli likelihood needs a FlowSpec (an empty one for the identity flow)")
+    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON) and flow is None:
+        raise L.TgpError("the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
+                         % ("Bernoulli" if lik == L.LIK_BERNOULLI else "Poisson"))
     md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
     ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
@@ -999,19 +1000,31 @@ def ell_flow(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
 def ell_bernoulli(Y, mu, v, flow, theta, S, rowp=None, scale=1.0):
     """Bernoulli (probit) quadrature ELL with gradients (likelihoods/Bernoulli.py expected_log_prob; tgp_ell_flow_f64 with
     TGP_LIK_BERNOULLI).  Returns dict(ell, g_mu, g_v, g_theta, g_rowp)."""
+    return _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, L.LIK_BERNOULLI)
+
+
+def ell_poisson(Y, mu, v, flow, theta, S, rowp=None, scale=1.0):
+    """Poisson quadrature ELL with gradients, the flow as the log-rate: scale sum_n E_q(f0)[y_n G(f0) - exp(G(f0))] -
+    lgamma(y_n + 1) (tgp_ell_flow_f64 with TGP_LIK_POISSON).  Returns dict(ell, g_mu, g_v, g_theta, g_rowp)."""
+    return _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, L.LIK_POISSON)
+
+
+def _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, lik):
+    """_ell_quad for a likelihood without a noise parameter (LIK_BERNOULLI, LIK_POISSON)."""
     lvn = torch.zeros(1, dtype=torch.float64, device=Y.device)      # required pointer, not read
-    res = _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_BERNOULLI)
+    res = _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, lik)
     del res["g_lvn"]
     return res
 
 
-class EllBernoulliFunction(torch.autograd.Function):
-    """ELL = Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) with autograd in (mu, v, theta, rowp)."""
+class EllNoiselessFunction(torch.autograd.Function):
+    """ELL of a quadrature likelihood without a noise parameter, `lik` = LIK_BERNOULLI (Bernoulli.expected_log_prob,
+    likelihoods/Bernoulli.py) or LIK_POISSON, with autograd in (mu, v, theta, rowp)."""
 
     @staticmethod
-    def forward(ctx, Y, mu, v, theta, rowp, flow, S):
-        res = ell_bernoulli(Y, mu.detach(), v.detach(), flow, theta.detach() if theta is not None else None, S,
-                            rowp.detach() if rowp is not None else None)
+    def forward(ctx, Y, mu, v, theta, rowp, flow, S, lik):
+        res = _ell_noiseless(Y, mu.detach(), v.detach(), flow, theta.detach() if theta is not None else None, S,
+                             rowp.detach() if rowp is not None else None, 1.0, lik)
         ctx.save_for_backward(res["g_mu"], res["g_v"], res["g_theta"],
                               res["g_rowp"] if res["g_rowp"] is not None else res["g_mu"])
         ctx.has = (theta is not None, rowp is not None)
@@ -1021,7 +1034,21 @@ class EllBernoulliFunction(torch.autograd.Function):
     def backward(ctx, g):
         gmu, gv, gth, grp = ctx.saved_tensors
         g = g.reshape(())
-        return (None, g * gmu, g * gv, g * gth if ctx.has[0] else None, g * grp if ctx.has[1] else None, None, None)
+        return (None, g * gmu, g * gv, g * gth if ctx.has[0] else None, g * grp if ctx.has[1] else None, None, None, None)
+
+
+class _EllOf:
+    """`apply(Y, mu, v, theta, rowp, flow, S)` of EllNoiselessFunction at one likelihood."""
+
+    def __init__(self, lik):
+        self.lik = lik
+
+    def apply(self, Y, mu, v, theta, rowp, flow, S):
+        return EllNoiselessFunction.apply(Y, mu, v, theta, rowp, flow, S, self.lik)
+
+
+EllBernoulliFunction = _EllOf(L.LIK_BERNOULLI)
+EllPoissonFunction = _EllOf(L.LIK_POISSON)
 
 
 class EllGaussFunction(torch.autograd.Function):
@@ -1262,7 +1289,8 @@ def flow_logdet(f, flow, theta, rowp=None, want_G=False):
 
 def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None, want_moments=True):
     """Predictive moments m1, m2 and per-row test log-likelihood kernel (see tgp_predict_f64).  lik = lib.LIK_BERNOULLI:
-    m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (`flow` a FlowSpec, possibly empty)."""
+    m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (`flow` a FlowSpec, possibly empty).
+    lik = lib.LIK_POISSON: m1 = E[y], m2 = Var[y] in counts, logp = the log predictive pmf at Y (finite however small)."""
     lib = L.load()
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")

@@ -79,6 +79,20 @@ def binary_dataset(name, seed=0):
     return X, Y.reshape(-1, 1)
 
 
+# count-regression stand-in: (rows, inputs)
+COUNTS_SHAPE = (800, 2)
+
+
+def counts_dataset(seed=0):
+    """Seeded `synthetic_counts`: X ~ N(0, 1), y ~ Poisson(exp(1 + sin(2 x0) + 0.5 x1)).  Returns numpy float64 X (n, d) and
+    Y (n, 1) with integer counts >= 0."""
+    n, d = COUNTS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    Y = rng.poisson(np.exp(1.0 + np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1]))
+    return X, Y.astype(np.float64).reshape(-1, 1)
+
+
 # multi-class stand-in: (rows, inputs, classes)
 BLOBS_SHAPE = (1200, 4, 4)
 
