@@ -126,6 +126,21 @@ extern "C" {
  * that it stays finite where every term underflows; Y_std is ignored.  The predictive is discrete: the quantile and CDF
  * entries refuse it (TGP_E_UNSUPPORTED). */
 #define TGP_LIK_POISSON 6
+/* Student-t noise around the flow for robust regression, y | f0 ~ StudentT(nu, loc = G(f0), scale = sigma).  For this likelihood
+ * model->log_var_noise points to TWO doubles {eta = log sigma^2, nu}: eta is the log of the squared SCALE (not of the variance,
+ * which is sigma^2 nu / (nu - 2)), nu the degrees of freedom, a fixed hyper-parameter.  Supported range 2 < nu <= 1e4 (past it
+ * the two lgamma of the constant cancel to ~1e-9 and the Gaussian likelihood is the model to take); the library does not look
+ * at nu, which lives on the device.  With r = y - g:
+ *   log p(y | g) = lgamma((nu+1)/2) - lgamma(nu/2) - log(nu pi)/2 - eta/2 - (nu+1)/2 log1p(r^2 / (nu sigma^2))
+ *   d log p / dg = (nu+1) r / (nu sigma^2 + r^2),   d log p / d eta = -1/2 + (nu+1) r^2 / (2 (nu sigma^2 + r^2)),
+ * double-precision pi, g not clamped, Gauss-Hermite over q(f0) (S, xs, wn required); v <= 0 counts as 0 and its adjoint is 0.
+ * Gradients: grads->log_var_noise stays ONE double, d/d eta (as out[1] of tgp_ell_flow_f64); nu has no gradient and nothing is
+ * written for it.  The training step always takes the general-M path.
+ * tgp_predict_f64, in the standardised units of the other regression likelihoods: m1 = sum_s wn_s g_s, m2 = sum_s wn_s g_s^2 -
+ * m1^2 + sigma^2 nu / (nu - 2) (+inf for nu <= 2), logp = log sum_s wn_s t_nu(y | g_s, sigma) - log Y_std, the exact log
+ * predictive density of the raw target WITH every constant, formed as a log-sum-exp.  The empty program runs the same sum.
+ * The quantile and CDF entries refuse it (TGP_E_UNSUPPORTED): the CDF needs the incomplete beta function. */
+#define TGP_LIK_STUDENT 7
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -218,8 +233,8 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
 
-/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI or TGP_LIK_POISSON training step runs on the
- * general-M path at every M. */
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON or TGP_LIK_STUDENT training step runs
+ * on the general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -482,7 +497,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
 /* TGP Gauss-Hermite expected log-likelihood through the flow (likelihoods/GaussianNonLinearMean.py:64-150),
  * with gradients w.r.t. mu, v, theta, rowp, log_var_noise.  out[0] = ELL, out[1] = dELL/dlog_var_noise.
  * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0.
- * model->lik == TGP_LIK_POISSON: the Poisson expected log-likelihood of its #define, out[1] = 0. */
+ * model->lik == TGP_LIK_POISSON: the Poisson expected log-likelihood of its #define, out[1] = 0.
+ * model->lik == TGP_LIK_STUDENT: the Student-t one of its #define (log_var_noise = {log sigma^2, nu}), out[1] = dELL/dlog sigma^2. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -562,6 +578,7 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
  * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON: see their #defines; Y_std is ignored.
+ * TGP_LIK_STUDENT: see its #define (Y_std is used, the constant is included).
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
  * (WarpedGaussianLinearMean.marginal_moments), logp = log N(T(y) | mu, v + noise) + log T'(y) - log Y_std, the exact warped
  * predictive density WITH its constant (float32 pi as everywhere); rowp is ignored. */
@@ -583,8 +600,8 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
  * of F per phase.  probs[q] <= 0.5 solves sum wn Phi(z) = p, probs[q] > 0.5 the upper-tail equation sum wn Phi(-z) = 1 - p, so
  * both tails are resolved to relative accuracy.  status (device int32[1], zeroed by the caller): the call ADDS the number of
  * roots that ran out of evaluations; their t is NaN.
- * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX and
- * TGP_LIK_POISSON are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
+ * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX,
+ * TGP_LIK_POISSON and TGP_LIK_STUDENT are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
  * over s: same input, same bits. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32

@@ -939,6 +939,11 @@ static int check_quantile_model(const tgp_model* model, const double* mu, const 
                    "per count)", entry);
     return TGP_E_UNSUPPORTED;
   }
+  if (model->lik == TGP_LIK_STUDENT) {
+    set_error_text("%s: no quantiles for TGP_LIK_STUDENT: the CDF of a Student-t mixture needs the incomplete beta function "
+                   "(its density is tgp_predict_f64's logp)", entry);
+    return TGP_E_UNSUPPORTED;
+  }
   if (model->lik == TGP_LIK_BERNOULLI || model->lik == TGP_LIK_WARPED || model->lik == TGP_LIK_SOFTMAX) {
     set_error_text("%s: no quantiles for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only; a warped model's are "
                    "T^-1(mu + z sqrt(v + noise)) through tgp_flow_inverse_f64)", entry, model->lik);

@@ -125,9 +125,11 @@ struct KzzSections {
 inline bool inducing_limits(int M, int D) { return M >= 1 && M <= TGP_BIG_MAX_M && D >= 1 && D <= 16; }
 inline bool known_kernel(int kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
 // the likelihoods k_ell_quad integrates by Gauss-Hermite through the flow (S, xs, wn, the program and theta are read)
-inline bool lik_is_quadrature(int lik) { return lik == TGP_LIK_FLOW || lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON; }
+inline bool lik_is_quadrature(int lik) {
+  return lik == TGP_LIK_FLOW || lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT;
+}
 // ... of which these have no fused row kernel: their training step takes the general-M path at every M, as MATERN32 does
-inline bool lik_general_only(int lik) { return lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON; }
+inline bool lik_general_only(int lik) { return lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT; }
 // *first = the first 16-byte aligned double of the caller's workspace `ws`; refused when fewer than need_doubles follow it
 inline int open_workspace(const char* entry, const char* sizer, void* ws, size_t ws_bytes, size_t need_doubles, double** first) {
   const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
@@ -157,8 +159,8 @@ int launch_mlp_backward(const tgp_mlp& d, const double* X, const double* W, cons
 // tgp_lik.hip
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* log_var_noise,
                      double scale, double* out, double* g_mu, double* g_v, double* ws, hipStream_t st);
-// the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, Poisson for TGP_LIK_POISSON, else
-// Gaussian (TGP_LIK_FLOW)
+// the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, Poisson for TGP_LIK_POISSON, Student-t
+// for TGP_LIK_STUDENT, else Gaussian (TGP_LIK_FLOW)
 int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st);
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,

@@ -93,6 +93,7 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
 //   Gaussian  (likelihoods/GaussianNonLinearMean.py:64-150)
 //   Bernoulli (likelihoods/Bernoulli.py), probit link: log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g)
 //   Poisson   (no counterpart in the reference), log link: log p(y | g) = y g - exp(g) - lgamma(y + 1)
+//   Student-t (no counterpart in the reference), location G(f0), scale sigma, nu degrees of freedom (TGP_LIK_STUDENT)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
@@ -120,30 +121,44 @@ __device__ inline BernNode bern_node(double g, double y) {
   return r;
 }
 
-// What a likelihood supplies to k_ell_quad, per quadrature node with g = G(f0): at(g, y) = whatever the three terms share, then
-//   log_p = log p(y | g),  dlog_p_deta = its derivative in eta = log noise variance (kNoise only),
+// What a likelihood supplies to k_ell_quad.  Once per launch: consts(log_var_noise) = its launch constants K (a struct of its
+// own: the noise pair, nothing, or StudentConst).  Per quadrature node with g = G(f0): at(g, y, K) = whatever the three
+// terms share, then
+//   log_p = log p(y | g),  dlog_p_deta = its derivative in eta = log_var_noise[0] (kNoise only),
 //   adjoint = scale w d log p / dg for the node's normalised weight w, which starts the reverse sweep.
-// eta and einv = exp(-eta) are read once per launch, and only where kNoise is set.
+// log_var_noise is read only where kNoise is set.
 // kRowTerm: log p has a part that depends on y alone, row_term(y), which the kernel adds once per row instead of once per node.
+// kBlockTerm: log p has a part that is the same for every row and node, block_term(K), which the kernel adds once per
+// workgroup, times its number of rows (the weights of a row sum to 1).
+struct EllNoise { double eta, einv; };    // eta = log noise variance, einv = exp(-eta)
+struct EllNone {};
 struct EllGauss {
   static constexpr bool kNoise = true;    // partial slot 1 carries the noise adjoint
   static constexpr bool kClampV = false;
   static constexpr bool kRowTerm = false;
-  static __device__ __forceinline__ double at(double g, double y) { return y - g; }   // the residual
-  static __device__ __forceinline__ double log_p(double r, double eta, double einv) {
-    return -0.5 * TGP_LOG_2PI_REF - 0.5 * eta - 0.5 * einv * r * r;
+  static constexpr bool kBlockTerm = false;
+  static __device__ __forceinline__ EllNoise consts(const double* lvn) { return {lvn[0], exp(-lvn[0])}; }
+  static __device__ __forceinline__ double at(double g, double y, const EllNoise&) { return y - g; }   // the residual
+  static __device__ __forceinline__ double log_p(double r, const EllNoise& k) {
+    return -0.5 * TGP_LOG_2PI_REF - 0.5 * k.eta - 0.5 * k.einv * r * r;
   }
-  static __device__ __forceinline__ double dlog_p_deta(double r, double einv) { return -0.5 + 0.5 * einv * r * r; }
-  static __device__ __forceinline__ double adjoint(double r, double scale, double w, double einv) { return scale * einv * w * r; }
+  static __device__ __forceinline__ double dlog_p_deta(double r, const EllNoise& k) { return -0.5 + 0.5 * k.einv * r * r; }
+  static __device__ __forceinline__ double adjoint(double r, double scale, double w, const EllNoise& k) {
+    return scale * k.einv * w * r;
+  }
 };
 struct EllBern {
   static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
   // q(f) variances below 0 count as 0 (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0
   static constexpr bool kClampV = true;
   static constexpr bool kRowTerm = false;
-  static __device__ __forceinline__ BernNode at(double g, double y) { return bern_node(g, y); }
-  static __device__ __forceinline__ double log_p(const BernNode& b, double, double) { return b.lp; }
-  static __device__ __forceinline__ double adjoint(const BernNode& b, double scale, double w, double) { return scale * w * b.dg; }
+  static constexpr bool kBlockTerm = false;
+  static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
+  static __device__ __forceinline__ BernNode at(double g, double y, const EllNone&) { return bern_node(g, y); }
+  static __device__ __forceinline__ double log_p(const BernNode& b, const EllNone&) { return b.lp; }
+  static __device__ __forceinline__ double adjoint(const BernNode& b, double scale, double w, const EllNone&) {
+    return scale * w * b.dg;
+  }
 };
 // Poisson counts, the flow as the log-rate: log p(y | g) = y g - exp(g) - lgamma(y + 1), d log p / dg = y - exp(g).  g is not
 // clamped: a node whose exp overflows gives -inf, as the float64 formula does.  The exponential is taken once per node and
@@ -153,10 +168,48 @@ struct EllPois {
   static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
   static constexpr bool kClampV = true;   // as EllBern
   static constexpr bool kRowTerm = true;
-  static __device__ __forceinline__ PoisNode at(double g, double y) { return {g, exp(g), y}; }
-  static __device__ __forceinline__ double log_p(const PoisNode& t, double, double) { return t.y * t.g - t.e; }
-  static __device__ __forceinline__ double adjoint(const PoisNode& t, double scale, double w, double) { return scale * w * (t.y - t.e); }
+  static constexpr bool kBlockTerm = false;
+  static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
+  static __device__ __forceinline__ PoisNode at(double g, double y, const EllNone&) { return {g, exp(g), y}; }
+  static __device__ __forceinline__ double log_p(const PoisNode& t, const EllNone&) { return t.y * t.g - t.e; }
+  static __device__ __forceinline__ double adjoint(const PoisNode& t, double scale, double w, const EllNone&) {
+    return scale * w * (t.y - t.e);
+  }
   static __device__ __forceinline__ double row_term(double y) { return -lgamma(y + 1.0); }
+};
+// Student-t noise of scale sigma around the flow, nu degrees of freedom (TGP_LIK_STUDENT): log_var_noise = {eta = log sigma^2,
+// nu}.  With r = y - g and q = nu sigma^2 + r^2:
+//   log p(y | g) = c(nu, eta) - (nu + 1) / 2 log1p(r^2 / (nu sigma^2)),  c = lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2 - eta / 2
+//   d log p / dg = (nu + 1) r / q,   d log p / d eta = -1/2 + (nu + 1) r^2 / (2 q).
+// g is not clamped.  One division per node, h = (nu + 1) / q, shared by both derivatives; 1 / (nu sigma^2) once per launch; c,
+// with its two lgamma, once per workgroup (block_term), by one lane.  |r| = 10^8 sigma: r^2 / (nu sigma^2) ~ 10^16, nothing
+// overflows.
+struct StudentConst { double eta, nu, nu1, nus2, inus2; };   // nu1 = nu + 1, nus2 = nu sigma^2, inus2 = 1 / nus2
+struct StudentNode { double r, r2, h; };                     // h = (nu + 1) / (nu sigma^2 + r^2)
+__device__ inline double student_log_const(double nu, double eta) {
+  return lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846) - 0.5 * eta;
+}
+struct EllStudent {
+  static constexpr bool kNoise = true;    // partial slot 1 carries the adjoint of eta (nu is not trained)
+  static constexpr bool kClampV = true;   // as EllBern
+  static constexpr bool kRowTerm = false;
+  static constexpr bool kBlockTerm = true;
+  static __device__ __forceinline__ StudentConst consts(const double* lvn) {
+    const double eta = lvn[0], nu = lvn[1], nus2 = nu * exp(eta);
+    return {eta, nu, nu + 1.0, nus2, 1.0 / nus2};
+  }
+  static __device__ __forceinline__ StudentNode at(double g, double y, const StudentConst& k) {
+    const double r = y - g, r2 = r * r;
+    return {r, r2, k.nu1 / (k.nus2 + r2)};
+  }
+  static __device__ __forceinline__ double log_p(const StudentNode& t, const StudentConst& k) {
+    return -0.5 * k.nu1 * log1p(t.r2 * k.inus2);
+  }
+  static __device__ __forceinline__ double dlog_p_deta(const StudentNode& t, const StudentConst&) { return -0.5 + 0.5 * t.h * t.r2; }
+  static __device__ __forceinline__ double adjoint(const StudentNode& t, double scale, double w, const StudentConst&) {
+    return scale * w * t.h * t.r;
+  }
+  static __device__ __forceinline__ double block_term(const StudentConst& k) { return student_log_const(k.nu, k.eta); }
 };
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
@@ -195,7 +248,7 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
   };
   const bool valid = n < md.N;
   const int nc = valid ? n : md.N - 1;
-  const double eta = Lik::kNoise ? md.log_var_noise[0] : 0.0, einv = Lik::kNoise ? exp(-eta) : 0.0;
+  const auto K = Lik::consts(md.log_var_noise);
   FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
   double ellp = 0.0, etap = 0.0, cm = 0.0, cv = 0.0;
   const double m_ = mu[nc], vn = Lik::kClampV ? (v[nc] > 0.0 ? v[nc] : 0.0) : v[nc];
@@ -214,10 +267,10 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
     flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-      const auto t = Lik::at(f[u], y);
-      ellp += wsn[u] * Lik::log_p(t, eta, einv);
-      if constexpr (Lik::kNoise) etap += wsn[u] * Lik::dlog_p_deta(t, einv);
-      c[u] = Lik::adjoint(t, md.scale, wsn[u], einv);
+      const auto t = Lik::at(f[u], y, K);
+      ellp += wsn[u] * Lik::log_p(t, K);
+      if constexpr (Lik::kNoise) etap += wsn[u] * Lik::dlog_p_deta(t, K);
+      c[u] = Lik::adjoint(t, md.scale, wsn[u], K);
     }
     flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
 #pragma unroll
@@ -245,6 +298,10 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
   __syncthreads();
   double* pb = part + (size_t)blockIdx.x * (2 + P);
   if (tid == 0) {
+    if constexpr (Lik::kBlockTerm) {   // the part of log p that no row or node changes, times this workgroup's rows
+      const int r0 = blockIdx.x * (4 * RW), nr = md.N - r0 < 4 * RW ? md.N - r0 : 4 * RW;
+      red[0] += (double)nr * Lik::block_term(K);
+    }
     pb[0] = md.scale * (red[0] + red[1] + red[2] + red[3]);
     pb[1] = Lik::kNoise ? md.scale * (red[4] + red[5] + red[6] + red[7]) : 0.0;
   }
@@ -486,6 +543,61 @@ __global__ __launch_bounds__(256) void k_predict_pois(tgp_model md, FlowProg fp,
   if (want_lp) logp[n] = mx + log(se) - lgamma(y + 1.0);
 }
 
+// Student-t predictive per row, in the standardised units of k_predict, g_s = G(mu + sqrt(2 v) x_s) (v <= 0 counts as 0):
+//   m1 = sum_s w_s g_s,  m2 = sum_s w_s g_s^2 - m1^2 + sigma^2 nu / (nu - 2)   (+inf for nu <= 2: no variance),
+//   logp = log sum_s w_s t_nu(y | g_s, sigma) - log Y_std = logsumexp_s(log w_s - (nu + 1) / 2 log1p(r_s^2 / (nu sigma^2)))
+//          + c(nu, eta) - log Y_std,
+// the exact log predictive density of the raw target with every constant; the sum is kept relative to its running maximum
+// as in k_predict_pois.  The empty program runs the same loop (no closed form for the Gaussian-Student convolution; the
+// two moments are exact at S >= 2).  Nodes past S and nodes of weight 0 do not enter.  X: the extended kind set.
+template <bool X>
+__global__ __launch_bounds__(256) void k_predict_student(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                          const double* __restrict__ v, const double* __restrict__ rowp,
+                                                          const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
+                                                          double* __restrict__ m2o, double* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  flow_params_lds<X>(md.theta, fp, tp, tg);
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= md.N) return;
+  const bool want_lp = logp && Y;
+  const double y = want_lp ? Y[n] : 0.0;
+  const StudentConst K = EllStudent::consts(md.log_var_noise);
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
+  const double vn = v[n] > 0.0 ? v[n] : 0.0;
+  const double m_ = mu[n], sq = sqrt(2.0 * vn);
+  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
+  constexpr int NB = 4;
+  for (int s0 = 0; s0 < md.S; s0 += NB) {
+    double g[NB], der[NB], wsn[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
+      g[u] = m_ + sq * md.xs[s];
+      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, false, X>(F, g, rpn, der);
+    TGP_EACH(u, NB) {
+      if (wsn[u] > 0.0) {
+        m1 += wsn[u] * g[u];
+        e2 += wsn[u] * g[u] * g[u];
+        if (want_lp) {
+          const double r = y - g[u];
+          const double t = log(wsn[u]) - 0.5 * K.nu1 * log1p(r * r * K.inus2);
+          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
+          else if (t > -INFINITY) se += exp(t - mx);
+        }
+      }
+    }
+  }
+  if (m1o) m1o[n] = m1;
+  if (m2o) m2o[n] = K.nu > 2.0 ? e2 - m1 * m1 + K.nus2 / (K.nu - 2.0) : INFINITY;
+  if (want_lp) logp[n] = mx + log(se) + student_log_const(K.nu, K.eta) - log(Y_std);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics; dsp/trainers/optimizers.py:12)
 // ---------------------------------------------------------------------------------------------------
@@ -657,6 +769,8 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
                    ? ell_launch<EllBern>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                : md.lik == TGP_LIK_POISSON
                    ? ell_launch<EllPois>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
+               : md.lik == TGP_LIK_STUDENT
+                   ? ell_launch<EllStudent>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                    : ell_launch<EllGauss>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp))
     return rc;
   hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
@@ -695,6 +809,11 @@ int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, co
       hipLaunchKernelGGL(k_predict_pois<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
     else
       hipLaunchKernelGGL(k_predict_pois<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+  } else if (md.lik == TGP_LIK_STUDENT) {
+    if (flow_prog_extended(fp.blk, fp.nblk))
+      hipLaunchKernelGGL(k_predict_student<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
+    else
+      hipLaunchKernelGGL(k_predict_student<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   } else if (flow_prog_extended(fp.blk, fp.nblk))
     hipLaunchKernelGGL(k_predict<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
   else

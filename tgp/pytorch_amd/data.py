@@ -175,11 +175,21 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     base = dataset_name.replace("synthetic_", "")
     if synth and (base in BINARY_SHAPES or base in ("blobs", "counts")):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
-    if (synth and base not in SHAPES) or (not synth and base not in UCI):
+    if (synth and base not in SHAPES and base != "outliers") or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
-    if synth:
+    outlier_idx = None
+    if synth and base == "outliers":
+        # synthetic_outliers (synthetic.outliers_dataset): 10 % of the TRAINING targets are gross errors, the test split is clean
+        from .synthetic import OUTLIERS_SHAPE, gross_errors, outliers_dataset
+        n, d, n_tr = OUTLIERS_SHAPE
+        X, Y = outliers_dataset()
+        perm = numpy.random.default_rng(seed).permutation(n)
+        tr_idx, te_idx = perm[:n_tr], perm[n_tr:]
+        X_tr, X_te, Y_te = X[tr_idx], X[te_idx], Y[te_idx]
+        Y_tr, outlier_idx = gross_errors(Y[tr_idx], seed=0 if seed is None else int(seed))
+    elif synth:
         n, d, n_tr = SHAPES[base]
         X, Y = _synthetic(base, seed)
         perm = numpy.random.default_rng(seed).permutation(n)
@@ -204,4 +214,6 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
                    "N_tr": X_tr.shape[0], "N_va": 0 if X_va is None else X_va.shape[0], "N_te": X_te.shape[0],
                    "Dx": X_tr.shape[1], "Dy": 1, "Y_std": Y_std, "X_all": None, "Y_all": None,
                    "train_idx": numpy.asarray(tr_idx), "test_idx": numpy.asarray(te_idx)}
+    if outlier_idx is not None and use_validation is None:
+        data_config["outlier_idx"] = outlier_idx        # rows of the training split that hold a gross error
     return loaders, data_config

@@ -19,6 +19,8 @@ LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
 LIK_POISSON = 6             # counts, the flow as the log-rate (TGP_LIK_POISSON)
+LIK_STUDENT = 7             # Student-t noise around the flow (TGP_LIK_STUDENT): log_var_noise = {log sigma^2, nu}
+STUDENT_MAX_DF = 1e4        # the supported degrees of freedom are 2 < nu <= STUDENT_MAX_DF (include/tgp_hip.h)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
 PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64

@@ -217,6 +217,50 @@ class Poisson(nn.Module):
         return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
 
 
+class StudentT(_GaussianBase):
+    """p(y|G(f)) = StudentT(y | df, loc = G(f), scale = sigma) for regression with gross errors in the targets: heavy tails keep
+    a few outliers from inflating the noise and with it every predictive interval.  `log_var_noise` (the Gaussian classes' name
+    and shape) holds log sigma^2, the log of the squared SCALE -- the noise variance is sigma^2 df / (df - 2); `noise_init` is
+    sigma^2.  `df`, the degrees of freedom, is a fixed hyper-parameter kept as a buffer: it is not in parameters(), so no
+    optimiser or weight decay moves it.  Supported range 2 < df <= 1e4 (ValueError outside): at or below 2 there is no variance,
+    far above the Gaussian likelihood is the model to take.  The quadrature over q(f0) runs in float64 on the GPU
+    (tgp_ell_flow_f64 / tgp_predict_f64 with TGP_LIK_STUDENT).  The reference has no such class."""
+
+    def __init__(self, out_dim, noise_init, noise_is_shared, quadrature_points, df=4.0):
+        super().__init__(out_dim, noise_init, noise_is_shared)
+        self.quad_points = quadrature_points
+        self.register_buffer("df", torch.tensor([ops.check_student_df(df)], dtype=cg.dtype))
+
+    def _flow_inputs(self, flow, X, dev, with_grad=False):
+        return GaussianNonLinearMean._flow_inputs(self, flow, X, dev, with_grad)
+
+    def sample_from_output(self, f, i, **kwargs):
+        """G(f) + sigma t, t a Student-t draw of df degrees of freedom."""
+        sd = torch.sqrt(positive_transform(self._lvn()[i])).detach()
+        t = td.StudentT(self.df.to(f.device, f.dtype)).sample(f.shape).reshape(f.shape)
+        return f + sd * t
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[log StudentT(y_n | df, G(f0), sigma)], differentiable in the moments, log_var_noise and the flow's
+        parameters; Y (1, MB), moments (1, MB)."""
+        assert len(flow) == self.out_dim == 1, "one flow per output; Dy = 1 on this path"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllStudentFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                            gauss_cov.reshape(-1).contiguous(), self._lvn().reshape(-1)[:1].contiguous(),
+                                            self.df, theta, rowp, spec, self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """(m1, m2) = mean and variance of the predictive in standardised units, each of gauss_mean's shape (1, MB); m2 holds
+        the Student-t's own variance sigma^2 df / (df - 2)."""
+        assert len(flow) == self.out_dim == 1
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device)
+        m1, m2, _ = ops.predict(gauss_mean.reshape(-1).contiguous(), gauss_cov.reshape(-1).contiguous(),
+                                self._lvn().detach().reshape(-1)[:1].contiguous(), spec, theta, self.quad_points, rowp,
+                                lik=ops.L.LIK_STUDENT, df=self.df)
+        return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
+
+
 class MulticlassCategorical(nn.Module):
     """p(y|G(f)) = softmax(G_1(f_1), ..., G_C(f_C))[y] over C latent GPs (likelihoods/MulticlassCategorical.py): every integral
     is a Monte-Carlo mean over `SMC` joint draws of the C latents of a row (tgp_ell_softmax_f64 / tgp_predict_softmax_f64).

@@ -23,6 +23,12 @@ SAL x 2) with the softmax likelihood over C latent GPs on synthetic_blobs, and r
 `--likelihood poisson` trains a count regression (SVGP: the log-Gaussian Poisson model; TGP: the flow, default SAL x 1, is
 the learned link to the log-rate) on synthetic_counts, and reports the test negative log-likelihood (of the observed counts,
 under the predictive pmf) and RMSE in counts beside those of the constant-rate baseline, a Poisson at the training mean.
+
+`--likelihood studentt --df 4` trains a robust regression (SVGP or TGP) with Student-t noise around G(f) on any regression
+data set; synthetic_outliers has gross errors in a tenth of its training targets and a clean test split:
+
+    python -m tgp.pytorch_amd.main --model SVGP --likelihood studentt --df 4 --dataset synthetic_outliers \\
+        --train_test_seed_split 1 --num_inducing 50 --epochs 500
 """
 import argparse
 
@@ -35,7 +41,8 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson,
+from .lib import STUDENT_MAX_DF
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson, StudentT,
                           WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
@@ -52,6 +59,7 @@ HYPER = {
     ("TGP", "banknote"): dict(arch="BCL_AL", blocks=5, steps=None),
     ("TGP", "blobs"): dict(arch="SAL", blocks=2, steps=None),
     ("TGP", "counts"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
@@ -64,7 +72,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
     ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
-                    choices=["boston", "power", "synthetic_boston", "synthetic_power"] + list(CLASSIFICATION_DATASETS)
+                    choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers"] + list(CLASSIFICATION_DATASETS)
                     + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
@@ -74,12 +82,15 @@ def main(argv=None):
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson"], default="gaussian",
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "studentt"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
-                         "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate")
+                         "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; studentt: "
+                         "robust regression, Student-t noise of --df degrees of freedom around G(f)")
+    ap.add_argument("--df", type=float, default=4.0,
+                    help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
                     help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
-                         "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli or poisson)")
+                         "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli, poisson or studentt)")
     ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
                     help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
                          "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
@@ -99,6 +110,11 @@ def main(argv=None):
         ap.error("--likelihood poisson: SVGP or TGP only")
     if pois != (args.dataset in COUNT_DATASETS):
         ap.error("--likelihood poisson goes with the count data sets (%s)" % ", ".join(COUNT_DATASETS))
+    stud = args.likelihood == "studentt"
+    if stud and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood studentt: SVGP or TGP only")
+    if stud and not (2.0 < args.df <= STUDENT_MAX_DF):
+        ap.error("--df: the Student-t degrees of freedom must be in (2, 1e4], got %g" % args.df)
     if bern and args.model == "ID_TGP":
         ap.error("--likelihood bernoulli: SVGP or TGP only")
     if bern != (args.dataset in CLASSIFICATION_DATASETS):
@@ -115,7 +131,7 @@ def main(argv=None):
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
         ap.error("--model WGP: no flow recipe for this data set, give --flow_arch / --num_blocks")
     if args.mean != "zero" and (wgp or multi or args.model == "ID_TGP"):
-        ap.error("--mean %s: SVGP or TGP with the gaussian, bernoulli or poisson likelihood only" % args.mean)
+        ap.error("--mean %s: SVGP or TGP with the gaussian, bernoulli, poisson or studentt likelihood only" % args.mean)
     if args.qu == "optimal" and (args.model not in ("SVGP", "WGP") or args.likelihood != "gaussian" or not args.whiten):
         ap.error("--qu optimal: SVGP or WGP with the gaussian likelihood and --whiten 1 (the likelihood must be Gaussian in f)")
     if args.init_Z == "greedy" and args.likelihood == "multiclass":
@@ -167,6 +183,8 @@ def main(argv=None):
         lik = Bernoulli()
     elif pois:
         lik = Poisson()
+    elif stud:
+        lik = StudentT(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points, df=args.df)
     elif wgp:
         lik = WarpedGaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, flow=flow_specs,
                                        quad_points=cg.quad_points)

@@ -25,7 +25,7 @@ from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
 from .means import MEAN_NAMES, ZeroMean, return_mean, return_projection_matrix
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson,
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson, StudentT,
                           WarpedGaussianLinearMean)
 from .utils import positive_transform
 
@@ -59,6 +59,8 @@ class sparse_MF_SP(nn.Module):
                  be_fully_bayesian: bool = False, init_params: dict = {}) -> None:
         super().__init__()
         assert len(model_specs) == 2, "Parameter model_specs should be len 2: mean name and kernel instance"
+        if isinstance(likelihood, StudentT) and int(num_outputs) != 1:
+            raise NotImplementedError("the Student-t likelihood is built for one output (num_outputs = 1)")
         # C outputs only as the C latent GPs of the multi-class likelihood (composed step)
         assert int(num_outputs) == 1 or (isinstance(likelihood, MulticlassCategorical) and int(num_outputs) == likelihood.C), \
             "this build implements the single-output path (Dy = 1, every BASELINE config)"
@@ -81,7 +83,7 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, StudentT, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
         if isinstance(likelihood, (Bernoulli, Poisson)):
             # the ABI's noise pointer: read by no Bernoulli or Poisson kernel, gradient 0; a buffer, so model.parameters() is the
             # reference's (Bernoulli) and holds no noise parameter (Poisson)
@@ -115,6 +117,9 @@ class sparse_MF_SP(nn.Module):
         if self._is_poisson and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
                                     for fl in getattr(g, "flow_arr", [])):
             raise NotImplementedError("the Poisson likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
+        if self._is_student and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
+                                    for fl in getattr(g, "flow_arr", [])):
+            raise NotImplementedError("the Student-t likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
         # mean function (sparse_MF_SP.py:184-206); mean_is_shared: one mean for all outputs, at Dy = 1 the same object
         name = model_specs[0]
         if name != "zero":
@@ -157,10 +162,14 @@ class sparse_MF_SP(nn.Module):
         return isinstance(self.likelihood, Poisson)
 
     @property
+    def _is_student(self):
+        return isinstance(self.likelihood, StudentT)
+
+    @property
     def _lik_id(self):
         """The `lik` of the ops calls: a lib.LIK_* for the likelihoods that are not told by the presence of a flow, else None."""
         return (ops.L.LIK_BERNOULLI if self._is_bernoulli else ops.L.LIK_POISSON if self._is_poisson else
-                ops.L.LIK_WARPED if self._is_warped else None)
+                ops.L.LIK_STUDENT if self._is_student else ops.L.LIK_WARPED if self._is_warped else None)
 
     @property
     def _is_warped(self):
@@ -377,7 +386,7 @@ class sparse_MF_SP(nn.Module):
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
-                   lik=self._lik_id,
+                   lik=self._lik_id, df=self.likelihood.df if self._is_student else None,
                    grad_Y=False)
         if self._has_mean:
             if spec is None:
@@ -417,6 +426,8 @@ class sparse_MF_SP(nn.Module):
             return "the Bernoulli likelihood is not Gaussian in f: q(u) has no closed-form optimum"
         if self._is_poisson:
             return "the Poisson likelihood is not Gaussian in f: q(u) has no closed-form optimum"
+        if self._is_student:
+            return "the Student-t likelihood is not Gaussian in f: q(u) has no closed-form optimum"
         if not isinstance(self.likelihood, GaussianLinearMean):
             if any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", [])):
                 return "input-dependent flows (ID_TGP) act on f: the likelihood is not Gaussian in f and q(u) has no closed-form optimum"
@@ -550,6 +561,20 @@ class sparse_MF_SP(nn.Module):
             # have no scale: Y_std is not used (no log Y_std is subtracted)
             lp, m1, m2 = self._poisson_predict(X3[0], Y.reshape(-1), want_moments=return_moments)
             return lp.sum().reshape(1), ([m1.reshape(1, MB), m2.reshape(1, MB)] if return_moments else None)
+        if self._is_student:
+            # sum_n log p(y_n | x_n), the exact log predictive density of the raw targets (every constant, -log Y_std), with
+            # [m1, m2] from the same tgp_predict_f64 launch
+            self._eval_mode()
+            with torch.no_grad():
+                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=False)
+                spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False)
+                m1, m2, lp = ops.predict(mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous(),
+                                         self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous(), spec,
+                                         theta.detach() if theta is not None else None, self.quad_points, rowp,
+                                         Y=Y.reshape(-1).to(mean_q_f.dtype), Y_std=float(Y_std.reshape(-1)[0]),
+                                         lik=ops.L.LIK_STUDENT, df=self.likelihood.df, want_moments=return_moments)
+            self.train()
+            return lp.sum().reshape(1), ([m1.reshape(1, MB), m2.reshape(1, MB)] if return_moments else None)
         predictive_params = None
         if return_moments:
             m1, m2, mean_q_f, cov_q_f = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
@@ -641,6 +666,10 @@ class sparse_MF_SP(nn.Module):
         if self._is_poisson and what != "posterior_quantiles":
             raise NotImplementedError("%s: the predictive of a Poisson model is discrete; predictive_pmf(X, kmax) gives its pmf "
                                       "(cumsum: the CDF) and posterior_quantiles the quantiles of the log-rate" % what)
+        if self._is_student and what != "posterior_quantiles":
+            raise NotImplementedError("%s: the CDF of a Student-t predictive needs the incomplete beta function, which is not "
+                                      "built; use the sampled intervals (sample_from_predictive_distribution), or "
+                                      "posterior_quantiles for the quantiles of G(f)" % what)
         if self.fully_bayesian:
             raise NotImplementedError("%s: the fully Bayesian model (an MC-dropout mixture over parameter draws) is out of "
                                       "scope; use the sampled intervals" % what)

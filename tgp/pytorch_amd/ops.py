@@ -149,15 +149,38 @@ def _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, fl
     return md, keep
 
 
+def student_noise(lvn, df):
+    """The two doubles {log sigma^2, nu} a TGP_LIK_STUDENT call's log_var_noise points to, as one float64 tensor on lvn's device:
+    `lvn` the one-element log squared scale, `df` the degrees of freedom (a number or a one-element tensor).  ValueError
+    outside the supported range 2 < nu <= lib.STUDENT_MAX_DF when `df` is a number (a tensor is not read back)."""
+    if df is None:
+        raise L.TgpError("the Student-t likelihood needs its degrees of freedom (df)")
+    if not torch.is_tensor(df):
+        check_student_df(df)
+        df = torch.tensor([float(df)], dtype=torch.float64, device=lvn.device)
+    return torch.cat((lvn.detach().reshape(-1)[:1].to(torch.float64), df.detach().reshape(-1)[:1].to(lvn.device, torch.float64)))
+
+
+def check_student_df(df):
+    """ValueError unless 2 < df <= lib.STUDENT_MAX_DF: below, the Student-t has no variance; above, its constant's two lgamma
+    cancel to ~1e-9 and the Gaussian likelihood is the one to take."""
+    df = float(df)
+    if not (2.0 < df <= L.STUDENT_MAX_DF):
+        raise ValueError("Student-t degrees of freedom must be in (2, %g], got %g" % (L.STUDENT_MAX_DF, df))
+    return df
+
+
 def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=None, rowp=None, S=None, jitter=0.0,
-              kl_scale=1.0, mb_global=None, want_moments=False, kernel="scale_rbf", plan=0, lik=None):
+              kl_scale=1.0, mb_global=None, want_moments=False, kernel="scale_rbf", plan=0, lik=None, df=None):
     """One fused ELBO evaluation + all gradients on the GPU.  Returns (out[4], grads dict, status[8], (mu, v)); status[0..2] are the
     Cholesky words of include/tgp_hip.h, status[4..7] the in-launch hand-off words (zero before and after every call).
 
     out = [ELL_shard - KL, ELL_shard, KL, 0]; grads are d(ELL_shard - kl_scale*KL)/d(param).
     `mb_global` = global minibatch size when X is a row shard (defaults to X.shape[0]).
     `lik` = lib.LIK_BERNOULLI: probit likelihood through `flow` (a FlowSpec, possibly empty); lvn is read by no kernel and
-    its gradient is 0.  `lik` = lib.LIK_POISSON: counts Y with the flow as the log-rate, the same conventions."""
+    its gradient is 0.  `lik` = lib.LIK_POISSON: counts Y with the flow as the log-rate, the same conventions.
+    `lik` = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom around the flow; lvn (one element) is the log of the
+    squared scale and grads["lvn"] its one-element gradient; `df` has none."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -167,10 +190,14 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     N, D = X.shape
     M = m.numel()
     scale = float(N_total) / float(mb_global if mb_global is not None else N)
-    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON) and flow is None:
+    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON, L.LIK_STUDENT) and flow is None:
         raise L.TgpError("the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
-                         % ("Bernoulli" if lik == L.LIK_BERNOULLI else "Poisson"))
-    md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
+                         % {L.LIK_BERNOULLI: "Bernoulli", L.LIK_POISSON: "Poisson", L.LIK_STUDENT: "Student-t"}[lik])
+    # (LIK_STUDENT: the library reads {log sigma^2, nu} behind the noise pointer and writes one gradient, that of log sigma^2)
+    if lik == L.LIK_STUDENT and lvn.numel() != 1:
+        raise L.TgpError("the Student-t step takes a one-element log_var_noise (log sigma^2); the degrees of freedom go in `df`")
+    noise = student_noise(lvn, df) if lik == L.LIK_STUDENT else lvn
+    md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, noise, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
     ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     status = _status(dev)
@@ -280,8 +307,11 @@ _STEP_PARAMS = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "rowp")
 
 def _step_kwargs(cfg):
     """The keyword arguments of elbo_step a model's `cfg` dict stands for."""
-    return dict(flow=cfg.get("flow"), S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
-                kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"), jitter=cfg.get("jitter", 0.0))
+    kw = dict(flow=cfg.get("flow"), S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
+              kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"), jitter=cfg.get("jitter", 0.0))
+    if cfg.get("df") is not None:       # the degrees of freedom of a Student-t model
+        kw["df"] = cfg["df"]
+    return kw
 
 
 def _step_save(ctx, grads, params, g_Y=None):
@@ -1051,6 +1081,34 @@ EllBernoulliFunction = _EllOf(L.LIK_BERNOULLI)
 EllPoissonFunction = _EllOf(L.LIK_POISSON)
 
 
+def ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp=None, scale=1.0):
+    """Student-t quadrature ELL with gradients: scale sum_n E_q(f0)[log StudentT(y_n | df, loc = G(f0), scale = sigma)], lvn =
+    log sigma^2 (tgp_ell_flow_f64 with TGP_LIK_STUDENT).  Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp); g_lvn =
+    dELL/dlvn, `df` has no gradient."""
+    return _ell_quad(Y, mu, v, student_noise(lvn, df), flow, theta, S, rowp, scale, L.LIK_STUDENT)
+
+
+class EllStudentFunction(torch.autograd.Function):
+    """ELL of the Student-t likelihood with autograd in (mu, v, log_var_noise, theta, rowp) and none in `df`."""
+
+    @staticmethod
+    def forward(ctx, Y, mu, v, lvn, df, theta, rowp, flow, S):
+        res = ell_student(Y, mu.detach(), v.detach(), lvn.detach(), df, flow, theta.detach() if theta is not None else None, S,
+                          rowp.detach() if rowp is not None else None)
+        ctx.save_for_backward(res["g_lvn"], res["g_mu"], res["g_v"], res["g_theta"],
+                              res["g_rowp"] if res["g_rowp"] is not None else res["g_lvn"])
+        ctx.has = (theta is not None, rowp is not None)
+        ctx.lvn_shape = lvn.shape
+        return res["ell"].reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        g_lvn, gmu, gv, gth, grp = ctx.saved_tensors
+        g = g.reshape(())
+        return (None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), None, g * gth if ctx.has[0] else None,
+                g * grp if ctx.has[1] else None, None, None)
+
+
 class EllGaussFunction(torch.autograd.Function):
     """ELL = GaussianLinearMean.expected_log_prob (likelihoods/GaussianLinearMean.py:60-87) with autograd in (mu, v,
     log_var_noise) -- the reference's method is plain torch code, differentiable wherever it is called; tgp_ell_gauss_f64
@@ -1287,11 +1345,18 @@ def flow_logdet(f, flow, theta, rowp=None, want_G=False):
     return out[0], G
 
 
-def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None, want_moments=True):
+def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, lik=None, want_moments=True, df=None):
     """Predictive moments m1, m2 and per-row test log-likelihood kernel (see tgp_predict_f64).  lik = lib.LIK_BERNOULLI:
     m1 = P(y = 1), m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (`flow` a FlowSpec, possibly empty).
-    lik = lib.LIK_POISSON: m1 = E[y], m2 = Var[y] in counts, logp = the log predictive pmf at Y (finite however small)."""
+    lik = lib.LIK_POISSON: m1 = E[y], m2 = Var[y] in counts, logp = the log predictive pmf at Y (finite however small).
+    lik = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom and squared scale exp(lvn): m1, m2 in standardised units
+    (m2 includes sigma^2 df / (df - 2)), logp = the exact log predictive density of the raw target, every constant and
+    -log Y_std included."""
     lib = L.load()
+    if lik == L.LIK_STUDENT:
+        if flow is None:
+            raise L.TgpError("the Student-t likelihood needs a FlowSpec (an empty one for the identity flow)")
+        lvn = student_noise(lvn, df)
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     dev, N = mu.device, mu.numel()

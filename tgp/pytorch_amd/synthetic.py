@@ -93,6 +93,32 @@ def counts_dataset(seed=0):
     return X, Y.astype(np.float64).reshape(-1, 1)
 
 
+# robust-regression stand-in: (rows, inputs, training rows)
+OUTLIERS_SHAPE = (1000, 2, 900)
+OUTLIERS_SHARE = 0.1
+
+
+def outliers_dataset(seed=0):
+    """Seeded `synthetic_outliers`: X ~ N(0, 1), y = sin(2 x0) + 0.5 x1 + 0.1 eps, a smooth regression problem with Gaussian
+    noise.  Returns numpy float64 X (n, d) and the CLEAN targets Y (n, 1); `gross_errors` corrupts a training split."""
+    n, d, _ = OUTLIERS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    Y = np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1] + 0.1 * rng.standard_normal(n)
+    return X, Y.reshape(-1, 1)
+
+
+def gross_errors(Y, seed=0, share=OUTLIERS_SHARE):
+    """A copy of the targets Y (n, 1) with round(share n) seeded rows replaced by gross errors: +-(5 to 15), either sign, against
+    clean targets of standard deviation ~0.9.  Returns (Y_dirty, the replaced rows' indices, sorted)."""
+    rng = np.random.default_rng(seed + 7919)
+    n = Y.shape[0]
+    idx = np.sort(rng.choice(n, size=int(round(share * n)), replace=False))
+    out = Y.copy()
+    out[idx, 0] = rng.choice([-1.0, 1.0], size=idx.size) * rng.uniform(5.0, 15.0, size=idx.size)
+    return out, idx
+
+
 # multi-class stand-in: (rows, inputs, classes)
 BLOBS_SHAPE = (1200, 4, 4)
 

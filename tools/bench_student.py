@@ -1,0 +1,130 @@
+"""Step time of the eager Student-t training step (ops.elbo_step, lik = LIK_STUDENT, df = 4, SAL x 1) on the Power shape
+(N = 8611, D = 4, M = 100, S = 32) against the eager TGP_LIK_FLOW step on the same chain and the same targets.  A Student-t step
+takes the general-M path at every M; the Gaussian step of this shape would take the fused row kernels, and tgp_model.plan has no
+bit that sends it elsewhere, so both are timed with the Matern-3/2 kernel, which runs on the general-M path for every
+likelihood -- the two steps then differ in the likelihood kernel alone (k_ell_quad<EllStudent> against k_ell_quad<EllGauss>, at
+the same lanes per row and nodes in flight: ell_plan does not look at the likelihood).  The steps are timed in ALTERNATING blocks in
+one process on one device (HIP events around each block; the warm-up / steps convention of bench.py, which this script does not
+touch).  `--trace` additionally runs a few steps of each likelihood in a fresh child process under `rocprofv3 --kernel-trace
+--stats` and reports the mean times of the two k_ell_quad instantiations.  Prints one JSON line; not a bench.py workload, and no
+threshold is attached to its numbers.
+
+    python tools/bench_student.py --steps 200 --warmup 20 --blocks 5 --trace > profiles/student_step.txt
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch                                    # noqa: E402
+
+from oracle import tgp_oracle as orc            # noqa: E402
+
+DEV = "cuda:0"
+DF = 4.0
+KERNELS = {"EllStudent": "k_ell_quad_student", "EllGauss": "k_ell_quad_gauss"}
+
+
+def stepper(prob, lik, kernel):
+    """A closure running one eager step of `lik` ("student" / "flow") with everything resident on the device."""
+    from tgp.pytorch_amd import lib as L
+    from tgp.pytorch_amd import ops
+    p = {k: v.to(DEV) for k, v in prob["params"].items()}
+    X, Y = prob["X"].to(DEV), prob["Y"].to(DEV)
+    flow = ops.FlowSpec(prob["program"], p["theta"].numel(), 0, DEV)
+    # (the two doubles {log sigma^2, nu} are joined per step, as the eager path of a model does)
+    extra = dict(lik=L.LIK_STUDENT, df=torch.tensor([DF], dtype=torch.float64, device=DEV)) if lik == "student" else {}
+
+    def step():
+        return ops.elbo_step(X, Y, p["Z"], p["raw_lengthscale"], p["raw_outputscale"], p["m"], p["Lam"], p["log_var_noise"],
+                             prob["N_total"], flow=flow, theta=p["theta"], S=32, kernel=kernel, **extra)
+    return step
+
+
+def block(step, steps):
+    """microseconds per step over `steps` eager steps"""
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        step()
+    t1.record()
+    torch.cuda.synchronize()
+    return 1e3 * t0.elapsed_time(t1) / steps
+
+
+def kernel_trace(steps):
+    """{instantiation: calls, mean microseconds} of k_ell_quad from a child process under rocprofv3 (the program goes after `--`)."""
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "student", "--", sys.executable,
+               os.path.abspath(__file__), "--eager-steps", str(steps)]
+        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, timeout=600)
+        for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+            with open(path) as fh:
+                for row in csv.DictReader(fh):
+                    name = row.get("Name", "")
+                    for key, label in KERNELS.items():
+                        if "k_ell_quad" in name and key in name:      # (every (lanes per row, nodes in flight) instantiation)
+                            acc = out.setdefault(label, {"calls": 0, "total_us": 0.0, "names": []})
+                            acc["calls"] += int(row["Calls"])
+                            acc["total_us"] += int(row["Calls"]) * float(row["AverageNs"]) / 1e3
+                            acc["names"].append(name.split("(")[0])
+    for acc in out.values():
+        acc["mean_us"] = acc.pop("total_us") / acc["calls"]
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200, help="steps per timed block")
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--blocks", type=int, default=5, help="alternating timed blocks per step")
+    ap.add_argument("--trace", action="store_true", help="add the kernel-trace times of k_ell_quad<EllStudent / EllGauss> (child process)")
+    ap.add_argument("--eager-steps", type=int, default=0, help="(the traced child) run this many steps of each likelihood")
+    args = ap.parse_args(argv)
+    prob = orc.synthetic_problem(8611, 4, 100, seed=0, flow="sal1", S=32)
+    steppers = {"student_matern32": stepper(prob, "student", "scale_matern32"),
+                "flow_matern32": stepper(prob, "flow", "scale_matern32"),
+                "student_rbf": stepper(prob, "student", "scale_rbf")}
+    if args.eager_steps:
+        for key in ("student_matern32", "flow_matern32"):
+            for _ in range(args.eager_steps):
+                out, _, status, _ = steppers[key]()
+            torch.cuda.synchronize()
+            assert int(status[0]) == 0 and bool(torch.isfinite(out[0]))
+        return
+    last = {}
+    for k, step in steppers.items():
+        for _ in range(args.warmup):
+            last[k] = step()
+    torch.cuda.synchronize()
+    times = {k: [] for k in steppers}
+    for _ in range(args.blocks):
+        for k, step in steppers.items():
+            times[k].append(block(step, args.steps))
+    res = {"workload": "eager_step_power_sal1", "df": DF, "steps": args.steps, "warmup": args.warmup, "blocks": args.blocks,
+           "device": torch.cuda.get_device_name(0)}
+    for k, ts in times.items():
+        out, _, status, _ = last[k]
+        assert int(status[0]) == 0 and int(status[1]) == 0
+        res[k + "_us_per_step_median"] = sorted(ts)[len(ts) // 2]
+        res[k + "_us_per_step_blocks"] = ts
+        res[k + "_elbo"] = float(out[0])
+    res["student_over_flow"] = res["student_matern32_us_per_step_median"] / res["flow_matern32_us_per_step_median"]
+    if args.trace:
+        tr = kernel_trace(10)
+        res["kernel_trace"] = tr
+        if len(tr) == 2:
+            res["k_ell_quad_student_over_gauss"] = tr["k_ell_quad_student"]["mean_us"] / tr["k_ell_quad_gauss"]["mean_us"]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
