@@ -141,6 +141,13 @@ extern "C" {
  * predictive density of the raw target WITH every constant, formed as a log-sum-exp.  The empty program runs the same sum.
  * The quantile and CDF entries refuse it (TGP_E_UNSUPPORTED): the CDF needs the incomplete beta function. */
 #define TGP_LIK_STUDENT 7
+/* Heteroscedastic Gaussian noise around the flow, y ~ N(G(f), exp(c + h)): f is latent GP 0 (through the flow), h latent GP 1 (no
+ * flow), c = log_var_noise[0] the prior mean of the log-variance.  A documented constant only, like TGP_LIK_SOFTMAX: every
+ * single-output entry (tgp_elbo_step_f64 and its phases / Adam variants, tgp_optimal_qu_f64, tgp_ell_flow_f64, tgp_predict_f64,
+ * tgp_predict_quantile_f64, tgp_predict_cdf_f64) returns TGP_E_UNSUPPORTED for it and tgp_last_error() names the entries to use:
+ * tgp_ell_hetero_f64, composed with tgp_qf_moments_f64 / tgp_qf_moments_bwd_f64 / tgp_kl_whitened_f64 per latent GP, and
+ * tgp_predict_hetero_f64. */
+#define TGP_LIK_HETERO 8
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -503,6 +510,19 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Heteroscedastic Gaussian expected log-likelihood (TGP_LIK_HETERO).  mu, v, mu_bar, v_bar are (2,N): row 0 belongs to f,
+ * q(f_n) = N(mu1, v1), row 1 to the log-noise GP, q(h_n) = N(mu2, v2), independent.  h integrates out in closed form; with
+ * c = log_var_noise[0], a_n = c + mu2_n, p_n = exp(-a_n + v2_n / 2) and A_n = sum_s wn_s (y_n - G(mu1_n + sqrt(2 v1_n) xs_s))^2:
+ *   out[0] = scale sum_n (-log(2 pi) / 2 - a_n / 2 - p_n A_n / 2)        (the constant: tgp_ell_flow_f64's)
+ *   out[1] = d out[0] / d c = sum_n mu_bar[1][n];   mu_bar[1][n] = scale (-1/2 + p_n A_n / 2),   v_bar[1][n] = -scale p_n A_n / 4;
+ *   mu_bar[0], v_bar[0], g_theta, g_rowp: those of tgp_ell_flow_f64 with exp(-log_var_noise) replaced by the row's p_n.
+ * Every output pointer is optional.  v1 <= 0 and v2 <= 0 count as 0 and their adjoint is written as 0; p_n is not clamped.
+ * Model fields: those tgp_ell_flow_f64 reads (model->lik is ignored); workspace: tgp_ell_workspace_bytes(N, P, RP).  Fixed
+ * summation order, no float atomics: same input, same bits. */
+int tgp_ell_hetero_f64(const tgp_model* model, const double* Y, const double* mu /* (2,N) */, const double* v /* (2,N) */,
+                       const double* rowp, double* out, double* mu_bar /* (2,N) */, double* v_bar /* (2,N) */, double* g_theta,
+                       double* g_rowp, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Flow evaluation G(f), dG/df, log dG/df for f of shape (S,N) (row n uses rowp[n,:]):
  * CompositeFlow.forward (models/flow.py:155-158) and Flow.forward_grad (:101-104); serves prediction and the
  * WGP-style log-Jacobian (likelihoods/WarpedGaussianLinearMean.py:65-85).  Any output may be NULL. */
@@ -584,6 +604,18 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
  * predictive density WITH its constant (float32 pi as everywhere); rowp is ignored. */
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream);
+
+/* The heteroscedastic predictive (TGP_LIK_HETERO) from the moments of both latent GPs, mu, v of shape (2,N) as for
+ * tgp_ell_hetero_f64, in the standardised units of tgp_predict_f64; g_s = G(mu1 + sqrt(2 v1) xs_s), a = log_var_noise[0] + mu2,
+ * variances <= 0 count as 0:
+ *   m1 = sum_s wn_s g_s,   m2 = sum_s wn_s g_s^2 - m1^2 + exp(a + v2 / 2)    (the empty program: mu1 and v1 + exp(a + v2 / 2)),
+ *   logp = log sum_s sum_t wn_s wn_t N(y | g_s, exp(a + sqrt(2 v2) xs_t)) - log Y_std,
+ * the exact log density of the raw target under the S x S product rule WITH its constant (double-precision pi), formed as a
+ * max-subtracted log-sum-exp: finite for a residual of 1e8 noise standard deviations.  The S node values of a row are computed
+ * once and kept in LDS.  m1, m2, logp are each optional; Y may be NULL (then logp is not written).  model->lik is ignored.
+ * Limit: 1 <= S <= TGP_QUANTILE_MAX_S (TGP_E_UNSUPPORTED otherwise).  Fixed summation order: same input, same bits. */
+int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */, const double* v /* (2,N) */, const double* rowp,
+                           const double* Y, double Y_std, double* m1, double* m2, double* logp, void* stream);
 
 /* Exact CDF and quantiles of the predictive distribution tgp_predict_f64 integrates (TGP_LIK_GAUSS and TGP_LIK_FLOW; model
  * fields as for tgp_predict_f64, everything in the model's standardised units):

@@ -101,6 +101,15 @@ static tgp_model gauss_copy(const tgp_model& m, int lik = TGP_LIK_GAUSS) {
   return g;
 }
 
+// TGP_LIK_HETERO has two latent GPs: every single-output entry refuses it by name (true: refused, tgp_last_error() says where to go)
+static bool refuse_hetero(const tgp_model* m, const char* entry) {
+  if (m == nullptr || m->lik != TGP_LIK_HETERO) return false;
+  set_error_text("%s: TGP_LIK_HETERO has two latent GPs and no single-output entry: use tgp_ell_hetero_f64 (composed with "
+                 "tgp_qf_moments_f64, tgp_qf_moments_bwd_f64 and tgp_kl_whitened_f64 per latent GP) and tgp_predict_hetero_f64",
+                 entry);
+  return true;
+}
+
 static int check_adam(const tgp_adam_args* a) {
   return a && a->params && a->grads && a->exp_avg && a->exp_avg_sq && a->step_dev && a->n >= 1 ? 0 : -1;
 }
@@ -273,6 +282,7 @@ static int elbo_step_impl(const tgp_model* model, const double* X, const double*
                    "tgp_qf_moments_bwd_f64 and tgp_kl_whitened_f64 per class");
     return TGP_E_UNSUPPORTED;
   }
+  if (refuse_hetero(model, "tgp_elbo_step_f64")) return TGP_E_UNSUPPORTED;
   if (model != nullptr && model->lik == TGP_LIK_WARPED)
     return elbo_step_warped(model, X, Y, out, grads, mu, v, status, workspace, workspace_bytes, phases, adam, stream);
   if (int rc = check_model(model, true)) return rc;
@@ -402,6 +412,7 @@ size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return 
 int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
                        void* workspace, size_t workspace_bytes, void* stream) {
   if (model == nullptr) return -1;
+  if (refuse_hetero(model, "tgp_optimal_qu_f64")) return TGP_E_UNSUPPORTED;   // (not Gaussian in h: no closed-form optimum)
   if (!known_kernel(model->kernel)) return -1;
   if (optimal_qu_workspace_bytes(model->N, model->D, model->M) == 0) {
     set_error_text("tgp_optimal_qu_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", model->N, model->D,
@@ -757,6 +768,7 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream) {
+  if (refuse_hetero(model, "tgp_ell_flow_f64")) return TGP_E_UNSUPPORTED;
   if (!model || model->N < 1 || model->S < 1 || !model->xs || !model->wn || !model->log_var_noise) return -1;
   if (check_flow_args(model)) return -1;
   if (!Y) return -2;
@@ -770,6 +782,32 @@ int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, 
   tgp_model md;
   if (int rc = flow_args(model, true, fp, md)) return rc;
   return launch_ell_quad(md, fp, Y, mu, v, rowp, out, g_mu, g_v, g_theta, g_rowp, static_cast<double*>(workspace),
+                         static_cast<hipStream_t>(stream));
+}
+
+int tgp_ell_hetero_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
+                       double* out, double* mu_bar, double* v_bar, double* g_theta, double* g_rowp, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (!model || model->N < 1 || model->S < 1 || !model->xs || !model->wn || !model->log_var_noise) return -1;
+  if (check_flow_args(model)) return -1;
+  if (!Y) return -2;
+  if (!mu) return -3;
+  if (!v) return -4;
+  if (model->RP > 0 && !rowp) return -5;
+  if (!workspace) return -11;
+  // the launch needs somewhere to put out[0..1]: without `out`, the two doubles past the partials (inside the sizer's slack)
+  const size_t need = lik_workspace_doubles(model->N, model->P, model->RP);
+  if (workspace_bytes < need * sizeof(double)) {
+    set_error_text("tgp_ell_hetero_f64: workspace of %zu bytes, tgp_ell_workspace_bytes gives %zu", workspace_bytes,
+                   need * sizeof(double));
+    return TGP_E_WORKSPACE;
+  }
+  FlowProg fp;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
+  md.lik = TGP_LIK_HETERO;   // (whatever the caller's model says: this entry IS the likelihood)
+  double* ws = static_cast<double*>(workspace);
+  return launch_ell_quad(md, fp, Y, mu, v, rowp, out ? out : ws + need - 2, mu_bar, v_bar, g_theta, g_rowp, ws,
                          static_cast<hipStream_t>(stream));
 }
 
@@ -908,6 +946,7 @@ int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int
 
 int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                     double Y_std, double* m1, double* m2, double* logp, void* stream) {
+  if (refuse_hetero(model, "tgp_predict_f64")) return TGP_E_UNSUPPORTED;
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
   if (model->lik == TGP_LIK_WARPED) {
     tgp_model mw = *model;
@@ -930,9 +969,27 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
   return launch_predict(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
 }
 
+int tgp_predict_hetero_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
+                           double Y_std, double* m1, double* m2, double* logp, void* stream) {
+  if (!model || model->N < 1 || !model->log_var_noise) return -1;
+  if (model->S < 1 || model->S > TGP_QUANTILE_MAX_S) {
+    set_error_text("tgp_predict_hetero_f64: S = %d outside 1..%d", model->S, TGP_QUANTILE_MAX_S);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->xs || !model->wn || check_flow_args(model, true)) return -1;
+  if (!mu) return -2;
+  if (!v) return -3;
+  if (model->RP > 0 && !rowp) return -4;
+  FlowProg fp;
+  tgp_model md;
+  if (int rc = flow_args(model, true, fp, md)) return rc;
+  return launch_predict_hetero(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
+}
+
 // the checks the two quantile entries share: likelihood, limits, the pointers the kernels read
 static int check_quantile_model(const tgp_model* model, const double* mu, const double* v, const double* rowp, const char* entry,
                                 bool* flowed) {
+  if (refuse_hetero(model, entry)) return TGP_E_UNSUPPORTED;
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
   if (model->lik == TGP_LIK_POISSON) {
     set_error_text("%s: no quantiles for TGP_LIK_POISSON: the predictive is discrete (its pmf is tgp_predict_f64's logp, one row "

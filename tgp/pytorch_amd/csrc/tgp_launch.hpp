@@ -160,7 +160,7 @@ int launch_mlp_backward(const tgp_mlp& d, const double* X, const double* W, cons
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* log_var_noise,
                      double scale, double* out, double* g_mu, double* g_v, double* ws, hipStream_t st);
 // the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, Poisson for TGP_LIK_POISSON, Student-t
-// for TGP_LIK_STUDENT, else Gaussian (TGP_LIK_FLOW)
+// for TGP_LIK_STUDENT, heteroscedastic Gaussian for TGP_LIK_HETERO (mu, v, g_mu, g_v then (2,N)), else Gaussian (TGP_LIK_FLOW)
 int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st);
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,
@@ -194,6 +194,9 @@ int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const doubl
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st);
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                        const double* Y, double* cdf, double* sf, hipStream_t st);
+// ... and the heteroscedastic predictive on the same node table: mu, v (2,N), moments and the S x S log density
+int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 
 // tgp_softmax.hip (multi-class likelihood: softmax over C latent GPs, Monte Carlo over all classes of a row)
 struct SmxArgs {                 // by-value kernel argument built from a tgp_softmax descriptor

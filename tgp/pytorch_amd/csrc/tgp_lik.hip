@@ -94,6 +94,7 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
 //   Bernoulli (likelihoods/Bernoulli.py), probit link: log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g)
 //   Poisson   (no counterpart in the reference), log link: log p(y | g) = y g - exp(g) - lgamma(y + 1)
 //   Student-t (no counterpart in the reference), location G(f0), scale sigma, nu degrees of freedom (TGP_LIK_STUDENT)
+//   heteroscedastic Gaussian (no counterpart in the reference), log noise variance c + h, h a second latent GP (TGP_LIK_HETERO)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
@@ -130,6 +131,9 @@ __device__ inline BernNode bern_node(double g, double y) {
 // kRowTerm: log p has a part that depends on y alone, row_term(y), which the kernel adds once per row instead of once per node.
 // kBlockTerm: log p has a part that is the same for every row and node, block_term(K), which the kernel adds once per
 // workgroup, times its number of rows (the weights of a row sum to 1).
+// kRowConst: the constants differ from row to row.  mu, v, g_mu, g_v are then (2,N): row 1 holds the moments of a second latent
+// GP, from which row_consts(K, mu2, v2) makes the row's own K; per node row_acc(t, w) is summed over the row's nodes into A, and
+// row_mu_bar(A, K), row_v_bar(A, K) are d log p / d mu2, d log p / d v2 of the row, written (times scale) to row 1 of g_mu, g_v.
 struct EllNoise { double eta, einv; };    // eta = log noise variance, einv = exp(-eta)
 struct EllNone {};
 struct EllGauss {
@@ -137,6 +141,7 @@ struct EllGauss {
   static constexpr bool kClampV = false;
   static constexpr bool kRowTerm = false;
   static constexpr bool kBlockTerm = false;
+  static constexpr bool kRowConst = false;
   static __device__ __forceinline__ EllNoise consts(const double* lvn) { return {lvn[0], exp(-lvn[0])}; }
   static __device__ __forceinline__ double at(double g, double y, const EllNoise&) { return y - g; }   // the residual
   static __device__ __forceinline__ double log_p(double r, const EllNoise& k) {
@@ -153,6 +158,7 @@ struct EllBern {
   static constexpr bool kClampV = true;
   static constexpr bool kRowTerm = false;
   static constexpr bool kBlockTerm = false;
+  static constexpr bool kRowConst = false;
   static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
   static __device__ __forceinline__ BernNode at(double g, double y, const EllNone&) { return bern_node(g, y); }
   static __device__ __forceinline__ double log_p(const BernNode& b, const EllNone&) { return b.lp; }
@@ -169,6 +175,7 @@ struct EllPois {
   static constexpr bool kClampV = true;   // as EllBern
   static constexpr bool kRowTerm = true;
   static constexpr bool kBlockTerm = false;
+  static constexpr bool kRowConst = false;
   static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
   static __device__ __forceinline__ PoisNode at(double g, double y, const EllNone&) { return {g, exp(g), y}; }
   static __device__ __forceinline__ double log_p(const PoisNode& t, const EllNone&) { return t.y * t.g - t.e; }
@@ -194,6 +201,7 @@ struct EllStudent {
   static constexpr bool kClampV = true;   // as EllBern
   static constexpr bool kRowTerm = false;
   static constexpr bool kBlockTerm = true;
+  static constexpr bool kRowConst = false;
   static __device__ __forceinline__ StudentConst consts(const double* lvn) {
     const double eta = lvn[0], nu = lvn[1], nus2 = nu * exp(eta);
     return {eta, nu, nu + 1.0, nus2, 1.0 / nus2};
@@ -211,6 +219,44 @@ struct EllStudent {
   }
   static __device__ __forceinline__ double block_term(const StudentConst& k) { return student_log_const(k.nu, k.eta); }
 };
+// Heteroscedastic Gaussian noise around the flow (TGP_LIK_HETERO): y ~ N(G(f), exp(c + h)), c = log_var_noise[0], h a second latent
+// GP with q(h_n) = N(mu2_n, v2_n) independent of q(f_n).  h integrates out in closed form: with a = c + mu2 and
+// p = E_q[exp(-(c + h))] = exp(-a + v2 / 2),
+//   E_q(h)[log N(y | g, e^(c+h))] = -log(2 pi) / 2 - a / 2 - p r^2 / 2,      r = y - g,
+// which is EllGauss's node term at the row's own pair (eta, einv) = (a, p): the node functions are EllGauss's.  With
+// A = sum_s w_s r_s^2:  d/dmu2 = -1/2 + p A / 2,  d/dv2 = -p A / 4,  d/dc = sum_n d/dmu2_n (partial slot 1, as the noise adjoint).
+// v2 <= 0 counts as 0 and its adjoint is 0 (as for v1); p is not clamped: the float64 formula.
+struct HeteroRow : EllNoise { bool v2pos; };
+struct EllHetero {
+  static constexpr bool kNoise = true;    // partial slot 1 carries the adjoint of c
+  static constexpr bool kClampV = true;   // as EllBern
+  static constexpr bool kRowTerm = false;
+  static constexpr bool kBlockTerm = false;
+  static constexpr bool kRowConst = true;
+  static __device__ __forceinline__ double consts(const double* lvn) { return lvn[0]; }
+  static __device__ __forceinline__ HeteroRow row_consts(double c, double mu2, double v2) {
+    const bool pos = v2 > 0.0;
+    const double a = c + mu2;
+    HeteroRow k;
+    k.eta = a; k.einv = exp(-a + (pos ? 0.5 * v2 : 0.0)); k.v2pos = pos;
+    return k;
+  }
+  static __device__ __forceinline__ double at(double g, double y, const HeteroRow&) { return y - g; }
+  static __device__ __forceinline__ double log_p(double r, const HeteroRow& k) { return EllGauss::log_p(r, k); }
+  static __device__ __forceinline__ double dlog_p_deta(double r, const HeteroRow& k) { return EllGauss::dlog_p_deta(r, k); }
+  static __device__ __forceinline__ double adjoint(double r, double scale, double w, const HeteroRow& k) {
+    return EllGauss::adjoint(r, scale, w, k);
+  }
+  static __device__ __forceinline__ double row_acc(double r, double w) { return w * r * r; }
+  static __device__ __forceinline__ double row_mu_bar(double A, const HeteroRow& k) { return -0.5 + 0.5 * k.einv * A; }
+  static __device__ __forceinline__ double row_v_bar(double A, const HeteroRow& k) { return k.v2pos ? -0.25 * k.einv * A : 0.0; }
+};
+// the constants of data row nc: the launch constants, or what the policy makes of them and the row's second pair of moments
+template <class Lik, class K0>
+__device__ __forceinline__ auto ell_row_consts(const K0& k0, const double* __restrict__ mu, const double* __restrict__ v, int N, int nc) {
+  if constexpr (Lik::kRowConst) return Lik::row_consts(k0, mu[(size_t)N + nc], v[(size_t)N + nc]);
+  else return k0;
+}
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
 // lane.  The launcher picks LPR from N so that a chunk of ~16k rows still yields ~1000 workgroups.
@@ -248,9 +294,10 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
   };
   const bool valid = n < md.N;
   const int nc = valid ? n : md.N - 1;
-  const auto K = Lik::consts(md.log_var_noise);
+  const auto K = ell_row_consts<Lik>(Lik::consts(md.log_var_noise), mu, v, md.N, nc);
   FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
   double ellp = 0.0, etap = 0.0, cm = 0.0, cv = 0.0;
+  [[maybe_unused]] double racc = 0.0;   // kRowConst: this lane's part of the row's A
   const double m_ = mu[nc], vn = Lik::kClampV ? (v[nc] > 0.0 ? v[nc] : 0.0) : v[nc];
   const double sq = sqrt(2.0 * vn), y = Y[nc];
   const double* rp = rowp ? rowp + (size_t)nc * RP : nullptr;
@@ -270,6 +317,7 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
       const auto t = Lik::at(f[u], y, K);
       ellp += wsn[u] * Lik::log_p(t, K);
       if constexpr (Lik::kNoise) etap += wsn[u] * Lik::dlog_p_deta(t, K);
+      if constexpr (Lik::kRowConst) racc += Lik::row_acc(t, wsn[u]);
       c[u] = Lik::adjoint(t, md.scale, wsn[u], K);
     }
     flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
@@ -288,6 +336,13 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
   if (valid && qn == 0) {
     if (g_mu) g_mu[n] = cm;
     if (g_v) g_v[n] = (!Lik::kClampV || vn > 0.0) ? cv / sq : 0.0;
+  }
+  if constexpr (Lik::kRowConst) {   // the adjoints of the row's second pair of moments: row 1 of the (2,N) outputs
+    const double A = group_sum(racc);
+    if (valid && qn == 0) {
+      if (g_mu) g_mu[(size_t)md.N + n] = md.scale * Lik::row_mu_bar(A, K);
+      if (g_v) g_v[(size_t)md.N + n] = md.scale * Lik::row_v_bar(A, K);
+    }
   }
   ellp = wave_sum(ellp);
   if constexpr (Lik::kNoise) etap = wave_sum(etap);
@@ -771,6 +826,8 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
                    ? ell_launch<EllPois>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                : md.lik == TGP_LIK_STUDENT
                    ? ell_launch<EllStudent>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
+               : md.lik == TGP_LIK_HETERO   // (tgp_ell_hetero_f64 only: mu, v, g_mu, g_v are (2,N))
+                   ? ell_launch<EllHetero>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                    : ell_launch<EllGauss>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp))
     return rc;
   hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);

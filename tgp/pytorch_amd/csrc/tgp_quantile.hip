@@ -4,6 +4,7 @@
 //   k_pred_cdf<X>       cdf = F_n(Y_n) and the upper tail 1 - F_n from its own sum
 //   k_pred_quantile<X>  t = the root of F_n(t) = p for Q probabilities per row, a bracketed Newton iteration on the S node values
 //   k_quantile_gauss    TGP_LIK_GAUSS / the empty program: one Gaussian, closed forms for both
+//   k_predict_hetero<X> the heteroscedastic predictive (tgp_predict_hetero_f64): moments and log density on the same node table
 // QLPR = 16 lanes share a data row (4 rows per wave, one wave per workgroup): the lanes sweep the row's S nodes -- and the Q
 // starting points G(mu + zq sqrt v) -- through the flow once (flow_forward_n, 4 elements in flight per lane) into LDS, and
 // every evaluation of F afterwards reads those S numbers only: lane l adds the nodes l, l + 16, ... in that order, the 16
@@ -202,9 +203,102 @@ __global__ __launch_bounds__(256) void k_quantile_gauss(int N, const double* __r
   if (sf) sf[n] = z < 0.0 ? big : small;
 }
 
+// Heteroscedastic Gaussian predictive (TGP_LIK_HETERO), mu, v of shape (2,N): row 0 the moments of f (through the flow), row 1
+// those of the log-noise GP h; a = log_var_noise + mu2, variances <= 0 count as 0.  Per row, in standardised units:
+//   m1 = sum_s wn_s g_s,   m2 = sum_s wn_s g_s^2 - m1^2 + exp(a + v2 / 2)     (the empty program: mu1 and v1 + exp(a + v2 / 2)),
+//   logp = log sum_s sum_t wn_s wn_t N(y | g_s, exp(a + sqrt(2 v2) xs_t)) - log Y_std,
+// the exact log density of the raw target under the S x S product rule, with its constant (double-precision pi, as Student-t).
+// The row's 16 lanes sweep the S node values into LDS once (q_sweep); lane l then takes the noise nodes t = l, l + 16, ... and
+// runs over all s for each, keeping its sum relative to its running maximum (as k_predict_pois); the 16 lanes' (maximum, sum)
+// pairs are joined under the row's maximum, so logp is finite where every term underflows (|y - g| = 1e8 sigma: terms near
+// -5e15).  Weights of 0 do not enter.  Fixed order, no atomics: same input, same bits.
+// dynamic LDS: tp, tg, then wn, log wn, xs (S rounded up to even each), then QROWS node tables of q_row_stride(S)
+template <bool X>
+__global__ __launch_bounds__(64) void k_predict_hetero(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                       const double* __restrict__ v, const double* __restrict__ rowp,
+                                                       const double* __restrict__ Y, double Y_std, int stride,
+                                                       double* __restrict__ m1o, double* __restrict__ m2o,
+                                                       double* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int lane = threadIdx.x, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S, S2 = (S + 1) / 2 * 2;
+  double* lw = wl + S2;
+  double* xl = lw + S2;
+  double* gs = xl + S2 + (size_t)r * stride;
+  for (int s = lane; s < S; s += 64) {
+    const double w = md.wn[s];
+    wl[s] = w;
+    lw[s] = w > 0.0 ? log(w) : -INFINITY;
+    xl[s] = md.xs[s];
+  }
+  flow_params_lds<X>(md.theta, fp, tp, tg);   // (ends with a barrier: the three tables are staged too)
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double m_ = mu[nc], v1 = v[nc] > 0.0 ? v[nc] : 0.0;
+  const double v2r = v[(size_t)md.N + nc], v2 = v2r > 0.0 ? v2r : 0.0;
+  const double a = md.log_var_noise[0] + mu[(size_t)md.N + nc];
+  q_sweep<X>(F, md, rp, m_, v1, nullptr, 0, l16, gs);
+  __syncthreads();
+  if (m1o || m2o) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int s0 = 0; s0 < S; s0 += QLPR) {
+      const int s = s0 + l16, sc = s < S ? s : S - 1;
+      const double w = s < S ? wl[sc] : 0.0, g = gs[sc];
+      s1 += w * g;
+      s2 += w * g * g;
+    }
+    s1 = row16_sum(s1);
+    s2 = row16_sum(s2);
+    const double noise = exp(a + 0.5 * v2);
+    if (valid && l16 == 0) {
+      if (m1o) m1o[n] = fp.nblk == 0 ? m_ : s1;
+      if (m2o) m2o[n] = fp.nblk == 0 ? v1 + noise : s2 - s1 * s1 + noise;
+    }
+  }
+  if (logp && Y) {
+    const double y = Y[nc], sq2 = sqrt(2.0 * v2);
+    double mx = -INFINITY, se = 0.0;
+    for (int t0 = 0; t0 < S; t0 += QLPR) {
+      const int t = t0 + l16;
+      if (t < S && wl[t] > 0.0) {
+        const double la = a + sq2 * xl[t], hiv = 0.5 * exp(-la);     // log variance at noise node t, 1 / (2 variance)
+        const double base = lw[t] - 0.5 * (1.8378770664093454836 + la);
+        for (int s = 0; s < S; ++s) {
+          const double rr = y - gs[s], term = base + lw[s] - hiv * rr * rr;
+          if (term > mx) { se = se * exp(mx - term) + 1.0; mx = term; }
+          else if (term > -INFINITY) se += exp(term - mx);
+        }
+      }
+    }
+    double gmx = mx;
+#pragma unroll
+    for (int o = 1; o < QLPR; o <<= 1) gmx = fmax(gmx, __shfl_xor(gmx, o));
+    const double tot = row16_sum(mx > -INFINITY ? se * exp(mx - gmx) : 0.0);
+    if (valid && l16 == 0) logp[n] = gmx + log(tot) - log(Y_std);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
+int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
+  const int stride = q_row_stride(md.S);
+  const size_t lds = (2 * (size_t)((md.P + 2) / 2 * 2) + 3 * (size_t)((md.S + 1) / 2 * 2) + (size_t)QROWS * stride) * sizeof(double);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_predict_hetero<true> : k_predict_hetero<false>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, Y_std, stride, m1, m2, logp);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 static size_t q_lds_bytes(const tgp_model& md, int Q, int* stride) {
   *stride = q_row_stride(md.S + Q);
   return (2 * (size_t)((md.P + 2) / 2 * 2) + (size_t)((md.S + 1) / 2 * 2) + (size_t)QROWS * *stride) * sizeof(double);

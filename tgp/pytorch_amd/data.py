@@ -175,12 +175,20 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     base = dataset_name.replace("synthetic_", "")
     if synth and (base in BINARY_SHAPES or base in ("blobs", "counts")):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
-    if (synth and base not in SHAPES and base != "outliers") or (not synth and base not in UCI):
+    if (synth and base not in SHAPES and base not in ("outliers", "hetero")) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
-    outlier_idx = None
-    if synth and base == "outliers":
+    outlier_idx = noise_std = None
+    if synth and base == "hetero":
+        # synthetic_hetero (synthetic.hetero_dataset): the noise level depends on the inputs; the rows' true sigma travels along
+        from .synthetic import HETERO_SHAPE, hetero_dataset
+        n, d, n_tr = HETERO_SHAPE
+        X, Y, noise_std = hetero_dataset(0 if seed is None else int(seed))
+        perm = numpy.random.default_rng(seed).permutation(n)
+        tr_idx, te_idx = perm[:n_tr], perm[n_tr:]
+        X_tr, Y_tr, X_te, Y_te = X[tr_idx], Y[tr_idx], X[te_idx], Y[te_idx]
+    elif synth and base == "outliers":
         # synthetic_outliers (synthetic.outliers_dataset): 10 % of the TRAINING targets are gross errors, the test split is clean
         from .synthetic import OUTLIERS_SHAPE, gross_errors, outliers_dataset
         n, d, n_tr = OUTLIERS_SHAPE
@@ -216,4 +224,6 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
                    "train_idx": numpy.asarray(tr_idx), "test_idx": numpy.asarray(te_idx)}
     if outlier_idx is not None and use_validation is None:
         data_config["outlier_idx"] = outlier_idx        # rows of the training split that hold a gross error
+    if noise_std is not None and use_validation is None:
+        data_config["noise_std_te"] = t(noise_std[te_idx])      # the test rows' true noise standard deviation, raw units
     return loaders, data_config

@@ -38,7 +38,7 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
     """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
     combination, else the message both refuse it with (_refuse) before they load the library or touch the device; the
     trainers take the eager loop on a message.  A pure function of the description: `mean` = None / "linear" / "identity",
-    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "studentt" / "multiclass", `collective` as passed to the engine (asking
+    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "studentt" / "multiclass" / "hetero", `collective` as passed to the engine (asking
     for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`)."""
     multi_rank = int(world_size) > 1 or collective is not None
     if not is_whiten:      # `params` of an unwhitened model describe q(u) itself; the captured step has no transform in it
@@ -51,6 +51,9 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
         return "the step engines have no Student-t likelihood: it trains on the eager path (ops.ElboFunction)"
     if likelihood == "multiclass":
         return "the step engines have no multi-class likelihood: its C latent GPs train on the eager path's composed step"
+    if likelihood == "hetero":
+        return ("the step engines have no heteroscedastic likelihood: its two latent GPs train on the eager path's composed "
+                "step, on one rank")
     if mean is not None:
         if minibatch:
             return "the '%s' mean function has no minibatch engine: full batch on one rank (ElboEngine), or the eager loop" % mean

@@ -20,7 +20,8 @@ LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)
 LIK_SOFTMAX = 5             # softmax over C latent GPs (TGP_LIK_SOFTMAX): the stand-alone tgp_ell_softmax_f64 only
 LIK_POISSON = 6             # counts, the flow as the log-rate (TGP_LIK_POISSON)
 LIK_STUDENT = 7             # Student-t noise around the flow (TGP_LIK_STUDENT): log_var_noise = {log sigma^2, nu}
-STUDENT_MAX_DF = 1e4        # the supported degrees of freedom are 2 < nu <= STUDENT_MAX_DF (include/tgp_hip.h)
+LIK_HETERO = 8              # heteroscedastic Gaussian, a second latent GP for the log-noise (TGP_LIK_HETERO): tgp_ell_hetero_f64 only
+STUDENT_MAX_DF = 1e4       # the supported degrees of freedom are 2 < nu <= STUDENT_MAX_DF (include/tgp_hip.h)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
 PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64
@@ -144,6 +145,9 @@ _SIGS = {
     "tgp_ell_gauss_f64": (C.c_int, [_dp, _dp, _dp, C.c_int32, _dp, C.c_double, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_ell_flow_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t,
                                    _dp]),
+    "tgp_ell_hetero_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t,
+                                     _dp]),
+    "tgp_predict_hetero_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     "tgp_flow_eval_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     "tgp_flow_logdet_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_flow_logdet_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),

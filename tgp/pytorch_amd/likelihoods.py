@@ -261,6 +261,62 @@ class StudentT(_GaussianBase):
         return m1.reshape(gauss_mean.shape), m2.reshape(gauss_mean.shape)
 
 
+class HeteroscedasticGaussian(nn.Module):
+    """p(y | f, h) = N(y | G(f), exp(c + h)) for regression with input-dependent noise: f is latent GP 0 (with the model's
+    flow), h latent GP 1 (no flow) and c = `log_var_noise`, the one parameter: the prior mean of the log noise variance,
+    initialised at log `noise_init`.  The moments arrive as (2, MB): row 0 those of q(f), row 1 those of q(h).  h integrates out
+    of the expected log-likelihood in closed form (tgp_ell_hetero_f64); the predictive density is an S x S product rule
+    (tgp_predict_hetero_f64); DESIGN.md 8.  The reference has no such class."""
+
+    def __init__(self, noise_init, quadrature_points):
+        super().__init__()
+        self.out_dim = 2
+        self.quad_points = quadrature_points
+        self.log_var_noise = nn.Parameter(torch.ones(1, 1, dtype=cg.dtype) *
+                                          inverse_positive_transform(torch.tensor(noise_init, dtype=cg.dtype)))
+
+    def _flow_inputs(self, flow, X, dev, with_grad=False):
+        return GaussianNonLinearMean._flow_inputs(self, flow, X, dev, with_grad)
+
+    def _checks(self, gauss_mean, gauss_cov, flow):
+        assert gauss_mean.dim() == 2 and gauss_mean.size(0) == 2 and gauss_cov.shape == gauss_mean.shape, \
+            "the heteroscedastic likelihood takes the moments of two latent GPs, shape (2, MB)"
+        assert len(flow) >= 1, "Flow list must hold the flow of f (output 0)"
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, scale=1.0, **kwargs):
+        """scale sum_n E_q(f) q(h)[log N(y_n | G(f), exp(c + h))], differentiable in both pairs of moments, c and the flow's
+        parameters; Y (1, MB), moments (2, MB)."""
+        self._checks(gauss_mean, gauss_cov, flow)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllHeteroFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.contiguous(), gauss_cov.contiguous(),
+                                           self.log_var_noise.reshape(-1)[:1].contiguous(), theta, rowp, spec, self.quad_points,
+                                           float(scale))
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, Y=None, Y_std=1.0, **kwargs):
+        """(m1, m2) = mean and variance of the predictive in standardised units, each (1, MB); m2 holds the mean noise variance
+        exp(c + mu_h + v_h / 2).  With Y also the per-row exact log predictive density (MB,) as a third value, same launch."""
+        self._checks(gauss_mean, gauss_cov, flow)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device)
+        m1, m2, lp = ops.predict_hetero(gauss_mean.detach().contiguous(), gauss_cov.detach().contiguous(),
+                                        self.log_var_noise.detach().reshape(-1)[:1].contiguous(), spec, theta, self.quad_points,
+                                        rowp, Y=Y, Y_std=Y_std)
+        m1, m2 = m1.reshape(1, -1), m2.reshape(1, -1)
+        return (m1, m2) if Y is None else (m1, m2, lp)
+
+    def noise_std(self, gauss_mean_h, gauss_cov_h, probs):
+        """Quantiles of the noise standard deviation exp((c + h) / 2) under q(h) = N(mean, cov), closed form (h -> exp is
+        increasing): exp((c + mean + z_p sqrt(cov)) / 2), shape (Q, MB) for probs of length Q."""
+        _, zq = ops.quantile_probs(probs, gauss_mean_h.device)
+        mu, sd = gauss_mean_h.detach().reshape(1, -1), torch.sqrt(gauss_cov_h.detach().clamp_min(0.0)).reshape(1, -1)
+        return torch.exp(0.5 * (self.log_var_noise.detach().reshape(()) + mu + zq.reshape(-1, 1) * sd))
+
+    def sample_from_output(self, f, i, **kwargs):
+        """G(f) + exp((c + h) / 2) eps for f of shape (2, n): row 0 the draws of G(f), row 1 those of h."""
+        assert f.size(0) == 2, "Bad specified input"
+        sd = torch.exp(0.5 * (self.log_var_noise.detach().reshape(()) + f[1]))
+        return f[0] + sd * torch.randn_like(f[0])
+
+
 class MulticlassCategorical(nn.Module):
     """p(y|G(f)) = softmax(G_1(f_1), ..., G_C(f_C))[y] over C latent GPs (likelihoods/MulticlassCategorical.py): every integral
     is a Monte-Carlo mean over `SMC` joint draws of the C latents of a row (tgp_ell_softmax_f64 / tgp_predict_softmax_f64).

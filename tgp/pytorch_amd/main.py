@@ -29,6 +29,13 @@ data set; synthetic_outliers has gross errors in a tenth of its training targets
 
     python -m tgp.pytorch_amd.main --model SVGP --likelihood studentt --df 4 --dataset synthetic_outliers \\
         --train_test_seed_split 1 --num_inducing 50 --epochs 500
+
+`--likelihood hetero` trains a regression with input-dependent Gaussian noise (SVGP or TGP): a second latent GP models the log
+noise variance.  It reports the test negative log-likelihood and RMSE and, on synthetic_hetero (noise from 0.05 to 1.0 across
+x0), the correlation of the learned with the true log noise level:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood hetero --dataset synthetic_hetero \\
+        --train_test_seed_split 1 --num_inducing 50 --epochs 2000
 """
 import argparse
 
@@ -42,8 +49,8 @@ from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanh
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
 from .lib import STUDENT_MAX_DF
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson, StudentT,
-                          WarpedGaussianLinearMean)
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
+                          Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import GREEDY_VARIANCE, KMEANS
@@ -60,6 +67,7 @@ HYPER = {
     ("TGP", "blobs"): dict(arch="SAL", blocks=2, steps=None),
     ("TGP", "counts"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
@@ -72,7 +80,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
     ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
-                    choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers"] + list(CLASSIFICATION_DATASETS)
+                    choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero"]
+                    + list(CLASSIFICATION_DATASETS)
                     + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
@@ -82,10 +91,11 @@ def main(argv=None):
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "studentt"], default="gaussian",
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "studentt", "hetero"], default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; studentt: "
-                         "robust regression, Student-t noise of --df degrees of freedom around G(f)")
+                         "robust regression, Student-t noise of --df degrees of freedom around G(f); hetero: regression with "
+                         "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
@@ -115,6 +125,19 @@ def main(argv=None):
         ap.error("--likelihood studentt: SVGP or TGP only")
     if stud and not (2.0 < args.df <= STUDENT_MAX_DF):
         ap.error("--df: the Student-t degrees of freedom must be in (2, 1e4], got %g" % args.df)
+    het = args.likelihood == "hetero"
+    if het and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood hetero: SVGP or TGP only (no ID_TGP, no WGP)")
+    if het and (args.dataset in CLASSIFICATION_DATASETS + MULTICLASS_DATASETS + COUNT_DATASETS):
+        ap.error("--likelihood hetero goes with the regression data sets")
+    if het and args.mean != "zero":
+        ap.error("--likelihood hetero: --mean zero only (mean functions are not built for the two-GP model)")
+    if het and args.qu == "optimal":
+        ap.error("--likelihood hetero: --qu adam only (two coupled latent GPs: no closed-form optimal q(u))")
+    if het and args.coverage == "exact":
+        ap.error("--likelihood hetero: --coverage sampled only (the exact CDF of the double mixture is not built)")
+    if het and args.init_Z == "greedy":
+        ap.error("--init_Z greedy: one latent GP only (not --likelihood hetero)")
     if bern and args.model == "ID_TGP":
         ap.error("--likelihood bernoulli: SVGP or TGP only")
     if bern != (args.dataset in CLASSIFICATION_DATASETS):
@@ -183,6 +206,9 @@ def main(argv=None):
         lik = Bernoulli()
     elif pois:
         lik = Poisson()
+    elif het:
+        Dy = 2                              # latent GP 0: f (with the flow), latent GP 1: h, the log noise variance (no flow)
+        lik = HeteroscedasticGaussian(noise_init=0.05, quadrature_points=cg.quad_points)
     elif stud:
         lik = StudentT(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points, df=args.df)
     elif wgp:
@@ -205,8 +231,8 @@ def main(argv=None):
         model = sparse_MF_GP(**common)
     else:
         # (multi-class: every class builds its own flow from the same spec list)
-        model = sparse_MF_SP(flow_specs=[flow_specs] * Dy if multi else [flow_specs], flow_connection="single",
-                             be_fully_bayesian=False, **common)
+        model = sparse_MF_SP(flow_specs=[flow_specs] * Dy if multi else [flow_specs, [("identity", [])]] if het else [flow_specs],
+                             flow_connection="single", be_fully_bayesian=False, **common)
     model.to(cg.device)
 
     lr = 0.01
@@ -245,6 +271,13 @@ def main(argv=None):
     else:
         print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
             args.dataset, args.num_inducing, args.model, -res[6], res[7]))
+    if het and "noise_std_te" in dc:
+        # how well the learned noise level follows the true one: Pearson correlation of log median sigma(x*) with log sigma(x*)
+        # over the test rows (invariant to the targets' standardisation)
+        learned = torch.log(model.predictive_noise_std(dc["X_te"].to(cg.device), 0.5)[0]).cpu()
+        corr = torch.corrcoef(torch.stack((learned, torch.log(dc["noise_std_te"]))))[0, 1].item()
+        print("Dataset {}, num inducing points {}, model {}, log noise std correlation {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, corr))
     if args.model == "ID_TGP":
         model.be_fully_bayesian(True)
         res = trainer.compute_metrics()

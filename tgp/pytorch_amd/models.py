@@ -10,9 +10,10 @@ What differs is underneath: every number is produced by the HIP kernels of libtg
 blocked Cholesky, hand-derived adjoints, the MLP kernel for the input-dependent flows' networks in training AND in
 every evaluation method).  There is NO CPU fallback: calling these methods with CPU tensors
 raises (the oracle in oracle/ is the CPU restatement, and it is test infrastructure only).
-Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs), 'scale_rbf' / 'scale_matern32' kernel,
-float64.  Mean functions 'zero', 'linear' and 'identity' (means.py; a non-zero mean with the multi-class, warped and
-input-dependent models raises NotImplementedError).  Both q(u) parameterisations: with is_whiten=False the parameters (m, L_q) describe
+Restrictions of this build (asserted): one output GP (Dy = 1, all BASELINE configs; C latent GPs with MulticlassCategorical, two
+-- f and the log-noise h -- with HeteroscedasticGaussian), 'scale_rbf' / 'scale_matern32' kernel, float64.  Mean functions
+'zero', 'linear' and 'identity' (means.py; a non-zero mean with the multi-class, heteroscedastic, warped and input-dependent
+models raises NotImplementedError).  Both q(u) parameterisations: with is_whiten=False the parameters (m, L_q) describe
 q(u) = N(m, L_q L_q^T) and every method runs the whitened kernels at m_w = L^-1 m, Lam_w = L^-1 tril(L_q) (tgp_unwhiten_f64).
 """
 from typing import List
@@ -25,8 +26,8 @@ from . import config as cg
 from . import ops
 from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
 from .means import MEAN_NAMES, ZeroMean, return_mean, return_projection_matrix
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, MulticlassCategorical, Poisson, StudentT,
-                          WarpedGaussianLinearMean)
+from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
+                          Poisson, StudentT, WarpedGaussianLinearMean)
 from .utils import positive_transform
 
 DEFAULT_INIT = {"variational_distribution": {"variance_scale": 1.0, "mean_scale": 0.0}}
@@ -61,9 +62,13 @@ class sparse_MF_SP(nn.Module):
         assert len(model_specs) == 2, "Parameter model_specs should be len 2: mean name and kernel instance"
         if isinstance(likelihood, StudentT) and int(num_outputs) != 1:
             raise NotImplementedError("the Student-t likelihood is built for one output (num_outputs = 1)")
-        # C outputs only as the C latent GPs of the multi-class likelihood (composed step)
-        assert int(num_outputs) == 1 or (isinstance(likelihood, MulticlassCategorical) and int(num_outputs) == likelihood.C), \
+        # C outputs only as the C latent GPs of the multi-class likelihood, 2 only as (f, h) of the heteroscedastic one (composed
+        # step)
+        assert int(num_outputs) == 1 or (isinstance(likelihood, MulticlassCategorical) and int(num_outputs) == likelihood.C) or \
+            (isinstance(likelihood, HeteroscedasticGaussian) and int(num_outputs) == 2), \
             "this build implements the single-output path (Dy = 1, every BASELINE config)"
+        assert not isinstance(likelihood, HeteroscedasticGaussian) or int(num_outputs) == 2, \
+            "HeteroscedasticGaussian needs num_outputs = 2: latent GP 0 is f, latent GP 1 the log-noise h"
         assert not isinstance(likelihood, MulticlassCategorical) or int(num_outputs) == likelihood.C, \
             "MulticlassCategorical needs num_outputs = its number of classes"
         assert model_specs[0] in MEAN_NAMES, "mean function must be one of %s, got %r" % (", ".join(MEAN_NAMES), model_specs[0])
@@ -83,7 +88,7 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, StudentT, WarpedGaussianLinearMean, MulticlassCategorical)) else cg.quad_points
+        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, StudentT, WarpedGaussianLinearMean, MulticlassCategorical, HeteroscedasticGaussian)) else cg.quad_points
         if isinstance(likelihood, (Bernoulli, Poisson)):
             # the ABI's noise pointer: read by no Bernoulli or Poisson kernel, gradient 0; a buffer, so model.parameters() is the
             # reference's (Bernoulli) and holds no noise parameter (Poisson)
@@ -120,6 +125,14 @@ class sparse_MF_SP(nn.Module):
         if self._is_student and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
                                     for fl in getattr(g, "flow_arr", [])):
             raise NotImplementedError("the Student-t likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
+        if self._is_hetero:
+            if any(not isinstance(fl, IdentityFlow) for fl in getattr(self.G_matrix[1], "flow_arr", [self.G_matrix[1]])):
+                raise NotImplementedError("the heteroscedastic likelihood takes no flow on h, the log-noise GP: flow_specs[1] must be empty")
+            if any(getattr(fl, "input_dependent", False) for fl in getattr(self.G_matrix[0], "flow_arr", [])):
+                raise NotImplementedError("the heteroscedastic likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
+            if model_specs[0] != "zero":
+                raise NotImplementedError("the '%s' mean function is not built for the heteroscedastic likelihood: use the 'zero' mean"
+                                          % model_specs[0])
         # mean function (sparse_MF_SP.py:184-206); mean_is_shared: one mean for all outputs, at Dy = 1 the same object
         name = model_specs[0]
         if name != "zero":
@@ -178,6 +191,15 @@ class sparse_MF_SP(nn.Module):
     @property
     def _is_multiclass(self):
         return isinstance(self.likelihood, MulticlassCategorical)
+
+    @property
+    def _is_hetero(self):
+        return isinstance(self.likelihood, HeteroscedasticGaussian)
+
+    @property
+    def _is_composed(self):
+        """Several latent GPs: the step is composed per GP from the stand-alone pieces (_qf_per_class, per-GP KL)."""
+        return self._is_multiclass or self._is_hetero
 
     def _gp_params(self, c=None, jitter=0.0, ladder=None, info=None):
         """What the whitened kernels consume: (Z, raw_ls, raw_os, m, Lam, lvn).  Whitened: the parameters themselves.
@@ -245,6 +267,43 @@ class sparse_MF_SP(nn.Module):
         KLD = KLD.sum()
         return ELL - KLD, ELL, KLD
 
+    def _elbo_hetero(self, X2, Y):
+        """ELL - KL_f - KL_h composed as _elbo_multiclass: the q(f) and q(h) moments and the two KL terms from the stand-alone
+        differentiable pieces, then ONE heteroscedastic likelihood launch (tgp_ell_hetero_f64) that returns the adjoints of all
+        four moment vectors, c and the flow's parameters."""
+        mu, v = self._qf_per_class(X2)
+        KLD = self.KLD().sum()
+        ELL = self.likelihood.expected_log_prob(Y.t(), mu, v, flow=self.G_matrix, X=X2.unsqueeze(0),
+                                                scale=self.N / Y.size(0)).sum()
+        return ELL - KLD, ELL, KLD
+
+    def _hetero_predict(self, X2, Y=None, Y_std=1.0):
+        """Eval-mode q(f), q(h) moments at the rows of X2 and ONE tgp_predict_hetero_f64 launch on them:
+        (m1 (1, N), m2 (1, N), logp (N,) or None, mean_q_f (2, N, 1), cov_q_f (2, N, 1)); no autograd."""
+        self._require_gpu(X2)
+        self._eval_mode()
+        with torch.no_grad():
+            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X2, diagonal=True, is_duvenaud=False)
+            res = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X2.unsqueeze(0),
+                                                   Y=None if Y is None else Y.reshape(-1).to(mean_q_f.dtype), Y_std=Y_std)
+        self.train()
+        return res[0], res[1], (res[2] if Y is not None else None), mean_q_f, cov_q_f
+
+    def predictive_noise_std(self, X, probs):
+        """Quantiles of the noise standard deviation sqrt(exp(c + h(x))) under q(h) at the rows of X, shape (Q, N), in the
+        model's standardised units: exp((c + mu_h + z_p sqrt(v_h)) / 2), closed form.  probs 0.5: the median noise level."""
+        if not self._is_hetero:
+            raise NotImplementedError("predictive_noise_std: the heteroscedastic likelihood only; %s has one noise level"
+                                      % type(self.likelihood).__name__)
+        X2 = X[0] if X.dim() == 3 else X
+        self._require_gpu(X2)
+        self._eval_mode()
+        with torch.no_grad():
+            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X2, diagonal=True, is_duvenaud=False)
+            q = self.likelihood.noise_std(mean_q_f[1].reshape(-1), cov_q_f[1].reshape(-1), probs)
+        self.train()
+        return q
+
     def _flow_inputs(self, X2d, with_grad, samples=1):
         """(FlowSpec or None, theta, rowp): shared scalars stacked into one vector, per-row parameters from the MLPs on the
         HIP kernel (dropout follows the nets' Dropout layers, as in the reference).  `samples` > 1 (fully Bayesian
@@ -298,6 +357,9 @@ class sparse_MF_SP(nn.Module):
         gradients are enabled and a parameter requires them the call raises (diagonal=True is the differentiable path).
         MB <= 4096, single-output models only."""
         assert not is_duvenaud, "is_duvenaud=False on this path"
+        if not diagonal and self._is_hetero:
+            raise NotImplementedError("diagonal=False is not built for the heteroscedastic likelihood (HeteroscedasticGaussian: "
+                                      "two latent GPs)")
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         if not diagonal:
@@ -317,7 +379,7 @@ class sparse_MF_SP(nn.Module):
             if self._has_mean:       # mu + m(X) (sparse_MF_SP.py:355,360), in place
                 mu = self.mean_function.vector(X2.detach(), inp=mu).detach()
             return mu.reshape(1, -1, 1), cov.unsqueeze(0)
-        if self._is_multiclass:
+        if self._is_composed:
             mu, v = self._qf_per_class(X2)
             return mu.unsqueeze(2), v.unsqueeze(2)
         info = {}
@@ -350,10 +412,10 @@ class sparse_MF_SP(nn.Module):
         reference's, or with is_whiten=False the KL against N(0, K_ZZ + j I) (:433-453), differentiable in Z and the kernel
         parameters too."""
         if not self.is_whiten:
-            if self._is_multiclass:
+            if self._is_composed:
                 return torch.stack([self._kld_unwhitened(c) for c in range(self.out_dim)])
             return self._kld_unwhitened().reshape(1)
-        if self._is_multiclass:
+        if self._is_composed:
             kls = []
             for c in range(self.out_dim):
                 m, Lam = self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c]
@@ -376,6 +438,9 @@ class sparse_MF_SP(nn.Module):
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
         if self._is_multiclass:
             return self._elbo_multiclass(X2, Y)
+        if self._is_hetero:
+            assert _qu_jitter is None
+            return self._elbo_hetero(X2, Y)
         if self._is_poisson:
             self.likelihood.check_targets(Y)      # counts only (ValueError); the kernels themselves take any real >= 0
         info = {}
@@ -428,6 +493,9 @@ class sparse_MF_SP(nn.Module):
             return "the Poisson likelihood is not Gaussian in f: q(u) has no closed-form optimum"
         if self._is_student:
             return "the Student-t likelihood is not Gaussian in f: q(u) has no closed-form optimum"
+        if self._is_hetero:
+            return ("the heteroscedastic likelihood (HeteroscedasticGaussian) has two coupled latent GPs: neither q(u) has a "
+                    "closed-form optimum")
         if not isinstance(self.likelihood, GaussianLinearMean):
             if any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", [])):
                 return "input-dependent flows (ID_TGP) act on f: the likelihood is not Gaussian in f and q(u) has no closed-form optimum"
@@ -494,6 +562,11 @@ class sparse_MF_SP(nn.Module):
     def predictive_distribution(self, X, diagonal: bool = True, S_MC_NNet: int = None):
         """m1, m2 (Dy, MB) + q(f) moments (sparse_MF_SP.py:457-540)."""
         assert not self.is_training, "This method only works in eval mode"
+        if self._is_hetero:
+            if not diagonal:
+                raise NotImplementedError("diagonal=False is not built for the heteroscedastic likelihood (two latent GPs)")
+            m1, m2, _, mean_q_f, cov_q_f = self._hetero_predict(X[0] if X.dim() == 3 else X)
+            return m1, m2, mean_q_f, cov_q_f
         assert diagonal
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._eval_mode()
@@ -533,6 +606,11 @@ class sparse_MF_SP(nn.Module):
         MB = X.size(0)
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._require_gpu(X3)
+        if self._is_hetero:
+            # sum_n log p(y_n | x_n), the exact log predictive density of the raw targets under the S x S product rule (every
+            # constant, -log Y_std), with [m1, m2] from the same tgp_predict_hetero_f64 launch
+            m1, m2, lp, _, _ = self._hetero_predict(X3[0], Y, float(Y_std.reshape(-1)[0]))
+            return lp.sum().reshape(1), ([m1, m2] if return_moments else None)
         if self._is_multiclass:
             # sum_n log P[n, y_n] in float64, P and its logarithm from one tgp_predict_softmax_f64 launch (the reference goes
             # through float32 and compute_calibration_measures)
@@ -670,6 +748,11 @@ class sparse_MF_SP(nn.Module):
             raise NotImplementedError("%s: the CDF of a Student-t predictive needs the incomplete beta function, which is not "
                                       "built; use the sampled intervals (sample_from_predictive_distribution), or "
                                       "posterior_quantiles for the quantiles of G(f)" % what)
+        if self._is_hetero and what != "posterior_quantiles":
+            raise NotImplementedError("%s: the exact CDF and quantiles of the heteroscedastic likelihood's double mixture "
+                                      "(HeteroscedasticGaussian) are not built; use the sampled intervals "
+                                      "(sample_from_predictive_distribution), posterior_quantiles for G(f) or "
+                                      "predictive_noise_std for the noise level" % what)
         if self.fully_bayesian:
             raise NotImplementedError("%s: the fully Bayesian model (an MC-dropout mixture over parameter draws) is out of "
                                       "scope; use the sampled intervals" % what)
@@ -678,6 +761,8 @@ class sparse_MF_SP(nn.Module):
         with torch.no_grad():
             mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X.repeat(self.out_dim, 1, 1), diagonal=True,
                                                                         is_duvenaud=False)
+            if self._is_hetero:      # output 0: f, the latent GP that goes through the flow
+                mean_q_f, cov_q_f = mean_q_f[:1], cov_q_f[:1]
             spec, theta, rowp = self._flow_inputs(X, with_grad=False)
         lvn = self._raw_params()[5].detach().reshape(-1)[:1].contiguous()
         theta = theta.detach() if theta is not None else None
@@ -770,6 +855,9 @@ class sparse_MF_SP(nn.Module):
         covariance."""
         if self._is_multiclass:
             raise NotImplementedError("posterior_paths is not built for multi-class models (num_outputs = C latent GPs)")
+        if self._is_hetero:
+            raise NotImplementedError("posterior_paths is not built for the heteroscedastic likelihood (HeteroscedasticGaussian: "
+                                      "two latent GPs)")
         if self.fully_bayesian:
             raise NotImplementedError("posterior_paths is not built for be_fully_bayesian models: the MC-dropout flows have "
                                       "no fixed per-row parameters, so a draw would not be one function")
@@ -788,7 +876,8 @@ class sparse_MF_SP(nn.Module):
         N, _ = X.shape
         with torch.no_grad():
             f_k, _, _, f_0 = self.sample_from_variational_marginal(X, S, diagonal=diagonal, is_duvenaud=False)
-            samples = [self.likelihood.sample_from_output(f_k, i).view(S, N, 1) for i in range(self.out_dim)]
+            # (the heteroscedastic likelihood has ONE observed output, drawn from both latent rows of f_k)
+            samples = [self.likelihood.sample_from_output(f_k, i).view(S, N, 1) for i in range(1 if self._is_hetero else self.out_dim)]
         self.train()
         return torch.stack(samples, dim=0), f_k, f_0
 

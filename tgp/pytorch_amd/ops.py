@@ -1109,6 +1109,76 @@ class EllStudentFunction(torch.autograd.Function):
                 g * grp if ctx.has[1] else None, None, None)
 
 
+def ell_hetero(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
+    """Heteroscedastic Gaussian ELL with gradients, y ~ N(G(f), exp(lvn + h)): mu, v of shape (2, N), row 0 the moments of q(f),
+    row 1 those of the log-noise GP q(h), which integrates out in closed form (tgp_ell_hetero_f64, one launch).  `flow` a
+    FlowSpec (an empty one for the identity flow).  Returns ell_student's dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp) -- g_mu,
+    g_v the row-0 adjoints, g_lvn = dELL/dlvn -- plus g_mu_h, g_v_h, the row-1 adjoints (views of the same (2, N) buffers)."""
+    lib = L.load()
+    if flow is None:
+        raise L.TgpError("the heteroscedastic likelihood needs a FlowSpec (an empty one for the identity flow)")
+    Y, mu, v, lvn = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    dev, N = Y.device, Y.numel()
+    if tuple(mu.shape) != (2, N) or tuple(v.shape) != (2, N):
+        raise L.TgpError("ell_hetero: mu and v must be (2, N) = (2, %d), got %s and %s" % (N, tuple(mu.shape), tuple(v.shape)))
+    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=L.LIK_HETERO)
+    ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    gmu, gv = torch.empty_like(mu), torch.empty_like(v)
+    gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
+    grp = torch.empty_like(rowp) if rowp is not None else None
+    L.check(lib.tgp_ell_hetero_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
+                                   L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
+            "tgp_ell_hetero_f64")
+    return {"ell": out[0], "g_lvn": out[1], "g_mu": gmu[0], "g_v": gv[0], "g_theta": gth[:flow.P], "g_rowp": grp,
+            "g_mu_h": gmu[1], "g_v_h": gv[1]}
+
+
+class EllHeteroFunction(torch.autograd.Function):
+    """ELL of the heteroscedastic Gaussian likelihood with autograd in (mu, v, log_var_noise, theta, rowp); mu, v (2, N).  Value
+    and every gradient come from one launch; `scale` multiplies them inside it."""
+
+    @staticmethod
+    def forward(ctx, Y, mu, v, lvn, theta, rowp, flow, S, scale):
+        res = ell_hetero(Y, mu.detach(), v.detach(), lvn.detach(), flow, theta.detach() if theta is not None else None, S,
+                         rowp.detach() if rowp is not None else None, scale=scale)
+        gmu, gv = torch.stack((res["g_mu"], res["g_mu_h"])), torch.stack((res["g_v"], res["g_v_h"]))
+        ctx.save_for_backward(res["g_lvn"], gmu, gv, res["g_theta"], res["g_rowp"] if res["g_rowp"] is not None else res["g_lvn"])
+        ctx.has = (theta is not None, rowp is not None)
+        ctx.lvn_shape = lvn.shape
+        return res["ell"].reshape(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        g_lvn, gmu, gv, gth, grp = ctx.saved_tensors
+        g = g.reshape(())
+        return (None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has[0] else None,
+                g * grp if ctx.has[1] else None, None, None, None)
+
+
+def predict_hetero(mu, v, lvn, flow, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, want_moments=True):
+    """The heteroscedastic predictive from the moments of both latent GPs (mu, v of shape (2, N); tgp_predict_hetero_f64, one
+    launch): (m1, m2, logp) in standardised units, m2 with the mean noise exp(lvn + mu_h + v_h / 2), logp = the exact log density
+    of the raw target under the S x S product rule, constant and -log Y_std included (None without Y)."""
+    lib = L.load()
+    if flow is None:
+        raise L.TgpError("the heteroscedastic likelihood needs a FlowSpec (an empty one for the identity flow)")
+    mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    if mu.dim() != 2 or mu.shape[0] != 2 or v.shape != mu.shape:
+        raise L.TgpError("predict_hetero: mu and v must be (2, N), got %s and %s" % (tuple(mu.shape), tuple(v.shape)))
+    dev, N = mu.device, mu.shape[1]
+    md, keep = _flow_model(N, S, flow, theta, lvn, dev, lik=L.LIK_HETERO)
+    m1, m2 = (torch.empty(N, dtype=torch.float64, device=dev), torch.empty(N, dtype=torch.float64, device=dev)) \
+        if want_moments else (None, None)
+    logp = torch.empty(N, dtype=torch.float64, device=dev) if Y is not None else None
+    Yc = _c(Y.reshape(-1), "Y") if Y is not None else None
+    L.check(lib.tgp_predict_hetero_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), float(Y_std), L.ptr(m1), L.ptr(m2),
+                                       L.ptr(logp), L.stream_ptr()), "tgp_predict_hetero_f64")
+    return m1, m2, logp
+
+
 class EllGaussFunction(torch.autograd.Function):
     """ELL = GaussianLinearMean.expected_log_prob (likelihoods/GaussianLinearMean.py:60-87) with autograd in (mu, v,
     log_var_noise) -- the reference's method is plain torch code, differentiable wherever it is called; tgp_ell_gauss_f64

@@ -119,6 +119,31 @@ def gross_errors(Y, seed=0, share=OUTLIERS_SHARE):
     return out, idx
 
 
+# input-dependent-noise stand-in: (rows, inputs, training rows) and the range of the noise standard deviation
+HETERO_SHAPE = (1000, 2, 900)
+HETERO_NOISE = (0.05, 1.0)
+
+
+def hetero_noise_std(X):
+    """The true noise standard deviation of `synthetic_hetero` at the rows of X (n, d): log-linear in x0 over [-2, 2], from
+    HETERO_NOISE[0] at x0 = -2 to HETERO_NOISE[1] at x0 = 2."""
+    lo, hi = HETERO_NOISE
+    return lo * (hi / lo) ** ((np.asarray(X)[:, 0] + 2.0) / 4.0)
+
+
+def hetero_dataset(seed=0):
+    """Seeded `synthetic_hetero`: X ~ U(-2, 2)^2, y = sin(2 x0) + 0.5 x1 + sigma(x0) eps, a smooth mean under Gaussian noise whose
+    standard deviation runs log-uniformly from 0.05 to 1.0 across x0 (hetero_noise_std).  mean log sigma = -1.50 against
+    log sqrt(mean sigma^2) = -0.90: a perfect noise model gains about 0.6 nats per point over the best constant one.  Returns
+    numpy float64 X (n, d), Y (n, 1) and sigma (n,), the rows' true noise standard deviation."""
+    n, d, _ = HETERO_SHAPE
+    rng = np.random.default_rng(15485863 + 31 * seed)
+    X = rng.uniform(-2.0, 2.0, size=(n, d))
+    sigma = hetero_noise_std(X)
+    Y = np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1] + sigma * rng.standard_normal(n)
+    return X, Y.reshape(-1, 1), sigma
+
+
 # multi-class stand-in: (rows, inputs, classes)
 BLOBS_SHAPE = (1200, 4, 4)
 

@@ -135,7 +135,7 @@ class Trainer_SP_regression:
         from .data import DeviceLoader
         from .engine import ElboEngine, MinibatchEngine, engine_refusal
         from .flow import compile_flow, mlp_spec
-        from .likelihoods import (Bernoulli, GaussianLinearMean, MulticlassCategorical, Poisson, StudentT,
+        from .likelihoods import (Bernoulli, GaussianLinearMean, HeteroscedasticGaussian, MulticlassCategorical, Poisson, StudentT,
                                   WarpedGaussianLinearMean)
         if not getattr(cg, "use_step_engine", True) or opt != "adam":
             return None
@@ -148,7 +148,8 @@ class Trainer_SP_regression:
         mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
         lik = next((name for cls, name in ((WarpedGaussianLinearMean, "warped"), (Bernoulli, "bernoulli"),
                                            (MulticlassCategorical, "multiclass"), (Poisson, "poisson"),
-                                           (StudentT, "studentt")) if isinstance(model.likelihood, cls)), None)
+                                           (StudentT, "studentt"), (HeteroscedasticGaussian, "hetero"))
+                    if isinstance(model.likelihood, cls)), None)
         cover = dict(is_whiten=getattr(model, "is_whiten", True), mean=None if mean_fn is None else mean_fn.name, likelihood=lik,
                      minibatch=len(ld) != 1)
         if engine_refusal(**cover) is not None:        # (before the flow is compiled: whether it is input-dependent comes below)
@@ -398,12 +399,13 @@ class Trainer_SP_regression:
         exact = self.coverage == "exact"
         poisson = getattr(self.model, "_is_poisson", False)
         student = getattr(self.model, "_is_student", False)
-        if exact and (self.model.fully_bayesian or poisson or student):
+        hetero = getattr(self.model, "_is_hetero", False)
+        if exact and (self.model.fully_bayesian or poisson or student or hetero):
             # an MC-dropout mixture over parameter draws has no closed CDF here, a count model no continuous quantiles, a
-            # Student-t model no CDF kernel: the sampled recipe, said once
+            # Student-t or heteroscedastic model no CDF kernel: the sampled recipe, said once
             if not self._coverage_fallback_said:
                 print("[tgp.pytorch_amd] coverage='exact' is not built for the %s model: sampled coverage instead"
-                      % ("Poisson" if poisson else "Student-t" if student else "fully Bayesian"))
+                      % ("Poisson" if poisson else "Student-t" if student else "heteroscedastic" if hetero else "fully Bayesian"))
                 self._coverage_fallback_said = True
             exact = False
         if exact:
