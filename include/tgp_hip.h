@@ -642,6 +642,25 @@ int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const dou
 int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                         double* cdf /* (N) */, double* sf /* (N), optional */, void* stream);
 
+/* Continuous ranked probability score of the same predictive at Y (TGP_LIK_GAUSS and TGP_LIK_FLOW; model fields and limits
+ * as for tgp_predict_cdf_f64, standardised units), CRPS_n = int (F_n(t) - 1{t >= Y_n})^2 dt in closed form.  With
+ * g_s = G(mu_n + sqrt(2 max(v_n, 0)) xs_s), sig^2 = exp(log_var_noise[0]) and
+ *   a(z) = z erf(z / sqrt 2) + sqrt(2 / pi) exp(-z^2 / 2)      (= z (2 Phi(z) - 1) + 2 phi(z); even, a(z) >= |z|):
+ *   T1 = sig sum_s wn_s a((Y_n - g_s) / sig)                                                             (E|Y - y|)
+ *   T2 = sig / sqrt(pi) sum_s wn_s^2 + sqrt(2) sig sum_{s<t} wn_s wn_t a((g_s - g_t) / (sqrt(2) sig))    (E|Y - Y'| / 2)
+ *   crps[n] = T1 - T2;   parts (optional, (2,N)): T1 in row 0, T2 in row 1, crps = T1 - T2 bit for bit.
+ * TGP_LIK_GAUSS or an empty program: one term, sd = sqrt(max(v, 0) + sig^2), z = (Y - mu) / sd, T1 = sd a(z), T2 = sd / sqrt(pi),
+ * CRPS = sd (a(z) - 1 / sqrt(pi)).  A row with v <= 0 counts as v = 0 (its nodes coincide; no special case).  The sums are
+ * evaluated as written with the caller's wn, nothing is renormalised; every term is positive and a(z) = |z| once the
+ * exponential underflows, so targets 1e8 sig away give finite values.  The S node values are computed once per row and kept in
+ * LDS; T2 takes each of the S (S - 1) / 2 unordered pairs once, numbered by cyclic offset (pair k: nodes k mod S and
+ * (k mod S + k div S + 1) mod S), in a fixed order that does not depend on N: no float atomics, same input, same bits, and a
+ * row's value depends on that row's inputs only.  Limits: 1 <= S <= TGP_QUANTILE_MAX_S; every lik but TGP_LIK_GAUSS and
+ * TGP_LIK_FLOW is refused -- TGP_E_UNSUPPORTED, tgp_last_error() starts with the entry and names lik = k or S = k.  A null
+ * model, mu, v, Y, crps: -1, -2, -3, -5, -6.  Every refusal happens before any launch. */
+int tgp_predict_crps_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
+                         double* crps /* (N) */, double* parts /* (2,N): T1 row 0, T2 row 1; optional */, void* stream);
+
 /* Inducing-point initialisation: the numerical kernels behind utils.KMEANS, which replaces
  * sklearn.cluster.KMeans(init='k-means++', n_init, random_state) of dsp/utils.py:143-159.  Random draws, the stopping
  * rule and the restarts stay on the host (tgp/pytorch_amd/utils.py); D <= 16.

@@ -1051,6 +1051,24 @@ int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* 
   return launch_predict_cdf(md, fp, mu, v, rowp, Y, cdf, sf, static_cast<hipStream_t>(stream));
 }
 
+int tgp_predict_crps_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
+                         double* crps, double* parts, void* stream) {
+  // (every other likelihood by its number: the closed pair term is the Gaussian mixture's)
+  if (model && model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW) {
+    set_error_text("tgp_predict_crps_f64: no closed-form CRPS for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only: the pair term "
+                   "is that of an equal-variance Gaussian mixture)", model->lik);
+    return TGP_E_UNSUPPORTED;
+  }
+  bool flowed = false;
+  if (int rc = check_quantile_model(model, mu, v, rowp, "tgp_predict_crps_f64", &flowed)) return rc;
+  if (!Y) return -5;
+  if (!crps) return -6;
+  FlowProg fp;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
+  return launch_predict_crps(md, fp, mu, v, rowp, Y, crps, parts, static_cast<hipStream_t>(stream));
+}
+
 int tgp_kmeans_assign_f64(const double* X, int32_t N, int32_t D, const double* C, int32_t K, int32_t* labels, double* mind2,
                           void* stream) {
   if (!X) return -1;

@@ -194,6 +194,9 @@ int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const doubl
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st);
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                        const double* Y, double* cdf, double* sf, hipStream_t st);
+// ... the CRPS of the same predictive at Y: crps (N), parts (2,N) = T1, T2 (optional)
+int launch_predict_crps(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                        const double* Y, double* crps, double* parts, hipStream_t st);
 // ... and the heteroscedastic predictive on the same node table: mu, v (2,N), moments and the S x S log density
 int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                           const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st);

@@ -5,6 +5,8 @@
 //   k_pred_quantile<X>  t = the root of F_n(t) = p for Q probabilities per row, a bracketed Newton iteration on the S node values
 //   k_quantile_gauss    TGP_LIK_GAUSS / the empty program: one Gaussian, closed forms for both
 //   k_predict_hetero<X> the heteroscedastic predictive (tgp_predict_hetero_f64): moments and log density on the same node table
+//   k_pred_crps<X, W>   the CRPS int (F_n(t) - 1{t >= Y_n})^2 dt in closed form: one pass over the nodes, one over their pairs
+//   k_crps_gauss        ... of one Gaussian (TGP_LIK_GAUSS / the empty program)
 // QLPR = 16 lanes share a data row (4 rows per wave, one wave per workgroup): the lanes sweep the row's S nodes -- and the Q
 // starting points G(mu + zq sqrt v) -- through the flow once (flow_forward_n, 4 elements in flight per lane) into LDS, and
 // every evaluation of F afterwards reads those S numbers only: lane l adds the nodes l, l + 16, ... in that order, the 16
@@ -283,6 +285,117 @@ __global__ __launch_bounds__(64) void k_predict_hetero(tgp_model md, FlowProg fp
   }
 }
 
+// Continuous ranked probability score of the predictive at Y (tgp_predict_crps_f64), CRPS_n = T1 - T2 in standardised units:
+//   a(z) = z erf(z / sqrt 2) + sqrt(2 / pi) exp(-z^2 / 2)                            (even, >= |z|; = |z| once the exponential is 0)
+//   T1 = sig sum_s wn_s a((y - g_s) / sig)                                           = E|Y - y|
+//   T2 = sig / sqrt(pi) sum_s wn_s^2 + sqrt(2) sig sum_{s<t} wn_s wn_t a((g_s - g_t) / (sqrt(2) sig))   = E|Y - Y'| / 2
+// evaluated as written with the caller's wn (nothing is renormalised); every term is positive.  A row with v <= 0 counts as
+// v = 0: its nodes coincide and the sums give sig (a((y - G(mu)) / sig) - (sum wn)^2 / sqrt(pi)) with no special case.
+// ORDER.  The row's 16 lanes sweep the S node values into LDS once (q_sweep).  T1 and sum wn^2: lane l adds the nodes
+// l, l + 16, ... in that order (as q_eval), row16_sum joins the 16 partials.  The S (S - 1) / 2 unordered pairs are numbered by
+// cyclic offset: pair k = 0 .. S (S - 1) / 2 - 1 is (s, t) = (k mod S, (k mod S + k div S + 1) mod S) -- offsets 1 .. (S - 1) / 2
+// over every s, and for even S the first S / 2 pairs of offset S / 2; each pair once.  With CRPS_WAVES waves per workgroup
+// (all on the same QROWS rows), lane l of wave w adds the pairs k = 16 w + l + 16 CRPS_WAVES j, j = 0, 1, ... in that order,
+// row16_sum joins a wave's 16 partials, and the waves' sums are added in the order w = 0, 1, ... from LDS.  CRPS_WAVES is a
+// constant of the build -- never a function of N -- so a row's bits depend on that row's inputs only.  No float atomics.
+// The loops are uniform over the workgroup (a lane past the last pair adds a weight of 0).
+// dynamic LDS: tp, tg, wn as k_pred_cdf, QROWS node tables of q_row_stride(S), then CRPS_WAVES x QROWS wave sums
+#ifndef TGP_CRPS_WAVES
+#define TGP_CRPS_WAVES 4
+#endif
+#define CRPS_WAVES TGP_CRPS_WAVES
+#define Q_SQRT_2_OVER_PI 0.79788456080286535588
+#define Q_INV_SQRT_PI 0.56418958354775628695
+#define Q_SQRT2 1.41421356237309504880
+
+__device__ __forceinline__ double crps_a(double z) { return z * erf(z * Q_SQRT1_2) + Q_SQRT_2_OVER_PI * exp(-0.5 * z * z); }
+
+template <bool X, int W>
+__global__ __launch_bounds__(64 * W) void k_pred_crps(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                      const double* __restrict__ v, const double* __restrict__ rowp,
+                                                      const double* __restrict__ Y, int stride, double* __restrict__ crps,
+                                                      double* __restrict__ parts) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S;
+  double* gs = wl + (S + 1) / 2 * 2 + (size_t)r * stride;
+  double* red = wl + (S + 1) / 2 * 2 + (size_t)QROWS * stride;
+  for (int s = tid; s < S; s += 64 * W) wl[s] = md.wn[s];
+  flow_params_lds<X>(md.theta, fp, tp, tg);   // (ends with a barrier: wl is staged too)
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
+  const double sig = sqrt(exp(md.log_var_noise[0]));
+  if (wv == 0) q_sweep<X>(F, md, rp, mu[nc], vn, nullptr, 0, l16, gs);
+  __syncthreads();
+  // ---- the pairs, dealt over the W waves
+  const int npair = S * (S - 1) / 2;
+  const double sig2 = Q_SQRT2 * sig;
+  double pr = 0.0;
+  {
+    int k = wv * QLPR + l16, d = k / S, s = k - d * S;       // pair k: offset d + 1 from node s
+    for (int k0 = 0; k0 < npair; k0 += QLPR * W) {
+      const bool in = k < npair;
+      int t = s + d + 1;
+      if (t >= S) t -= S;
+      const int sc = in ? s : 0, tc = in ? t : 0;
+      const double w = in ? wl[sc] * wl[tc] : 0.0;
+      pr += w * crps_a((gs[sc] - gs[tc]) / sig2);
+      k += QLPR * W;
+      s += QLPR * W;
+      while (s >= S) { s -= S; ++d; }
+    }
+  }
+  pr = row16_sum(pr);
+  if constexpr (W > 1) {
+    if (l16 == 0) red[wv * QROWS + r] = pr;
+    __syncthreads();
+    if (wv != 0) return;
+    pr = red[r];
+    for (int w = 1; w < W; ++w) pr += red[w * QROWS + r];
+  }
+  // ---- T1 and the diagonal of T2: one pass over the nodes
+  const double y = Y[nc];
+  double t1 = 0.0, w2 = 0.0;
+  for (int s0 = 0; s0 < S; s0 += QLPR) {
+    const int s = s0 + l16, sc = s < S ? s : S - 1;
+    const double w = s < S ? wl[sc] : 0.0;
+    t1 += w * crps_a((y - gs[sc]) / sig);
+    w2 += w * w;
+  }
+  t1 = row16_sum(t1);
+  w2 = row16_sum(w2);
+  if (valid && l16 == 0) {
+    const double T1 = sig * t1, T2 = sig * Q_INV_SQRT_PI * w2 + sig2 * pr;
+    crps[n] = T1 - T2;
+    if (parts) {
+      parts[n] = T1;
+      parts[(size_t)md.N + n] = T2;
+    }
+  }
+}
+
+// TGP_LIK_GAUSS / the empty program: one Gaussian of sd^2 = max(v, 0) + sig^2, z = (y - mu) / sd:
+// T1 = sd a(z), T2 = sd / sqrt(pi), CRPS = T1 - T2 = sd (a(z) - 1 / sqrt(pi)).
+__global__ __launch_bounds__(256) void k_crps_gauss(int N, const double* __restrict__ mu, const double* __restrict__ v,
+                                                    const double* __restrict__ lvn, const double* __restrict__ Y,
+                                                    double* __restrict__ crps, double* __restrict__ parts) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const double sd = sqrt(fmax(v[n], 0.0) + exp(lvn[0]));
+  const double T1 = sd * crps_a((Y[n] - mu[n]) / sd), T2 = sd * Q_INV_SQRT_PI;
+  crps[n] = T1 - T2;
+  if (parts) {
+    parts[n] = T1;
+    parts[(size_t)N + n] = T2;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
@@ -339,6 +452,25 @@ int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu
   auto* const kern = ext ? k_pred_cdf<true> : k_pred_cdf<false>;
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, stride, cdf, sf);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_predict_crps(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                        const double* Y, double* crps, double* parts, hipStream_t st) {
+  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+    hipLaunchKernelGGL(k_crps_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise, Y, crps, parts);
+    LAUNCH_CHECK();
+    return 0;
+  }
+  int stride = 0;
+  const size_t lds = q_lds_bytes(md, 0, &stride) + (size_t)CRPS_WAVES * QROWS * sizeof(double);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_pred_crps<true, CRPS_WAVES> : k_pred_crps<false, CRPS_WAVES>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64 * CRPS_WAVES), lds, st, md, fp, mu, v, rowp, Y, stride, crps,
+                     parts);
   LAUNCH_CHECK();
   return 0;
 }

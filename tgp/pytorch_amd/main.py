@@ -112,6 +112,9 @@ def main(argv=None):
                     help="inducing inputs at the start: kmeans = centroids of k-means++ / Lloyd, best of 10 (the reference); greedy = "
                          "the training rows picked by greedy conditional-variance selection (pivoted Cholesky of K_XX) under the "
                          "kernel at its initial hyper-parameters; prints the share of tr(K_XX) they leave unexplained")
+    ap.add_argument("--scores", action="store_true",
+                    help="also print the test CRPS and 95 %% interval score (regression; raw units): exact where the predictive "
+                         "CDF is, else the CRPS of 100 predictive draws per row and no interval score")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -148,6 +151,8 @@ def main(argv=None):
         ap.error("--likelihood multiclass: SVGP or TGP only")
     if multi != (args.dataset in MULTICLASS_DATASETS):
         ap.error("--likelihood multiclass goes with the multi-class data sets (%s)" % ", ".join(MULTICLASS_DATASETS))
+    if args.scores and (bern or multi):
+        ap.error("--scores: regression only (the CRPS and the interval score are scores of a predictive distribution on the reals)")
     wgp = args.model == "WGP"
     if wgp and (bern or multi):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
@@ -264,6 +269,9 @@ def main(argv=None):
             args.dataset, args.num_inducing, args.model, -res[6], res[7]))
         print("Dataset {}, constant rate {:.3f}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
             args.dataset, rate.item(), base_nll, base_rmse))
+        if args.scores:
+            print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
+                args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))
         return res
     if args.model == "ID_TGP":       # the reference's result lines (main.py:309-324)
         print("Dataset {}, num inducing points {}, POINT ESTIMATE FLOW , Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
@@ -278,6 +286,11 @@ def main(argv=None):
         corr = torch.corrcoef(torch.stack((learned, torch.log(dc["noise_std_te"]))))[0, 1].item()
         print("Dataset {}, num inducing points {}, model {}, log noise std correlation {:.3f}".format(
             args.dataset, args.num_inducing, args.model, corr))
+    if args.scores:
+        sc = trainer.compute_scores()["test"]
+        print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f}, Test interval score (95%) {}".format(
+            args.dataset, args.num_inducing, args.model, sc["crps"],
+            "n/a" if sc["interval_score"] is None else "{:.4f}".format(sc["interval_score"])))
     if args.model == "ID_TGP":
         model.be_fully_bayesian(True)
         res = trainer.compute_metrics()

@@ -739,6 +739,23 @@ class sparse_MF_SP(nn.Module):
     # ---- exact quantiles and CDF of the predictive / posterior marginals -----------------------------------
     def _quantile_inputs(self, X, what):
         """Eval-mode q(f) moments (mu, v of shape (N,)), the noise and the flow inputs of the rows of X, under no_grad."""
+        if what == "predictive_crps":        # (its own reasons; the existing values of `what` below are unchanged)
+            name = type(self.likelihood).__name__
+            if self._is_bernoulli or self._is_multiclass:
+                raise NotImplementedError("predictive_crps: a %s model predicts classes, which have no CRPS" % name)
+            why = None
+            if self._is_student:
+                why = "the Student-t likelihood (%s) has no closed pair term E|Y - Y'| for a mixture of t densities" % name
+            elif self._is_hetero:
+                why = ("the heteroscedastic likelihood (%s) is a double mixture with unequal variances, whose pair term is not "
+                       "built" % name)
+            elif self._is_warped:
+                why = "the warped predictive (%s) is not a Gaussian mixture in y, so it has no closed pair term" % name
+            elif self.fully_bayesian:
+                why = "the fully Bayesian model is an MC-dropout mixture over parameter draws, which the kernel does not sum"
+            if why is not None:
+                raise NotImplementedError("predictive_crps: %s; pass samples=S for the sampled estimator "
+                                          "(ops.crps_from_samples of S predictive draws)" % why)
         if self._is_bernoulli or self._is_multiclass:
             raise NotImplementedError("%s: a %s model has no quantiles" % (what, type(self.likelihood).__name__))
         if self._is_poisson and what != "posterior_quantiles":
@@ -808,6 +825,51 @@ class sparse_MF_SP(nn.Module):
                 cdf, _ = ops.predict_cdf(mu, v, lvn, y, spec, theta, self.quad_points, rowp)
         self.train()
         return cdf.unsqueeze(0)
+
+    def predictive_crps(self, X, Y, Y_std=None, samples=None, kmax=None):
+        """The continuous ranked probability score of p(y* | x*) at the targets Y (N,1), shape (Dy, N), in the model's
+        standardised units -- or times Y_std when that is given (the CRPS has the units of the target).  Exact through
+        ops.predict_crps for whatever predictive_cdf serves through the Gauss-Hermite mixture (Gaussian and flow likelihoods).
+        A Poisson model: sum_k (cdf_k - 1{k >= y})^2 over k = 0..kmax from predictive_pmf(X, kmax); kmax is the caller's, as
+        for predictive_pmf (past the mass the terms are 0).  samples=S: ops.crps_from_samples of S draws of
+        sample_from_predictive_distribution, for any regression model.  Without it Student-t, heteroscedastic, warped and fully
+        Bayesian models raise NotImplementedError; Bernoulli and multi-class models always do."""
+        exact = samples is None and not self._is_poisson
+        if exact or self._is_bernoulli or self._is_multiclass:
+            ins = self._quantile_inputs(X, "predictive_crps")       # (the refusals; classifiers are refused on every route)
+        y = Y.reshape(-1)
+        if samples is not None:
+            was = self.is_training
+            self.set_is_training(False)
+            try:
+                draws, _, _ = self.sample_from_predictive_distribution(X, int(samples))       # (Dy,S,N,1)
+            finally:
+                self.set_is_training(was)
+            out = ops.crps_from_samples(draws[0, :, :, 0], y.to(draws.dtype)).unsqueeze(0)
+        elif self._is_poisson:
+            if kmax is None:
+                raise ValueError("predictive_crps of a Poisson model needs kmax, the last count of the sum (predictive_pmf's)")
+            cdf = self.predictive_pmf(X, kmax).cumsum(1)                                       # (N, kmax + 1)
+            k = torch.arange(int(kmax) + 1, dtype=cdf.dtype, device=cdf.device).unsqueeze(0)
+            out = ((cdf - (k >= y.to(cdf.dtype).unsqueeze(1)).to(cdf.dtype)) ** 2).sum(1).unsqueeze(0)
+        else:
+            mu, v, lvn, spec, theta, rowp = ins
+            with torch.no_grad():
+                out = ops.predict_crps(mu, v, lvn, y.to(mu.dtype), spec, theta, self.quad_points, rowp).unsqueeze(0)
+            self.train()
+        if Y_std is not None:
+            out = out * float(torch.as_tensor(Y_std).reshape(-1)[0])
+        return out
+
+    def predictive_interval_score(self, X, Y, alpha=0.05, Y_std=None):
+        """The interval score of the central (1 - alpha) predictive interval at the targets Y (N,1), shape (Dy, N):
+        ops.interval_score of predictive_quantiles(X, [alpha / 2, 1 - alpha / 2]) -- the same models, the same refusals.
+        Standardised units, or times Y_std when that is given."""
+        q = self.predictive_quantiles(X, [0.5 * alpha, 1.0 - 0.5 * alpha])[0]                  # (2,N)
+        out = ops.interval_score(q[0], q[1], Y.reshape(-1).to(q.dtype), alpha).unsqueeze(0)
+        if Y_std is not None:
+            out = out * float(torch.as_tensor(Y_std).reshape(-1)[0])
+        return out
 
     # ---- sampling (sparse_MF_SP.py:837-992) --------------------------------------------------------
     def sample_from_variational_marginal_base(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None, S: int = 1):

@@ -1494,6 +1494,45 @@ def predict_cdf(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None):
     return cdf, sf
 
 
+def predict_crps(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None, want_parts=False):
+    """The continuous ranked probability score of the predictive at Y per row, int (F_n(t) - 1{t >= Y_n})^2 dt in closed form
+    (tgp_predict_crps_f64): crps (N,), in the model's standardised units like Y.  want_parts: (crps, parts) with parts (2,N) =
+    T1 = E|Y - y| and T2 = E|Y - Y'| / 2, crps = T1 - T2 bit for bit.  flow=None: the Gaussian likelihood's closed form."""
+    lib = L.load()
+    mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    Yc = _c(Y.reshape(-1), "Y")
+    if Yc.numel() != mu.numel():
+        raise ValueError("Y must hold one value per row (%d), got %d" % (mu.numel(), Yc.numel()))
+    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    crps = torch.empty_like(mu)
+    parts = torch.empty(2, mu.numel(), dtype=torch.float64, device=mu.device) if want_parts else None
+    L.check(lib.tgp_predict_crps_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), L.ptr(crps), L.ptr(parts), L.stream_ptr()),
+            "tgp_predict_crps_f64")
+    return (crps, parts) if want_parts else crps
+
+
+def crps_from_samples(draws, y):
+    """The CRPS of the empirical distribution of `draws` (S,N) at y (N,), per row: the sorted-sample form
+    1/S sum_i |x_i - y| - 1/S^2 sum_i (2 i - S - 1) x_(i), i = 1..S over the sorted draws, which is exactly the double sum
+    1/S sum_i |x_i - y| - 1/(2 S^2) sum_ij |x_i - x_j|.  Plain torch on the tensors' device."""
+    S = draws.shape[0]
+    x = draws.reshape(S, -1)
+    y = y.reshape(1, -1).to(x.dtype)
+    xs, _ = torch.sort(x, dim=0)
+    c = (2.0 * torch.arange(1, S + 1, dtype=x.dtype, device=x.device) - S - 1.0).reshape(S, 1)
+    return (x - y).abs().sum(0) / S - (c * xs).sum(0) / (S * S)
+
+
+def interval_score(lo, hi, y, alpha):
+    """The interval score of the central (1 - alpha) interval [lo, hi] at y (Gneiting & Raftery 2007):
+    (hi - lo) + 2/alpha (lo - y)_+ + 2/alpha (y - hi)_+, elementwise."""
+    alpha = float(alpha)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("alpha must lie strictly inside (0, 1), got %r" % alpha)
+    return (hi - lo) + (2.0 / alpha) * (lo - y).clamp_min(0.0) + (2.0 / alpha) * (y - hi).clamp_min(0.0)
+
+
 # ---------------------------------------------------------------------------------------------------
 # per-row parameter networks of the input-dependent flows (models/flow.py:836-897)
 # ---------------------------------------------------------------------------------------------------

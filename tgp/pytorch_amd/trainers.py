@@ -51,6 +51,7 @@ class Trainer_SP_regression:
             raise ValueError("coverage must be 'sampled' or 'exact', got %r" % (coverage,))
         self.coverage = coverage
         self._coverage_fallback_said = False
+        self._scores_fallback_said = False
         # [train], [train, test] or [train, valid, test] (trainer_base.py:50-59)
         dl = list(data_loaders)
         self.train_loader, self.valid_loader, self.test_loader = dl[0], None, None
@@ -436,6 +437,38 @@ class Trainer_SP_regression:
         out += list(self._loader_metrics(self.valid_loader)) if self.is_valid else [0.0, 0.0, 0.0]
         out += list(self._loader_metrics(self.test_loader)) if self.is_test else [0.0, 0.0, 0.0]
         return tuple(out)
+
+    # ---- proper scores beside the log score ----------------------------------------------------------------
+    def _loader_scores(self, loader, samples):
+        model = self.model
+        sampled = samples is not None or model.fully_bayesian or any(
+            getattr(model, a, False) for a in ("_is_poisson", "_is_student", "_is_hetero", "_is_warped"))
+        if sampled and samples is None and not self._scores_fallback_said:
+            print("[tgp.pytorch_amd] the exact CRPS is not built for this model: the CRPS of %d predictive draws per row instead, "
+                  "and no interval score" % self.S_test)
+            self._scores_fallback_said = True
+        ystd = self.Y_std.reshape(-1)[:1].to(cg.device)
+        tot, crps, isc = 0.0, 0.0, 0.0
+        for x, y in loader:
+            x, y = x.to(cg.device), y.to(cg.device)
+            model.set_is_training(False)
+            if sampled:
+                crps += model.predictive_crps(x, y, Y_std=ystd, samples=self.S_test if samples is None else samples).sum().item()
+            else:
+                crps += model.predictive_crps(x, y, Y_std=ystd).sum().item()
+                isc += model.predictive_interval_score(x, y, 0.05, Y_std=ystd).sum().item()
+            tot += x.size(0)
+        return {"crps": crps / tot, "interval_score": None if sampled else isc / tot}
+
+    def compute_scores(self, samples=None):
+        """{"train" | "valid" | "test": {"crps": mean, "interval_score": mean}} in raw units (standardised scores times Y_std):
+        the exact CRPS (model.predictive_crps) and the 95 % interval score of the exact quantiles where they exist; otherwise --
+        or with samples=S -- the CRPS of S (default S_test) predictive draws per row, said once, and interval_score None.  A
+        split without a loader is None."""
+        self.refresh_qu()
+        return {"train": self._loader_scores(self.train_loader, samples),
+                "valid": self._loader_scores(self.valid_loader, samples) if self.is_valid else None,
+                "test": self._loader_scores(self.test_loader, samples) if self.is_test else None}
 
 
 class Trainer_SP_classification(Trainer_SP_regression):
