@@ -205,7 +205,8 @@ def test_method_refusals_name_the_likelihood():
     try:
         for kind in ("svgp", "tgp"):
             model, X = _model(kind)
-            assert model._is_hetero and model._is_composed and model.out_dim == 2 and model._lik_id is None
+            assert model.likelihood.num_latent == 2 and model.likelihood.engine_name == "hetero"
+            assert model._is_composed and model.out_dim == 2 and model._lik_id is None
             assert "likelihood.log_var_noise" in dict(model.named_parameters())
             assert model.Z.shape == (2, 5, 3) and model.q_U.variational_mean.shape == (2, 5)
             Y = torch.zeros(30, 1, dtype=F64)

@@ -97,8 +97,9 @@ def test_engine_refusal_and_model_surface():
     from tgp.pytorch_amd.engine import engine_refusal
     assert "Poisson" in engine_refusal(likelihood="poisson")
     assert "Poisson" in engine_refusal(likelihood="poisson", minibatch=True)
-    for name in ("_is_poisson", "predictive_pmf"):
-        assert hasattr(models.sparse_MF_SP, name)
+    from tgp.pytorch_amd import likelihoods
+    assert likelihoods.Poisson.lik_id == L.LIK_POISSON and likelihoods.Poisson.kind == "count"
+    assert hasattr(models.sparse_MF_SP, "predictive_pmf")
     assert callable(ops.ell_poisson) and callable(ops.EllPoissonFunction.apply) and callable(ops.EllBernoulliFunction.apply)
 
 

@@ -124,7 +124,8 @@ def test_engine_refusal_and_surface():
     from tgp.pytorch_amd.engine import engine_refusal
     assert "Student-t" in engine_refusal(likelihood="studentt")
     assert "Student-t" in engine_refusal(likelihood="studentt", minibatch=True)
-    assert hasattr(models.sparse_MF_SP, "_is_student")
+    from tgp.pytorch_amd import likelihoods
+    assert likelihoods.StudentT.lik_id == L.LIK_STUDENT
     assert callable(ops.ell_student) and callable(ops.EllStudentFunction.apply)
     lvn = torch.zeros(1, dtype=F64)
     assert ops.student_noise(lvn, 4.0).tolist() == [0.0, 4.0]
@@ -164,7 +165,7 @@ def test_model_refusals():
             _model("svgp", num_outputs=2)
         for kind in ("svgp", "tgp"):
             model, X = _model(kind)
-            assert model._is_student and model._lik_id == L.LIK_STUDENT
+            assert model.likelihood.lik_id == L.LIK_STUDENT and model._lik_id == L.LIK_STUDENT
             assert [n for n, _ in model.named_parameters() if "df" in n.split(".")] == []
             assert "likelihood.log_var_noise" in dict(model.named_parameters())
             Y = torch.zeros(30, 1, dtype=F64)

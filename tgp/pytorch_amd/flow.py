@@ -343,6 +343,15 @@ def nets_rowp(nets, X2d, samples=1, spec=None, with_grad=False):
     return ops.mlp_forward(spec.salted(ops.MASK_SALT_NETS), Xs, W, bool(drop_on), step)
 
 
+def stack_theta(theta_list, device=None, with_grad=False):
+    """The shared scalar parameters of a compiled flow (compile_flow's `theta` list) as one vector on `device` (None: where
+    they are), None for an empty list.  `with_grad` keeps the graph to the parameters; else they enter detached."""
+    if not theta_list:
+        return None
+    theta = torch.stack([p.reshape(()) if with_grad else p.detach().reshape(()) for p in theta_list])
+    return theta if device is None else theta.to(device)
+
+
 def compile_flow(flow):
     """CompositeFlow -> (ops.FlowSpec, [shared scalar nn.Parameters in theta order], [per-row MLPs in column order])."""
     blocks, theta, nets = [], [], []

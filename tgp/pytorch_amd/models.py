@@ -24,11 +24,8 @@ import torch.nn as nn
 
 from . import config as cg
 from . import ops
-from .flow import CompositeFlow, IdentityFlow, compile_flow, instance_flow
+from .flow import IdentityFlow, compile_flow, instance_flow, stack_theta
 from .means import MEAN_NAMES, ZeroMean, return_mean, return_projection_matrix
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
-                          Poisson, StudentT, WarpedGaussianLinearMean)
-from .utils import positive_transform
 
 DEFAULT_INIT = {"variational_distribution": {"variance_scale": 1.0, "mean_scale": 0.0}}
 
@@ -60,17 +57,13 @@ class sparse_MF_SP(nn.Module):
                  be_fully_bayesian: bool = False, init_params: dict = {}) -> None:
         super().__init__()
         assert len(model_specs) == 2, "Parameter model_specs should be len 2: mean name and kernel instance"
-        if isinstance(likelihood, StudentT) and int(num_outputs) != 1:
-            raise NotImplementedError("the Student-t likelihood is built for one output (num_outputs = 1)")
-        # C outputs only as the C latent GPs of the multi-class likelihood, 2 only as (f, h) of the heteroscedastic one (composed
-        # step)
-        assert int(num_outputs) == 1 or (isinstance(likelihood, MulticlassCategorical) and int(num_outputs) == likelihood.C) or \
-            (isinstance(likelihood, HeteroscedasticGaussian) and int(num_outputs) == 2), \
-            "this build implements the single-output path (Dy = 1, every BASELINE config)"
-        assert not isinstance(likelihood, HeteroscedasticGaussian) or int(num_outputs) == 2, \
-            "HeteroscedasticGaussian needs num_outputs = 2: latent GP 0 is f, latent GP 1 the log-noise h"
-        assert not isinstance(likelihood, MulticlassCategorical) or int(num_outputs) == likelihood.C, \
-            "MulticlassCategorical needs num_outputs = its number of classes"
+        if int(num_outputs) != likelihood.num_latent:
+            if likelihood.num_latent == 1 and likelihood.outputs_refusal is not None:
+                raise NotImplementedError(likelihood.outputs_refusal)
+            # C outputs only as the C latent GPs of the multi-class likelihood, 2 only as (f, h) of the heteroscedastic one (composed
+            # step)
+            assert int(num_outputs) == 1, "this build implements the single-output path (Dy = 1, every BASELINE config)"
+            raise AssertionError(likelihood.outputs_refusal)
         assert model_specs[0] in MEAN_NAMES, "mean function must be one of %s, got %r" % (", ".join(MEAN_NAMES), model_specs[0])
         assert not (K_is_shared or Z_is_shared or q_U_is_shared), "sharing flags are False in main.py"
         assert not mean_is_shared or model_specs[0] == "linear", \
@@ -88,8 +81,8 @@ class sparse_MF_SP(nn.Module):
         self.init_params = ip
         self.standard_sampler = None        # the reference re-creates a td.MultivariateNormal here; sampling uses torch.randn
         self.is_training = True
-        self.quad_points = likelihood.quad_points if isinstance(likelihood, (GaussianNonLinearMean, Bernoulli, Poisson, StudentT, WarpedGaussianLinearMean, MulticlassCategorical, HeteroscedasticGaussian)) else cg.quad_points
-        if isinstance(likelihood, (Bernoulli, Poisson)):
+        self.quad_points = getattr(likelihood, "quad_points", cg.quad_points)
+        if not likelihood.has_noise and not likelihood.composed:
             # the ABI's noise pointer: read by no Bernoulli or Poisson kernel, gradient 0; a buffer, so model.parameters() is the
             # reference's (Bernoulli) and holds no noise parameter (Poisson)
             self.register_buffer("_bern_lvn", torch.zeros(1, dtype=cg.dtype), persistent=False)
@@ -119,26 +112,14 @@ class sparse_MF_SP(nn.Module):
             G.append(instance_flow(fl) if isinstance(fl, list) else fl)
         self.G_matrix = nn.ModuleList(G)
         self.G_flow_connection = flow_connection
-        if self._is_poisson and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
-                                    for fl in getattr(g, "flow_arr", [])):
-            raise NotImplementedError("the Poisson likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
-        if self._is_student and any(getattr(fl, "input_dependent", False) for g in self.G_matrix
-                                    for fl in getattr(g, "flow_arr", [])):
-            raise NotImplementedError("the Student-t likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
-        if self._is_hetero:
-            if any(not isinstance(fl, IdentityFlow) for fl in getattr(self.G_matrix[1], "flow_arr", [self.G_matrix[1]])):
-                raise NotImplementedError("the heteroscedastic likelihood takes no flow on h, the log-noise GP: flow_specs[1] must be empty")
-            if any(getattr(fl, "input_dependent", False) for fl in getattr(self.G_matrix[0], "flow_arr", [])):
-                raise NotImplementedError("the heteroscedastic likelihood is built for SVGP and TGP: input-dependent flows (ID_TGP) are not")
-            if model_specs[0] != "zero":
-                raise NotImplementedError("the '%s' mean function is not built for the heteroscedastic likelihood: use the 'zero' mean"
-                                          % model_specs[0])
+        if any(not isinstance(fl, IdentityFlow) for g in self.G_matrix[likelihood.flow_outputs:] for fl in getattr(g, "flow_arr", [g])):
+            raise NotImplementedError(likelihood.extra_flow_refusal)
+        if self._input_dependent and likelihood.refuses_input_dependent is not None:
+            raise NotImplementedError(likelihood.refuses_input_dependent)
         # mean function (sparse_MF_SP.py:184-206); mean_is_shared: one mean for all outputs, at Dy = 1 the same object
         name = model_specs[0]
         if name != "zero":
-            what = ("the multi-class model" if self._is_multiclass else "the warped likelihood" if self._is_warped else
-                    "input-dependent flows (ID_TGP)" if any(getattr(fl, "input_dependent", False) for g in self.G_matrix
-                                                             for fl in getattr(g, "flow_arr", [])) else None)
+            what = likelihood.refuses_mean or ("input-dependent flows (ID_TGP)" if self._input_dependent else None)
             if what is not None:
                 raise NotImplementedError("the '%s' mean function is not built for %s: use the 'zero' mean" % (name, what))
         W = return_projection_matrix(self.inp_dim, self.out_dim, X.reshape(-1, self.inp_dim)) if name == "identity" else None
@@ -167,39 +148,24 @@ class sparse_MF_SP(nn.Module):
         return not isinstance(self.mean_function, ZeroMean)
 
     @property
-    def _is_bernoulli(self):
-        return isinstance(self.likelihood, Bernoulli)
+    def _input_dependent(self):
+        """A flow of the model has per-row parameters from a network on X (ID_TGP)."""
+        return any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", []))
 
     @property
-    def _is_poisson(self):
-        return isinstance(self.likelihood, Poisson)
-
-    @property
-    def _is_student(self):
-        return isinstance(self.likelihood, StudentT)
+    def _noise(self):
+        """What the ABI's noise pointer reads: the likelihood's noise, else the zero that no kernel reads (None: no such call)."""
+        return self.likelihood.noise() if self.likelihood.has_noise else getattr(self, "_bern_lvn", None)
 
     @property
     def _lik_id(self):
         """The `lik` of the ops calls: a lib.LIK_* for the likelihoods that are not told by the presence of a flow, else None."""
-        return (ops.L.LIK_BERNOULLI if self._is_bernoulli else ops.L.LIK_POISSON if self._is_poisson else
-                ops.L.LIK_STUDENT if self._is_student else ops.L.LIK_WARPED if self._is_warped else None)
-
-    @property
-    def _is_warped(self):
-        return isinstance(self.likelihood, WarpedGaussianLinearMean)
-
-    @property
-    def _is_multiclass(self):
-        return isinstance(self.likelihood, MulticlassCategorical)
-
-    @property
-    def _is_hetero(self):
-        return isinstance(self.likelihood, HeteroscedasticGaussian)
+        return self.likelihood.lik_id
 
     @property
     def _is_composed(self):
         """Several latent GPs: the step is composed per GP from the stand-alone pieces (_qf_per_class, per-GP KL)."""
-        return self._is_multiclass or self._is_hetero
+        return self.likelihood.composed
 
     def _gp_params(self, c=None, jitter=0.0, ladder=None, info=None):
         """What the whitened kernels consume: (Z, raw_ls, raw_os, m, Lam, lvn).  Whitened: the parameters themselves.
@@ -236,63 +202,70 @@ class sparse_MF_SP(nn.Module):
             D = self.inp_dim
             return (self.Z[c], k.base_kernel.raw_lengthscale.reshape(-1, D)[c], k.raw_outputscale.reshape(-1)[c:c + 1],
                     self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c], None)
-        lvn = self._bern_lvn if self._is_bernoulli or self._is_poisson else self.likelihood.log_var_noise.reshape(-1)[:1]
         return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.raw_outputscale.reshape(-1),
-                self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], lvn)
+                self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], self._noise)
+
+    def _qf_one(self, X2, c=None):
+        """(mu, v) of q(f) at the rows of X2 for latent GP c (None: the only one): tgp_qf_moments_f64, differentiable like the
+        reference's autograd through sparse_MF_SP.py:274-396 (tgp_qf_moments_bwd_f64, its own ladder from jitter 0: with an
+        unwhitened q(u) it ends where the transform's did, same matrix, same ladder) when a parameter needs it."""
+        info = {}
+        Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
+            return ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
+        return ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
+                              kernel=self.covariance_function.hip_kernel)
 
     def _qf_per_class(self, X2):
-        """(mu, v) of shape (C, MB): one tgp_qf_moments_f64 per latent GP, in class order on the current stream;
-        differentiable (tgp_qf_moments_bwd_f64) when a parameter needs it."""
-        mus, vs = [], []
-        for c in range(self.out_dim):
-            info = {}
-            Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
-            if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
-                mu, v = ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
-            else:
-                mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
-                                       kernel=self.covariance_function.hip_kernel)
-            mus.append(mu)
-            vs.append(v)
+        """(mu, v) of shape (C, MB): one _qf_one per latent GP, in class order on the current stream."""
+        mus, vs = zip(*(self._qf_one(X2, c) for c in range(self.out_dim)))
         return torch.stack(mus), torch.stack(vs)
 
-    def _elbo_multiclass(self, X2, Y, eps=None):
-        """ELL - sum_c KL_c (sparse_MF_SP.py:590-593) composed from the stand-alone differentiable pieces: per class the
-        q(f) moments and the KL, then ONE softmax likelihood launch over all classes.  Each class's row kernel runs twice,
-        once for the moments and once for their adjoint (the known cost of the composed step)."""
-        mu, v = self._qf_per_class(X2)
-        KLD = self.KLD()
-        X3 = X2.unsqueeze(0).expand(self.out_dim, -1, -1)
-        ELL = self.likelihood.expected_log_prob(Y.t(), mu, v, flow=self.G_matrix, X=X3, eps=eps, scale=self.N / Y.size(0)).sum()
-        KLD = KLD.sum()
-        return ELL - KLD, ELL, KLD
-
-    def _elbo_hetero(self, X2, Y):
-        """ELL - KL_f - KL_h composed as _elbo_multiclass: the q(f) and q(h) moments and the two KL terms from the stand-alone
-        differentiable pieces, then ONE heteroscedastic likelihood launch (tgp_ell_hetero_f64) that returns the adjoints of all
-        four moment vectors, c and the flow's parameters."""
+    def _elbo_composed(self, X2, Y):
+        """ELL - sum_c KL_c (sparse_MF_SP.py:590-593) of a model of several latent GPs (multi-class: C, heteroscedastic: f and h)
+        composed from the stand-alone differentiable pieces: per GP the q(f) moments and the KL, then ONE likelihood launch
+        over all of them (tgp_ell_softmax_f64 / tgp_ell_hetero_f64) that returns the adjoints of every moment vector, the
+        noise and the flows' parameters.  Each GP's row kernel runs twice, once for the moments and once for their adjoint
+        (the known cost of the composed step)."""
         mu, v = self._qf_per_class(X2)
         KLD = self.KLD().sum()
-        ELL = self.likelihood.expected_log_prob(Y.t(), mu, v, flow=self.G_matrix, X=X2.unsqueeze(0),
-                                                scale=self.N / Y.size(0)).sum()
+        X3 = X2.unsqueeze(0).expand(self.likelihood.flow_outputs, -1, -1)
+        ELL = self.likelihood.expected_log_prob(Y.t(), mu, v, flow=self.G_matrix, X=X3, scale=self.N / Y.size(0)).sum()
         return ELL - KLD, ELL, KLD
 
-    def _hetero_predict(self, X2, Y=None, Y_std=1.0):
-        """Eval-mode q(f), q(h) moments at the rows of X2 and ONE tgp_predict_hetero_f64 launch on them:
-        (m1 (1, N), m2 (1, N), logp (N,) or None, mean_q_f (2, N, 1), cov_q_f (2, N, 1)); no autograd."""
+    def _predict_rows(self, X2, Y=None, Y_std=1.0, want_moments=True, qf=None):
+        """The ONE predictive launch of the likelihood (ops.predict / predict_hetero / predict_softmax, by its predict_rows) at
+        the rows of X2: eval mode -> q(f) moments (or `qf`, already there) -> flow inputs -> launch -> train(); no autograd.
+        (m1, m2, logp or None, mean_q_f, cov_q_f), the first three as the likelihood shapes them.  A count model takes Y of
+        B * N entries: block b of the launch holds the counts Y[b * N:(b + 1) * N] against the same N rows, their moments
+        repeated B times (predictive_pmf); it has no input-dependent flow, so no MC-dropout mixture."""
+        count = self.likelihood.kind == "count"
+        if count and self.fully_bayesian:
+            raise NotImplementedError("a %s model has no input-dependent flows, so no fully Bayesian (MC-dropout) mode"
+                                      % self.likelihood.display)
         self._require_gpu(X2)
         self._eval_mode()
         with torch.no_grad():
-            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X2, diagonal=True, is_duvenaud=False)
-            res = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X2.unsqueeze(0),
-                                                   Y=None if Y is None else Y.reshape(-1).to(mean_q_f.dtype), Y_std=Y_std)
+            mean_q_f, cov_q_f = qf if qf is not None else self.marginal_variational_qf_parameters(X2, diagonal=True,
+                                                                                                  is_duvenaud=False)
+            spec, theta, rowp = self._flow_inputs(X2, with_grad=False)
+            mu, v = mean_q_f.squeeze(2), cov_q_f.squeeze(2)
+            if count and Y is not None:
+                B = Y.numel() // X2.shape[0]
+                assert B * X2.shape[0] == Y.numel(), "Y must hold a whole number of blocks of X's rows"
+                mu, v = mu.reshape(-1).repeat(B), v.reshape(-1).repeat(B)
+            lvn = self._noise
+            res = self.likelihood.predict_rows(mu, v, None if lvn is None else lvn.detach().contiguous(), spec,
+                                               theta.detach() if theta is not None else None, rowp,
+                                               Y=None if Y is None else Y.reshape(-1).to(mu.dtype), Y_std=Y_std,
+                                               want_moments=want_moments)
         self.train()
-        return res[0], res[1], (res[2] if Y is not None else None), mean_q_f, cov_q_f
+        return (*res, mean_q_f, cov_q_f)
 
     def predictive_noise_std(self, X, probs):
         """Quantiles of the noise standard deviation sqrt(exp(c + h(x))) under q(h) at the rows of X, shape (Q, N), in the
         model's standardised units: exp((c + mu_h + z_p sqrt(v_h)) / 2), closed form.  probs 0.5: the median noise level."""
-        if not self._is_hetero:
+        if not hasattr(self.likelihood, "noise_std"):
             raise NotImplementedError("predictive_noise_std: the heteroscedastic likelihood only; %s has one noise level"
                                       % type(self.likelihood).__name__)
         X2 = X[0] if X.dim() == 3 else X
@@ -309,17 +282,15 @@ class sparse_MF_SP(nn.Module):
         HIP kernel (dropout follows the nets' Dropout layers, as in the reference).  `samples` > 1 (fully Bayesian
         evaluation): the rows are evaluated `samples` times in ONE launch, rowp row s * N + n, every (sample, row) with
         its own dropout mask -- the reference's X.repeat to (S_MC, N, Dx), models/sparse_MF_SP.py:753-758."""
-        if self._is_warped:          # the likelihood's own flow, applied to the targets: shared parameters only
-            ctx = torch.enable_grad() if with_grad else torch.no_grad()
+        ctx = torch.enable_grad() if with_grad else torch.no_grad()
+        if self.likelihood.compiles_flows:     # the warp on the targets, the C flows of a multi-class model: shared parameters only
             with ctx:
-                spec, theta = self.likelihood._flow_inputs(X2d.device, with_grad=with_grad)
-            return spec, theta, None
-        if isinstance(self.likelihood, GaussianLinearMean):
+                return self.likelihood._flow_inputs(self.G_matrix, X2d, X2d.device, with_grad=with_grad)
+        if not self.likelihood.has_flow:
             return None, None, None
         spec, theta_list, nets = compile_flow(self.G_matrix[0])
-        ctx = torch.enable_grad() if with_grad else torch.no_grad()
         with ctx:
-            theta = torch.stack([p.reshape(()) for p in theta_list]) if theta_list else None
+            theta = stack_theta(theta_list, None, with_grad)
             rowp = None
             if nets:
                 if "mlp" not in self._cfg:
@@ -357,14 +328,11 @@ class sparse_MF_SP(nn.Module):
         gradients are enabled and a parameter requires them the call raises (diagonal=True is the differentiable path).
         MB <= 4096, single-output models only."""
         assert not is_duvenaud, "is_duvenaud=False on this path"
-        if not diagonal and self._is_hetero:
-            raise NotImplementedError("diagonal=False is not built for the heteroscedastic likelihood (HeteroscedasticGaussian: "
-                                      "two latent GPs)")
+        if not diagonal and self.likelihood.refuses_full_cov is not None:
+            raise NotImplementedError(self.likelihood.refuses_full_cov)
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         if not diagonal:
-            if self._is_multiclass:
-                raise NotImplementedError("diagonal=False is not built for multi-class models (num_outputs = C latent GPs)")
             info = {}
             Z, rl, ro, m, Lam, _ = self._gp_params(info=info)
             if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
@@ -382,15 +350,7 @@ class sparse_MF_SP(nn.Module):
         if self._is_composed:
             mu, v = self._qf_per_class(X2)
             return mu.unsqueeze(2), v.unsqueeze(2)
-        info = {}
-        Z, rl, ro, m, Lam, _ = self._gp_params(info=info)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
-            # differentiable like the reference's (autograd through :274-396): tgp_qf_moments_bwd_f64 in the backward
-            # (its own ladder from jitter 0: with an unwhitened q(u) it ends where the transform's did, same matrix, same ladder)
-            mu, v = ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
-        else:
-            mu, v = ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
-                                   kernel=self.covariance_function.hip_kernel)
+        mu, v = self._qf_one(X2)
         if self._has_mean:           # mu + m(X) (sparse_MF_SP.py:355,360): every method downstream of (mu, v) gets it from here
             if torch.is_grad_enabled() and (mu.requires_grad or any(q.requires_grad for q in self.mean_function.parameters())):
                 mu = mu + self.mean_function.vector(X2.detach())
@@ -398,37 +358,24 @@ class sparse_MF_SP(nn.Module):
                 mu = self.mean_function.vector(X2.detach(), inp=mu)
         return mu.reshape(1, -1, 1), v.reshape(1, -1, 1)
 
-    def _kld_unwhitened(self, c=None):
-        """KL(q(u) || p(u)) of sparse_MF_SP.py:433-453: p(u) = N(0, K_ZZ + j I) from add_jitter_MultivariateNormal, which adds
-        at least 1e-8 (ladder 1e-8 * 10^i, i < 5).  Equal to the whitened KL at unwhiten(m, L_q; j); differentiable in Z,
-        the kernel parameters, m and L_q."""
-        Z, rl, ro, m_w, Lam_w, _ = self._gp_params(c, jitter=ops.KL_PRIOR_JITTERS[0], ladder=ops.KL_PRIOR_JITTERS)
-        if torch.is_grad_enabled() and (m_w.requires_grad or Lam_w.requires_grad):
-            return ops.KlFunction.apply(m_w, Lam_w).reshape(())
-        return ops.kl_whitened(m_w.detach(), Lam_w.detach())[0].reshape(()).clone()
+    def _kl_one(self, c=None):
+        """KL(q(u) || p(u)) of latent GP c (None: the only one), 0-d.  Whitened (sparse_MF_SP.py:406-431): differentiable in
+        (m, L_q) like the reference's.  Unwhitened (:433-453): p(u) = N(0, K_ZZ + j I) from add_jitter_MultivariateNormal, which
+        adds at least 1e-8 (ladder 1e-8 * 10^i, i < 5); equal to the whitened KL at unwhiten(m, L_q; j) and differentiable in Z
+        and the kernel parameters too."""
+        if self.is_whiten:
+            m, Lam = self.q_U.variational_mean[c or 0], self.q_U.chol_variational_covar[c or 0]
+        else:
+            _, _, _, m, Lam, _ = self._gp_params(c, jitter=ops.KL_PRIOR_JITTERS[0], ladder=ops.KL_PRIOR_JITTERS)
+        if torch.is_grad_enabled() and (m.requires_grad or Lam.requires_grad):
+            return ops.KlFunction.apply(m, Lam).reshape(())
+        return ops.kl_whitened(m.detach(), Lam.detach())[0].reshape(())
 
     def KLD(self):
-        """KL(q(u) || p(u)), shape (Dy,): the whitened form (sparse_MF_SP.py:406-431), differentiable in (m, L_q) like the
-        reference's, or with is_whiten=False the KL against N(0, K_ZZ + j I) (:433-453), differentiable in Z and the kernel
-        parameters too."""
-        if not self.is_whiten:
-            if self._is_composed:
-                return torch.stack([self._kld_unwhitened(c) for c in range(self.out_dim)])
-            return self._kld_unwhitened().reshape(1)
+        """KL(q(u) || p(u)), shape (Dy,): one _kl_one per latent GP."""
         if self._is_composed:
-            kls = []
-            for c in range(self.out_dim):
-                m, Lam = self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c]
-                if torch.is_grad_enabled() and (m.requires_grad or Lam.requires_grad):
-                    kls.append(ops.KlFunction.apply(m, Lam).reshape(()))
-                else:
-                    kls.append(ops.kl_whitened(m.detach(), Lam.detach())[0].reshape(()).clone())
-            return torch.stack(kls)
-        m, Lam = self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0]
-        if torch.is_grad_enabled() and (m.requires_grad or Lam.requires_grad):
-            return ops.KlFunction.apply(m, Lam).reshape(1)
-        kl, _, _ = ops.kl_whitened(m.detach(), Lam.detach())
-        return kl.reshape(1)
+            return torch.stack([self._kl_one(c) for c in range(self.out_dim)])
+        return self._kl_one().reshape(1)
 
     def ELBO(self, X, Y, _qu_jitter=None):
         """Returns (ELBO, ELL, KLD): positive ELBO with autograd, the trainer negates (sparse_MF_SP.py:552-598).
@@ -436,13 +383,10 @@ class sparse_MF_SP(nn.Module):
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
-        if self._is_multiclass:
-            return self._elbo_multiclass(X2, Y)
-        if self._is_hetero:
+        if self._is_composed:
             assert _qu_jitter is None
-            return self._elbo_hetero(X2, Y)
-        if self._is_poisson:
-            self.likelihood.check_targets(Y)      # counts only (ValueError); the kernels themselves take any real >= 0
+            return self._elbo_composed(X2, Y)
+        self.likelihood.check_targets(Y)          # (a count model: counts only; the kernels themselves take any real >= 0)
         info = {}
         Z, rl, ro, m, Lam, lvn = self._gp_params(info=info)
         if _qu_jitter is not None:
@@ -451,8 +395,7 @@ class sparse_MF_SP(nn.Module):
         cfg = self._cfg
         cfg.update(N_total=self.N, flow=spec, S=self.quad_points, check_status=(cg.status_check == "always"),
                    global_jitter=cg.global_jitter, kernel=self.covariance_function.hip_kernel,
-                   lik=self._lik_id, df=self.likelihood.df if self._is_student else None,
-                   grad_Y=False)
+                   grad_Y=False, **self.likelihood.lik_kwargs())
         if self._has_mean:
             if spec is None:
                 # Gaussian likelihood: the unchanged closed-form step on Y - m(X); the step hands back the targets' adjoint
@@ -485,21 +428,9 @@ class sparse_MF_SP(nn.Module):
     def _qu_refusal(self):
         """Why this model has no closed-form optimal q(u), or None.  The closed form needs a likelihood that is Gaussian in f
         (on the targets themselves, on Y - m(X), or on the warped targets T(Y)) and the whitened parameterisation."""
-        if self._is_multiclass:
-            return "the multi-class (softmax) likelihood is not Gaussian in f: q(u) has no closed-form optimum"
-        if self._is_bernoulli:
-            return "the Bernoulli likelihood is not Gaussian in f: q(u) has no closed-form optimum"
-        if self._is_poisson:
-            return "the Poisson likelihood is not Gaussian in f: q(u) has no closed-form optimum"
-        if self._is_student:
-            return "the Student-t likelihood is not Gaussian in f: q(u) has no closed-form optimum"
-        if self._is_hetero:
-            return ("the heteroscedastic likelihood (HeteroscedasticGaussian) has two coupled latent GPs: neither q(u) has a "
-                    "closed-form optimum")
-        if not isinstance(self.likelihood, GaussianLinearMean):
-            if any(getattr(fl, "input_dependent", False) for g in self.G_matrix for fl in getattr(g, "flow_arr", [])):
-                return "input-dependent flows (ID_TGP) act on f: the likelihood is not Gaussian in f and q(u) has no closed-form optimum"
-            return "a flow on f (TGP) makes the likelihood non-Gaussian in f: q(u) has no closed-form optimum (SVGP and WGP have one)"
+        lik = self.likelihood
+        if lik.refuses_optimal_qu is not None:
+            return lik.refuses_optimal_qu_id if lik.refuses_optimal_qu_id is not None and self._input_dependent else lik.refuses_optimal_qu
         if not self.is_whiten:
             return "is_whiten=False: the closed form is built for the whitened q(u) only"
         return None
@@ -518,7 +449,7 @@ class sparse_MF_SP(nn.Module):
         with torch.no_grad():
             Z, rl, ro, _, _, lvn = self._raw_params()
             t = Y.detach().reshape(-1).contiguous()
-            if self._is_warped:
+            if self.likelihood.flow_on_targets:
                 spec, theta, _ = self._flow_inputs(X2, with_grad=False)
                 if spec.nblk > 0:
                     t = ops.flow_eval(t, spec, None if theta is None else theta.detach(), want=("G",))["G"]
@@ -549,8 +480,8 @@ class sparse_MF_SP(nn.Module):
     def ELL(self, X, Y, mean, cov):
         """N/MB * E_q(f)[log p(y|G(f))] from given moments (sparse_MF_SP.py:601-626); no autograd."""
         MB = Y.size(0)
-        if self._is_multiclass and X.dim() == 2:
-            X = X.unsqueeze(0).expand(self.out_dim, -1, -1)
+        if self._is_composed and X.dim() == 2:
+            X = X.unsqueeze(0).expand(self.likelihood.flow_outputs, -1, -1)
         ell = self.likelihood.expected_log_prob(Y.t(), mean.squeeze(dim=2), cov.squeeze(dim=2), flow=self.G_matrix, X=X)
         return self.N / MB * ell
 
@@ -562,12 +493,13 @@ class sparse_MF_SP(nn.Module):
     def predictive_distribution(self, X, diagonal: bool = True, S_MC_NNet: int = None):
         """m1, m2 (Dy, MB) + q(f) moments (sparse_MF_SP.py:457-540)."""
         assert not self.is_training, "This method only works in eval mode"
-        if self._is_hetero:
-            if not diagonal:
-                raise NotImplementedError("diagonal=False is not built for the heteroscedastic likelihood (two latent GPs)")
-            m1, m2, _, mean_q_f, cov_q_f = self._hetero_predict(X[0] if X.dim() == 3 else X)
-            return m1, m2, mean_q_f, cov_q_f
+        lik = self.likelihood
+        if not diagonal and lik.refuses_full_cov_predictive is not None:
+            raise NotImplementedError(lik.refuses_full_cov_predictive)
         assert diagonal
+        if lik.composed:             # the moments of all latent GPs into the likelihood's one launch
+            m1, m2, _, mean_q_f, cov_q_f = self._predict_rows(X[0] if X.dim() == 3 else X)
+            return m1, m2, mean_q_f, cov_q_f
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._eval_mode()
         with torch.no_grad():
@@ -579,24 +511,18 @@ class sparse_MF_SP(nn.Module):
                 # tgp_predict_f64 launch, then the mixture moments (:516-531)
                 S, MB = int(S_MC_NNet), X3.shape[1]
                 spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False, samples=S)
-                if self._is_bernoulli:
-                    # P of every (sample, row) in one tgp_predict_f64 launch, the MC mean per row (sparse_MF_SP.py:521-525)
-                    P, _, _ = ops.predict(mean_q_f.reshape(-1).repeat(S), cov_q_f.reshape(-1).repeat(S), self._bern_lvn, spec,
-                                          theta.detach() if theta is not None else None, self.quad_points, rowp,
-                                          lik=ops.L.LIK_BERNOULLI)
+                mY, cY, _ = ops.predict(mean_q_f.reshape(-1).repeat(S), cov_q_f.reshape(-1).repeat(S),
+                                        self._noise.detach().contiguous(), spec, theta.detach() if theta is not None else None,
+                                        self.quad_points, rowp, **lik.lik_kwargs())
+                if lik.kind == "classifier":     # P of every (sample, row), the MC mean per row (sparse_MF_SP.py:521-525)
                     self.train()
-                    return P.reshape(S, MB, 1).mean(0), None, mean_q_f, cov_q_f
-                lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
-                mY, cY, _ = ops.predict(mean_q_f.reshape(-1).repeat(S), cov_q_f.reshape(-1).repeat(S), lvn, spec,
-                                        theta.detach() if theta is not None else None, self.quad_points, rowp)
+                    return mY.reshape(S, MB, 1).mean(0), None, mean_q_f, cov_q_f
                 mY, cY = mY.reshape(1, S, MB), cY.reshape(1, S, MB)       # (Dy, S, MB)
                 m1 = mY.mean(1)
                 m2 = (cY + mY ** 2).mean(1) - m1 ** 2
-            elif self._is_bernoulli or self._is_multiclass:      # P(y = 1) of shape (MB, 1) / P of shape (MB, C)
-                m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X3), None
-            else:
-                m1, m2 = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), diagonal=True,
-                                                          flow=self.G_matrix, X=X3)
+            else:                    # (a classifier gives P(y = 1) of shape (MB, 1) alone)
+                res = lik.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), diagonal=True, flow=self.G_matrix, X=X3)
+                m1, m2 = (res, None) if lik.kind == "classifier" else res
         self.train()
         return m1, m2, mean_q_f, cov_q_f
 
@@ -606,23 +532,19 @@ class sparse_MF_SP(nn.Module):
         MB = X.size(0)
         X3 = X.repeat(self.out_dim, 1, 1) if X.dim() == 2 else X
         self._require_gpu(X3)
-        if self._is_hetero:
-            # sum_n log p(y_n | x_n), the exact log predictive density of the raw targets under the S x S product rule (every
-            # constant, -log Y_std), with [m1, m2] from the same tgp_predict_hetero_f64 launch
-            m1, m2, lp, _, _ = self._hetero_predict(X3[0], Y, float(Y_std.reshape(-1)[0]))
-            return lp.sum().reshape(1), ([m1, m2] if return_moments else None)
-        if self._is_multiclass:
-            # sum_n log P[n, y_n] in float64, P and its logarithm from one tgp_predict_softmax_f64 launch (the reference goes
-            # through float32 and compute_calibration_measures)
-            self._eval_mode()
-            with torch.no_grad():
-                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=False)
-                P, lp = self.likelihood.marginal_moments(mean_q_f.squeeze(2), cov_q_f.squeeze(2), flow=self.G_matrix, X=X3,
-                                                         Y=Y.reshape(-1).to(mean_q_f.dtype))
-            assert torch.isfinite(lp).all(), "Got saturated probabilities"
-            self.train()
-            return lp.sum().reshape(1), ([P] if return_moments else None)
-        if self._is_bernoulli:
+        lik = self.likelihood
+        if lik.one_launch_logp:
+            # sum_n log p(y_n | x_n) with [m1, m2] from the same launch: the exact log predictive density of the raw targets,
+            # every constant and -log Y_std (Student-t; heteroscedastic: under the S x S product rule), the log predictive pmf
+            # of the observed counts (Poisson: counts have no scale, Y_std is not used), log P[n, y_n] in float64 (multi-class:
+            # the reference goes through float32 and compute_calibration_measures)
+            ystd = float(Y_std.reshape(-1)[0]) if lik.kind == "regression" else 1.0
+            m1, m2, lp, _, _ = self._predict_rows(X3[0], Y, ystd, want_moments=return_moments)
+            assert lik.kind != "classifier" or torch.isfinite(lp).all(), "Got saturated probabilities"
+            if not return_moments:
+                return lp.sum().reshape(1), None
+            return lp.sum().reshape(1), ([m1] if m2 is None else [m1.reshape(1, MB), m2.reshape(1, MB)])
+        if lik.kind == "classifier":
             # sum_n y log P + (1 - y) log(1 - P) in float64 (the reference takes it through float32 and
             # compute_calibration_measures), P as predictive_distribution returns it (MC mean when fully Bayesian)
             P, _, _, _ = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
@@ -634,98 +556,50 @@ class sparse_MF_SP(nn.Module):
                     torch.where(y != 1, (1 - y) * torch.log1p(-P), torch.zeros_like(P))
             self.train()
             return lp.sum().reshape(1), ([torch.stack((1.0 - P, P), dim=1)] if return_moments else None)
-        if self._is_poisson:
-            # sum_n log p(y_n | x_n), the log predictive pmf of the observed counts, with [m1, m2] from the same launch; counts
-            # have no scale: Y_std is not used (no log Y_std is subtracted)
-            lp, m1, m2 = self._poisson_predict(X3[0], Y.reshape(-1), want_moments=return_moments)
-            return lp.sum().reshape(1), ([m1.reshape(1, MB), m2.reshape(1, MB)] if return_moments else None)
-        if self._is_student:
-            # sum_n log p(y_n | x_n), the exact log predictive density of the raw targets (every constant, -log Y_std), with
-            # [m1, m2] from the same tgp_predict_f64 launch
-            self._eval_mode()
-            with torch.no_grad():
-                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=False)
-                spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False)
-                m1, m2, lp = ops.predict(mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous(),
-                                         self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous(), spec,
-                                         theta.detach() if theta is not None else None, self.quad_points, rowp,
-                                         Y=Y.reshape(-1).to(mean_q_f.dtype), Y_std=float(Y_std.reshape(-1)[0]),
-                                         lik=ops.L.LIK_STUDENT, df=self.likelihood.df, want_moments=return_moments)
-            self.train()
-            return lp.sum().reshape(1), ([m1.reshape(1, MB), m2.reshape(1, MB)] if return_moments else None)
-        predictive_params = None
+        predictive_params, qf = None, None
         if return_moments:
-            m1, m2, mean_q_f, cov_q_f = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
+            m1, m2, *qf = self.predictive_distribution(X3, diagonal=True, S_MC_NNet=S_MC_NNet)
             predictive_params = [m1, m2]
-        else:
-            self._eval_mode()
-            with torch.no_grad():
-                mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X3, diagonal=True, is_duvenaud=False)
-        self._eval_mode()
         ystd = float(Y_std.reshape(-1)[0])
-        mu, v = mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous()
-        lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
+        if lik.refuses_optimal_qu is None:
+            # Gaussian in f, on the targets or on the warped ones: log N(y | mu, v + s2), or the exact warped predictive density
+            # log N(T(y) | mu, v + s2) + log T'(y), - log Y_std, summed over the rows (the reference's branch for the warped class
+            # would give log N(y | m1, m2): DESIGN.md 8; its moments cost S flow inversions per row and are not asked for again)
+            lp = self._predict_rows(X3[0], Y, ystd, want_moments=not lik.flow_on_targets, qf=qf)[2]
+            return lp.sum().reshape(1), predictive_params
+        self._eval_mode()
         with torch.no_grad():
-            if self._is_warped:
-                # the exact warped predictive density log N(T(y) | mu, v + s2) + log T'(y) - log Y_std, summed over the rows
-                # (the reference's branch for this class would give log N(y | m1, m2): DESIGN.md 8)
-                spec, theta, _ = self._flow_inputs(X3[0], with_grad=False)
-                _, _, lp = ops.predict(mu, v, lvn, spec, theta, self.quad_points, Y=Y, Y_std=ystd, lik=ops.L.LIK_WARPED,
-                                       want_moments=False)
-                log_p_y = lp.sum().reshape(1)
-            elif isinstance(self.likelihood, GaussianLinearMean):
-                _, _, lp = ops.predict(mu, v, lvn, Y=Y, Y_std=ystd)
-                log_p_y = lp.sum().reshape(1)
+            mean_q_f, cov_q_f = qf if qf is not None else self.marginal_variational_qf_parameters(X3, diagonal=True,
+                                                                                                  is_duvenaud=False)
+            mu, v = mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous()
+            lvn = self.likelihood.log_var_noise.detach().reshape(-1)[:1].contiguous()
+            # S_MC dropout samples (fully Bayesian) in ONE pass: the nets over S_MC * N rows, one tgp_predict_f64
+            # launch over the same rows (sparse_MF_SP.py:753-768 expands X, Y the same way)
+            n_mc = int(S_MC_NNet) if self.fully_bayesian else 1
+            spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False, samples=n_mc)
+            rep = (lambda t: t.repeat(n_mc)) if n_mc > 1 else (lambda t: t)
+            _, _, lp = ops.predict(rep(mu), rep(v), lvn, spec, theta.detach() if theta is not None else None,
+                                   self.quad_points, rowp, Y=rep(Y.reshape(-1)), Y_std=ystd)
+            # kernel: logsumexp_s[log(w_s/sqrt(pi)) + logN]; the reference sums log w_s + logN and subtracts
+            # 0.5*log(pi) where cg.pi is a float32 tensor (sparse_MF_SP.py:768-776): rebuild exactly that
+            lp = lp.reshape(n_mc, MB) + 0.5 * float(numpy.log(numpy.pi))
+            # float32 arithmetic of the reference's constant, with the correctly rounded float32 log(pi) (a host
+            # torch.log in float32 differs by 1 ulp between CPU ISAs, which would make the result host-dependent)
+            log_pi32 = numpy.log(numpy.float32(numpy.pi))
+            if self.fully_bayesian:
+                stack = lp - float(numpy.float32(0.5) * log_pi32)
+                log_p_y = (torch.logsumexp(stack, 0).sum() - MB * numpy.log(n_mc)).reshape(1)
             else:
-                # S_MC dropout samples (fully Bayesian) in ONE pass: the nets over S_MC * N rows, one tgp_predict_f64
-                # launch over the same rows (sparse_MF_SP.py:753-768 expands X, Y the same way)
-                n_mc = int(S_MC_NNet) if self.fully_bayesian else 1
-                spec, theta, rowp = self._flow_inputs(X3[0], with_grad=False, samples=n_mc)
-                rep = (lambda t: t.repeat(n_mc)) if n_mc > 1 else (lambda t: t)
-                _, _, lp = ops.predict(rep(mu), rep(v), lvn, spec, theta.detach() if theta is not None else None,
-                                       self.quad_points, rowp, Y=rep(Y.reshape(-1)), Y_std=ystd)
-                # kernel: logsumexp_s[log(w_s/sqrt(pi)) + logN]; the reference sums log w_s + logN and subtracts
-                # 0.5*log(pi) where cg.pi is a float32 tensor (sparse_MF_SP.py:768-776): rebuild exactly that
-                lp = lp.reshape(n_mc, MB) + 0.5 * float(numpy.log(numpy.pi))
-                # float32 arithmetic of the reference's constant, with the correctly rounded float32 log(pi) (a host
-                # torch.log in float32 differs by 1 ulp between CPU ISAs, which would make the result host-dependent)
-                log_pi32 = numpy.log(numpy.float32(numpy.pi))
-                if self.fully_bayesian:
-                    stack = lp - float(numpy.float32(0.5) * log_pi32)
-                    log_p_y = (torch.logsumexp(stack, 0).sum() - MB * numpy.log(n_mc)).reshape(1)
-                else:
-                    log_p_y = (lp[0].sum() - float(numpy.float32(0.5 * MB) * log_pi32)).reshape(1)
+                log_p_y = (lp[0].sum() - float(numpy.float32(0.5 * MB) * log_pi32)).reshape(1)
         self.train()
         return log_p_y, predictive_params
 
     # ---- count models: the predictive pmf -----------------------------------------------------------------
-    def _poisson_predict(self, X2, Y, want_moments=True):
-        """ONE tgp_predict_f64 launch of a Poisson model over B blocks of the N rows of X2, block b with the counts
-        Y[b * N:(b + 1) * N] (the q(f) moments repeated B times): (logp (B * N,), m1 (N,), m2 (N,)), the moments None unless
-        asked for.  Eval mode, no autograd.  A Poisson model has no input-dependent flow, so there are no per-row parameters
-        (a mean function is part of mu) and no MC-dropout mixture."""
-        if self.fully_bayesian:
-            raise NotImplementedError("a Poisson model has no input-dependent flows, so no fully Bayesian (MC-dropout) mode")
-        self._require_gpu(X2)
-        N = X2.shape[0]
-        B = Y.numel() // N
-        assert B * N == Y.numel(), "Y must hold a whole number of blocks of X's rows"
-        self._eval_mode()
-        with torch.no_grad():
-            mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X2.unsqueeze(0), diagonal=True, is_duvenaud=False)
-            spec, theta, rowp = self._flow_inputs(X2, with_grad=False)
-            assert rowp is None
-            m1, m2, lp = ops.predict(mean_q_f.reshape(-1).repeat(B), cov_q_f.reshape(-1).repeat(B), self._bern_lvn, spec,
-                                     theta.detach() if theta is not None else None, self.quad_points, None,
-                                     Y=Y.to(mean_q_f.dtype), lik=ops.L.LIK_POISSON, want_moments=want_moments)
-        self.train()
-        return (lp, m1[:N], m2[:N]) if want_moments else (lp, None, None)
-
     def predictive_pmf(self, X, kmax: int):
         """The predictive pmf of a count model at the rows of X (N, Dx): P of shape (N, kmax + 1), P[n, k] = p(y_n = k | x_n),
         the exponential of tgp_predict_f64's log pmf from one launch over N (kmax + 1) rows (block k asks for the count k).
         Rows sum to 1 once kmax is past the mass; P.cumsum(1) is the predictive CDF, from which count intervals are read."""
-        if not self._is_poisson:
+        if self.likelihood.kind != "count":
             raise NotImplementedError("predictive_pmf: a count likelihood (Poisson) only; %s models have predictive_quantiles "
                                       "or class probabilities" % type(self.likelihood).__name__)
         assert X.dim() == 2, "Invalid input X.shape"
@@ -733,43 +607,26 @@ class sparse_MF_SP(nn.Module):
         assert kmax >= 0, "kmax must be >= 0"
         N = X.shape[0]
         k = torch.arange(kmax + 1, dtype=X.dtype, device=X.device).repeat_interleave(N)
-        lp, _, _ = self._poisson_predict(X, k, want_moments=False)
+        lp = self._predict_rows(X, k, want_moments=False)[2]       # block k of the launch asks for the count k
         return torch.exp(lp).reshape(kmax + 1, N).t().contiguous()
 
     # ---- exact quantiles and CDF of the predictive / posterior marginals -----------------------------------
     def _quantile_inputs(self, X, what):
         """Eval-mode q(f) moments (mu, v of shape (N,)), the noise and the flow inputs of the rows of X, under no_grad."""
-        if what == "predictive_crps":        # (its own reasons; the existing values of `what` below are unchanged)
-            name = type(self.likelihood).__name__
-            if self._is_bernoulli or self._is_multiclass:
+        lik, name = self.likelihood, type(self.likelihood).__name__
+        if what == "predictive_crps":        # (its own reasons; the other values of `what` have theirs below)
+            if lik.kind == "classifier":
                 raise NotImplementedError("predictive_crps: a %s model predicts classes, which have no CRPS" % name)
-            why = None
-            if self._is_student:
-                why = "the Student-t likelihood (%s) has no closed pair term E|Y - Y'| for a mixture of t densities" % name
-            elif self._is_hetero:
-                why = ("the heteroscedastic likelihood (%s) is a double mixture with unequal variances, whose pair term is not "
-                       "built" % name)
-            elif self._is_warped:
-                why = "the warped predictive (%s) is not a Gaussian mixture in y, so it has no closed pair term" % name
-            elif self.fully_bayesian:
+            why = lik.refuses_crps % name if lik.refuses_crps is not None else None
+            if why is None and self.fully_bayesian:
                 why = "the fully Bayesian model is an MC-dropout mixture over parameter draws, which the kernel does not sum"
             if why is not None:
                 raise NotImplementedError("predictive_crps: %s; pass samples=S for the sampled estimator "
                                           "(ops.crps_from_samples of S predictive draws)" % why)
-        if self._is_bernoulli or self._is_multiclass:
-            raise NotImplementedError("%s: a %s model has no quantiles" % (what, type(self.likelihood).__name__))
-        if self._is_poisson and what != "posterior_quantiles":
-            raise NotImplementedError("%s: the predictive of a Poisson model is discrete; predictive_pmf(X, kmax) gives its pmf "
-                                      "(cumsum: the CDF) and posterior_quantiles the quantiles of the log-rate" % what)
-        if self._is_student and what != "posterior_quantiles":
-            raise NotImplementedError("%s: the CDF of a Student-t predictive needs the incomplete beta function, which is not "
-                                      "built; use the sampled intervals (sample_from_predictive_distribution), or "
-                                      "posterior_quantiles for the quantiles of G(f)" % what)
-        if self._is_hetero and what != "posterior_quantiles":
-            raise NotImplementedError("%s: the exact CDF and quantiles of the heteroscedastic likelihood's double mixture "
-                                      "(HeteroscedasticGaussian) are not built; use the sampled intervals "
-                                      "(sample_from_predictive_distribution), posterior_quantiles for G(f) or "
-                                      "predictive_noise_std for the noise level" % what)
+        if lik.kind == "classifier":
+            raise NotImplementedError("%s: a %s model has no quantiles" % (what, name))
+        if lik.refuses_cdf is not None and what != "posterior_quantiles":
+            raise NotImplementedError(lik.refuses_cdf % what)
         if self.fully_bayesian:
             raise NotImplementedError("%s: the fully Bayesian model (an MC-dropout mixture over parameter draws) is out of "
                                       "scope; use the sampled intervals" % what)
@@ -778,10 +635,10 @@ class sparse_MF_SP(nn.Module):
         with torch.no_grad():
             mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X.repeat(self.out_dim, 1, 1), diagonal=True,
                                                                         is_duvenaud=False)
-            if self._is_hetero:      # output 0: f, the latent GP that goes through the flow
-                mean_q_f, cov_q_f = mean_q_f[:1], cov_q_f[:1]
+            # (of two latent GPs, output 0: f, the one that goes through the flow)
+            mean_q_f, cov_q_f = mean_q_f[:lik.flow_outputs], cov_q_f[:lik.flow_outputs]
             spec, theta, rowp = self._flow_inputs(X, with_grad=False)
-        lvn = self._raw_params()[5].detach().reshape(-1)[:1].contiguous()
+        lvn = self._noise.detach().reshape(-1)[:1].contiguous()
         theta = theta.detach() if theta is not None else None
         return mean_q_f.reshape(-1).contiguous(), cov_q_f.reshape(-1).contiguous(), lvn, spec, theta, rowp
 
@@ -791,7 +648,7 @@ class sparse_MF_SP(nn.Module):
         T^-1(mu + zq sqrt(v + noise)).  probs: any order, each strictly inside (0, 1)."""
         mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "predictive_quantiles")
         with torch.no_grad():
-            if self._is_warped:
+            if self.likelihood.flow_on_targets:
                 _, zq = ops.quantile_probs(probs, mu.device)
                 t = mu.unsqueeze(0) + zq.unsqueeze(1) * torch.sqrt(v.clamp_min(0.0) + torch.exp(lvn)).unsqueeze(0)
                 q, _ = ops.flow_inverse(t, spec, theta)
@@ -807,7 +664,7 @@ class sparse_MF_SP(nn.Module):
         with torch.no_grad():
             _, zq = ops.quantile_probs(probs, mu.device)
             f = mu.unsqueeze(0) + zq.unsqueeze(1) * torch.sqrt(v.clamp_min(0.0)).unsqueeze(0)
-            if spec is not None and spec.nblk > 0 and not self._is_warped:
+            if spec is not None and spec.nblk > 0 and not self.likelihood.flow_on_targets:
                 f = ops.flow_eval(f.contiguous(), spec, theta, rowp, want=("G",))["G"]
         self.train()
         return f.unsqueeze(0)
@@ -818,7 +675,7 @@ class sparse_MF_SP(nn.Module):
         mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "predictive_cdf")
         with torch.no_grad():
             y = Y.reshape(-1).to(mu.dtype)
-            if self._is_warped:
+            if self.likelihood.flow_on_targets:
                 t = ops.flow_eval(y.contiguous(), spec, theta, want=("G",))["G"] if spec.nblk > 0 else y
                 cdf, _ = ops.predict_cdf(mu, v, lvn, t)
             else:
@@ -834,8 +691,9 @@ class sparse_MF_SP(nn.Module):
         for predictive_pmf (past the mass the terms are 0).  samples=S: ops.crps_from_samples of S draws of
         sample_from_predictive_distribution, for any regression model.  Without it Student-t, heteroscedastic, warped and fully
         Bayesian models raise NotImplementedError; Bernoulli and multi-class models always do."""
-        exact = samples is None and not self._is_poisson
-        if exact or self._is_bernoulli or self._is_multiclass:
+        count = self.likelihood.kind == "count"
+        exact = samples is None and not count
+        if exact or self.likelihood.kind == "classifier":
             ins = self._quantile_inputs(X, "predictive_crps")       # (the refusals; classifiers are refused on every route)
         y = Y.reshape(-1)
         if samples is not None:
@@ -846,7 +704,7 @@ class sparse_MF_SP(nn.Module):
             finally:
                 self.set_is_training(was)
             out = ops.crps_from_samples(draws[0, :, :, 0], y.to(draws.dtype)).unsqueeze(0)
-        elif self._is_poisson:
+        elif count:
             if kmax is None:
                 raise ValueError("predictive_crps of a Poisson model needs kmax, the last count of the sum (predictive_pmf's)")
             cdf = self.predictive_pmf(X, kmax).cumsum(1)                                       # (N, kmax + 1)
@@ -915,11 +773,8 @@ class sparse_MF_SP(nn.Module):
         4096-row cap.  The draw is fixed at the current parameters (detached copies).  `generator`: a seeded CPU torch.Generator
         behind the frequencies and the normals.  Unwhitened models go through the transform of `_gp_params`, as for the full
         covariance."""
-        if self._is_multiclass:
-            raise NotImplementedError("posterior_paths is not built for multi-class models (num_outputs = C latent GPs)")
-        if self._is_hetero:
-            raise NotImplementedError("posterior_paths is not built for the heteroscedastic likelihood (HeteroscedasticGaussian: "
-                                      "two latent GPs)")
+        if self.likelihood.refuses_paths is not None:
+            raise NotImplementedError(self.likelihood.refuses_paths)
         if self.fully_bayesian:
             raise NotImplementedError("posterior_paths is not built for be_fully_bayesian models: the MC-dropout flows have "
                                       "no fixed per-row parameters, so a draw would not be one function")
@@ -939,7 +794,7 @@ class sparse_MF_SP(nn.Module):
         with torch.no_grad():
             f_k, _, _, f_0 = self.sample_from_variational_marginal(X, S, diagonal=diagonal, is_duvenaud=False)
             # (the heteroscedastic likelihood has ONE observed output, drawn from both latent rows of f_k)
-            samples = [self.likelihood.sample_from_output(f_k, i).view(S, N, 1) for i in range(1 if self._is_hetero else self.out_dim)]
+            samples = [self.likelihood.sample_from_output(f_k, i).view(S, N, 1) for i in range(self.likelihood.observed_outputs)]
         self.train()
         return torch.stack(samples, dim=0), f_k, f_0
 

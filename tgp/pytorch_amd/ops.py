@@ -1003,21 +1003,24 @@ def _flow_model(N, S, flow, theta, lvn, dev, scale=1.0, lik=None):
     return md, (xs, wn)
 
 
-def _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, lik):
-    """tgp_ell_flow_f64 for either quadrature likelihood: dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp)."""
+def _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, lik, entry="tgp_ell_flow_f64", rows=None):
+    """One quadrature ELL launch, `entry` at likelihood `lik`: dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp).  `rows`: mu and v
+    hold the moments of that many latent GPs, shape (rows, N), and so do g_mu and g_v (None: one GP, shape (N,))."""
     lib = L.load()
     Y, mu, v, lvn = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     dev, N = Y.device, Y.numel()
+    if rows is not None and (tuple(mu.shape) != (rows, N) or tuple(v.shape) != (rows, N)):
+        raise L.TgpError("%s: mu and v must be (%d, N) = (%d, %d), got %s and %s"
+                         % (entry[4:-4], rows, rows, N, tuple(mu.shape), tuple(v.shape)))
     md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=lik)
     ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
     out = torch.empty(2, dtype=torch.float64, device=dev)
     gmu, gv = torch.empty_like(mu), torch.empty_like(v)
     gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
     grp = torch.empty_like(rowp) if rowp is not None else None
-    L.check(lib.tgp_ell_flow_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
-                                 L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
-            "tgp_ell_flow_f64")
+    L.check(getattr(lib, entry)(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
+                                L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()), entry)
     return {"ell": out[0], "g_lvn": out[1], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "g_rowp": grp}
 
 
@@ -1047,40 +1050,6 @@ def _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, lik):
     return res
 
 
-class EllNoiselessFunction(torch.autograd.Function):
-    """ELL of a quadrature likelihood without a noise parameter, `lik` = LIK_BERNOULLI (Bernoulli.expected_log_prob,
-    likelihoods/Bernoulli.py) or LIK_POISSON, with autograd in (mu, v, theta, rowp)."""
-
-    @staticmethod
-    def forward(ctx, Y, mu, v, theta, rowp, flow, S, lik):
-        res = _ell_noiseless(Y, mu.detach(), v.detach(), flow, theta.detach() if theta is not None else None, S,
-                             rowp.detach() if rowp is not None else None, 1.0, lik)
-        ctx.save_for_backward(res["g_mu"], res["g_v"], res["g_theta"],
-                              res["g_rowp"] if res["g_rowp"] is not None else res["g_mu"])
-        ctx.has = (theta is not None, rowp is not None)
-        return res["ell"].reshape(1)
-
-    @staticmethod
-    def backward(ctx, g):
-        gmu, gv, gth, grp = ctx.saved_tensors
-        g = g.reshape(())
-        return (None, g * gmu, g * gv, g * gth if ctx.has[0] else None, g * grp if ctx.has[1] else None, None, None, None)
-
-
-class _EllOf:
-    """`apply(Y, mu, v, theta, rowp, flow, S)` of EllNoiselessFunction at one likelihood."""
-
-    def __init__(self, lik):
-        self.lik = lik
-
-    def apply(self, Y, mu, v, theta, rowp, flow, S):
-        return EllNoiselessFunction.apply(Y, mu, v, theta, rowp, flow, S, self.lik)
-
-
-EllBernoulliFunction = _EllOf(L.LIK_BERNOULLI)
-EllPoissonFunction = _EllOf(L.LIK_POISSON)
-
-
 def ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp=None, scale=1.0):
     """Student-t quadrature ELL with gradients: scale sum_n E_q(f0)[log StudentT(y_n | df, loc = G(f0), scale = sigma)], lvn =
     log sigma^2 (tgp_ell_flow_f64 with TGP_LIK_STUDENT).  Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp); g_lvn =
@@ -1088,73 +1057,17 @@ def ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp=None, scale=1.0):
     return _ell_quad(Y, mu, v, student_noise(lvn, df), flow, theta, S, rowp, scale, L.LIK_STUDENT)
 
 
-class EllStudentFunction(torch.autograd.Function):
-    """ELL of the Student-t likelihood with autograd in (mu, v, log_var_noise, theta, rowp) and none in `df`."""
-
-    @staticmethod
-    def forward(ctx, Y, mu, v, lvn, df, theta, rowp, flow, S):
-        res = ell_student(Y, mu.detach(), v.detach(), lvn.detach(), df, flow, theta.detach() if theta is not None else None, S,
-                          rowp.detach() if rowp is not None else None)
-        ctx.save_for_backward(res["g_lvn"], res["g_mu"], res["g_v"], res["g_theta"],
-                              res["g_rowp"] if res["g_rowp"] is not None else res["g_lvn"])
-        ctx.has = (theta is not None, rowp is not None)
-        ctx.lvn_shape = lvn.shape
-        return res["ell"].reshape(1)
-
-    @staticmethod
-    def backward(ctx, g):
-        g_lvn, gmu, gv, gth, grp = ctx.saved_tensors
-        g = g.reshape(())
-        return (None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), None, g * gth if ctx.has[0] else None,
-                g * grp if ctx.has[1] else None, None, None)
-
-
 def ell_hetero(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     """Heteroscedastic Gaussian ELL with gradients, y ~ N(G(f), exp(lvn + h)): mu, v of shape (2, N), row 0 the moments of q(f),
     row 1 those of the log-noise GP q(h), which integrates out in closed form (tgp_ell_hetero_f64, one launch).  `flow` a
     FlowSpec (an empty one for the identity flow).  Returns ell_student's dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp) -- g_mu,
     g_v the row-0 adjoints, g_lvn = dELL/dlvn -- plus g_mu_h, g_v_h, the row-1 adjoints (views of the same (2, N) buffers)."""
-    lib = L.load()
     if flow is None:
         raise L.TgpError("the heteroscedastic likelihood needs a FlowSpec (an empty one for the identity flow)")
-    Y, mu, v, lvn = _c(Y.reshape(-1), "Y"), _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
-    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
-    dev, N = Y.device, Y.numel()
-    if tuple(mu.shape) != (2, N) or tuple(v.shape) != (2, N):
-        raise L.TgpError("ell_hetero: mu and v must be (2, N) = (2, %d), got %s and %s" % (N, tuple(mu.shape), tuple(v.shape)))
-    md, keep = _flow_model(N, S, flow, theta, lvn, dev, scale, lik=L.LIK_HETERO)
-    ws = torch.empty(lib.tgp_ell_workspace_bytes(N, flow.P, md.RP) // 8 + 16, dtype=torch.float64, device=dev)
-    out = torch.empty(2, dtype=torch.float64, device=dev)
-    gmu, gv = torch.empty_like(mu), torch.empty_like(v)
-    gth = torch.empty(max(flow.P, 1), dtype=torch.float64, device=dev)
-    grp = torch.empty_like(rowp) if rowp is not None else None
-    L.check(lib.tgp_ell_hetero_f64(md, L.ptr(Y), L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(out), L.ptr(gmu), L.ptr(gv),
-                                   L.ptr(gth), L.ptr(grp), L.ptr(ws), ws.numel() * 8, L.stream_ptr()),
-            "tgp_ell_hetero_f64")
-    return {"ell": out[0], "g_lvn": out[1], "g_mu": gmu[0], "g_v": gv[0], "g_theta": gth[:flow.P], "g_rowp": grp,
-            "g_mu_h": gmu[1], "g_v_h": gv[1]}
-
-
-class EllHeteroFunction(torch.autograd.Function):
-    """ELL of the heteroscedastic Gaussian likelihood with autograd in (mu, v, log_var_noise, theta, rowp); mu, v (2, N).  Value
-    and every gradient come from one launch; `scale` multiplies them inside it."""
-
-    @staticmethod
-    def forward(ctx, Y, mu, v, lvn, theta, rowp, flow, S, scale):
-        res = ell_hetero(Y, mu.detach(), v.detach(), lvn.detach(), flow, theta.detach() if theta is not None else None, S,
-                         rowp.detach() if rowp is not None else None, scale=scale)
-        gmu, gv = torch.stack((res["g_mu"], res["g_mu_h"])), torch.stack((res["g_v"], res["g_v_h"]))
-        ctx.save_for_backward(res["g_lvn"], gmu, gv, res["g_theta"], res["g_rowp"] if res["g_rowp"] is not None else res["g_lvn"])
-        ctx.has = (theta is not None, rowp is not None)
-        ctx.lvn_shape = lvn.shape
-        return res["ell"].reshape(1)
-
-    @staticmethod
-    def backward(ctx, g):
-        g_lvn, gmu, gv, gth, grp = ctx.saved_tensors
-        g = g.reshape(())
-        return (None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has[0] else None,
-                g * grp if ctx.has[1] else None, None, None, None)
+    res = _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_HETERO, entry="tgp_ell_hetero_f64", rows=2)
+    gmu, gv = res["g_mu"], res["g_v"]
+    res.update(g_mu=gmu[0], g_v=gv[0], g_mu_h=gmu[1], g_v_h=gv[1])
+    return res
 
 
 def predict_hetero(mu, v, lvn, flow, theta=None, S=None, rowp=None, Y=None, Y_std=1.0, want_moments=True):
@@ -1179,47 +1092,6 @@ def predict_hetero(mu, v, lvn, flow, theta=None, S=None, rowp=None, Y=None, Y_st
     return m1, m2, logp
 
 
-class EllGaussFunction(torch.autograd.Function):
-    """ELL = GaussianLinearMean.expected_log_prob (likelihoods/GaussianLinearMean.py:60-87) with autograd in (mu, v,
-    log_var_noise) -- the reference's method is plain torch code, differentiable wherever it is called; tgp_ell_gauss_f64
-    returns the value and every gradient in one launch."""
-
-    @staticmethod
-    def forward(ctx, Y, mu, v, lvn):
-        ell, g_lvn, gmu, gv = ell_gauss(Y, mu.detach(), v.detach(), lvn.detach())
-        ctx.save_for_backward(g_lvn, gmu, gv)
-        ctx.lvn_shape = lvn.shape
-        return ell.reshape(1)
-
-    @staticmethod
-    def backward(ctx, g):
-        g_lvn, gmu, gv = ctx.saved_tensors
-        g = g.reshape(())
-        return None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape)
-
-
-class EllFlowFunction(torch.autograd.Function):
-    """ELL = GaussianNonLinearMean.expected_log_prob (likelihoods/GaussianNonLinearMean.py:64-150) with autograd in (mu, v,
-    log_var_noise, theta, rowp): tgp_ell_flow_f64 returns all of them."""
-
-    @staticmethod
-    def forward(ctx, Y, mu, v, lvn, theta, rowp, flow, S):
-        res = ell_flow(Y, mu.detach(), v.detach(), lvn.detach(), flow, theta.detach() if theta is not None else None, S,
-                       rowp.detach() if rowp is not None else None)
-        ctx.save_for_backward(res["g_lvn"], res["g_mu"], res["g_v"], res["g_theta"],
-                              res["g_rowp"] if res["g_rowp"] is not None else res["g_lvn"])
-        ctx.has = (theta is not None, rowp is not None)
-        ctx.lvn_shape = lvn.shape
-        return res["ell"].reshape(1)
-
-    @staticmethod
-    def backward(ctx, g):
-        g_lvn, gmu, gv, gth, grp = ctx.saved_tensors
-        g = g.reshape(())
-        return (None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has[0] else None,
-                g * grp if ctx.has[1] else None, None, None)
-
-
 def ell_warp(Y, mu, v, lvn, flow, theta, scale=1.0, want_t=False):
     """Warped-GP ELL with gradients (likelihoods/WarpedGaussianLinearMean.py:65-85; tgp_ell_warp_f64, one launch).
     Returns dict(ell, g_lvn, logdet, g_mu, g_v, g_theta, t)."""
@@ -1240,22 +1112,89 @@ def ell_warp(Y, mu, v, lvn, flow, theta, scale=1.0, want_t=False):
     return {"ell": out[0], "g_lvn": out[1], "logdet": out[2], "g_mu": gmu, "g_v": gv, "g_theta": gth[:flow.P], "t": t}
 
 
-class EllWarpFunction(torch.autograd.Function):
-    """ELL = WarpedGaussianLinearMean.expected_log_prob with autograd in (mu, v, log_var_noise, theta)."""
+class EllFunction(torch.autograd.Function):
+    """The one autograd wrapper of the row-wise ELL launches.  forward(Y, mu, v, lvn | None, theta | None, rowp | None, ell):
+    `ell(Y, mu, v, lvn, theta, rowp)` is the launch -- an ell_* of this module bound to its extras (flow, S, lik, df, scale) --
+    and gets the tensors detached; of its dict(ell, g_mu, g_v, g_lvn, g_theta, g_rowp) the gradients of the inputs that are
+    present are kept for the backward.  Value and every gradient come from that one launch."""
+
+    GRADS = (None, "g_mu", "g_v", "g_lvn", "g_theta", "g_rowp")     # by input, in forward's order (Y has none)
 
     @staticmethod
-    def forward(ctx, Y, mu, v, lvn, theta, flow):
-        res = ell_warp(Y, mu.detach(), v.detach(), lvn.detach(), flow, theta.detach() if theta is not None else None)
-        ctx.save_for_backward(res["g_lvn"], res["g_mu"], res["g_v"], res["g_theta"])
-        ctx.has = theta is not None
-        ctx.lvn_shape = lvn.shape
+    def forward(ctx, Y, mu, v, lvn, theta, rowp, ell):
+        ins = (Y, mu, v, lvn, theta, rowp)
+        res = ell(*(t.detach() if t is not None else None for t in ins))
+        ctx.has = tuple(k is not None and t is not None for k, t in zip(EllFunction.GRADS, ins))
+        ctx.save_for_backward(*(res[k] for k, has in zip(EllFunction.GRADS, ctx.has) if has))
+        ctx.lvn_shape = lvn.shape if lvn is not None else None
         return res["ell"].reshape(1)
 
     @staticmethod
     def backward(ctx, g):
-        g_lvn, gmu, gv, gth = ctx.saved_tensors
-        g = g.reshape(())
-        return None, g * gmu, g * gv, (g * g_lvn).reshape(ctx.lvn_shape), g * gth if ctx.has else None, None
+        g, saved = g.reshape(()), iter(ctx.saved_tensors)
+        grads = [g * next(saved) if has else None for has in ctx.has]
+        if grads[3] is not None:
+            grads[3] = grads[3].reshape(ctx.lvn_shape)
+        return (*grads, None)
+
+
+class _EllOf:
+    """A public Ell*Function name: `apply` keeps that name's own argument list and binds it to EllFunction -- `bind(*args)`
+    gives EllFunction's (Y, mu, v, lvn, theta, rowp, ell)."""
+
+    def __init__(self, bind, doc):
+        self.bind, self.__doc__ = bind, doc
+
+    def apply(self, *args):
+        return EllFunction.apply(*self.bind(*args))
+
+
+def _gauss_dict(Y, mu, v, lvn, theta, rowp):
+    return dict(zip(("ell", "g_lvn", "g_mu", "g_v"), ell_gauss(Y, mu, v, lvn)))
+
+
+def _hetero_pairs(res):
+    """ell_hetero's dict with g_mu, g_v as the (2, N) pairs the (2, N) inputs take."""
+    return dict(res, g_mu=torch.stack((res["g_mu"], res["g_mu_h"])), g_v=torch.stack((res["g_v"], res["g_v_h"])))
+
+
+def _ell_noiseless_of(lik):
+    return lambda Y, mu, v, theta, rowp, flow, S: (
+        Y, mu, v, None, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: _ell_noiseless(Y, mu, v, flow, theta, S, rowp, 1.0, lik))
+
+
+EllGaussFunction = _EllOf(
+    lambda Y, mu, v, lvn: (Y, mu, v, lvn, None, None, _gauss_dict),
+    """apply(Y, mu, v, lvn): ELL = GaussianLinearMean.expected_log_prob (likelihoods/GaussianLinearMean.py:60-87) with autograd
+    in (mu, v, log_var_noise) -- the reference's method is plain torch code, differentiable wherever it is called.""")
+EllFlowFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_flow(Y, mu, v, lvn, flow, theta, S, rowp)),
+    """apply(Y, mu, v, lvn, theta, rowp, flow, S): ELL = GaussianNonLinearMean.expected_log_prob
+    (likelihoods/GaussianNonLinearMean.py:64-150) with autograd in (mu, v, log_var_noise, theta, rowp).""")
+EllBernoulliFunction = _EllOf(
+    _ell_noiseless_of(L.LIK_BERNOULLI),
+    """apply(Y, mu, v, theta, rowp, flow, S): ELL = Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) with autograd in
+    (mu, v, theta, rowp).""")
+EllPoissonFunction = _EllOf(
+    _ell_noiseless_of(L.LIK_POISSON),
+    """apply(Y, mu, v, theta, rowp, flow, S): ELL of the Poisson likelihood with autograd in (mu, v, theta, rowp).""")
+EllStudentFunction = _EllOf(
+    lambda Y, mu, v, lvn, df, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp)),
+    """apply(Y, mu, v, lvn, df, theta, rowp, flow, S): ELL of the Student-t likelihood with autograd in (mu, v, log_var_noise,
+    theta, rowp) and none in `df`.""")
+EllHeteroFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, rowp, flow, S, scale: (
+        Y, mu, v, lvn, theta, rowp,
+        lambda Y, mu, v, lvn, theta, rowp: _hetero_pairs(ell_hetero(Y, mu, v, lvn, flow, theta, S, rowp, scale=scale))),
+    """apply(Y, mu, v, lvn, theta, rowp, flow, S, scale): ELL of the heteroscedastic Gaussian likelihood with autograd in (mu, v,
+    log_var_noise, theta, rowp); mu, v (2, N).  `scale` multiplies value and gradients inside the launch.""")
+EllWarpFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, flow: (
+        Y, mu, v, lvn, theta, None, lambda Y, mu, v, lvn, theta, rowp: ell_warp(Y, mu, v, lvn, flow, theta)),
+    """apply(Y, mu, v, lvn, theta, flow): ELL = WarpedGaussianLinearMean.expected_log_prob with autograd in (mu, v, log_var_noise,
+    theta).""")
 
 
 class SoftmaxSpec:

@@ -135,9 +135,7 @@ class Trainer_SP_regression:
         are the run's -- optimiser, groups, frozen parameters, loader."""
         from .data import DeviceLoader
         from .engine import ElboEngine, MinibatchEngine, engine_refusal
-        from .flow import compile_flow, mlp_spec
-        from .likelihoods import (Bernoulli, GaussianLinearMean, HeteroscedasticGaussian, MulticlassCategorical, Poisson, StudentT,
-                                  WarpedGaussianLinearMean)
+        from .flow import compile_flow, mlp_spec, stack_theta
         if not getattr(cg, "use_step_engine", True) or opt != "adam":
             return None
         if self.qu == "optimal":
@@ -147,10 +145,7 @@ class Trainer_SP_regression:
             return None
         model = self.model
         mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
-        lik = next((name for cls, name in ((WarpedGaussianLinearMean, "warped"), (Bernoulli, "bernoulli"),
-                                           (MulticlassCategorical, "multiclass"), (Poisson, "poisson"),
-                                           (StudentT, "studentt"), (HeteroscedasticGaussian, "hetero"))
-                    if isinstance(model.likelihood, cls)), None)
+        lik = getattr(model.likelihood, "engine_name", None)
         cover = dict(is_whiten=getattr(model, "is_whiten", True), mean=None if mean_fn is None else mean_fn.name, likelihood=lik,
                      minibatch=len(ld) != 1)
         if engine_refusal(**cover) is not None:        # (before the flow is compiled: whether it is input-dependent comes below)
@@ -162,8 +157,8 @@ class Trainer_SP_regression:
         if {id(q) for g in groups for q in g["params"]} != {id(q) for q in model.parameters()}:
             return None
         nets, theta_list, blocks = [], [], None
-        warped = lik == "warped"
-        if warped or not isinstance(model.likelihood, GaussianLinearMean):
+        warped = getattr(model.likelihood, "flow_on_targets", False)
+        if getattr(model.likelihood, "has_flow", True):
             spec, theta_list, nets = compile_flow(model.likelihood.flow[0] if warped else model.G_matrix[0])
             blocks = spec.blocks
         if engine_refusal(per_row=bool(nets), **cover) is not None:
@@ -183,7 +178,7 @@ class Trainer_SP_regression:
         params = {"Z": Z.detach(), "raw_lengthscale": rl.detach(), "raw_outputscale": ro.detach(), "m": m.detach(),
                   "Lam": Lam.detach(), "log_var_noise": lvn.detach()}
         if theta_list:
-            params["theta"] = torch.stack([p.detach().reshape(()) for p in theta_list])
+            params["theta"] = stack_theta(theta_list)
         W = torch.cat([p.detach().reshape(-1) for p in nn_params]) if nn_params else None
         kw = dict(flow_blocks=blocks, S=getattr(model, "quad_points", None), lr=lr_ALL,
                   kernel=model.covariance_function.hip_kernel, mlp=mspec, mlp_weights=W, nn_weight_decay=wd, mlp_training=True,
@@ -234,7 +229,7 @@ class Trainer_SP_regression:
         if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1 or len(ld) != 1:
             return None
         mean_fn = model.mean_function if model._has_mean else None
-        if collapsed_refusal(likelihood="warped" if model._is_warped else None,
+        if collapsed_refusal(likelihood="warped" if getattr(model.likelihood, "flow_on_targets", False) else None,
                              mean=None if mean_fn is None else (mean_fn.name,)) is not None:
             return None
         if any(g["lr"] != lr_ALL or g["weight_decay"] != 0.0 for g in groups):
@@ -398,15 +393,14 @@ class Trainer_SP_regression:
         logp, (m1, _m2) = self.model.test_log_likelihood(X, Y, return_moments=True, Y_std=self.Y_std.to(X.device),
                                                          S_MC_NNet=self.S_test if self.model.fully_bayesian else None)
         exact = self.coverage == "exact"
-        poisson = getattr(self.model, "_is_poisson", False)
-        student = getattr(self.model, "_is_student", False)
-        hetero = getattr(self.model, "_is_hetero", False)
-        if exact and (self.model.fully_bayesian or poisson or student or hetero):
+        lik = getattr(self.model, "likelihood", None)          # (a foreign model's may carry no traits: the exact route then)
+        no_cdf = getattr(lik, "refuses_cdf", None) is not None
+        if exact and (self.model.fully_bayesian or no_cdf):
             # an MC-dropout mixture over parameter draws has no closed CDF here, a count model no continuous quantiles, a
             # Student-t or heteroscedastic model no CDF kernel: the sampled recipe, said once
             if not self._coverage_fallback_said:
                 print("[tgp.pytorch_amd] coverage='exact' is not built for the %s model: sampled coverage instead"
-                      % ("Poisson" if poisson else "Student-t" if student else "heteroscedastic" if hetero else "fully Bayesian"))
+                      % (lik.display if no_cdf else "fully Bayesian"))
                 self._coverage_fallback_said = True
             exact = False
         if exact:
@@ -442,7 +436,7 @@ class Trainer_SP_regression:
     def _loader_scores(self, loader, samples):
         model = self.model
         sampled = samples is not None or model.fully_bayesian or any(
-            getattr(model, a, False) for a in ("_is_poisson", "_is_student", "_is_hetero", "_is_warped"))
+            getattr(getattr(model, "likelihood", None), a, None) is not None for a in ("refuses_cdf", "refuses_crps"))
         if sampled and samples is None and not self._scores_fallback_said:
             print("[tgp.pytorch_amd] the exact CRPS is not built for this model: the CRPS of %d predictive draws per row instead, "
                   "and no interval score" % self.S_test)
@@ -474,7 +468,7 @@ class Trainer_SP_regression:
 class Trainer_SP_classification(Trainer_SP_regression):
     """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
     the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood (engine.engine_refusal).  Multi-class models
-    (MulticlassCategorical, C latent GPs) train on the eager path too, on the composed step of models._elbo_multiclass; their
+    (MulticlassCategorical, C latent GPs) train on the eager path too, on the composed step of models._elbo_composed; their
     accuracy is the argmax over the C class probabilities (trainers_classification.py:132)."""
 
     def performance_metrics(self, X, Y):
