@@ -148,6 +148,22 @@ extern "C" {
  * tgp_ell_hetero_f64, composed with tgp_qf_moments_f64 / tgp_qf_moments_bwd_f64 / tgp_kl_whitened_f64 per latent GP, and
  * tgp_predict_hetero_f64. */
 #define TGP_LIK_HETERO 8
+/* Negative-binomial counts with the flow as the log-mean, y ~ NB(mean = exp(G(f0)), dispersion r): Var[y | f0] = mean + mean^2 / r,
+ * r -> inf the Poisson.  log_var_noise[0] = lambda = log r, a TRAINED parameter in the noise slot.  Supported range
+ * 1e-3 <= r <= 1e3: the terms of d/dlambda cancel as r grows (relative error of the float64 formula 1e-11 at r = 50, 2e-10 at
+ * 1e3, 2e-7 at 1e4), and past 1e3 TGP_LIK_POISSON is the model to take; the library does not look at r, which lives on the
+ * device.  With g = G(f0), u = g - lambda and sp(u) = log(1 + e^u), evaluated as u > 0 ? u + log1p(e^-u) : log1p(e^u):
+ *   log p(y | g)      = lgamma(y + r) - lgamma(r) - lgamma(y + 1) + y u - (y + r) sp(u)
+ *   d log p / dg      = y - (y + r) sigmoid(u)                     ( = r (y - mean) / (r + mean) )
+ *   d log p / dlambda = r [psi(y + r) - psi(r)] - r sp(u) - d log p / dg,      psi the digamma function,
+ * y any real >= 0 (the library does not ask for integers), g not clamped, Gauss-Hermite over q(f0) (S, xs, wn required); v <= 0
+ * counts as 0 and its adjoint is 0.  Gradients: grads->log_var_noise is ONE double, d/dlambda (as out[1] of tgp_ell_flow_f64).
+ * The training step always takes the general-M path.
+ * tgp_predict_f64: m1 = E[y] = sum_s wn_s exp(g_s), m2 = Var[y] = m1 + (1 + 1/r) sum_s wn_s exp(2 g_s) - m1^2 (the empty program:
+ * the log-normal closed forms E[mean] = exp(mu + v/2), E[mean^2] = exp(2 mu + 2 v)), logp = log sum_s wn_s NB(y | exp(g_s), r),
+ * the log predictive pmf, formed as a log-sum-exp so that it stays finite where every term underflows; Y_std is ignored.  The
+ * predictive is discrete: the quantile, CDF and CRPS entries refuse it (TGP_E_UNSUPPORTED). */
+#define TGP_LIK_NEGBIN 9
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  RBF: s2 exp(-r^2/2);  MATERN32: s2 (1 + sqrt3 r) exp(-sqrt3 r), r = sqrt(max(r^2, 1e-30)) as gpytorch's
@@ -240,8 +256,8 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
 
-/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON or TGP_LIK_STUDENT training step runs
- * on the general-M path at every M. */
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT or TGP_LIK_NEGBIN training
+ * step runs on the general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -505,7 +521,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
  * with gradients w.r.t. mu, v, theta, rowp, log_var_noise.  out[0] = ELL, out[1] = dELL/dlog_var_noise.
  * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0.
  * model->lik == TGP_LIK_POISSON: the Poisson expected log-likelihood of its #define, out[1] = 0.
- * model->lik == TGP_LIK_STUDENT: the Student-t one of its #define (log_var_noise = {log sigma^2, nu}), out[1] = dELL/dlog sigma^2. */
+ * model->lik == TGP_LIK_STUDENT: the Student-t one of its #define (log_var_noise = {log sigma^2, nu}), out[1] = dELL/dlog sigma^2.
+ * model->lik == TGP_LIK_NEGBIN: the negative-binomial one of its #define (log_var_noise = log r), out[1] = dELL/dlog r. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -597,7 +614,8 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON: see their #defines; Y_std is ignored.
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN: see their #defines; Y_std is
+ * ignored.
  * TGP_LIK_STUDENT: see its #define (Y_std is used, the constant is included).
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
  * (WarpedGaussianLinearMean.marginal_moments), logp = log N(T(y) | mu, v + noise) + log T'(y) - log Y_std, the exact warped
@@ -633,7 +651,7 @@ int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */,
  * both tails are resolved to relative accuracy.  status (device int32[1], zeroed by the caller): the call ADDS the number of
  * roots that ran out of evaluations; their t is NaN.
  * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX,
- * TGP_LIK_POISSON and TGP_LIK_STUDENT are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
+ * TGP_LIK_POISSON, TGP_LIK_STUDENT and TGP_LIK_NEGBIN are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
  * over s: same input, same bits. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32

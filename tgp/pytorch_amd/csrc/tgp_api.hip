@@ -996,6 +996,11 @@ static int check_quantile_model(const tgp_model* model, const double* mu, const 
                    "per count)", entry);
     return TGP_E_UNSUPPORTED;
   }
+  if (model->lik == TGP_LIK_NEGBIN) {
+    set_error_text("%s: no quantiles for TGP_LIK_NEGBIN: the predictive is discrete (its pmf is tgp_predict_f64's logp, one row "
+                   "per count)", entry);
+    return TGP_E_UNSUPPORTED;
+  }
   if (model->lik == TGP_LIK_STUDENT) {
     set_error_text("%s: no quantiles for TGP_LIK_STUDENT: the CDF of a Student-t mixture needs the incomplete beta function "
                    "(its density is tgp_predict_f64's logp)", entry);

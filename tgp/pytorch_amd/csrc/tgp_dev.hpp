@@ -266,6 +266,19 @@ __device__ __forceinline__ double softplus_d(double x) {
 }
 __device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp_fast(-x)); }
 
+// digamma psi(x) = d lgamma(x) / dx for x > 0 (the device math library has none): the recurrence psi(x) = psi(x + 1) - 1 / x up
+// to an argument >= 10, then the asymptotic series log x - 1 / (2 x) - sum_k B_2k / (2 k x^2k) through x^-12, whose first
+// omitted term is x^-14 / 12 < 1e-15 there.  At most ten divisions; not for a per-node path (EllNegBin: once per row).  The
+// recurrence is bounded: ten steps take every x > 0 past 10, and x <= 0, -inf or NaN ends in the series as NaN or garbage instead
+// of spinning a lane (x + 1 == x below -2^53).
+__device__ inline double digamma_d(double x) {
+  double s = 0.0;
+  for (int i = 0; i < 10 && x < 10.0; ++i) { s -= 1.0 / x; x += 1.0; }
+  const double i = 1.0 / x, i2 = i * i;
+  const double t = i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0 - i2 * (691.0 / 32760.0))))));
+  return s + (log(x) - 0.5 * i - t);
+}
+
 // ---- N independent evaluations written STAGE BY STAGE.  The row kernel runs one wave per SIMD, so the only latency
 // hiding the f64 pipe gets is independent instructions of the same wave; unrolled node-by-node the chains below were
 // emitted back to back (hipcc keeps source order inside a block: ~9.5 cycles per instruction measured instead of 4).

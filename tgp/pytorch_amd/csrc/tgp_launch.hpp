@@ -126,10 +126,12 @@ inline bool inducing_limits(int M, int D) { return M >= 1 && M <= TGP_BIG_MAX_M 
 inline bool known_kernel(int kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
 // the likelihoods k_ell_quad integrates by Gauss-Hermite through the flow (S, xs, wn, the program and theta are read)
 inline bool lik_is_quadrature(int lik) {
-  return lik == TGP_LIK_FLOW || lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT;
+  return lik == TGP_LIK_FLOW || lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT || lik == TGP_LIK_NEGBIN;
 }
 // ... of which these have no fused row kernel: their training step takes the general-M path at every M, as MATERN32 does
-inline bool lik_general_only(int lik) { return lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT; }
+inline bool lik_general_only(int lik) {
+  return lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT || lik == TGP_LIK_NEGBIN;
+}
 // *first = the first 16-byte aligned double of the caller's workspace `ws`; refused when fewer than need_doubles follow it
 inline int open_workspace(const char* entry, const char* sizer, void* ws, size_t ws_bytes, size_t need_doubles, double** first) {
   const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
@@ -160,11 +162,19 @@ int launch_mlp_backward(const tgp_mlp& d, const double* X, const double* W, cons
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* log_var_noise,
                      double scale, double* out, double* g_mu, double* g_v, double* ws, hipStream_t st);
 // the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, Poisson for TGP_LIK_POISSON, Student-t
-// for TGP_LIK_STUDENT, heteroscedastic Gaussian for TGP_LIK_HETERO (mu, v, g_mu, g_v then (2,N)), else Gaussian (TGP_LIK_FLOW)
+// for TGP_LIK_STUDENT, negative binomial for TGP_LIK_NEGBIN, heteroscedastic Gaussian for TGP_LIK_HETERO (mu, v, g_mu, g_v then
+// (2,N)), else Gaussian (TGP_LIK_FLOW)
 int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st);
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,
                      double* logdG, hipStream_t st, double* sum_out = nullptr, double* ws = nullptr);
+// tgp_lik_negbin.hip: the TGP_LIK_NEGBIN instantiations behind launch_ell_quad (ell_plan's LPR, NB, workgroups and LDS; `ext`: the
+// program holds a kind past STEPTANH) and launch_predict (`lds`: its dynamic LDS)
+int launch_ell_negbin(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+                      const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
+                      double* g_rowp);
+int launch_predict_negbin(const tgp_model& md, const FlowProg& fp, size_t lds, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,

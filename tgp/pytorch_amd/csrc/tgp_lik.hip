@@ -6,6 +6,7 @@
 // coalesced row-major reads, lane-private LDS accumulators, two-pass deterministic reductions.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
+#include "tgp_ell.hpp"
 
 namespace tgp {
 
@@ -86,281 +87,6 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
     if (j < split) out[j] = s;
     else if (out2) out2[j - split] = s;
   }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Quadrature likelihoods through the flow with gradients, E_q(f0)[log p(y | G(f0))] by Gauss-Hermite:
-//   Gaussian  (likelihoods/GaussianNonLinearMean.py:64-150)
-//   Bernoulli (likelihoods/Bernoulli.py), probit link: log p(y | g) = y log Phi(g) + (1 - y) log Phi(-g)
-//   Poisson   (no counterpart in the reference), log link: log p(y | g) = y g - exp(g) - lgamma(y + 1)
-//   Student-t (no counterpart in the reference), location G(f0), scale sigma, nu degrees of freedom (TGP_LIK_STUDENT)
-//   heteroscedastic Gaussian (no counterpart in the reference), log noise variance c + h, h a second latent GP (TGP_LIK_HETERO)
-// ---------------------------------------------------------------------------------------------------
-
-// The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
-//   Phi(-a) = erfc(t) / 2 = erfcx(t) exp(-a^2 / 2) / 2      log Phi(-a) = log(erfcx(t) / 2) - a^2 / 2
-//   Phi(a)  = 1 - erfc(t) / 2                                log Phi(a)  = log1p(-erfc(t) / 2)
-//   lambda(z) = phi(z) / Phi(z):  lambda(-a) = sqrt(2 / pi) / erfcx(t),  lambda(a) = phi(a) / Phi(a)
-// Every quantity stays finite and accurate however large |g| is (the reference forms Phi first: its BCELoss clamps the log
-// at -100 once |g| passes ~8).  lp = y log Phi(g) + (1 - y) log Phi(-g), dg = d lp / dg = y lambda(g) - (1 - y) lambda(-g);
-// pp / pm (optional) = Phi(g) / Phi(-g).
-struct BernNode { double lp, dg, pp, pm; };
-__device__ inline BernNode bern_node(double g, double y) {
-  const double a = fabs(g), t = a * 0.70710678118654752440;
-  const double ec = erfc(t), ex = erfcx(t);
-  const double phia = 0.39894228040143267794 * exp(-0.5 * a * a);   // phi(a)
-  const double lp_hi = log1p(-0.5 * ec);                              // log Phi(a)
-  const double lp_lo = log(0.5 * ex) - 0.5 * a * a;                   // log Phi(-a)
-  const double lam_hi = phia / (1.0 - 0.5 * ec);                      // lambda(a)
-  const double lam_lo = 0.79788456080286535588 / ex;                  // lambda(-a)
-  const bool pos = g >= 0.0;
-  BernNode r;
-  r.lp = y * (pos ? lp_hi : lp_lo) + (1.0 - y) * (pos ? lp_lo : lp_hi);
-  r.dg = y * (pos ? lam_hi : lam_lo) - (1.0 - y) * (pos ? lam_lo : lam_hi);
-  r.pp = pos ? 1.0 - 0.5 * ec : 0.5 * ec;
-  r.pm = pos ? 0.5 * ec : 1.0 - 0.5 * ec;
-  return r;
-}
-
-// What a likelihood supplies to k_ell_quad.  Once per launch: consts(log_var_noise) = its launch constants K (a struct of its
-// own: the noise pair, nothing, or StudentConst).  Per quadrature node with g = G(f0): at(g, y, K) = whatever the three
-// terms share, then
-//   log_p = log p(y | g),  dlog_p_deta = its derivative in eta = log_var_noise[0] (kNoise only),
-//   adjoint = scale w d log p / dg for the node's normalised weight w, which starts the reverse sweep.
-// log_var_noise is read only where kNoise is set.
-// kRowTerm: log p has a part that depends on y alone, row_term(y), which the kernel adds once per row instead of once per node.
-// kBlockTerm: log p has a part that is the same for every row and node, block_term(K), which the kernel adds once per
-// workgroup, times its number of rows (the weights of a row sum to 1).
-// kRowConst: the constants differ from row to row.  mu, v, g_mu, g_v are then (2,N): row 1 holds the moments of a second latent
-// GP, from which row_consts(K, mu2, v2) makes the row's own K; per node row_acc(t, w) is summed over the row's nodes into A, and
-// row_mu_bar(A, K), row_v_bar(A, K) are d log p / d mu2, d log p / d v2 of the row, written (times scale) to row 1 of g_mu, g_v.
-struct EllNoise { double eta, einv; };    // eta = log noise variance, einv = exp(-eta)
-struct EllNone {};
-struct EllGauss {
-  static constexpr bool kNoise = true;    // partial slot 1 carries the noise adjoint
-  static constexpr bool kClampV = false;
-  static constexpr bool kRowTerm = false;
-  static constexpr bool kBlockTerm = false;
-  static constexpr bool kRowConst = false;
-  static __device__ __forceinline__ EllNoise consts(const double* lvn) { return {lvn[0], exp(-lvn[0])}; }
-  static __device__ __forceinline__ double at(double g, double y, const EllNoise&) { return y - g; }   // the residual
-  static __device__ __forceinline__ double log_p(double r, const EllNoise& k) {
-    return -0.5 * TGP_LOG_2PI_REF - 0.5 * k.eta - 0.5 * k.einv * r * r;
-  }
-  static __device__ __forceinline__ double dlog_p_deta(double r, const EllNoise& k) { return -0.5 + 0.5 * k.einv * r * r; }
-  static __device__ __forceinline__ double adjoint(double r, double scale, double w, const EllNoise& k) {
-    return scale * k.einv * w * r;
-  }
-};
-struct EllBern {
-  static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
-  // q(f) variances below 0 count as 0 (Bernoulli.py: gauss_cov[gauss_cov < 0] = 0), where the adjoint of v is 0
-  static constexpr bool kClampV = true;
-  static constexpr bool kRowTerm = false;
-  static constexpr bool kBlockTerm = false;
-  static constexpr bool kRowConst = false;
-  static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
-  static __device__ __forceinline__ BernNode at(double g, double y, const EllNone&) { return bern_node(g, y); }
-  static __device__ __forceinline__ double log_p(const BernNode& b, const EllNone&) { return b.lp; }
-  static __device__ __forceinline__ double adjoint(const BernNode& b, double scale, double w, const EllNone&) {
-    return scale * w * b.dg;
-  }
-};
-// Poisson counts, the flow as the log-rate: log p(y | g) = y g - exp(g) - lgamma(y + 1), d log p / dg = y - exp(g).  g is not
-// clamped: a node whose exp overflows gives -inf, as the float64 formula does.  The exponential is taken once per node and
-// shared by the value and the adjoint; lgamma once per row (row_term).
-struct PoisNode { double g, e, y; };
-struct EllPois {
-  static constexpr bool kNoise = false;   // no noise parameter: partial slot 1 is 0
-  static constexpr bool kClampV = true;   // as EllBern
-  static constexpr bool kRowTerm = true;
-  static constexpr bool kBlockTerm = false;
-  static constexpr bool kRowConst = false;
-  static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
-  static __device__ __forceinline__ PoisNode at(double g, double y, const EllNone&) { return {g, exp(g), y}; }
-  static __device__ __forceinline__ double log_p(const PoisNode& t, const EllNone&) { return t.y * t.g - t.e; }
-  static __device__ __forceinline__ double adjoint(const PoisNode& t, double scale, double w, const EllNone&) {
-    return scale * w * (t.y - t.e);
-  }
-  static __device__ __forceinline__ double row_term(double y) { return -lgamma(y + 1.0); }
-};
-// Student-t noise of scale sigma around the flow, nu degrees of freedom (TGP_LIK_STUDENT): log_var_noise = {eta = log sigma^2,
-// nu}.  With r = y - g and q = nu sigma^2 + r^2:
-//   log p(y | g) = c(nu, eta) - (nu + 1) / 2 log1p(r^2 / (nu sigma^2)),  c = lgamma((nu + 1) / 2) - lgamma(nu / 2) - log(nu pi) / 2 - eta / 2
-//   d log p / dg = (nu + 1) r / q,   d log p / d eta = -1/2 + (nu + 1) r^2 / (2 q).
-// g is not clamped.  One division per node, h = (nu + 1) / q, shared by both derivatives; 1 / (nu sigma^2) once per launch; c,
-// with its two lgamma, once per workgroup (block_term), by one lane.  |r| = 10^8 sigma: r^2 / (nu sigma^2) ~ 10^16, nothing
-// overflows.
-struct StudentConst { double eta, nu, nu1, nus2, inus2; };   // nu1 = nu + 1, nus2 = nu sigma^2, inus2 = 1 / nus2
-struct StudentNode { double r, r2, h; };                     // h = (nu + 1) / (nu sigma^2 + r^2)
-__device__ inline double student_log_const(double nu, double eta) {
-  return lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * log(nu * 3.14159265358979323846) - 0.5 * eta;
-}
-struct EllStudent {
-  static constexpr bool kNoise = true;    // partial slot 1 carries the adjoint of eta (nu is not trained)
-  static constexpr bool kClampV = true;   // as EllBern
-  static constexpr bool kRowTerm = false;
-  static constexpr bool kBlockTerm = true;
-  static constexpr bool kRowConst = false;
-  static __device__ __forceinline__ StudentConst consts(const double* lvn) {
-    const double eta = lvn[0], nu = lvn[1], nus2 = nu * exp(eta);
-    return {eta, nu, nu + 1.0, nus2, 1.0 / nus2};
-  }
-  static __device__ __forceinline__ StudentNode at(double g, double y, const StudentConst& k) {
-    const double r = y - g, r2 = r * r;
-    return {r, r2, k.nu1 / (k.nus2 + r2)};
-  }
-  static __device__ __forceinline__ double log_p(const StudentNode& t, const StudentConst& k) {
-    return -0.5 * k.nu1 * log1p(t.r2 * k.inus2);
-  }
-  static __device__ __forceinline__ double dlog_p_deta(const StudentNode& t, const StudentConst&) { return -0.5 + 0.5 * t.h * t.r2; }
-  static __device__ __forceinline__ double adjoint(const StudentNode& t, double scale, double w, const StudentConst&) {
-    return scale * w * t.h * t.r;
-  }
-  static __device__ __forceinline__ double block_term(const StudentConst& k) { return student_log_const(k.nu, k.eta); }
-};
-// Heteroscedastic Gaussian noise around the flow (TGP_LIK_HETERO): y ~ N(G(f), exp(c + h)), c = log_var_noise[0], h a second latent
-// GP with q(h_n) = N(mu2_n, v2_n) independent of q(f_n).  h integrates out in closed form: with a = c + mu2 and
-// p = E_q[exp(-(c + h))] = exp(-a + v2 / 2),
-//   E_q(h)[log N(y | g, e^(c+h))] = -log(2 pi) / 2 - a / 2 - p r^2 / 2,      r = y - g,
-// which is EllGauss's node term at the row's own pair (eta, einv) = (a, p): the node functions are EllGauss's.  With
-// A = sum_s w_s r_s^2:  d/dmu2 = -1/2 + p A / 2,  d/dv2 = -p A / 4,  d/dc = sum_n d/dmu2_n (partial slot 1, as the noise adjoint).
-// v2 <= 0 counts as 0 and its adjoint is 0 (as for v1); p is not clamped: the float64 formula.
-struct HeteroRow : EllNoise { bool v2pos; };
-struct EllHetero {
-  static constexpr bool kNoise = true;    // partial slot 1 carries the adjoint of c
-  static constexpr bool kClampV = true;   // as EllBern
-  static constexpr bool kRowTerm = false;
-  static constexpr bool kBlockTerm = false;
-  static constexpr bool kRowConst = true;
-  static __device__ __forceinline__ double consts(const double* lvn) { return lvn[0]; }
-  static __device__ __forceinline__ HeteroRow row_consts(double c, double mu2, double v2) {
-    const bool pos = v2 > 0.0;
-    const double a = c + mu2;
-    HeteroRow k;
-    k.eta = a; k.einv = exp(-a + (pos ? 0.5 * v2 : 0.0)); k.v2pos = pos;
-    return k;
-  }
-  static __device__ __forceinline__ double at(double g, double y, const HeteroRow&) { return y - g; }
-  static __device__ __forceinline__ double log_p(double r, const HeteroRow& k) { return EllGauss::log_p(r, k); }
-  static __device__ __forceinline__ double dlog_p_deta(double r, const HeteroRow& k) { return EllGauss::dlog_p_deta(r, k); }
-  static __device__ __forceinline__ double adjoint(double r, double scale, double w, const HeteroRow& k) {
-    return EllGauss::adjoint(r, scale, w, k);
-  }
-  static __device__ __forceinline__ double row_acc(double r, double w) { return w * r * r; }
-  static __device__ __forceinline__ double row_mu_bar(double A, const HeteroRow& k) { return -0.5 + 0.5 * k.einv * A; }
-  static __device__ __forceinline__ double row_v_bar(double A, const HeteroRow& k) { return k.v2pos ? -0.25 * k.einv * A : 0.0; }
-};
-// the constants of data row nc: the launch constants, or what the policy makes of them and the row's second pair of moments
-template <class Lik, class K0>
-__device__ __forceinline__ auto ell_row_consts(const K0& k0, const double* __restrict__ mu, const double* __restrict__ v, int N, int nc) {
-  if constexpr (Lik::kRowConst) return Lik::row_consts(k0, mu[(size_t)N + nc], v[(size_t)N + nc]);
-  else return k0;
-}
-
-// LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
-// lane.  The launcher picks LPR from N so that a chunk of ~16k rows still yields ~1000 workgroups.
-// NBX = NB | TGP_FLOWX: the flow sweeps know the extended kind set (X; see k_rows)
-template <class Lik, int LPR, int NBX>
-__global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, const double* __restrict__ Y,
-                                                   const double* __restrict__ mu, const double* __restrict__ v,
-                                                   const double* __restrict__ rowp, double* __restrict__ part,
-                                                   double* __restrict__ g_mu, double* __restrict__ g_v,
-                                                   double* __restrict__ g_rowp) {
-  constexpr int NB = NBX & (TGP_FLOWX - 1);
-  constexpr bool X = NBX & TGP_FLOWX;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* sm = reinterpret_cast<double*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = md.P, RP = md.RP;
-  const int nb = fp.nblk > 0 ? fp.nblk : 1;
-  constexpr int RW = 64 / LPR;                              // rows per wave
-  double* stack = sm;                                       // nblk * NB * 256: block inputs (checkpoint mode)
-  double* accw = stack + (size_t)nb * NB * 256;             // 4 waves x P: per-wave shared-parameter accumulators
-  double* accr = accw + (size_t)4 * (P > 0 ? P : 1);        // RP * 256 (per-row parameters, lane-private)
-  double* red = accr + (size_t)RP * 256;                    // 16
-  double* tp = red + 16;                                    // P+2
-  double* tg = tp + (P + 2) / 2 * 2;                        // P+2
-  double* ti = tg + (P + 2) / 2 * 2;                        // P+2: reciprocals (flow_rcp_param)
-  for (int i = tid; i < 4 * (P > 0 ? P : 1) + RP * 256; i += 256) accw[i] = 0.0;
-  flow_params_lds<X>(md.theta, fp, tp, tg, ti);
-  // lane group q takes the quadrature nodes s = q + LPR (NB j + u).  Every lane runs the same trip count (wave-wide
-  // sums inside the reverse sweep); nodes past S and padding rows carry weight 0.
-  const int qn = lane / RW;
-  const int n = blockIdx.x * (4 * RW) + wave * RW + (lane % RW);
-  auto group_sum = [&](double x) {   // over the LPR lanes of a row: lanes differing in the bits above log2(RW)
-#pragma unroll
-    for (int o = RW; o < 64; o <<= 1) x += __shfl_xor(x, o);
-    return x;
-  };
-  const bool valid = n < md.N;
-  const int nc = valid ? n : md.N - 1;
-  const auto K = ell_row_consts<Lik>(Lik::consts(md.log_var_noise), mu, v, md.N, nc);
-  FlowDev F{fp.blk, fp.nblk, tp, tg, ti};
-  double ellp = 0.0, etap = 0.0, cm = 0.0, cv = 0.0;
-  [[maybe_unused]] double racc = 0.0;   // kRowConst: this lane's part of the row's A
-  const double m_ = mu[nc], vn = Lik::kClampV ? (v[nc] > 0.0 ? v[nc] : 0.0) : v[nc];
-  const double sq = sqrt(2.0 * vn), y = Y[nc];
-  const double* rp = rowp ? rowp + (size_t)nc * RP : nullptr;
-  double* aw = accw + (size_t)wave * (P > 0 ? P : 1);
-  for (int s0 = 0; s0 < md.S; s0 += LPR * NB) {
-    double f[NB], c[NB], xsn[NB], wsn[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int s = s0 + LPR * u + qn, sc = s < md.S ? s : md.S - 1;
-      xsn[u] = md.xs[sc];
-      wsn[u] = (valid && s < md.S) ? md.wn[sc] : 0.0;
-      f[u] = m_ + sq * xsn[u];
-    }
-    flow_forward_ckpt<NB, X>(F, f, rp, stack + tid, 256);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const auto t = Lik::at(f[u], y, K);
-      ellp += wsn[u] * Lik::log_p(t, K);
-      if constexpr (Lik::kNoise) etap += wsn[u] * Lik::dlog_p_deta(t, K);
-      if constexpr (Lik::kRowConst) racc += Lik::row_acc(t, wsn[u]);
-      c[u] = Lik::adjoint(t, md.scale, wsn[u], K);
-    }
-    flow_backward_ckpt<NB, X>(F, c, rp, stack + tid, 256, aw, lane, accr + tid, 256);
-#pragma unroll
-    for (int u = 0; u < NB; ++u) { cm += c[u]; cv += c[u] * xsn[u]; }
-  }
-  if constexpr (Lik::kRowTerm) {   // the weights sum to 1: the part of log p that is constant over the nodes, once per row
-    if (valid && qn == 0) ellp += Lik::row_term(y);
-  }
-  cm = group_sum(cm);
-  cv = group_sum(cv);
-  for (int j = 0; j < RP; ++j) {
-    const double a = group_sum(accr[(size_t)j * 256 + tid]);
-    if (valid && qn == 0 && g_rowp) g_rowp[(size_t)n * RP + j] = a;
-  }
-  if (valid && qn == 0) {
-    if (g_mu) g_mu[n] = cm;
-    if (g_v) g_v[n] = (!Lik::kClampV || vn > 0.0) ? cv / sq : 0.0;
-  }
-  if constexpr (Lik::kRowConst) {   // the adjoints of the row's second pair of moments: row 1 of the (2,N) outputs
-    const double A = group_sum(racc);
-    if (valid && qn == 0) {
-      if (g_mu) g_mu[(size_t)md.N + n] = md.scale * Lik::row_mu_bar(A, K);
-      if (g_v) g_v[(size_t)md.N + n] = md.scale * Lik::row_v_bar(A, K);
-    }
-  }
-  ellp = wave_sum(ellp);
-  if constexpr (Lik::kNoise) etap = wave_sum(etap);
-  if (lane == 0) {
-    red[wave] = ellp;
-    if constexpr (Lik::kNoise) red[4 + wave] = etap;
-  }
-  __syncthreads();
-  double* pb = part + (size_t)blockIdx.x * (2 + P);
-  if (tid == 0) {
-    if constexpr (Lik::kBlockTerm) {   // the part of log p that no row or node changes, times this workgroup's rows
-      const int r0 = blockIdx.x * (4 * RW), nr = md.N - r0 < 4 * RW ? md.N - r0 : 4 * RW;
-      red[0] += (double)nr * Lik::block_term(K);
-    }
-    pb[0] = md.scale * (red[0] + red[1] + red[2] + red[3]);
-    pb[1] = Lik::kNoise ? md.scale * (red[4] + red[5] + red[6] + red[7]) : 0.0;
-  }
-  for (int j = tid; j < P; j += 256) pb[2 + j] = (accw[j] + accw[P + j]) + (accw[2 * P + j] + accw[3 * P + j]);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -539,71 +265,12 @@ __global__ __launch_bounds__(256) void k_predict_bern(tgp_model md, FlowProg fp,
   if (logp && Y) logp[n] = lp_done ? lp : (y != 0.0 ? y * log(P1) : 0.0) + (y != 1.0 ? (1.0 - y) * log(P0) : 0.0);
 }
 
-// Poisson predictive per row, g_s = G(mu + sqrt(2 v) x_s) the log-rate at node s (v <= 0 counts as 0):
-//   m1 = E[y] = sum_s w_s exp(g_s),  m2 = Var[y] = m1 + sum_s w_s exp(2 g_s) - m1^2   (law of total variance; the empty
-//   program: the log-normal closed forms m1 = exp(mu + v / 2), m2 = m1 + (exp(v) - 1) m1^2),
-//   logp = log sum_s w_s Poisson(y | exp(g_s)) = logsumexp_s(log w_s + y g_s - exp(g_s)) - lgamma(y + 1),
-// the log predictive pmf with its constant.  The sum is kept relative to its running maximum (rescaled when a larger term
-// arrives), so logp is finite where every single term underflows -- y = 10^4 at a rate of e^2: terms near -10^5.  Nodes past S
-// and nodes of weight 0 do not enter.  X: the extended kind set.
-template <bool X>
-__global__ __launch_bounds__(256) void k_predict_pois(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                       const double* __restrict__ v, const double* __restrict__ rowp,
-                                                       const double* __restrict__ Y, double* __restrict__ m1o,
-                                                       double* __restrict__ m2o, double* __restrict__ logp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  flow_params_lds<X>(md.theta, fp, tp, tg);
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= md.N) return;
-  const bool want_lp = logp && Y;
-  const double y = want_lp ? Y[n] : 0.0;
-  FlowDev F{fp.blk, fp.nblk, tp, tg};
-  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-  const double vn = v[n] > 0.0 ? v[n] : 0.0;
-  const double m_ = mu[n], sq = sqrt(2.0 * vn);
-  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
-  constexpr int NB = 4;
-  for (int s0 = 0; s0 < md.S; s0 += NB) {
-    double g[NB], der[NB], wsn[NB];
-    const double* rpn[NB];
-    TGP_EACH(u, NB) {
-      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-      g[u] = m_ + sq * md.xs[s];
-      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-      rpn[u] = rp;
-    }
-    flow_forward_n<NB, false, X>(F, g, rpn, der);
-    TGP_EACH(u, NB) {
-      if (wsn[u] > 0.0) {
-        const double e = exp(g[u]);
-        m1 += wsn[u] * e;
-        e2 += wsn[u] * e * e;
-        if (want_lp) {
-          const double t = log(wsn[u]) + y * g[u] - e;
-          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
-          else if (t > -INFINITY) se += exp(t - mx);
-        }
-      }
-    }
-  }
-  double m2 = m1 + e2 - m1 * m1;
-  if (fp.nblk == 0) {
-    m1 = exp(m_ + 0.5 * vn);
-    m2 = m1 + expm1(vn) * m1 * m1;
-  }
-  if (m1o) m1o[n] = m1;
-  if (m2o) m2o[n] = m2;
-  if (want_lp) logp[n] = mx + log(se) - lgamma(y + 1.0);
-}
-
 // Student-t predictive per row, in the standardised units of k_predict, g_s = G(mu + sqrt(2 v) x_s) (v <= 0 counts as 0):
 //   m1 = sum_s w_s g_s,  m2 = sum_s w_s g_s^2 - m1^2 + sigma^2 nu / (nu - 2)   (+inf for nu <= 2: no variance),
 //   logp = log sum_s w_s t_nu(y | g_s, sigma) - log Y_std = logsumexp_s(log w_s - (nu + 1) / 2 log1p(r_s^2 / (nu sigma^2)))
 //          + c(nu, eta) - log Y_std,
 // the exact log predictive density of the raw target with every constant; the sum is kept relative to its running maximum
-// as in k_predict_pois.  The empty program runs the same loop (no closed form for the Gaussian-Student convolution; the
+// as in k_predict_count.  The empty program runs the same loop (no closed form for the Gaussian-Student convolution; the
 // two moments are exact at S >= 2).  Nodes past S and nodes of weight 0 do not enter.  X: the extended kind set.
 template <bool X>
 __global__ __launch_bounds__(256) void k_predict_student(tgp_model md, FlowProg fp, const double* __restrict__ mu,
@@ -780,36 +447,6 @@ static int ell_plan(const tgp_model& md, const FlowProg& fp, int* lpr, int* nbn,
   return flow_lds(md, fp.nblk, NB, lds);
 }
 
-// one launch of k_ell_quad<Lik, LPR, NB> or, for a program with a kind past STEPTANH (ext), k_ell_quad<Lik, LPR, NB | TGP_FLOWX>;
-// each of the two kernel functions has its own dynamic-LDS high-water mark (ensure_lds)
-template <class Lik, int LPR, int NB, class... Args>
-static int ell_launch_one(bool ext, int nb, size_t lds, hipStream_t st, Args... args) {
-  static size_t cur[2] = {48 * 1024, 48 * 1024};
-  auto* const kern = ext ? k_ell_quad<Lik, LPR, NB | TGP_FLOWX> : k_ell_quad<Lik, LPR, NB>;
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, st, args...);
-  LAUNCH_CHECK();
-  return 0;
-}
-// the instantiation for ell_plan's (LPR, NB)
-template <class Lik, class... Args>
-static int ell_launch(int LPR, int NB, Args... args) {
-  if (LPR == 4) {
-    if (NB == 8) return ell_launch_one<Lik, 4, 8>(args...);
-    if (NB == 4) return ell_launch_one<Lik, 4, 4>(args...);
-    if (NB == 2) return ell_launch_one<Lik, 4, 2>(args...);
-    return ell_launch_one<Lik, 4, 1>(args...);
-  }
-  if (LPR == 16) {
-    if (NB == 4) return ell_launch_one<Lik, 16, 4>(args...);
-    if (NB == 2) return ell_launch_one<Lik, 16, 2>(args...);
-    return ell_launch_one<Lik, 16, 1>(args...);
-  }
-  if (NB == 4) return ell_launch_one<Lik, 32, 4>(args...);
-  if (NB == 2) return ell_launch_one<Lik, 32, 2>(args...);
-  return ell_launch_one<Lik, 32, 1>(args...);
-}
-
 int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st) {
   // nodes in flight per lane: all of the lane's nodes when the checkpoint stack fits (the per-step wave reductions of
@@ -824,6 +461,8 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
                    ? ell_launch<EllBern>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                : md.lik == TGP_LIK_POISSON
                    ? ell_launch<EllPois>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
+               : md.lik == TGP_LIK_NEGBIN   // (its instantiations: tgp_lik_negbin.hip)
+                   ? launch_ell_negbin(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                : md.lik == TGP_LIK_STUDENT
                    ? ell_launch<EllStudent>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
                : md.lik == TGP_LIK_HETERO   // (tgp_ell_hetero_f64 only: mu, v, g_mu, g_v are (2,N))
@@ -863,9 +502,11 @@ int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, co
       hipLaunchKernelGGL(k_predict_bern<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
   } else if (md.lik == TGP_LIK_POISSON) {
     if (flow_prog_extended(fp.blk, fp.nblk))
-      hipLaunchKernelGGL(k_predict_pois<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+      hipLaunchKernelGGL((k_predict_count<EllPois, true>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
     else
-      hipLaunchKernelGGL(k_predict_pois<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+      hipLaunchKernelGGL((k_predict_count<EllPois, false>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
+  } else if (md.lik == TGP_LIK_NEGBIN) {
+    return launch_predict_negbin(md, fp, lds, mu, v, rowp, Y, m1, m2, logp, st);
   } else if (md.lik == TGP_LIK_STUDENT) {
     if (flow_prog_extended(fp.blk, fp.nblk))
       hipLaunchKernelGGL(k_predict_student<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);

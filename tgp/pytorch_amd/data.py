@@ -125,12 +125,14 @@ def load_uci_split(base, seed, root):
 
 def _binary_dataset(base, batch_size, use_validation, seed, options):
     """synthetic_heart / synthetic_banknote (synthetic.binary_dataset), the multi-class synthetic_blobs
-    (synthetic.blobs_dataset; data_config["num_classes"]) and the count set synthetic_counts (synthetic.counts_dataset): a
+    (synthetic.blobs_dataset; data_config["num_classes"]) and the count sets synthetic_counts (synthetic.counts_dataset) and
+    synthetic_overdispersed (synthetic.overdispersed_dataset; data_config["dispersion"] keeps its true r): a
     seeded 90 / 10 split, X standardised by the train split, labels and counts left as they are (Y_std = 1)."""
-    from .synthetic import binary_dataset, blobs_dataset, counts_dataset
+    from .synthetic import OVERDISPERSED_R, binary_dataset, blobs_dataset, counts_dataset, overdispersed_dataset
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
-    X, Y = blobs_dataset() if base == "blobs" else (counts_dataset() if base == "counts" else binary_dataset(base))
+    X, Y = (blobs_dataset() if base == "blobs" else counts_dataset() if base == "counts" else
+            overdispersed_dataset() if base == "overdispersed" else binary_dataset(base))
     n = X.shape[0]
     perm = numpy.random.default_rng(seed).permutation(n)
     n_tr = int(round(0.9 * n))
@@ -155,7 +157,9 @@ def _binary_dataset(base, batch_size, use_validation, seed, options):
                    "train_idx": numpy.asarray(tr_idx), "test_idx": numpy.asarray(te_idx)}
     if base == "blobs":
         data_config["num_classes"] = int(Y.max()) + 1
-    if base == "counts":
+    if base == "overdispersed":
+        data_config["dispersion"] = OVERDISPERSED_R
+    if base in ("counts", "overdispersed"):
         data_config["Y_mean"] = numpy.zeros(1)      # said outright: the targets are the raw counts, RMSE and NLL are in counts
     return loaders, data_config
 
@@ -173,7 +177,7 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     options = options or {}
     synth = dataset_name.startswith("synthetic_")
     base = dataset_name.replace("synthetic_", "")
-    if synth and (base in BINARY_SHAPES or base in ("blobs", "counts")):
+    if synth and (base in BINARY_SHAPES or base in ("blobs", "counts", "overdispersed")):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
     if (synth and base not in SHAPES and base not in ("outliers", "hetero")) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))

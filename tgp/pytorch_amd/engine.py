@@ -38,7 +38,7 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
     """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
     combination, else the message both refuse it with (_refuse) before they load the library or touch the device; the
     trainers take the eager loop on a message.  A pure function of the description: `mean` = None / "linear" / "identity",
-    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "studentt" / "multiclass" / "hetero", `collective` as passed to the engine (asking
+    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "negbinomial" / "studentt" / "multiclass" / "hetero", `collective` as passed to the engine (asking
     for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`)."""
     multi_rank = int(world_size) > 1 or collective is not None
     if not is_whiten:      # `params` of an unwhitened model describe q(u) itself; the captured step has no transform in it
@@ -47,6 +47,8 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
         return "the step engines have no Bernoulli likelihood: it trains on the eager path (ops.ElboFunction)"
     if likelihood == "poisson":
         return "the step engines have no Poisson likelihood: it trains on the eager path (ops.ElboFunction)"
+    if likelihood == "negbinomial":
+        return "the step engines have no negative-binomial likelihood: it trains on the eager path (ops.ElboFunction)"
     if likelihood == "studentt":
         return "the step engines have no Student-t likelihood: it trains on the eager path (ops.ElboFunction)"
     if likelihood == "multiclass":

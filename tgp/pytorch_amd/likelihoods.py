@@ -27,7 +27,8 @@ class Likelihood(nn.Module):
     lik_id = None                   # lib.LIK_* of the step and of ops.predict; None: told by the flow's presence, or composed
     engine_name = None              # the `likelihood=` key of engine.engine_refusal
     kind = "regression"             # | "classifier" (class probabilities, no quantiles, no CRPS) | "count" (a pmf)
-    has_noise = True                # log_var_noise exists; False: the ABI's noise pointer gets a zero that no kernel reads
+    has_noise = True                # a trained scalar sits behind the ABI's noise pointer and noise() returns it (log_var_noise,
+                                    # or one of another name: log_dispersion); False: the pointer gets a zero that no kernel reads
     has_flow = True                 # False: the Gaussian closed form, no flow program at all
     flow_on_targets = False         # the flow is the likelihood's own (`self.flow`) and warps the targets, not f
     compiles_flows = False          # _flow_inputs is the likelihood's own: shared flow parameters only
@@ -298,6 +299,63 @@ class Poisson(Likelihood):
         """(m1, m2) = (E[y], Var[y]) of the predictive, in counts, each of gauss_mean's shape (1, MB)."""
         self._checks(gauss_mean, flow, X)
         return self._moments(gauss_mean, gauss_cov, flow, X)
+
+
+class NegativeBinomial(Poisson):
+    """p(y|G(f)) = NB(y | mean = exp(G(f)), dispersion r) for over-dispersed counts: Var[y | f] = mean + mean^2 / r, and r -> inf is
+    the Poisson likelihood.  One parameter, `log_dispersion` = log r (one element, initialised at log `dispersion_init`), which
+    sits where the Gaussian classes' log_var_noise sits in the ABI and is trained through the same gradient slot.  Supported
+    range 1e-3 <= r <= 1e3 (past it the terms of d/dlog r cancel and Poisson is the model to take; nothing looks at the value
+    during training).  The quadrature over q(f0) runs in float64 on the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with
+    TGP_LIK_NEGBIN).  The reference has no such class; the interface is Poisson's."""
+
+    display = "negative-binomial"
+    lik_id = ops.L.LIK_NEGBIN
+    engine_name = "negbinomial"
+    has_noise = True
+    outputs_refusal = "the negative-binomial likelihood is built for one output (num_outputs = 1)"
+    refuses_input_dependent = NO_INPUT_DEPENDENT % display
+    refuses_optimal_qu = NOT_GAUSSIAN_IN_F % display
+    refuses_cdf = ("%s: the predictive of a negative-binomial model is discrete; predictive_pmf(X, kmax) gives its pmf "
+                   "(cumsum: the CDF) and posterior_quantiles the quantiles of the log-mean")
+
+    def __init__(self, dispersion_init=1.0):
+        super().__init__()
+        r = float(dispersion_init)
+        if not r > 0.0:
+            raise ValueError("the dispersion of the negative-binomial likelihood must be > 0, got %g" % r)
+        self.log_dispersion = nn.Parameter(torch.log(torch.tensor([r], dtype=cg.dtype)))
+
+    def noise(self):
+        """log r, the one element behind the ABI's noise pointer, with the graph to the parameter."""
+        return self.log_dispersion.reshape(-1)[:1]
+
+    @property
+    def dispersion(self):
+        """r = exp(log_dispersion), detached."""
+        return torch.exp(self.log_dispersion.detach())
+
+    @staticmethod
+    def check_targets(Y):
+        """ValueError unless every target is a count: an integer >= 0 (the kernels take any real >= 0 and do not look)."""
+        Yd = Y.detach()
+        if not bool(((Yd >= 0) & (Yd == torch.round(Yd))).all()):     # (a NaN fails both comparisons)
+            raise ValueError("the negative-binomial likelihood takes counts: every target must be an integer >= 0")
+
+    def sample_from_output(self, f, i, **kwargs):
+        """A Gamma-Poisson draw: Poisson(exp(f) Gamma(r, r))."""
+        r = self.dispersion.to(f.device, f.dtype).reshape(())
+        return torch.poisson(torch.exp(f) * td.Gamma(r, r).sample(f.shape).reshape(f.shape))
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[log NB(y_n | exp(G(f0)), r)], differentiable in the moments, log_dispersion and the flow's parameters;
+        Y (1, MB) counts, moments (1, MB)."""
+        self.check_targets(Y)
+        self._checks(gauss_mean, flow, X)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllNegBinFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                           gauss_cov.reshape(-1).contiguous(), self.noise().contiguous(), theta, rowp, spec,
+                                           self.quad_points)
 
 
 class StudentT(_GaussianBase):

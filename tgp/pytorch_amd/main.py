@@ -24,6 +24,13 @@ SAL x 2) with the softmax likelihood over C latent GPs on synthetic_blobs, and r
 the learned link to the log-rate) on synthetic_counts, and reports the test negative log-likelihood (of the observed counts,
 under the predictive pmf) and RMSE in counts beside those of the constant-rate baseline, a Poisson at the training mean.
 
+`--likelihood negbinomial` is the same with the negative-binomial likelihood for over-dispersed counts (Var = mean + mean^2 / r):
+the dispersion r is trained from --dispersion_init, and the run also prints the learned r.  synthetic_overdispersed is
+synthetic_counts's log-mean under NB noise of r = 2:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood negbinomial --dataset synthetic_overdispersed \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 2000
+
 `--likelihood studentt --df 4` trains a robust regression (SVGP or TGP) with Student-t noise around G(f) on any regression
 data set; synthetic_outliers has gross errors in a tenth of its training targets and a clean test split:
 
@@ -50,7 +57,7 @@ from .initializers import find_forward_params, find_forward_params_input_depende
 from .kernels import instance_kernel
 from .lib import STUDENT_MAX_DF
 from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
-                          Poisson, StudentT, WarpedGaussianLinearMean)
+                          NegativeBinomial, Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import GREEDY_VARIANCE, KMEANS
@@ -66,12 +73,13 @@ HYPER = {
     ("TGP", "banknote"): dict(arch="BCL_AL", blocks=5, steps=None),
     ("TGP", "blobs"): dict(arch="SAL", blocks=2, steps=None),
     ("TGP", "counts"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "overdispersed"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
-COUNT_DATASETS = ("synthetic_counts",)
+COUNT_DATASETS = ("synthetic_counts", "synthetic_overdispersed")
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -91,13 +99,17 @@ def main(argv=None):
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "studentt", "hetero"], default="gaussian",
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "negbinomial", "studentt", "hetero"],
+                    default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
-                         "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; studentt: "
+                         "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; negbinomial: the same "
+                         "for over-dispersed counts, with a trained dispersion r (Var = mean + mean^2 / r); studentt: "
                          "robust regression, Student-t noise of --df degrees of freedom around G(f); hetero: regression with "
                          "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
+    ap.add_argument("--dispersion_init", type=float, default=1.0,
+                    help="the dispersion r of --likelihood negbinomial at the start (trained; supported range 1e-3 <= r <= 1e3)")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
                     help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
                          "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli, poisson or studentt)")
@@ -121,8 +133,13 @@ def main(argv=None):
     pois = args.likelihood == "poisson"
     if pois and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood poisson: SVGP or TGP only")
-    if pois != (args.dataset in COUNT_DATASETS):
-        ap.error("--likelihood poisson goes with the count data sets (%s)" % ", ".join(COUNT_DATASETS))
+    negb = args.likelihood == "negbinomial"
+    if negb and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood negbinomial: SVGP or TGP only")
+    if negb and not (1e-3 <= args.dispersion_init <= 1e3):
+        ap.error("--dispersion_init: the dispersion must be in [1e-3, 1e3], got %g" % args.dispersion_init)
+    if (pois or negb) != (args.dataset in COUNT_DATASETS):
+        ap.error("--likelihood %s goes with the count data sets (%s)" % ("negbinomial" if negb else "poisson", ", ".join(COUNT_DATASETS)))
     stud = args.likelihood == "studentt"
     if stud and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood studentt: SVGP or TGP only")
@@ -211,6 +228,8 @@ def main(argv=None):
         lik = Bernoulli()
     elif pois:
         lik = Poisson()
+    elif negb:
+        lik = NegativeBinomial(dispersion_init=args.dispersion_init)
     elif het:
         Dy = 2                              # latent GP 0: f (with the flow), latent GP 1: h, the log noise variance (no flow)
         lik = HeteroscedasticGaussian(noise_init=0.05, quadrature_points=cg.quad_points)
@@ -260,7 +279,7 @@ def main(argv=None):
         print("Dataset {}, num inducing points {}, model {}, Test Accuracy {:.3f}".format(
             args.dataset, args.num_inducing, args.model, res[5]))
         return res
-    if pois:
+    if pois or negb:
         # the constant-rate baseline: a Poisson at the mean of the training counts, its NLL and RMSE on the test counts
         rate, y_te = dc["Y_tr"].mean(), dc["Y_te"].reshape(-1)
         base_nll = -(y_te * torch.log(rate) - rate - torch.lgamma(y_te + 1.0)).mean().item()
@@ -269,6 +288,10 @@ def main(argv=None):
             args.dataset, args.num_inducing, args.model, -res[6], res[7]))
         print("Dataset {}, constant rate {:.3f}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
             args.dataset, rate.item(), base_nll, base_rmse))
+        if negb:
+            print("Dataset {}, num inducing points {}, model {}, learned dispersion r {:.3f}{}".format(
+                args.dataset, args.num_inducing, args.model, float(lik.dispersion),
+                "" if "dispersion" not in dc else " (true r {:.3f})".format(dc["dispersion"])))
         if args.scores:
             print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
                 args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))

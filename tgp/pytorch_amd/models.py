@@ -706,7 +706,8 @@ class sparse_MF_SP(nn.Module):
             out = ops.crps_from_samples(draws[0, :, :, 0], y.to(draws.dtype)).unsqueeze(0)
         elif count:
             if kmax is None:
-                raise ValueError("predictive_crps of a Poisson model needs kmax, the last count of the sum (predictive_pmf's)")
+                raise ValueError("predictive_crps of a %s model needs kmax, the last count of the sum (predictive_pmf's)"
+                                 % self.likelihood.display)
             cdf = self.predictive_pmf(X, kmax).cumsum(1)                                       # (N, kmax + 1)
             k = torch.arange(int(kmax) + 1, dtype=cdf.dtype, device=cdf.device).unsqueeze(0)
             out = ((cdf - (k >= y.to(cdf.dtype).unsqueeze(1)).to(cdf.dtype)) ** 2).sum(1).unsqueeze(0)

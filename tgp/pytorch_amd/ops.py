@@ -180,7 +180,9 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     `lik` = lib.LIK_BERNOULLI: probit likelihood through `flow` (a FlowSpec, possibly empty); lvn is read by no kernel and
     its gradient is 0.  `lik` = lib.LIK_POISSON: counts Y with the flow as the log-rate, the same conventions.
     `lik` = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom around the flow; lvn (one element) is the log of the
-    squared scale and grads["lvn"] its one-element gradient; `df` has none."""
+    squared scale and grads["lvn"] its one-element gradient; `df` has none.
+    `lik` = lib.LIK_NEGBIN: negative-binomial counts with the flow as the log-mean; lvn (one element) is the log dispersion
+    log r and grads["lvn"] its gradient."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -190,9 +192,10 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     N, D = X.shape
     M = m.numel()
     scale = float(N_total) / float(mb_global if mb_global is not None else N)
-    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON, L.LIK_STUDENT) and flow is None:
+    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON, L.LIK_STUDENT, L.LIK_NEGBIN) and flow is None:
         raise L.TgpError("the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
-                         % {L.LIK_BERNOULLI: "Bernoulli", L.LIK_POISSON: "Poisson", L.LIK_STUDENT: "Student-t"}[lik])
+                         % {L.LIK_BERNOULLI: "Bernoulli", L.LIK_POISSON: "Poisson", L.LIK_STUDENT: "Student-t",
+                            L.LIK_NEGBIN: "negative-binomial"}[lik])
     # (LIK_STUDENT: the library reads {log sigma^2, nu} behind the noise pointer and writes one gradient, that of log sigma^2)
     if lik == L.LIK_STUDENT and lvn.numel() != 1:
         raise L.TgpError("the Student-t step takes a one-element log_var_noise (log sigma^2); the degrees of freedom go in `df`")
@@ -1057,6 +1060,13 @@ def ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp=None, scale=1.0):
     return _ell_quad(Y, mu, v, student_noise(lvn, df), flow, theta, S, rowp, scale, L.LIK_STUDENT)
 
 
+def ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
+    """Negative-binomial quadrature ELL with gradients, the flow as the log-mean: scale sum_n E_q(f0)[log NB(y_n | mean =
+    exp(G(f0)), dispersion r)], lvn = log r, 1e-3 <= r <= 1e3 (tgp_ell_flow_f64 with TGP_LIK_NEGBIN).  Returns dict(ell, g_lvn,
+    g_mu, g_v, g_theta, g_rowp); g_lvn = dELL/dlvn."""
+    return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_NEGBIN)
+
+
 def ell_hetero(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     """Heteroscedastic Gaussian ELL with gradients, y ~ N(G(f), exp(lvn + h)): mu, v of shape (2, N), row 0 the moments of q(f),
     row 1 those of the log-noise GP q(h), which integrates out in closed form (tgp_ell_hetero_f64, one launch).  `flow` a
@@ -1184,6 +1194,11 @@ EllStudentFunction = _EllOf(
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_student(Y, mu, v, lvn, df, flow, theta, S, rowp)),
     """apply(Y, mu, v, lvn, df, theta, rowp, flow, S): ELL of the Student-t likelihood with autograd in (mu, v, log_var_noise,
     theta, rowp) and none in `df`.""")
+EllNegBinFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp)),
+    """apply(Y, mu, v, lvn, theta, rowp, flow, S): ELL of the negative-binomial likelihood with autograd in (mu, v, the log
+    dispersion, theta, rowp).""")
 EllHeteroFunction = _EllOf(
     lambda Y, mu, v, lvn, theta, rowp, flow, S, scale: (
         Y, mu, v, lvn, theta, rowp,
@@ -1360,7 +1375,8 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     lik = lib.LIK_POISSON: m1 = E[y], m2 = Var[y] in counts, logp = the log predictive pmf at Y (finite however small).
     lik = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom and squared scale exp(lvn): m1, m2 in standardised units
     (m2 includes sigma^2 df / (df - 2)), logp = the exact log predictive density of the raw target, every constant and
-    -log Y_std included."""
+    -log Y_std included.
+    lik = lib.LIK_NEGBIN: as LIK_POISSON with the dispersion r = exp(lvn): m2 = m1 + (1 + 1/r) E[mean^2] - m1^2."""
     lib = L.load()
     if lik == L.LIK_STUDENT:
         if flow is None:

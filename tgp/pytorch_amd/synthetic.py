@@ -93,6 +93,21 @@ def counts_dataset(seed=0):
     return X, Y.astype(np.float64).reshape(-1, 1)
 
 
+OVERDISPERSED_R = 2.0      # the dispersion of synthetic_overdispersed
+
+
+def overdispersed_dataset(seed=0):
+    """Seeded `synthetic_overdispersed`: the inputs and the latent log-mean of synthetic_counts, y ~ NB(mean = exp(1 + sin(2 x0)
+    + 0.5 x1), r = OVERDISPERSED_R) drawn as a Gamma-Poisson mixture, y ~ Poisson(mean Gamma(r, 1) / r): Var = mean + mean^2 / r.
+    Returns numpy float64 X (n, d) and Y (n, 1) with integer counts >= 0."""
+    n, d = COUNTS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    mean = np.exp(1.0 + np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1])
+    Y = rng.poisson(mean * rng.gamma(OVERDISPERSED_R, 1.0 / OVERDISPERSED_R, size=n))
+    return X, Y.astype(np.float64).reshape(-1, 1)
+
+
 # robust-regression stand-in: (rows, inputs, training rows)
 OUTLIERS_SHAPE = (1000, 2, 900)
 OUTLIERS_SHARE = 0.1
