@@ -498,10 +498,69 @@ size_t tgp_cholesky_workspace_bytes(int32_t M);
  *   C = alpha * op(A) op(B) + beta * C, row-major, op = transpose when trans_* != 0.
  * m, n multiples of 128, k a multiple of 16, lda/ldb even, A and B 16-byte aligned (callers pad).  `tri` declares triangular operands so that the k range
  * is trimmed per output tile: 1 op(A) lower, 2 op(A) upper, 4 op(B) lower, 8 op(B) upper, 16 compute only the
- * lower block triangle of C (flags OR-ed; 0 = general). */
+ * lower block triangle of C (flags OR-ed; 0 = general).  A misaligned A / B, and a leading dimension that is odd (lda, ldb)
+ * or shorter than the row it strides (lda, ldb, ldc), are refused with that argument's code. */
 int tgp_gemm_f64(int32_t trans_a, int32_t trans_b, int32_t tri, int32_t m, int32_t n, int32_t k, double alpha,
                  const double* A, int32_t lda, const double* B, int32_t ldb, double beta, double* C, int32_t ldc,
                  void* stream);
+
+/* The same contraction with everything the tiled kernels can fuse into it, as one descriptor:
+ *   x = alpha * (op(A) o a_mul * diag(k_scale)) op(B) + gamma * add;  x *= col_scale[j] * row_scale[i];
+ *   x += rowv[i] * colv[j];  C = x + beta * C
+ * Fields 1-14 are tgp_gemm_f64's arguments in its order, so that a refusal carries the same code from both entries:
+ * the return value of tgp_gemm_ex_f64 / tgp_gemm_route is -(number of the offending FIELD, counted from 1 as numbered
+ * below); -1 also stands for a NULL descriptor.  Every optional pointer is NULL when unused.
+ *   a_mul     matrix with A's shape and leading dimension, multiplied into A element by element (16-byte aligned)
+ *   k_scale   (k) scales of the contraction index (16-byte aligned)
+ *   add       (m, n) with leading dimension ldadd >= n; excludes beta != 0 (the epilogue reads one extra matrix)
+ *   rowv, colv  the rank-one term: both or neither
+ *   ksplit    >= 1: the k range of every output tile is cut into ksplit slabs of whole 16-wide stages; slab z is written,
+ *             epilogue included, to C + z * cz (cz >= (m - 1) * ldc + n doubles) and the CALLER adds the slabs
+ *   xcd       workgroup -> tile order: 0 natural, 1 the column tiles of a tile row share an XCD, 2 the tiles of a k slab
+ *             share an XCD (ksplit a multiple of 8, natural otherwise).  A pure speed choice: results do not depend on it
+ *   scratch   NULL: one launch, as above.  Otherwise ksplit must be 1 and the product takes the route of the M x M
+ *             products of the training step: split-K (min(8, 256 / tiles, k / 64) slabs, fewer than 2 = no split) into
+ *             m * n-double slabs in `scratch`, then a fixed-order reduction C = sum of the slabs + beta * C.  When
+ *             scratch_doubles is too small for the slabs, or add / col_scale / row_scale / rowv is given, it is the unsplit launch. */
+typedef struct tgp_gemm_ex {
+  int32_t trans_a, trans_b, tri; /*  1  2  3 */
+  int32_t m, n, k;               /*  4  5  6 */
+  double alpha;                  /*  7       */
+  const double* A;               /*  8       */
+  int32_t lda;                   /*  9: >= the row length of A as stored (k, or m when trans_a), even */
+  const double* B;               /* 10       */
+  int32_t ldb;                   /* 11: >= the row length of B as stored (n, or k when trans_b), even */
+  double beta;                   /* 12       */
+  double* C;                     /* 13       */
+  int32_t ldc;                   /* 14: >= n */
+  const double* a_mul;           /* 15       */
+  const double* k_scale;         /* 16       */
+  const double* add;             /* 17       */
+  int32_t ldadd;                 /* 18       */
+  double gamma;                  /* 19       */
+  const double* col_scale;       /* 20: (n)  */
+  const double* row_scale;       /* 21: (m)  */
+  const double* rowv;            /* 22: (m)  */
+  const double* colv;            /* 23: (n)  */
+  int32_t ksplit;                /* 24       */
+  size_t cz;                     /* 25       */
+  int32_t xcd;                   /* 26       */
+  double* scratch;               /* 27       */
+  size_t scratch_doubles;        /* 28       */
+} tgp_gemm_ex;
+int tgp_gemm_ex_f64(const tgp_gemm_ex* d, void* stream);
+/* Two independent products in one launch, as the blocked factorisation issues them: a with op(B) transposed (trans_a = 0,
+ * trans_b = 1), b plain (trans_a = trans_b = 0).  Fused when neither has a_mul / k_scale, both or neither have an
+ * epilogue, and ksplit = 1; two launches otherwise.  scratch must be NULL.  Codes: a's field numbers, b's plus 32. */
+int tgp_gemm_pair_ex_f64(const tgp_gemm_ex* a, const tgp_gemm_ex* b, void* stream);
+/* Host only, no pointer is looked at but for its alignment: the kernel and workgroup order the launcher chooses for `d`
+ * (scratch ignored), or the refusal code of tgp_gemm_ex_f64. */
+#define TGP_GEMM_ROUTE_128 0          /* 128 x 128 tiles, natural order (or the caller's xcd 1 / 2)                   */
+#define TGP_GEMM_ROUTE_128_PAIRED 1   /* ... triangular op(B): column tiles j and n/128-1-j share a workgroup          */
+#define TGP_GEMM_ROUTE_128_HEAVY 2    /* ... triangular op(B), unpaired: per-XCD heaviest-column-first order            */
+#define TGP_GEMM_ROUTE_128_TRIANGLE 3 /* ... TRI_C_LOWER with split-K: compact enumeration of the lower block triangle  */
+#define TGP_GEMM_ROUTE_64 4           /* 64 x 64 tiles, 8 waves                                                        */
+int tgp_gemm_route(const tgp_gemm_ex* d);
 
 /* Whitened KL and its gradients: sparse_MF_SP.KLD, models/sparse_MF_SP.py:406-431. out[0] = KL. */
 int tgp_kl_whitened_f64(const double* m, const double* Lam, int32_t M, double* out, double* g_m, double* g_Lam,

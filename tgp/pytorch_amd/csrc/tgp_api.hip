@@ -727,6 +727,18 @@ int tgp_mean_backward_f64(const double* X, int32_t N, int32_t D, const double* a
                               static_cast<hipStream_t>(stream));
 }
 
+// what the kernels' 16-byte operand loads and the row-major layout ask of A, B and the leading dimensions (the codes are
+// tgp_gemm_f64's argument numbers): the launcher would refuse the first two with a bare -1 and not look at the third
+static int check_gemm_operands(int32_t trans_a, int32_t trans_b, int32_t m, int32_t n, int32_t k, const double* A, int32_t lda,
+                               const double* B, int32_t ldb, int32_t ldc) {
+  if (reinterpret_cast<uintptr_t>(A) & 15) return -8;
+  if ((lda & 1) || lda < (trans_a ? m : k)) return -9;
+  if (reinterpret_cast<uintptr_t>(B) & 15) return -10;
+  if ((ldb & 1) || ldb < (trans_b ? k : n)) return -11;
+  if (ldc < n) return -14;
+  return 0;
+}
+
 int tgp_gemm_f64(int32_t trans_a, int32_t trans_b, int32_t tri, int32_t m, int32_t n, int32_t k, double alpha,
                  const double* A, int32_t lda, const double* B, int32_t ldb, double beta, double* C, int32_t ldc,
                  void* stream) {
@@ -737,8 +749,57 @@ int tgp_gemm_f64(int32_t trans_a, int32_t trans_b, int32_t tri, int32_t m, int32
   if (!A) return -8;
   if (!B) return -10;
   if (!C) return -13;
+  if (int rc = check_gemm_operands(trans_a, trans_b, m, n, k, A, lda, B, ldb, ldc)) return rc;
   return launch_gemm_plain(trans_a != 0, trans_b != 0, tri, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc,
                            static_cast<hipStream_t>(stream));
+}
+
+// the descriptor's checks, in field order after tgp_gemm_f64's own (whose codes fields 1-14 share); `ptrs`: A, B, C are required
+static int check_gemm_ex(const tgp_gemm_ex* d, bool ptrs) {
+  if (!d) return -1;
+  if (d->tri < 0 || d->tri > 31) return -3;
+  if (d->m < 1 || d->m % 128) return -4;
+  if (d->n < 1 || d->n % 128) return -5;
+  if (d->k < 1 || d->k % 16) return -6;
+  if (ptrs && !d->A) return -8;
+  if (ptrs && !d->B) return -10;
+  if (ptrs && !d->C) return -13;
+  if (int rc = check_gemm_operands(d->trans_a, d->trans_b, d->m, d->n, d->k, d->A, d->lda, d->B, d->ldb, d->ldc)) return rc;
+  if (reinterpret_cast<uintptr_t>(d->a_mul) & 15) return -15;
+  if (reinterpret_cast<uintptr_t>(d->k_scale) & 15) return -16;
+  if (d->add && d->beta != 0.0) return -17;
+  if (d->add && d->ldadd < d->n) return -18;
+  if (!d->rowv != !d->colv) return d->rowv ? -23 : -22;  // the rank-one term needs both vectors
+  if (d->ksplit < 1) return -24;
+  if (d->scratch && d->ksplit != 1) return -24;
+  if (!d->scratch && d->ksplit > 1 && d->cz < (size_t)(d->m - 1) * (size_t)d->ldc + (size_t)d->n) return -25;
+  if (d->xcd < 0 || d->xcd > 2) return -26;
+  if (reinterpret_cast<uintptr_t>(d->scratch) & 7) return -27;
+  return 0;
+}
+
+int tgp_gemm_ex_f64(const tgp_gemm_ex* d, void* stream) {
+  if (int rc = check_gemm_ex(d, true)) return rc;
+  return launch_gemm_ex(*d, static_cast<hipStream_t>(stream));
+}
+
+int tgp_gemm_pair_ex_f64(const tgp_gemm_ex* a, const tgp_gemm_ex* b, void* stream) {
+  if (!a) return -1;
+  if (!b) return -1 - 32;
+  if (int rc = check_gemm_ex(a, true)) return rc;
+  if (a->trans_a != 0) return -1;
+  if (a->trans_b == 0) return -2;
+  if (a->scratch) return -27;
+  if (int rc = check_gemm_ex(b, true)) return rc - 32;
+  if (b->trans_a != 0) return -1 - 32;
+  if (b->trans_b != 0) return -2 - 32;
+  if (b->scratch) return -27 - 32;
+  return launch_gemm_pair_ex(*a, *b, static_cast<hipStream_t>(stream));
+}
+
+int tgp_gemm_route(const tgp_gemm_ex* d) {
+  if (int rc = check_gemm_ex(d, false)) return rc;
+  return gemm_route_ex(*d);
 }
 
 int tgp_kl_whitened_f64(const double* m, const double* Lam, int32_t M, double* out, double* g_m, double* g_Lam,

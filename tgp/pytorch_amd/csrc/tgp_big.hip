@@ -204,8 +204,9 @@ static bool gemm_has_epi(const GemmArgs& g) {
 
 static int launch_gemm64(bool tb, const GemmArgs& g, hipStream_t st);
 
-int launch_gemm(bool ta, bool tb, const GemmArgs& g_in, hipStream_t st) {
-  GemmArgs g = g_in;
+// The launcher's whole decision, shared by launch_gemm and the host-only query tgp_gemm_route: normalises `g` (pair, xcd)
+// and returns the kernel and workgroup order it gets (TGP_GEMM_ROUTE_*), or -1 where gemm_normalise refuses.
+static int gemm_route(bool ta, bool tb, GemmArgs& g) {
   if (gemm_normalise(g)) return -1;
   {
     // products without operand modifiers, with a (possibly triangular) op(B), whose 128 x 128 tiling leaves the chip mostly
@@ -226,12 +227,21 @@ int launch_gemm(bool ta, bool tb, const GemmArgs& g_in, hipStream_t st) {
       long small8 = (rows2 * per_row2 + 255) / 256;
       const long longest2 = 2 * (tri ? nj2 : 2 * kb);
       if (small8 < longest2) small8 = longest2;
-      if (small8 * 10 < big * 8 * 7) return launch_gemm64(tb, g, st);   // predicted at least 30 % faster
+      if (small8 * 10 < big * 8 * 7) return TGP_GEMM_ROUTE_64;   // predicted at least 30 % faster
     }
   }
-  const bool mod = g.a_mul != nullptr || g.k_scale != nullptr;
-  const bool epi = g.add != nullptr || g.beta != 0.0 || g.col_scale || g.row_scale || g.rowv || g.colv;
-  return launch_gemm128(ta, tb, mod, epi, g, st);
+  if (g.xcd == 3) return TGP_GEMM_ROUTE_128_TRIANGLE;
+  if (g.pair) return TGP_GEMM_ROUTE_128_PAIRED;
+  if (g.xcd == 4) return TGP_GEMM_ROUTE_128_HEAVY;
+  return TGP_GEMM_ROUTE_128;
+}
+
+int launch_gemm(bool ta, bool tb, const GemmArgs& g_in, hipStream_t st) {
+  GemmArgs g = g_in;
+  const int route = gemm_route(ta, tb, g);
+  if (route < 0) return -1;
+  if (route == TGP_GEMM_ROUTE_64) return launch_gemm64(tb, g, st);
+  return launch_gemm128(ta, tb, gemm_has_mod(g), gemm_has_epi(g), g, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2204,6 +2214,27 @@ int launch_big_cholesky_bwd(const double* L, const double* Linv, const double* L
 int launch_gemm_plain(bool ta, bool tb, int tri, int m, int n, int k, double alpha, const double* A, int lda, const double* B,
                       int ldb, double beta, double* C, int ldc, hipStream_t st) {
   return launch_gemm(ta, tb, gemm_args(A, lda, B, ldb, C, ldc, m, n, k, alpha, beta, tri), st);
+}
+
+// diagnostic / test entries on the descriptor of the C ABI: every field of GemmArgs a caller may set
+static GemmArgs gemm_args_ex(const tgp_gemm_ex& d) {
+  GemmArgs g = gemm_args(d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.m, d.n, d.k, d.alpha, d.beta, d.tri);
+  g.a_mul = d.a_mul; g.k_scale = d.k_scale; g.add = d.add; g.ldadd = d.ldadd; g.gamma = d.gamma;
+  g.col_scale = d.col_scale; g.row_scale = d.row_scale; g.rowv = d.rowv; g.colv = d.colv;
+  g.ksplit = d.ksplit; g.cz = d.cz; g.xcd = d.xcd;
+  return g;
+}
+int launch_gemm_ex(const tgp_gemm_ex& d, hipStream_t st) {
+  const GemmArgs g = gemm_args_ex(d);
+  if (d.scratch) return gemm_mm_on(d.trans_a != 0, d.trans_b != 0, g, d.scratch, d.scratch_doubles, st);
+  return launch_gemm(d.trans_a != 0, d.trans_b != 0, g, st);
+}
+int launch_gemm_pair_ex(const tgp_gemm_ex& a, const tgp_gemm_ex& b, hipStream_t st) {
+  return launch_gemm_pair_ft_ff(gemm_args_ex(a), gemm_args_ex(b), st);
+}
+int gemm_route_ex(const tgp_gemm_ex& d) {
+  GemmArgs g = gemm_args_ex(d);
+  return gemm_route(d.trans_a != 0, d.trans_b != 0, g);
 }
 
 }  // namespace tgp

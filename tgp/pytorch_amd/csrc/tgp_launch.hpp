@@ -80,6 +80,11 @@ int launch_big_cholesky_bwd(const double* L, const double* Linv, const double* L
                             size_t ws_doubles, hipStream_t st);
 int launch_gemm_plain(bool ta, bool tb, int tri, int m, int n, int k, double alpha, const double* A, int lda, const double* B,
                       int ldb, double beta, double* C, int ldc, hipStream_t st);
+// the descriptor entries (arguments checked by the caller): launch_gemm, or gemm_mm_on's split-K + reduction when d.scratch
+// is given; launch_gemm_pair_ft_ff; the route launch_gemm would take (TGP_GEMM_ROUTE_*, -1 where it refuses)
+int launch_gemm_ex(const tgp_gemm_ex& d, hipStream_t st);
+int launch_gemm_pair_ex(const tgp_gemm_ex& a, const tgp_gemm_ex& b, hipStream_t st);
+int gemm_route_ex(const tgp_gemm_ex& d);
 
 // One factorisation for every M <= TGP_BIG_MAX_M: the single-workgroup kernel up to TGP_FUSED_MAX_M, above it the blocked one,
 // which alone needs scratch -- chol_ws_doubles(M) doubles at `cws`, a whole number of 64-double sections.

@@ -77,6 +77,19 @@ class TgpSoftmax(C.Structure):
                 ("step_dev", _dp), ("row0", C.c_int64)]
 
 
+class TgpGemmEx(C.Structure):
+    # (the field order is the code of a refusal: -(position, counted from 1))
+    _fields_ = [("trans_a", C.c_int32), ("trans_b", C.c_int32), ("tri", C.c_int32), ("m", C.c_int32), ("n", C.c_int32),
+                ("k", C.c_int32), ("alpha", C.c_double), ("A", _dp), ("lda", C.c_int32), ("B", _dp), ("ldb", C.c_int32),
+                ("beta", C.c_double), ("C", _dp), ("ldc", C.c_int32), ("a_mul", _dp), ("k_scale", _dp), ("add", _dp),
+                ("ldadd", C.c_int32), ("gamma", C.c_double), ("col_scale", _dp), ("row_scale", _dp), ("rowv", _dp),
+                ("colv", _dp), ("ksplit", C.c_int32), ("cz", C.c_size_t), ("xcd", C.c_int32), ("scratch", _dp),
+                ("scratch_doubles", C.c_size_t)]
+
+
+GEMM_ROUTE_128, GEMM_ROUTE_128_PAIRED, GEMM_ROUTE_128_HEAVY, GEMM_ROUTE_128_TRIANGLE, GEMM_ROUTE_64 = 0, 1, 2, 3, 4
+
+
 class TgpError(RuntimeError):
     pass
 
@@ -116,6 +129,9 @@ _SIGS = {
     "tgp_cholesky_f64": (C.c_int, [_dp, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_gemm_f64": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, _dp, C.c_int32,
                                _dp, C.c_int32, C.c_double, _dp, C.c_int32, _dp]),
+    "tgp_gemm_ex_f64": (C.c_int, [C.POINTER(TgpGemmEx), _dp]),
+    "tgp_gemm_pair_ex_f64": (C.c_int, [C.POINTER(TgpGemmEx), C.POINTER(TgpGemmEx), _dp]),
+    "tgp_gemm_route": (C.c_int, [C.POINTER(TgpGemmEx)]),
     "tgp_cholesky_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "tgp_cholesky_bwd_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "tgp_cholesky_bwd_f64": (C.c_int, [_dp, _dp, _dp, C.c_int32, _dp, _dp, C.c_size_t, _dp]),

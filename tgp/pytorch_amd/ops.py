@@ -965,6 +965,77 @@ def gemm(A, B, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, C=None, tri=0)
     return C
 
 
+def _rows(t, name):
+    """(pointer, leading dimension) of a 2-D float64 device tensor whose rows are contiguous: a view into a wider buffer
+    keeps its stride as the leading dimension."""
+    if t is None:
+        return None, 0
+    if not t.is_cuda or t.dtype != torch.float64 or t.dim() != 2 or t.stride(1) != 1:
+        raise L.TgpError("gemm: %s must be a 2-D float64 device tensor with contiguous rows" % name)
+    return L.C.c_void_p(t.data_ptr()), t.stride(0)
+
+
+def gemm_desc(A, B, C, trans_a=False, trans_b=False, tri=0, alpha=1.0, beta=0.0, a_mul=None, k_scale=None, add=None, gamma=0.0,
+              col_scale=None, row_scale=None, rowv=None, colv=None, ksplit=1, xcd=0, scratch=None):
+    """The tgp_gemm_ex descriptor of C = epilogue(alpha (op(A) o a_mul diag(k_scale)) op(B)) (include/tgp_hip.h).  A, B, C,
+    a_mul and add may be row-strided views; with ksplit > 1 and no scratch, C is (ksplit, m, n): slab z at C[z]."""
+    d = L.TgpGemmEx()
+    d.A, d.lda = _rows(A, "A")
+    d.B, d.ldb = _rows(B, "B")
+    m, k = (A.shape[1], A.shape[0]) if trans_a else (A.shape[0], A.shape[1])
+    k2, n = (B.shape[1], B.shape[0]) if trans_b else (B.shape[0], B.shape[1])
+    if k != k2:
+        raise L.TgpError("gemm: inner dimensions differ (%d vs %d)" % (k, k2))
+    if C.dim() == 3:
+        if C.shape[0] != ksplit or scratch is not None:
+            raise L.TgpError("gemm: a 3-D C holds the ksplit slabs of a product without scratch")
+        d.cz, C = C.stride(0), C[0]
+    if tuple(C.shape) != (m, n):
+        raise L.TgpError("gemm: C is %s, the product %d x %d" % (tuple(C.shape), m, n))
+    d.C, d.ldc = _rows(C, "C")
+    if a_mul is not None:
+        d.a_mul, ldm = _rows(a_mul, "a_mul")
+        if tuple(a_mul.shape) != tuple(A.shape) or ldm != d.lda:
+            raise L.TgpError("gemm: a_mul must have A's shape and leading dimension")
+    d.add, d.ldadd = _rows(add, "add")
+    for name, v, length in (("k_scale", k_scale, k), ("col_scale", col_scale, n), ("row_scale", row_scale, m), ("rowv", rowv, m),
+                            ("colv", colv, n)):
+        if v is not None:
+            if v.numel() != length:
+                raise L.TgpError("gemm: %s has %d entries, not %d" % (name, v.numel(), length))
+            setattr(d, name, L.ptr(v))
+    d.trans_a, d.trans_b, d.tri, d.m, d.n, d.k = int(bool(trans_a)), int(bool(trans_b)), int(tri), m, n, k
+    d.alpha, d.beta, d.gamma, d.ksplit, d.xcd = float(alpha), float(beta), float(gamma), int(ksplit), int(xcd)
+    if scratch is not None:
+        d.scratch, d.scratch_doubles = L.ptr(scratch), scratch.numel()
+    return d
+
+
+def gemm_ex(A, B, C, **kw):
+    """tgp_gemm_ex_f64 on gemm_desc's arguments: the tiled float64 GEMM with its operand modifiers, epilogue terms, split-K
+    slabs (or, with `scratch`, the split-K + reduction route of the step's M x M products) and workgroup orders."""
+    L.check(L.load().tgp_gemm_ex_f64(L.C.byref(gemm_desc(A, B, C, **kw)), L.stream_ptr()), "tgp_gemm_ex_f64")
+    return C
+
+
+def gemm_pair_ex(a, b):
+    """tgp_gemm_pair_ex_f64: two gemm_desc products (a with op(B) transposed, b plain) in one launch where they qualify."""
+    L.check(L.load().tgp_gemm_pair_ex_f64(L.C.byref(a), L.C.byref(b), L.stream_ptr()), "tgp_gemm_pair_ex_f64")
+
+
+def gemm_route(m, n, k, trans_a=False, trans_b=False, tri=0, beta=0.0, ksplit=1, xcd=0, mod=False):
+    """tgp_gemm_route: the kernel and workgroup order (lib.GEMM_ROUTE_*) the launcher gives a product of this shape, or its
+    refusal code.  Host only: no device, no operand (mod: as if a_mul / k_scale were given)."""
+    d = L.TgpGemmEx()
+    d.trans_a, d.trans_b, d.tri, d.m, d.n, d.k = int(bool(trans_a)), int(bool(trans_b)), int(tri), m, n, k
+    d.lda, d.ldb, d.ldc = (m if trans_a else k), (k if trans_b else n), n
+    d.alpha, d.beta, d.ksplit, d.xcd = 1.0, float(beta), int(ksplit), int(xcd)
+    d.cz = m * n
+    if mod:
+        d.k_scale = L.C.c_void_p(16)        # never dereferenced
+    return L.load().tgp_gemm_route(L.C.byref(d))
+
+
 def kl_whitened(m, Lam):
     """Whitened KL and gradients (models/sparse_MF_SP.py:406-431): returns (KL 0-d, g_m, g_Lam)."""
     lib = L.load()
