@@ -285,10 +285,11 @@ def test_pred_matches_torch_per_row():
     from tgp.pytorch_amd import ops
     g = load_golden("bern_med_bcl_al2")
     theta = g["params"]["theta"]
-    P, _, _ = ops.predict(g["mu"].to(DEV), g["v"].to(DEV), torch.zeros(1, dtype=F64, device=DEV),
-                          _spec(g["program"], theta.numel()), theta.to(DEV), 32, lik=L.LIK_BERNOULLI)
-    xs, ws = (torch.tensor(a) for a in np.polynomial.hermite.hermgauss(32))
-    assert rel_err(P.cpu(), pred_torch(g["mu"], g["v"], g["program"], theta, xs, ws)) < TOL_VAL
+    for S in (32, 1, 5):      # (1: one partly filled group of four nodes; 5: a full group and a one-node tail)
+        P, _, _ = ops.predict(g["mu"].to(DEV), g["v"].to(DEV), torch.zeros(1, dtype=F64, device=DEV),
+                              _spec(g["program"], theta.numel()), theta.to(DEV), S, lik=L.LIK_BERNOULLI)
+        xs, ws = (torch.tensor(a) for a in np.polynomial.hermite.hermgauss(S))
+        assert rel_err(P.cpu(), pred_torch(g["mu"], g["v"], g["program"], theta, xs, ws)) < TOL_VAL, S
 
 
 def test_fully_bayesian_prediction_is_an_mc_average():

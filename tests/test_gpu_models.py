@@ -103,6 +103,22 @@ def test_evaluation_path_matches_reference(name, flow):
     mu, v = model.marginal_variational_qf_parameters(g["X"].to(DEV), diagonal=True, is_duvenaud=False)
     assert mu.shape == (1, g["X"].shape[0], 1) and rel_err(mu.cpu().reshape(-1), g["mu"]) < 1e-9
     assert rel_err(model.KLD().cpu(), g["KLD"]) < 1e-12
+    if flow is None:
+        return
+    # the predictive kernel on the same moments against the oracle at node counts the fixtures do not hold: one partly filled
+    # group of four nodes, and a full group with a one-node tail
+    from tgp.pytorch_amd import ops
+    p = g["params"]
+    spec = ops.FlowSpec([tuple(int(x) for x in b) for b in g["program"]], p["theta"].numel(), 0, DEV)
+    ystd = float(Y_std[0])
+    for S in (1, 5):
+        xs, ws = (torch.tensor(a) for a in np.polynomial.hermite.hermgauss(S))
+        k1, k2, klp = ops.predict(g["mu"].to(DEV), g["v"].to(DEV), p["log_var_noise"].reshape(-1)[:1].to(DEV), spec,
+                                  p["theta"].to(DEV), S, Y=g["Y"].reshape(-1).to(DEV), Y_std=ystd)
+        o1, o2 = orc.marginal_moments_flow(g["mu"], g["v"], p["log_var_noise"], g["program"], p["theta"], xs, ws)
+        olp = orc.test_log_lik_flow(g["Y"].reshape(-1), g["mu"], g["v"], p["log_var_noise"], g["program"], p["theta"], xs, ws, ystd)
+        klp = klp.cpu() + 0.5 * math.log(math.pi) - 0.5 * orc.LOG_PI_REF_F32    # (the kernel leaves the constant to its caller)
+        assert rel_err(klp, olp) < 1e-9 and rel_err(k1.cpu(), o1) < 1e-9 and rel_err(k2.cpu(), o2) < 1e-8, S
 
 
 @pytest.mark.parametrize("resident", [True, False])

@@ -198,7 +198,7 @@ def test_extremes(r):
 
 
 # ---- 3. the prediction kernel ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("S", [32, 80])
+@pytest.mark.parametrize("S", [32, 80, 1, 5])      # (1: one partly filled group of four nodes; 5: a full group and a one-node tail)
 @pytest.mark.parametrize("case", CASES)
 def test_predict_matches_restatement(case, S):
     from tgp.pytorch_amd import lib as L
@@ -219,10 +219,10 @@ def test_predict_matches_restatement(case, S):
         vc = v.clamp(min=0.0)
         c1, c2 = torch.exp(mu + 0.5 * vc), torch.exp(2.0 * mu + 2.0 * vc)
         assert rel_err(m1.cpu(), c1) < TOL_VAL and rel_err(m2.cpu(), c1 + (1.0 + 1.0 / r) * c2 - c1 * c1) < TOL_VAL
-        # ... which the quadrature of the restatement reproduces
+        # ... which the quadrature of the restatement reproduces (from 32 nodes on)
         wn = (ws / np.sqrt(np.pi)).reshape(-1, 1)
         gq = mu.reshape(1, -1) + torch.sqrt(2.0 * vc).reshape(1, -1) * xs.reshape(-1, 1)
-        assert rel_err((wn * torch.exp(gq)).sum(0), c1) < TOL_VAL and rel_err((wn * torch.exp(2.0 * gq)).sum(0), c2) < TOL_VAL
+        assert S < 32 or (rel_err((wn * torch.exp(gq)).sum(0), c1) < TOL_VAL and rel_err((wn * torch.exp(2.0 * gq)).sum(0), c2) < TOL_VAL)
     # without targets: moments only, no logp
     m1b, m2b, none = ops.predict(mu.to(DEV), v.to(DEV), lam.to(DEV), _spec(program, P, RP), _dev(theta), S, _dev(rowp),
                                  lik=L.LIK_NEGBIN)

@@ -166,7 +166,7 @@ def test_extremes():
 
 # ---- 3. the prediction kernel ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nu", [2.5, 30.0])
-@pytest.mark.parametrize("S", [20, 50])
+@pytest.mark.parametrize("S", [20, 50, 1, 5])      # (1: one partly filled group of four nodes; 5: a full group and a one-node tail)
 @pytest.mark.parametrize("case", ["empty", "sal2", "flows_med_arcsl2", "idsal"])
 def test_predict_matches_restatement(case, S, nu):
     from tgp.pytorch_amd import lib as L
@@ -186,7 +186,8 @@ def test_predict_matches_restatement(case, S, nu):
     if case == "empty":
         vc = v.clamp(min=0.0)
         assert float((m1.cpu() - mu).abs().max()) < TOL_VAL
-        assert rel_err(m2.cpu(), vc + 0.07 * nu / (nu - 2.0)) < TOL_VAL
+        # (one node carries no spread: S = 1 gives sigma^2 nu / (nu - 2) alone; from S = 2 on the rule is exact for f^2)
+        assert rel_err(m2.cpu(), (vc if S > 1 else 0.0 * vc) + 0.07 * nu / (nu - 2.0)) < TOL_VAL
     # without targets: moments only
     m1b, m2b, none = ops.predict(mu.to(DEV), v.to(DEV), lvn.to(DEV), _spec(program, P, RP), _dev(theta), S, _dev(rowp),
                                  lik=L.LIK_STUDENT, df=nu)

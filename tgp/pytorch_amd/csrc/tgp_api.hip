@@ -1052,24 +1052,10 @@ static int check_quantile_model(const tgp_model* model, const double* mu, const 
                                 bool* flowed) {
   if (refuse_hetero(model, entry)) return TGP_E_UNSUPPORTED;
   if (!model || model->N < 1 || !model->log_var_noise) return -1;
-  if (model->lik == TGP_LIK_POISSON) {
-    set_error_text("%s: no quantiles for TGP_LIK_POISSON: the predictive is discrete (its pmf is tgp_predict_f64's logp, one row "
-                   "per count)", entry);
-    return TGP_E_UNSUPPORTED;
-  }
-  if (model->lik == TGP_LIK_NEGBIN) {
-    set_error_text("%s: no quantiles for TGP_LIK_NEGBIN: the predictive is discrete (its pmf is tgp_predict_f64's logp, one row "
-                   "per count)", entry);
-    return TGP_E_UNSUPPORTED;
-  }
-  if (model->lik == TGP_LIK_STUDENT) {
-    set_error_text("%s: no quantiles for TGP_LIK_STUDENT: the CDF of a Student-t mixture needs the incomplete beta function "
-                   "(its density is tgp_predict_f64's logp)", entry);
-    return TGP_E_UNSUPPORTED;
-  }
-  if (model->lik == TGP_LIK_BERNOULLI || model->lik == TGP_LIK_WARPED || model->lik == TGP_LIK_SOFTMAX) {
-    set_error_text("%s: no quantiles for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only; a warped model's are "
-                   "T^-1(mu + z sqrt(v + noise)) through tgp_flow_inverse_f64)", entry, model->lik);
+  const LikRow* row = lik_row(model->lik);
+  if (!row) return -1;
+  if (row->no_quantiles) {
+    set_error_text("%s: no quantiles for %s", entry, row->no_quantiles);
     return TGP_E_UNSUPPORTED;
   }
   if (model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW) return -1;

@@ -1,6 +1,7 @@
-// tgp_ell.hpp -- the quadrature likelihood through the flow as templates over a likelihood policy: the policies, k_ell_quad with its
-// launch helpers and the count predictive k_predict_count.  tgp_lik.hip instantiates them for the Gaussian, Bernoulli, Poisson,
-// Student-t and heteroscedastic policies, tgp_lik_negbin.hip for the negative-binomial one (a unit of its own for the compile time).
+// tgp_ell.hpp -- the quadrature likelihood through the flow as templates over a likelihood policy: the training policies and
+// k_ell_quad, the predictive policies and k_predict_quad, each with its launch helper.  tgp_lik.hip instantiates them for the
+// Gaussian, Bernoulli, Poisson, Student-t and heteroscedastic policies and holds the table of likelihoods (lik_row),
+// tgp_lik_negbin.hip instantiates them for the negative-binomial policy (a unit of its own for the compile time).
 #pragma once
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
@@ -17,7 +18,7 @@ namespace tgp {
 //   heteroscedastic Gaussian (no counterpart in the reference), log noise variance c + h, h a second latent GP (TGP_LIK_HETERO)
 // ---------------------------------------------------------------------------------------------------
 
-// The node term shared by k_ell_quad<EllBern> and k_predict_bern.  With a = |g|, t = a / sqrt 2:
+// The node term shared by k_ell_quad<EllBern> and PredBern.  With a = |g|, t = a / sqrt 2:
 //   Phi(-a) = erfc(t) / 2 = erfcx(t) exp(-a^2 / 2) / 2      log Phi(-a) = log(erfcx(t) / 2) - a^2 / 2
 //   Phi(a)  = 1 - erfc(t) / 2                                log Phi(a)  = log1p(-erfc(t) / 2)
 //   lambda(z) = phi(z) / Phi(z):  lambda(-a) = sqrt(2 / pi) / erfcx(t),  lambda(a) = phi(a) / Phi(a)
@@ -51,8 +52,9 @@ __device__ inline BernNode bern_node(double g, double y) {
 // kRowTerm: log p has a part that depends on y alone, row_term(y), which the kernel adds once per row instead of once per node.
 // kRowNoise (with kRowTerm and kNoise): that part depends on the launch constants too -- row_term(y, K) -- and so does its
 // derivative in eta, row_deta(y, K), which a row adds once to the noise adjoint (partial slot 1) beside its nodes' dlog_p_deta.
-// The count policies (EllPois, EllNegBin) also serve k_predict_count: rate(t) = exp(g) of a node, and kOverDisp says whether the
-// conditional variance exceeds the mean, by mean^2 excess(K); plus_log_p(a, t, K) = a + log_p(t, K), a the log weight of the node.
+// The count policies (EllPois, EllNegBin) also serve the predictive policy PredCount: rate(t) = exp(g) of a node, and kOverDisp
+// says whether the conditional variance exceeds the mean, by mean^2 excess(K); plus_log_p(a, t, K) = a + log_p(t, K), a the log
+// weight of the node.
 // kBlockTerm: log p has a part that is the same for every row and node, block_term(K), which the kernel adds once per
 // workgroup, times its number of rows (the weights of a row sum to 1).
 // kRowConst: the constants differ from row to row.  mu, v, g_mu, g_v are then (2,N): row 1 holds the moments of a second latent
@@ -103,7 +105,7 @@ struct EllPois {
   static constexpr bool kRowNoise = false;
   static constexpr bool kBlockTerm = false;
   static constexpr bool kRowConst = false;
-  static constexpr bool kOverDisp = false;   // k_predict_count: Var[y | rate] = rate
+  static constexpr bool kOverDisp = false;   // PredCount: Var[y | rate] = rate
   static __device__ __forceinline__ EllNone consts(const double*) { return {}; }
   static __device__ __forceinline__ PoisNode at(double g, double y, const EllNone&) { return {g, exp(g), y}; }
   static __device__ __forceinline__ double log_p(const PoisNode& t, const EllNone&) { return t.y * t.g - t.e; }
@@ -111,7 +113,7 @@ struct EllPois {
     return scale * w * (t.y - t.e);
   }
   static __device__ __forceinline__ double row_term(double y) { return -lgamma(y + 1.0); }
-  static __device__ __forceinline__ double rate(const PoisNode& t) { return t.e; }   // k_predict_count: exp(g)
+  static __device__ __forceinline__ double rate(const PoisNode& t) { return t.e; }   // PredCount: exp(g)
   // a + log_p, in the order the predictive has always summed it
   static __device__ __forceinline__ double plus_log_p(double a, const PoisNode& t, const EllNone&) { return a + t.y * t.g - t.e; }
 };
@@ -300,82 +302,228 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
   for (int j = tid; j < P; j += 256) pb[2 + j] = (accw[j] + accw[P + j]) + (accw[2 * P + j] + accw[3 * P + j]);
 }
 
-// The predictive of a count likelihood per row (Lik = EllPois, EllNegBin), g_s = G(mu + sqrt(2 v) x_s) the log-rate at node s
-// (v <= 0 counts as 0).  Poisson:
+// ---------------------------------------------------------------------------------------------------
+// Prediction given the q(f) moments of a row: m1, m2 and the test log-likelihood logp, by the same Gauss-Hermite sweep through
+// the flow, g_s = G(mu + sqrt(2 v) x_s), as a template over a predictive policy (k_predict_quad).  A policy supplies
+//   kClampV                     v <= 0 counts as 0 in the sweep
+//   consts(md, fp, Y_std)       its launch constants K, from md.log_var_noise
+//   Acc                         what it sums over the nodes (a small struct that starts at its neutral element)
+//   node(a, w, g, R, K)         adds the node of normalised weight w to a; the nodes arrive in the order s = 0 .. S - 1, the
+//                               padding of the last group of four after them at weight 0
+//   finish(a, R, K)             (m1, m2, logp) from the sums
+//   closed(md, fp)              the launch needs no sweep: closed_row(R, log_var_noise, Y_std) gives the three at once
+// R is the row: mu and v as stored, its target y (0 when no logp is asked for) and want_lp.
+// ---------------------------------------------------------------------------------------------------
+struct PredRow { double m, v, y; bool want_lp; };
+struct PredOut { double m1, m2, lp; };
+
+// log sum_i exp(t_i), kept relative to its running maximum (rescaled when a larger term arrives): finite where every single term
+// underflows -- a count of 10^4 at a rate of e^2 has terms near -10^5.  A term of -inf adds nothing; all of them: -inf.
+struct LogSumExp { double mx = -INFINITY, se = 0.0; };
+__device__ __forceinline__ void lse_push(LogSumExp& l, double t) {
+  if (t > l.mx) { l.se = l.se * exp(l.mx - t) + 1.0; l.mx = t; }
+  else if (t > -INFINITY) l.se += exp(t - l.mx);
+}
+__device__ __forceinline__ double lse_value(const LogSumExp& l) { return l.mx + log(l.se); }
+struct PredSums { double m1 = 0.0, e2 = 0.0; LogSumExp l; };   // sum w x, sum w x^2 and the log-sum-exp of log w + log p(y | g)
+struct PredSweepOnly {   // a policy without a closed form
+  static __device__ __forceinline__ bool closed(const tgp_model&, const FlowProg&) { return false; }
+  static __device__ __forceinline__ PredOut closed_row(const PredRow&, const double*, double) { return {}; }
+};
+
+// Gaussian noise around the flow (TGP_LIK_FLOW) and the plain Gaussian (TGP_LIK_GAUSS), in the standardised units of the targets;
+// logp is the per-row kernel of the test log-likelihood (without the -0.5 log(pi) constant: log w_s = log(wn_s) + 0.5 log(pi), the
+// caller adds the reference's constants)
+//   flow : GaussianNonLinearMean.marginal_moments (:176-203) ; sparse_MF_SP.test_log_likelihood (:705-776)
+//   gauss: GaussianLinearMean.marginal_moments (:89-118)     ; sparse_MF_SP.py:786-799
+// v is not clamped.  Nodes of weight 0 do not enter.  A TGP_LIK_FLOW call with an empty program runs the sweep.
+struct PredGauss {
+  static constexpr bool kClampV = false;
+  struct K { double noise, Y_std, lvar, ivar; };   // of var = Y_std^2 noise: its log and reciprocal
+  using Acc = PredSums;
+  static __device__ __forceinline__ bool closed(const tgp_model& md, const FlowProg&) { return md.lik == TGP_LIK_GAUSS; }
+  static __device__ __forceinline__ PredOut closed_row(const PredRow& R, const double* lvn, double Y_std) {
+    const double m1 = R.m, m2 = exp(lvn[0]) + R.v;
+    if (!R.want_lp) return {m1, m2, 0.0};
+    const double sd = Y_std * sqrt(m2), var = sd * sd, r = Y_std * R.y - Y_std * m1;
+    return {m1, m2, -0.5 * (TGP_LOG_2PI_REF + log(var) + r * r / var)};
+  }
+  static __device__ __forceinline__ K consts(const tgp_model& md, const FlowProg&, double Y_std) {
+    const double noise = exp(md.log_var_noise[0]), sdy = Y_std * sqrt(noise), var = sdy * sdy;
+    return {noise, Y_std, log(var), 1.0 / var};
+  }
+  static __device__ __forceinline__ void node(Acc& a, double w, double g, const PredRow& R, const K& k) {
+    if (!(w > 0.0)) return;
+    a.m1 += w * g;
+    a.e2 += w * g * g;
+    if (R.want_lp) {
+      const double r = k.Y_std * R.y - k.Y_std * g;
+      lse_push(a.l, log(w) - 0.5 * (TGP_LOG_2PI_REF + k.lvar + r * r * k.ivar));
+    }
+  }
+  static __device__ __forceinline__ PredOut finish(const Acc& a, const PredRow& R, const K& k) {
+    return {a.m1, k.noise + a.e2 - a.m1 * a.m1, R.want_lp ? lse_value(a.l) : 0.0};
+  }
+};
+
+// Bernoulli, probit link: P = Phi(mu / sqrt(1 + v)) for the empty program (R&W eq. 3.80, Bernoulli.py marginal_moments; v as
+// stored), else sum_s w_s Phi(g_s), clamped to [0, 1].  P(y = 1) and P(y = 0) are each summed on their own (no 1 - P cancellation).
+// m1 = P, m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (no constant).
+struct PredBern {
+  static constexpr bool kClampV = true;
+  struct Acc { double P1 = 0.0, P0 = 0.0; };
+  static __device__ __forceinline__ bool closed(const tgp_model&, const FlowProg& fp) { return fp.nblk == 0; }
+  // the node term gives log P and log(1 - P) without forming P (finite however far out mu / sqrt(1 + v) is)
+  static __device__ __forceinline__ PredOut closed_row(const PredRow& R, const double*, double) {
+    const BernNode b = bern_node(R.m / sqrt(1.0 + R.v), R.y);
+    return {b.pp, b.pp * b.pm, b.lp};
+  }
+  static __device__ __forceinline__ EllNone consts(const tgp_model&, const FlowProg&, double) { return {}; }
+  static __device__ __forceinline__ void node(Acc& a, double w, double g, const PredRow&, const EllNone&) {
+    const BernNode b = bern_node(g, 0.0);
+    a.P1 += w * b.pp;
+    a.P0 += w * b.pm;
+  }
+  static __device__ __forceinline__ PredOut finish(const Acc& a, const PredRow& R, const EllNone&) {
+    const double P1 = fmin(fmax(a.P1, 0.0), 1.0), P0 = fmin(fmax(a.P0, 0.0), 1.0);
+    if (!R.want_lp) return {P1, P1 * P0, 0.0};
+    return {P1, P1 * P0, (R.y != 0.0 ? R.y * log(P1) : 0.0) + (R.y != 1.0 ? (1.0 - R.y) * log(P0) : 0.0)};
+  }
+};
+
+// Student-t noise (EllStudent's constants), in the standardised units of PredGauss:
+//   m1 = sum_s w_s g_s,  m2 = sum_s w_s g_s^2 - m1^2 + sigma^2 nu / (nu - 2)   (+inf for nu <= 2: no variance),
+//   logp = log sum_s w_s t_nu(y | g_s, sigma) - log Y_std = logsumexp_s(log w_s - (nu + 1) / 2 log1p(r_s^2 / (nu sigma^2)))
+//          + c(nu, eta) - log Y_std,
+// the exact log predictive density of the raw target with every constant.  No closed form (the Gaussian-Student convolution has
+// none): the empty program runs the sweep, and the two moments are exact at S >= 2.  Nodes of weight 0 do not enter.
+struct PredStudent : PredSweepOnly {
+  static constexpr bool kClampV = true;
+  struct K : StudentConst { double Y_std; };
+  using Acc = PredSums;
+  static __device__ __forceinline__ K consts(const tgp_model& md, const FlowProg&, double Y_std) {
+    return {EllStudent::consts(md.log_var_noise), Y_std};
+  }
+  static __device__ __forceinline__ void node(Acc& a, double w, double g, const PredRow& R, const K& k) {
+    if (!(w > 0.0)) return;
+    a.m1 += w * g;
+    a.e2 += w * g * g;
+    if (R.want_lp) {
+      const double r = R.y - g;
+      lse_push(a.l, log(w) - 0.5 * k.nu1 * log1p(r * r * k.inus2));
+    }
+  }
+  static __device__ __forceinline__ PredOut finish(const Acc& a, const PredRow& R, const K& k) {
+    return {a.m1, k.nu > 2.0 ? a.e2 - a.m1 * a.m1 + k.nus2 / (k.nu - 2.0) : INFINITY,
+            R.want_lp ? lse_value(a.l) + student_log_const(k.nu, k.eta) - log(k.Y_std) : 0.0};
+  }
+};
+
+// The count likelihoods (Lik = EllPois, EllNegBin), g_s the log-rate at node s.  Poisson:
 //   m1 = E[y] = sum_s w_s exp(g_s),  m2 = Var[y] = m1 + sum_s w_s exp(2 g_s) - m1^2   (law of total variance; the empty
-//   program: the log-normal closed forms m1 = exp(mu + v / 2), m2 = m1 + (exp(v) - 1) m1^2),
+//   program: the log-normal closed forms m1 = exp(mu + v / 2), m2 = m1 + (exp(v) - 1) m1^2, v <= 0 as 0),
 //   logp = log sum_s w_s Poisson(y | exp(g_s)) = logsumexp_s(log w_s + y g_s - exp(g_s)) - lgamma(y + 1),
-// the log predictive pmf with its constant.  The sum is kept relative to its running maximum (rescaled when a larger term
-// arrives), so logp is finite where every single term underflows -- y = 10^4 at a rate of e^2: terms near -10^5.  Nodes past S
-// and nodes of weight 0 do not enter.  Negative binomial (kOverDisp): the same with the policy's node term and row term,
+// the log predictive pmf with its constant; the empty program takes it from the sweep as well.  Nodes of weight 0 do not enter.
+// Negative binomial (kOverDisp): the same with the policy's node term and row term,
 //   m2 = m1 + (1 + 1/r) sum_s w_s exp(2 g_s) - m1^2   (the empty program: E[mean^2] = exp(2 mu + 2 v) = exp(v) m1^2),
 //   logp = logsumexp_s(log w_s + y u_s - (y + r) sp(u_s)) + lgamma(y + r) - lgamma(r) - lgamma(y + 1).
+template <class Lik>
+struct PredCount : PredSweepOnly {
+  static constexpr bool kClampV = true;
+  struct K { decltype(Lik::consts(nullptr)) lik; bool lognormal; };   // lognormal: the empty program, the moments in closed form
+  using Acc = PredSums;
+  static __device__ __forceinline__ K consts(const tgp_model& md, const FlowProg& fp, double) {
+    return {Lik::consts(md.log_var_noise), fp.nblk == 0};
+  }
+  static __device__ __forceinline__ void node(Acc& a, double w, double g, const PredRow& R, const K& k) {
+    if (!(w > 0.0)) return;
+    const auto nd = Lik::at(g, R.y, k.lik);
+    const double e = Lik::rate(nd);
+    a.m1 += w * e;
+    a.e2 += w * e * e;
+    if (R.want_lp) lse_push(a.l, Lik::plus_log_p(log(w), nd, k.lik));
+  }
+  static __device__ __forceinline__ PredOut finish(const Acc& a, const PredRow& R, const K& k) {
+    const double vn = R.v > 0.0 ? R.v : 0.0;
+    PredOut o;
+    if constexpr (Lik::kOverDisp) {
+      const double c = Lik::excess(k.lik);
+      o.m1 = k.lognormal ? exp(R.m + 0.5 * vn) : a.m1;
+      o.m2 = k.lognormal ? o.m1 + (expm1(vn) + c * exp(vn)) * o.m1 * o.m1 : a.m1 + (1.0 + c) * a.e2 - a.m1 * a.m1;
+    } else {
+      o.m1 = k.lognormal ? exp(R.m + 0.5 * vn) : a.m1;
+      o.m2 = k.lognormal ? o.m1 + expm1(vn) * o.m1 * o.m1 : a.m1 + a.e2 - a.m1 * a.m1;
+    }
+    if (!R.want_lp) o.lp = 0.0;
+    else if constexpr (Lik::kRowNoise) o.lp = lse_value(a.l) + Lik::row_term(R.y, k.lik);
+    else o.lp = lse_value(a.l) + Lik::row_term(R.y);
+    return o;
+  }
+};
+
+// 256 rows per workgroup, one row per lane, NB = 4 nodes per flow_forward_n call; dynamic LDS: 2 (P + 2) doubles.  The last
+// group of four is filled up with node S - 1 again at weight 0.  Y may be null (no logp), m1o and m2o too.
+// The log-sum-exp skips a term of -inf in every policy.  k_predict, which this kernel replaced for PredGauss, had no such guard
+// and let in every node s < S: a row whose every term is -inf now gets logp = -inf where it got NaN, and so does a row whose
+// first node has weight 0 -- which no Gauss-Hermite rule of S <= 256 nodes has: none of their weights underflows, so "weight
+// above 0" and "s < S" name the same nodes there.  On finite terms the two forms are the same arithmetic.
 // X: the extended kind set.
-template <class Lik, bool X>
-__global__ __launch_bounds__(256) void k_predict_count(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                       const double* __restrict__ v, const double* __restrict__ rowp,
-                                                       const double* __restrict__ Y, double* __restrict__ m1o,
-                                                       double* __restrict__ m2o, double* __restrict__ logp) {
+template <class Pred, bool X>
+__global__ __launch_bounds__(256) void k_predict_quad(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                      const double* __restrict__ v, const double* __restrict__ rowp,
+                                                      const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
+                                                      double* __restrict__ m2o, double* __restrict__ logp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* tp = reinterpret_cast<double*>(smem_raw);
   double* tg = tp + (md.P + 2) / 2 * 2;
-  flow_params_lds<X>(md.theta, fp, tp, tg);
+  const bool closed = Pred::closed(md, fp);
+  if (!closed) flow_params_lds<X>(md.theta, fp, tp, tg);
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= md.N) return;
   const bool want_lp = logp && Y;
   const double y = want_lp ? Y[n] : 0.0;
-  const auto K = Lik::consts(md.log_var_noise);
-  FlowDev F{fp.blk, fp.nblk, tp, tg};
-  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-  const double vn = v[n] > 0.0 ? v[n] : 0.0;
-  const double m_ = mu[n], sq = sqrt(2.0 * vn);
-  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
-  constexpr int NB = 4;
-  for (int s0 = 0; s0 < md.S; s0 += NB) {
-    double g[NB], der[NB], wsn[NB];
-    const double* rpn[NB];
-    TGP_EACH(u, NB) {
-      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-      g[u] = m_ + sq * md.xs[s];
-      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-      rpn[u] = rp;
-    }
-    flow_forward_n<NB, false, X>(F, g, rpn, der);
-    TGP_EACH(u, NB) {
-      if (wsn[u] > 0.0) {
-        const auto nd = Lik::at(g[u], y, K);
-        const double e = Lik::rate(nd);
-        m1 += wsn[u] * e;
-        e2 += wsn[u] * e * e;
-        if (want_lp) {
-          const double t = Lik::plus_log_p(log(wsn[u]), nd, K);
-          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
-          else if (t > -INFINITY) se += exp(t - mx);
-        }
-      }
-    }
-  }
-  double m2;
-  if constexpr (Lik::kOverDisp) {
-    const double c = Lik::excess(K);
-    m2 = m1 + (1.0 + c) * e2 - m1 * m1;
-    if (fp.nblk == 0) {
-      m1 = exp(m_ + 0.5 * vn);
-      m2 = m1 + (expm1(vn) + c * exp(vn)) * m1 * m1;
-    }
+  PredOut o;
+  // (each arm reads its row itself, the sweep after its set-up, as the kernels before this one did: read once ahead of the
+  //  branch, the same loads cost PredBern 6 VGPRs, 129 for 123, and with them its fourth wave per SIMD)
+  if (closed) {
+    o = Pred::closed_row(PredRow{mu[n], v[n], y, want_lp}, md.log_var_noise, Y_std);
   } else {
-    m2 = m1 + e2 - m1 * m1;
-    if (fp.nblk == 0) {
-      m1 = exp(m_ + 0.5 * vn);
-      m2 = m1 + expm1(vn) * m1 * m1;
+    const auto K = Pred::consts(md, fp, Y_std);
+    FlowDev F{fp.blk, fp.nblk, tp, tg};
+    const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
+    const PredRow R{mu[n], v[n], y, want_lp};
+    const double vn = Pred::kClampV ? (R.v > 0.0 ? R.v : 0.0) : R.v;
+    const double sq = sqrt(2.0 * vn);
+    typename Pred::Acc a;
+    constexpr int NB = 4;   // quadrature nodes in flight (stage-by-stage evaluation, flow_forward_n)
+    for (int s0 = 0; s0 < md.S; s0 += NB) {
+      double g[NB], der[NB], wsn[NB];
+      const double* rpn[NB];
+      TGP_EACH(u, NB) {
+        const int s = s0 + u < md.S ? s0 + u : md.S - 1;
+        g[u] = R.m + sq * md.xs[s];
+        wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
+        rpn[u] = rp;
+      }
+      flow_forward_n<NB, false, X>(F, g, rpn, der);
+      TGP_EACH(u, NB) Pred::node(a, wsn[u], g[u], R, K);
     }
+    o = Pred::finish(a, R, K);
   }
-  if (m1o) m1o[n] = m1;
-  if (m2o) m2o[n] = m2;
-  if (want_lp) {
-    if constexpr (Lik::kRowNoise) logp[n] = mx + log(se) + Lik::row_term(y, K);
-    else logp[n] = mx + log(se) + Lik::row_term(y);
-  }
+  if (m1o) m1o[n] = o.m1;
+  if (m2o) m2o[n] = o.m2;
+  if (want_lp) logp[n] = o.lp;
+}
+
+// one launch of k_predict_quad<Pred, false> or, for a program with a kind past STEPTANH, k_predict_quad<Pred, true>
+template <class Pred>
+static int predict_launch(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
+  auto* const kern = flow_prog_extended(fp.blk, fp.nblk) ? k_predict_quad<Pred, true> : k_predict_quad<Pred, false>;
+  hipLaunchKernelGGL(kern, dim3((md.N + 255) / 256), dim3(256), 2 * (size_t)(md.P + 2) * sizeof(double), st, md, fp, mu, v, rowp,
+                     Y, Y_std, m1, m2, logp);
+  LAUNCH_CHECK();
+  return 0;
 }
 
 // one launch of k_ell_quad<Lik, LPR, NB> or, for a program with a kind past STEPTANH (ext), k_ell_quad<Lik, LPR, NB | TGP_FLOWX>;
@@ -406,6 +554,13 @@ static int ell_launch(int LPR, int NB, Args... args) {
   if (NB == 4) return ell_launch_one<Lik, 32, 4>(args...);
   if (NB == 2) return ell_launch_one<Lik, 32, 2>(args...);
   return ell_launch_one<Lik, 32, 1>(args...);
+}
+// ... under the signature of a LikRow
+template <class Lik>
+static int ell_launch_row(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+                          const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu,
+                          double* g_v, double* g_rowp) {
+  return ell_launch<Lik>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);
 }
 
 }  // namespace tgp

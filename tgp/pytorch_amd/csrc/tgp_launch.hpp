@@ -129,14 +129,26 @@ struct KzzSections {
 };
 inline bool inducing_limits(int M, int D) { return M >= 1 && M <= TGP_BIG_MAX_M && D >= 1 && D <= 16; }
 inline bool known_kernel(int kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
-// the likelihoods k_ell_quad integrates by Gauss-Hermite through the flow (S, xs, wn, the program and theta are read)
-inline bool lik_is_quadrature(int lik) {
-  return lik == TGP_LIK_FLOW || lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT || lik == TGP_LIK_NEGBIN;
-}
-// ... of which these have no fused row kernel: their training step takes the general-M path at every M, as MATERN32 does
-inline bool lik_general_only(int lik) {
-  return lik == TGP_LIK_BERNOULLI || lik == TGP_LIK_POISSON || lik == TGP_LIK_STUDENT || lik == TGP_LIK_NEGBIN;
-}
+
+// What the host asks about a likelihood, one row per TGP_LIK_* id (the table: tgp_lik.hip).  The two launchers take the same
+// arguments for every row -- ell: ell_plan's LPR, NB, workgroups and LDS, `ext`: the program holds a kind past STEPTANH.
+using EllLaunch = int(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+                      const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu,
+                      double* g_v, double* g_rowp);
+using PredictLaunch = int(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
+struct LikRow {
+  int lik;
+  const char* name;          // the id's macro, as text
+  bool quadrature;           // k_ell_quad integrates it by Gauss-Hermite through the flow (S, xs, wn, the program and theta are read)
+  bool general_only;         // ... and has no fused row kernel: its training step takes the general-M path at every M, as MATERN32 does
+  EllLaunch* ell;            // launch_ell_quad's k_ell_quad instantiations (those of EllGauss where the id has no policy of its own)
+  PredictLaunch* predict;    // launch_predict's k_predict_quad instantiations; nullptr: tgp_predict_f64 has none for it
+  const char* no_quantiles;  // what the quantile / CDF entries say after "no quantiles for "; nullptr: they serve it
+};
+const LikRow* lik_row(int lik);   // nullptr: no such id
+inline bool lik_is_quadrature(int lik) { const LikRow* r = lik_row(lik); return r && r->quadrature; }
+inline bool lik_general_only(int lik) { const LikRow* r = lik_row(lik); return r && r->general_only; }
 // *first = the first 16-byte aligned double of the caller's workspace `ws`; refused when fewer than need_doubles follow it
 inline int open_workspace(const char* entry, const char* sizer, void* ws, size_t ws_bytes, size_t need_doubles, double** first) {
   const uintptr_t a = (reinterpret_cast<uintptr_t>(ws) + 15) & ~(uintptr_t)15;
@@ -166,20 +178,13 @@ int launch_mlp_backward(const tgp_mlp& d, const double* X, const double* W, cons
 // tgp_lik.hip
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* log_var_noise,
                      double scale, double* out, double* g_mu, double* g_v, double* ws, hipStream_t st);
-// the quadrature likelihood through the flow: Bernoulli for md.lik == TGP_LIK_BERNOULLI, Poisson for TGP_LIK_POISSON, Student-t
-// for TGP_LIK_STUDENT, negative binomial for TGP_LIK_NEGBIN, heteroscedastic Gaussian for TGP_LIK_HETERO (mu, v, g_mu, g_v then
-// (2,N)), else Gaussian (TGP_LIK_FLOW)
+// the quadrature likelihood through the flow, by the row of md.lik (TGP_LIK_HETERO: mu, v, g_mu, g_v are (2,N))
 int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, const double* mu, const double* v, const double* rowp,
                     double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, double* ws, hipStream_t st);
 int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, int S, int N, const double* rowp, double* G, double* dG,
                      double* logdG, hipStream_t st, double* sum_out = nullptr, double* ws = nullptr);
-// tgp_lik_negbin.hip: the TGP_LIK_NEGBIN instantiations behind launch_ell_quad (ell_plan's LPR, NB, workgroups and LDS; `ext`: the
-// program holds a kind past STEPTANH) and launch_predict (`lds`: its dynamic LDS)
-int launch_ell_negbin(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
-                      const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
-                      double* g_rowp);
-int launch_predict_negbin(const tgp_model& md, const FlowProg& fp, size_t lds, const double* mu, const double* v, const double* rowp,
-                          const double* Y, double* m1, double* m2, double* logp, hipStream_t st);
+EllLaunch ell_launch_negbin;           // tgp_lik_negbin.hip: what the TGP_LIK_NEGBIN row points to
+PredictLaunch predict_launch_negbin;
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,

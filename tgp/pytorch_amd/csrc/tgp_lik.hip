@@ -146,181 +146,6 @@ __global__ __launch_bounds__(256) void k_flow_eval(tgp_model md, FlowProg fp, co
 }
 
 // ---------------------------------------------------------------------------------------------------
-// prediction given q(f) moments: m1, m2 and per-row test log-likelihood (without the -0.5 log(pi) constant)
-//   flow : GaussianNonLinearMean.marginal_moments (:176-203) ; sparse_MF_SP.test_log_likelihood (:705-776)
-//   gauss: GaussianLinearMean.marginal_moments (:89-118)     ; sparse_MF_SP.py:786-799
-// X: the extended kind set
-// ---------------------------------------------------------------------------------------------------
-template <bool X>
-__global__ __launch_bounds__(256) void k_predict(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                  const double* __restrict__ v, const double* __restrict__ rowp,
-                                                  const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
-                                                  double* __restrict__ m2o, double* __restrict__ logp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  if (md.lik == TGP_LIK_FLOW) flow_params_lds<X>(md.theta, fp, tp, tg);
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= md.N) return;
-  const double noise = exp(md.log_var_noise[0]);
-  if (md.lik == TGP_LIK_GAUSS) {
-    const double m1 = mu[n], m2 = noise + v[n];
-    if (m1o) m1o[n] = m1;
-    if (m2o) m2o[n] = m2;
-    if (logp && Y) {
-      const double sd = Y_std * sqrt(m2), var = sd * sd, r = Y_std * Y[n] - Y_std * m1;
-      logp[n] = -0.5 * (TGP_LOG_2PI_REF + log(var) + r * r / var);
-    }
-    return;
-  }
-  FlowDev F{fp.blk, fp.nblk, tp, tg};
-  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-  const double m_ = mu[n], sq = sqrt(2.0 * v[n]);
-  const double sdy = Y_std * sqrt(noise), var = sdy * sdy;
-  const double yy = Y ? Y_std * Y[n] : 0.0;
-  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
-  const double lvar = log(var), ivar = 1.0 / var;
-  constexpr int NB = 4;  // quadrature nodes in flight (stage-by-stage evaluation, flow_forward_n)
-  for (int s0 = 0; s0 < md.S; s0 += NB) {
-    double g[NB], der[NB], wsn[NB];
-    const double* rpn[NB];
-    TGP_EACH(u, NB) {
-      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-      g[u] = m_ + sq * md.xs[s];
-      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-      rpn[u] = rp;
-    }
-    flow_forward_n<NB, false, X>(F, g, rpn, der);
-    TGP_EACH(u, NB) {
-      if (s0 + u < md.S) {
-        m1 += wsn[u] * g[u];
-        e2 += wsn[u] * g[u] * g[u];
-        if (logp && Y) {
-          // log w_s = log(wn_s) + 0.5 log(pi); the caller adds the reference's constants
-          const double r = yy - Y_std * g[u];
-          const double t = log(wsn[u]) - 0.5 * (TGP_LOG_2PI_REF + lvar + r * r * ivar);
-          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
-          else se += exp(t - mx);
-        }
-      }
-    }
-  }
-  if (m1o) m1o[n] = m1;
-  if (m2o) m2o[n] = noise + e2 - m1 * m1;
-  if (logp && Y) logp[n] = mx + log(se);
-}
-
-// Predictive probability per row: P = Phi(mu / sqrt(1 + v)) for the empty program (R&W eq. 3.80, Bernoulli.py
-// marginal_moments), else sum_s w_s Phi(G(mu + sqrt(2 v) x_s)) with the row's own v, clamped to [0, 1].
-// m1 = P, m2 = P (1 - P), logp = y log P + (1 - y) log(1 - P) (no constant).  X: the extended kind set.
-template <bool X>
-__global__ __launch_bounds__(256) void k_predict_bern(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                       const double* __restrict__ v, const double* __restrict__ rowp,
-                                                       const double* __restrict__ Y, double* __restrict__ m1o,
-                                                       double* __restrict__ m2o, double* __restrict__ logp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  flow_params_lds<X>(md.theta, fp, tp, tg);
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= md.N) return;
-  const double y = (logp && Y) ? Y[n] : 0.0;
-  double P1 = 0.0, P0 = 0.0;   // P(y = 1), P(y = 0), each summed on its own (no 1 - P cancellation)
-  double lp = 0.0;
-  bool lp_done = false;
-  if (fp.nblk == 0) {
-    // closed form: the node term gives log P and log(1 - P) without forming P (finite however far out mu / sqrt(1 + v) is)
-    const BernNode b = bern_node(mu[n] / sqrt(1.0 + v[n]), y);
-    P1 = b.pp;
-    P0 = b.pm;
-    lp = b.lp;
-    lp_done = true;
-  } else {
-    FlowDev F{fp.blk, fp.nblk, tp, tg};
-    const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-    const double vn = v[n] > 0.0 ? v[n] : 0.0;
-    const double m_ = mu[n], sq = sqrt(2.0 * vn);
-    constexpr int NB = 4;
-    for (int s0 = 0; s0 < md.S; s0 += NB) {
-      double g[NB], der[NB], wsn[NB];
-      const double* rpn[NB];
-      TGP_EACH(u, NB) {
-        const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-        g[u] = m_ + sq * md.xs[s];
-        wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-        rpn[u] = rp;
-      }
-      flow_forward_n<NB, false, X>(F, g, rpn, der);
-      TGP_EACH(u, NB) {
-        const BernNode b = bern_node(g[u], 0.0);
-        P1 += wsn[u] * b.pp;
-        P0 += wsn[u] * b.pm;
-      }
-    }
-    P1 = fmin(fmax(P1, 0.0), 1.0);
-    P0 = fmin(fmax(P0, 0.0), 1.0);
-  }
-  if (m1o) m1o[n] = P1;
-  if (m2o) m2o[n] = P1 * P0;
-  if (logp && Y) logp[n] = lp_done ? lp : (y != 0.0 ? y * log(P1) : 0.0) + (y != 1.0 ? (1.0 - y) * log(P0) : 0.0);
-}
-
-// Student-t predictive per row, in the standardised units of k_predict, g_s = G(mu + sqrt(2 v) x_s) (v <= 0 counts as 0):
-//   m1 = sum_s w_s g_s,  m2 = sum_s w_s g_s^2 - m1^2 + sigma^2 nu / (nu - 2)   (+inf for nu <= 2: no variance),
-//   logp = log sum_s w_s t_nu(y | g_s, sigma) - log Y_std = logsumexp_s(log w_s - (nu + 1) / 2 log1p(r_s^2 / (nu sigma^2)))
-//          + c(nu, eta) - log Y_std,
-// the exact log predictive density of the raw target with every constant; the sum is kept relative to its running maximum
-// as in k_predict_count.  The empty program runs the same loop (no closed form for the Gaussian-Student convolution; the
-// two moments are exact at S >= 2).  Nodes past S and nodes of weight 0 do not enter.  X: the extended kind set.
-template <bool X>
-__global__ __launch_bounds__(256) void k_predict_student(tgp_model md, FlowProg fp, const double* __restrict__ mu,
-                                                          const double* __restrict__ v, const double* __restrict__ rowp,
-                                                          const double* __restrict__ Y, double Y_std, double* __restrict__ m1o,
-                                                          double* __restrict__ m2o, double* __restrict__ logp) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* tp = reinterpret_cast<double*>(smem_raw);
-  double* tg = tp + (md.P + 2) / 2 * 2;
-  flow_params_lds<X>(md.theta, fp, tp, tg);
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= md.N) return;
-  const bool want_lp = logp && Y;
-  const double y = want_lp ? Y[n] : 0.0;
-  const StudentConst K = EllStudent::consts(md.log_var_noise);
-  FlowDev F{fp.blk, fp.nblk, tp, tg};
-  const double* rp = rowp ? rowp + (size_t)n * md.RP : nullptr;
-  const double vn = v[n] > 0.0 ? v[n] : 0.0;
-  const double m_ = mu[n], sq = sqrt(2.0 * vn);
-  double m1 = 0.0, e2 = 0.0, mx = -INFINITY, se = 0.0;
-  constexpr int NB = 4;
-  for (int s0 = 0; s0 < md.S; s0 += NB) {
-    double g[NB], der[NB], wsn[NB];
-    const double* rpn[NB];
-    TGP_EACH(u, NB) {
-      const int s = s0 + u < md.S ? s0 + u : md.S - 1;
-      g[u] = m_ + sq * md.xs[s];
-      wsn[u] = s0 + u < md.S ? md.wn[s] : 0.0;
-      rpn[u] = rp;
-    }
-    flow_forward_n<NB, false, X>(F, g, rpn, der);
-    TGP_EACH(u, NB) {
-      if (wsn[u] > 0.0) {
-        m1 += wsn[u] * g[u];
-        e2 += wsn[u] * g[u] * g[u];
-        if (want_lp) {
-          const double r = y - g[u];
-          const double t = log(wsn[u]) - 0.5 * K.nu1 * log1p(r * r * K.inus2);
-          if (t > mx) { se = se * exp(mx - t) + 1.0; mx = t; }
-          else if (t > -INFINITY) se += exp(t - mx);
-        }
-      }
-    }
-  }
-  if (m1o) m1o[n] = m1;
-  if (m2o) m2o[n] = K.nu > 2.0 ? e2 - m1 * m1 + K.nus2 / (K.nu - 2.0) : INFINITY;
-  if (want_lp) logp[n] = mx + log(se) + student_log_const(K.nu, K.eta) - log(Y_std);
-}
-
-// ---------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam semantics; dsp/trainers/optimizers.py:12)
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_adam(double* __restrict__ p, const double* __restrict__ g,
@@ -418,6 +243,37 @@ int launch_gather_rows(const double* X, const double* Y, int N, int D, const int
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The likelihoods (LikRow, tgp_launch.hpp).  A new one is a policy in tgp_ell.hpp and a row here.
+// ---------------------------------------------------------------------------------------------------
+#define TGP_STR_(x) #x
+#define TGP_STR(x) TGP_STR_(x)
+#define NOQ_DISCRETE ": the predictive is discrete (its pmf is tgp_predict_f64's logp, one row per count)"
+#define NOQ_STUDENT ": the CDF of a Student-t mixture needs the incomplete beta function (its density is tgp_predict_f64's logp)"
+#define NOQ_OTHER(ID) /* by its number */                                                                          \
+  "lik = " TGP_STR(TGP_LIK_##ID) " (TGP_LIK_GAUSS and TGP_LIK_FLOW only; a warped model's are T^-1(mu + z sqrt(v + noise)) " \
+  "through tgp_flow_inverse_f64)"
+#define LIK_ROW(ID, ...) {TGP_LIK_##ID, "TGP_LIK_" #ID, __VA_ARGS__}
+static const LikRow lik_table[] = {
+    //      id         quadrature  general_only  ell                           predict                              no_quantiles
+    LIK_ROW(GAUSS,     false, false, ell_launch_row<EllGauss>,   predict_launch<PredGauss>,          nullptr),
+    LIK_ROW(FLOW,      true,  false, ell_launch_row<EllGauss>,   predict_launch<PredGauss>,          nullptr),
+    LIK_ROW(ADJOINT,   false, false, ell_launch_row<EllGauss>,   nullptr,                            nullptr),
+    LIK_ROW(BERNOULLI, true,  true,  ell_launch_row<EllBern>,    predict_launch<PredBern>,           NOQ_OTHER(BERNOULLI)),
+    LIK_ROW(WARPED,    false, false, ell_launch_row<EllGauss>,   nullptr,                            NOQ_OTHER(WARPED)),
+    LIK_ROW(SOFTMAX,   false, false, ell_launch_row<EllGauss>,   nullptr,                            NOQ_OTHER(SOFTMAX)),
+    LIK_ROW(POISSON,   true,  true,  ell_launch_row<EllPois>,    predict_launch<PredCount<EllPois>>, "TGP_LIK_POISSON" NOQ_DISCRETE),
+    LIK_ROW(STUDENT,   true,  true,  ell_launch_row<EllStudent>, predict_launch<PredStudent>,        "TGP_LIK_STUDENT" NOQ_STUDENT),
+    // (tgp_ell_hetero_f64 only; every single-output entry refuses it before it asks)
+    LIK_ROW(HETERO,    false, false, ell_launch_row<EllHetero>,  nullptr,                            nullptr),
+    LIK_ROW(NEGBIN,    true,  true,  ell_launch_negbin,          predict_launch_negbin,              "TGP_LIK_NEGBIN" NOQ_DISCRETE),
+};
+const LikRow* lik_row(int lik) {
+  for (const LikRow& r : lik_table)
+    if (r.lik == lik) return &r;
+  return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------------
 int launch_ell_gauss(const double* Y, const double* mu, const double* v, int N, const double* lvn, double scale,
@@ -457,18 +313,9 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
   const int rows = 256 / LPR;
   const int nb = (md.N + rows - 1) / rows;
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-  if (int rc = md.lik == TGP_LIK_BERNOULLI
-                   ? ell_launch<EllBern>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
-               : md.lik == TGP_LIK_POISSON
-                   ? ell_launch<EllPois>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
-               : md.lik == TGP_LIK_NEGBIN   // (its instantiations: tgp_lik_negbin.hip)
-                   ? launch_ell_negbin(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
-               : md.lik == TGP_LIK_STUDENT
-                   ? ell_launch<EllStudent>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
-               : md.lik == TGP_LIK_HETERO   // (tgp_ell_hetero_f64 only: mu, v, g_mu, g_v are (2,N))
-                   ? ell_launch<EllHetero>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)
-                   : ell_launch<EllGauss>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp))
-    return rc;
+  const LikRow* row = lik_row(md.lik);
+  if (!row) return -1;
+  if (int rc = row->ell(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)) return rc;
   hipLaunchKernelGGL(k_sum_parts, dim3((2 + md.P + 31) / 32), dim3(256), 0, st, ws, nb, 2 + md.P, out, g_theta, 2);
   LAUNCH_CHECK();
   return 0;
@@ -494,30 +341,13 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
 
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
-  const size_t lds = 2 * (size_t)(md.P + 2) * sizeof(double);
-  if (md.lik == TGP_LIK_BERNOULLI) {
-    if (flow_prog_extended(fp.blk, fp.nblk))
-      hipLaunchKernelGGL(k_predict_bern<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-    else
-      hipLaunchKernelGGL(k_predict_bern<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-  } else if (md.lik == TGP_LIK_POISSON) {
-    if (flow_prog_extended(fp.blk, fp.nblk))
-      hipLaunchKernelGGL((k_predict_count<EllPois, true>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-    else
-      hipLaunchKernelGGL((k_predict_count<EllPois, false>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-  } else if (md.lik == TGP_LIK_NEGBIN) {
-    return launch_predict_negbin(md, fp, lds, mu, v, rowp, Y, m1, m2, logp, st);
-  } else if (md.lik == TGP_LIK_STUDENT) {
-    if (flow_prog_extended(fp.blk, fp.nblk))
-      hipLaunchKernelGGL(k_predict_student<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
-    else
-      hipLaunchKernelGGL(k_predict_student<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
-  } else if (flow_prog_extended(fp.blk, fp.nblk))
-    hipLaunchKernelGGL(k_predict<true>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
-  else
-    hipLaunchKernelGGL(k_predict<false>, dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp);
-  LAUNCH_CHECK();
-  return 0;
+  const LikRow* row = lik_row(md.lik);
+  if (!row) return -1;
+  if (!row->predict) {
+    set_error_text("tgp_predict_f64: no predictive for %s here", row->name);
+    return TGP_E_UNSUPPORTED;
+  }
+  return row->predict(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, st);
 }
 
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,

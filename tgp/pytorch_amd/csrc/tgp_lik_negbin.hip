@@ -1,5 +1,5 @@
 // tgp_lik_negbin.hip -- the negative-binomial likelihood (TGP_LIK_NEGBIN): its policy and the instantiations of k_ell_quad and
-// k_predict_count (tgp_ell.hpp) for it, in a unit of their own: three lgamma and two digamma per kernel make these 22 kernels as
+// k_predict_quad (tgp_ell.hpp) for it, in a unit of their own: three lgamma and two digamma per kernel make these 22 kernels as
 // slow to compile as two thirds of tgp_lik.hip's 115.
 #include "tgp_ell.hpp"
 
@@ -23,7 +23,7 @@ struct EllNegBin {
   static constexpr bool kRowNoise = true;
   static constexpr bool kBlockTerm = false;
   static constexpr bool kRowConst = false;
-  static constexpr bool kOverDisp = true;   // k_predict_count: Var[y | mean] = mean + mean^2 excess(K)
+  static constexpr bool kOverDisp = true;   // PredCount: Var[y | mean] = mean + mean^2 excess(K)
   static __device__ __forceinline__ NegBinConst consts(const double* lvn) {
     const double lam = lvn[0], r = exp(lam);
     return {lam, r, lgamma(r), digamma_d(r)};
@@ -42,25 +42,20 @@ struct EllNegBin {
     return lgamma(y + k.r) - k.lgr - lgamma(y + 1.0);
   }
   static __device__ __forceinline__ double row_deta(double y, const NegBinConst& k) { return k.r * (digamma_d(y + k.r) - k.psir); }
-  static __device__ __forceinline__ double rate(const NegBinNode& t) { return exp(t.g); }   // k_predict_count: the mean
+  static __device__ __forceinline__ double rate(const NegBinNode& t) { return exp(t.g); }   // PredCount: the mean
   static __device__ __forceinline__ double excess(const NegBinConst& k) { return 1.0 / k.r; }
   static __device__ __forceinline__ double plus_log_p(double a, const NegBinNode& t, const NegBinConst& k) { return a + log_p(t, k); }
 };
 
-int launch_ell_negbin(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+int ell_launch_negbin(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                       const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
                       double* g_rowp) {
-  return ell_launch<EllNegBin>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);
+  return ell_launch_row<EllNegBin>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);
 }
 
-int launch_predict_negbin(const tgp_model& md, const FlowProg& fp, size_t lds, const double* mu, const double* v, const double* rowp,
-                          const double* Y, double* m1, double* m2, double* logp, hipStream_t st) {
-  if (flow_prog_extended(fp.blk, fp.nblk))
-    hipLaunchKernelGGL((k_predict_count<EllNegBin, true>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-  else
-    hipLaunchKernelGGL((k_predict_count<EllNegBin, false>), dim3((md.N + 255) / 256), dim3(256), lds, st, md, fp, mu, v, rowp, Y, m1, m2, logp);
-  LAUNCH_CHECK();
-  return 0;
+int predict_launch_negbin(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                          const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st) {
+  return predict_launch<PredCount<EllNegBin>>(md, fp, mu, v, rowp, Y, Y_std, m1, m2, logp, st);
 }
 
 }  // namespace tgp

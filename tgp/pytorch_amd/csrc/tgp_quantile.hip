@@ -13,7 +13,7 @@
 // partial sums are added by a DPP butterfly (every lane of the row ends with the same bits).  No float atomics, fixed
 // summation order: same input, same bits.  The loops are uniform over the wave (a row that is done keeps evaluating at its
 // root until the wave's last row is done), so the cross-lane adds always run with every lane on.
-// X: the extended flow kind set, as in k_predict<X>.
+// X: the extended flow kind set, as in k_predict_quad<Pred, X>.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void k_quantile_gauss(int N, const double* __r
 //   logp = log sum_s sum_t wn_s wn_t N(y | g_s, exp(a + sqrt(2 v2) xs_t)) - log Y_std,
 // the exact log density of the raw target under the S x S product rule, with its constant (double-precision pi, as Student-t).
 // The row's 16 lanes sweep the S node values into LDS once (q_sweep); lane l then takes the noise nodes t = l, l + 16, ... and
-// runs over all s for each, keeping its sum relative to its running maximum (as k_predict_count); the 16 lanes' (maximum, sum)
+// runs over all s for each, keeping its sum relative to its running maximum (as lse_push of tgp_ell.hpp); the 16 lanes' (maximum, sum)
 // pairs are joined under the row's maximum, so logp is finite where every term underflows (|y - g| = 1e8 sigma: terms near
 // -5e15).  Weights of 0 do not enter.  Fixed order, no atomics: same input, same bits.
 // dynamic LDS: tp, tg, then wn, log wn, xs (S rounded up to even each), then QROWS node tables of q_row_stride(S)

@@ -33,6 +33,9 @@ CAPTURE_MODE = "thread_local"
 # "mean_a" / "mean_b": a linear mean function's parameters; "nn" (packed MLP weights) last: the weight-decay group
 ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "mean_a", "mean_b", "nn")
 
+# the `likelihood` names of the quadrature likelihoods that train through ops.ElboFunction only
+EAGER_ONLY = {"bernoulli": L.LIK_BERNOULLI, "poisson": L.LIK_POISSON, "negbinomial": L.LIK_NEGBIN, "studentt": L.LIK_STUDENT}
+
 
 def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, collective=None, per_row=False, minibatch=False):
     """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
@@ -43,14 +46,9 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
     multi_rank = int(world_size) > 1 or collective is not None
     if not is_whiten:      # `params` of an unwhitened model describe q(u) itself; the captured step has no transform in it
         return "the step engines need is_whiten=True: an unwhitened q(u) trains on the eager path (Trainer_SP), on one rank"
-    if likelihood == "bernoulli":
-        return "the step engines have no Bernoulli likelihood: it trains on the eager path (ops.ElboFunction)"
-    if likelihood == "poisson":
-        return "the step engines have no Poisson likelihood: it trains on the eager path (ops.ElboFunction)"
-    if likelihood == "negbinomial":
-        return "the step engines have no negative-binomial likelihood: it trains on the eager path (ops.ElboFunction)"
-    if likelihood == "studentt":
-        return "the step engines have no Student-t likelihood: it trains on the eager path (ops.ElboFunction)"
+    if likelihood in EAGER_ONLY:
+        return ("the step engines have no %s likelihood: it trains on the eager path (ops.ElboFunction)"
+                % L.LIK_DISPLAY[EAGER_ONLY[likelihood]])
     if likelihood == "multiclass":
         return "the step engines have no multi-class likelihood: its C latent GPs train on the eager path's composed step"
     if likelihood == "hetero":

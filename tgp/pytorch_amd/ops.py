@@ -192,10 +192,8 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     N, D = X.shape
     M = m.numel()
     scale = float(N_total) / float(mb_global if mb_global is not None else N)
-    if lik in (L.LIK_BERNOULLI, L.LIK_POISSON, L.LIK_STUDENT, L.LIK_NEGBIN) and flow is None:
-        raise L.TgpError("the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
-                         % {L.LIK_BERNOULLI: "Bernoulli", L.LIK_POISSON: "Poisson", L.LIK_STUDENT: "Student-t",
-                            L.LIK_NEGBIN: "negative-binomial"}[lik])
+    if lik in L.LIK_DISPLAY and flow is None:
+        raise L.TgpError(L.NEEDS_FLOWSPEC % L.LIK_DISPLAY[lik])
     # (LIK_STUDENT: the library reads {log sigma^2, nu} behind the noise pointer and writes one gradient, that of log sigma^2)
     if lik == L.LIK_STUDENT and lvn.numel() != 1:
         raise L.TgpError("the Student-t step takes a one-element log_var_noise (log sigma^2); the degrees of freedom go in `df`")
@@ -1451,7 +1449,7 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     lib = L.load()
     if lik == L.LIK_STUDENT:
         if flow is None:
-            raise L.TgpError("the Student-t likelihood needs a FlowSpec (an empty one for the identity flow)")
+            raise L.TgpError(L.NEEDS_FLOWSPEC % L.LIK_DISPLAY[lik])
         lvn = student_noise(lvn, df)
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
