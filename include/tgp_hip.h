@@ -386,6 +386,35 @@ int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, in
                  const double* raw_os, const double* Y, double* C, double* b, void* workspace, size_t workspace_bytes,
                  void* stream);
 
+/* Natural-gradient step of the whitened q(u) = N(m, Lam Lam^T) for any likelihood, in its conjugate-computation form (Khan & Lin
+ * 2017; Salimbeni et al. 2018): the closed-form optimum above with per-row pseudo-observations.  With K = K_ZZ + jitter I = L L^T,
+ * a_n = L^-1 k_Z(x_n), mu_n = a_n^T m, and the adjoints mu_bar_n = d(c ELL)/d mu_n, v_bar_n = d(c ELL)/d v_n that tgp_ell_gauss_f64 /
+ * tgp_ell_flow_f64 write as g_mu, g_v at scale c (they already hold c):
+ *   lambda_n = -2 v_bar_n, lambda_n <- max(lambda_n, site_floor) (a NaN site_floor: no floor), r_n = mu_bar_n + lambda_n mu_n
+ *   C = K_ZX diag(lambda) K_XZ,  b = K_ZX r        one pass over the rows, the sites formed per row, K_ZX never stored
+ *   B = I + L^-1 C L^-T,  h = L^-1 b,  P = (Lam Lam^T)^-1
+ *   P' = (1 - rho) P + rho B,  h' = (1 - rho) P m + rho h,  Lam' Lam'^T = P'^-1 (Lam' lower, positive diagonal),  m' = P'^-1 h'
+ * rho in (0, 1] is the step size in natural parameters; with the Gaussian likelihood's adjoints and rho = 1 the step is
+ * tgp_optimal_qu_f64's optimum.  At rho = 1 model->m and model->Lam are not read.  Lam's diagonal may have any sign.
+ * Uses model->{N,D,M,kernel,jitter,Z,raw_ls,raw_os,m,Lam}; lik, scale and the flow fields are ignored.  X (N,D); mu, mu_bar,
+ * v_bar (N); outputs m_out (M), Lam_out (M,M; exact zeros above the diagonal) -- they may be the model's own m / Lam.
+ * status[0] is tgp_cholesky_f64's for K (the host runs the jitter ladder) and status[1] == 1 its NaN flag.  When K's factorisation
+ * succeeded and met no NaN, status[1] reports the q(u) side: -(pivot) when Lam Lam^T is not positive definite, 1 + pivot when P' is
+ * not (sites of a likelihood that is not log-concave, without a floor); NaNs without a failing pivot count as pivot M + 1 -- more
+ * jitter does not help there.  When status[0] or status[1] is not zero the outputs are not written.  One stream, no host synchronisation, fixed summation orders: same input, same bits.
+ * tgp_kxwxk_f64 is the weighted first stage alone: C = K_ZX diag(w) K_XZ (M,M; C[i][j] == C[j][i] bit for bit), b = K_ZX r (M);
+ * w of any sign; r == NULL or b == NULL skips b.  With w = 1 it returns tgp_kxxk_f64's bits.
+ * Limits and error codes are tgp_kxxk_f64's / tgp_optimal_qu_f64's; rho outside (0, 1] or an unknown kernel gives
+ * TGP_E_UNSUPPORTED before any pointer is read. */
+size_t tgp_kxwxk_workspace_bytes(int32_t N, int32_t M);
+int tgp_kxwxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, int32_t M, int32_t D, const double* raw_ls,
+                  const double* raw_os, const double* w, const double* r, double* C, double* b, void* workspace,
+                  size_t workspace_bytes, void* stream);
+size_t tgp_natgrad_qu_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_natgrad_qu_f64(const tgp_model* model, const double* X, const double* mu, const double* mu_bar, const double* v_bar,
+                       double rho, double site_floor, double* m_out, double* Lam_out, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Greedy conditional-variance selection of inducing points: the pivoted Cholesky factorisation of K_XX (Burt, Rasmussen, van der
  * Wilk 2020, "Convergence of sparse variational inference in Gaussian processes regression").  It picks the M rows of X that most
  * reduce tr(K_XX - Q_XX), Q_XX = K_XZ K_ZZ^-1 K_ZX, and returns that residual trace after every pick.  With s2 the kernel's

@@ -446,6 +446,50 @@ int tgp_kxxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, in
   return launch_kxxk(kernel, X, N, Z, M, D, raw_ls, raw_os, Y, C, b, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_kxwxk_workspace_bytes(int32_t N, int32_t M) { return kxwxk_workspace_bytes(N, M); }
+
+int tgp_kxwxk_f64(int32_t kernel, const double* X, int32_t N, const double* Z, int32_t M, int32_t D, const double* raw_ls,
+                  const double* raw_os, const double* w, const double* r, double* C, double* b, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (!known_kernel(kernel)) return -1;
+  if (D < 1 || D > 16 || kxwxk_workspace_bytes(N, M) == 0) {
+    set_error_text("tgp_kxwxk_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", N, D, M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!X) return -2;
+  if (!Z || !raw_ls || !raw_os) return -4;
+  if (!w) return -9;
+  if (!C) return -11;
+  if (!workspace) return -13;
+  return launch_kxwxk(kernel, X, N, Z, M, D, raw_ls, raw_os, w, r, C, b, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+size_t tgp_natgrad_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return natgrad_qu_workspace_bytes(N, D, M); }
+
+int tgp_natgrad_qu_f64(const tgp_model* model, const double* X, const double* mu, const double* mu_bar, const double* v_bar,
+                       double rho, double site_floor, double* m_out, double* Lam_out, int32_t* status, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (!(rho > 0.0 && rho <= 1.0) || !known_kernel(model->kernel) || natgrad_qu_workspace_bytes(model->N, model->D, model->M) == 0) {
+    set_error_text("tgp_natgrad_qu_f64: rho = %g, kernel = %d, N = %d, D = %d, M = %d outside 0 < rho <= 1, kernel TGP_KERNEL_SCALE_RBF "
+                   "or TGP_KERNEL_SCALE_MATERN32, N >= 1, 1 <= M <= %d, 1 <= D <= 16", rho, model->kernel, model->N, model->D, model->M,
+                   TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os) return -1;
+  if (rho < 1.0 && (!model->m || !model->Lam)) return -1;
+  if (!X) return -2;
+  if (!mu) return -3;
+  if (!mu_bar) return -4;
+  if (!v_bar) return -5;
+  if (!m_out) return -8;
+  if (!Lam_out) return -9;
+  if (!status) return -10;
+  if (!workspace) return -11;
+  return launch_natgrad_qu(*model, X, mu, mu_bar, v_bar, rho, site_floor, m_out, Lam_out, status, workspace, workspace_bytes,
+                           static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_greedy_inducing_workspace_bytes(int32_t N, int32_t D, int32_t M) { return greedy_inducing_workspace_bytes(N, D, M); }
 
 int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double* raw_ls, const double* raw_os, int32_t kernel,

@@ -271,6 +271,14 @@ int launch_kxxk(int kernel, const double* X, int N, const double* Z, int M, int 
 size_t optimal_qu_workspace_bytes(int N, int D, int M);
 int launch_optimal_qu(const tgp_model& md, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
                       void* workspace, size_t workspace_bytes, hipStream_t st);
+// ... the weighted pass C = K_ZX diag(w) K_XZ, b = K_ZX r, and the natural-gradient step of q(u) on the same chain
+size_t kxwxk_workspace_bytes(int N, int M);
+int launch_kxwxk(int kernel, const double* X, int N, const double* Z, int M, int D, const double* raw_ls, const double* raw_os,
+                 const double* w, const double* r, double* C, double* b, void* workspace, size_t workspace_bytes, hipStream_t st);
+size_t natgrad_qu_workspace_bytes(int N, int D, int M);
+int launch_natgrad_qu(const tgp_model& md, const double* X, const double* mu, const double* mu_bar, const double* v_bar, double rho,
+                      double site_floor, double* m_out, double* Lam_out, int32_t* status, void* workspace, size_t workspace_bytes,
+                      hipStream_t st);
 
 // tgp_greedy.hip (greedy conditional-variance selection of inducing points: the pivoted Cholesky factorisation of K_XX)
 size_t greedy_inducing_workspace_bytes(int N, int D, int M);

@@ -148,6 +148,12 @@ _SIGS = {
     "tgp_kxxk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_kxxk_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t,
                                _dp]),
+    "tgp_kxwxk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "tgp_kxwxk_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                C.c_size_t, _dp]),
+    "tgp_natgrad_qu_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "tgp_natgrad_qu_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _dp,
+                                     C.c_size_t, _dp]),
     "tgp_greedy_inducing_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "tgp_greedy_inducing_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, _dp, _dp, _dp, _dp,
                                           _dp, C.c_size_t, _dp]),

@@ -116,10 +116,15 @@ def main(argv=None):
     ap.add_argument("--coverage", choices=["sampled", "exact"], default="sampled",
                     help="95 %% interval of the coverage metric (regression): sampled = order statistics of 100 predictive draws "
                          "per row (the reference); exact = the 2.5 %% / 97.5 %% quantiles of the predictive CDF")
-    ap.add_argument("--qu", choices=["adam", "optimal"], default="adam",
+    ap.add_argument("--qu", choices=["adam", "optimal", "natgrad"], default="adam",
                     help="q(u): adam = m and Lam trained by Adam like every other parameter (the reference); optimal = set to "
                          "their closed-form optimum before every step and evaluation, the hyper-parameters train on the "
-                         "collapsed bound (SVGP and WGP, --whiten 1, data sets of one full batch)")
+                         "collapsed bound (SVGP and WGP, --whiten 1, data sets of one full batch); natgrad = one natural-gradient "
+                         "step of q(u) per minibatch at step size --natgrad_lr, Adam on the other parameters (SVGP and TGP with "
+                         "one latent GP, any of their likelihoods, --whiten 1, --mean zero)")
+    ap.add_argument("--natgrad_lr", type=float, default=1.0,
+                    help="step size of --qu natgrad in natural parameters, in (0, 1]: 1 on one full batch per epoch, below 1 with "
+                         "several minibatches")
     ap.add_argument("--init_Z", choices=["kmeans", "greedy"], default="kmeans",
                     help="inducing inputs at the start: kmeans = centroids of k-means++ / Lloyd, best of 10 (the reference); greedy = "
                          "the training rows picked by greedy conditional-variance selection (pivoted Cholesky of K_XX) under the "
@@ -179,6 +184,21 @@ def main(argv=None):
         ap.error("--mean %s: SVGP or TGP with the gaussian, bernoulli, poisson or studentt likelihood only" % args.mean)
     if args.qu == "optimal" and (args.model not in ("SVGP", "WGP") or args.likelihood != "gaussian" or not args.whiten):
         ap.error("--qu optimal: SVGP or WGP with the gaussian likelihood and --whiten 1 (the likelihood must be Gaussian in f)")
+    if args.qu == "natgrad":
+        if het:
+            ap.error("--qu natgrad: not --likelihood hetero (two coupled latent GPs: the step is built for one)")
+        if multi:
+            ap.error("--qu natgrad: not --likelihood multiclass (C coupled latent GPs: the step is built for one)")
+        if wgp:
+            ap.error("--qu natgrad: not --model WGP (Gaussian in f on the warped targets: --qu optimal gives the exact optimum)")
+        if args.model == "ID_TGP":
+            ap.error("--qu natgrad: not --model ID_TGP (input-dependent flows: the step is built for shared flow parameters)")
+        if not args.whiten:
+            ap.error("--qu natgrad: --whiten 1 only (the step is built for the whitened q(u))")
+        if args.mean != "zero":
+            ap.error("--qu natgrad: --mean zero only (the step is built for the zero prior mean)")
+        if not 0.0 < args.natgrad_lr <= 1.0:
+            ap.error("--natgrad_lr: the step size must be in (0, 1], got %g" % args.natgrad_lr)
     if args.init_Z == "greedy" and args.likelihood == "multiclass":
         ap.error("--init_Z greedy: one latent GP only (not --likelihood multiclass)")
     if args.model == "ID_TGP" and args.flow_arch not in (None, "SAL"):
@@ -269,7 +289,7 @@ def main(argv=None):
     trainer_cls = Trainer_SP_classification if (bern or multi) else Trainer_SP_regression
     trainer = trainer_cls(model=model, data_loaders=loaders, validate_each=max(args.epochs // 10, 1), plot=False,
                                     track=False, Y_std=Y_std, plot_each=-1, S_test=100, inference_in_cpu=True,
-                                    coverage=args.coverage, qu=args.qu)
+                                    coverage=args.coverage, qu=args.qu, natgrad_lr=args.natgrad_lr)
     trainer.train(epochs=args.epochs, lr_ALL=lr, opt="adam", keep_parameter_groups=True,
                   optimisation_schedule=([1.0], specs), lr_groups=None)
     res = trainer.compute_metrics()

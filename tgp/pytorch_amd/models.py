@@ -379,7 +379,7 @@ class sparse_MF_SP(nn.Module):
 
     def ELBO(self, X, Y, _qu_jitter=None):
         """Returns (ELBO, ELL, KLD): positive ELBO with autograd, the trainer negates (sparse_MF_SP.py:552-598).
-        `_qu_jitter` (collapsed_bound only): q(u) enters as a constant and the step starts at this jitter."""
+        `_qu_jitter` (collapsed_bound and the trainer's natgrad loop): q(u) enters as a constant and the step starts at this jitter."""
         X2 = X[0] if X.dim() == 3 else X
         self._require_gpu(X2)
         assert Y.dim() == 2 and Y.shape[1] == 1, "Y must be (MB, 1)"
@@ -470,6 +470,67 @@ class sparse_MF_SP(nn.Module):
         theorem) and q_U, a constant of the step here, receives none.  q_U holds the optimum afterwards."""
         info = self.set_optimal_qu(X, Y)
         return self.ELBO(X, Y, _qu_jitter=info["jitter"])
+
+    # ---- natural-gradient steps of q(u): any likelihood of one latent GP -----------------------------------
+    def _natgrad_refusal(self):
+        """Why this model has no natural-gradient step of q(u), or None.  The step is built for one whitened latent GP with a
+        zero prior mean whose likelihood sees f through shared parameters only."""
+        lik = self.likelihood
+        if lik.num_latent > 1:
+            return ("a likelihood of %d coupled latent GPs (%s): the step is built for one latent GP"
+                    % (lik.num_latent, type(lik).__name__))
+        if lik.flow_on_targets:
+            return ("the warped likelihood is Gaussian in f on the warped targets: set_optimal_qu gives the exact optimum of "
+                    "q(u) in one step")
+        if not self.is_whiten:
+            return "is_whiten=False: the step is built for the whitened q(u) only"
+        if self.fully_bayesian:
+            return "be_fully_bayesian: the step needs the flow's parameters without dropout noise"
+        if self._input_dependent:
+            return "input-dependent flows (ID_TGP): the step is built for shared flow parameters"
+        if self._has_mean:
+            return "a non-zero mean function: the step is built for the zero prior mean"
+        return None
+
+    def natgrad_step_qu(self, X, Y, lr=1.0, site_floor=0.0):
+        """One natural-gradient step of q(u) at the current hyper-parameters and for these rows, step size `lr` in (0, 1], written
+        into q_U (no autograd): ops.qf_moments -> the likelihood's own ops.ell_* launch at scale N / MB, whose g_mu, g_v are the
+        per-row adjoints -> ops.natgrad_qu at the jitter the moments ended with.  With the Gaussian likelihood and lr = 1 it is
+        set_optimal_qu; for the others a damped Newton step on q(u) that needs no learning rate for m and Lam.  `site_floor`
+        clamps the per-row precisions from below (0.0 keeps P' positive definite for every likelihood; None: no floor, and a
+        likelihood that is not log-concave may raise ops.NotPSDError -- q_U is left as it was then).  Returns the `info` dict
+        (info["jitter"]).  NotImplementedError, naming the reason, for the models the step is not built for."""
+        why = self._natgrad_refusal()
+        if why is not None:
+            raise NotImplementedError("natgrad_step_qu: " + why)
+        X2 = X[0] if X.dim() == 3 else X
+        self._require_gpu(X2)
+        self.likelihood.check_targets(Y)
+        info = {}
+        kern = self.covariance_function.hip_kernel
+        ladder = ops.jitter_ladder(jitter=cg.global_jitter)
+        with torch.no_grad():
+            Z, rl, ro, m, Lam, lvn = (None if t is None else t.detach().contiguous() for t in self._raw_params())
+            X2 = X2.detach()
+            spec, theta, rowp = self._flow_inputs(X2, with_grad=False)
+            theta = None if theta is None else theta.detach()
+            y = Y.detach().reshape(-1).to(Z.dtype).contiguous()
+            jit = 0.0
+            while True:
+                # moments, sites and the step share one factor of K_ZZ: where the step's ladder climbs past the jitter the moments
+                # ended with, they are formed again there (a finite ladder: the jitter only rises)
+                mu, v = ops.qf_moments(X2, Z, rl, ro, m, Lam, jitter=jit, kernel=kern, info=info)
+                jit = info["jitter"]
+                res = ops._ell_rows(y, mu, v, lvn if self.likelihood.has_noise else None, spec, theta, self.quad_points, rowp,
+                                    scale=self.N / y.numel(), **self.likelihood.lik_kwargs())
+                m_new, Lam_new = ops.natgrad_qu(X2, Z, rl, ro, m, Lam, mu, res["g_mu"], res["g_v"], rho=float(lr),
+                                                site_floor=site_floor, jitter=jit, kernel=kern, info=info, ladder=ladder)
+                if info["jitter"] == jit:
+                    break
+                jit = info["jitter"]
+            self.q_U.variational_mean.data[0].copy_(m_new)
+            self.q_U.chol_variational_covar.data[0].copy_(Lam_new)
+        return info
 
     def check_status(self):
         """Lazy Cholesky status check (cg.status_check = 'lazy'): raises like psd_safe_cholesky would have."""

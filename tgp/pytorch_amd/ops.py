@@ -673,6 +673,96 @@ def optimal_qu(X, Y, Z, raw_ls, raw_os, lvn, N_total, jitter=0.0, kernel="scale_
 
 
 # ---------------------------------------------------------------------------------------------------
+# natural-gradient step of q(u) for any likelihood: the closed form above with per-row pseudo-observations
+# ---------------------------------------------------------------------------------------------------
+def kxwxk(X, Z, raw_ls, raw_os, w, r=None, kernel="scale_rbf", workspace_bytes=None):
+    """(C, b) = (K_ZX diag(w) K_XZ (M, M), K_ZX r (M) or None) in one pass over the rows of X, K_ZX generated on chip
+    (tgp_kxwxk_f64).  w (N) may have any sign.  C is exactly symmetric; fixed summation order: two calls give the same bits, and
+    w = 1 gives kxxk's."""
+    lib = L.load()
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    w = _c(w.reshape(-1), "w")
+    r = _c(None if r is None else r.reshape(-1), "r")
+    N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape[1] != D or w.numel() != N or (r is not None and r.numel() != N):
+        raise ValueError("kxwxk: X (N, D), Z (M, D), w (N), r (N)")
+    dev = X.device
+    ws, nbytes = _scratch(lib.tgp_kxwxk_workspace_bytes(N, M), dev, workspace_bytes)
+    C = torch.empty(M, M, dtype=torch.float64, device=dev)
+    b = torch.empty(M, dtype=torch.float64, device=dev) if r is not None else None
+    L.check(lib.tgp_kxwxk_f64(kernel_id(kernel), L.ptr(X), N, L.ptr(Z), M, D, L.ptr(raw_ls), L.ptr(raw_os), L.ptr(w), L.ptr(r),
+                              L.ptr(C), L.ptr(b), L.ptr(ws), nbytes, L.stream_ptr()), "tgp_kxwxk_f64")
+    return C, b
+
+
+def natgrad_qu(X, Z, raw_ls, raw_os, m, Lam, mu, mu_bar, v_bar, rho=1.0, site_floor=0.0, jitter=0.0, kernel="scale_rbf",
+               info=None, ladder=None, out=None, check=True, workspace_bytes=None):
+    """(m', Lam'): one natural-gradient step of the whitened q(u) = N(m, Lam Lam^T), step size `rho` in (0, 1], from the adjoints
+    mu_bar = d(c ELL)/d mu, v_bar = d(c ELL)/d v of the likelihood at the moments of q(f) (mu = a^T m; the adjoints carry c)
+    (tgp_natgrad_qu_f64).  Sites lambda = max(-2 v_bar, site_floor) (site_floor None: no floor), r = mu_bar + lambda mu; with
+    K_ZZ + jitter I = L L^T:  P' = (1 - rho) (Lam Lam^T)^-1 + rho (I + L^-1 K_ZX diag(lambda) K_XZ L^-T),  Lam' Lam'^T = P'^-1,
+    m' = P'^-1 ((1 - rho) (Lam Lam^T)^-1 m + rho L^-1 K_ZX r).  With the Gaussian likelihood's adjoints and rho = 1 it is
+    optimal_qu.  The factorisation of K runs under psd_safe_cholesky's ladder as in optimal_qu (`info["jitter"]`); a q(u)-side
+    matrix that is not positive definite -- Lam Lam^T, or P' for a likelihood that is not log-concave without a floor -- raises
+    NotPSDError naming it (`info["not_pd"]`), no jitter tried, and nothing is written.  `out` = (m, Lam): written in place (they
+    may be the inputs).  `check` False: one call, the status is not read (no host sync).  No autograd."""
+    lib = L.load()
+    X = _c(X, "X")
+    Z, raw_ls, raw_os, m, Lam = _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os"), _c(m.reshape(-1), "m"), _c(Lam, "Lam")
+    mu, mu_bar, v_bar = _c(mu.reshape(-1), "mu"), _c(mu_bar.reshape(-1), "mu_bar"), _c(v_bar.reshape(-1), "v_bar")
+    N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape[1] != D or m.numel() != M or tuple(Lam.shape) != (M, M) or not mu.numel() == mu_bar.numel() == v_bar.numel() == N:
+        raise ValueError("natgrad_qu: X (N, D), Z (M, D), m (M), Lam (M, M), mu, mu_bar, v_bar (N)")
+    dev = X.device
+    m_out, Lam_out = out if out is not None else (torch.empty(M, dtype=torch.float64, device=dev),
+                                                  torch.empty(M, M, dtype=torch.float64, device=dev))
+    lvn = torch.zeros(1, dtype=torch.float64, device=dev)      # required pointer of the struct, not read
+    md, _ = _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, 1.0, jitter, 1.0, None, None, None, kernel)
+    ws, nbytes = _scratch(lib.tgp_natgrad_qu_workspace_bytes(N, D, M), dev, workspace_bytes)
+    status = _status(dev)
+    floor = float("nan") if site_floor is None else float(site_floor)
+    q_side = [0]
+
+    def attempt(jit):
+        md.jitter = jit
+        L.check(lib.tgp_natgrad_qu_f64(md, L.ptr(X), L.ptr(mu), L.ptr(mu_bar), L.ptr(v_bar), float(rho), floor, L.ptr(m_out),
+                                       L.ptr(Lam_out), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()), "tgp_natgrad_qu_f64")
+        if not check:
+            return False
+        st = status.cpu()
+        if int(st[0]) != 0 or int(st[3]) != 0 or int(st[1]) == 1:   # K's factorisation (status[1] == 1: its NaN flag): the ladder's
+            return raise_for_status(st) and int(st[0])
+        q_side[0] = int(st[1])                      # K succeeded: status[1] reports Lam Lam^T (-pivot) or P' (1 + pivot)
+        return False
+    run_jitter_ladder(attempt, jitter, ladder, info=info)
+    if q_side[0] != 0:
+        of_p = q_side[0] > 0
+        what = "P' = (1 - rho) (Lam Lam^T)^-1 + rho (I + L^-1 K_ZX diag(lambda) K_XZ L^-T)" if of_p else "Lam Lam^T"
+        pivot = q_side[0] - 1 if of_p else -q_side[0]
+        if info is not None:
+            info["not_pd"] = "P'" if of_p else "Lam Lam^T"
+        raise NotPSDError("natgrad_qu: %s not positive definite (%s): q(u) is left as it was; more jitter on K_ZZ does not "
+                          "help -- use a site floor (site_floor=0.0) or a smaller step"
+                          % (what, "pivot %d" % pivot if pivot <= M else "it holds NaNs"))
+    return m_out, Lam_out
+
+
+def _ell_rows(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0, lik=None, df=None):
+    """The row-wise ELL launch of a likelihood by its traits, the one its Ell*Function runs (natgrad_step_qu asks by trait, not by
+    class): `flow` None -> ell_gauss, else the quadrature launch at `lik` (None: LIK_FLOW) with `df` beside the noise for the
+    Student-t.  `lvn` None: a likelihood without a noise parameter.  dict(ell, g_mu, g_v, ...)."""
+    if flow is None:
+        return dict(zip(("ell", "g_lvn", "g_mu", "g_v"), ell_gauss(Y, mu, v, lvn, scale=scale)))
+    if lvn is None:
+        return _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, lik)
+    if df is not None:
+        lvn = student_noise(lvn, df)
+    return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_FLOW if lik is None else lik)
+
+
+# ---------------------------------------------------------------------------------------------------
 # greedy conditional-variance selection of inducing points (the pivoted Cholesky factorisation of K_XX)
 # ---------------------------------------------------------------------------------------------------
 def greedy_inducing(X, M, raw_ls, raw_os, kernel="scale_rbf", min_var=1e-8, workspace_bytes=None):

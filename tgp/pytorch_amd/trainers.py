@@ -30,14 +30,24 @@ def return_optimizer(opt, parameters, lr):
 
 class Trainer_SP_regression:
     def __init__(self, model, data_loaders, validate_each, plot, track, Y_std, plot_each, S_test,
-                 inference_in_cpu=False, coverage="sampled", qu="adam"):
+                 inference_in_cpu=False, coverage="sampled", qu="adam", natgrad_lr=1.0):
         self.model = model
         # q(u): "adam" = m and Lam are trained like every other parameter (the reference); "optimal" = they are set to their
         # closed-form optimum before every step and every evaluation and the optimiser trains the hyper-parameters on the
-        # collapsed bound (models.collapsed_bound: Gaussian and warped likelihoods, whitened, one full batch per epoch)
-        if qu not in ("adam", "optimal"):
-            raise ValueError("qu must be 'adam' or 'optimal', got %r" % (qu,))
+        # collapsed bound (models.collapsed_bound: Gaussian and warped likelihoods, whitened, one full batch per epoch);
+        # "natgrad" = every minibatch opens with one natural-gradient step of q(u) at step size natgrad_lr
+        # (models.natgrad_step_qu: any likelihood of one whitened latent GP, any number of minibatches -- natgrad_lr < 1 when
+        # there is more than one), then the optimiser trains the other parameters on the ELBO, in the eager loop
+        if qu not in ("adam", "optimal", "natgrad"):
+            raise ValueError("qu must be 'adam', 'optimal' or 'natgrad', got %r" % (qu,))
         self.qu = qu
+        self.natgrad_lr = float(natgrad_lr)
+        if qu == "natgrad":
+            why = model._natgrad_refusal() if hasattr(model, "_natgrad_refusal") else "the model has no natgrad_step_qu"
+            if why is not None:
+                raise NotImplementedError("qu='natgrad': " + why)
+            if not 0.0 < self.natgrad_lr <= 1.0:
+                raise ValueError("natgrad_lr must be in (0, 1], got %r" % (natgrad_lr,))
         if qu == "optimal":
             why = model._qu_refusal() if hasattr(model, "_qu_refusal") else "the model has no set_optimal_qu"
             if why is not None:
@@ -84,7 +94,7 @@ class Trainer_SP_regression:
         holds already (keep_parameter_groups=True) -- skipped, and naming one again is an error like in the reference.
         Returns (groups, names placed in them)."""
         named = OrderedDict(self.model.named_parameters())
-        if self.qu == "optimal":         # q(u) is a function of the other parameters here: no optimiser holds it
+        if self.qu in ("optimal", "natgrad"):    # q(u) is set in closed form here: no optimiser holds it
             named = OrderedDict((n, q) for n, q in named.items() if not n.startswith("q_U."))
         taken, frozen, groups, placed = set(), set(), [], []
         seen_keys = set()
@@ -140,6 +150,8 @@ class Trainer_SP_regression:
             return None
         if self.qu == "optimal":
             return self._collapsed_engine_for(groups, lr_ALL)
+        if self.qu == "natgrad":         # the step engines hold no natural-gradient step: the eager loop
+            return None
         ld = self.train_loader
         if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1:
             return None
@@ -298,7 +310,15 @@ class Trainer_SP_regression:
         self.KLD_arr += h[:, 2].tolist()
 
     def ELBO_call(self, x, y):
-        loss, elogl, kld = self.model.collapsed_bound(x, y) if self.qu == "optimal" else self.model.ELBO(x, y)
+        if self.qu == "optimal":
+            loss, elogl, kld = self.model.collapsed_bound(x, y)
+        elif self.qu == "natgrad":
+            # one step of q(u), then the ELBO with q(u) as a constant at the jitter the step ended with (as collapsed_bound does):
+            # the backward computes nothing for q_U, whose .grad no optimiser would ever clear
+            info = self.model.natgrad_step_qu(x, y, lr=self.natgrad_lr)
+            loss, elogl, kld = self.model.ELBO(x, y, _qu_jitter=info["jitter"])
+        else:
+            loss, elogl, kld = self.model.ELBO(x, y)
         loss = -loss
         self.param_elbo = [loss, elogl, kld]
         return loss
