@@ -786,7 +786,10 @@ int tgp_kmeans_pp_f64(const double* X, int32_t N, int32_t D, const int64_t* cand
  * Packed weights per net, torch parameter order: [W1 (H,D) | b1 (H) | W2 (H,H) | b2 (H) | ... | Wout (1,H) | bout (1)].
  * Dropout masks are a counter-based hash of (seed, step, net, layer, row, unit); `step_dev` (int32 on the device,
  * e.g. the Adam step counter of tgp_adam_dev_f64; NULL = 0) makes the mask change every step and stay valid under
- * hipGraph replay; forward and backward of one step must see the same value.  H <= 64, L <= 3. */
+ * hipGraph replay; forward and backward of one step must see the same value.  H <= 64, L <= 3.  The backward kernel also
+ * keeps L activation strips of H x 66 doubles in LDS: a shape whose image exceeds one CU's 160 KiB - 1 KiB is refused by
+ * tgp_mlp_backward_f64 / tgp_mlp_backward_adam_f64 with TGP_E_LDS before any launch (L = 3 with H >= 54 at D <= 8; the
+ * forward, which has no strips, runs it).  The host restates the size as ops.MlpSpec.lds_bytes(). */
 typedef struct tgp_mlp {
   int32_t N, D, H, L, nnets;
   int32_t act;      /* 0 relu, 1 tanh */

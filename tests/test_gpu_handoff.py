@@ -117,10 +117,13 @@ def test_environment_variables_do_not_reach_the_engine(monkeypatch):
 
 
 @pytest.mark.parametrize("N,D,M,flow", [(2153, 13, 128, "sal2"),      # 1 792 assembly items, 1 815 parameters outside Lam: the loops
-                                        (2153, 4, 100, "tanh3x2"), (700, 16, 60, None), (455, 13, 5, None)])
+                                        (2153, 4, 100, "tanh3x2"), (700, 16, 60, None), (455, 13, 5, None),
+                                        # general-M path: Lam in k_big_glam (lam_off), the rest in the tail launch that skips it
+                                        (600, 5, 150, "sal2"), (700, 5, 300, None)])
 def test_update_inside_the_backward_launch_equals_the_separate_update(N, D, M, flow):
     """tgp_elbo_step_adam_f64 (Adam inside k_bwd: Lam in the threads that form its gradient, the rest from the LDS mirror of the
-    final block) against the same steps as gradients + tgp_adam_dev: parameters, moments and scalars after three steps."""
+    final block; M > 128: Lam inside k_big_glam, the rest in a launch that skips it) against the same steps as gradients +
+    tgp_adam_dev: parameters, moments and scalars after three steps."""
     a = _engine(N, D, M, flow, seed=5)
     assert a.fused_adam
     for _ in range(3):

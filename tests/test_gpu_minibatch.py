@@ -47,6 +47,60 @@ def test_gather_rows_walks_through_the_epoch():
     assert torch.equal(Xb[:50], X[c0 + 7:c0 + 57])          # shard offset, identity order, cursor left alone
 
 
+@pytest.mark.parametrize("use_index", [True, False])
+@pytest.mark.parametrize("D,nrows", [(1, 100), (16, 10),        # nrows (D + 1) < 256: one workgroup holds the ticket and the cursor
+                                     (1, 300), (16, 150)])      # 3 and 10 workgroups: the last ticket holder advances the cursor
+def test_gather_rows_two_ranks_tile_the_batch_eager_and_replayed(D, nrows, use_index):
+    """tgp_gather_rows_f64 as two ranks use it: offsets 0 and nrows, advance = 2 nrows, each rank its own cursor -- together they
+    serve rows index[c : c + 2 nrows] of the epoch (index NULL: the stored order), exact copies.  `advance` does not divide
+    `wrap` (N = 1000, or 1001 where 2 nrows would divide 1000): the position returns to 0 at the first value >= wrap.  Then ONE captured
+    launch of rank 0, replayed through two epochs, serves what the eager walk served, and its cursor reads [0, 0] at each epoch's
+    end."""
+    from tgp.pytorch_amd import lib as L
+    h = L.load()
+    g = torch.Generator().manual_seed(D * 1000 + nrows)
+    N, adv = 1000, 2 * nrows
+    if N % adv == 0:
+        N = 1001                                             # (20, 200: keep `advance` from dividing `wrap`)
+    per_epoch = -(-N // adv)
+    X = torch.randn(N, D, generator=g, dtype=torch.float64).to(DEV)
+    Y = torch.randn(N, generator=g, dtype=torch.float64).to(DEV)
+    perm = torch.randperm(N, generator=g).to(torch.int32).to(DEV) if use_index else None
+    src = perm.long() if use_index else torch.arange(N, device=DEV)
+
+    def launch(cur, off, Xb, Yb):
+        L.check(h.tgp_gather_rows_f64(L.ptr(X), L.ptr(Y), N, D, L.ptr(perm), L.ptr(cur), off, nrows, adv, N, L.ptr(Xb), L.ptr(Yb),
+                                      L.stream_ptr()), "tgp_gather_rows_f64")
+    curs = [torch.zeros(2, dtype=torch.int32, device=DEV) for _ in range(2)]
+    bufs = [(torch.full((nrows, D), -7.0, dtype=torch.float64, device=DEV), torch.full((nrows,), -7.0, dtype=torch.float64, device=DEV))
+            for _ in range(2)]
+    served = []
+    for step in range(2 * per_epoch):
+        c0 = (step % per_epoch) * adv
+        assert [int(c[0]) for c in curs] == [c0, c0]
+        for r in range(2):
+            launch(curs[r], r * nrows, *bufs[r])
+        torch.cuda.synchronize()
+        Xb, Yb = torch.cat([bufs[0][0], bufs[1][0]]), torch.cat([bufs[0][1], bufs[1][1]])
+        n = min(adv, N - c0)                                 # the rows of the batch that exist (the epoch's last batch is ragged)
+        idx = src[c0:c0 + n]
+        assert torch.equal(Xb[:n], X[idx]) and torch.equal(Yb[:n], Y[idx])
+        nxt = 0 if c0 + adv >= N else c0 + adv
+        assert all(c.tolist() == [nxt, 0] for c in curs)
+        served.append((bufs[0][0].clone(), bufs[0][1].clone()))
+    cur = torch.zeros(2, dtype=torch.int32, device=DEV)
+    Xg, Yg = torch.zeros(nrows, D, dtype=torch.float64, device=DEV), torch.zeros(nrows, dtype=torch.float64, device=DEV)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        launch(cur, 0, Xg, Yg)
+    for step in range(2 * per_epoch):
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(Xg, served[step][0]) and torch.equal(Yg, served[step][1]), step
+        if (step + 1) % per_epoch == 0:
+            assert cur.tolist() == [0, 0]
+
+
 @pytest.mark.parametrize("flow,M,graph", [("sal2", 20, True), ("tanh2x2", 20, False), (None, 150, True)])
 def test_minibatch_engine_matches_oracle_adam_history(flow, M, graph):
     """2 epochs x (3 full batches of 256 + a ragged one of 132), stored order, against the oracle stepped batch by batch

@@ -301,7 +301,7 @@ def mlp_spec(nets, seed=0):
             if ls[-1].linear.in_features != H:
                 return None
         spec = ops.MlpSpec(D, H, Lh, len(nets), act=act, drop_p=p, seed=seed)
-        if spec.lds_bytes() > 158 * 1024:      # padded weights + activation strips must fit one CU's LDS (tgp_mlp.hip)
+        if spec.lds_bytes() > ops.MLP_LDS_MAX:      # padded weights + activation strips must fit one CU's LDS (tgp_mlp.hip)
             return None
         return spec
     except (KeyError, AttributeError, IndexError, TypeError):

@@ -1650,6 +1650,9 @@ def interval_score(lo, hi, y, alpha):
 # ---------------------------------------------------------------------------------------------------
 # per-row parameter networks of the input-dependent flows (models/flow.py:836-897)
 # ---------------------------------------------------------------------------------------------------
+MLP_LDS_MAX = 160 * 1024 - 1024     # what tgp_launch.hpp ensure_lds grants a kernel on gfx950 (160 KiB less the static words)
+
+
 class MlpSpec:
     """nnets MLPs of one architecture D -> H x L -> 1 (Linear -> act -> Dropout per hidden layer)."""
 
@@ -1670,11 +1673,16 @@ class MlpSpec:
         return self.D * self.H + self.H + (self.L - 1) * (self.H * self.H + self.H) + self.H + 1
 
     def lds_bytes(self):
-        """LDS image of the backward kernel (tgp_mlp.hip mlp_lds): padded weights + activation strips."""
-        kp0, kph = (self.D + 3) // 4 * 4, (self.H + 3) // 4 * 4
-        w = kph * kp0 + kph + (self.L - 1) * (kph * kph + kph) + kph + 2
-        n = w + (kp0 + self.L * kph) * 65           # strips [unit][64 rows + 1]
-        return ((n + 1) // 2 * 2 + 64) * 8           # + d out of the block's 64 rows
+        """Dynamic LDS of the backward kernel, tgp_mlp.hip mlp_lds(D, H, L, bwd = true) restated term by term: the weight image
+        padded to the kernel variant's R = 4 NKS units (32, 52 or 64 -- not to H), the input strip, the output layer's per-wave
+        sums and L activation strips [H][66].  A shape is trainable on the kernels iff this is <= MLP_LDS_MAX (ensure_lds);
+        tgp_mlp_backward_f64 answers TGP_E_LDS beyond it (L = 3 with H > 53, at D <= 8)."""
+        R = 4 * (8 if self.H <= 32 else 13 if self.H <= 52 else 16)
+        kp0, st = (self.D + 3) // 4 * 4, 66
+        n = R * kp0 + R + (self.L - 1) * (R * R + R) + R + 2      # W_0, b_0, the hidden layers' W_l, b_l, then wo, bo
+        n += kp0 * st                                             # x0
+        n = (n + 4 * (self.H + 1) + 1) // 2 * 2                   # dwo
+        return (n + self.L * self.H * st) * 8
 
     def struct(self, N, training):
         d = L.TgpMlp()
