@@ -471,8 +471,8 @@ int tgp_natgrad_qu_f64(const tgp_model* model, const double* X, const double* mu
                        size_t workspace_bytes, void* stream) {
   if (model == nullptr) return -1;
   if (!(rho > 0.0 && rho <= 1.0) || !known_kernel(model->kernel) || natgrad_qu_workspace_bytes(model->N, model->D, model->M) == 0) {
-    set_error_text("tgp_natgrad_qu_f64: rho = %g, kernel = %d, N = %d, D = %d, M = %d outside 0 < rho <= 1, kernel TGP_KERNEL_SCALE_RBF "
-                   "or TGP_KERNEL_SCALE_MATERN32, N >= 1, 1 <= M <= %d, 1 <= D <= 16", rho, model->kernel, model->N, model->D, model->M,
+    set_error_text("tgp_natgrad_qu_f64: rho = %g, kernel = %d, N = %d, D = %d, M = %d outside 0 < rho <= 1, " TGP_KNOWN_KERNELS_TEXT
+                   ", N >= 1, 1 <= M <= %d, 1 <= D <= 16", rho, model->kernel, model->N, model->D, model->M,
                    TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
   }
@@ -497,7 +497,7 @@ int tgp_greedy_inducing_f64(const double* X, int32_t N, int32_t D, const double*
                             size_t workspace_bytes, void* stream) {
   if (!known_kernel(kernel) || greedy_inducing_workspace_bytes(N, D, M) == 0) {
     set_error_text("tgp_greedy_inducing_f64: N = %d, D = %d, M = %d, kernel = %d outside 1 <= M <= min(N, %d), 1 <= D <= 16, "
-                   "kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, kernel, TGP_BIG_MAX_M);
+                   TGP_KNOWN_KERNELS_TEXT, N, D, M, kernel, TGP_BIG_MAX_M);
     return TGP_E_UNSUPPORTED;
   }
   if (!X) return -1;
@@ -522,7 +522,7 @@ int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t 
   if (model == nullptr) return -1;
   if (!known_kernel(model->kernel) || pathwise_workspace_bytes(1, model->D, model->M, R2, S) == 0) {
     set_error_text("tgp_pathwise_coeff_f64: D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside 1 <= D <= 16, 1 <= M <= %d, "
-                   "1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", model->D, model->M, R2, S,
+                   "1 <= R2 <= %d, 1 <= S <= %d, " TGP_KNOWN_KERNELS_TEXT, model->D, model->M, R2, S,
                    model->kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
     return TGP_E_UNSUPPORTED;
   }
@@ -541,7 +541,7 @@ int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D,
                           void* stream) {
   if (!known_kernel(kernel) || pathwise_workspace_bytes(N, D, M, R2, S) == 0) {
     set_error_text("tgp_pathwise_eval_f64: N = %d, D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside N >= 1, 1 <= D <= 16, "
-                   "1 <= M <= %d, 1 <= R2 <= %d, 1 <= S <= %d, kernel TGP_KERNEL_SCALE_RBF or TGP_KERNEL_SCALE_MATERN32", N, D, M, R2, S,
+                   "1 <= M <= %d, 1 <= R2 <= %d, 1 <= S <= %d, " TGP_KNOWN_KERNELS_TEXT, N, D, M, R2, S,
                    kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
     return TGP_E_UNSUPPORTED;
   }

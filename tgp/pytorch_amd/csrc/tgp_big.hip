@@ -714,6 +714,7 @@ __device__ __forceinline__ void big_hdr_block(const BigPlan& p, const tgp_model&
     hdr[H_ETA] = md.log_var_noise[0];
     hdr[H_EINV] = exp(-md.log_var_noise[0]);
     hdr[H_SIG_OS] = sigmoid_d(md.raw_os[0]);
+    hdr[H_ALPHA] = cov_alpha(p.kernel, md.raw_os);
     status[0] = 0;
     status[1] = 0;
     status[2] = 0;
@@ -793,10 +794,11 @@ __device__ __forceinline__ void big_kmm_element(const BigPlan& p, const tgp_mode
       const double t = zrv[d] - zcv[d];
       d2 += t * t;
     }
-    k = cov_value(p.kernel, ws[p.hdr + H_S2], d2);
+    const Cov cov = make_cov(p.kernel, ws[p.hdr + H_S2], ws[p.hdr + H_ALPHA]);
+    k = cov_value(cov, d2);
     if (row == col) k += md.jitter;
     if constexpr (!FIRST) {
-      if (p.kernel != TGP_KERNEL_SCALE_RBF) ws[p.Kmmg + e] = cov_gweight(p.kernel, ws[p.hdr + H_S2], d2);
+      if (p.kernel != TGP_KERNEL_SCALE_RBF) ws[p.Kmmg + e] = cov_gweight(cov, d2);
       if (k != k) status[1] = 1;
       if (col <= row) lq = md.Lam[(size_t)row * M + col];
     }
@@ -1321,7 +1323,10 @@ __global__ __launch_bounds__(256) void k_big_xaug(BigPlan p, const double* __res
   ws[p.Xaug + e] = x;
 }
 
-// K'[n][m] = k(xs_n, zs_m) (gweight: its derivative weight k_g instead); block = 32 data rows x 128 inducing columns
+// K'[n][m] = k(xs_n, zs_m) (gweight: its derivative weight k_g instead); block = 32 data rows x 128 inducing columns.
+// KERNEL: the covariance function's id as a compile-time constant -- one exponential per element is all the RBF instance holds
+// (a runtime switch over four kernels cost the RBF minibatch step 0.2-0.5 %, profiles/kernel_family.txt)
+template <int KERNEL>
 __global__ __launch_bounds__(256) void k_big_knm(BigPlan p, const double* __restrict__ X, int nrows, double* __restrict__ ws,
                                                   int gweight) {
   __shared__ double xl[32 * 16];
@@ -1337,7 +1342,7 @@ __global__ __launch_bounds__(256) void k_big_knm(BigPlan p, const double* __rest
 #pragma unroll
   for (int d = 0; d < 16; ++d) zs[d] = d < DP ? ws[p.Zs + (size_t)m * DP + d] : 0.0;
   __syncthreads();
-  const double s2 = ws[p.hdr + H_S2];
+  const Cov cov = make_cov(KERNEL, ws[p.hdr + H_S2], KERNEL == TGP_KERNEL_SCALE_RQ ? ws[p.hdr + H_ALPHA] : 0.0);
   double* __restrict__ Kc = ws + p.Kc;
   for (int u = 0; u < 16; ++u) {
     const int nl = rg * 16 + u;
@@ -1346,7 +1351,16 @@ __global__ __launch_bounds__(256) void k_big_knm(BigPlan p, const double* __rest
       const double t = xl[nl * DP + d] - zs[d];
       d2 += t * t;
     }
-    Kc[(size_t)(n0 + nl) * p.MP + m] = m < p.M ? (gweight ? cov_gweight(p.kernel, s2, d2) : cov_value(p.kernel, s2, d2)) : 0.0;
+    Kc[(size_t)(n0 + nl) * p.MP + m] = m < p.M ? (gweight ? cov_gweight(cov, d2) : cov_value(cov, d2)) : 0.0;
+  }
+}
+
+static void launch_big_knm(const BigPlan& p, dim3 grid, hipStream_t st, const double* X, int nrows, double* ws, int gweight) {
+  switch (p.kernel) {
+    case TGP_KERNEL_SCALE_MATERN32: hipLaunchKernelGGL(k_big_knm<TGP_KERNEL_SCALE_MATERN32>, grid, dim3(256), 0, st, p, X, nrows, ws, gweight); break;
+    case TGP_KERNEL_SCALE_MATERN52: hipLaunchKernelGGL(k_big_knm<TGP_KERNEL_SCALE_MATERN52>, grid, dim3(256), 0, st, p, X, nrows, ws, gweight); break;
+    case TGP_KERNEL_SCALE_RQ: hipLaunchKernelGGL(k_big_knm<TGP_KERNEL_SCALE_RQ>, grid, dim3(256), 0, st, p, X, nrows, ws, gweight); break;
+    default: hipLaunchKernelGGL(k_big_knm<TGP_KERNEL_SCALE_RBF>, grid, dim3(256), 0, st, p, X, nrows, ws, gweight); break;
   }
 }
 
@@ -1916,7 +1930,7 @@ static int big_chunk_kernel(const BigPlan& p, const double* Xc, int nrows, doubl
     hipLaunchKernelGGL(k_big_xaug, dim3((unsigned)((size_t)NC * BIG_XW / 256)), dim3(256), 0, st, p, Xc, nrows, ws);
     LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_big_knm, dim3(MP / 128, NC / 32), dim3(256), 0, st, p, Xc, nrows, ws, 0);
+  launch_big_knm(p, dim3(MP / 128, NC / 32), st, Xc, nrows, ws, 0);
   LAUNCH_CHECK();
   return 0;
 }
@@ -2032,7 +2046,7 @@ int launch_big_step(const tgp_model& md, const FlowProg& fp, const double* X, co
         GemmArgs atk = at;
         atk.C = ws + p.TpartK;
         GEMM(true, false, atk);
-        hipLaunchKernelGGL(k_big_knm, dim3(MP / 128, NC / 32), dim3(256), 0, st, pc, X + c0 * p.D, nrows, ws, 1);
+        launch_big_knm(pc, dim3(MP / 128, NC / 32), st, X + c0 * p.D, nrows, ws, 1);
         LAUNCH_CHECK();
       }
       GEMM(true, false, at);

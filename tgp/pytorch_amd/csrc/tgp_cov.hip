@@ -47,10 +47,10 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
   __shared__ double Kt[TL_KC * TL_LDN];
   __shared__ double xsT[16 * TL_T];  // [d][column]: scaled rows of X*
   __shared__ double red[256];
-  __shared__ double ils[17];
+  __shared__ double ils[TL_ILS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const int n0 = blockIdx.x * TL_T;
-  tile_scales(D, raw_ls, raw_os, ils);
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
   __syncthreads();
   for (int i = tid; i < 16 * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
     xsT[i] = d < D ? X[(size_t)n * D + d] * ils[d] : 0.0;
   }
   __syncthreads();
-  const double s2 = ils[16];
+  const Cov cov = tile_cov(kernel, ils);
   const int gk = tid >> 4, gc = tid & 15;  // generation role: contraction index gk of the step, columns gc + 16 u
   const int M16 = (M + 15) / 16 * 16;
   double mup = 0.0;
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_cov_a(int kernel, const double* __restr
             const double t = xsT[d * TL_T + c] - z[d];
             d2 += t * t;
           }
-          Kt[gk * TL_LDN + c] = cov_value(kernel, s2, d2);
+          Kt[gk * TL_LDN + c] = cov_value(cov, d2);
         }
       }
       __syncthreads();
@@ -131,12 +131,12 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
                                                     double* __restrict__ Sigma) {
   __shared__ __attribute__((aligned(16))) double buf[TL_T * TL_LDT];  // operand tiles (2 x 16 x 80), then the output tile
   __shared__ double xiT[16 * TL_T], xjT[16 * TL_T];
-  __shared__ double ils[17];
+  __shared__ double ils[TL_ILS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   int ti, tj;
   tile_lower(blockIdx.x, ti, tj);
   const int i0 = ti * TL_T, j0 = tj * TL_T;
-  tile_scales(D, raw_ls, raw_os, ils);
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
   __syncthreads();
   for (int i = tid; i < 16 * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
     xiT[i] = d < D ? X[(size_t)ni * D + d] * ils[d] : 0.0;
     xjT[i] = d < D ? X[(size_t)nj * D + d] * ils[d] : 0.0;
   }
-  const double s2 = ils[16];
+  const Cov cov = tile_cov(kernel, ils);
   double* At = buf;
   double* Ct = buf + TL_KC * TL_LDN;
   d4 acc[4];
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_cov_sigma(int kernel, const double* __r
         const double u = xiT[d * TL_T + il] - xjT[d * TL_T + jl];
         d2 += u * u;
       }
-      buf[il * TL_LDT + jl] = cov_value(kernel, s2, d2) + acc[c][r];
+      buf[il * TL_LDT + jl] = cov_value(cov, d2) + acc[c][r];
     }
   __syncthreads();
   if (ti != tj) {

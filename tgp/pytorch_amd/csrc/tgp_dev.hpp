@@ -87,7 +87,8 @@ struct Plan {
 };
 
 // hdr slots
-enum { H_S2 = 0, H_KL = 1, H_ETA = 2, H_EINV = 3, H_SIG_OS = 4, H_STEP = 5, H_STAMP = 8, H_PSTAMP = 32, H_OUT = 60, H_N = 64 };
+enum { H_S2 = 0, H_KL = 1, H_ETA = 2, H_EINV = 3, H_SIG_OS = 4, H_STEP = 5, H_ALPHA = 6, H_STAMP = 8, H_PSTAMP = 32, H_OUT = 60, H_N = 64 };
+// (H_ALPHA: the RQ kernel's alpha, general-M path only)
 // (H_OUT .. H_OUT+3: where tgp_qf_moments_bwd_f64 lets the backward chain put its four ELBO scalars -- it has no `out`)
 // slab scalar slots
 enum { C_ELL = 0, C_ETAB = 1, C_SVB = 2, C_PAD = 3, C_THETA = 4 };
@@ -192,23 +193,6 @@ __device__ __forceinline__ double exp_fast(double x) {
   return ldexp(fma(s1, r8, s0), (int)k);
 }
 
-// Covariance value from the squared scaled distance d2 = |(x - z)/l|^2, and the weight of -1/2 d(d2) in its
-// derivative (k_g = -2 dk/d(d2)):   RBF      k = s2 exp(-d2/2)                       k_g = k
-//                                   MATERN32 k = s2 (1 + a r) exp(-a r), a = sqrt 3    k_g = 3 s2 exp(-a r)
-// with r = sqrt(max(d2, 1e-30)) as gpytorch's covar_dist clamps it (third-party formula, gpytorch 1.1.1 MaternKernel).
-#define TGP_SQRT3 1.7320508075688772
-__device__ __forceinline__ double cov_value(int kernel, double s2, double d2) {
-  if (kernel == TGP_KERNEL_SCALE_MATERN32) {
-    const double ar = TGP_SQRT3 * sqrt(fmax(d2, 1e-30));
-    return s2 * (1.0 + ar) * exp_fast(-ar);
-  }
-  return s2 * exp_fast(-0.5 * d2);
-}
-__device__ __forceinline__ double cov_gweight(int kernel, double s2, double d2) {
-  if (kernel == TGP_KERNEL_SCALE_MATERN32) return 3.0 * s2 * exp_fast(-TGP_SQRT3 * sqrt(fmax(d2, 1e-30)));
-  return s2 * exp_fast(-0.5 * d2);
-}
-
 // 1/sqrt(d): v_rsq_f64 estimate + two Newton steps (same scheme as rsqrt_nr below, declared here for the flows)
 __device__ __forceinline__ double rsqrt_nr_fwd(double d) {
   double y = __builtin_amdgcn_rsq(d);
@@ -253,6 +237,55 @@ __device__ __forceinline__ double rcp_fast(double x) {
   y = fma(fma(-x, y, 1.0), y, y);
   y = fma(fma(-x, y, 1.0), y, y);
   return y;
+}
+
+// Covariance value from the squared scaled distance d2 = |(x - z)/l|^2, and the weight of -1/2 d(d2) in its
+// derivative (k_g = -2 dk/d(d2)):   RBF      k = s2 exp(-d2/2)                                  k_g = k
+//                                   MATERN32 k = s2 (1 + a r) exp(-a r), a = sqrt 3               k_g = 3 s2 exp(-a r)
+//                                   MATERN52 k = s2 (1 + a r + 5/3 d2) exp(-a r), a = sqrt 5      k_g = 5/3 s2 (1 + a r) exp(-a r)
+//                                   RQ       k = s2 (1 + d2/(2 alpha))^-alpha                     k_g = s2 (1 + d2/(2 alpha))^(-alpha-1)
+// with r = sqrt(max(d2, 1e-30)) as gpytorch's covar_dist clamps it (third-party formulas, gpytorch 1.1.1 MaternKernel, RQKernel).
+// Every k_g is finite at d2 = 0: the Z and length-scale gradients are formed from expanded statistics that cancel there.
+// The RQ power is exp(-alpha log1p(d2/(2 alpha))) on the short-chain exp and log above, never pow.
+#define TGP_SQRT3 1.7320508075688772
+#define TGP_SQRT5 2.2360679774997897
+// what a kernel evaluates a covariance with: the id, the output scale and the RQ kernel's alpha with 1/(2 alpha) (zero otherwise)
+struct Cov {
+  int kernel;
+  double s2, alpha, inv2a;
+};
+// alpha sits behind the raw output scale, and only the RQ kernel's raw_os has that second double
+__device__ __forceinline__ double cov_alpha(int kernel, const double* __restrict__ raw_os) {
+  return kernel == TGP_KERNEL_SCALE_RQ ? raw_os[1] : 0.0;
+}
+__device__ __forceinline__ Cov make_cov(int kernel, double s2, double alpha) {
+  return Cov{kernel, s2, alpha, kernel == TGP_KERNEL_SCALE_RQ ? 0.5 / alpha : 0.0};
+}
+// log(1 + x), x >= 0: log_fast of the rounded sum plus the first-order term of what the rounding dropped
+__device__ __forceinline__ double log1p_fast(double x) {
+  const double u = 1.0 + x;
+  return fma(x - (u - 1.0), __builtin_amdgcn_rcp(u), log_fast(u));
+}
+__device__ __forceinline__ double cov_value(const Cov& c, double d2) {
+  if (c.kernel == TGP_KERNEL_SCALE_MATERN32) {
+    const double ar = TGP_SQRT3 * sqrt(fmax(d2, 1e-30));
+    return c.s2 * (1.0 + ar) * exp_fast(-ar);
+  }
+  if (c.kernel == TGP_KERNEL_SCALE_MATERN52) {
+    const double r = sqrt(fmax(d2, 1e-30)), ar = TGP_SQRT5 * r;
+    return c.s2 * fma(5.0 / 3.0, r * r, 1.0 + ar) * exp_fast(-ar);
+  }
+  if (c.kernel == TGP_KERNEL_SCALE_RQ) return c.s2 * exp_fast(-c.alpha * log1p_fast(d2 * c.inv2a));
+  return c.s2 * exp_fast(-0.5 * d2);
+}
+__device__ __forceinline__ double cov_gweight(const Cov& c, double d2) {
+  if (c.kernel == TGP_KERNEL_SCALE_MATERN32) return 3.0 * c.s2 * exp_fast(-TGP_SQRT3 * sqrt(fmax(d2, 1e-30)));
+  if (c.kernel == TGP_KERNEL_SCALE_MATERN52) {
+    const double ar = TGP_SQRT5 * sqrt(fmax(d2, 1e-30));
+    return (5.0 / 3.0) * c.s2 * (1.0 + ar) * exp_fast(-ar);
+  }
+  if (c.kernel == TGP_KERNEL_SCALE_RQ) return c.s2 * exp_fast(-(c.alpha + 1.0) * log1p_fast(d2 * c.inv2a));
+  return c.s2 * exp_fast(-0.5 * d2);
 }
 
 // F.softplus (threshold 20) and sigmoid on the short-chain exp / log above.  The library log1p(exp(x)) is ~250

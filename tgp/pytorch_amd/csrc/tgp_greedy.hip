@@ -101,6 +101,7 @@ __global__ __launch_bounds__(GR_WG) void k_greedy_step(int kernel, const double*
   if (j > 0 && st >= 0 && st < j) return;
   if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
   const double s2 = softplus_d(raw_os[0]);
+  const Cov cov = make_cov(kernel, s2, cov_alpha(kernel, raw_os));
   double dp = s2, tr = (double)N * s2;
   int p = 0;
   if (j > 0) gr_reduce_records(part + (size_t)((j - 1) & 1) * nwg * GR_REC, nwg, dp, p, tr, red);
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(GR_WG) void k_greedy_step(int kernel, const double*
     double acc = 0.0;
 #pragma unroll 8
     for (int l = 0; l < j; ++l) acc += cn[(size_t)l * N] * cp[l];
-    const double c = (cov_value(kernel, s2, d2) - acc) / sqrt(dp);
+    const double c = (cov_value(cov, d2) - acc) / sqrt(dp);
     C[(size_t)j * N + n] = c;
     const double dold = j == 0 ? s2 : d[n];
     const bool picked = dold < 0.0 || n == (size_t)p;

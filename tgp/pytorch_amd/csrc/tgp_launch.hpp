@@ -128,7 +128,12 @@ struct KzzSections {
   }
 };
 inline bool inducing_limits(int M, int D) { return M >= 1 && M <= TGP_BIG_MAX_M && D >= 1 && D <= 16; }
-inline bool known_kernel(int kernel) { return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32; }
+inline bool known_kernel(int kernel) {
+  return kernel == TGP_KERNEL_SCALE_RBF || kernel == TGP_KERNEL_SCALE_MATERN32 || kernel == TGP_KERNEL_SCALE_MATERN52 ||
+         kernel == TGP_KERNEL_SCALE_RQ;
+}
+// how the entries' refusal texts name them
+#define TGP_KNOWN_KERNELS_TEXT "kernel TGP_KERNEL_SCALE_RBF, _MATERN32, _MATERN52 or _RQ"
 
 // What the host asks about a likelihood, one row per TGP_LIK_* id (the table: tgp_lik.hip).  The two launchers take the same
 // arguments for every row -- ell: ell_plan's LPR, NB, workgroups and LDS, `ext`: the program holds a kind past STEPTANH.

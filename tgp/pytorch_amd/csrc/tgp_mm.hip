@@ -981,12 +981,12 @@ __global__ __launch_bounds__(256) void k_cov_tile(int kernel, const double* __re
                                                    const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
                                                    double jitter, int self, double* __restrict__ K) {
   __shared__ double xl[COV_ROWS * 16];
-  __shared__ double ils[17];
+  __shared__ double ils[18];  // 1/l, s2, alpha
   const int tid = threadIdx.x, cp = tid & 63, rg = tid >> 6;
   const long n0 = (long)blockIdx.x * COV_ROWS;
   const int m0 = blockIdx.y * COV_COLS + 2 * cp;
   if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  if (tid == 64) { ils[16] = softplus_d(raw_os[0]); ils[17] = cov_alpha(kernel, raw_os); }
   // the thread's two X2 rows (clamped: out-of-range columns compute a finite value that is never stored)
   double z0[16], z1[16];
   {
@@ -1038,7 +1038,8 @@ __global__ __launch_bounds__(256) void k_cov_tile(int kernel, const double* __re
       exp_fast_n<4>(e);
       TGP_EACH(u, 4) e[u] *= s2;
     } else {
-      TGP_EACH(u, 4) e[u] = cov_value(kernel, s2, e[u]);
+      const Cov cov = make_cov(kernel, s2, ils[17]);
+      TGP_EACH(u, 4) e[u] = cov_value(cov, e[u]);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -1072,13 +1073,13 @@ __global__ __launch_bounds__(256) void k_cov_flat(int kernel, const double* __re
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* zT = reinterpret_cast<double*>(smem_raw);  // D x N2
   double* xT = zT + (size_t)D * N2;                  // D x COVF_ROWS
-  __shared__ double ils[17];
+  __shared__ double ils[18];  // 1/l, s2, alpha
   const int tid = threadIdx.x;
   const long n0 = (long)blockIdx.x * COVF_ROWS;
   const long nrem = (long)N1 - n0;
   const int nr = (int)(nrem < COVF_ROWS ? nrem : COVF_ROWS);
   if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  if (tid == 64) { ils[16] = softplus_d(raw_os[0]); ils[17] = cov_alpha(kernel, raw_os); }
   __syncthreads();
   for (int i = tid; i < N2 * D; i += 256) {
     const int c = i / D, d = i - c * D;
@@ -1113,7 +1114,8 @@ __global__ __launch_bounds__(256) void k_cov_flat(int kernel, const double* __re
       exp_fast_n<4>(ev);
       TGP_EACH(u, 4) ev[u] *= s2;
     } else {
-      TGP_EACH(u, 4) ev[u] = cov_value(kernel, s2, ev[u]);
+      const Cov cov = make_cov(kernel, s2, ils[17]);
+      TGP_EACH(u, 4) ev[u] = cov_value(cov, ev[u]);
     }
     if (self) {
       if (n0 + r == c) ev[0] += jitter;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
   __shared__ double Ki[TL_KC * TL_LDN], Kj[TL_KC * TL_LDN];
   __shared__ double ziT[DP * TL_T], zjT[DP * TL_T];  // [d][inducing point]: scaled rows of Z
   __shared__ double red[16 * TL_T];
-  __shared__ double ils[17];
+  __shared__ double ils[TL_ILS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const int t = blockIdx.x, g = blockIdx.y;
   int ti, tj;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
   bool has_r = Y != nullptr;
   if constexpr (W) has_r = rw.b != nullptr;
   const bool diag = ti == tj, want_b = tj == 0 && has_r && bpart != nullptr;
-  tile_scales(D, raw_ls, raw_os, ils);
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
   __syncthreads();
   for (int i = tid; i < DP * TL_T; i += 256) {
     const int d = i >> 6, c = i & 63;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
     zjT[i] = d < D ? Z[(size_t)mj * D + d] * ils[d] : 0.0;
   }
   __syncthreads();
-  const double s2 = ils[16];
+  const Cov cov = tile_cov(kernel, ils);
   const int gk = tid >> 4, gc = tid & 15;  // generation role: row gk of the step, inducing points gc + 16 u
   const int n_begin = g * G, n_end = n_begin + G < N ? n_begin + G : N;
   const double* Bt = diag ? Ki : Kj;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
           const double q = ziT[d * TL_T + c] - x[d];
           d2 += q * q;
         }
-        const double kv = valid ? cov_value(kernel, s2, d2) : 0.0;
+        const double kv = valid ? cov_value(cov, d2) : 0.0;
         Ki[gk * TL_LDN + c] = kv;
         bp[u] += kv * yv;
       }
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void k_kxxk(int kernel, const double* __restri
             const double q = zjT[d * TL_T + c] - x[d];
             d2 += q * q;
           }
-          Kj[gk * TL_LDN + c] = valid ? cov_value(kernel, s2, d2) : 0.0;
+          Kj[gk * TL_LDN + c] = valid ? cov_value(cov, d2) : 0.0;
         }
       }
     }

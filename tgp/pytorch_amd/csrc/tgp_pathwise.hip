@@ -75,14 +75,14 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
   __shared__ double xsT[DP * RW];    // [d][data row]: scaled rows of X
   __shared__ double omS[2][8 * 16];  // [step parity][frequency of the step][d]: the step's rows of omega
   __shared__ double zS[2][16 * 16];  // [step parity][inducing point of the step][d]: the step's scaled rows of Z
-  __shared__ double ils[17];
+  __shared__ double ils[TL_ILS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
   const size_t n0 = (size_t)blockIdx.x * RW;
   const int pk = tid >> 4, pd = tid & 15;  // staging role: row pk of a step's omega / Z rows, dimension pd
   // the wave's part of the product (wave-uniform): with RW = 16 and one sample tile only wave 0 multiplies
   const int rt = RW == 64 ? 16 * w : 0, t0 = RW == 64 ? 0 : w, tstep = RW == 64 ? 1 : 4;
   const bool mma = RW == 64 || NT >= 4 || w == 0;
-  tile_scales(D, raw_ls, raw_os, ils);
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
   __syncthreads();
   for (int i = tid; i < DP * RW; i += 256) {
     const int d = i / RW, c = i % RW;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
   if (tid < 128) omS[0][tid] = pd < D ? omega[(size_t)(pk < R2 ? pk : R2 - 1) * D + pd] : 0.0;
   if (M > 0) zS[0][tid] = pd < D ? Z[(size_t)(pk < M ? pk : M - 1) * D + pd] * ils[pd] : 0.0;
   __syncthreads();
-  const double s2 = ils[16];
+  const Cov cov = tile_cov(kernel, ils);
   d4 acc[NTW];
 #pragma unroll
   for (int u = 0; u < NTW; ++u) acc[u] = d4{0.0, 0.0, 0.0, 0.0};
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
             const double q = xsT[d * RW + c] - z[d];
             d2 += q * q;
           }
-          Ft[gk * LDN + c] = cov_value(kernel, s2, d2);
+          Ft[gk * LDN + c] = cov_value(cov, d2);
         }
       }
       zS[par ^ 1][tid] = pre;  // (read by the next step, behind this step's two barriers)

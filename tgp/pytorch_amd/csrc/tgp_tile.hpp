@@ -12,12 +12,16 @@ constexpr int TL_LDN = 80;  // LDS stride (f64) of a [16 k][64 n] operand tile: 
 constexpr int TL_LDK = 18;  // LDS stride (f64) of a [64 r][16 k] operand tile: 16 rows x 2 k of a half wave in distinct banks
 constexpr int TL_LDT = 65;  // LDS stride (f64) of the 64 x 64 output tile: conflict-free along rows and along columns
 
-// ils[d] = 1 / length-scale d for d < D and zero above, ils[16] = the output scale.  The caller's barrier follows.
-__device__ __forceinline__ void tile_scales(int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os, double* ils) {
+// ils[d] = 1 / length-scale d for d < D and zero above, ils[16] = the output scale, ils[17] = the RQ kernel's alpha (TL_ILS doubles).
+// The caller's barrier follows; tile_cov reads the covariance description back after it.
+constexpr int TL_ILS = 18;
+__device__ __forceinline__ void tile_scales(int kernel, int D, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                            double* ils) {
   const int tid = threadIdx.x;
   if (tid < 16) ils[tid] = tid < D ? 1.0 / softplus_d(raw_ls[tid]) : 0.0;
-  if (tid == 64) ils[16] = softplus_d(raw_os[0]);
+  if (tid == 64) { ils[16] = softplus_d(raw_os[0]); ils[17] = cov_alpha(kernel, raw_os); }
 }
+__device__ __forceinline__ Cov tile_cov(int kernel, const double* ils) { return make_cov(kernel, ils[16], ils[17]); }
 
 // tile t of the lower block triangle, row major: (ti, tj), tj <= ti
 __device__ __forceinline__ void tile_lower(int t, int& ti, int& tj) {

@@ -122,13 +122,13 @@ __global__ __launch_bounds__(256) void k_kmm_bwd(int kernel, const double* __res
                                                   const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
                                                   const double* __restrict__ Kbar, double* __restrict__ Zbar,
                                                   double* __restrict__ part) {
-  __shared__ double ils[17];
+  __shared__ double ils[TL_ILS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  tile_scales(D, raw_ls, raw_os, ils);
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
   __syncthreads();
   const int i = blockIdx.x * 4 + w;
   if (i >= M) return;
-  const double s2 = ils[16];
+  const Cov cov = tile_cov(kernel, ils), cov1 = make_cov(kernel, 1.0, cov.alpha);
   double zi[16], gz[16], gl[16], go = 0.0;
 #pragma unroll
   for (int d = 0; d < 16; ++d) {
@@ -144,8 +144,8 @@ __global__ __launch_bounds__(256) void k_kmm_bwd(int kernel, const double* __res
       d2 += u[d] * u[d];
     }
     const double s = Kbar[(size_t)i * M + j] + Kbar[(size_t)j * M + i];
-    go += s * cov_value(kernel, 1.0, d2);
-    const double sk = s * cov_gweight(kernel, s2, d2);
+    go += s * cov_value(cov1, d2);
+    const double sk = s * cov_gweight(cov, d2);
 #pragma unroll
     for (int d = 0; d < 16; ++d) {
       const double t = sk * u[d];

@@ -37,12 +37,14 @@ ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "mean_a", "mean_b"
 EAGER_ONLY = {"bernoulli": L.LIK_BERNOULLI, "poisson": L.LIK_POISSON, "negbinomial": L.LIK_NEGBIN, "studentt": L.LIK_STUDENT}
 
 
-def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, collective=None, per_row=False, minibatch=False):
+def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, collective=None, per_row=False, minibatch=False,
+                   kernel=None):
     """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
     combination, else the message both refuse it with (_refuse) before they load the library or touch the device; the
     trainers take the eager loop on a message.  A pure function of the description: `mean` = None / "linear" / "identity",
     `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "negbinomial" / "studentt" / "multiclass" / "hetero", `collective` as passed to the engine (asking
-    for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`)."""
+    for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`),
+    `kernel` = the covariance function's instance_kernel name (None: any but 'scale_rq')."""
     multi_rank = int(world_size) > 1 or collective is not None
     if not is_whiten:      # `params` of an unwhitened model describe q(u) itself; the captured step has no transform in it
         return "the step engines need is_whiten=True: an unwhitened q(u) trains on the eager path (Trainer_SP), on one rank"
@@ -68,6 +70,9 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
             return "the warped likelihood's engine is single-rank (world_size = 1): no data-parallel warped step"
         if per_row:
             return "the warped likelihood takes shared flow parameters only"
+    if kernel == "scale_rq":   # (as the Student-t likelihood's nu behind log_var_noise)
+        return ("the step engines have no rational-quadratic kernel: their flat parameter buffer has one slot behind raw_os and "
+                "the kernel reads {raw_outputscale, alpha} there; 'scale_rq' trains on the eager path (ops.ElboFunction)")
     return None
 
 
@@ -328,7 +333,7 @@ class ElboEngine:
         each other's intermediates.  `fused_adam` False: Adam stays a launch of its own where the update could ride in the
         backward launches.  What is refused, and why, is engine_refusal()."""
         _refuse(is_whiten=is_whiten, mean=None if mean is None else mean[0], likelihood=likelihood, world_size=world_size,
-                collective=collective, per_row=mlp is not None or rowp is not None)
+                collective=collective, per_row=mlp is not None or rowp is not None, kernel=kernel)
         if likelihood not in (None, "warped"):
             raise ValueError("likelihood must be None or 'warped'")
         self.collapsed = bool(collapsed)
@@ -853,7 +858,8 @@ class MinibatchEngine:
         mean = engine_kw.get("mean")
         _refuse(is_whiten=engine_kw.get("is_whiten", True), mean=None if mean is None else mean[0],
                 likelihood=engine_kw.get("likelihood"), world_size=world_size, collective=engine_kw.get("collective"),
-                per_row=engine_kw.get("mlp") is not None or engine_kw.get("rowp") is not None, minibatch=True)
+                per_row=engine_kw.get("mlp") is not None or engine_kw.get("rowp") is not None, minibatch=True,
+                kernel=engine_kw.get("kernel"))
         self.device = torch.device(device)
         self.lib = L.load()
         self.X = X.to(self.device, torch.float64).contiguous()

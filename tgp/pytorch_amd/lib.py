@@ -35,8 +35,10 @@ E_WORKSPACE = -101
 _dp = C.c_void_p
 
 
-KERNEL_SCALE_RBF, KERNEL_SCALE_MATERN32 = 0, 1
-KERNELS = {"scale_rbf": KERNEL_SCALE_RBF, "scale_matern32": KERNEL_SCALE_MATERN32}
+KERNEL_SCALE_RBF, KERNEL_SCALE_MATERN32, KERNEL_SCALE_RQ, KERNEL_SCALE_MATERN52 = 0, 1, 3, 5      # (2 and 4: not assigned, refused)
+KERNELS = {"scale_rbf": KERNEL_SCALE_RBF, "scale_matern32": KERNEL_SCALE_MATERN32, "scale_matern52": KERNEL_SCALE_MATERN52,
+           "scale_rq": KERNEL_SCALE_RQ}
+RQ_MIN_ALPHA, RQ_MAX_ALPHA = 1e-2, 1e4   # the supported alpha of 'scale_rq' (include/tgp_hip.h); its raw_os is {raw_outputscale, alpha}
 # tgp_model.plan (include/tgp_hip.h TGP_PLAN_*): kernel-selection overrides of ONE call; 0 = the library's choice
 PLAN_ROWS_AUTO, PLAN_ROWS_K16, PLAN_ROWS_K, PLAN_ROWS4_NW4, PLAN_ROWS4_NW8 = 0, 1, 2, 3, 4
 PLAN_NO_CHUNK_OVERLAP = 16

@@ -55,12 +55,15 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .lib import STUDENT_MAX_DF
+from .lib import RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
 from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
                           NegativeBinomial, Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import GREEDY_VARIANCE, KMEANS
+
+# --kernel -> the instance_kernel name
+KERNEL_CHOICES = {"rbf": "scale_rbf", "matern32": "scale_matern32", "matern52": "scale_matern52", "rq": "scale_rq"}
 
 # code/exp_config.py:4-86
 HYPER = {
@@ -108,6 +111,11 @@ def main(argv=None):
                          "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
+    ap.add_argument("--kernel", choices=list(KERNEL_CHOICES), default="rbf",
+                    help="covariance function, ARD under an output scale: rbf (the reference's main.py); matern32, matern52: "
+                         "Matern with nu = 3/2, 5/2; rq: rational quadratic with the fixed --rq_alpha (eager loop)")
+    ap.add_argument("--rq_alpha", type=float, default=2.0,
+                    help="alpha of --kernel rq, fixed (not trained), 1e-2 <= alpha <= 1e4")
     ap.add_argument("--dispersion_init", type=float, default=1.0,
                     help="the dispersion r of --likelihood negbinomial at the start (trained; supported range 1e-3 <= r <= 1e3)")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
@@ -150,6 +158,8 @@ def main(argv=None):
         ap.error("--likelihood studentt: SVGP or TGP only")
     if stud and not (2.0 < args.df <= STUDENT_MAX_DF):
         ap.error("--df: the Student-t degrees of freedom must be in (2, 1e4], got %g" % args.df)
+    if args.kernel == "rq" and not (RQ_MIN_ALPHA <= args.rq_alpha <= RQ_MAX_ALPHA):
+        ap.error("--rq_alpha: the rational-quadratic alpha must be in [1e-2, 1e4], got %g" % args.rq_alpha)
     het = args.likelihood == "hetero"
     if het and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood hetero: SVGP or TGP only (no ID_TGP, no WGP)")
@@ -262,8 +272,11 @@ def main(argv=None):
         lik = GaussianLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False)
     else:
         lik = GaussianNonLinearMean(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points)
-    K = instance_kernel("scale_rbf", ard_num_dim=Dx, num_multioutput=Dy, kernel_is_shared=False,
-                        init_params={"length_scale": 2.0, "kernel_scale": 2.0, "noisy_variance": 1e-6})
+    kernel_init = {"length_scale": 2.0, "kernel_scale": 2.0, "noisy_variance": 1e-6}
+    if args.kernel == "rq":
+        kernel_init["alpha"] = args.rq_alpha
+    K = instance_kernel(KERNEL_CHOICES[args.kernel], ard_num_dim=Dx, num_multioutput=Dy, kernel_is_shared=False,
+                        init_params=kernel_init)
     if args.init_Z == "greedy":
         init_Z, sel = GREEDY_VARIANCE(dc["X_tr"], args.num_inducing, K, return_info=True)
         print("init_Z greedy: trace[M]/trace[0] = %.6e" % float(sel["trace"][-1] / sel["trace"][0]))

@@ -200,9 +200,9 @@ class sparse_MF_SP(nn.Module):
         k = self.covariance_function
         if c is not None:            # latent GP c of a multi-class model: slice c of the batched parameters, no noise
             D = self.inp_dim
-            return (self.Z[c], k.base_kernel.raw_lengthscale.reshape(-1, D)[c], k.raw_outputscale.reshape(-1)[c:c + 1],
+            return (self.Z[c], k.base_kernel.raw_lengthscale.reshape(-1, D)[c], k.packed_outputscale(c),
                     self.q_U.variational_mean[c], self.q_U.chol_variational_covar[c], None)
-        return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.raw_outputscale.reshape(-1),
+        return (self.Z[0], k.base_kernel.raw_lengthscale.reshape(-1), k.packed_outputscale(),
                 self.q_U.variational_mean[0], self.q_U.chol_variational_covar[0], self._noise)
 
     def _qf_one(self, X2, c=None):

@@ -57,7 +57,8 @@ _ws_cache = {}
 
 
 def kernel_id(kernel):
-    """'scale_rbf' / 'scale_matern32' (instance_kernel names, models/utils_models.py:188-204) or a TGP_KERNEL_* id."""
+    """A name of lib.KERNELS ('scale_rbf', 'scale_matern32': instance_kernel names, models/utils_models.py:188-204;
+    'scale_matern52', 'scale_rq') or a TGP_KERNEL_* id."""
     if isinstance(kernel, str):
         if kernel not in L.KERNELS:
             raise L.TgpError("kernel '%s' has no HIP implementation (have: %s)" % (kernel, ", ".join(L.KERNELS)))
@@ -131,6 +132,7 @@ def _model_struct(X, Z, raw_ls, raw_os, m, Lam, lvn, scale, jitter, kl_scale, fl
     """`lik` None: LIK_GAUSS without a flow, LIK_FLOW with one; LIK_BERNOULLI needs a FlowSpec (empty for SVGP)."""
     md = L.TgpModel()
     md.kernel = kernel_id(kernel)
+    _os(raw_os, md.kernel)       # (two doubles behind the pointer for 'scale_rq')
     md.plan = int(plan)          # lib.PLAN_*: which of the equivalent kernels this call runs; 0 = the library's choice
     md.N, md.D = X.shape[0], X.shape[1]
     md.M = m.numel()
@@ -159,6 +161,41 @@ def student_noise(lvn, df):
         check_student_df(df)
         df = torch.tensor([float(df)], dtype=torch.float64, device=lvn.device)
     return torch.cat((lvn.detach().reshape(-1)[:1].to(torch.float64), df.detach().reshape(-1)[:1].to(lvn.device, torch.float64)))
+
+
+def rq_scale(raw_os, alpha):
+    """The two doubles {raw_outputscale, alpha} a TGP_KERNEL_SCALE_RQ call's raw_os points to, as one float64 tensor on raw_os's
+    device: `raw_os` the one-element raw output scale (autograd flows through to it), `alpha` a number or a one-element tensor.
+    ValueError outside lib.RQ_MIN_ALPHA <= alpha <= lib.RQ_MAX_ALPHA when `alpha` is a number (a tensor is not read back)."""
+    if alpha is None:
+        raise L.TgpError("the rational-quadratic kernel needs its alpha")
+    if not torch.is_tensor(alpha):
+        alpha = torch.tensor([check_rq_alpha(alpha)], dtype=torch.float64, device=raw_os.device)
+    return torch.cat((raw_os.reshape(-1)[:1].to(torch.float64), alpha.detach().reshape(-1)[:1].to(raw_os.device, torch.float64)))
+
+
+def check_rq_alpha(alpha):
+    """ValueError unless lib.RQ_MIN_ALPHA <= alpha <= lib.RQ_MAX_ALPHA: above, the kernel is the RBF to O(1/alpha)."""
+    alpha = float(alpha)
+    if not (L.RQ_MIN_ALPHA <= alpha <= L.RQ_MAX_ALPHA):
+        raise ValueError("the rational-quadratic alpha must be in [%g, %g], got %g" % (L.RQ_MIN_ALPHA, L.RQ_MAX_ALPHA, alpha))
+    return alpha
+
+
+def _os(raw_os, kernel):
+    """The contiguous float64 raw_os of a call with `kernel`: one element, or rq_scale's two for 'scale_rq' -- the library reads
+    raw_os[1] for that kernel, so a shorter tensor is refused here."""
+    raw_os = _c(raw_os, "raw_os")
+    want = 2 if kernel_id(kernel) == L.KERNEL_SCALE_RQ else 1
+    if raw_os.numel() != want:
+        raise ValueError("raw_os: %d element%s for this kernel (ops.rq_scale packs {raw_outputscale, alpha} for 'scale_rq'), got %d"
+                         % (want, "s" if want > 1 else "", raw_os.numel()))
+    return raw_os
+
+
+def _os_grad(raw_os):
+    """Where a call writes d/d raw_outputscale: raw_os's shape, the library fills element 0 and alpha's slot stays zero."""
+    return torch.empty_like(raw_os) if raw_os.numel() == 1 else torch.zeros_like(raw_os)
 
 
 def check_student_df(df):
@@ -202,7 +239,7 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
     status = _status(dev)
-    g = {"Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os),
+    g = {"Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": _os_grad(raw_os),
          "m": torch.empty_like(m), "Lam": torch.empty_like(Lam), "lvn": torch.empty_like(lvn)}
     gs = L.TgpGrads()
     gs.Z, gs.raw_ls, gs.raw_os, gs.m, gs.Lam, gs.log_var_noise = (L.ptr(g[k]) for k in ("Z", "raw_ls", "raw_os", "m",
@@ -460,6 +497,7 @@ def qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, mu_bar, v_bar, jitter=0.0, kern
     dev = X.device
     ws = workspace(X.shape[0], X.shape[1], md.M, 1, 0, 0, 0, dev, md.kernel, plan)
     g = {k: torch.empty_like(t) for k, t in zip(("Z", "raw_ls", "raw_os", "m", "Lam"), par)}
+    g["raw_os"] = _os_grad(par[2])
     glvn = torch.empty_like(lvn)
     gs = L.TgpGrads()
     gs.Z, gs.raw_ls, gs.raw_os, gs.m, gs.Lam = (L.ptr(g[k]) for k in ("Z", "raw_ls", "raw_os", "m", "Lam"))
@@ -530,6 +568,7 @@ def unwhiten(Z, raw_ls, raw_os, m, L_q, jitter=0.0, check=True, kernel="scale_rb
     library (tests of its refusal)."""
     lib = L.load()
     Z, raw_ls, raw_os, m, L_q = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"), (L_q, "L_q")))
+    _os(raw_os, kernel)
     M, D = Z.shape
     dev = Z.device
     kid = kernel_id(kernel)
@@ -555,7 +594,7 @@ def unwhiten(Z, raw_ls, raw_os, m, L_q, jitter=0.0, check=True, kernel="scale_rb
 def unwhiten_bwd(Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w, m_w_bar, Lam_w_bar, kernel="scale_rbf", workspace_bytes=None):
     """Adjoint of `unwhiten` (tgp_unwhiten_bwd_f64): dict(m, L_q, Z, raw_ls, raw_os) for the cotangents of (m_w, Lam_w)."""
     lib = L.load()
-    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls, "raw_ls"), _os(raw_os, kernel)
     Lo, Li, m_w, Lam_w = _c(Lo, "L"), _c(Li, "Linv"), _c(m_w, "m_w"), _c(Lam_w, "Lam_w")
     m_w_bar, Lam_w_bar = _c(m_w_bar.reshape(-1), "m_w_bar"), _c(Lam_w_bar, "Lam_w_bar")
     M, D = Z.shape
@@ -564,7 +603,7 @@ def unwhiten_bwd(Z, raw_ls, raw_os, Lo, Li, m_w, Lam_w, m_w_bar, Lam_w_bar, kern
     dev = Z.device
     ws, nbytes = _scratch(lib.tgp_unwhiten_bwd_workspace_bytes(M, D), dev, workspace_bytes)
     g = {"m": torch.empty(M, dtype=torch.float64, device=dev), "L_q": torch.empty(M, M, dtype=torch.float64, device=dev),
-         "Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": torch.empty_like(raw_os)}
+         "Z": torch.empty_like(Z), "raw_ls": torch.empty_like(raw_ls), "raw_os": _os_grad(raw_os)}
     L.check(lib.tgp_unwhiten_bwd_f64(kernel_id(kernel), L.ptr(Z), L.ptr(raw_ls), L.ptr(raw_os), M, D, L.ptr(Lo), L.ptr(Li),
                                      L.ptr(m_w), L.ptr(Lam_w), L.ptr(m_w_bar), L.ptr(Lam_w_bar), L.ptr(g["m"]), L.ptr(g["L_q"]),
                                      L.ptr(g["Z"]), L.ptr(g["raw_ls"]), L.ptr(g["raw_os"]), L.ptr(ws), nbytes, L.stream_ptr()),
@@ -627,7 +666,7 @@ def kxxk(X, Z, raw_ls, raw_os, Y=None, kernel="scale_rbf", workspace_bytes=None)
     """(C, b) = (K_ZX K_XZ (M, M), K_ZX y (M) or None) in one pass over the rows of X, K_ZX generated on chip (tgp_kxxk_f64).
     C is exactly symmetric; fixed summation order: two calls give the same bits."""
     lib = L.load()
-    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _os(raw_os, kernel)
     Y = _c(None if Y is None else Y.reshape(-1), "Y")
     N, D = X.shape
     M = Z.shape[0]
@@ -680,7 +719,7 @@ def kxwxk(X, Z, raw_ls, raw_os, w, r=None, kernel="scale_rbf", workspace_bytes=N
     (tgp_kxwxk_f64).  w (N) may have any sign.  C is exactly symmetric; fixed summation order: two calls give the same bits, and
     w = 1 gives kxxk's."""
     lib = L.load()
-    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls, "raw_ls"), _os(raw_os, kernel)
     w = _c(w.reshape(-1), "w")
     r = _c(None if r is None else r.reshape(-1), "r")
     N, D = X.shape
@@ -773,8 +812,8 @@ def greedy_inducing(X, M, raw_ls, raw_os, kernel="scale_rbf", min_var=1e-8, work
     d_n <- max(d_n - c_n^2, 0), trace[j+1] = sum of d over the rows not picked; trace[0] = N s2.  M + 1 launches and one host
     read, at the end.  Fixed reduction orders: two calls give the same bits."""
     lib = L.load()
-    X, raw_ls, raw_os = _c(X, "X"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
-    if X.dim() != 2 or raw_ls.numel() != X.shape[1] or raw_os.numel() != 1:
+    X, raw_ls, raw_os = _c(X, "X"), _c(raw_ls.reshape(-1), "raw_ls"), _os(raw_os.reshape(-1), kernel)
+    if X.dim() != 2 or raw_ls.numel() != X.shape[1]:
         raise ValueError("greedy_inducing: X (N, D), raw_ls (D), raw_os (1)")
     N, D = X.shape
     M = int(M)
@@ -802,14 +841,14 @@ def pathwise_coeff(Z, raw_ls, raw_os, m, Lam, omega, W, eps, jitter=0.0, kernel=
     W (S, 2 R2), eps (S, M): standard normals.  The factorisation runs under psd_safe_cholesky's ladder as in qf_cov;
     `info["jitter"]` receives the value it ended with.  Fixed summation orders: two calls give the same bits.  No autograd."""
     lib = L.load()
-    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
+    Z, raw_ls, raw_os = _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _os(raw_os.reshape(-1), kernel)
     m, Lam, omega, W, eps = _c(m.reshape(-1), "m"), _c(Lam, "Lam"), _c(omega, "omega"), _c(W, "W"), _c(eps, "eps")
     M, D = Z.shape
     if omega.dim() != 2 or W.dim() != 2 or eps.dim() != 2:
         raise ValueError("pathwise_coeff: omega (R2, D), W (S, 2 R2), eps (S, M)")
     R2, S = omega.shape[0], W.shape[0]
     if (omega.shape[1] != D or W.shape[1] != 2 * R2 or eps.shape != (S, M) or m.numel() != M or Lam.shape != (M, M)
-            or raw_ls.numel() != D or raw_os.numel() != 1):
+            or raw_ls.numel() != D):
         raise ValueError("pathwise_coeff: Z (M, D), raw_ls (D), raw_os (1), m (M), Lam (M, M), omega (R2, D), W (S, 2 R2), "
                          "eps (S, M)")
     dev = Z.device
@@ -831,12 +870,12 @@ def pathwise_eval(X, Z, raw_ls, raw_os, omega, coef, kernel="scale_rbf", batch_r
     """F0 (S, N): the draws of `coef` (pathwise_coeff) on the rows of X (tgp_pathwise_eval_f64).  A value depends on its row of
     X and on coef only: `batch_rows` evaluates X in pieces of that many rows (bounded operands) and returns the same bits."""
     lib = L.load()
-    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _c(raw_os.reshape(-1), "raw_os")
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _os(raw_os.reshape(-1), kernel)
     omega, coef = _c(omega, "omega"), _c(coef, "coef")
     if X.dim() != 2 or Z.dim() != 2 or omega.dim() != 2 or coef.dim() != 2:
         raise ValueError("pathwise_eval: X (N, D), Z (M, D), omega (R2, D), coef (2 R2 + M, S)")
     (N, D), M, R2, S = X.shape, Z.shape[0], omega.shape[0], coef.shape[1]
-    if Z.shape[1] != D or omega.shape[1] != D or coef.shape[0] != 2 * R2 + M or raw_ls.numel() != D or raw_os.numel() != 1:
+    if Z.shape[1] != D or omega.shape[1] != D or coef.shape[0] != 2 * R2 + M or raw_ls.numel() != D:
         raise ValueError("pathwise_eval: X (N, D), Z (M, D), raw_ls (D), raw_os (1), omega (R2, D), coef (2 R2 + M, S)")
     if batch_rows is not None and int(batch_rows) < 1:
         raise ValueError("pathwise_eval: batch_rows >= 1")
@@ -930,7 +969,7 @@ class MeanFunction(torch.autograd.Function):
 def kernel_matrix(X1, X2, raw_ls, raw_os, kernel="scale_rbf", jitter=0.0):
     """K(X1, X2) (X2 None: K(X1, X1) + jitter I) for 'scale_rbf' / 'scale_matern32' (tgp_kernel_matrix_f64)."""
     lib = L.load()
-    X1, raw_ls, raw_os = _c(X1, "X1"), _c(raw_ls, "raw_ls"), _c(raw_os, "raw_os")
+    X1, raw_ls, raw_os = _c(X1, "X1"), _c(raw_ls, "raw_ls"), _os(raw_os, kernel)
     X2 = _c(X2, "X2")
     N1, D = X1.shape
     N2 = X2.shape[0] if X2 is not None else N1

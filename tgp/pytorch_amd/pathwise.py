@@ -11,12 +11,19 @@ from . import ops
 from .flow import compile_flow, nets_rowp
 
 
-def spectral_frequencies(kernel_name, R2, D, generator=None, device=None):
+# the kernels whose spectral density this module samples: a set of its own, not lib.KERNELS ('scale_matern52' evaluates on the
+# device like the others but its sampler, Student-t frequencies with 5 degrees of freedom, is not here yet)
+SPECTRAL_KERNELS = ("scale_rbf", "scale_matern32", "scale_rq")
+
+
+def spectral_frequencies(kernel_name, R2, D, generator=None, device=None, alpha=None):
     """omega (R2, D) float64: frequencies of the unit-length-scale kernel, drawn on the host from `generator` (a seeded CPU
     torch.Generator; None: torch's global one).  'scale_rbf': N(0, I_D).  'scale_matern32': g sqrt(3 / c) row-wise with
-    g ~ N(0, I_D) and c ~ chi^2(3) -- the multivariate Student-t with 2 nu = 3 degrees of freedom."""
-    if kernel_name not in ops.L.KERNELS:
-        raise ops.L.TgpError("kernel '%s' has no spectral sampler (have: %s)" % (kernel_name, ", ".join(ops.L.KERNELS)))
+    g ~ N(0, I_D) and c ~ chi^2(3) -- the multivariate Student-t with 2 nu = 3 degrees of freedom.  'scale_rq': g sqrt(tau)
+    row-wise with tau ~ Gamma(shape alpha, rate alpha) -- the kernel is the RBF of precision tau averaged over that law; `alpha`
+    is required for it (lib.RQ_MIN_ALPHA .. lib.RQ_MAX_ALPHA) and read by no other kernel."""
+    if kernel_name not in SPECTRAL_KERNELS:
+        raise ops.L.TgpError("kernel '%s' has no spectral sampler (have: %s)" % (kernel_name, ", ".join(SPECTRAL_KERNELS)))
     R2, D = int(R2), int(D)
     if R2 < 1 or D < 1:
         raise ValueError("spectral_frequencies: R2 >= 1, D >= 1")
@@ -24,6 +31,12 @@ def spectral_frequencies(kernel_name, R2, D, generator=None, device=None):
     if kernel_name == "scale_matern32":
         c = torch.randn(R2, 3, dtype=torch.float64, generator=generator).pow(2).sum(1, keepdim=True)
         g = g * torch.sqrt(3.0 / c)
+    elif kernel_name == "scale_rq":
+        if alpha is None:
+            raise ops.L.TgpError("spectral_frequencies: 'scale_rq' needs its alpha")
+        a = ops.check_rq_alpha(alpha)
+        tau = torch._standard_gamma(torch.full((R2, 1), a, dtype=torch.float64), generator=generator) / a
+        g = g * torch.sqrt(tau)
     return g if device is None else g.to(device)
 
 
@@ -97,7 +110,8 @@ def draw_paths(Z, raw_ls, raw_os, m, Lam, kernel, S, num_frequencies=1024, gener
     eps (S, M) come from `generator` on the host, in that order; the coefficients from ops.pathwise_coeff."""
     S, R2 = int(S), int(num_frequencies)
     M, D = Z.shape
-    omega = spectral_frequencies(kernel, R2, D, generator)
+    # (the RQ kernel's alpha sits behind the raw output scale: ops.rq_scale)
+    omega = spectral_frequencies(kernel, R2, D, generator, alpha=float(raw_os.reshape(-1)[1]) if kernel == "scale_rq" else None)
     W = torch.randn(S, 2 * R2, dtype=torch.float64, generator=generator)
     eps = torch.randn(S, M, dtype=torch.float64, generator=generator)
     dev = Z.device

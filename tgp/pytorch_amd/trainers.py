@@ -159,7 +159,7 @@ class Trainer_SP_regression:
         mean_fn = model.mean_function if getattr(model, "_has_mean", False) else None
         lik = getattr(model.likelihood, "engine_name", None)
         cover = dict(is_whiten=getattr(model, "is_whiten", True), mean=None if mean_fn is None else mean_fn.name, likelihood=lik,
-                     minibatch=len(ld) != 1)
+                     minibatch=len(ld) != 1, kernel=getattr(getattr(model, "covariance_function", None), "hip_kernel", None))
         if engine_refusal(**cover) is not None:        # (before the flow is compiled: whether it is input-dependent comes below)
             return None
         if not hasattr(model, "_gp_params") or any(g["lr"] != lr_ALL for g in groups):
@@ -236,8 +236,10 @@ class Trainer_SP_regression:
         data.DeviceLoader, every parameter but q(u) trained at one learning rate.  None otherwise: the eager loop
         (models.collapsed_bound + the torch optimiser) then serves the run."""
         from .data import DeviceLoader
-        from .engine import ElboEngine, collapsed_refusal
+        from .engine import ElboEngine, collapsed_refusal, engine_refusal
         ld, model = self.train_loader, self.model
+        if engine_refusal(kernel=model.covariance_function.hip_kernel) is not None:
+            return None
         if not isinstance(ld, DeviceLoader) or not ld.X.is_cuda or ld.Y.shape[1] != 1 or len(ld) != 1:
             return None
         mean_fn = model.mean_function if model._has_mean else None
