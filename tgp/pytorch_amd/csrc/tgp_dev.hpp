@@ -1086,11 +1086,24 @@ __device__ __forceinline__ double flow_red(double x) {
 // PN (see flow_forward_store): the per-row partials of a SAL block are PER NODE -- each node of a lane belongs to another data
 // row -- and go to the block's own, now dead, stack slots (slot + 0: d/da, slot + 1: d/db of node u) through `gst`, the
 // writable alias of `stack`; the caller gathers them per row afterwards.  accr is unused then.
+// PN makes ONE trip with every pair of the wave in flight, so a lane forms each SHARED parameter's partial exactly once per
+// launch: nothing is accumulated and nothing crosses lanes inside the sweep.  Partial i of a block (of a STEPTANH block's step
+// k: i = 0 .. 3) is stored, lane-private, in node i of the block's first stack slot (of slot 1 + k), which the step has just read
+// and which is dead from then on (flow_park; NB >= 4); lane i < NP notes that place -- slot * NB + node -- for parameter
+// poff + i in the wave's table `ploc`, so that the caller can sum the 64 lanes of every parameter once, after the sweep
+// (k_rows).  accq, qstride and qlead are unused.
+template <int NB, int NP>
+__device__ __forceinline__ void flow_park(double* gst, int sstride, int* ploc, int slot, int poff, const double (&pv)[NP]) {
+  static_assert(NP <= NB, "a slot holds NB nodes per lane");
+  TGP_EACH(i, NP) gst[(slot * NB + i) * sstride] = pv[i];
+  const int ln = threadIdx.x & 63;
+  if (ln < NP) ploc[poff + ln] = slot * NB + ln;
+}
 template <int NB, int RED = 0, bool PN = false, bool X = false>
 __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], const double* __restrict__ rp,
                                            const double* stack, int sstride, int nslots, double* accq, int qstride,
                                            bool qlead, double* accr, int rstride, const double* const* rpn = nullptr,
-                                           double* gst = nullptr) {
+                                           double* gst = nullptr, int* ploc = nullptr) {
   // (accq / accr live in LDS: lds_acc.  Every block reads all its LDS operands -- parameters AND stack slots -- before
   //  the first use: one exposed LDS round trip per block step instead of three or four.)
   int sl = nslots;
@@ -1118,7 +1131,10 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
           p3 -= cg * xv[u];
           c[u] *= gq[u] + ad;
         }
-        if constexpr (RED == 2) {
+        if constexpr (PN) {
+          const double pv[4] = {p0, p1 * g1, p2, p3 * g3};
+          flow_park<NB>(gst, sstride, ploc, sl, poff, pv);
+        } else if constexpr (RED == 2) {
           const int ln = threadIdx.x & 63;
           const double vv = wave_sum4(p0, p1 * g1, p2, p3 * g3, ln);
           if ((ln & 15) == 0) lds_acc(accq + (poff + (ln >> 4)) * qstride, vv);
@@ -1145,8 +1161,13 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
           pl += c[u] * dl[u];
           c[u] *= gp[u];
         }
-        pl = flow_red<RED>(pl);
-        if (qlead) lds_acc(accq + poff * qstride, pl);
+        if constexpr (PN) {
+          const double pv[1] = {pl};
+          flow_park<NB>(gst, sstride, ploc, sl, poff, pv);
+        } else {
+          pl = flow_red<RED>(pl);
+          if (qlead) lds_acc(accq + poff * qstride, pl);
+        }
         continue;
       }
     }
@@ -1171,7 +1192,10 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
         lds_acc(accr + (poff + 0) * rstride, pa);
         lds_acc(accr + (poff + 1) * rstride, pb);
       } else {
-        if constexpr (RED == 2) {
+        if constexpr (PN) {
+          const double pv[2] = {pa, pb};
+          flow_park<NB>(gst, sstride, ploc, sl, poff, pv);
+        } else if constexpr (RED == 2) {
           const int ln = threadIdx.x & 63;
           const double vv = wave_sum2(pa, pb, ln);
           if ((ln & 31) == 0) lds_acc(accq + (poff + (ln >> 5)) * qstride, vv);
@@ -1216,7 +1240,10 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
         lds_acc(accr + (poff + 0) * rstride, pa);
         lds_acc(accr + (poff + 1) * rstride, pb);
       } else {
-        if constexpr (RED == 2) {
+        if constexpr (PN) {
+          const double pv[2] = {pa, pb};
+          flow_park<NB>(gst, sstride, ploc, sl, poff, pv);
+        } else if constexpr (RED == 2) {
           const int ln = threadIdx.x & 63;
           const double vv = wave_sum2(pa, pb, ln);
           if ((ln & 31) == 0) lds_acc(accq + (poff + (ln >> 5)) * qstride, vv);
@@ -1251,7 +1278,10 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
           p3 -= dz[u];
           gp[u] += se[u];
         }
-        if constexpr (RED == 2) {
+        if constexpr (PN) {
+          const double pv[4] = {p0, p1 * g1, p2, p3 * g3};
+          flow_park<NB>(gst, sstride, ploc, sl + 1 + k, o, pv);
+        } else if constexpr (RED == 2) {
           const int ln = threadIdx.x & 63;
           const double vv = wave_sum4(p0, p1 * g1, p2, p3 * g3, ln);
           if ((ln & 15) == 0) lds_acc(accq + (o + (ln >> 4)) * qstride, vv);

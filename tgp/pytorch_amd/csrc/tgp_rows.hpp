@@ -52,7 +52,7 @@ struct RowArgs {
 
 // LDS carve-up (offsets in doubles)
 struct RowLds {
-  size_t zs, ils, mv, tile, xt, vbs, mbs, tp, tg, ti, xs, wn, stack, acc, red, prog, rin, cbuf, rpl, total;
+  size_t zs, ils, mv, tile, xt, vbs, mbs, tp, tg, ti, xs, wn, stack, acc, ploc, red, prog, rin, cbuf, rpl, total;
 };
 #define TGP_RW_SMALL 10          /* data rows per wave of the k_rows<.., RW = 10> variant (see the kernel) */
 #define TGP_RW_NODES 5           /* its quadrature nodes in flight per lane: 10 rows x 32 nodes = 64 lanes x 5 */
@@ -85,16 +85,19 @@ __host__ __device__ inline RowLds row_lds(const Plan& p, int mode, int nslots, i
     const size_t st = (size_t)(nslots > 0 ? nslots : 1) * (mode == 1 ? (rw < 16 ? TGP_RW_NODES : TGP_NODES_IN_FLIGHT) : 1) * 256;
     if (L.tile + st > o) take(L.tile + st - o);
     L.stack = L.tile;
-    L.acc = take((size_t)(p.P > 0 ? p.P : 1) * 64 + (size_t)p.RP * 256);  // [P][64] quad-reduced + [RP][256] per lane
-    L.rin = L.cbuf = L.rpl = o;
+    // [P][64] quad-reduced + [RP][256] per lane; rw < 16: [P][4], every wave's own sum of each shared parameter (the reverse sweep
+    // accumulates nothing there: flow_backward_store, PN), + the [RP][256] part as it is
+    L.acc = take((size_t)(p.P > 0 ? p.P : 1) * (rw < 16 ? 4 : 64) + (size_t)p.RP * 256);
+    L.ploc = L.rin = L.cbuf = L.rpl = o;
     if (rw < 16) {   // the quadrature's (row, node) pairs are dealt over all 64 lanes: per-wave row inputs and pair results
+      L.ploc = take((size_t)2 * (p.P > 0 ? p.P : 1));   // [4 waves][P] int32: where the reverse sweep leaves parameter j's partials (slot * NB + node)
       L.rin = take(4 * 48);
       L.cbuf = take((size_t)4 * 64 * TGP_RW_NODES);
       L.rpl = take((size_t)4 * 16 * 2 * p.RP);   // per wave and row: (transformed value, d value / d raw) of every per-row column
     }
   } else {
     L.tile = take((size_t)p.MP * 32);  // only the two operand panels (2 x MP x 16)
-    L.xt = L.vbs = L.mbs = L.stack = L.acc = L.rin = L.cbuf = L.rpl = o;
+    L.xt = L.vbs = L.mbs = L.stack = L.acc = L.ploc = L.rin = L.cbuf = L.rpl = o;
   }
   L.total = o;
   return L;
@@ -153,6 +156,40 @@ __device__ __forceinline__ d4 subst_chain(const double* a0, int nsum, int dstep0
     __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
   }
   return out;
+}
+
+// x[l] + x[l ^ 1] (CTRL = 0xB1, quad_perm [1,0,3,2]) or x[l] + x[l ^ 2] (0x4E, quad_perm [2,3,0,1]) on DPP
+template <int CTRL>
+__device__ __forceinline__ double quad_perm_sum(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  const int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+  const int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+  return x + __hiloint2double(h2, l2);
+}
+// k_rows<.., RW < 16>: this wave's sum, over its 64 lanes, of every shared flow parameter's partials.  The reverse sweep left
+// them lane-private in the flow stack (flow_park; ploc[j] = slot * NB + node of parameter j, -1 where no block owns j), so this
+// is a transposed LDS read: sixteen parameters per round, four lanes each -- lane l takes parameter j0 + (l >> 2) and of its
+// 64 values the strip of lanes 16 s .., s = l & 3.  Every parameter's values start at a multiple of 256 doubles, i.e. in one
+// bank, so in step i the lane reads element (i + (l >> 2) + 8 (s >> 1)) mod 16 of its strip: the 32 lanes of a half wave
+// (8 parameters x 4 strips) then hit bank 16 (s & 1) + that element, 32 different ones.  The order of the adds is fixed -- a
+// balanced tree over the 16 steps, then the four lanes of the parameter by two DPP adds -- so the result is the same bits run
+// to run; lane s = 0 stores it to accw[4 j] (accw = the wave's column of acc[P][4]).  `stackw` = the stack at the wave's lane 0.
+__device__ __forceinline__ void flow_param_wave_sums(const double* stackw, const int32_t* ploc, int P, int lane, double* accw) {
+  const int jj = lane >> 2, s = lane & 3, sk = jj + 8 * (s >> 1);
+  int off[16];
+  TGP_EACH(i, 16) off[i] = 16 * s + ((i + sk) & 15);
+  for (int j0 = 0; j0 < P; j0 += 16) {
+    const int j = j0 + jj;
+    const int loc = ploc[j < P ? j : P - 1];
+    const double* src = stackw + (size_t)(loc < 0 ? 0 : loc) * 256;
+    double v[16];
+    TGP_EACH(i, 16) v[i] = src[off[i]];
+    TGP_EACH(i, 8) v[i] += v[i + 8];
+    TGP_EACH(i, 4) v[i] += v[i + 4];
+    TGP_EACH(i, 2) v[i] += v[i + 2];
+    const double t = quad_perm_sum<0x4E>(quad_perm_sum<0xB1>(v[0] + v[1]));
+    if (s == 0 && j < P) accw[4 * j] = loc < 0 ? 0.0 : t;
+  }
 }
 
 #ifdef TGP_STAMPS
@@ -428,8 +465,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
   }
   if (TRAIN) {
-    const int nacc = P * 64 + RP * 256;
-    for (int i = tid; i < nacc; i += 256) acc[i] = 0.0;
+    if constexpr (RW < 16) {
+      // nothing is accumulated in `acc` at RW < 16 (see the likelihood): no zero-fill; only the waves' tables of the places
+      // of the parameters' partials start as "none"
+      int32_t* pl = reinterpret_cast<int32_t*>(sm + L.ploc);
+      for (int i = tid; i < 4 * P; i += 256) pl[i] = -1;
+    } else {
+      const int nacc = P * 64 + RP * 256;
+      for (int i = tid; i < nacc; i += 256) acc[i] = 0.0;
+    }
   }
   lds_barrier();
 
@@ -558,8 +602,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           rpl[(nl * RP + col) * 2 + 1] = der;
         }
       }
-      double* accq = acc + wave * 16 + nl;
-      double* accr = acc + (size_t)P * 64 + tid;
+      int32_t* ploc = reinterpret_cast<int32_t*>(sm + L.ploc) + wave * P;   // this wave's table of the places of the parameters' partials
       lds_barrier();  // the stack aliases the operand panels: all waves must be done with GEMM 2 (and rin is visible)
       double xn[NB], wq[NB], f[NB], c[NB], yv[NB];
       const double* rpn[NB];   // LDS table of each pair's row (ID_TGP; the launcher admits per-row SAL blocks only)
@@ -582,11 +625,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         etap += wq[u] * (-0.5 + 0.5 * einv * r * r);
         c[u] = a.scale * einv * wq[u] * r;
       }
-      flow_backward_store<NB, 0, true, X>(F, c, nullptr, stack + tid, 256, a.prog.nslots, accq, 64, q == 0, accr, 256, rpn, stack + tid);
+      // (one trip: every lane forms each shared parameter's partial exactly once, so the sweep stores them lane-private in dead
+      //  stack slots instead of reducing and accumulating them step by step -- flow_backward_store, PN)
+      flow_backward_store<NB, 0, true, X>(F, c, nullptr, stack + tid, 256, a.prog.nslots, nullptr, 0, false, acc + (size_t)P * 4 + tid, 256, rpn,
+                                          stack + tid, ploc);
 #pragma unroll
       for (int u = 0; u < NB; ++u) cb[lane + 64 * u] = c[u];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
+      // this wave's sum of every shared parameter, before the back substitution's panels overwrite the low stack slots
+      flow_param_wave_sums(stack + wave * 64, ploc, P, lane, acc + wave);
       if (a.g_rowp != nullptr && RP > 0) {
         // per-row parameter gradients: the pairs of a per-row SAL block left (d/da, d/db) in the block's two first stack
         // slots; row lane (nl, q) adds the nodes q, q + 4, ... of its row, the quad completes the sum (fixed order)
@@ -810,9 +858,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     st_wt(&slab[p.slab_C + C_SVB], red[2] + red[6] + red[10] + red[14]);
     st_wt(&slab[p.slab_C + C_PAD], 0.0);
   }
-  for (int j = wave; j < P; j += 4) {
-    const double s = wave_sum(acc[j * 64 + lane]);
-    if (lane == 0) st_wt(&slab[p.slab_C + C_THETA + j], s);
+  if constexpr (RW < 16) {
+    // the four waves' sums of parameter j (flow_param_wave_sums, behind several barriers by now), added in wave order
+    const bool fl = p.lik == TGP_LIK_FLOW;
+    for (int j = tid; j < P; j += 256)
+      st_wt(&slab[p.slab_C + C_THETA + j], fl ? ((acc[4 * j] + acc[4 * j + 1]) + acc[4 * j + 2]) + acc[4 * j + 3] : 0.0);
+  } else {
+    for (int j = wave; j < P; j += 4) {
+      const double s = wave_sum(acc[j * 64 + lane]);
+      if (lane == 0) st_wt(&slab[p.slab_C + C_THETA + j], s);
+    }
   }
   ROW_STAMP(a.ws, p, 10);
 #ifdef TGP_STAMPS

@@ -2,7 +2,8 @@ import os, sys, torch
 os.environ.setdefault("TGP_ALLOW_STALE_LIB", "1")   # the stamped build carries no source hash (build_stamp.sh)
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import tgp.pytorch_amd.lib as L
-L.LIB_PATH = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tools/probes/stamp/libtgp_hip.so")
+# stamp_run.py [a stamped libtgp_hip.so]; without an argument the one build_stamp.sh leaves beside this file
+L.LIB_PATH = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "stamp", "libtgp_hip.so")
 from tgp.pytorch_amd.engine import ElboEngine
 from tgp.pytorch_amd import synthetic as orc
 names = ["stage", "x+hdr", "Kexp", "gemm1", "gemm2", "mu/v", "flow", "gemm3+4", "phase1(T)", "phase2(G,s)", "tail"]
