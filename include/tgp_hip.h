@@ -164,6 +164,24 @@ extern "C" {
  * the log predictive pmf, formed as a log-sum-exp so that it stays finite where every term underflows; Y_std is ignored.  The
  * predictive is discrete: the quantile, CDF and CRPS entries refuse it (TGP_E_UNSUPPORTED). */
 #define TGP_LIK_NEGBIN 9
+/* Ordered categories through the flow (cumulative probit), y in {0, .., K-1}, 2 <= K <= 64, with K-1 strictly increasing FIXED bin
+ * edges b_1 < .. < b_{K-1} (b_0 = -inf, b_K = +inf) and noise of scale sigma on the latent side: for this likelihood
+ * model->log_var_noise points to K+1 doubles {eta = log sigma^2, K, b_1, .., b_{K-1}}; eta is trained, K and the edges are fixed
+ * hyper-parameters.  The library does not look at them (they live on the device): the host layer checks that the edges are finite
+ * and increasing and that 2 <= K <= 64.  With g = G(f0), u = (b_{y+1} - g) / sigma and l = (b_y - g) / sigma:
+ *   log p(y | g)     = log(Phi(u) - Phi(l))
+ *   d log p / dg     = (phi(l) - phi(u)) / (sigma (Phi(u) - Phi(l)))
+ *   d log p / d eta  = (l phi(l) - u phi(u)) / (2 (Phi(u) - Phi(l)))           (the terms of an infinite edge are 0),
+ * formed on the side where both tails are small and through erfcx, so that all three stay finite however far g is from the bin.
+ * The class is y clamped into [0, K-1]; a y that is not >= 0 (NaN included) counts as 0: no target makes a kernel read past the
+ * K-1 edges.  Gauss-Hermite over q(f0) (S, xs, wn required); v <= 0 counts as 0 and its adjoint is 0.  Gradients:
+ * grads->log_var_noise stays ONE double, d/d eta (as out[1] of tgp_ell_flow_f64); K and the edges have no gradient and nothing
+ * is written for them.  The training step always takes the general-M path.
+ * tgp_predict_f64: m1 = E[y] = sum_s wn_s sum_j (1 - Phi_j(g_s)), m2 = Var[y] = sum_s wn_s sum_j (2j - 1)(1 - Phi_j(g_s)) - m1^2 with
+ * Phi_j(g) = Phi((b_j - g) / sigma), j = 1 .. K-1; logp = log sum_s wn_s p(y | g_s), the log predictive pmf, formed as a
+ * log-sum-exp.  The empty program is closed: P(y <= k) = Phi((b_{k+1} - mu) / sqrt(sigma^2 + max(v, 0))).  Y_std is ignored (classes
+ * have no units).  The predictive is discrete: the quantile, CDF and CRPS entries refuse it (TGP_E_UNSUPPORTED). */
+#define TGP_LIK_ORDINAL 10
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  With d2 = |(x - z)/l|^2, l = softplus(raw_ls), s2 = softplus(raw_os[0]) and r = sqrt(max(d2, 1e-30)) as gpytorch's
@@ -274,8 +292,8 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
 
-/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT or TGP_LIK_NEGBIN training
- * step runs on the general-M path at every M. */
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN or
+ * TGP_LIK_ORDINAL training step runs on the general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -628,7 +646,9 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
  * model->lik == TGP_LIK_BERNOULLI: Bernoulli.expected_log_prob (likelihoods/Bernoulli.py) instead, out[1] = 0.
  * model->lik == TGP_LIK_POISSON: the Poisson expected log-likelihood of its #define, out[1] = 0.
  * model->lik == TGP_LIK_STUDENT: the Student-t one of its #define (log_var_noise = {log sigma^2, nu}), out[1] = dELL/dlog sigma^2.
- * model->lik == TGP_LIK_NEGBIN: the negative-binomial one of its #define (log_var_noise = log r), out[1] = dELL/dlog r. */
+ * model->lik == TGP_LIK_NEGBIN: the negative-binomial one of its #define (log_var_noise = log r), out[1] = dELL/dlog r.
+ * model->lik == TGP_LIK_ORDINAL: the cumulative-probit one of its #define (log_var_noise = {log sigma^2, K, b_1, .., b_{K-1}}),
+ * out[1] = dELL/dlog sigma^2. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -720,7 +740,7 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN: see their #defines; Y_std is
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN, TGP_LIK_ORDINAL: see their #defines; Y_std is
  * ignored.
  * TGP_LIK_STUDENT: see its #define (Y_std is used, the constant is included).
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
@@ -757,7 +777,7 @@ int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */,
  * both tails are resolved to relative accuracy.  status (device int32[1], zeroed by the caller): the call ADDS the number of
  * roots that ran out of evaluations; their t is NaN.
  * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX,
- * TGP_LIK_POISSON, TGP_LIK_STUDENT and TGP_LIK_NEGBIN are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
+ * TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN and TGP_LIK_ORDINAL are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
  * over s: same input, same bits. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32

@@ -1,7 +1,8 @@
 // tgp_ell.hpp -- the quadrature likelihood through the flow as templates over a likelihood policy: the training policies and
 // k_ell_quad, the predictive policies and k_predict_quad, each with its launch helper.  tgp_lik.hip instantiates them for the
 // Gaussian, Bernoulli, Poisson, Student-t and heteroscedastic policies and holds the table of likelihoods (lik_row),
-// tgp_lik_negbin.hip instantiates them for the negative-binomial policy (a unit of its own for the compile time).
+// tgp_lik_negbin.hip instantiates them for the negative-binomial policy and tgp_lik_ordinal.hip for the ordinal policies
+// (EllOrdinal, PredOrdinal), each in a unit of its own for the compile time.
 #pragma once
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
@@ -16,6 +17,9 @@ namespace tgp {
 //   Student-t (no counterpart in the reference), location G(f0), scale sigma, nu degrees of freedom (TGP_LIK_STUDENT)
 //   negative binomial (no counterpart in the reference), log link, dispersion r: mean exp(g), variance mean + mean^2 / r (TGP_LIK_NEGBIN)
 //   heteroscedastic Gaussian (no counterpart in the reference), log noise variance c + h, h a second latent GP (TGP_LIK_HETERO)
+//   ordinal (no counterpart in the reference), cumulative probit over K ordered classes with fixed bin edges b_1 < .. < b_{K-1}:
+//     log p(y | g) = log(Phi((b_{y+1} - g) / sigma) - Phi((b_y - g) / sigma)); the flow learns the spacing of the levels
+//     (TGP_LIK_ORDINAL, tgp_lik_ordinal.hip)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and PredBern.  With a = |g|, t = a / sqrt 2:

@@ -190,6 +190,8 @@ int launch_flow_eval(const tgp_model& md, const FlowProg& fp, const double* f, i
                      double* logdG, hipStream_t st, double* sum_out = nullptr, double* ws = nullptr);
 EllLaunch ell_launch_negbin;           // tgp_lik_negbin.hip: what the TGP_LIK_NEGBIN row points to
 PredictLaunch predict_launch_negbin;
+EllLaunch ell_launch_ordinal;          // tgp_lik_ordinal.hip: what the TGP_LIK_ORDINAL row points to
+PredictLaunch predict_launch_ordinal;
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,

@@ -266,6 +266,7 @@ static const LikRow lik_table[] = {
     // (tgp_ell_hetero_f64 only; every single-output entry refuses it before it asks)
     LIK_ROW(HETERO,    false, false, ell_launch_row<EllHetero>,  nullptr,                            nullptr),
     LIK_ROW(NEGBIN,    true,  true,  ell_launch_negbin,          predict_launch_negbin,              "TGP_LIK_NEGBIN" NOQ_DISCRETE),
+    LIK_ROW(ORDINAL,   true,  true,  ell_launch_ordinal,         predict_launch_ordinal,             "TGP_LIK_ORDINAL" NOQ_DISCRETE),
 };
 const LikRow* lik_row(int lik) {
   for (const LikRow& r : lik_table)

@@ -23,9 +23,12 @@ LIK_STUDENT = 7             # Student-t noise around the flow (TGP_LIK_STUDENT):
 LIK_HETERO = 8              # heteroscedastic Gaussian, a second latent GP for the log-noise (TGP_LIK_HETERO): tgp_ell_hetero_f64 only
 LIK_NEGBIN = 9              # negative-binomial counts, the flow as the log-mean (TGP_LIK_NEGBIN): log_var_noise = log r
 # what a message calls the likelihoods that go through a FlowSpec on the eager path only (the step engines have none of them)
-LIK_DISPLAY = {LIK_BERNOULLI: "Bernoulli", LIK_POISSON: "Poisson", LIK_STUDENT: "Student-t", LIK_NEGBIN: "negative-binomial"}
+LIK_ORDINAL = 10            # ordered classes, cumulative probit around the flow (TGP_LIK_ORDINAL): log_var_noise = {log sigma^2, K, edges}
+LIK_DISPLAY = {LIK_BERNOULLI: "Bernoulli", LIK_POISSON: "Poisson", LIK_STUDENT: "Student-t", LIK_NEGBIN: "negative-binomial",
+               LIK_ORDINAL: "ordinal"}
 NEEDS_FLOWSPEC = "the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
 STUDENT_MAX_DF = 1e4       # the supported degrees of freedom are 2 < nu <= STUDENT_MAX_DF (include/tgp_hip.h)
+ORDINAL_MAX_K = 64         # the supported number of classes is 2 <= K <= ORDINAL_MAX_K (include/tgp_hip.h)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
 PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64

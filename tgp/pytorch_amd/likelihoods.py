@@ -358,6 +358,86 @@ class NegativeBinomial(Poisson):
                                            self.quad_points)
 
 
+class Ordinal(Likelihood):
+    """p(y = k | G(f)) = Phi((b_{k+1} - G(f)) / sigma) - Phi((b_k - G(f)) / sigma) for ORDERED categories y in {0, .., K-1}
+    (ratings, grades, severity levels): the cumulative-probit likelihood with K - 1 fixed bin edges b_1 < .. < b_{K-1}, b_0 = -inf,
+    b_K = +inf.  `bin_edges` is a buffer, not a parameter (no optimiser moves it); the default is b_j = j - K / 2, unit spacing,
+    centred.  With the edges fixed the monotone flow G of a TGP learns the spacing of the levels, which is ordinal regression
+    with learned cut-points; SVGP keeps the spacing the edges give.  One parameter, `log_var_noise` = log sigma^2 (the Gaussian
+    classes' name, shape (1, 1)); `noise_init` is sigma^2.  2 <= num_classes <= 64.  The quadrature over q(f0) runs in float64 on
+    the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with TGP_LIK_ORDINAL).  kind = "count": predictive_pmf(X, K - 1) is
+    the class probabilities, predictive_crps(kmax=K - 1) the ranked probability score.  The reference has no such class."""
+
+    display = "ordinal"
+    lik_id = ops.L.LIK_ORDINAL
+    engine_name = "ordinal"
+    kind = "count"
+    has_noise = True
+    one_launch_logp = True
+    outputs_refusal = "the ordinal likelihood is built for one output (num_outputs = 1)"
+    refuses_input_dependent = NO_INPUT_DEPENDENT % display
+    refuses_optimal_qu = NOT_GAUSSIAN_IN_F % display
+    refuses_cdf = ("%s: the predictive of an ordinal model is discrete; predictive_pmf(X, num_classes - 1) gives its class "
+                   "probabilities (cumsum: the CDF, from which the median class is read) and posterior_quantiles the quantiles "
+                   "of G(f)")
+
+    def __init__(self, num_classes, bin_edges=None, noise_init=1.0, quadrature_points=None):
+        super().__init__()
+        K = int(num_classes)
+        if K != num_classes or not 2 <= K <= ops.L.ORDINAL_MAX_K:
+            raise ValueError("the ordinal likelihood takes 2 <= num_classes <= %d, got %s" % (ops.L.ORDINAL_MAX_K, num_classes))
+        if bin_edges is None:
+            bin_edges = [j - K / 2.0 for j in range(1, K)]
+        edges = ops.check_ordinal_edges(bin_edges).clone().to(cg.dtype)
+        if edges.numel() != K - 1:
+            raise ValueError("the ordinal likelihood of %d classes takes %d bin edges, got %d" % (K, K - 1, edges.numel()))
+        if not float(noise_init) > 0.0:
+            raise ValueError("the noise variance of the ordinal likelihood must be > 0, got %g" % float(noise_init))
+        self.num_classes = K
+        self.quad_points = cg.quad_points if quadrature_points is None else quadrature_points
+        self.register_buffer("bin_edges", edges)
+        self.log_var_noise = nn.Parameter(torch.ones(1, 1, dtype=cg.dtype) *
+                                          inverse_positive_transform(torch.tensor(noise_init, dtype=cg.dtype)))
+
+    def lik_kwargs(self):
+        """The bin edges ride beside the noise: ops.ordinal_noise puts {log sigma^2, K, b_1, .., b_{K-1}} behind the ABI's noise
+        pointer (the `df` key is the slot for what rides there)."""
+        return {"lik": self.lik_id, "df": self.bin_edges}
+
+    def check_targets(self, Y):
+        """ValueError unless every target is a class: an integer in [0, num_classes - 1] (the kernels clamp and do not look)."""
+        Yd = Y.detach()
+        if not bool(((Yd >= 0) & (Yd <= self.num_classes - 1) & (Yd == torch.round(Yd))).all()):     # (a NaN fails all three)
+            raise ValueError("the ordinal likelihood takes classes: every target must be an integer in [0, %d]"
+                             % (self.num_classes - 1))
+
+    def sample_from_output(self, f, i, **kwargs):
+        """The number of bin edges below f + sigma eps."""
+        sd = torch.sqrt(positive_transform(self.log_var_noise.detach().reshape(())))
+        z = f + sd * torch.randn_like(f)
+        return (z.unsqueeze(-1) > self.bin_edges.to(f.device, f.dtype)).sum(-1).to(cg.dtype)
+
+    def _checks(self, gauss_mean, flow, X):
+        assert len(flow) == 1, "Flow list must be size 1 for the ordinal likelihood"
+        assert gauss_mean.size(0) == 1, "Ordinal regression on this path has one output GP"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[log p(y_n | G(f0))], differentiable in the moments, log_var_noise and the flow's parameters (none in
+        bin_edges); Y (1, MB) classes, moments (1, MB)."""
+        self.check_targets(Y)
+        self._checks(gauss_mean, flow, X)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllOrdinalFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                            gauss_cov.reshape(-1).contiguous(), self.noise().contiguous(), self.bin_edges, theta,
+                                            rowp, spec, self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """(m1, m2) = (E[y], Var[y]) of the predictive, in classes, each of gauss_mean's shape (1, MB)."""
+        self._checks(gauss_mean, flow, X)
+        return self._moments(gauss_mean, gauss_cov, flow, X)
+
+
 class StudentT(_GaussianBase):
     """p(y|G(f)) = StudentT(y | df, loc = G(f), scale = sigma) for regression with gross errors in the targets: heavy tails keep
     a few outliers from inflating the noise and with it every predictive interval.  `log_var_noise` (the Gaussian classes' name

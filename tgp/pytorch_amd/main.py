@@ -43,6 +43,15 @@ x0), the correlation of the learned with the true log noise level:
 
     python -m tgp.pytorch_amd.main --model TGP --likelihood hetero --dataset synthetic_hetero \\
         --train_test_seed_split 1 --num_inducing 50 --epochs 2000
+
+`--likelihood ordinal` trains an ordinal regression (SVGP or TGP) on the ordered classes of synthetic_ratings: the
+cumulative-probit likelihood with fixed, evenly spaced bin edges, so that the flow of a TGP (default SAL x 1) learns the spacing
+of the levels.  It reports the test negative log-likelihood, the accuracy of the modal class and the mean absolute error of the
+predictive median class, and the same three for the baseline that predicts the training class frequencies everywhere; with
+--scores also the ranked probability score:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood ordinal --dataset synthetic_ratings \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 2000
 """
 import argparse
 
@@ -57,7 +66,7 @@ from .initializers import find_forward_params, find_forward_params_input_depende
 from .kernels import instance_kernel
 from .lib import RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
 from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
-                          NegativeBinomial, Poisson, StudentT, WarpedGaussianLinearMean)
+                          NegativeBinomial, Ordinal, Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
 from .utils import GREEDY_VARIANCE, KMEANS
@@ -79,10 +88,12 @@ HYPER = {
     ("TGP", "overdispersed"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "ratings"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
 COUNT_DATASETS = ("synthetic_counts", "synthetic_overdispersed")
+ORDINAL_DATASETS = ("synthetic_ratings",)
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -93,7 +104,7 @@ def main(argv=None):
     ap.add_argument("--dataset", required=True,
                     choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero"]
                     + list(CLASSIFICATION_DATASETS)
-                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS))
+                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
@@ -102,13 +113,16 @@ def main(argv=None):
     ap.add_argument("--num_steps", type=int, default=None, help="tanh steps per StepTanhL block (default: the recipe's)")
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
-    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "negbinomial", "studentt", "hetero"],
+    ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "negbinomial", "studentt", "hetero",
+                                             "ordinal"],
                     default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; negbinomial: the same "
                          "for over-dispersed counts, with a trained dispersion r (Var = mean + mean^2 / r); studentt: "
                          "robust regression, Student-t noise of --df degrees of freedom around G(f); hetero: regression with "
-                         "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP)")
+                         "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP); ordinal: "
+                         "ordered classes, cumulative probit with fixed bin edges, the flow learns the spacing of the levels "
+                         "(SVGP or TGP, synthetic_ratings)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
     ap.add_argument("--kernel", choices=list(KERNEL_CHOICES), default="rbf",
@@ -143,6 +157,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
+    ordn = args.likelihood == "ordinal"
+    if ordn and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood ordinal: SVGP or TGP only")
+    if ordn != (args.dataset in ORDINAL_DATASETS):
+        ap.error("--likelihood ordinal goes with the ordinal data sets (%s), and they with it" % ", ".join(ORDINAL_DATASETS))
     pois = args.likelihood == "poisson"
     if pois and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood poisson: SVGP or TGP only")
@@ -260,8 +279,10 @@ def main(argv=None):
         lik = Poisson()
     elif negb:
         lik = NegativeBinomial(dispersion_init=args.dispersion_init)
+    elif ordn:
+        lik = Ordinal(dc["num_classes"], quadrature_points=cg.quad_points)     # the default edges: unit spacing, centred
     elif het:
-        Dy = 2                              # latent GP 0: f (with the flow), latent GP 1: h, the log noise variance (no flow)
+        Dy = 2                           # latent GP 0: f (with the flow), latent GP 1: h, the log noise variance (no flow)
         lik = HeteroscedasticGaussian(noise_init=0.05, quadrature_points=cg.quad_points)
     elif stud:
         lik = StudentT(out_dim=Dy, noise_init=0.05, noise_is_shared=False, quadrature_points=cg.quad_points, df=args.df)
@@ -311,6 +332,33 @@ def main(argv=None):
             args.dataset, args.num_inducing, args.model, -res[4]))
         print("Dataset {}, num inducing points {}, model {}, Test Accuracy {:.3f}".format(
             args.dataset, args.num_inducing, args.model, res[5]))
+        return res
+    if ordn:
+        # the class of the test rows by the predictive pmf: its mode, and its median read from the CDF; beside them the baseline
+        # that predicts the training class frequencies everywhere
+        Kc = lik.num_classes
+        y_te = dc["Y_te"].reshape(-1)
+        model.set_is_training(False)
+        pmf = model.predictive_pmf(dc["X_te"].to(cg.device), Kc - 1).cpu()
+        acc = (pmf.argmax(1).to(y_te.dtype) == y_te).double().mean().item()
+        median = (pmf.cumsum(1) < 0.5).sum(1).clamp(max=Kc - 1).to(y_te.dtype)
+        mae = (median - y_te).abs().mean().item()
+        freq = torch.bincount(dc["Y_tr"].reshape(-1).long(), minlength=Kc).to(y_te.dtype) / dc["Y_tr"].numel()
+        base_nll = -torch.log(freq[y_te.long()]).mean().item()
+        base_acc = (freq.argmax().to(y_te.dtype) == y_te).double().mean().item()
+        base_mae = ((freq.cumsum(0) < 0.5).sum().clamp(max=Kc - 1).to(y_te.dtype) - y_te).abs().mean().item()
+        print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, -res[6]))
+        print("Dataset {}, num inducing points {}, model {}, Test Accuracy (modal class) {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, acc))
+        print("Dataset {}, num inducing points {}, model {}, Test MAE (median class) {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, mae))
+        print("Dataset {}, class frequencies, Test Negative LOGL {:.3f}, Test Accuracy {:.3f}, Test MAE {:.3f}".format(
+            args.dataset, base_nll, base_acc, base_mae))
+        if args.scores:
+            rps = model.predictive_crps(dc["X_te"].to(cg.device), dc["Y_te"].to(cg.device), kmax=Kc - 1).mean().item()
+            print("Dataset {}, num inducing points {}, model {}, Test ranked probability score {:.4f}".format(
+                args.dataset, args.num_inducing, args.model, rps))
         return res
     if pois or negb:
         # the constant-rate baseline: a Poisson at the mean of the training counts, its NLL and RMSE on the test counts

@@ -238,7 +238,8 @@ class sparse_MF_SP(nn.Module):
         the rows of X2: eval mode -> q(f) moments (or `qf`, already there) -> flow inputs -> launch -> train(); no autograd.
         (m1, m2, logp or None, mean_q_f, cov_q_f), the first three as the likelihood shapes them.  A count model takes Y of
         B * N entries: block b of the launch holds the counts Y[b * N:(b + 1) * N] against the same N rows, their moments
-        repeated B times (predictive_pmf); it has no input-dependent flow, so no MC-dropout mixture."""
+        repeated B times (predictive_pmf); it has no input-dependent flow, so no MC-dropout mixture.  The likelihood's
+        lik_kwargs() carry, in their `df` key, what rides beside the noise (ops.noise_slot): degrees of freedom or bin edges."""
         count = self.likelihood.kind == "count"
         if count and self.fully_bayesian:
             raise NotImplementedError("a %s model has no input-dependent flows, so no fully Bayesian (MC-dropout) mode"
@@ -498,7 +499,9 @@ class sparse_MF_SP(nn.Module):
         per-row adjoints -> ops.natgrad_qu at the jitter the moments ended with.  With the Gaussian likelihood and lr = 1 it is
         set_optimal_qu; for the others a damped Newton step on q(u) that needs no learning rate for m and Lam.  `site_floor`
         clamps the per-row precisions from below (0.0 keeps P' positive definite for every likelihood; None: no floor, and a
-        likelihood that is not log-concave may raise ops.NotPSDError -- q_U is left as it was then).  Returns the `info` dict
+        likelihood that is not log-concave may raise ops.NotPSDError -- q_U is left as it was then).  The `df` key of the
+        likelihood's lik_kwargs() is the slot for what rides beside the noise (ops.noise_slot): the Student-t's degrees of
+        freedom, the ordinal likelihood's bin edges.  Returns the `info` dict
         (info["jitter"]).  NotImplementedError, naming the reason, for the models the step is not built for."""
         why = self._natgrad_refusal()
         if why is not None:
@@ -657,12 +660,13 @@ class sparse_MF_SP(nn.Module):
 
     # ---- count models: the predictive pmf -----------------------------------------------------------------
     def predictive_pmf(self, X, kmax: int):
-        """The predictive pmf of a count model at the rows of X (N, Dx): P of shape (N, kmax + 1), P[n, k] = p(y_n = k | x_n),
-        the exponential of tgp_predict_f64's log pmf from one launch over N (kmax + 1) rows (block k asks for the count k).
-        Rows sum to 1 once kmax is past the mass; P.cumsum(1) is the predictive CDF, from which count intervals are read."""
+        """The predictive pmf of a count or ordinal model at the rows of X (N, Dx): P of shape (N, kmax + 1), P[n, k] =
+        p(y_n = k | x_n), the exponential of tgp_predict_f64's log pmf from one launch over N (kmax + 1) rows (block k asks for the
+        count, or class, k).  Rows sum to 1 once kmax is past the mass (an ordinal model of K classes: kmax = K - 1); P.cumsum(1)
+        is the predictive CDF, from which count intervals and the median class are read."""
         if self.likelihood.kind != "count":
-            raise NotImplementedError("predictive_pmf: a count likelihood (Poisson) only; %s models have predictive_quantiles "
-                                      "or class probabilities" % type(self.likelihood).__name__)
+            raise NotImplementedError("predictive_pmf: a count (Poisson, negative-binomial) or ordinal likelihood only; %s models "
+                                      "have predictive_quantiles or class probabilities" % type(self.likelihood).__name__)
         assert X.dim() == 2, "Invalid input X.shape"
         kmax = int(kmax)
         assert kmax >= 0, "kmax must be >= 0"

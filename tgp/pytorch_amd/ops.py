@@ -163,6 +163,51 @@ def student_noise(lvn, df):
     return torch.cat((lvn.detach().reshape(-1)[:1].to(torch.float64), df.detach().reshape(-1)[:1].to(lvn.device, torch.float64)))
 
 
+_EDGES_SEEN = {}      # (data_ptr, version, numel, device) of the last device tensor of bin edges check_ordinal_edges passed
+
+
+def check_ordinal_edges(edges):
+    """The bin edges of the ordinal likelihood as a float64 vector; ValueError unless they are finite, strictly increasing and
+    1 <= len <= lib.ORDINAL_MAX_K - 1.  A device tensor is read back once: the check of an unchanged buffer is remembered."""
+    e = torch.as_tensor(edges, dtype=torch.float64).detach().reshape(-1)
+    key = (e.data_ptr(), e._version, e.numel(), str(e.device))
+    if e.is_cuda and _EDGES_SEEN.get("key") == key:
+        return e
+    if not 1 <= e.numel() <= L.ORDINAL_MAX_K - 1:
+        raise ValueError("the ordinal likelihood takes 1 to %d bin edges (2 to %d classes), got %d"
+                         % (L.ORDINAL_MAX_K - 1, L.ORDINAL_MAX_K, e.numel()))
+    h = e.cpu()
+    if not bool(torch.isfinite(h).all()):
+        raise ValueError("the bin edges of the ordinal likelihood must be finite, got %s" % h.tolist())
+    if not bool((h[1:] > h[:-1]).all()):
+        raise ValueError("the bin edges of the ordinal likelihood must be strictly increasing, got %s" % h.tolist())
+    if e.is_cuda:
+        _EDGES_SEEN["key"] = key
+    return e
+
+
+def ordinal_noise(lvn, edges):
+    """The K + 1 doubles {log sigma^2, K, b_1, .., b_{K-1}} a TGP_LIK_ORDINAL call's log_var_noise points to, as one float64 tensor
+    on lvn's device: `lvn` the one-element log noise variance, `edges` the K - 1 bin edges (a sequence or a tensor; no gradient).
+    ValueError unless the edges are finite, strictly increasing and 1 <= len <= 63 (check_ordinal_edges)."""
+    if edges is None:
+        raise L.TgpError("the ordinal likelihood needs its bin edges")
+    e = check_ordinal_edges(edges).to(lvn.device)
+    K = torch.full((1,), float(e.numel() + 1), dtype=torch.float64, device=lvn.device)     # (a fill: no host-to-device copy)
+    return torch.cat((lvn.detach().reshape(-1)[:1].to(torch.float64), K, e))
+
+
+def noise_slot(lvn, lik, extras):
+    """What sits behind the ABI's noise pointer in a call at likelihood `lik`: `lvn` itself, or, for the likelihoods that carry
+    fixed hyper-parameters beside the noise, lvn[0] followed by them -- `extras` is what rides there: the degrees of freedom of
+    LIK_STUDENT (student_noise), the bin edges of LIK_ORDINAL (ordinal_noise)."""
+    if lik == L.LIK_STUDENT:
+        return student_noise(lvn, extras)
+    if lik == L.LIK_ORDINAL:
+        return ordinal_noise(lvn, extras)
+    return lvn
+
+
 def rq_scale(raw_os, alpha):
     """The two doubles {raw_outputscale, alpha} a TGP_KERNEL_SCALE_RQ call's raw_os points to, as one float64 tensor on raw_os's
     device: `raw_os` the one-element raw output scale (autograd flows through to it), `alpha` a number or a one-element tensor.
@@ -219,7 +264,10 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     `lik` = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom around the flow; lvn (one element) is the log of the
     squared scale and grads["lvn"] its one-element gradient; `df` has none.
     `lik` = lib.LIK_NEGBIN: negative-binomial counts with the flow as the log-mean; lvn (one element) is the log dispersion
-    log r and grads["lvn"] its gradient."""
+    log r and grads["lvn"] its gradient.
+    `lik` = lib.LIK_ORDINAL: ordered classes Y in {0, .., K-1} (cumulative probit around the flow); lvn (one element) is the log
+    noise variance and grads["lvn"] its gradient.  `df` is the slot for what rides beside the noise (noise_slot): here the K - 1
+    fixed bin edges, which have no gradient."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -234,7 +282,9 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     # (LIK_STUDENT: the library reads {log sigma^2, nu} behind the noise pointer and writes one gradient, that of log sigma^2)
     if lik == L.LIK_STUDENT and lvn.numel() != 1:
         raise L.TgpError("the Student-t step takes a one-element log_var_noise (log sigma^2); the degrees of freedom go in `df`")
-    noise = student_noise(lvn, df) if lik == L.LIK_STUDENT else lvn
+    if lik == L.LIK_ORDINAL and lvn.numel() != 1:
+        raise L.TgpError("the ordinal step takes a one-element log_var_noise (log sigma^2); the bin edges go in `df`")
+    noise = noise_slot(lvn, lik, df)
     md, keep = _model_struct(X, Z, raw_ls, raw_os, m, Lam, noise, scale, jitter, kl_scale, flow, theta, S, kernel, plan, lik)
     ws = workspace(N, D, M, md.S, md.nblk, md.P, md.RP, dev, md.kernel, plan, md.lik)
     out = torch.empty(4, dtype=torch.float64, device=dev)
@@ -347,7 +397,7 @@ def _step_kwargs(cfg):
     """The keyword arguments of elbo_step a model's `cfg` dict stands for."""
     kw = dict(flow=cfg.get("flow"), S=cfg.get("S"), kl_scale=cfg.get("kl_scale", 1.0), mb_global=cfg.get("mb_global"),
               kernel=cfg.get("kernel", "scale_rbf"), lik=cfg.get("lik"), jitter=cfg.get("jitter", 0.0))
-    if cfg.get("df") is not None:       # the degrees of freedom of a Student-t model
+    if cfg.get("df") is not None:       # what rides beside the noise: a Student-t model's degrees of freedom, an ordinal one's edges
         kw["df"] = cfg["df"]
     return kw
 
@@ -790,14 +840,15 @@ def natgrad_qu(X, Z, raw_ls, raw_os, m, Lam, mu, mu_bar, v_bar, rho=1.0, site_fl
 
 def _ell_rows(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0, lik=None, df=None):
     """The row-wise ELL launch of a likelihood by its traits, the one its Ell*Function runs (natgrad_step_qu asks by trait, not by
-    class): `flow` None -> ell_gauss, else the quadrature launch at `lik` (None: LIK_FLOW) with `df` beside the noise for the
-    Student-t.  `lvn` None: a likelihood without a noise parameter.  dict(ell, g_mu, g_v, ...)."""
+    class): `flow` None -> ell_gauss, else the quadrature launch at `lik` (None: LIK_FLOW).  `df` is the slot for what rides beside
+    the noise (noise_slot): the Student-t's degrees of freedom, the ordinal likelihood's bin edges.  `lvn` None: a likelihood
+    without a noise parameter.  dict(ell, g_mu, g_v, ...)."""
     if flow is None:
         return dict(zip(("ell", "g_lvn", "g_mu", "g_v"), ell_gauss(Y, mu, v, lvn, scale=scale)))
     if lvn is None:
         return _ell_noiseless(Y, mu, v, flow, theta, S, rowp, scale, lik)
     if df is not None:
-        lvn = student_noise(lvn, df)
+        lvn = noise_slot(lvn, lik, df)
     return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_FLOW if lik is None else lik)
 
 
@@ -1265,6 +1316,14 @@ def ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_NEGBIN)
 
 
+def ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp=None, scale=1.0):
+    """Ordinal (cumulative-probit) quadrature ELL with gradients: scale sum_n E_q(f0)[log(Phi((b_{y_n + 1} - G(f0)) / sigma) -
+    Phi((b_{y_n} - G(f0)) / sigma))], Y the classes 0 .. K-1, lvn = log sigma^2, `edges` the K - 1 fixed bin edges b_1 < .. < b_{K-1}
+    (tgp_ell_flow_f64 with TGP_LIK_ORDINAL).  Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp); g_lvn = dELL/dlvn, the edges
+    have no gradient."""
+    return _ell_quad(Y, mu, v, ordinal_noise(lvn, edges), flow, theta, S, rowp, scale, L.LIK_ORDINAL)
+
+
 def ell_hetero(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     """Heteroscedastic Gaussian ELL with gradients, y ~ N(G(f), exp(lvn + h)): mu, v of shape (2, N), row 0 the moments of q(f),
     row 1 those of the log-noise GP q(h), which integrates out in closed form (tgp_ell_hetero_f64, one launch).  `flow` a
@@ -1397,6 +1456,11 @@ EllNegBinFunction = _EllOf(
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp)),
     """apply(Y, mu, v, lvn, theta, rowp, flow, S): ELL of the negative-binomial likelihood with autograd in (mu, v, the log
     dispersion, theta, rowp).""")
+EllOrdinalFunction = _EllOf(
+    lambda Y, mu, v, lvn, edges, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp)),
+    """apply(Y, mu, v, lvn, edges, theta, rowp, flow, S): ELL of the ordinal likelihood with autograd in (mu, v, log_var_noise,
+    theta, rowp) and none in the bin edges.""")
 EllHeteroFunction = _EllOf(
     lambda Y, mu, v, lvn, theta, rowp, flow, S, scale: (
         Y, mu, v, lvn, theta, rowp,
@@ -1574,12 +1638,15 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     lik = lib.LIK_STUDENT: Student-t noise of `df` degrees of freedom and squared scale exp(lvn): m1, m2 in standardised units
     (m2 includes sigma^2 df / (df - 2)), logp = the exact log predictive density of the raw target, every constant and
     -log Y_std included.
-    lik = lib.LIK_NEGBIN: as LIK_POISSON with the dispersion r = exp(lvn): m2 = m1 + (1 + 1/r) E[mean^2] - m1^2."""
+    lik = lib.LIK_NEGBIN: as LIK_POISSON with the dispersion r = exp(lvn): m2 = m1 + (1 + 1/r) E[mean^2] - m1^2.
+    lik = lib.LIK_ORDINAL: m1 = E[y], m2 = Var[y] in classes, logp = the log predictive pmf of class Y (closed form for an
+    empty `flow`).  `df` is the slot for what rides beside the noise (noise_slot): the Student-t's degrees of freedom, the
+    ordinal likelihood's bin edges."""
     lib = L.load()
-    if lik == L.LIK_STUDENT:
+    if lik in (L.LIK_STUDENT, L.LIK_ORDINAL):
         if flow is None:
             raise L.TgpError(L.NEEDS_FLOWSPEC % L.LIK_DISPLAY[lik])
-        lvn = student_noise(lvn, df)
+        lvn = noise_slot(lvn, lik, df)
     mu, v, lvn = _c(mu, "mu"), _c(v, "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     dev, N = mu.device, mu.numel()

@@ -108,6 +108,24 @@ def overdispersed_dataset(seed=0):
     return X, Y.astype(np.float64).reshape(-1, 1)
 
 
+# ordinal-regression stand-in: (rows, inputs), the number of classes and the cuts of the latent that separate them
+RATINGS_SHAPE = (800, 2)
+RATINGS_CLASSES = 5
+RATINGS_CUTS = (-1.0, -0.6, 0.3, 1.2)
+
+
+def synthetic_ratings(seed=0):
+    """Seeded `synthetic_ratings`: X ~ N(0, 1), latent h = sin(2 x0) + 0.5 x1, y = #{j : h + 0.3 eps > c_j} in {0, .., 4} with the
+    UNEVENLY spaced cuts c = RATINGS_CUTS -- the spacing of the levels is what a flow under evenly spaced bin edges has to learn.
+    Returns numpy float64 X (n, d) and Y (n, 1) with integer classes."""
+    n, d = RATINGS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    z = np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1] + 0.3 * rng.standard_normal(n)
+    Y = (z.reshape(-1, 1) > np.asarray(RATINGS_CUTS).reshape(1, -1)).sum(1)
+    return X, Y.astype(np.float64).reshape(-1, 1)
+
+
 # robust-regression stand-in: (rows, inputs, training rows)
 OUTLIERS_SHAPE = (1000, 2, 900)
 OUTLIERS_SHARE = 0.1
