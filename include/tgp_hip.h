@@ -182,6 +182,29 @@ extern "C" {
  * log-sum-exp.  The empty program is closed: P(y <= k) = Phi((b_{k+1} - mu) / sqrt(sigma^2 + max(v, 0))).  Y_std is ignored (classes
  * have no units).  The predictive is discrete: the quantile, CDF and CRPS entries refuse it (TGP_E_UNSUPPORTED). */
 #define TGP_LIK_ORDINAL 10
+/* Gamma noise with a log link for positive targets, y > 0, y | f0 ~ Gamma(shape a, mean exp(G(f0))): rate a exp(-g), Var[y | f0] =
+ * exp(2 g) / a, the variance proportional to the squared mean.  log_var_noise[0] = lambda = log a, a TRAINED parameter in the
+ * noise slot.  Supported range TGP_GAMMA_MIN_SHAPE <= a <= TGP_GAMMA_MAX_SHAPE: below it the extreme quantiles leave the double
+ * range (a = 0.01, p = 1e-6: log t ~ -1377); the library does not look at a, which lives on the device.  With g = G(f0),
+ * l = log y and z = l - g:
+ *   log p(y | g)      = [a log a - lgamma(a) - l] + a (z - e^z)
+ *   d log p / dg      = a (e^z - 1)
+ *   d log p / dlambda = a (log a + 1 - psi(a)) + a (z - e^z),      psi the digamma function,
+ * g not clamped (a node whose e^z overflows gives -inf, as the float64 formula does), Gauss-Hermite over q(f0) (S, xs, wn
+ * required); v <= 0 counts as 0 and its adjoint is 0.  The library does not check y > 0 (log y of such a target is -inf or
+ * NaN).  Gradients: grads->log_var_noise is ONE double, d/dlambda (as out[1] of tgp_ell_flow_f64).  The training step always
+ * takes the general-M path.
+ * tgp_predict_f64: m1 = E[y] = sum_s wn_s exp(g_s), m2 = Var[y] = (1 + 1/a) sum_s wn_s exp(2 g_s) - m1^2 (the empty program: the
+ * log-normal closed forms E[mean] = exp(mu + v/2), E[mean^2] = exp(2 mu + 2 v)), logp = log sum_s wn_s Gamma(y | a, a e^-g_s)
+ * - log Y_std, formed as a log-sum-exp: a Gamma family is closed under scaling, so this is the density of the raw target when
+ * the targets were divided by Y_std and not centred.
+ * The predictive is a location family in log y: tgp_predict_cdf_f64 and tgp_predict_quantile_f64 serve it (below);
+ * tgp_predict_crps_f64 refuses it (a mixture of Gammas has no closed pair term). */
+#define TGP_LIK_GAMMA 11
+#define TGP_GAMMA_MIN_SHAPE 0.1
+#define TGP_GAMMA_MAX_SHAPE 1e3
+/* most terms of the power series / continued fraction of the regularised incomplete gamma function (tgp_quantile.hip) */
+#define TGP_GAMMA_PQ_MAXIT 2048
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  With d2 = |(x - z)/l|^2, l = softplus(raw_ls), s2 = softplus(raw_os[0]) and r = sqrt(max(d2, 1e-30)) as gpytorch's
@@ -292,8 +315,8 @@ size_t tgp_workspace_bytes_kernel(int32_t N, int32_t D, int32_t M, int32_t S, in
 size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                 int32_t kernel, int32_t plan);
 
-/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN or
- * TGP_LIK_ORDINAL training step runs on the general-M path at every M. */
+/* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN,
+ * TGP_LIK_ORDINAL or TGP_LIK_GAMMA training step runs on the general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -648,7 +671,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
  * model->lik == TGP_LIK_STUDENT: the Student-t one of its #define (log_var_noise = {log sigma^2, nu}), out[1] = dELL/dlog sigma^2.
  * model->lik == TGP_LIK_NEGBIN: the negative-binomial one of its #define (log_var_noise = log r), out[1] = dELL/dlog r.
  * model->lik == TGP_LIK_ORDINAL: the cumulative-probit one of its #define (log_var_noise = {log sigma^2, K, b_1, .., b_{K-1}}),
- * out[1] = dELL/dlog sigma^2. */
+ * out[1] = dELL/dlog sigma^2.
+ * model->lik == TGP_LIK_GAMMA: the Gamma one of its #define (log_var_noise = log a), out[1] = dELL/dlog a. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -742,7 +766,7 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
  * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN, TGP_LIK_ORDINAL: see their #defines; Y_std is
  * ignored.
- * TGP_LIK_STUDENT: see its #define (Y_std is used, the constant is included).
+ * TGP_LIK_STUDENT, TGP_LIK_GAMMA: see their #defines (Y_std is used, the constant is included).
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
  * (WarpedGaussianLinearMean.marginal_moments), logp = log N(T(y) | mu, v + noise) + log T'(y) - log Y_std, the exact warped
  * predictive density WITH its constant (float32 pi as everywhere); rowp is ignored. */
@@ -761,7 +785,8 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
 int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */, const double* v /* (2,N) */, const double* rowp,
                            const double* Y, double Y_std, double* m1, double* m2, double* logp, void* stream);
 
-/* Exact CDF and quantiles of the predictive distribution tgp_predict_f64 integrates (TGP_LIK_GAUSS and TGP_LIK_FLOW; model
+/* Exact CDF and quantiles of the predictive distribution tgp_predict_f64 integrates (TGP_LIK_GAUSS and TGP_LIK_FLOW, and
+ * TGP_LIK_GAMMA as described at the end; model
  * fields as for tgp_predict_f64, everything in the model's standardised units):
  *   p(y | x_n) = sum_s wn_s N(y | g_ns, sig^2),  g_ns = G(mu_n + sqrt(2 v_n) xs_s),  sig^2 = exp(log_var_noise)
  *   F_n(t) = sum_s wn_s Phi((t - g_ns) / sig),   strictly increasing, F_n' = the density above.
@@ -778,7 +803,18 @@ int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */,
  * roots that ran out of evaluations; their t is NaN.
  * Limits: 1 <= S <= TGP_QUANTILE_MAX_S, 1 <= Q <= TGP_QUANTILE_MAX_Q; TGP_LIK_BERNOULLI, TGP_LIK_WARPED, TGP_LIK_SOFTMAX,
  * TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN and TGP_LIK_ORDINAL are refused -- all with TGP_E_UNSUPPORTED, tgp_last_error() names the entry.  float64, no float atomics, fixed summation order
- * over s: same input, same bits. */
+ * over s: same input, same bits.
+ * TGP_LIK_GAMMA (its #define): the same two entries on the mixture of Gammas, in tau = log t with a = exp(log_var_noise[0]):
+ *   F_n(tau) = sum_s wn_s P(a, a e^(tau - g_ns)),  the upper tail sum_s wn_s Q(a, a e^(tau - g_ns)) from its own sum,
+ *   F_n'(tau) = sum_s wn_s h(tau - g_ns),  h(z) = exp(a (z - expm1(z)) + [a log a - a - lgamma(a)]),
+ * P and Q the regularised lower and upper incomplete gamma functions: the power series for x < a + 1 (P, Q = 1 - P), the
+ * modified-Lentz continued fraction otherwise (Q, P = 1 - Q), both with the leading factor h, at most TGP_GAMMA_PQ_MAXIT terms.
+ * cdf[n] = F_n(log Y[n]); Y[n] <= 0: cdf = 0, sf = sum wn.  Quantiles: t = exp(tau) in the model's units, the root rule above
+ * run on tau (stop rule on tau) for every row -- v <= 0 rows and the empty program too, there is no closed form -- from
+ * tau0 = G(mu + zq sqrt v) + s(a, p), s the larger of the Wilson-Hilferty value 3 log(1 - 1/(9a) + zq / (3 sqrt a)) (where its
+ * argument is positive) and the small-argument value (log p + lgamma(a + 1)) / a - log a, first step
+ * max(1 / sqrt a, 1 / a, |tau0| 2^-20).  Covered: TGP_GAMMA_MIN_SHAPE <= a <= TGP_GAMMA_MAX_SHAPE, v in [0, 4], p in
+ * [1e-6, 1 - 1e-6]. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32
 int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* probs,

@@ -2,7 +2,8 @@
 // k_ell_quad, the predictive policies and k_predict_quad, each with its launch helper.  tgp_lik.hip instantiates them for the
 // Gaussian, Bernoulli, Poisson, Student-t and heteroscedastic policies and holds the table of likelihoods (lik_row),
 // tgp_lik_negbin.hip instantiates them for the negative-binomial policy and tgp_lik_ordinal.hip for the ordinal policies
-// (EllOrdinal, PredOrdinal), each in a unit of its own for the compile time.
+// (EllOrdinal, PredOrdinal) and tgp_lik_gamma.hip for the Gamma policies (EllGamma, PredGamma), each in a unit of its own for
+// the compile time.
 #pragma once
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
@@ -20,6 +21,7 @@ namespace tgp {
 //   ordinal (no counterpart in the reference), cumulative probit over K ordered classes with fixed bin edges b_1 < .. < b_{K-1}:
 //     log p(y | g) = log(Phi((b_{y+1} - g) / sigma) - Phi((b_y - g) / sigma)); the flow learns the spacing of the levels
 //     (TGP_LIK_ORDINAL, tgp_lik_ordinal.hip)
+//   Gamma (no counterpart in the reference), log link, shape a: mean exp(g), variance exp(2 g) / a (TGP_LIK_GAMMA, tgp_lik_gamma.hip)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and PredBern.  With a = |g|, t = a / sqrt 2:

@@ -192,6 +192,8 @@ EllLaunch ell_launch_negbin;           // tgp_lik_negbin.hip: what the TGP_LIK_N
 PredictLaunch predict_launch_negbin;
 EllLaunch ell_launch_ordinal;          // tgp_lik_ordinal.hip: what the TGP_LIK_ORDINAL row points to
 PredictLaunch predict_launch_ordinal;
+EllLaunch ell_launch_gamma;            // tgp_lik_gamma.hip: what the TGP_LIK_GAMMA row points to
+PredictLaunch predict_launch_gamma;
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,
@@ -216,7 +218,7 @@ int launch_flow_inverse(const tgp_model& md, const FlowProg& fp, const double* t
 int launch_predict_warp(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* Y, double Y_std,
                         double* m1, double* m2, double* logp, hipStream_t st);
 
-// tgp_quantile.hip (exact CDF and quantiles of the Gauss-Hermite predictive; TGP_LIK_GAUSS / TGP_LIK_FLOW)
+// tgp_quantile.hip (exact CDF and quantiles of the Gauss-Hermite predictive; TGP_LIK_GAUSS / TGP_LIK_FLOW / TGP_LIK_GAMMA)
 int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st);
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,

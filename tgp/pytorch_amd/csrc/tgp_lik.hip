@@ -267,6 +267,7 @@ static const LikRow lik_table[] = {
     LIK_ROW(HETERO,    false, false, ell_launch_row<EllHetero>,  nullptr,                            nullptr),
     LIK_ROW(NEGBIN,    true,  true,  ell_launch_negbin,          predict_launch_negbin,              "TGP_LIK_NEGBIN" NOQ_DISCRETE),
     LIK_ROW(ORDINAL,   true,  true,  ell_launch_ordinal,         predict_launch_ordinal,             "TGP_LIK_ORDINAL" NOQ_DISCRETE),
+    LIK_ROW(GAMMA,     true,  true,  ell_launch_gamma,           predict_launch_gamma,               nullptr),
 };
 const LikRow* lik_row(int lik) {
   for (const LikRow& r : lik_table)

@@ -1,8 +1,8 @@
 // tgp_quantile.hip -- exact predictive CDF and quantiles of the Gauss-Hermite predictive of tgp_predict_f64:
 //   p(y | x_n) = sum_s wn_s N(y | g_ns, sig^2),  g_ns = G(mu_n + sqrt(2 v_n) xs_s),  sig^2 = exp(log_var_noise)
 //   F_n(t) = sum_s wn_s Phi((t - g_ns) / sig),   F_n'(t) = sum_s wn_s phi((t - g_ns) / sig) / sig   (the density above)
-//   k_pred_cdf<X>       cdf = F_n(Y_n) and the upper tail 1 - F_n from its own sum
-//   k_pred_quantile<X>  t = the root of F_n(t) = p for Q probabilities per row, a bracketed Newton iteration on the S node values
+//   k_pred_cdf<C, X>    cdf = F_n(Y_n) and the upper tail 1 - F_n from its own sum
+//   k_pred_quantile<C, X> t = the root of F_n(t) = p for Q probabilities per row, a bracketed Newton iteration on the S node values
 //   k_quantile_gauss    TGP_LIK_GAUSS / the empty program: one Gaussian, closed forms for both
 //   k_predict_hetero<X> the heteroscedastic predictive (tgp_predict_hetero_f64): moments and log density on the same node table
 //   k_pred_crps<X, W>   the CRPS int (F_n(t) - 1{t >= Y_n})^2 dt in closed form: one pass over the nodes, one over their pairs
@@ -14,6 +14,10 @@
 // summation order: same input, same bits.  The loops are uniform over the wave (a row that is done keeps evaluating at its
 // root until the wave's last row is done), so the cross-lane adds always run with every lane on.
 // X: the extended flow kind set, as in k_predict_quad<Pred, X>.
+// C: the mixture component of k_pred_cdf and k_pred_quantile, a policy.  QGauss is the Gaussian around the flow above.  QGamma
+// (TGP_LIK_GAMMA) is a Gamma of shape a = exp(log_var_noise) and mean exp(g_ns): a location family in tau = log t,
+//   F_n(tau) = sum_s wn_s P(a, a e^(tau - g_ns)),   F_n'(tau) = sum_s wn_s h(tau - g_ns)      (gamma_pq below),
+// so the same root rule runs on tau and the kernel returns t = exp(tau).
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 
@@ -55,6 +59,108 @@ __device__ __forceinline__ QSum q_eval(const double* __restrict__ g, const doubl
   return r;
 }
 
+// What a mixture component supplies to k_pred_cdf and k_pred_quantile: consts(log_var_noise) = its per-thread constants K;
+// eval<DENS>(g, wn, S, l16, x, K) = the three sums at x; arg(y) = the x at which the CDF of the target y is read and value(x) the
+// quantile a root x stands for; start(gq, zq, p, K) = the first x of the root of probability p, gq = G(mu + zq sqrt v), and
+// first_step(x, K) the first bracket step; kZeroVarClosed: the start is the root of a row without variance.
+struct QGauss {
+  static constexpr bool kZeroVarClosed = true;   // one node value: the start is the closed form G(mu) + zq sig
+  struct K { double sig; };
+  static __device__ __forceinline__ K consts(const double* lvn) { return {sqrt(exp(lvn[0]))}; }
+  template <bool DENS>
+  static __device__ __forceinline__ QSum eval(const double* __restrict__ g, const double* __restrict__ wn, int S, int l16, double x,
+                                              const K& k) {
+    return q_eval<DENS>(g, wn, S, l16, x, k.sig);
+  }
+  static __device__ __forceinline__ double arg(double y) { return y; }
+  static __device__ __forceinline__ double value(double x) { return x; }
+  static __device__ __forceinline__ double start(double gq, double zq, double, const K& k) { return gq + zq * k.sig; }
+  static __device__ __forceinline__ double first_step(double x, const K& k) { return fmax(k.sig, fabs(x) * 9.5367431640625e-07); }
+};
+
+// The regularised incomplete gamma functions P(a, x) and Q(a, x) = 1 - P at x = a e^z, with the density of the component in z,
+//   h(z) = x^a e^-x / Gamma(a) = exp(a (z - expm1(z)) + c),   c = a log a - a - lgamma(a)   (once per thread, QGamma::K::c):
+// the expm1 form has none of the cancellation of a log x - x - lgamma(a) at large a.  x < a + 1: the power series
+// P = h sum_n x^n / (a (a + 1) .. (a + n)), Q = 1 - P; otherwise the continued fraction of Q by the modified Lentz rule,
+// P = 1 - Q: each side is computed where it is the small one or both are of order one.  x = 0 (z = -inf): (0, 1); x = +inf:
+// (1, 0).  At most TGP_GAMMA_PQ_MAXIT terms (a in [0.1, 1e3], z in [-8, 3]: 268 at most, tests/test_gamma_host.py); a NaN runs
+// the series to that cap and comes out as NaN.  Lanes run different trip counts and meet again behind the loop.
+struct GammaPQ { double P, Q, h; };
+__device__ __forceinline__ GammaPQ gamma_pq(double a, double c, double z) {
+  const double x = a * exp(z);
+  if (x == 0.0) return {0.0, 1.0, 0.0};
+  if (x == INFINITY) return {1.0, 0.0, 0.0};
+  const double h = exp(a * (z - expm1(z)) + c);
+  if (x < a + 1.0) {
+    double ap = a, sum = 1.0 / a, del = sum;
+    for (int n = 0; n < TGP_GAMMA_PQ_MAXIT; ++n) {
+      ap += 1.0;
+      del *= x / ap;
+      sum += del;
+      if (fabs(del) < fabs(sum) * 1.1102230246251565e-16) break;
+    }
+    const double P = sum * h;
+    return {P, 1.0 - P, h};
+  }
+  constexpr double FPMIN = 1e-300;
+  double b = x + 1.0 - a, cc = 1.0 / FPMIN, d = 1.0 / b, f = d;
+  for (int i = 1; i <= TGP_GAMMA_PQ_MAXIT; ++i) {
+    const double an = -(double)i * ((double)i - a);
+    b += 2.0;
+    d = an * d + b;
+    if (fabs(d) < FPMIN) d = FPMIN;
+    cc = b + an / cc;
+    if (fabs(cc) < FPMIN) cc = FPMIN;
+    d = 1.0 / d;
+    const double del = d * cc;
+    f *= del;
+    if (fabs(del - 1.0) < 1.1102230246251565e-16) break;
+  }
+  const double Qv = f * h;
+  return {1.0 - Qv, Qv, h};
+}
+
+struct QGamma {
+  static constexpr bool kZeroVarClosed = false;   // no closed form: a row without variance iterates like any other
+  struct K { double a, c, lga1, lam; };           // c as in gamma_pq, lga1 = lgamma(a + 1), lam = log a
+  static __device__ __forceinline__ K consts(const double* lvn) {
+    const double lam = lvn[0], a = exp(lam);
+    return {a, a * lam - a - lgamma(a), lgamma(a + 1.0), lam};
+  }
+  // lower = sum_s wn_s P(a, a e^z_s), upper = sum_s wn_s Q(a, a e^z_s), dens = sum_s wn_s h(z_s) at x = tau, z_s = tau - g_s
+  template <bool DENS>
+  static __device__ __forceinline__ QSum eval(const double* __restrict__ g, const double* __restrict__ wn, int S, int l16, double x,
+                                              const K& k) {
+    double lo = 0.0, up = 0.0, dn = 0.0;
+    for (int s0 = 0; s0 < S; s0 += QLPR) {
+      const int s = s0 + l16, sc = s < S ? s : S - 1;
+      const double w = s < S ? wn[sc] : 0.0;
+      const GammaPQ r = gamma_pq(k.a, k.c, x - g[sc]);
+      lo += w * r.P;
+      up += w * r.Q;
+      if (DENS) dn += w * r.h;
+    }
+    QSum r;
+    r.lower = row16_sum(lo);
+    r.upper = row16_sum(up);
+    r.dens = DENS ? row16_sum(dn) : 0.0;
+    return r;
+  }
+  // tau = log y; a target <= 0 has nothing below it (tau = -inf: every term is (0, 1)); a NaN stays one
+  static __device__ __forceinline__ double arg(double y) { return y > 0.0 ? log(y) : (y <= 0.0 ? -INFINITY : y); }
+  static __device__ __forceinline__ double value(double x) { return exp(x); }
+  // the log-quantile of one Gamma(a, rate a) around the flow's value: the larger of the Wilson-Hilferty value (where its argument
+  // is positive) and the small-argument value from P(a, x) ~ x^a / Gamma(a + 1)
+  static __device__ __forceinline__ double start(double gq, double zq, double p, const K& k) {
+    const double wh = 1.0 - 1.0 / (9.0 * k.a) + zq / (3.0 * sqrt(k.a));
+    const double sm = (log(p) + k.lga1) / k.a - k.lam;
+    return gq + (wh > 0.0 ? fmax(3.0 * log(wh), sm) : sm);
+  }
+  static __device__ __forceinline__ double first_step(double x, const K& k) {
+    return fmax(fmax(1.0 / sqrt(k.a), 1.0 / k.a), fabs(x) * 9.5367431640625e-07);
+  }
+};
+
 // The row's elements e = 0 .. S + Q - 1 through the flow into gs[e]: the quadrature nodes mu + sqrt(2 v) xs_e (the argument
 // k_predict forms), then the Q starting points mu + zq_q sqrt(v).  Lane l16 takes e = l16 + 16 j, four at a time.
 template <bool X>
@@ -80,7 +186,7 @@ __device__ __forceinline__ void q_sweep(const FlowDev& F, const tgp_model& md, c
 }
 
 // dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), wn (S rounded up to even), then QROWS node tables of q_row_stride(S + Q)
-template <bool X>
+template <class C, bool X>
 __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp, const double* __restrict__ mu,
                                                       const double* __restrict__ v, const double* __restrict__ rowp,
                                                       const double* __restrict__ probs, const double* __restrict__ zq, int Q,
@@ -99,7 +205,7 @@ __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp,
   const int nc = valid ? n : md.N - 1;
   const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
   const double m_ = mu[nc], vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
-  const double sig = sqrt(exp(md.log_var_noise[0]));
+  const typename C::K K = C::consts(md.log_var_noise);
   q_sweep<X>(F, md, rp, m_, vn, zq, Q, l16, gs);
   __syncthreads();
   for (int q = 0; q < Q; ++q) {
@@ -107,20 +213,20 @@ __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp,
     const bool upper = p > 0.5;
     const double tgt = upper ? 1.0 - p : p;
     // fx = F(x) - p, taken from the tail that is small: increasing in x on both sides, derivative = the density
-    double x = gs[S + q] + zq[q] * sig;
-    QSum e = q_eval<true>(gs, wl, S, l16, x, sig);
+    double x = C::start(gs[S + q], zq[q], p, K);
+    QSum e = C::template eval<true>(gs, wl, S, l16, x, K);
     double fx = upper ? tgt - e.upper : e.lower - tgt, dn = e.dens;
-    // a row without variance has one node value: the start is its closed form G(mu) + zq sig
-    bool done = !(vr > 0.0) || fx == 0.0, fail = false;
+    // QGauss: a row without variance has one node value: the start is its closed form G(mu) + zq sig
+    bool done = (C::kZeroVarClosed && !(vr > 0.0)) || fx == 0.0, fail = false;
     // ---- bracket: doubling steps from the start
-    double step = fmax(sig, fabs(x) * 9.5367431640625e-07);
+    double step = C::first_step(x, K);
     const bool grow_up = fx < 0.0;
     double lo = grow_up ? x : x - step, hi = grow_up ? x + step : x;
     bool ok = done;
     for (int it = 0; it < Q_MAXIT; ++it) {
       if (__ballot(!ok) == 0ull) break;
       const double probe = ok ? x : (grow_up ? hi : lo);
-      const QSum eb = q_eval<false>(gs, wl, S, l16, probe, sig);
+      const QSum eb = C::template eval<false>(gs, wl, S, l16, probe, K);
       const double fb = upper ? tgt - eb.upper : eb.lower - tgt;
       if (!ok) {
         if (grow_up ? fb >= 0.0 : fb <= 0.0) {
@@ -147,18 +253,18 @@ __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp,
         }
       }
       if (__ballot(!done) == 0ull) break;
-      e = q_eval<true>(gs, wl, S, l16, x, sig);
+      e = C::template eval<true>(gs, wl, S, l16, x, K);
       if (!done) { fx = upper ? tgt - e.upper : e.lower - tgt; dn = e.dens; }
     }
     if (!done) fail = true;
     if (valid && l16 == 0) {
-      t_out[(size_t)q * md.N + n] = fail ? NAN : x;
+      t_out[(size_t)q * md.N + n] = fail ? NAN : C::value(x);
       if (fail) atomicAdd(status, 1);
     }
   }
 }
 
-template <bool X>
+template <class C, bool X>
 __global__ __launch_bounds__(64) void k_pred_cdf(tgp_model md, FlowProg fp, const double* __restrict__ mu,
                                                  const double* __restrict__ v, const double* __restrict__ rowp,
                                                  const double* __restrict__ Y, int stride, double* __restrict__ cdf,
@@ -177,10 +283,10 @@ __global__ __launch_bounds__(64) void k_pred_cdf(tgp_model md, FlowProg fp, cons
   const int nc = valid ? n : md.N - 1;
   const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
   const double vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
-  const double sig = sqrt(exp(md.log_var_noise[0]));
+  const typename C::K K = C::consts(md.log_var_noise);
   q_sweep<X>(F, md, rp, mu[nc], vn, nullptr, 0, l16, gs);
   __syncthreads();
-  const QSum e = q_eval<false>(gs, wl, S, l16, Y[nc], sig);
+  const QSum e = C::template eval<false>(gs, wl, S, l16, C::arg(Y[nc]), K);
   if (valid && l16 == 0) {
     cdf[n] = e.lower;
     if (sf) sf[n] = e.upper;
@@ -419,7 +525,8 @@ static size_t q_lds_bytes(const tgp_model& md, int Q, int* stride) {
 
 int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st) {
-  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+  const bool gam = md.lik == TGP_LIK_GAMMA;   // no Gaussian shortcut: the empty program runs the kernel on g_s = mu + sqrt(2 v) xs_s
+  if (!gam && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
     hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise, zq, Q, t,
                        (const double*)nullptr, (double*)nullptr, (double*)nullptr);
     LAUNCH_CHECK();
@@ -428,9 +535,10 @@ int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const doubl
   int stride = 0;
   const size_t lds = q_lds_bytes(md, Q, &stride);
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-  static size_t cur[2] = {48 * 1024, 48 * 1024};
-  auto* const kern = ext ? k_pred_quantile<true> : k_pred_quantile<false>;
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  static size_t cur[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = gam ? (ext ? k_pred_quantile<QGamma, true> : k_pred_quantile<QGamma, false>)
+                         : (ext ? k_pred_quantile<QGauss, true> : k_pred_quantile<QGauss, false>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * gam + ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, probs, zq, Q, stride, t,
                      status);
   LAUNCH_CHECK();
@@ -439,7 +547,8 @@ int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const doubl
 
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                        const double* Y, double* cdf, double* sf, hipStream_t st) {
-  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+  const bool gam = md.lik == TGP_LIK_GAMMA;
+  if (!gam && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
     hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise,
                        (const double*)nullptr, 0, (double*)nullptr, Y, cdf, sf);
     LAUNCH_CHECK();
@@ -448,9 +557,10 @@ int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu
   int stride = 0;
   const size_t lds = q_lds_bytes(md, 0, &stride);
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-  static size_t cur[2] = {48 * 1024, 48 * 1024};
-  auto* const kern = ext ? k_pred_cdf<true> : k_pred_cdf<false>;
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  static size_t cur[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = gam ? (ext ? k_pred_cdf<QGamma, true> : k_pred_cdf<QGamma, false>)
+                         : (ext ? k_pred_cdf<QGauss, true> : k_pred_cdf<QGauss, false>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * gam + ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, stride, cdf, sf);
   LAUNCH_CHECK();
   return 0;

@@ -358,6 +358,88 @@ class NegativeBinomial(Poisson):
                                            self.quad_points)
 
 
+class Gamma(Likelihood):
+    """p(y|G(f)) = Gamma(y | shape a, mean exp(G(f))) for positive, skewed targets (durations, claim sizes, rainfall, prices):
+    the rate is a exp(-G(f)) and Var[y | f] = exp(2 G(f)) / a, the variance proportional to the squared mean.  One parameter,
+    `log_shape` = log a (one element, initialised at log `shape_init`), which sits where the Gaussian classes' log_var_noise sits
+    in the ABI and is trained through the same gradient slot.  Supported range lib.GAMMA_MIN_SHAPE <= a <= lib.GAMMA_MAX_SHAPE
+    (below it the extreme quantiles leave the double range; nothing looks at the value during training, the exact CDF and
+    quantiles of the model refuse a shape that has left it).  The quadrature over q(f0) runs in float64 on the GPU
+    (tgp_ell_flow_f64 / tgp_predict_f64 with TGP_LIK_GAMMA); the predictive is a mixture of Gammas, a location family in log y,
+    whose exact CDF and quantiles tgp_predict_cdf_f64 / tgp_predict_quantile_f64 serve.  kind = "regression": the
+    log density is that of the raw target (-log Y_std included: the targets may be scaled, not centred).  The reference has no
+    such class."""
+
+    display = "gamma"
+    lik_id = ops.L.LIK_GAMMA
+    engine_name = "gamma"
+    kind = "regression"
+    has_noise = True
+    one_launch_logp = True
+    outputs_refusal = "the gamma likelihood is built for one output (num_outputs = 1)"
+    refuses_input_dependent = NO_INPUT_DEPENDENT % display
+    refuses_optimal_qu = NOT_GAUSSIAN_IN_F % display
+    refuses_cdf = None
+    refuses_crps = "the predictive of a gamma model (%s) is a mixture of Gammas, which has no closed pair term"
+
+    def __init__(self, shape_init=1.0, quadrature_points=None):
+        super().__init__()
+        a = float(shape_init)
+        if not ops.L.GAMMA_MIN_SHAPE <= a <= ops.L.GAMMA_MAX_SHAPE:
+            raise ValueError("the shape of the gamma likelihood must lie in [%g, %g], got %g"
+                             % (ops.L.GAMMA_MIN_SHAPE, ops.L.GAMMA_MAX_SHAPE, a))
+        self.quad_points = cg.quad_points if quadrature_points is None else quadrature_points
+        self.log_shape = nn.Parameter(torch.log(torch.tensor([a], dtype=cg.dtype)))
+
+    def noise(self):
+        """log a, the one element behind the ABI's noise pointer, with the graph to the parameter."""
+        return self.log_shape.reshape(-1)[:1]
+
+    @property
+    def shape(self):
+        """a = exp(log_shape), detached."""
+        return torch.exp(self.log_shape.detach())
+
+    def check_shape(self):
+        """ValueError, naming the range, if the trained shape has left [lib.GAMMA_MIN_SHAPE, lib.GAMMA_MAX_SHAPE] (one sync)."""
+        a = float(self.shape.reshape(-1)[0])
+        if not ops.L.GAMMA_MIN_SHAPE <= a <= ops.L.GAMMA_MAX_SHAPE:      # (a NaN fails both comparisons)
+            raise ValueError("the shape of the gamma likelihood is %g: the exact CDF and quantiles cover [%g, %g]"
+                             % (a, ops.L.GAMMA_MIN_SHAPE, ops.L.GAMMA_MAX_SHAPE))
+
+    @staticmethod
+    def check_targets(Y):
+        """ValueError unless every target is finite and > 0 (the kernels take log y and do not look)."""
+        Yd = Y.detach()
+        if not bool(((Yd > 0) & torch.isfinite(Yd)).all()):     # (a NaN fails the comparison)
+            raise ValueError("the gamma likelihood takes positive targets: every target must be finite and > 0")
+
+    def sample_from_output(self, f, i, **kwargs):
+        """exp(f) Gamma(a, rate a): mean exp(f), shape a."""
+        a = self.shape.to(f.device, f.dtype).reshape(())
+        return torch.exp(f) * td.Gamma(a, a).sample(f.shape).reshape(f.shape)
+
+    def _checks(self, gauss_mean, flow, X):
+        assert len(flow) == 1, "Flow list must be size 1 for the gamma likelihood"
+        assert gauss_mean.size(0) == 1, "Gamma regression on this path has one output GP"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[log Gamma(y_n | a, a exp(-G(f0)))], differentiable in the moments, log_shape and the flow's parameters;
+        Y (1, MB) positive targets, moments (1, MB)."""
+        self.check_targets(Y)
+        self._checks(gauss_mean, flow, X)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllGammaFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                          gauss_cov.reshape(-1).contiguous(), self.noise().contiguous(), theta, rowp, spec,
+                                          self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """(m1, m2) = (E[y], Var[y]) of the predictive, m2 = (1 + 1/a) E[exp(2 G(f))] - m1^2, each of gauss_mean's shape (1, MB)."""
+        self._checks(gauss_mean, flow, X)
+        return self._moments(gauss_mean, gauss_cov, flow, X)
+
+
 class Ordinal(Likelihood):
     """p(y = k | G(f)) = Phi((b_{k+1} - G(f)) / sigma) - Phi((b_k - G(f)) / sigma) for ORDERED categories y in {0, .., K-1}
     (ratings, grades, severity levels): the cumulative-probit likelihood with K - 1 fixed bin edges b_1 < .. < b_{K-1}, b_0 = -inf,

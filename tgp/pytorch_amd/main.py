@@ -52,6 +52,14 @@ predictive median class, and the same three for the baseline that predicts the t
 
     python -m tgp.pytorch_amd.main --model TGP --likelihood ordinal --dataset synthetic_ratings \\
         --train_test_seed_split 1 --num_inducing 20 --epochs 2000
+
+`--likelihood gamma` trains a Gamma regression with a log link (SVGP or TGP, default flow SAL x 1) on the positive targets of
+synthetic_claims: y ~ Gamma(shape a, mean exp(G(f))), a trained from --shape_init.  It reports the test negative log-likelihood
+and RMSE in raw units, the learned shape, and the same two for a constant baseline (a Gamma at the training mean with the
+moment-matched shape); `--coverage exact` takes the 95 % interval from the exact quantiles of the mixture of Gammas:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood gamma --dataset synthetic_claims \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 2000 --coverage exact
 """
 import argparse
 
@@ -64,8 +72,8 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .lib import RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
-from .likelihoods import (Bernoulli, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
+from .lib import GAMMA_MAX_SHAPE, GAMMA_MIN_SHAPE, RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
+from .likelihoods import (Bernoulli, Gamma, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
                           NegativeBinomial, Ordinal, Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
@@ -89,11 +97,13 @@ HYPER = {
     ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "ratings"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "claims"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
 COUNT_DATASETS = ("synthetic_counts", "synthetic_overdispersed")
 ORDINAL_DATASETS = ("synthetic_ratings",)
+POSITIVE_DATASETS = ("synthetic_claims",)
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -104,7 +114,7 @@ def main(argv=None):
     ap.add_argument("--dataset", required=True,
                     choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero"]
                     + list(CLASSIFICATION_DATASETS)
-                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS))
+                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS) + list(POSITIVE_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
@@ -114,7 +124,7 @@ def main(argv=None):
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
     ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "negbinomial", "studentt", "hetero",
-                                             "ordinal"],
+                                             "ordinal", "gamma"],
                     default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; negbinomial: the same "
@@ -122,7 +132,8 @@ def main(argv=None):
                          "robust regression, Student-t noise of --df degrees of freedom around G(f); hetero: regression with "
                          "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP); ordinal: "
                          "ordered classes, cumulative probit with fixed bin edges, the flow learns the spacing of the levels "
-                         "(SVGP or TGP, synthetic_ratings)")
+                         "(SVGP or TGP, synthetic_ratings); gamma: positive targets, Gamma noise with a log link and a trained "
+                         "shape, Var = mean^2 / shape (SVGP or TGP, synthetic_claims)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
     ap.add_argument("--kernel", choices=list(KERNEL_CHOICES), default="rbf",
@@ -132,6 +143,8 @@ def main(argv=None):
                     help="alpha of --kernel rq, fixed (not trained), 1e-2 <= alpha <= 1e4")
     ap.add_argument("--dispersion_init", type=float, default=1.0,
                     help="the dispersion r of --likelihood negbinomial at the start (trained; supported range 1e-3 <= r <= 1e3)")
+    ap.add_argument("--shape_init", type=float, default=1.0,
+                    help="the shape of --likelihood gamma at the start (trained; supported range 0.1 <= shape <= 1e3)")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
                     help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
                          "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli, poisson or studentt)")
@@ -162,6 +175,13 @@ def main(argv=None):
         ap.error("--likelihood ordinal: SVGP or TGP only")
     if ordn != (args.dataset in ORDINAL_DATASETS):
         ap.error("--likelihood ordinal goes with the ordinal data sets (%s), and they with it" % ", ".join(ORDINAL_DATASETS))
+    gam = args.likelihood == "gamma"
+    if gam and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood gamma: SVGP or TGP only")
+    if gam and not (GAMMA_MIN_SHAPE <= args.shape_init <= GAMMA_MAX_SHAPE):
+        ap.error("--shape_init: the shape must be in [0.1, 1e3], got %g" % args.shape_init)
+    if gam != (args.dataset in POSITIVE_DATASETS):
+        ap.error("--likelihood gamma goes with the positive data sets (%s), and they with it" % ", ".join(POSITIVE_DATASETS))
     pois = args.likelihood == "poisson"
     if pois and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood poisson: SVGP or TGP only")
@@ -279,6 +299,8 @@ def main(argv=None):
         lik = Poisson()
     elif negb:
         lik = NegativeBinomial(dispersion_init=args.dispersion_init)
+    elif gam:
+        lik = Gamma(shape_init=args.shape_init, quadrature_points=cg.quad_points)
     elif ordn:
         lik = Ordinal(dc["num_classes"], quadrature_points=cg.quad_points)     # the default edges: unit spacing, centred
     elif het:
@@ -373,6 +395,27 @@ def main(argv=None):
             print("Dataset {}, num inducing points {}, model {}, learned dispersion r {:.3f}{}".format(
                 args.dataset, args.num_inducing, args.model, float(lik.dispersion),
                 "" if "dispersion" not in dc else " (true r {:.3f})".format(dc["dispersion"])))
+        if args.scores:
+            print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
+                args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))
+        return res
+    if gam:
+        # the constant baseline: one Gamma everywhere, at the mean of the training targets with the moment-matched shape
+        # mean^2 / variance; its NLL and RMSE on the test targets
+        y_tr, y_te = dc["Y_tr"].reshape(-1), dc["Y_te"].reshape(-1)
+        mean = y_tr.mean()
+        a0 = mean ** 2 / y_tr.var(unbiased=False)
+        base_nll = -(a0 * torch.log(a0 / mean) - torch.lgamma(a0) + (a0 - 1.0) * torch.log(y_te) - a0 * y_te / mean).mean().item()
+        base_rmse = ((y_te - mean) ** 2).mean().sqrt().item()
+        print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, -res[6], res[7]))
+        print("Dataset {}, num inducing points {}, model {}, Test coverage (95%, {}) {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, args.coverage, res[8]))
+        print("Dataset {}, constant Gamma (mean {:.3f}, shape {:.3f}), Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, mean.item(), a0.item(), base_nll, base_rmse))
+        print("Dataset {}, num inducing points {}, model {}, learned shape {:.3f}{}".format(
+            args.dataset, args.num_inducing, args.model, float(lik.shape),
+            "" if "shape" not in dc else " (true shape {:.3f})".format(dc["shape"])))
         if args.scores:
             print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
                 args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))

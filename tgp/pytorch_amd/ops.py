@@ -1316,6 +1316,13 @@ def ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp=None, scale=1.0):
     return _ell_quad(Y, mu, v, lvn, flow, theta, S, rowp, scale, L.LIK_NEGBIN)
 
 
+def ell_gamma(Y, mu, v, log_shape, flow, theta, S, rowp=None, scale=1.0):
+    """Gamma quadrature ELL with gradients, the flow as the log-mean: scale sum_n E_q(f0)[log Gamma(y_n | shape a, rate
+    a exp(-G(f0)))], log_shape = log a, 0.1 <= a <= 1e3, Y > 0 (tgp_ell_flow_f64 with TGP_LIK_GAMMA).  Returns dict(ell, g_lvn,
+    g_mu, g_v, g_theta, g_rowp); g_lvn = dELL/dlog_shape."""
+    return _ell_quad(Y, mu, v, log_shape, flow, theta, S, rowp, scale, L.LIK_GAMMA)
+
+
 def ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp=None, scale=1.0):
     """Ordinal (cumulative-probit) quadrature ELL with gradients: scale sum_n E_q(f0)[log(Phi((b_{y_n + 1} - G(f0)) / sigma) -
     Phi((b_{y_n} - G(f0)) / sigma))], Y the classes 0 .. K-1, lvn = log sigma^2, `edges` the K - 1 fixed bin edges b_1 < .. < b_{K-1}
@@ -1456,6 +1463,11 @@ EllNegBinFunction = _EllOf(
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_negbin(Y, mu, v, lvn, flow, theta, S, rowp)),
     """apply(Y, mu, v, lvn, theta, rowp, flow, S): ELL of the negative-binomial likelihood with autograd in (mu, v, the log
     dispersion, theta, rowp).""")
+EllGammaFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_gamma(Y, mu, v, lvn, flow, theta, S, rowp)),
+    """apply(Y, mu, v, log_shape, theta, rowp, flow, S): ELL of the Gamma likelihood with autograd in (mu, v, the log shape,
+    theta, rowp).""")
 EllOrdinalFunction = _EllOf(
     lambda Y, mu, v, lvn, edges, theta, rowp, flow, S: (
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp)),
@@ -1641,7 +1653,9 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     lik = lib.LIK_NEGBIN: as LIK_POISSON with the dispersion r = exp(lvn): m2 = m1 + (1 + 1/r) E[mean^2] - m1^2.
     lik = lib.LIK_ORDINAL: m1 = E[y], m2 = Var[y] in classes, logp = the log predictive pmf of class Y (closed form for an
     empty `flow`).  `df` is the slot for what rides beside the noise (noise_slot): the Student-t's degrees of freedom, the
-    ordinal likelihood's bin edges."""
+    ordinal likelihood's bin edges.
+    lik = lib.LIK_GAMMA: m1 = E[y], m2 = Var[y] = (1 + 1/a) E[mean^2] - m1^2 with the shape a = exp(lvn), logp = the log predictive
+    density of the raw target, -log Y_std included (targets divided by Y_std, not centred)."""
     lib = L.load()
     if lik in (L.LIK_STUDENT, L.LIK_ORDINAL):
         if flow is None:
@@ -1671,22 +1685,26 @@ def quantile_probs(probs, device=None):
     return (p, zq) if device is None else (p.to(device), zq.to(device))
 
 
-def _quantile_model(mu, lvn, flow, theta, S):
+def _quantile_model(mu, lvn, flow, theta, S, lik=None):
     if flow is not None and S is None:
         raise ValueError("a flow needs S, the number of Gauss-Hermite nodes")
-    return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device)
+    if lik == L.LIK_GAMMA and flow is None:
+        raise L.TgpError(L.NEEDS_FLOWSPEC % L.LIK_DISPLAY[lik])
+    return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device, lik=lik)
 
 
-def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=None, check=True):
+def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=None, check=True, lik=None):
     """Exact quantiles of the predictive distribution ops.predict integrates (tgp_predict_quantile_f64): t of shape (Q,N), in
     the model's standardised units, t[q,n] the root of sum_s wn_s Phi((t - G(mu_n + sqrt(2 v_n) xs_s)) / sigma) = probs[q].
     flow=None: the Gaussian likelihood's closed form.  With `check` the status word is read (one sync) and a root that did
-    not converge raises; check=False returns (t, status) and leaves NaN in its place."""
+    not converge raises; check=False returns (t, status) and leaves NaN in its place.
+    lik = lib.LIK_GAMMA (`flow` a FlowSpec, possibly empty; lvn the log shape): the quantiles of the mixture of Gammas, t > 0,
+    the roots found in log t; every other value of `lik` but None is the library's to refuse."""
     lib = L.load()
     mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     p, zq = quantile_probs(probs, mu.device)
-    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    md, keep = _quantile_model(mu, lvn, flow, theta, S, lik)
     t = torch.empty(p.numel(), mu.numel(), dtype=torch.float64, device=mu.device)
     status = torch.zeros(1, dtype=torch.int32, device=mu.device)
     L.check(lib.tgp_predict_quantile_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(p), L.ptr(zq), p.numel(), L.ptr(t),
@@ -1698,16 +1716,17 @@ def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=Non
     return t
 
 
-def predict_cdf(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None):
+def predict_cdf(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None, lik=None):
     """(cdf, sf): the predictive CDF at Y per row -- the PIT values of a calibration plot -- and the upper tail 1 - cdf from
-    its own sum (tgp_predict_cdf_f64); Y in the model's standardised units."""
+    its own sum (tgp_predict_cdf_f64); Y in the model's standardised units.  lik = lib.LIK_GAMMA: of the mixture of Gammas
+    (lvn the log shape); a Y <= 0 has cdf 0."""
     lib = L.load()
     mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
     Yc = _c(Y.reshape(-1), "Y")
     if Yc.numel() != mu.numel():
         raise ValueError("Y must hold one value per row (%d), got %d" % (mu.numel(), Yc.numel()))
-    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    md, keep = _quantile_model(mu, lvn, flow, theta, S, lik)
     cdf, sf = torch.empty_like(mu), torch.empty_like(mu)
     L.check(lib.tgp_predict_cdf_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), L.ptr(cdf), L.ptr(sf), L.stream_ptr()),
             "tgp_predict_cdf_f64")

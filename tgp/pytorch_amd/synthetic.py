@@ -126,6 +126,22 @@ def synthetic_ratings(seed=0):
     return X, Y.astype(np.float64).reshape(-1, 1)
 
 
+# positive-target stand-in: (rows, inputs) and the shape of the Gamma noise
+CLAIMS_SHAPE = (500, 2)
+CLAIMS_SHAPE_A = 3.0
+
+
+def synthetic_claims(seed=0):
+    """Seeded `synthetic_claims`: X ~ N(0, 1), y ~ Gamma(shape CLAIMS_SHAPE_A, mean exp(sin(2 x0) + 0.5 x1)) -- positive, skewed
+    targets whose variance is proportional to their squared mean.  Returns numpy float64 X (n, d) and Y (n, 1), every y > 0."""
+    n, d = CLAIMS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    mean = np.exp(np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1])
+    Y = np.maximum(mean * rng.gamma(CLAIMS_SHAPE_A, 1.0 / CLAIMS_SHAPE_A, size=n), np.finfo(np.float64).tiny)
+    return X, Y.astype(np.float64).reshape(-1, 1)
+
+
 # robust-regression stand-in: (rows, inputs, training rows)
 OUTLIERS_SHAPE = (1000, 2, 900)
 OUTLIERS_SHARE = 0.1
