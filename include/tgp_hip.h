@@ -205,6 +205,29 @@ extern "C" {
 #define TGP_GAMMA_MAX_SHAPE 1e3
 /* most terms of the power series / continued fraction of the regularised incomplete gamma function (tgp_quantile.hip) */
 #define TGP_GAMMA_PQ_MAXIT 2048
+/* Beta noise with a logit link for proportions, 0 < y < 1, y | f0 ~ Beta(mu phi, (1 - mu) phi) with mu = sigmoid(G(f0)): the flow's
+ * value is the log-odds of the mean, phi the precision, Var[y | f0] = mu (1 - mu) / (1 + phi).  log_var_noise[0] = lambda =
+ * log phi, a TRAINED parameter in the noise slot.  Supported range TGP_BETA_MIN_PRECISION <= phi <= TGP_BETA_MAX_PRECISION; the
+ * library does not look at phi, which lives on the device.  With g = G(f0), ly = log y, l1 = log1p(-y), y* = ly - l1,
+ * a = mu phi and b = (1 - mu) phi, 1 - mu formed as sigmoid(-g) so that neither a nor b loses digits at large |g|:
+ *   log p(y | g)      = lgamma(phi) - lgamma(a) - lgamma(b) + a y* + phi l1 - ly - l1
+ *   d log p / dg      = mu (1 - mu) phi [y* - psi(a) + psi(b)]
+ *   d log p / dlambda = phi [psi(phi) - mu psi(a) - (1 - mu) psi(b) + mu y* + l1],      psi the digamma function,
+ * g not clamped, Gauss-Hermite over q(f0) (S, xs, wn required); v <= 0 counts as 0 and its adjoint is 0.  The library does not
+ * check 0 < y < 1 (the logs of such a target are -inf or NaN).  Gradients: grads->log_var_noise is ONE double, d/dlambda (as
+ * out[1] of tgp_ell_flow_f64).  The training step always takes the general-M path.
+ * tgp_predict_f64: m1 = E[y] = sum_s wn_s mu_s, m2 = Var[y] = sum_s wn_s mu_s (1 - mu_s) / (1 + phi) + sum_s wn_s mu_s^2 - m1^2
+ * (the last two from 1 - mu_s where m1 > 1/2: the same variance, without the cancellation next to 1),
+ * logp = log sum_s wn_s Beta(y | a_s, b_s), formed as a log-sum-exp; the empty program runs the same sweep.  The targets are
+ * never standardised: Y_std is ignored.
+ * tgp_predict_cdf_f64 and tgp_predict_quantile_f64 serve the mixture of Betas (below); tgp_predict_crps_f64 refuses it (a
+ * mixture of Betas has no closed pair term). */
+#define TGP_LIK_BETA 12
+#define TGP_BETA_MIN_PRECISION 0.5
+#define TGP_BETA_MAX_PRECISION 1e3
+/* most steps of the continued fraction of the regularised incomplete beta function (tgp_quantile.hip): twice the 87 that the
+ * covered box needs (tests/test_beta_host.py) */
+#define TGP_BETA_CF_MAXIT 174
 
 /* covariance function: instance_kernel(name, ...) of models/utils_models.py:145-204 (gpytorch kernels, ARD, softplus
  * parameters).  With d2 = |(x - z)/l|^2, l = softplus(raw_ls), s2 = softplus(raw_os[0]) and r = sqrt(max(d2, 1e-30)) as gpytorch's
@@ -316,7 +339,7 @@ size_t tgp_workspace_bytes_plan(int32_t N, int32_t D, int32_t M, int32_t S, int3
                                 int32_t kernel, int32_t plan);
 
 /* Same for a call with likelihood `lik` (TGP_LIK_*): a TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_STUDENT, TGP_LIK_NEGBIN,
- * TGP_LIK_ORDINAL or TGP_LIK_GAMMA training step runs on the general-M path at every M. */
+ * TGP_LIK_ORDINAL, TGP_LIK_GAMMA or TGP_LIK_BETA training step runs on the general-M path at every M. */
 size_t tgp_workspace_bytes_lik(int32_t N, int32_t D, int32_t M, int32_t S, int32_t nblk, int32_t P, int32_t RP,
                                int32_t kernel, int32_t plan, int32_t lik);
 
@@ -672,7 +695,8 @@ int tgp_ell_gauss_f64(const double* Y, const double* mu, const double* v, int32_
  * model->lik == TGP_LIK_NEGBIN: the negative-binomial one of its #define (log_var_noise = log r), out[1] = dELL/dlog r.
  * model->lik == TGP_LIK_ORDINAL: the cumulative-probit one of its #define (log_var_noise = {log sigma^2, K, b_1, .., b_{K-1}}),
  * out[1] = dELL/dlog sigma^2.
- * model->lik == TGP_LIK_GAMMA: the Gamma one of its #define (log_var_noise = log a), out[1] = dELL/dlog a. */
+ * model->lik == TGP_LIK_GAMMA: the Gamma one of its #define (log_var_noise = log a), out[1] = dELL/dlog a.
+ * model->lik == TGP_LIK_BETA: the Beta one of its #define (log_var_noise = log phi), out[1] = dELL/dlog phi. */
 int tgp_ell_flow_f64(const tgp_model* model, const double* Y, const double* mu, const double* v, const double* rowp,
                      double* out, double* g_mu, double* g_v, double* g_theta, double* g_rowp, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -764,7 +788,7 @@ int tgp_predict_softmax_f64(const tgp_softmax* d, const double* mu, const double
 /* Evaluation path given q(f) moments: predictive moments m1, m2
  * (GaussianNonLinearMean.marginal_moments :152-203 / GaussianLinearMean.marginal_moments :89-118) and the
  * per-row test log-likelihood WITHOUT the -0.5*log(pi) constant (models/sparse_MF_SP.py:705-776, 786-799).
- * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN, TGP_LIK_ORDINAL: see their #defines; Y_std is
+ * Y may be NULL (then logp is not written).  TGP_LIK_BERNOULLI, TGP_LIK_POISSON, TGP_LIK_NEGBIN, TGP_LIK_ORDINAL, TGP_LIK_BETA: see their #defines; Y_std is
  * ignored.
  * TGP_LIK_STUDENT, TGP_LIK_GAMMA: see their #defines (Y_std is used, the constant is included).
  * TGP_LIK_WARPED: m1 = sum_s wn_s T^-1(mu + sqrt(2 (v + noise)) xs_s), m2 = the same of (T^-1)^2, minus m1^2
@@ -786,7 +810,7 @@ int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */,
                            const double* Y, double Y_std, double* m1, double* m2, double* logp, void* stream);
 
 /* Exact CDF and quantiles of the predictive distribution tgp_predict_f64 integrates (TGP_LIK_GAUSS and TGP_LIK_FLOW, and
- * TGP_LIK_GAMMA as described at the end; model
+ * TGP_LIK_GAMMA and TGP_LIK_BETA as described at the end; model
  * fields as for tgp_predict_f64, everything in the model's standardised units):
  *   p(y | x_n) = sum_s wn_s N(y | g_ns, sig^2),  g_ns = G(mu_n + sqrt(2 v_n) xs_s),  sig^2 = exp(log_var_noise)
  *   F_n(t) = sum_s wn_s Phi((t - g_ns) / sig),   strictly increasing, F_n' = the density above.
@@ -814,7 +838,23 @@ int tgp_predict_hetero_f64(const tgp_model* model, const double* mu /* (2,N) */,
  * tau0 = G(mu + zq sqrt v) + s(a, p), s the larger of the Wilson-Hilferty value 3 log(1 - 1/(9a) + zq / (3 sqrt a)) (where its
  * argument is positive) and the small-argument value (log p + lgamma(a + 1)) / a - log a, first step
  * max(1 / sqrt a, 1 / a, |tau0| 2^-20).  Covered: TGP_GAMMA_MIN_SHAPE <= a <= TGP_GAMMA_MAX_SHAPE, v in [0, 4], p in
- * [1e-6, 1 - 1e-6]. */
+ * [1e-6, 1 - 1e-6].
+ * TGP_LIK_BETA (its #define): the same two entries on the mixture of Betas, in x = logit t with phi = exp(log_var_noise[0]),
+ * a_ns = phi sigmoid(g_ns), b_ns = phi sigmoid(-g_ns):
+ *   F_n(x) = sum_s wn_s I_t(a_ns, b_ns),  the upper tail sum_s wn_s I_{1-t}(b_ns, a_ns) from its own sum,
+ *   F_n'(x) = sum_s wn_s h_ns(x),  h_ns = exp(a_ns log t + b_ns log(1 - t) - log B(a_ns, b_ns)),  log t = -softplus(-x),
+ *   log(1 - t) = -softplus(x),
+ * I the regularised incomplete beta function by the modified-Lentz continued fraction with h as the front factor, on the side
+ * where it converges fast: t < (a + 1) / (a + b + 2): I_t(a, b) = h cf(a, b, t) / a and the other tail 1 - that; else
+ * I_{1-t}(b, a) = h cf(b, a, 1 - t) / b and the other tail 1 - that; at most TGP_BETA_CF_MAXIT steps.  Not a location family:
+ * a_ns, b_ns and -log B of a row are computed once per row and kept in LDS beside the node values.  cdf[n] = F_n(logit Y[n]);
+ * Y[n] <= 0: cdf = 0, sf = sum wn; Y[n] >= 1: cdf = sum wn, sf = 0; NaN stays NaN.  Quantiles: t = sigmoid(x), the root rule
+ * above run on x (stop rule on x) for every row -- v <= 0 rows and the empty program too -- from x0 = gq + zq sqrt(1 / a + 1 / b)
+ * with a, b those of gq = G(mu + zq sqrt v), first step max(2 / sqrt phi, |x0| 2^-20).  Covered: TGP_BETA_MIN_PRECISION <= phi
+ * <= TGP_BETA_MAX_PRECISION, node values |g_ns| <= 12, |x| <= 15, p in [1e-6, 1 - 1e-6]: there a tail >= 1e-60 is within 2e-10
+ * of its value, relatively (1.3e-10 measured; 3e-14 for |g_ns| <= 4: the tail that is 1 - the computed one loses digits when
+ * the smaller shape parameter, and with it that tail, is tiny).  The root is resolved in x; the returned double t can say no
+ * more about 1 - t than its spacing of 2^-53 near 1 allows, and is exactly 1 for x > 36.7. */
 #define TGP_QUANTILE_MAX_S 256
 #define TGP_QUANTILE_MAX_Q 32
 int tgp_predict_quantile_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* probs,

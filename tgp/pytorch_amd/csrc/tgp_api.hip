@@ -1102,8 +1102,9 @@ static int check_quantile_model(const tgp_model* model, const double* mu, const 
     set_error_text("%s: no quantiles for %s", entry, row->no_quantiles);
     return TGP_E_UNSUPPORTED;
   }
-  if (model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW && model->lik != TGP_LIK_GAMMA) return -1;
-  *flowed = model->lik != TGP_LIK_GAUSS;   // TGP_LIK_GAMMA: whatever the program's length
+  if (model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW && model->lik != TGP_LIK_GAMMA && model->lik != TGP_LIK_BETA)
+    return -1;
+  *flowed = model->lik != TGP_LIK_GAUSS;   // TGP_LIK_GAMMA, TGP_LIK_BETA: whatever the program's length
   if (*flowed) {
     if (model->S < 1 || model->S > TGP_QUANTILE_MAX_S) {
       set_error_text("%s: S = %d outside 1..%d", entry, model->S, TGP_QUANTILE_MAX_S);

@@ -2,9 +2,10 @@
 // k_ell_quad, the predictive policies and k_predict_quad, each with its launch helper.  tgp_lik.hip instantiates them for the
 // Gaussian, Bernoulli, Poisson, Student-t and heteroscedastic policies and holds the table of likelihoods (lik_row),
 // tgp_lik_negbin.hip instantiates them for the negative-binomial policy and tgp_lik_ordinal.hip for the ordinal policies
-// (EllOrdinal, PredOrdinal) and tgp_lik_gamma.hip for the Gamma policies (EllGamma, PredGamma), each in a unit of its own for
-// the compile time.
+// (EllOrdinal, PredOrdinal), tgp_lik_gamma.hip for the Gamma policies (EllGamma, PredGamma) and tgp_lik_beta.hip for the Beta
+// policies (EllBeta, PredBeta), each in a unit of its own for the compile time.
 #pragma once
+#include <type_traits>
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 
@@ -22,6 +23,8 @@ namespace tgp {
 //     log p(y | g) = log(Phi((b_{y+1} - g) / sigma) - Phi((b_y - g) / sigma)); the flow learns the spacing of the levels
 //     (TGP_LIK_ORDINAL, tgp_lik_ordinal.hip)
 //   Gamma (no counterpart in the reference), log link, shape a: mean exp(g), variance exp(2 g) / a (TGP_LIK_GAMMA, tgp_lik_gamma.hip)
+//   Beta (no counterpart in the reference), logit link, precision phi: mean mu = sigmoid(g), variance mu (1 - mu) / (1 + phi)
+//     (TGP_LIK_BETA, tgp_lik_beta.hip)
 // ---------------------------------------------------------------------------------------------------
 
 // The node term shared by k_ell_quad<EllBern> and PredBern.  With a = |g|, t = a / sqrt 2:
@@ -543,11 +546,19 @@ static int ell_launch_one(bool ext, int nb, size_t lds, hipStream_t st, Args... 
   LAUNCH_CHECK();
   return 0;
 }
+// the most nodes in flight k_ell_quad is built with for a policy: Lik::kMaxNB where the policy names one (EllBeta: 4, the kernel
+// spills at 8), else 8.  The policy's LikRow carries the same number to ell_plan (ell_max_nb).
+template <class Lik, class = void>
+struct EllMaxNB { static constexpr int value = 8; };
+template <class Lik>
+struct EllMaxNB<Lik, std::void_t<decltype(Lik::kMaxNB)>> { static constexpr int value = Lik::kMaxNB; };
 // the instantiation for ell_plan's (LPR, NB)
 template <class Lik, class... Args>
 static int ell_launch(int LPR, int NB, Args... args) {
   if (LPR == 4) {
-    if (NB == 8) return ell_launch_one<Lik, 4, 8>(args...);
+    if constexpr (EllMaxNB<Lik>::value >= 8) {
+      if (NB == 8) return ell_launch_one<Lik, 4, 8>(args...);
+    }
     if (NB == 4) return ell_launch_one<Lik, 4, 4>(args...);
     if (NB == 2) return ell_launch_one<Lik, 4, 2>(args...);
     return ell_launch_one<Lik, 4, 1>(args...);

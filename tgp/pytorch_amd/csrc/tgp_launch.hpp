@@ -150,6 +150,7 @@ struct LikRow {
   EllLaunch* ell;            // launch_ell_quad's k_ell_quad instantiations (those of EllGauss where the id has no policy of its own)
   PredictLaunch* predict;    // launch_predict's k_predict_quad instantiations; nullptr: tgp_predict_f64 has none for it
   const char* no_quantiles;  // what the quantile / CDF entries say after "no quantiles for "; nullptr: they serve it
+  int ell_max_nb = 8;        // ell_plan's cap on the nodes in flight per lane (EllMaxNB, tgp_ell.hpp)
 };
 const LikRow* lik_row(int lik);   // nullptr: no such id
 inline bool lik_is_quadrature(int lik) { const LikRow* r = lik_row(lik); return r && r->quadrature; }
@@ -194,6 +195,8 @@ EllLaunch ell_launch_ordinal;          // tgp_lik_ordinal.hip: what the TGP_LIK_
 PredictLaunch predict_launch_ordinal;
 EllLaunch ell_launch_gamma;            // tgp_lik_gamma.hip: what the TGP_LIK_GAMMA row points to
 PredictLaunch predict_launch_gamma;
+EllLaunch ell_launch_beta;             // tgp_lik_beta.hip: what the TGP_LIK_BETA row points to
+PredictLaunch predict_launch_beta;
 int launch_predict(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp, const double* Y,
                    double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
 int launch_adam(double* params, const double* grads, double* exp_avg, double* exp_avg_sq, int64_t n, double lr,
@@ -218,7 +221,7 @@ int launch_flow_inverse(const tgp_model& md, const FlowProg& fp, const double* t
 int launch_predict_warp(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* Y, double Y_std,
                         double* m1, double* m2, double* logp, hipStream_t st);
 
-// tgp_quantile.hip (exact CDF and quantiles of the Gauss-Hermite predictive; TGP_LIK_GAUSS / TGP_LIK_FLOW / TGP_LIK_GAMMA)
+// tgp_quantile.hip (exact CDF and quantiles of the Gauss-Hermite predictive; TGP_LIK_GAUSS / TGP_LIK_FLOW / TGP_LIK_GAMMA / TGP_LIK_BETA)
 int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st);
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,

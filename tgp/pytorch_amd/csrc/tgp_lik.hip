@@ -268,6 +268,7 @@ static const LikRow lik_table[] = {
     LIK_ROW(NEGBIN,    true,  true,  ell_launch_negbin,          predict_launch_negbin,              "TGP_LIK_NEGBIN" NOQ_DISCRETE),
     LIK_ROW(ORDINAL,   true,  true,  ell_launch_ordinal,         predict_launch_ordinal,             "TGP_LIK_ORDINAL" NOQ_DISCRETE),
     LIK_ROW(GAMMA,     true,  true,  ell_launch_gamma,           predict_launch_gamma,               nullptr),
+    LIK_ROW(BETA,      true,  true,  ell_launch_beta,            predict_launch_beta,                nullptr, 4),
 };
 const LikRow* lik_row(int lik) {
   for (const LikRow& r : lik_table)
@@ -299,6 +300,8 @@ static int flow_lds(const tgp_model& md, int nblk, int NB, size_t* bytes) {
 static int ell_plan(const tgp_model& md, const FlowProg& fp, int* lpr, int* nbn, size_t* lds) {
   const int LPR = ell_lpr(md.N);
   int NB = LPR == 4 ? (md.S > 16 ? 8 : 4) : (LPR == 16 ? (md.S > 32 ? 4 : (md.S > 16 ? 2 : 1)) : (md.S > 64 ? 4 : (md.S > 32 ? 2 : 1)));
+  const LikRow* row = lik_row(md.lik);
+  if (row && NB > row->ell_max_nb) NB = row->ell_max_nb;   // (TGP_LIK_BETA: k_ell_quad<EllBeta, 4, 8> would spill)
   while (NB > 1 && (flow_lds(md, fp.nblk, NB, lds) != 0 || *lds > 120 * 1024)) NB >>= 1;
   *lpr = LPR;
   *nbn = NB;

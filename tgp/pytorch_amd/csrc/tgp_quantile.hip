@@ -17,7 +17,9 @@
 // C: the mixture component of k_pred_cdf and k_pred_quantile, a policy.  QGauss is the Gaussian around the flow above.  QGamma
 // (TGP_LIK_GAMMA) is a Gamma of shape a = exp(log_var_noise) and mean exp(g_ns): a location family in tau = log t,
 //   F_n(tau) = sum_s wn_s P(a, a e^(tau - g_ns)),   F_n'(tau) = sum_s wn_s h(tau - g_ns)      (gamma_pq below),
-// so the same root rule runs on tau and the kernel returns t = exp(tau).
+// so the same root rule runs on tau and the kernel returns t = exp(tau).  QBeta (TGP_LIK_BETA) is a Beta(phi sigmoid(g_ns),
+// phi sigmoid(-g_ns)), phi = exp(log_var_noise): the root rule runs on x = logit t over a regularised incomplete beta function
+// (beta_cf below) and the kernel returns t = sigmoid(x).
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 
@@ -62,10 +64,14 @@ __device__ __forceinline__ QSum q_eval(const double* __restrict__ g, const doubl
 // What a mixture component supplies to k_pred_cdf and k_pred_quantile: consts(log_var_noise) = its per-thread constants K;
 // eval<DENS>(g, wn, S, l16, x, K) = the three sums at x; arg(y) = the x at which the CDF of the target y is read and value(x) the
 // quantile a root x stands for; start(gq, zq, p, K) = the first x of the root of probability p, gq = G(mu + zq sqrt v), and
-// first_step(x, K) the first bracket step; kZeroVarClosed: the start is the root of a row without variance.
+// first_step(x, K) the first bracket step; kZeroVarClosed: the start is the root of a row without variance.  kCols: the columns
+// of S doubles its node table takes (the launchers size the row for them); prep(gs, S, Q, l16, K), after the sweep, once per
+// row: what the component keeps per node beside or in place of the node value (QBeta; nothing for the other two).
 struct QGauss {
   static constexpr bool kZeroVarClosed = true;   // one node value: the start is the closed form G(mu) + zq sig
+  static constexpr int kCols = 1;
   struct K { double sig; };
+  static __device__ __forceinline__ void prep(double*, int, int, int, K&) {}
   static __device__ __forceinline__ K consts(const double* lvn) { return {sqrt(exp(lvn[0]))}; }
   template <bool DENS>
   static __device__ __forceinline__ QSum eval(const double* __restrict__ g, const double* __restrict__ wn, int S, int l16, double x,
@@ -122,7 +128,9 @@ __device__ __forceinline__ GammaPQ gamma_pq(double a, double c, double z) {
 
 struct QGamma {
   static constexpr bool kZeroVarClosed = false;   // no closed form: a row without variance iterates like any other
+  static constexpr int kCols = 1;
   struct K { double a, c, lga1, lam; };           // c as in gamma_pq, lga1 = lgamma(a + 1), lam = log a
+  static __device__ __forceinline__ void prep(double*, int, int, int, K&) {}
   static __device__ __forceinline__ K consts(const double* lvn) {
     const double lam = lvn[0], a = exp(lam);
     return {a, a * lam - a - lgamma(a), lgamma(a + 1.0), lam};
@@ -161,6 +169,107 @@ struct QGamma {
   }
 };
 
+// The continued fraction of the regularised incomplete beta function, I_t(a, b) = t^a (1 - t)^b / (a B(a, b)) beta_cf(a, b, t), by
+// the modified Lentz rule, two coefficients per step; it converges fast for t < (a + 1) / (a + b + 2).  At most TGP_BETA_CF_MAXIT
+// steps (phi in [0.5, 1e3], |g| <= 12, |logit t| <= 15: 87 at most, tests/test_beta_host.py); a NaN runs to that cap and comes
+// out as NaN.  Lanes run different trip counts and meet again behind the loop.
+__device__ __forceinline__ double beta_cf(double a, double b, double t) {
+  constexpr double FPMIN = 1e-300;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * t / qap;
+  if (fabs(d) < FPMIN) d = FPMIN;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= TGP_BETA_CF_MAXIT; ++m) {
+    const double dm = (double)m, m2 = 2.0 * dm;
+    double aa = dm * (b - dm) * t / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < FPMIN) d = FPMIN;
+    c = 1.0 + aa / c;
+    if (fabs(c) < FPMIN) c = FPMIN;
+    d = 1.0 / d;
+    h *= d * c;
+    aa = -(a + dm) * (qab + dm) * t / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < FPMIN) d = FPMIN;
+    c = 1.0 + aa / c;
+    if (fabs(c) < FPMIN) c = FPMIN;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < 2.2204460492503131e-16) break;
+  }
+  return h;
+}
+
+// QBeta (TGP_LIK_BETA): the component at node s is a Beta(a_s, b_s), a_s = phi sigmoid(g_ns), b_s = phi sigmoid(-g_ns),
+// phi = exp(log_var_noise).  Not a location family -- both shape parameters change from node to node -- so prep() turns the node
+// table of a row, once per row, into three columns: a_s in place of g_s, then behind the Q starting points b_s and
+// nlb_s = -log B(a_s, b_s) = lgamma(phi) - lgamma(a_s) - lgamma(b_s) (K::off = S + Q is where b starts).  The root rule runs on
+// x = logit t and the kernel returns t = sigmoid(x); with lt = log t = -softplus(-x) and lu = log(1 - t) = -softplus(x), formed once
+// per evaluation from one exp(-|x|),
+//   h_s = exp(a_s lt + b_s lu + nlb_s)                the density of the component in x (the Jacobian t (1 - t) removes the two -1s)
+//   t < (a_s + 1) / (phi + 2):  lower = h_s beta_cf(a_s, b_s, t) / a_s,      upper = 1 - lower
+//   else:                       upper = h_s beta_cf(b_s, a_s, 1 - t) / b_s,  lower = 1 - upper,
+// each tail computed where it is the small one or both are of order one.  x = -inf: (0, 1); x = +inf: (1, 0).
+struct QBeta {
+  static constexpr bool kZeroVarClosed = false;   // no closed form: a row without variance iterates like any other
+  static constexpr int kCols = 3;                 // columns of the node table
+  struct K { double phi, lgphi; int off; };
+  static __device__ __forceinline__ K consts(const double* lvn) {
+    const double phi = exp(lvn[0]);
+    return {phi, lgamma(phi), 0};
+  }
+  // lane l16 rewrites the node values it wrote in q_sweep (s = l16 mod 16): no barrier in between
+  static __device__ __forceinline__ void prep(double* __restrict__ gs, int S, int Q, int l16, K& k) {
+    k.off = S + Q;
+    for (int s = l16; s < S; s += QLPR) {
+      const double g = gs[s], e = exp(-fabs(g)), d = 1.0 / (1.0 + e), ed = e * d;
+      const double a = (g > 0.0 ? d : ed) * k.phi, b = (g > 0.0 ? ed : d) * k.phi;
+      gs[s] = a;
+      gs[k.off + s] = b;
+      gs[k.off + S + s] = k.lgphi - lgamma(a) - lgamma(b);
+    }
+  }
+  template <bool DENS>
+  static __device__ __forceinline__ QSum eval(const double* __restrict__ g, const double* __restrict__ wn, int S, int l16, double x,
+                                              const K& k) {
+    const double e = exp(-fabs(x)), d = 1.0 / (1.0 + e), ed = e * d, l1e = log1p(e);
+    const double t = x > 0.0 ? d : ed, u = x > 0.0 ? ed : d;                      // t and 1 - t
+    const double lt = x > 0.0 ? -l1e : x - l1e, lu = x > 0.0 ? -x - l1e : -l1e;   // their logs
+    double lo = 0.0, up = 0.0, dn = 0.0;
+    for (int s0 = 0; s0 < S; s0 += QLPR) {
+      const int s = s0 + l16, sc = s < S ? s : S - 1;
+      const double w = s < S ? wn[sc] : 0.0;
+      const double a = g[sc], b = g[k.off + sc], h = exp(a * lt + b * lu + g[k.off + S + sc]);
+      const bool low = t < (a + 1.0) / (a + b + 2.0);
+      const double small = low ? h * beta_cf(a, b, t) / a : h * beta_cf(b, a, u) / b, big = 1.0 - small;
+      lo += w * (low ? small : big);
+      up += w * (low ? big : small);
+      if (DENS) dn += w * h;
+    }
+    QSum r;
+    r.lower = row16_sum(lo);
+    r.upper = row16_sum(up);
+    r.dens = DENS ? row16_sum(dn) : 0.0;
+    return r;
+  }
+  // x = logit y; a target <= 0 has nothing below it, a target >= 1 nothing above; a NaN stays one
+  static __device__ __forceinline__ double arg(double y) {
+    return y <= 0.0 ? -INFINITY : (y >= 1.0 ? INFINITY : log(y) - log1p(-y));
+  }
+  static __device__ __forceinline__ double value(double x) { return 1.0 / (1.0 + exp(-x)); }
+  // the logit of one Beta(a, b) around the flow's value gq is roughly normal with variance 1 / a + 1 / b
+  static __device__ __forceinline__ double start(double gq, double zq, double, const K& k) {
+    const double e = exp(-fabs(gq));
+    return gq + zq * sqrt((1.0 + e) * (1.0 + e) / (e * k.phi));   // 1 / a + 1 / b = 1 / (phi mu (1 - mu)), mu (1 - mu) = e d^2
+  }
+  // 1 / a + 1 / b >= 4 / phi
+  static __device__ __forceinline__ double first_step(double x, const K& k) {
+    return fmax(2.0 / sqrt(k.phi), fabs(x) * 9.5367431640625e-07);
+  }
+};
+
 // The row's elements e = 0 .. S + Q - 1 through the flow into gs[e]: the quadrature nodes mu + sqrt(2 v) xs_e (the argument
 // k_predict forms), then the Q starting points mu + zq_q sqrt(v).  Lane l16 takes e = l16 + 16 j, four at a time.
 template <bool X>
@@ -185,7 +294,7 @@ __device__ __forceinline__ void q_sweep(const FlowDev& F, const tgp_model& md, c
   }
 }
 
-// dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), wn (S rounded up to even), then QROWS node tables of q_row_stride(S + Q)
+// dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), wn (S rounded up to even), then QROWS node tables of q_row_stride(kCols S + Q)
 template <class C, bool X>
 __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp, const double* __restrict__ mu,
                                                       const double* __restrict__ v, const double* __restrict__ rowp,
@@ -205,8 +314,9 @@ __global__ __launch_bounds__(64) void k_pred_quantile(tgp_model md, FlowProg fp,
   const int nc = valid ? n : md.N - 1;
   const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
   const double m_ = mu[nc], vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
-  const typename C::K K = C::consts(md.log_var_noise);
+  typename C::K K = C::consts(md.log_var_noise);
   q_sweep<X>(F, md, rp, m_, vn, zq, Q, l16, gs);
+  C::prep(gs, S, Q, l16, K);
   __syncthreads();
   for (int q = 0; q < Q; ++q) {
     const double p = probs[q];
@@ -283,8 +393,9 @@ __global__ __launch_bounds__(64) void k_pred_cdf(tgp_model md, FlowProg fp, cons
   const int nc = valid ? n : md.N - 1;
   const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
   const double vr = v[nc], vn = vr > 0.0 ? vr : 0.0;
-  const typename C::K K = C::consts(md.log_var_noise);
+  typename C::K K = C::consts(md.log_var_noise);
   q_sweep<X>(F, md, rp, mu[nc], vn, nullptr, 0, l16, gs);
+  C::prep(gs, S, 0, l16, K);
   __syncthreads();
   const QSum e = C::template eval<false>(gs, wl, S, l16, C::arg(Y[nc]), K);
   if (valid && l16 == 0) {
@@ -518,27 +629,29 @@ int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double*
   return 0;
 }
 
-static size_t q_lds_bytes(const tgp_model& md, int Q, int* stride) {
-  *stride = q_row_stride(md.S + Q);
+static size_t q_lds_bytes(const tgp_model& md, int Q, int* stride, int cols = 1) {
+  *stride = q_row_stride(cols * md.S + Q);
   return (2 * (size_t)((md.P + 2) / 2 * 2) + (size_t)((md.S + 1) / 2 * 2) + (size_t)QROWS * *stride) * sizeof(double);
 }
 
 int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                             const double* probs, const double* zq, int Q, double* t, int32_t* status, hipStream_t st) {
-  const bool gam = md.lik == TGP_LIK_GAMMA;   // no Gaussian shortcut: the empty program runs the kernel on g_s = mu + sqrt(2 v) xs_s
-  if (!gam && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
+  // TGP_LIK_GAMMA, TGP_LIK_BETA: no Gaussian shortcut, the empty program runs the kernel on g_s = mu + sqrt(2 v) xs_s
+  const int comp = md.lik == TGP_LIK_GAMMA ? 1 : md.lik == TGP_LIK_BETA ? 2 : 0;
+  if (!comp && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
     hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise, zq, Q, t,
                        (const double*)nullptr, (double*)nullptr, (double*)nullptr);
     LAUNCH_CHECK();
     return 0;
   }
   int stride = 0;
-  const size_t lds = q_lds_bytes(md, Q, &stride);
+  const size_t lds = q_lds_bytes(md, Q, &stride, comp == 2 ? QBeta::kCols : 1);
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-  static size_t cur[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-  auto* const kern = gam ? (ext ? k_pred_quantile<QGamma, true> : k_pred_quantile<QGamma, false>)
-                         : (ext ? k_pred_quantile<QGauss, true> : k_pred_quantile<QGauss, false>);
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * gam + ext])) return rc;
+  static size_t cur[6] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = comp == 2   ? (ext ? k_pred_quantile<QBeta, true> : k_pred_quantile<QBeta, false>)
+                     : comp == 1 ? (ext ? k_pred_quantile<QGamma, true> : k_pred_quantile<QGamma, false>)
+                                 : (ext ? k_pred_quantile<QGauss, true> : k_pred_quantile<QGauss, false>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * comp + ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, probs, zq, Q, stride, t,
                      status);
   LAUNCH_CHECK();
@@ -547,20 +660,21 @@ int launch_predict_quantile(const tgp_model& md, const FlowProg& fp, const doubl
 
 int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                        const double* Y, double* cdf, double* sf, hipStream_t st) {
-  const bool gam = md.lik == TGP_LIK_GAMMA;
-  if (!gam && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
+  const int comp = md.lik == TGP_LIK_GAMMA ? 1 : md.lik == TGP_LIK_BETA ? 2 : 0;
+  if (!comp && (md.lik == TGP_LIK_GAUSS || fp.nblk == 0)) {
     hipLaunchKernelGGL(k_quantile_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, mu, v, md.log_var_noise,
                        (const double*)nullptr, 0, (double*)nullptr, Y, cdf, sf);
     LAUNCH_CHECK();
     return 0;
   }
   int stride = 0;
-  const size_t lds = q_lds_bytes(md, 0, &stride);
+  const size_t lds = q_lds_bytes(md, 0, &stride, comp == 2 ? QBeta::kCols : 1);
   const bool ext = flow_prog_extended(fp.blk, fp.nblk);
-  static size_t cur[4] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
-  auto* const kern = gam ? (ext ? k_pred_cdf<QGamma, true> : k_pred_cdf<QGamma, false>)
-                         : (ext ? k_pred_cdf<QGauss, true> : k_pred_cdf<QGauss, false>);
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * gam + ext])) return rc;
+  static size_t cur[6] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = comp == 2   ? (ext ? k_pred_cdf<QBeta, true> : k_pred_cdf<QBeta, false>)
+                     : comp == 1 ? (ext ? k_pred_cdf<QGamma, true> : k_pred_cdf<QGamma, false>)
+                                 : (ext ? k_pred_cdf<QGauss, true> : k_pred_cdf<QGauss, false>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * comp + ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, stride, cdf, sf);
   LAUNCH_CHECK();
   return 0;

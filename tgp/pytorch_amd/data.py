@@ -128,16 +128,18 @@ def _binary_dataset(base, batch_size, use_validation, seed, options):
     (synthetic.blobs_dataset; data_config["num_classes"]) and the count sets synthetic_counts (synthetic.counts_dataset) and
     synthetic_overdispersed (synthetic.overdispersed_dataset; data_config["dispersion"] keeps its true r) and the ordinal set
     synthetic_ratings (synthetic.synthetic_ratings; data_config["num_classes"]) and the positive set synthetic_claims
-    (synthetic.synthetic_claims; data_config["shape"] keeps the true shape of its Gamma noise): a
-    seeded 90 / 10 split, X standardised by the train split, labels, counts, classes and positive targets left as they are
-    (not centred, Y_std = 1)."""
-    from .synthetic import (CLAIMS_SHAPE_A, OVERDISPERSED_R, RATINGS_CLASSES, binary_dataset, blobs_dataset, counts_dataset,
-                            overdispersed_dataset, synthetic_claims, synthetic_ratings)
+    (synthetic.synthetic_claims; data_config["shape"] keeps the true shape of its Gamma noise) and the proportions of
+    synthetic_proportions (synthetic.synthetic_proportions; data_config["precision"] keeps the true precision of its Beta noise): a
+    seeded 90 / 10 split, X standardised by the train split, labels, counts, classes, positive targets and proportions left as
+    they are (not centred, Y_std = 1)."""
+    from .synthetic import (CLAIMS_SHAPE_A, OVERDISPERSED_R, PROPORTIONS_PRECISION, RATINGS_CLASSES, binary_dataset, blobs_dataset,
+                            counts_dataset, overdispersed_dataset, synthetic_claims, synthetic_proportions, synthetic_ratings)
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
     X, Y = (blobs_dataset() if base == "blobs" else counts_dataset() if base == "counts" else
             overdispersed_dataset() if base == "overdispersed" else synthetic_ratings() if base == "ratings" else
-            synthetic_claims() if base == "claims" else binary_dataset(base))
+            synthetic_claims() if base == "claims" else synthetic_proportions() if base == "proportions" else
+            binary_dataset(base))
     n = X.shape[0]
     perm = numpy.random.default_rng(seed).permutation(n)
     n_tr = int(round(0.9 * n))
@@ -168,8 +170,10 @@ def _binary_dataset(base, batch_size, use_validation, seed, options):
         data_config["dispersion"] = OVERDISPERSED_R
     if base == "claims":
         data_config["shape"] = CLAIMS_SHAPE_A
-    if base in ("counts", "overdispersed", "ratings", "claims"):
-        data_config["Y_mean"] = numpy.zeros(1)      # said outright: the targets are the raw counts (classes, amounts), RMSE and NLL are in them
+    if base == "proportions":
+        data_config["precision"] = PROPORTIONS_PRECISION
+    if base in ("counts", "overdispersed", "ratings", "claims", "proportions"):
+        data_config["Y_mean"] = numpy.zeros(1)      # said outright: the targets are the raw counts (classes, amounts, proportions), RMSE and NLL are in them
     return loaders, data_config
 
 
@@ -186,7 +190,7 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     options = options or {}
     synth = dataset_name.startswith("synthetic_")
     base = dataset_name.replace("synthetic_", "")
-    if synth and (base in BINARY_SHAPES or base in ("blobs", "counts", "overdispersed", "ratings", "claims")):
+    if synth and (base in BINARY_SHAPES or base in ("blobs", "counts", "overdispersed", "ratings", "claims", "proportions")):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
     if (synth and base not in SHAPES and base not in ("outliers", "hetero")) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))

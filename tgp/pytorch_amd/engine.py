@@ -35,7 +35,7 @@ ORDER = ("Z", "raw_ls", "raw_os", "m", "Lam", "lvn", "theta", "mean_a", "mean_b"
 
 # the `likelihood` names of the quadrature likelihoods that train through ops.ElboFunction only
 EAGER_ONLY = {"bernoulli": L.LIK_BERNOULLI, "poisson": L.LIK_POISSON, "negbinomial": L.LIK_NEGBIN, "studentt": L.LIK_STUDENT,
-              "ordinal": L.LIK_ORDINAL, "gamma": L.LIK_GAMMA}
+              "ordinal": L.LIK_ORDINAL, "gamma": L.LIK_GAMMA, "beta": L.LIK_BETA}
 
 
 def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, collective=None, per_row=False, minibatch=False,
@@ -43,7 +43,7 @@ def engine_refusal(is_whiten=True, mean=None, likelihood=None, world_size=1, col
     """What the step engines cover, stated once: None when ElboEngine (`minibatch` False) or MinibatchEngine (True) takes the
     combination, else the message both refuse it with (_refuse) before they load the library or touch the device; the
     trainers take the eager loop on a message.  A pure function of the description: `mean` = None / "linear" / "identity",
-    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "negbinomial" / "studentt" / "ordinal" / "gamma" / "multiclass" / "hetero", `collective` as passed to the engine (asking
+    `likelihood` = None (Gaussian or flow) / "warped" / "bernoulli" / "poisson" / "negbinomial" / "studentt" / "ordinal" / "gamma" / "beta" / "multiclass" / "hetero", `collective` as passed to the engine (asking
     for one counts as data-parallel, like world_size > 1), `per_row` = input-dependent flow parameters (an MLP or `rowp`),
     `kernel` = the covariance function's instance_kernel name (None: any but 'scale_rq')."""
     multi_rank = int(world_size) > 1 or collective is not None

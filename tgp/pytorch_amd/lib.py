@@ -25,11 +25,14 @@ LIK_NEGBIN = 9              # negative-binomial counts, the flow as the log-mean
 # what a message calls the likelihoods that go through a FlowSpec on the eager path only (the step engines have none of them)
 LIK_ORDINAL = 10            # ordered classes, cumulative probit around the flow (TGP_LIK_ORDINAL): log_var_noise = {log sigma^2, K, edges}
 LIK_GAMMA = 11              # positive targets, Gamma noise with the flow as the log-mean (TGP_LIK_GAMMA): log_var_noise = log shape
+LIK_BETA = 12               # proportions in (0, 1), Beta noise with the flow as the log-odds of the mean (TGP_LIK_BETA): log_var_noise = log precision
 LIK_DISPLAY = {LIK_BERNOULLI: "Bernoulli", LIK_POISSON: "Poisson", LIK_STUDENT: "Student-t", LIK_NEGBIN: "negative-binomial",
-               LIK_ORDINAL: "ordinal", LIK_GAMMA: "Gamma"}
+               LIK_ORDINAL: "ordinal", LIK_GAMMA: "Gamma", LIK_BETA: "Beta"}
 NEEDS_FLOWSPEC = "the %s likelihood needs a FlowSpec (an empty one for the identity flow)"
 STUDENT_MAX_DF = 1e4       # the supported degrees of freedom are 2 < nu <= STUDENT_MAX_DF (include/tgp_hip.h)
 GAMMA_MIN_SHAPE, GAMMA_MAX_SHAPE = 0.1, 1e3   # the supported shapes of LIK_GAMMA (include/tgp_hip.h)
+BETA_MIN_PRECISION, BETA_MAX_PRECISION = 0.5, 1e3   # the supported precisions of LIK_BETA (include/tgp_hip.h)
+BETA_CF_MAXIT = 174        # most steps of the incomplete beta function's continued fraction (TGP_BETA_CF_MAXIT)
 GAMMA_PQ_MAXIT = 2048      # most terms of the incomplete gamma function's series / continued fraction (TGP_GAMMA_PQ_MAXIT)
 ORDINAL_MAX_K = 64         # the supported number of classes is 2 <= K <= ORDINAL_MAX_K (include/tgp_hip.h)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256

@@ -440,6 +440,92 @@ class Gamma(Likelihood):
         return self._moments(gauss_mean, gauss_cov, flow, X)
 
 
+class Beta(Likelihood):
+    """p(y|G(f)) = Beta(y | mu phi, (1 - mu) phi), mu = sigmoid(G(f)), for proportions and rates strictly inside (0, 1)
+    (conversion rates, fractions, percentages, probabilities as data): the flow's value is the log-odds of the mean, phi the
+    precision, Var[y | f] = mu (1 - mu) / (1 + phi) -- it shrinks towards both ends of the interval.  The link is fixed; the
+    monotone flow of a TGP learns what the link function should have been.  One parameter, `log_precision` = log phi (one
+    element, initialised at log `precision_init`), which sits where the Gaussian classes' log_var_noise sits in the ABI and is
+    trained through the same gradient slot.  Supported range lib.BETA_MIN_PRECISION <= phi <= lib.BETA_MAX_PRECISION (nothing
+    looks at the value during training; the exact CDF and quantiles of the model refuse a precision that has left it).  The
+    quadrature over q(f0) runs in float64 on the GPU (tgp_ell_flow_f64 / tgp_predict_f64 with TGP_LIK_BETA); the predictive is a
+    mixture of Betas whose exact CDF and quantiles tgp_predict_cdf_f64 / tgp_predict_quantile_f64 serve through a regularised
+    incomplete beta function.  kind = "regression"; the targets are never standardised (Y_std is ignored).  The
+    reference has no such class."""
+
+    display = "beta"
+    lik_id = ops.L.LIK_BETA
+    engine_name = "beta"
+    kind = "regression"
+    has_noise = True
+    one_launch_logp = True
+    outputs_refusal = "the beta likelihood is built for one output (num_outputs = 1)"
+    refuses_input_dependent = NO_INPUT_DEPENDENT % display
+    refuses_optimal_qu = NOT_GAUSSIAN_IN_F % display
+    refuses_cdf = None
+    refuses_crps = "the predictive of a beta model (%s) is a mixture of Betas, which has no closed pair term"
+
+    def __init__(self, precision_init=10.0, quadrature_points=None):
+        super().__init__()
+        phi = float(precision_init)
+        if not ops.L.BETA_MIN_PRECISION <= phi <= ops.L.BETA_MAX_PRECISION:
+            raise ValueError("the precision of the beta likelihood must lie in [%g, %g], got %g"
+                             % (ops.L.BETA_MIN_PRECISION, ops.L.BETA_MAX_PRECISION, phi))
+        self.quad_points = cg.quad_points if quadrature_points is None else quadrature_points
+        self.log_precision = nn.Parameter(torch.log(torch.tensor([phi], dtype=cg.dtype)))
+
+    def noise(self):
+        """log phi, the one element behind the ABI's noise pointer, with the graph to the parameter."""
+        return self.log_precision.reshape(-1)[:1]
+
+    @property
+    def precision(self):
+        """phi = exp(log_precision), detached."""
+        return torch.exp(self.log_precision.detach())
+
+    def check_precision(self):
+        """ValueError, naming the range, if the trained precision has left [lib.BETA_MIN_PRECISION, lib.BETA_MAX_PRECISION]
+        (one sync)."""
+        phi = float(self.precision.reshape(-1)[0])
+        if not ops.L.BETA_MIN_PRECISION <= phi <= ops.L.BETA_MAX_PRECISION:      # (a NaN fails both comparisons)
+            raise ValueError("the precision of the beta likelihood is %g: the exact CDF and quantiles cover [%g, %g]"
+                             % (phi, ops.L.BETA_MIN_PRECISION, ops.L.BETA_MAX_PRECISION))
+
+    @staticmethod
+    def check_targets(Y):
+        """ValueError unless every target is finite and strictly inside (0, 1) (the kernels take log y and log(1 - y) and do
+        not look)."""
+        Yd = Y.detach()
+        if not bool(((Yd > 0) & (Yd < 1)).all()):     # (a NaN fails both comparisons)
+            raise ValueError("the beta likelihood takes proportions: every target must be finite and strictly inside (0, 1)")
+
+    def sample_from_output(self, f, i, **kwargs):
+        """Beta(mu phi, (1 - mu) phi) at mu = sigmoid(f)."""
+        phi = self.precision.to(f.device, f.dtype).reshape(())
+        return td.Beta(torch.sigmoid(f) * phi, torch.sigmoid(-f) * phi).sample().reshape(f.shape)
+
+    def _checks(self, gauss_mean, flow, X):
+        assert len(flow) == 1, "Flow list must be size 1 for the beta likelihood"
+        assert gauss_mean.size(0) == 1, "Beta regression on this path has one output GP"
+        assert len(X.shape) == 3, 'Bad input X, expected (1,MB,Dx)'
+
+    def expected_log_prob(self, Y, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """sum_n E_q(f0)[log Beta(y_n | mu phi, (1 - mu) phi)], mu = sigmoid(G(f0)), differentiable in the moments, log_precision
+        and the flow's parameters; Y (1, MB) proportions, moments (1, MB)."""
+        self.check_targets(Y)
+        self._checks(gauss_mean, flow, X)
+        spec, theta, rowp = self._flow_inputs(flow, X, gauss_mean.device, with_grad=True)
+        return ops.EllBetaFunction.apply(Y.reshape(-1).to(gauss_mean.dtype), gauss_mean.reshape(-1).contiguous(),
+                                         gauss_cov.reshape(-1).contiguous(), self.noise().contiguous(), theta, rowp, spec,
+                                         self.quad_points)
+
+    def marginal_moments(self, gauss_mean, gauss_cov, flow, X, **kwargs):
+        """(m1, m2) = (E[y], Var[y]) of the predictive, m2 = E[mu (1 - mu)] / (1 + phi) + Var[mu], each of gauss_mean's shape
+        (1, MB)."""
+        self._checks(gauss_mean, flow, X)
+        return self._moments(gauss_mean, gauss_cov, flow, X)
+
+
 class Ordinal(Likelihood):
     """p(y = k | G(f)) = Phi((b_{k+1} - G(f)) / sigma) - Phi((b_k - G(f)) / sigma) for ORDERED categories y in {0, .., K-1}
     (ratings, grades, severity levels): the cumulative-probit likelihood with K - 1 fixed bin edges b_1 < .. < b_{K-1}, b_0 = -inf,

@@ -60,6 +60,15 @@ moment-matched shape); `--coverage exact` takes the 95 % interval from the exact
 
     python -m tgp.pytorch_amd.main --model TGP --likelihood gamma --dataset synthetic_claims \\
         --train_test_seed_split 1 --num_inducing 20 --epochs 2000 --coverage exact
+
+`--likelihood beta` trains a Beta regression with a logit link (SVGP or TGP, default flow SAL x 1) on the proportions of
+synthetic_proportions: y ~ Beta(mu phi, (1 - mu) phi), mu = sigmoid(G(f)), the precision phi trained from --precision_init.  It
+reports the test negative log-likelihood and RMSE, the learned precision, and the same two for a constant baseline (one Beta
+moment-matched to the training targets); `--coverage exact` takes the 95 % interval from the exact quantiles of the mixture of
+Betas:
+
+    python -m tgp.pytorch_amd.main --model TGP --likelihood beta --dataset synthetic_proportions \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 2000 --coverage exact
 """
 import argparse
 
@@ -72,8 +81,8 @@ from .flow import instance_flow
 from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
-from .lib import GAMMA_MAX_SHAPE, GAMMA_MIN_SHAPE, RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
-from .likelihoods import (Bernoulli, Gamma, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
+from .lib import BETA_MAX_PRECISION, BETA_MIN_PRECISION, GAMMA_MAX_SHAPE, GAMMA_MIN_SHAPE, RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
+from .likelihoods import (Bernoulli, Beta, Gamma, GaussianLinearMean, GaussianNonLinearMean, HeteroscedasticGaussian, MulticlassCategorical,
                           NegativeBinomial, Ordinal, Poisson, StudentT, WarpedGaussianLinearMean)
 from .models import sparse_MF_GP, sparse_MF_SP
 from .trainers import Trainer_SP_classification, Trainer_SP_regression
@@ -98,12 +107,14 @@ HYPER = {
     ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "ratings"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "claims"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "proportions"): dict(arch="SAL", blocks=1, steps=None),
 }
 CLASSIFICATION_DATASETS = ("synthetic_heart", "synthetic_banknote")
 MULTICLASS_DATASETS = ("synthetic_blobs",)
 COUNT_DATASETS = ("synthetic_counts", "synthetic_overdispersed")
 ORDINAL_DATASETS = ("synthetic_ratings",)
 POSITIVE_DATASETS = ("synthetic_claims",)
+PROPORTION_DATASETS = ("synthetic_proportions",)
 FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
 _PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
 
@@ -114,7 +125,8 @@ def main(argv=None):
     ap.add_argument("--dataset", required=True,
                     choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero"]
                     + list(CLASSIFICATION_DATASETS)
-                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS) + list(POSITIVE_DATASETS))
+                    + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS) + list(POSITIVE_DATASETS)
+                    + list(PROPORTION_DATASETS))
     ap.add_argument("--train_test_seed_split", required=True, type=int)
     ap.add_argument("--num_inducing", required=True, type=int)
     ap.add_argument("--epochs", type=int, default=15000)
@@ -124,7 +136,7 @@ def main(argv=None):
     ap.add_argument("--whiten", type=int, choices=[0, 1], default=1,
                     help="1: whitened q(v) (the reference's main.py); 0: q(u) on the inducing values (is_whiten=False, eager loop)")
     ap.add_argument("--likelihood", choices=["gaussian", "bernoulli", "multiclass", "poisson", "negbinomial", "studentt", "hetero",
-                                             "ordinal", "gamma"],
+                                             "ordinal", "gamma", "beta"],
                     default="gaussian",
                     help="gaussian: regression (default); bernoulli: binary classification, probit link; multiclass: "
                          "softmax over C latent GPs; poisson: count regression, the flow of the GP is the log-rate; negbinomial: the same "
@@ -133,7 +145,9 @@ def main(argv=None):
                          "input-dependent Gaussian noise, a second latent GP for the log noise variance (SVGP or TGP); ordinal: "
                          "ordered classes, cumulative probit with fixed bin edges, the flow learns the spacing of the levels "
                          "(SVGP or TGP, synthetic_ratings); gamma: positive targets, Gamma noise with a log link and a trained "
-                         "shape, Var = mean^2 / shape (SVGP or TGP, synthetic_claims)")
+                         "shape, Var = mean^2 / shape (SVGP or TGP, synthetic_claims); beta: proportions in (0, 1), Beta noise with a "
+                         "logit link and a trained precision, Var = mean (1 - mean) / (1 + precision) (SVGP or TGP, "
+                         "synthetic_proportions)")
     ap.add_argument("--df", type=float, default=4.0,
                     help="degrees of freedom of --likelihood studentt, fixed (not trained), 2 < df <= 1e4")
     ap.add_argument("--kernel", choices=list(KERNEL_CHOICES), default="rbf",
@@ -145,6 +159,8 @@ def main(argv=None):
                     help="the dispersion r of --likelihood negbinomial at the start (trained; supported range 1e-3 <= r <= 1e3)")
     ap.add_argument("--shape_init", type=float, default=1.0,
                     help="the shape of --likelihood gamma at the start (trained; supported range 0.1 <= shape <= 1e3)")
+    ap.add_argument("--precision_init", type=float, default=10.0,
+                    help="the precision of --likelihood beta at the start (trained; supported range 0.5 <= precision <= 1e3)")
     ap.add_argument("--mean", choices=["zero", "linear", "identity"], default="zero",
                     help="mean function of the GP: zero (the reference's main.py); linear m(x) = x a + b, trainable; identity "
                          "m(x) = x W, W the first principal direction of the training inputs (SVGP / TGP; gaussian, bernoulli, poisson or studentt)")
@@ -182,6 +198,13 @@ def main(argv=None):
         ap.error("--shape_init: the shape must be in [0.1, 1e3], got %g" % args.shape_init)
     if gam != (args.dataset in POSITIVE_DATASETS):
         ap.error("--likelihood gamma goes with the positive data sets (%s), and they with it" % ", ".join(POSITIVE_DATASETS))
+    beta = args.likelihood == "beta"
+    if beta and args.model not in ("SVGP", "TGP"):
+        ap.error("--likelihood beta: SVGP or TGP only")
+    if beta and not (BETA_MIN_PRECISION <= args.precision_init <= BETA_MAX_PRECISION):
+        ap.error("--precision_init: the precision must be in [0.5, 1e3], got %g" % args.precision_init)
+    if beta != (args.dataset in PROPORTION_DATASETS):
+        ap.error("--likelihood beta goes with the proportion data sets (%s), and they with it" % ", ".join(PROPORTION_DATASETS))
     pois = args.likelihood == "poisson"
     if pois and args.model not in ("SVGP", "TGP"):
         ap.error("--likelihood poisson: SVGP or TGP only")
@@ -301,6 +324,8 @@ def main(argv=None):
         lik = NegativeBinomial(dispersion_init=args.dispersion_init)
     elif gam:
         lik = Gamma(shape_init=args.shape_init, quadrature_points=cg.quad_points)
+    elif beta:
+        lik = Beta(precision_init=args.precision_init, quadrature_points=cg.quad_points)
     elif ordn:
         lik = Ordinal(dc["num_classes"], quadrature_points=cg.quad_points)     # the default edges: unit spacing, centred
     elif het:
@@ -416,6 +441,29 @@ def main(argv=None):
         print("Dataset {}, num inducing points {}, model {}, learned shape {:.3f}{}".format(
             args.dataset, args.num_inducing, args.model, float(lik.shape),
             "" if "shape" not in dc else " (true shape {:.3f})".format(dc["shape"])))
+        if args.scores:
+            print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
+                args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))
+        return res
+    if beta:
+        # the constant baseline: one Beta everywhere, moment-matched to the training targets (mean m, precision
+        # m (1 - m) / variance - 1); its NLL and RMSE on the test targets
+        y_tr, y_te = dc["Y_tr"].reshape(-1), dc["Y_te"].reshape(-1)
+        mean = y_tr.mean()
+        p0 = mean * (1.0 - mean) / y_tr.var(unbiased=False) - 1.0
+        a0, b0 = mean * p0, (1.0 - mean) * p0
+        base_nll = -(torch.lgamma(p0) - torch.lgamma(a0) - torch.lgamma(b0) + (a0 - 1.0) * torch.log(y_te)
+                     + (b0 - 1.0) * torch.log1p(-y_te)).mean().item()
+        base_rmse = ((y_te - mean) ** 2).mean().sqrt().item()
+        print("Dataset {}, num inducing points {}, model {}, Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, -res[6], res[7]))
+        print("Dataset {}, num inducing points {}, model {}, Test coverage (95%, {}) {:.3f}".format(
+            args.dataset, args.num_inducing, args.model, args.coverage, res[8]))
+        print("Dataset {}, constant Beta (mean {:.3f}, precision {:.3f}), Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
+            args.dataset, mean.item(), p0.item(), base_nll, base_rmse))
+        print("Dataset {}, num inducing points {}, model {}, learned precision {:.3f}{}".format(
+            args.dataset, args.num_inducing, args.model, float(lik.precision),
+            "" if "precision" not in dc else " (true precision {:.3f})".format(dc["precision"])))
         if args.scores:
             print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f} (sampled), Test interval score (95%) n/a".format(
                 args.dataset, args.num_inducing, args.model, trainer.compute_scores()["test"]["crps"]))

@@ -698,6 +698,8 @@ class sparse_MF_SP(nn.Module):
         assert X.dim() == 2, "Invalid input X.shape"
         if what != "posterior_quantiles" and hasattr(lik, "check_shape"):
             lik.check_shape()     # (a Gamma model: ValueError once the trained shape has left the range the root rule covers)
+        if what != "posterior_quantiles" and hasattr(lik, "check_precision"):
+            lik.check_precision()     # (a Beta model: the same of its precision)
         self._eval_mode()
         with torch.no_grad():
             mean_q_f, cov_q_f = self.marginal_variational_qf_parameters(X.repeat(self.out_dim, 1, 1), diagonal=True,
@@ -713,7 +715,8 @@ class sparse_MF_SP(nn.Module):
         """Exact quantiles of p(y* | x*) at the rows of X, shape (Dy, Q, N), in the model's standardised units: the roots of
         the Gauss-Hermite predictive CDF (ops.predict_quantiles); the Gaussian likelihood's closed form; a warped model's
         T^-1(mu + zq sqrt(v + noise)); a Gamma model's are those of its mixture of Gammas (ValueError if the trained shape has
-        left [lib.GAMMA_MIN_SHAPE, lib.GAMMA_MAX_SHAPE]).  probs: any order, each strictly inside (0, 1)."""
+        left [lib.GAMMA_MIN_SHAPE, lib.GAMMA_MAX_SHAPE]); a Beta model's those of its mixture of Betas, inside (0, 1) (ValueError if
+        the trained precision has left [lib.BETA_MIN_PRECISION, lib.BETA_MAX_PRECISION]).  probs: any order, each strictly inside (0, 1)."""
         mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X, "predictive_quantiles")
         with torch.no_grad():
             if self.likelihood.flow_on_targets:
@@ -757,7 +760,7 @@ class sparse_MF_SP(nn.Module):
         ops.predict_crps for whatever predictive_cdf serves through the Gauss-Hermite mixture (Gaussian and flow likelihoods).
         A Poisson model: sum_k (cdf_k - 1{k >= y})^2 over k = 0..kmax from predictive_pmf(X, kmax); kmax is the caller's, as
         for predictive_pmf (past the mass the terms are 0).  samples=S: ops.crps_from_samples of S draws of
-        sample_from_predictive_distribution, for any regression model.  Without it Student-t, heteroscedastic, Gamma, warped and fully
+        sample_from_predictive_distribution, for any regression model.  Without it Student-t, heteroscedastic, Gamma, Beta, warped and fully
         Bayesian models raise NotImplementedError; Bernoulli and multi-class models always do."""
         count = self.likelihood.kind == "count"
         exact = samples is None and not count

@@ -267,7 +267,9 @@ def elbo_step(X, Y, Z, raw_ls, raw_os, m, Lam, lvn, N_total, flow=None, theta=No
     log r and grads["lvn"] its gradient.
     `lik` = lib.LIK_ORDINAL: ordered classes Y in {0, .., K-1} (cumulative probit around the flow); lvn (one element) is the log
     noise variance and grads["lvn"] its gradient.  `df` is the slot for what rides beside the noise (noise_slot): here the K - 1
-    fixed bin edges, which have no gradient."""
+    fixed bin edges, which have no gradient.
+    `lik` = lib.LIK_GAMMA / lib.LIK_BETA: positive targets with the flow as the log-mean / proportions in (0, 1) with the flow as
+    the log-odds of the mean; lvn (one element) is the log shape / the log precision and grads["lvn"] its gradient."""
     lib = L.load()
     X, Y = _c(X, "X"), _c(Y.reshape(-1), "Y")
     Z, raw_ls, raw_os, m, Lam, lvn = (_c(t, n) for t, n in ((Z, "Z"), (raw_ls, "raw_ls"), (raw_os, "raw_os"), (m, "m"),
@@ -1323,6 +1325,13 @@ def ell_gamma(Y, mu, v, log_shape, flow, theta, S, rowp=None, scale=1.0):
     return _ell_quad(Y, mu, v, log_shape, flow, theta, S, rowp, scale, L.LIK_GAMMA)
 
 
+def ell_beta(Y, mu, v, log_precision, flow, theta, S, rowp=None, scale=1.0):
+    """Beta quadrature ELL with gradients, the flow as the log-odds of the mean: scale sum_n E_q(f0)[log Beta(y_n | mu phi,
+    (1 - mu) phi)], mu = sigmoid(G(f0)), log_precision = log phi, 0.5 <= phi <= 1e3, 0 < Y < 1 (tgp_ell_flow_f64 with
+    TGP_LIK_BETA).  Returns dict(ell, g_lvn, g_mu, g_v, g_theta, g_rowp); g_lvn = dELL/dlog_precision."""
+    return _ell_quad(Y, mu, v, log_precision, flow, theta, S, rowp, scale, L.LIK_BETA)
+
+
 def ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp=None, scale=1.0):
     """Ordinal (cumulative-probit) quadrature ELL with gradients: scale sum_n E_q(f0)[log(Phi((b_{y_n + 1} - G(f0)) / sigma) -
     Phi((b_{y_n} - G(f0)) / sigma))], Y the classes 0 .. K-1, lvn = log sigma^2, `edges` the K - 1 fixed bin edges b_1 < .. < b_{K-1}
@@ -1468,6 +1477,11 @@ EllGammaFunction = _EllOf(
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_gamma(Y, mu, v, lvn, flow, theta, S, rowp)),
     """apply(Y, mu, v, log_shape, theta, rowp, flow, S): ELL of the Gamma likelihood with autograd in (mu, v, the log shape,
     theta, rowp).""")
+EllBetaFunction = _EllOf(
+    lambda Y, mu, v, lvn, theta, rowp, flow, S: (
+        Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_beta(Y, mu, v, lvn, flow, theta, S, rowp)),
+    """apply(Y, mu, v, log_precision, theta, rowp, flow, S): ELL of the Beta likelihood with autograd in (mu, v, the log
+    precision, theta, rowp).""")
 EllOrdinalFunction = _EllOf(
     lambda Y, mu, v, lvn, edges, theta, rowp, flow, S: (
         Y, mu, v, lvn, theta, rowp, lambda Y, mu, v, lvn, theta, rowp: ell_ordinal(Y, mu, v, lvn, edges, flow, theta, S, rowp)),
@@ -1655,7 +1669,9 @@ def predict(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, Y=None, Y_std=
     empty `flow`).  `df` is the slot for what rides beside the noise (noise_slot): the Student-t's degrees of freedom, the
     ordinal likelihood's bin edges.
     lik = lib.LIK_GAMMA: m1 = E[y], m2 = Var[y] = (1 + 1/a) E[mean^2] - m1^2 with the shape a = exp(lvn), logp = the log predictive
-    density of the raw target, -log Y_std included (targets divided by Y_std, not centred)."""
+    density of the raw target, -log Y_std included (targets divided by Y_std, not centred).
+    lik = lib.LIK_BETA: m1 = E[y] = E[mean], m2 = Var[y] = E[mean (1 - mean)] / (1 + phi) + Var[mean] with the precision
+    phi = exp(lvn), logp = the log predictive density of the proportion Y; Y_std is ignored."""
     lib = L.load()
     if lik in (L.LIK_STUDENT, L.LIK_ORDINAL):
         if flow is None:
@@ -1688,7 +1704,7 @@ def quantile_probs(probs, device=None):
 def _quantile_model(mu, lvn, flow, theta, S, lik=None):
     if flow is not None and S is None:
         raise ValueError("a flow needs S, the number of Gauss-Hermite nodes")
-    if lik == L.LIK_GAMMA and flow is None:
+    if lik in (L.LIK_GAMMA, L.LIK_BETA) and flow is None:
         raise L.TgpError(L.NEEDS_FLOWSPEC % L.LIK_DISPLAY[lik])
     return _flow_model(mu.numel(), S, flow, theta, lvn, mu.device, lik=lik)
 
@@ -1699,7 +1715,8 @@ def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=Non
     flow=None: the Gaussian likelihood's closed form.  With `check` the status word is read (one sync) and a root that did
     not converge raises; check=False returns (t, status) and leaves NaN in its place.
     lik = lib.LIK_GAMMA (`flow` a FlowSpec, possibly empty; lvn the log shape): the quantiles of the mixture of Gammas, t > 0,
-    the roots found in log t; every other value of `lik` but None is the library's to refuse."""
+    the roots found in log t.  lik = lib.LIK_BETA (lvn the log precision): the quantiles of the mixture of Betas, 0 < t < 1, the
+    roots found in logit t.  Every other value of `lik` but None is the library's to refuse."""
     lib = L.load()
     mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
@@ -1719,7 +1736,8 @@ def predict_quantiles(mu, v, lvn, probs, flow=None, theta=None, S=None, rowp=Non
 def predict_cdf(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None, lik=None):
     """(cdf, sf): the predictive CDF at Y per row -- the PIT values of a calibration plot -- and the upper tail 1 - cdf from
     its own sum (tgp_predict_cdf_f64); Y in the model's standardised units.  lik = lib.LIK_GAMMA: of the mixture of Gammas
-    (lvn the log shape); a Y <= 0 has cdf 0."""
+    (lvn the log shape); a Y <= 0 has cdf 0.  lik = lib.LIK_BETA: of the mixture of Betas (lvn the log precision); a Y <= 0 has
+    cdf 0 and a Y >= 1 has sf 0."""
     lib = L.load()
     mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
     theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")

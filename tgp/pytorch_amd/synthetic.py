@@ -142,6 +142,27 @@ def synthetic_claims(seed=0):
     return X, Y.astype(np.float64).reshape(-1, 1)
 
 
+# proportion stand-in: (rows, inputs), the precision of the Beta noise and how far the targets are kept from 0 and 1
+PROPORTIONS_SHAPE = (500, 2)
+PROPORTIONS_PRECISION = 10.0
+PROPORTIONS_CLIP = 1e-6
+
+
+def synthetic_proportions(seed=0):
+    """Seeded `synthetic_proportions`: X ~ N(0, 1), y ~ Beta(mu phi, (1 - mu) phi) with phi = PROPORTIONS_PRECISION and
+    mu = Phi(1.5 sin(2 x0) + 0.5 x1) -- the probit, on purpose not the logistic link of the likelihood, so that the flow has a
+    link function to learn.  y is clipped to [PROPORTIONS_CLIP, 1 - PROPORTIONS_CLIP].  Returns numpy float64 X (n, d) and
+    Y (n, 1), every y strictly inside (0, 1)."""
+    from math import erf, sqrt
+    n, d = PROPORTIONS_SHAPE
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((n, d))
+    eta = 1.5 * np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1]
+    mu = 0.5 * (1.0 + np.vectorize(erf)(eta / sqrt(2.0)))
+    Y = np.clip(rng.beta(mu * PROPORTIONS_PRECISION, (1.0 - mu) * PROPORTIONS_PRECISION), PROPORTIONS_CLIP, 1.0 - PROPORTIONS_CLIP)
+    return X, Y.astype(np.float64).reshape(-1, 1)
+
+
 # robust-regression stand-in: (rows, inputs, training rows)
 OUTLIERS_SHAPE = (1000, 2, 900)
 OUTLIERS_SHARE = 0.1
