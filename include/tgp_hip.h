@@ -77,13 +77,26 @@ extern "C" {
  *          TGP_FLOW_ARCSINH  g = a + b asinh((f-c)/d) [+ f], asinh = log(x+sqrt(x^2+1)) (flow.py:495-521)
  *          TGP_FLOW_BOXCOX   g = (sgn(f)|f|^lam - 1)/lam [+ f]; lam == 0 is taken as 1e-11 (flow.py:377-417)
  *          TGP_FLOW_INV_BOXCOX g = sgn(w)|w|^(1/lam) [+ f], w = lam f + 1 (flow.py:424-443)
+ *          (6 is unassigned and refused)
+ *          TGP_FLOW_SINH     g = a + b sinh(x) [+ f], x = (f-c)/d; dg/df = (b/d) cosh(x) [+ 1] (flow.py:566-609)
+ *          TGP_FLOW_NORMCDF  g = a + b Phi(x) [+ f], x = (f-c)/d; dg/df = (b/d) phi(x) [+ 1], phi = exp(-x^2/2)/sqrt(2 pi)
+ *                            (flow.py:1006-1037 with is_learnable=True).  Bounded unless ADD_F0 is set.
+ *          TGP_FLOW_TUKEY    g = (e^{gam f} - 1)/gam e^{h f^2/2} (Tukey g-and-h, flow.py:451-492);
+ *                            dg/df = e^{h f^2/2} (e^{gam f} + h f (e^{gam f} - 1)/gam); gam == 0 is taken as 1e-11
+ *          TGP_FLOW_EXP      g = dg/df = e^f (flow.py:283-294)
+ *          TGP_FLOW_SOFTPLUS g = log(1 + e^f), dg/df = e^f/(1 + e^f); g = f, dg/df = 1 for f > 20 (torch's threshold; flow.py:262-276)
  *   K      number of tanh steps (STEPTANH only)
  *   poff   offset of the block's parameters in `theta` (shared scalars: AFFINE {a,b}, SAL {a,b},
- *          STEPTANH {a_k,b_k,c_k,d_k}_k, ARCSINH {a,b,c,d}, BOXCOX / INV_BOXCOX {lam}) or first column in
- *          `rowp` when TGP_FLAG_PER_ROW is set (AFFINE and SAL only; the other kinds refuse it)
- *   flags  TGP_FLAG_RESTRICT  set_restrictions=True: softplus on AFFINE.a / SAL.b / ARCSINH.b and .d
- *          TGP_FLAG_ADD_F0    add_init_f0=True
+ *          STEPTANH {a_k,b_k,c_k,d_k}_k, ARCSINH / SINH / NORMCDF {a,b,c,d}, BOXCOX / INV_BOXCOX {lam}, TUKEY {gam,h},
+ *          EXP / SOFTPLUS none) or first column in `rowp` when TGP_FLAG_PER_ROW is set (AFFINE and SAL only; the other
+ *          kinds refuse it)
+ *   flags  TGP_FLAG_RESTRICT  set_restrictions=True: softplus on AFFINE.a / SAL.b / b and d of ARCSINH, SINH and NORMCDF;
+ *                             TUKEY: gam = softplus(raw) (tukey_right); TUKEY's h = softplus(raw) with or without the flag
+ *          TGP_FLAG_ADD_F0    add_init_f0=True (refused on TUKEY, EXP and SOFTPLUS: the reference never adds f there)
  *          TGP_FLAG_PER_ROW   input-dependent parameters, one value per data row (flow.py:949-965)
+ *          TGP_FLAG_NEGATE    TUKEY only, and only with TGP_FLAG_RESTRICT: gam = -softplus(raw) (tukey_left); refused elsewhere
+ * NORMCDF, EXP and SOFTPLUS do not map onto the real line: the warped likelihood (TGP_LIK_WARPED) and tgp_flow_inverse_f64
+ * refuse a program that holds one (TGP_E_UNSUPPORTED).
  */
 #define TGP_FLOW_AFFINE 0
 #define TGP_FLOW_SAL 1
@@ -91,9 +104,15 @@ extern "C" {
 #define TGP_FLOW_ARCSINH 3
 #define TGP_FLOW_BOXCOX 4
 #define TGP_FLOW_INV_BOXCOX 5
+#define TGP_FLOW_SINH 7
+#define TGP_FLOW_NORMCDF 8
+#define TGP_FLOW_TUKEY 9
+#define TGP_FLOW_EXP 10
+#define TGP_FLOW_SOFTPLUS 11
 #define TGP_FLAG_RESTRICT 1
 #define TGP_FLAG_ADD_F0 2
 #define TGP_FLAG_PER_ROW 4
+#define TGP_FLAG_NEGATE 8
 
 /* likelihood selector */
 #define TGP_LIK_GAUSS 0 /* GaussianLinearMean.expected_log_prob, likelihoods/GaussianLinearMean.py:60-87       */

@@ -58,8 +58,12 @@ static int check_flow_points(const tgp_model* m, bool counts, const double* f, i
 
 // one block of a program against the `limit` parameters of the vector it indexes (`per_row_ok` false: shared parameters only)
 static int check_block(int kind, int K, int poff, int flags, int limit, bool per_row_ok = true) {
-  if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_INV_BOXCOX) return -1;
+  if (kind < TGP_FLOW_AFFINE || kind > TGP_FLOW_SOFTPLUS || kind == 6) return -1;   // (6 is unassigned)
   if (kind == TGP_FLOW_STEPTANH && K < 1) return -1;
+  // TGP_FLAG_NEGATE: the left-skewed TUKEY block's gam = -softplus(raw), nothing else
+  if ((flags & TGP_FLAG_NEGATE) && (kind != TGP_FLOW_TUKEY || !(flags & TGP_FLAG_RESTRICT))) return -1;
+  // the reference never adds f to a Tukey, exp or softplus block
+  if ((flags & TGP_FLAG_ADD_F0) && kind >= TGP_FLOW_TUKEY) return -1;
   if ((flags & TGP_FLAG_PER_ROW) && !per_row_ok) return TGP_E_UNSUPPORTED;
   // per-row parameters: AFFINE and SAL only (the reference has no input-dependent tanh-step, arcsinh or Box-Cox flow)
   if (kind >= TGP_FLOW_STEPTANH && (flags & TGP_FLAG_PER_ROW)) return -1;
@@ -82,6 +86,21 @@ static int make_prog(const tgp_model* m, bool flow, FlowProg& fp) {
   }
   fp.nslots = flow_slots(fp.blk, fp.nblk);
   return 0;
+}
+
+// A warp of the targets, and anything that is inverted, must map onto the real line: NORMCDF, EXP and SOFTPLUS do not (true:
+// refused, tgp_last_error() names the entry and the kind)
+static bool refuse_not_onto(const FlowProg& fp, const char* entry) {
+  for (int b = 0; b < fp.nblk; ++b) {
+    const int kind = fp.blk[4 * b];
+    if (kind == TGP_FLOW_NORMCDF || kind == TGP_FLOW_EXP || kind == TGP_FLOW_SOFTPLUS) {
+      set_error_text("%s: block %d has flow kind %d (%s), which does not map onto the real line: it cannot warp targets or be "
+                     "inverted", entry, b, kind,
+                     kind == TGP_FLOW_NORMCDF ? "TGP_FLOW_NORMCDF" : (kind == TGP_FLOW_EXP ? "TGP_FLOW_EXP" : "TGP_FLOW_SOFTPLUS"));
+      return true;
+    }
+  }
+  return false;
 }
 
 static const FlowProg no_flow{};   // the empty program of the q(f) entries
@@ -252,6 +271,7 @@ static int elbo_step_warped(const tgp_model* model, const double* X, const doubl
   FlowProg fp;
   tgp_model mw;
   if (int rc = flow_args(model, true, fp, mw)) return rc;
+  if (refuse_not_onto(fp, "tgp_elbo_step_f64 (TGP_LIK_WARPED)")) return TGP_E_UNSUPPORTED;
   // every argument of the Gaussian step has been checked above: nothing is enqueued for a call that will be refused.
   // An empty program is the Gaussian step itself on Y: t = Y, log T' = 0, no theta -- neither pass is launched.
   const bool warp = fp.nblk > 0;
@@ -961,6 +981,7 @@ int tgp_ell_warp_f64(const tgp_model* model, const double* Y, const double* mu, 
   FlowProg fp;
   tgp_model md;
   if (int rc = flow_args(model, true, fp, md)) return rc;
+  if (refuse_not_onto(fp, "tgp_ell_warp_f64")) return TGP_E_UNSUPPORTED;
   return launch_ell_warp(md, fp, TGP_WARP_FULL, Y, mu, v, out, g_mu, g_v, g_theta, t_out, static_cast<double*>(workspace),
                          static_cast<hipStream_t>(stream));
 }
@@ -1046,6 +1067,7 @@ int tgp_flow_inverse_f64(const tgp_model* model, const double* t, int32_t S, int
   FlowProg fp;
   tgp_model md;
   if (int rc = flow_args(model, true, fp, md)) return rc;
+  if (refuse_not_onto(fp, "tgp_flow_inverse_f64")) return TGP_E_UNSUPPORTED;
   return launch_flow_inverse(md, fp, t, S, N, rowp, x, status, static_cast<hipStream_t>(stream));
 }
 
@@ -1061,6 +1083,7 @@ int tgp_predict_f64(const tgp_model* model, const double* mu, const double* v, c
     if (!v) return -3;
     FlowProg fpw;
     if (int rc = flow_args(&mw, true, fpw, mw)) return rc;
+    if (refuse_not_onto(fpw, "tgp_predict_f64 (TGP_LIK_WARPED)")) return TGP_E_UNSUPPORTED;
     return launch_predict_warp(mw, fpw, mu, v, Y, Y_std, m1, m2, logp, static_cast<hipStream_t>(stream));
   }
   const bool flowed = lik_is_quadrature(model->lik);

@@ -640,36 +640,78 @@ struct FlowProg {
 };
 
 // Per-kind tables: the ONE source of "parameters per block", "which parameter goes through softplus" and "store-mode stack
-// slots per block" for the host (make_prog) and every kernel.  X = the extended kind set (ARCSINH, BOXCOX, INV_BOXCOX) is
-// compiled in; X = false is the original set (AFFINE, SAL, STEPTANH), for the kernels that never see the new kinds.
-template <bool X = true>
+// slots per block" for the host (make_prog) and every kernel.  The template argument X says which kinds are compiled in:
+//   TGP_XK_NONE (0, false)  the original set (AFFINE, SAL, STEPTANH), for the kernels that never see another kind
+//   TGP_XK_ALL  (1, true)   every kind: the host, and every kernel that takes a `bool X`
+//   TGP_XK_OLD  (2)         the original set and ARCSINH, BOXCOX, INV_BOXCOX, as they compiled before SINH .. SOFTPLUS existed:
+//                           the TGP_FLOWX instantiations of k_rows, k_rows4 and k_ell_quad, whose registers the later kinds must
+//                           not touch (18 of them gained scratch with the new kinds compiled in)
+// Every test of a kind past INV_BOXCOX is behind `X == TGP_XK_ALL` at compile time.
+#define TGP_XK_NONE 0
+#define TGP_XK_ALL 1
+#define TGP_XK_OLD 2
+// "the four-parameter family": g = a + b h((f - c)/d) [+ f] with h = asinh (ARCSINH), sinh (SINH) or Phi (NORMCDF).  One
+// parameter layout {a, b, c, d}, one restriction rule (softplus on b and d) and one reverse branch for all three: only the
+// forward (h and h') differs (flowx_block_n).  Kind 6 is unassigned: not a member of anything, refused by the API.
+template <int X = TGP_XK_ALL>
+__host__ __device__ __forceinline__ bool flow_kind_abcd(int kind) {
+  if (X == TGP_XK_ALL) return kind == TGP_FLOW_ARCSINH || kind == TGP_FLOW_SINH || kind == TGP_FLOW_NORMCDF;
+  return kind == TGP_FLOW_ARCSINH;
+}
+template <int X = TGP_XK_ALL>
 __host__ __device__ __forceinline__ int flow_block_params(int kind, int K) {
-  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH ? 4 : 1;   // {a, b, c, d} / {lam}
+  if (X == TGP_XK_ALL && kind > TGP_FLOW_INV_BOXCOX && !flow_kind_abcd<X>(kind))
+    return kind == TGP_FLOW_TUKEY ? 2 : 0;                                          // {gamma, h} / EXP, SOFTPLUS: none
+  if (X && kind >= TGP_FLOW_ARCSINH) return flow_kind_abcd<X>(kind) ? 4 : 1;        // {a, b, c, d} / {lam}
   return kind == TGP_FLOW_STEPTANH ? 4 * K : 2;
 }
 // parameter j of the block: softplus'ed?  STEPTANH b_k, d_k always (TanhFlow set_restrictions=True, flow.py:1075); with
-// TGP_FLAG_RESTRICT AFFINE.a, SAL.b, ARCSINH.b and .d (flow.py:335, 947, 514-516); BOXCOX lam never (flow.py:396-401)
-template <bool X = true>
+// TGP_FLAG_RESTRICT AFFINE.a, SAL.b, b and d of the four-parameter family (flow.py:335, 947, 514-516, 602-604, 1029-1031) and
+// TUKEY.gamma (flow.py:481, 490); TUKEY.h always (flow.py:469); BOXCOX lam never (flow.py:396-401)
+template <int X = TGP_XK_ALL>
 __host__ __device__ __forceinline__ bool flow_param_restricted(int kind, int flags, int j) {
-  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH && (flags & TGP_FLAG_RESTRICT) && (j & 1);
+  if (X == TGP_XK_ALL && kind == TGP_FLOW_TUKEY) return j == 1 || (flags & TGP_FLAG_RESTRICT);
+  if (X && kind >= TGP_FLOW_ARCSINH) return flow_kind_abcd<X>(kind) && (flags & TGP_FLAG_RESTRICT) && (j & 1);
   if (kind == TGP_FLOW_STEPTANH) return j & 1;
   return (flags & TGP_FLAG_RESTRICT) && j == (kind == TGP_FLOW_AFFINE ? 0 : 1);
 }
+// ... and is the softplus'ed value negated (tp = -softplus(raw), tg = -sigmoid(raw))?  TUKEY.gamma under TGP_FLAG_NEGATE
+// (TukeyLeftFlow, flow.py:490); the API admits the flag on no other kind, and only together with TGP_FLAG_RESTRICT
+template <int X = TGP_XK_ALL>
+__host__ __device__ __forceinline__ bool flow_param_negated(int kind, int flags, int j) {
+  return X == TGP_XK_ALL && kind == TGP_FLOW_TUKEY && j == 0 && (flags & TGP_FLAG_NEGATE);
+}
 // store-mode stack slots of a block (see flow_forward_store)
-template <bool X = true>
+template <int X = TGP_XK_ALL>
 __host__ __device__ __forceinline__ int flow_block_slots(int kind, int K) {
-  if (X && kind >= TGP_FLOW_ARCSINH) return kind == TGP_FLOW_ARCSINH ? 3 : 2;
+  if (X == TGP_XK_ALL && kind >= TGP_FLOW_TUKEY) return kind == TGP_FLOW_TUKEY ? 3 : 1;   // {dg/dgam, dg/dh, g'} / EXP, SOFTPLUS {g'}
+  if (X && kind >= TGP_FLOW_ARCSINH) return flow_kind_abcd<X>(kind) ? 3 : 2;
   return kind == TGP_FLOW_AFFINE ? 1 : (kind == TGP_FLOW_SAL ? 3 : 1 + K);
 }
-// Template-argument bit of the kernels that have an extended-kind instantiation (k_rows MODE, k_rows4 NW, k_ell_quad NB):
-// set = the flow sweeps are compiled with X = true.  (A bit of an existing argument, not a new argument, so that the
-// instantiations of the original kinds keep their symbols.)
+// Template-argument bits of the kernels that have extended-kind instantiations (k_rows MODE, k_rows4 NW, k_ell_quad NB).
+// (Bits of an existing argument, not a new argument, so that the instantiations of the original kinds keep their symbols.)
+//   TGP_FLOWX   the flow sweeps are compiled with X = TGP_XK_OLD: ARCSINH, BOXCOX, INV_BOXCOX
+//   TGP_FLOWX2  ... with X = TGP_XK_ALL: SINH, NORMCDF, TUKEY, EXP, SOFTPLUS as well.  Its own instantiations (and, for the row
+//               kernels, its own translation units): the TGP_FLOWX ones compile as they did before these kinds existed.  (Bit 7:
+//               bits 5-6 of k_rows' MODEX carry TGP_ROWS_KT.)
 #define TGP_FLOWX 16
+#define TGP_FLOWX2 128
+// the X of a kernel from its template argument's bits
+#define TGP_XK_OF(bits) (((bits) & TGP_FLOWX2) ? TGP_XK_ALL : (((bits) & TGP_FLOWX) ? TGP_XK_OLD : TGP_XK_NONE))
 // does a program need the extended kind set?  (the host picks the X instantiations of the flow kernels on this)
 __host__ __device__ inline bool flow_prog_extended(const int32_t* prog, int nblk) {
   for (int b = 0; b < nblk; ++b)
     if (prog[4 * b] >= TGP_FLOW_ARCSINH) return true;
   return false;
+}
+// ... and which bit: 0, TGP_FLOWX (no kind past INV_BOXCOX) or TGP_FLOWX2
+__host__ __device__ inline int flow_prog_xbit(const int32_t* prog, int nblk) {
+  int bit = 0;
+  for (int b = 0; b < nblk; ++b) {
+    if (prog[4 * b] > TGP_FLOW_INV_BOXCOX) return TGP_FLOWX2;
+    if (prog[4 * b] >= TGP_FLOW_ARCSINH) bit = TGP_FLOWX;
+  }
+  return bit;
 }
 
 struct FlowDev {
@@ -697,7 +739,7 @@ __device__ __forceinline__ double flow_rcp_param(const FlowDev& F, int i) {
 // `ti` (optional): 1 / tp[i] for every shared parameter, so that a step-tanh step takes 1 / softplus(d_k) from the table instead of
 // running a reciprocal chain per step and sweep
 // X: the extended kind set (flow_block_params)
-template <bool X>
+template <int X>
 __device__ inline void flow_params_lds(const double* theta, const FlowProg& fp, double* tp, double* tg, double* ti = nullptr) {
   for (int b = threadIdx.x; b < fp.nblk; b += blockDim.x) {
     const int kind = fp.blk[4 * b], K = fp.blk[4 * b + 1], poff = fp.blk[4 * b + 2], flags = fp.blk[4 * b + 3];
@@ -706,9 +748,10 @@ __device__ inline void flow_params_lds(const double* theta, const FlowProg& fp, 
     for (int j = 0; j < np; ++j) {
       const double x = theta[poff + j];
       const bool res = flow_param_restricted<X>(kind, flags, j);
-      const double tv = res ? softplus_d(x) : x;
+      const double sg = flow_param_negated<X>(kind, flags, j) ? -1.0 : 1.0;
+      const double tv = res ? sg * softplus_d(x) : x;
       tp[poff + j] = tv;
-      tg[poff + j] = res ? sigmoid_d(x) : 1.0;
+      tg[poff + j] = res ? sg * sigmoid_d(x) : 1.0;
       if (ti != nullptr) ti[poff + j] = rcp_fast(tv);
     }
   }
@@ -740,11 +783,91 @@ __device__ __forceinline__ double flow_param(const FlowDev& F, const double* rp,
 //               d0 = dg/dlam = sgn(f) p log|f|/lam - (sgn(f) p - 1)/lam^2
 //   INV_BOXCOX  w = lam f + 1, q = |w|^(1/lam):  g = sgn(w) q, dg/df = q/|w|,  d0 = dg/dlam = sgn(w) q (f/(lam w) - log|w|/lam^2)
 // |f|^lam is exp_fast(lam log_fast|f|); a lam of exactly 0 is taken as 1e-11 with d(used)/d(raw) = 1 (flow.py:396-401).
-template <int NB>
+//   SINH        x = (f - c)/d:  d0 = sinh x, d1 = x, d2 = (b/d) cosh x     } the (d0, d1, d2) of ARCSINH: the four-parameter family
+//   NORMCDF     x = (f - c)/d:  d0 = Phi(x), d1 = x, d2 = (b/d) phi(x)     } shares one reverse branch (flow_kind_abcd)
+//               sinh and cosh from ONE exp_fast of |x| and its reciprocal; Phi through erfc on the side where it is small
+//               (q_eval's rule), phi(x) = exp(-x^2/2)/sqrt(2 pi)
+//   TUKEY       u = expm1(gam f)/gam, E = exp(h f^2/2):  g = u E, dg/df = E (e^{gam f} + h f u),
+//               d0 = dg/dgam = E (f e^{gam f} - u)/gam, d1 = dg/dh = g f^2/2, d2 = dg/df; a gam of exactly 0 is taken as 1e-11
+//   EXP         g = dg/df = e^f;   SOFTPLUS  g = log(1 + e^f), dg/df = e^f/(1 + e^f); g = f, dg/df = 1 for f > 20 (torch's threshold)
+// EV (the evaluation sweep, flow_forward_n): an exponent past the float64 range gives +-inf, as SAL does there; the training
+// sweeps keep exp_fast's clamp to the finite range.
+#define TGP_INV_SQRT_2PI 0.39894228040143267794
+template <int NB, bool EV = false, int X = TGP_XK_ALL>
 __device__ __forceinline__ void flowx_block_n(const FlowDev& F, int kind, int poff, int flags, double (&f)[NB], double (&gp)[NB],
                                               double (&d0)[NB], double (&d1)[NB], double (&d2)[NB]) {
   const bool addf = flags & TGP_FLAG_ADD_F0;
-  if (kind == TGP_FLOW_ARCSINH) {
+  if (X == TGP_XK_ALL && (kind == TGP_FLOW_SINH || kind == TGP_FLOW_NORMCDF)) {
+    const double a = F.tp[poff], b = F.tp[poff + 1], c = F.tp[poff + 2], id = flow_rcp_param(F, poff + 3);
+    double hp[NB];
+    TGP_EACH(u, NB) d1[u] = (f[u] - c) * id;
+    if (kind == TGP_FLOW_SINH) {
+      double e[NB], ei[NB];
+      TGP_EACH(u, NB) e[u] = fabs(d1[u]);
+      exp_fast_n<NB>(e);
+      if constexpr (EV) { TGP_EACH(u, NB) e[u] = fabs(d1[u]) > 709.78 ? INFINITY : e[u]; }
+      TGP_EACH(u, NB) ei[u] = e[u];
+      rcp_fast_n<NB>(ei);
+      if constexpr (EV) { TGP_EACH(u, NB) ei[u] = fabs(d1[u]) > 709.78 ? 0.0 : ei[u]; }
+      TGP_EACH(u, NB) {
+        d0[u] = copysign(0.5 * (e[u] - ei[u]), d1[u]);
+        hp[u] = 0.5 * (e[u] + ei[u]);
+      }
+    } else {
+      TGP_EACH(u, NB) hp[u] = -0.5 * d1[u] * d1[u];
+      exp_fast_n<NB>(hp);
+      TGP_EACH(u, NB) {
+        const double small = 0.5 * erfc(fabs(d1[u]) * 0.70710678118654752440);
+        d0[u] = d1[u] < 0.0 ? small : 1.0 - small;
+        hp[u] *= TGP_INV_SQRT_2PI;
+      }
+    }
+    TGP_EACH(u, NB) {
+      d2[u] = b * id * hp[u];
+      const double g = a + b * d0[u];
+      gp[u] = addf ? d2[u] + 1.0 : d2[u];
+      f[u] = addf ? g + f[u] : g;
+    }
+  } else if (X == TGP_XK_ALL && kind == TGP_FLOW_TUKEY) {
+    double gam = F.tp[poff];
+    const double h = F.tp[poff + 1];
+    if (gam == 0.0) gam = 1e-11;
+    const double ig = rcp_fast(gam);
+    double E[NB];
+    TGP_EACH(u, NB) E[u] = 0.5 * h * f[u] * f[u];
+    exp_fast_n<NB>(E);
+    if constexpr (EV) { TGP_EACH(u, NB) E[u] = 0.5 * h * f[u] * f[u] > 709.78 ? INFINITY : E[u]; }
+    TGP_EACH(u, NB) {
+      const double em = expm1(gam * f[u]), eg = em + 1.0, uu = em * ig;
+      const double g = uu * E[u];
+      d0[u] = E[u] * (f[u] * eg - uu) * ig;
+      d1[u] = 0.5 * g * f[u] * f[u];
+      d2[u] = E[u] * fma(h * f[u], uu, eg);
+      gp[u] = d2[u];
+      f[u] = g;
+    }
+  } else if (X == TGP_XK_ALL && kind >= TGP_FLOW_EXP) {
+    double e[NB];
+    TGP_EACH(u, NB) e[u] = f[u];
+    exp_fast_n<NB>(e);
+    if (kind == TGP_FLOW_EXP) {
+      if constexpr (EV) { TGP_EACH(u, NB) e[u] = f[u] > 709.78 ? INFINITY : e[u]; }
+      TGP_EACH(u, NB) { gp[u] = e[u]; f[u] = e[u]; }
+    } else {
+      // softplus_d's form, stage by stage: log1p(e) = log(u) e/(u - 1), u = 1 + e; u == 1: e itself
+      double lu[NB], r1[NB], ru[NB];
+      TGP_EACH(u, NB) { lu[u] = 1.0 + e[u]; ru[u] = lu[u]; r1[u] = lu[u] == 1.0 ? 1.0 : lu[u] - 1.0; }
+      log_fast_n<NB>(lu);
+      rcp_fast_n<NB>(r1);
+      rcp_fast_n<NB>(ru);
+      TGP_EACH(u, NB) {
+        const bool lin = f[u] > 20.0;
+        const double sp = 1.0 + e[u] == 1.0 ? e[u] : lu[u] * (e[u] * r1[u]);
+        gp[u] = lin ? 1.0 : e[u] * ru[u];
+        f[u] = lin ? f[u] : sp;
+      }
+    }
+  } else if (kind == TGP_FLOW_ARCSINH) {
     const double a = F.tp[poff], b = F.tp[poff + 1], c = F.tp[poff + 2], id = flow_rcp_param(F, poff + 3);
     double q1[NB], is[NB], s[NB];
     TGP_EACH(u, NB) d1[u] = (f[u] - c) * id;
@@ -838,7 +961,7 @@ __device__ inline double flow_forward(const FlowDev& F, double f, const double* 
 // Unlike the training sweeps (exp clamped to the finite range), an exponent past the float64 range gives +inf here: the
 // reference's evaluation pushes every node through the naive sinh(b asinh f - a) and reports the inf.
 // X: the extended kind set is compiled in (flowx_block_n).
-template <int NB, bool DER, bool X = false>
+template <int NB, bool DER, int X = TGP_XK_NONE>
 __device__ inline void flow_forward_n(const FlowDev& F, double (&f)[NB], const double* const (&rp)[NB], double (&der)[NB]) {
   TGP_EACH(u, NB) der[u] = 1.0;
   for (int b = 0; b < F.nblk; ++b) {
@@ -847,7 +970,7 @@ __device__ inline void flow_forward_n(const FlowDev& F, double (&f)[NB], const d
     if constexpr (X) {
       if (kind >= TGP_FLOW_ARCSINH) {
         double gp[NB], d0[NB], d1[NB], d2[NB];
-        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        flowx_block_n<NB, true, X>(F, kind, poff, flags, f, gp, d0, d1, d2);
         if (DER) { TGP_EACH(u, NB) der[u] *= gp[u]; }
         continue;
       }
@@ -917,7 +1040,8 @@ __device__ inline void flow_forward_n(const FlowDev& F, double (&f)[NB], const d
 // "store" evaluation: NB quadrature nodes in flight per lane (independent dependency chains for the
 // single-wave-per-SIMD row kernel), forward keeps what the reverse sweep needs so that the reverse sweep
 // contains no transcendental.  Stack slots per block (flow_block_slots): AFFINE 1 {f_in}; SAL 3 {u, cosh t, g'}; STEPTANH 1+K
-// {f_in, tanh_k}; ARCSINH 3 {asinh x, x, b/(d s)}; BOXCOX and INV_BOXCOX 2 {dg/dlam, g'} (flowx_block_n).  Slot s of node u
+// {f_in, tanh_k}; ARCSINH, SINH, NORMCDF 3 {h(x), x, (b/d) h'(x)}; BOXCOX and INV_BOXCOX 2 {dg/dlam, g'}; TUKEY 3 {dg/dgam,
+// dg/dh, g'}; EXP and SOFTPLUS 1 {g'} (flowx_block_n).  Slot s of node u
 // lives at stack[(s*NB + u) * sstride].  The kinds past STEPTANH exist only in the X = true instantiations.
 // sinh/cosh/tanh are formed from ONE exp (+1 division): absolute error ~1e-16 * max(1, cosh), which is what the
 // residual y - G(f) needs; asinh keeps the reference's log form.
@@ -932,7 +1056,7 @@ __host__ __device__ inline int flow_slots(const int32_t* prog, int nblk) {
 // rpn[u], an LDS table of the row's TRANSFORMED parameters the caller staged -- entry 2 c = value of column c (softplus
 // already applied where the block restricts it), entry 2 c + 1 = d(value)/d(raw) -- so the sweeps neither wait for global
 // memory nor evaluate a softplus per node.  Supported for SAL blocks (the per-row flows of this package); `rp` is unused.
-template <int NB, bool PN = false, bool X = false>
+template <int NB, bool PN = false, int X = TGP_XK_NONE>
 __device__ inline void flow_forward_store(const FlowDev& F, double (&f)[NB], const double* __restrict__ rp,
                                           double* stack, int sstride, const double* const* rpn = nullptr) {
   int sl = 0;
@@ -944,20 +1068,23 @@ __device__ inline void flow_forward_store(const FlowDev& F, double (&f)[NB], con
     if constexpr (X) {
       if (kind >= TGP_FLOW_ARCSINH) {
         double gp[NB], d0[NB], d1[NB], d2[NB];
-        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
-        if (kind == TGP_FLOW_ARCSINH) {
+        flowx_block_n<NB, false, X>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        const int ns = flow_block_slots<X>(kind, K);
+        if (ns == 3) {          // the four-parameter family, TUKEY
           TGP_EACH(u, NB) {
             stack[((sl + 0) * NB + u) * sstride] = d0[u];
             stack[((sl + 1) * NB + u) * sstride] = d1[u];
             stack[((sl + 2) * NB + u) * sstride] = d2[u];
           }
-        } else {
+        } else if (ns == 2) {   // BOXCOX, INV_BOXCOX
           TGP_EACH(u, NB) {
             stack[((sl + 0) * NB + u) * sstride] = d0[u];
             stack[((sl + 1) * NB + u) * sstride] = gp[u];
           }
+        } else {                // EXP, SOFTPLUS
+          TGP_EACH(u, NB) stack[(sl * NB + u) * sstride] = gp[u];
         }
-        sl += flow_block_slots(kind, K);
+        sl += ns;
         continue;
       }
     }
@@ -1099,7 +1226,7 @@ __device__ __forceinline__ void flow_park(double* gst, int sstride, int* ploc, i
   const int ln = threadIdx.x & 63;
   if (ln < NP) ploc[poff + ln] = slot * NB + ln;
 }
-template <int NB, int RED = 0, bool PN = false, bool X = false>
+template <int NB, int RED = 0, bool PN = false, int X = TGP_XK_NONE>
 __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], const double* __restrict__ rp,
                                            const double* stack, int sstride, int nslots, double* accq, int qstride,
                                            bool qlead, double* accr, int rstride, const double* const* rpn = nullptr,
@@ -1113,7 +1240,7 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
     nx = flow_blk(F.prog, b > 0 ? b - 1 : 0);
     const bool pr = flags & TGP_FLAG_PER_ROW;
     if constexpr (X) {
-      if (kind == TGP_FLOW_ARCSINH) {
+      if (flow_kind_abcd<X>(kind)) {   // the four-parameter family: slots {h(x), x, (b/d) h'(x)}
         sl -= 3;
         double as[NB], xv[NB], gq[NB];
         TGP_EACH(u, NB) {
@@ -1147,6 +1274,40 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
             lds_acc(accq + (poff + 3) * qstride, p3);
           }
         }
+        continue;
+      }
+      if (X == TGP_XK_ALL && kind == TGP_FLOW_TUKEY) {   // slots {dg/dgam, dg/dh, g'}
+        sl -= 3;
+        double dg[NB], dh[NB], gp[NB];
+        TGP_EACH(u, NB) {
+          dg[u] = stack[((sl + 0) * NB + u) * sstride];
+          dh[u] = stack[((sl + 1) * NB + u) * sstride];
+          gp[u] = stack[((sl + 2) * NB + u) * sstride];
+        }
+        const double g0 = F.tg[poff], g1 = F.tg[poff + 1];
+        double p0 = 0.0, p1 = 0.0;
+        TGP_EACH(u, NB) {
+          p0 += c[u] * dg[u];
+          p1 += c[u] * dh[u];
+          c[u] *= gp[u];
+        }
+        p0 *= g0; p1 *= g1;
+        if constexpr (PN) {
+          const double pv[2] = {p0, p1};
+          flow_park<NB>(gst, sstride, ploc, sl, poff, pv);
+        } else if constexpr (RED == 2) {
+          const int ln = threadIdx.x & 63;
+          const double vv = wave_sum2(p0, p1, ln);
+          if ((ln & 31) == 0) lds_acc(accq + (poff + (ln >> 5)) * qstride, vv);
+        } else {
+          p0 = flow_red<RED>(p0); p1 = flow_red<RED>(p1);
+          if (qlead) { lds_acc(accq + (poff + 0) * qstride, p0); lds_acc(accq + (poff + 1) * qstride, p1); }
+        }
+        continue;
+      }
+      if (X == TGP_XK_ALL && kind >= TGP_FLOW_EXP) {     // EXP, SOFTPLUS: slot {g'}, no parameter
+        sl -= 1;
+        TGP_EACH(u, NB) c[u] *= stack[(sl * NB + u) * sstride];
         continue;
       }
       if (kind >= TGP_FLOW_BOXCOX) {
@@ -1309,7 +1470,7 @@ __device__ inline void flow_backward_store(const FlowDev& F, double (&c)[NB], co
 // Shared-parameter partials: summed over the NB nodes in registers, over the wave by shuffles (fixed tree), added by
 // lane 0 into the wave's own accumulator row accw[param] -- no atomics, fixed order.
 // ---------------------------------------------------------------------------------------------------
-template <int NB, bool X = false>
+template <int NB, int X = TGP_XK_NONE>
 __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], const double* __restrict__ rp, double* stack,
                                          int sstride) {
   for (int b = 0; b < F.nblk; ++b) {
@@ -1320,7 +1481,7 @@ __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], cons
     if constexpr (X) {
       if (kind >= TGP_FLOW_ARCSINH) {
         double gp[NB], d0[NB], d1[NB], d2[NB];
-        flowx_block_n<NB>(F, kind, poff, flags, f, gp, d0, d1, d2);
+        flowx_block_n<NB, false, X>(F, kind, poff, flags, f, gp, d0, d1, d2);
         continue;
       }
     }
@@ -1368,7 +1529,7 @@ __device__ inline void flow_forward_ckpt(const FlowDev& F, double (&f)[NB], cons
 }
 
 // c[u] = d(objective)/dG on entry, d(objective)/df0 on exit.  All lanes of the wave must call this together.
-template <int NB, bool X = false>
+template <int NB, int X = TGP_XK_NONE>
 __device__ inline void flow_backward_ckpt(const FlowDev& F, double (&c)[NB], const double* __restrict__ rp, const double* stack,
                                           int sstride, double* accw, int lane, double* accr, int rstride) {
   for (int b = F.nblk - 1; b >= 0; --b) {
@@ -1381,8 +1542,8 @@ __device__ inline void flow_backward_ckpt(const FlowDev& F, double (&c)[NB], con
       if (kind >= TGP_FLOW_ARCSINH) {
         // recompute the block from its input (checkpoint mode), then the partials as in flow_backward_store
         double gp[NB], d0[NB], d1[NB], d2[NB];
-        flowx_block_n<NB>(F, kind, poff, flags, fin, gp, d0, d1, d2);
-        if (kind == TGP_FLOW_ARCSINH) {
+        flowx_block_n<NB, false, X>(F, kind, poff, flags, fin, gp, d0, d1, d2);
+        if (flow_kind_abcd<X>(kind)) {
           double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
           TGP_EACH(u, NB) {
             const double cg = c[u] * d2[u];
@@ -1394,6 +1555,17 @@ __device__ inline void flow_backward_ckpt(const FlowDev& F, double (&c)[NB], con
           }
           const double vv = wave_sum4(p0, p1 * F.tg[poff + 1], p2, p3 * F.tg[poff + 3], lane);
           if ((lane & 15) == 0) accw[poff + (lane >> 4)] += vv;
+        } else if (X == TGP_XK_ALL && kind == TGP_FLOW_TUKEY) {
+          double p0 = 0.0, p1 = 0.0;
+          TGP_EACH(u, NB) {
+            p0 += c[u] * d0[u];
+            p1 += c[u] * d1[u];
+            c[u] *= gp[u];
+          }
+          const double vv = wave_sum2(p0 * F.tg[poff], p1 * F.tg[poff + 1], lane);
+          if ((lane & 31) == 0) accw[poff + (lane >> 5)] += vv;
+        } else if (X == TGP_XK_ALL && kind >= TGP_FLOW_EXP) {
+          TGP_EACH(u, NB) c[u] *= gp[u];
         } else {
           double pl = 0.0;
           TGP_EACH(u, NB) {

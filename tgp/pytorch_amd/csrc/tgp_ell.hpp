@@ -204,7 +204,7 @@ __device__ __forceinline__ auto ell_row_consts(const K0& k0, const double* __res
 
 // LPR lanes share a data row (64 / LPR rows per wave: row = lane % RW, node group = lane / RW), NB nodes in flight per
 // lane.  The launcher picks LPR from N so that a chunk of ~16k rows still yields ~1000 workgroups.
-// NBX = NB | TGP_FLOWX: the flow sweeps know the extended kind set (X; see k_rows)
+// NBX = NB | TGP_FLOWX or TGP_FLOWX2: the flow sweeps know the extended kind set (X; see k_rows)
 template <class Lik, int LPR, int NBX>
 __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, const double* __restrict__ Y,
                                                    const double* __restrict__ mu, const double* __restrict__ v,
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void k_ell_quad(tgp_model md, FlowProg fp, con
                                                    double* __restrict__ g_mu, double* __restrict__ g_v,
                                                    double* __restrict__ g_rowp) {
   constexpr int NB = NBX & (TGP_FLOWX - 1);
-  constexpr bool X = NBX & TGP_FLOWX;
+  constexpr int X = TGP_XK_OF(NBX);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   double* sm = reinterpret_cast<double*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = md.P, RP = md.RP;
@@ -535,13 +535,15 @@ static int predict_launch(const tgp_model& md, const FlowProg& fp, const double*
   return 0;
 }
 
-// one launch of k_ell_quad<Lik, LPR, NB> or, for a program with a kind past STEPTANH (ext), k_ell_quad<Lik, LPR, NB | TGP_FLOWX>;
-// each of the two kernel functions has its own dynamic-LDS high-water mark (ensure_lds)
+// one launch of k_ell_quad<Lik, LPR, NB> or, for a program with a kind past STEPTANH, k_ell_quad<Lik, LPR, NB | ext>, ext =
+// flow_prog_xbit: TGP_FLOWX, or TGP_FLOWX2 with a kind past INV_BOXCOX; each of the three kernel functions has its own
+// dynamic-LDS high-water mark (ensure_lds)
 template <class Lik, int LPR, int NB, class... Args>
-static int ell_launch_one(bool ext, int nb, size_t lds, hipStream_t st, Args... args) {
-  static size_t cur[2] = {48 * 1024, 48 * 1024};
-  auto* const kern = ext ? k_ell_quad<Lik, LPR, NB | TGP_FLOWX> : k_ell_quad<Lik, LPR, NB>;
-  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+static int ell_launch_one(int ext, int nb, size_t lds, hipStream_t st, Args... args) {
+  static size_t cur[3] = {48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = ext == TGP_FLOWX2 ? k_ell_quad<Lik, LPR, NB | TGP_FLOWX2>
+                                       : (ext ? k_ell_quad<Lik, LPR, NB | TGP_FLOWX> : k_ell_quad<Lik, LPR, NB>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext == TGP_FLOWX2 ? 2 : (ext ? 1 : 0)])) return rc;
   hipLaunchKernelGGL(kern, dim3(nb), dim3(256), lds, st, args...);
   LAUNCH_CHECK();
   return 0;
@@ -574,7 +576,7 @@ static int ell_launch(int LPR, int NB, Args... args) {
 }
 // ... under the signature of a LikRow
 template <class Lik>
-static int ell_launch_row(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+static int ell_launch_row(int LPR, int NB, int ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                           const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu,
                           double* g_v, double* g_rowp) {
   return ell_launch<Lik>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);

@@ -137,7 +137,7 @@ inline bool known_kernel(int kernel) {
 
 // What the host asks about a likelihood, one row per TGP_LIK_* id (the table: tgp_lik.hip).  The two launchers take the same
 // arguments for every row -- ell: ell_plan's LPR, NB, workgroups and LDS, `ext`: the program holds a kind past STEPTANH.
-using EllLaunch = int(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+using EllLaunch = int(int LPR, int NB, int ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                       const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu,
                       double* g_v, double* g_rowp);
 using PredictLaunch = int(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,

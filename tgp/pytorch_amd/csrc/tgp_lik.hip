@@ -317,7 +317,7 @@ int launch_ell_quad(const tgp_model& md, const FlowProg& fp, const double* Y, co
   if (int rc = ell_plan(md, fp, &LPR, &NB, &lds)) return rc;
   const int rows = 256 / LPR;
   const int nb = (md.N + rows - 1) / rows;
-  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  const int ext = flow_prog_xbit(fp.blk, fp.nblk);   // 0, TGP_FLOWX or TGP_FLOWX2: which k_ell_quad
   const LikRow* row = lik_row(md.lik);
   if (!row) return -1;
   if (int rc = row->ell(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, ws, g_mu, g_v, g_rowp)) return rc;

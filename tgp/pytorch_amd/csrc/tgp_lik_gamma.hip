@@ -77,7 +77,7 @@ struct PredGamma : PredSweepOnly {
   }
 };
 
-int ell_launch_gamma(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+int ell_launch_gamma(int LPR, int NB, int ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                      const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
                      double* g_rowp) {
   return ell_launch_row<EllGamma>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);

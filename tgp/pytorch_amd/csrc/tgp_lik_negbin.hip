@@ -47,7 +47,7 @@ struct EllNegBin {
   static __device__ __forceinline__ double plus_log_p(double a, const NegBinNode& t, const NegBinConst& k) { return a + log_p(t, k); }
 };
 
-int ell_launch_negbin(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+int ell_launch_negbin(int LPR, int NB, int ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                       const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
                       double* g_rowp) {
   return ell_launch_row<EllNegBin>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);

@@ -114,7 +114,7 @@ struct PredOrdinal {
   }
 };
 
-int ell_launch_ordinal(int LPR, int NB, bool ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
+int ell_launch_ordinal(int LPR, int NB, int ext, int nb, size_t lds, hipStream_t st, const tgp_model& md, const FlowProg& fp,
                        const double* Y, const double* mu, const double* v, const double* rowp, double* part, double* g_mu, double* g_v,
                        double* g_rowp) {
   return ell_launch_row<EllOrdinal>(LPR, NB, ext, nb, lds, st, md, fp, Y, mu, v, rowp, part, g_mu, g_v, g_rowp);

@@ -184,8 +184,9 @@ __device__ __forceinline__ void prep_xform_role(const Plan& p, const tgp_model& 
       const int j = t - poff;
       const double x = md.theta[t];
       const bool res = flow_param_restricted(kind, flags, j);
-      st_maybe<SHARED>(ws + p.tp + t, res ? softplus_d(x) : x);
-      st_maybe<SHARED>(ws + p.tg + t, res ? sigmoid_d(x) : 1.0);
+      const double sg = flow_param_negated(kind, flags, j) ? -1.0 : 1.0;   // (TUKEY.gamma of a left-skewed block)
+      st_maybe<SHARED>(ws + p.tp + t, res ? sg * softplus_d(x) : x);
+      st_maybe<SHARED>(ws + p.tg + t, res ? sg * sigmoid_d(x) : 1.0);
       break;
     }
   }

@@ -6,7 +6,8 @@ namespace tgp {
 
 #define DECL(n)                                                                     \
   int launch_rows_mt##n(const RowArgs& a, int mode, size_t lds, hipStream_t st); \
-  int launch_rows_mt##n##_x(const RowArgs& a, int mode, size_t lds, hipStream_t st);
+  int launch_rows_mt##n##_x(const RowArgs& a, int mode, size_t lds, hipStream_t st); \
+  int launch_rows_mt##n##_x2(const RowArgs& a, int mode, size_t lds, hipStream_t st);
 DECL(1) DECL(2) DECL(3) DECL(4) DECL(5) DECL(6) DECL(7) DECL(8)
 #undef DECL
 // the units of the trimmed training kernels, k_rows<MT, .., MODE | TGP_ROWS_KT(KT), ..> with KT = Plan::KL < 4 (tgp_rows_inst.hip
@@ -79,9 +80,24 @@ int launch_rows(const Plan& p, const tgp_model& md, const FlowProg& fp, const do
     lds = row_lds(p, 1, fp.nslots, TGP_RW_SMALL).total * sizeof(double);
     if (lds > lim) return TGP_E_LDS;
   } else if (lds > lim) return TGP_E_LDS;
-  // a training launch whose program holds a kind past STEPTANH: the TGP_FLOWX instantiation of the same plan
-  // (every training plan -- modes 1, 2, 200 and both k_rows4 widths -- exists in both sets)
-  if (train && p.lik == TGP_LIK_FLOW && flow_prog_extended(fp.blk, fp.nblk)) {
+  // a training launch whose program holds a kind past STEPTANH: the TGP_FLOWX instantiation of the same plan, or the
+  // TGP_FLOWX2 one when a kind is past INV_BOXCOX (every training plan -- modes 1, 2, 200 and both k_rows4 widths -- exists in
+  // all three sets)
+  const int xbit = (train && p.lik == TGP_LIK_FLOW) ? flow_prog_xbit(fp.blk, fp.nblk) : 0;
+  if (xbit == TGP_FLOWX2) {
+    switch (p.MT) {
+      case 1: return launch_rows_mt1_x2(a, mode, lds, st);
+      case 2: return launch_rows_mt2_x2(a, mode, lds, st);
+      case 3: return launch_rows_mt3_x2(a, mode, lds, st);
+      case 4: return launch_rows_mt4_x2(a, mode, lds, st);
+      case 5: return launch_rows_mt5_x2(a, mode, lds, st);
+      case 6: return launch_rows_mt6_x2(a, mode, lds, st);
+      case 7: return launch_rows_mt7_x2(a, mode, lds, st);
+      case 8: return launch_rows_mt8_x2(a, mode, lds, st);
+    }
+    return TGP_E_UNSUPPORTED;
+  }
+  if (xbit == TGP_FLOWX) {
     switch (p.MT) {
       case 1: return launch_rows_mt1_x(a, mode, lds, st);
       case 2: return launch_rows_mt2_x(a, mode, lds, st);

@@ -228,9 +228,9 @@ __device__ __forceinline__ void flow_param_wave_sums(const double* stackw, const
 template <int MT, int DP, int MODEX, int RW = 16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_rows(RowArgs a) {
   constexpr int KT = 4 - ((MODEX >> 5) & 3);
-  static_assert((MODEX & ~((TGP_FLOWX - 1) | TGP_FLOWX | TGP_ROWS_KT(1))) == 0, "MODEX = MODE | TGP_FLOWX | TGP_ROWS_KT(KT)");
+  static_assert((MODEX & ~((TGP_FLOWX - 1) | TGP_FLOWX | TGP_FLOWX2 | TGP_ROWS_KT(1))) == 0, "MODEX = MODE | TGP_FLOWX or TGP_FLOWX2 | TGP_ROWS_KT(KT)");
   constexpr int MODE = MODEX & (TGP_FLOWX - 1);
-  constexpr bool X = MODEX & TGP_FLOWX;
+  constexpr int X = TGP_XK_OF(MODEX);   // TGP_FLOWX2: the kinds past INV_BOXCOX as well (tgp_dev.hpp)
   static_assert(RW == 16 || (RW == TGP_RW_SMALL && MODE == 1), "rows per wave: 16, or TGP_RW_SMALL in training mode 1");
   static_assert(KT == 4 || (KT >= 1 && KT < 4 && MODE == 1), "k-steps of the last tile: 4, or 1 .. 3 in training mode 1");
   constexpr bool TRAIN = MODE != 0;

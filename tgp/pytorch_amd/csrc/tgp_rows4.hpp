@@ -101,7 +101,7 @@ __device__ __forceinline__ double row4_sum(double x) {
 template <int MT, int DP, bool TRAIN, int NWX>
 __global__ __launch_bounds__((NWX & (TGP_FLOWX - 1)) * 64) void k_rows4(RowArgs a) {
   constexpr int NW = NWX & (TGP_FLOWX - 1);
-  constexpr bool X = NWX & TGP_FLOWX;
+  constexpr int X = TGP_XK_OF(NWX);
   constexpr int MP = MT * 16, NT = NW * 64, NTRI = MT * (MT + 1) / 2, NIMG = NTRI * 256;
   constexpr int CT = (2 * DP + 1 + 15) / 16, CT16 = CT * 16, RB = 4 * NW;
   typedef double d2v __attribute__((ext_vector_type(2)));

@@ -1,6 +1,7 @@
 // tgp_rows_inst.hip -- one translation unit per MT (compiled 8x with -DTGP_MT=1..8 so the big unrolled
 // kernels build in parallel); each defines launch_rows_mt<N>().  Compiled another 8x with -DTGP_FLOWX_BUILD=1: the training
-// kernels whose flow sweeps know the extended kind set (the TGP_FLOWX bit set in MODE / NW), launch_rows_mt<N>_x().
+// kernels whose flow sweeps know the extended kind set (the TGP_FLOWX bit set in MODE / NW), launch_rows_mt<N>_x(), and 8x with
+// -DTGP_FLOWX_BUILD=2: the same with the kinds past INV_BOXCOX compiled in as well (TGP_FLOWX2), launch_rows_mt<N>_x2().
 // Compiled another 8 x 3 times with -DTGP_KT=1..3: the training kernels (mode 1 at 16 and at 10 rows per wave, plain kind set)
  // that leave out the padded k-steps of M's last tile (k_rows<.., MODE | TGP_ROWS_KT(KT), ..>), launch_rows_mt<N>_kt<K>().
 #include "tgp_rows.hpp"
@@ -15,7 +16,10 @@
 #endif
 #define CAT_(a, b) a##b
 #define CAT(a, b) CAT_(a, b)
-#if TGP_FLOWX_BUILD
+#if TGP_FLOWX_BUILD == 2
+#define TGP_XBIT TGP_FLOWX2
+#define TGP_LAUNCH_MT CAT(CAT(launch_rows_mt, TGP_MT), _x2)
+#elif TGP_FLOWX_BUILD
 #define TGP_XBIT TGP_FLOWX
 #define TGP_LAUNCH_MT CAT(CAT(launch_rows_mt, TGP_MT), _x)
 #else

@@ -61,13 +61,27 @@ __device__ inline WVal warp_block(int kind, int K, int flags, const double* tp, 
     r.g = (copysign(p, x) - 1.0) / lam;
     r.g1 = p / ax;
     if (D2) r.g2 = (lam - 1.0) * p / (ax * x);
-  } else {  // INV_BOXCOX
+  } else if (kind == TGP_FLOW_INV_BOXCOX) {
     double lam = tp[0];
     if (lam == 0.0) lam = 1e-11;
     const double w = lam * x + 1.0, aw = fabs(w), q = exp(log(aw) / lam);
     r.g = copysign(q, w);
     r.g1 = q / aw;
     if (D2) r.g2 = (1.0 - lam) * q / (aw * w);
+  } else if (kind == TGP_FLOW_SINH) {
+    const double a = tp[0], b = tp[1], c = tp[2], d = tp[3];
+    const double z = (x - c) / d, sh = sinh(z);
+    r.g = a + b * sh;
+    r.g1 = b * cosh(z) / d;
+    if (D2) r.g2 = b * sh / (d * d);
+  } else {  // TUKEY (the host refuses NORMCDF, EXP and SOFTPLUS as warps: they do not map onto the real line)
+    double gam = tp[0];
+    if (gam == 0.0) gam = 1e-11;
+    const double h = tp[1], em = expm1(gam * x), eg = em + 1.0, u = em / gam, E = exp(0.5 * h * x * x);
+    r.g = u * E;
+    r.g1 = E * (eg + h * x * u);
+    if (D2) r.g2 = h * x * r.g1 + E * (gam * eg + h * u + h * x * eg);
+    return r;   // (no ADD_F0 for this kind: the API refuses it)
   }
   if (addf) { r.g += x; r.g1 += 1.0; }
   return r;
@@ -189,12 +203,27 @@ __global__ __launch_bounds__(256) void k_ell_warp(tgp_model md, FlowProg fp, int
       if (lam == 0.0) lam = 1e-11;
       const double ax = fabs(xi), lx = log(ax), p = exp(lam * lx), sp = copysign(p, xi);
       warp_acc(a_, tg_, 0, gb * (sp * lx / lam - (sp - 1.0) / (lam * lam)) + cg * (p / ax * lx), lane);
-    } else {
+    } else if (kind == TGP_FLOW_INV_BOXCOX) {
       double lam = q[0];
       if (lam == 0.0) lam = 1e-11;
       const double w = lam * xi + 1.0, aw_ = fabs(w), lw = log(aw_), qq = exp(lw / lam), sq = copysign(qq, w);
       const double dl = xi / (lam * w) - lw / (lam * lam);
       warp_acc(a_, tg_, 0, gb * (sq * dl) + cg * (qq / aw_ * (dl - xi / w)), lane);
+    } else if (kind == TGP_FLOW_SINH) {
+      // g = a + b sinh z, g' = (b/d) cosh z, z = (x - c)/d
+      const double bb = q[1], cc = q[2], d = q[3], id = 1.0 / d;
+      const double z = (xi - cc) * id, sh = sinh(z), ch = cosh(z);
+      warp_acc(a_, tg_, 0, gb, lane);
+      warp_acc(a_, tg_, 1, gb * sh + cg * (ch * id), lane);
+      warp_acc(a_, tg_, 2, gb * (-bb * ch * id) + cg * (-bb * sh * id * id), lane);
+      warp_acc(a_, tg_, 3, gb * (-bb * ch * z * id) + cg * (-bb * id * id * (ch + z * sh)), lane);
+    } else {  // TUKEY: u_gam = du/dgam = (x e^{gam x} - u)/gam
+      double gam = q[0];
+      if (gam == 0.0) gam = 1e-11;
+      const double h = q[1], em = expm1(gam * xi), eg = em + 1.0, u = em / gam, E = exp(0.5 * h * xi * xi);
+      const double ug = (xi * eg - u) / gam, hx2 = 0.5 * xi * xi;
+      warp_acc(a_, tg_, 0, gb * (E * ug) + cg * (E * (xi * eg + h * xi * ug)), lane);
+      warp_acc(a_, tg_, 1, gb * (r.g * hx2) + cg * (hx2 * r.g1 + E * xi * u), lane);
     }
     gb = gb * r.g1 + cw * r.g2 * ig;
   }
@@ -289,13 +318,20 @@ __device__ inline double warp_newton(int kind, int K, int flags, const double* t
     }
   }
   if (!ok) { *fail = true; return x; }
-  for (int it = 0; it < WARP_INV_MAXIT; ++it) {
+  // TUKEY grows like e^{h x^2/2}: from a start far above the root a Newton step is only ~1/(h x) long and the bracket never
+  // cuts it short.  For that kind a step that would not at least halve the one before it gives way to a bisection (the rule of
+  // Numerical Recipes' rtsafe), with twice the evaluations; the other kinds iterate exactly as before.
+  const bool guard = kind == TGP_FLOW_TUKEY;
+  const int maxit = guard ? 2 * WARP_INV_MAXIT : WARP_INV_MAXIT;
+  double dxprev = hi - lo;
+  for (int it = 0; it < maxit; ++it) {
     const double fx = r.g - t;
     if (fx == 0.0) return x;
     if (fx < 0.0) lo = x; else hi = x;
     double xn = x - fx / r.g1;
-    if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+    if (!(xn > lo && xn < hi) || (guard && fabs(2.0 * fx) > fabs(dxprev * r.g1))) xn = 0.5 * (lo + hi);
     const double dx = fabs(xn - x);
+    dxprev = dx;
     x = xn;
     if (dx <= 8.8817841970012523e-16 * fmax(1.0, fabs(x))) return x;
     r = warp_block<false>(kind, K, flags, tp, pa, pb, x);
@@ -318,7 +354,7 @@ __device__ inline double warp_inverse(const FlowProg& fp, const double* tp, cons
       pa = tp[poff]; pb = tp[poff + 1];
     }
     const double* q = tp + poff;
-    if (addf || kind == TGP_FLOW_STEPTANH) {
+    if (addf || kind == TGP_FLOW_STEPTANH || kind == TGP_FLOW_TUKEY) {
       x = warp_newton(kind, K, flags, q, pa, pb, x, fail);
     } else if (kind == TGP_FLOW_AFFINE) {
       x = (x - pb) / pa;
@@ -326,6 +362,8 @@ __device__ inline double warp_inverse(const FlowProg& fp, const double* tp, cons
       x = sinh((log(x + sqrt(x * x + 1.0)) + pa) / pb);
     } else if (kind == TGP_FLOW_ARCSINH) {
       x = q[2] + q[3] * sinh((x - q[0]) / q[1]);
+    } else if (kind == TGP_FLOW_SINH) {
+      x = q[2] + q[3] * asinh((x - q[0]) / q[1]);
     } else if (kind == TGP_FLOW_BOXCOX) {      // the INV_BOXCOX block of the same lam
       x = warp_block<false>(TGP_FLOW_INV_BOXCOX, 0, 0, q, 0.0, 0.0, x).g;
     } else {

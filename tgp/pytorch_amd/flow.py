@@ -6,11 +6,14 @@ The modules are parameter holders + a compiler to the flow *program* the HIP ker
 (`compile_flow`); `forward()` evaluates the flow on the GPU through tgp_flow_eval_f64 (no autograd: the
 training path differentiates inside the fused kernel, ops.ElboFunction).  Provided: affine, sinh_arcsinh,
 tanh (inside step_flow), step_flow, identity -- the flows main.py's default recipes reach -- and arcsinh, boxcox and
-inverseboxcox, the other kinds the reference's generators (flows.py: ArcSL, BoxCoxL, InverseBoxCoxL, build_chain) emit.
+inverseboxcox, the other kinds the reference's generators (flows.py: ArcSL, BoxCoxL, InverseBoxCoxL, build_chain) emit;
+sinh, normalCDF, tukey / tukey_left / tukey_right, exp and softplus (shared parameters only; their `torch_map` restates the
+map in torch for CPU checks, forward() stays the HIP kernel).
 Box-Cox constraints other than the default (a Python callable) cannot run inside a captured step and are refused.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as Fn
 
 from . import config as cg
 from . import lib as L
@@ -37,9 +40,24 @@ def instance_flow(flow_list, is_composite=True):
             fl = BoxCoxFlow(**init_values)
         elif name in ("inverseboxcox", "inverse_boxcox"):
             fl = InverseBoxCoxFlow(**init_values)
+        elif name == "sinh":
+            fl = SinhFlow(**init_values)
+        elif name == "normalCDF":
+            fl = NormalCDFFlow(**init_values)
+        elif name == "tukey":
+            fl = TukeyFlow(**init_values)
+        elif name == "tukey_left":
+            fl = TukeyLeftFlow(**init_values)
+        elif name == "tukey_right":
+            fl = TukeyRightFlow(**init_values)
+        elif name == "exp":
+            fl = ExpFlow()
+        elif name == "softplus":
+            fl = SoftplusFlow()
         else:
             raise ValueError("Unkown flow identifier {} (this build provides affine, sinh_arcsinh, tanh, step_flow, "
-                             "identity, arcsinh, boxcox, inverseboxcox)".format(name))
+                             "identity, arcsinh, boxcox, inverseboxcox, sinh, normalCDF, tukey, tukey_left, tukey_right, "
+                             "exp, softplus)".format(name))
         FL.append(fl)
     return CompositeFlow(FL) if is_composite else FL
 
@@ -176,6 +194,107 @@ class ArcsinhFlow(Flow):
             setattr(self, n, nn.Parameter(torch.tensor(v, dtype=cg.dtype)))
         self.set_restrictions = True if add_init_f0 else set_restrictions
         self.add_init_f0 = add_init_f0
+
+
+class _FourParamFlow(Flow):
+    """a + b*h((f0-c)/d) [+ f0]: the parameter holder the arcsinh, sinh and normal-CDF flows share (one parameter order, one
+    restriction rule; include/tgp_hip.h "the four-parameter family")."""
+
+    def __init__(self, init_a, init_b, init_c, init_d, add_init_f0, set_restrictions, input_dependent=False):
+        super().__init__()
+        for n, v in (("a", init_a), ("b", init_b), ("c", init_c), ("d", init_d)):
+            setattr(self, n, nn.Parameter(torch.tensor(v, dtype=cg.dtype)))
+        self.set_restrictions = True if add_init_f0 else set_restrictions
+        self.add_init_f0 = add_init_f0
+        self.input_dependent = bool(input_dependent)      # (compile_flow refuses True: shared parameters only)
+
+    def _h(self, x):
+        raise NotImplementedError
+
+    def torch_map(self, f0):
+        """The map as the reference's forward writes it, in differentiable torch on f0's device: the statement the CPU tests
+        compare the kernels' formulas with.  forward() is the HIP kernel."""
+        b, d = (Fn.softplus(self.b), Fn.softplus(self.d)) if self.set_restrictions else (self.b, self.d)
+        fk = self.a + b * self._h((f0 - self.c) / d)
+        return fk + f0 if self.add_init_f0 else fk
+
+
+class SinhFlow(_FourParamFlow):
+    """fk = a + b*sinh((f0-c)/d) [+ f0] (flow.py:566-609): the heavier-tailed counterpart of arcsinh; set_restrictions: b, d
+    through softplus (forced by add_init_f0)."""
+
+    def _h(self, x):
+        return torch.sinh(x)
+
+
+class NormalCDFFlow(_FourParamFlow):
+    """fk = a + b*Phi((f0-c)/d) [+ f0] (flow.py:1006-1037 with is_learnable=True): a saturating, bounded warp.  The
+    parameter-free Phi (is_learnable=False) is not provided."""
+
+    def __init__(self, init_a, init_b, init_c, init_d, add_init_f0, set_restrictions, is_learnable=True,
+                 input_dependent=False):
+        if not is_learnable:
+            raise NotImplementedError("NormalCDFFlow(is_learnable=False): the parameter-free Phi is not provided; pass "
+                                      "is_learnable=True (a = 0, b = 1, c = 0, d = 1 is the same map)")
+        super().__init__(init_a, init_b, init_c, init_d, add_init_f0, set_restrictions, input_dependent)
+        self.is_learnable = True
+
+    def _h(self, x):
+        return 0.5 * torch.erfc(-x * (0.5 ** 0.5))
+
+
+class TukeyFlow(Flow):
+    """Tukey g-and-h: fk = (exp(g*f0) - 1)/g * exp(h*f0^2/2), h = softplus(h_raw), g = g_raw != 0 (flow.py:451-474; a g of
+    exactly 0 is taken as 1e-11).  The reference stores add_init_f0 and ignores it; here True is refused."""
+    gamma_sign = 0          # 0: g = g_raw; +1: softplus(g_raw) (TukeyRightFlow); -1: -softplus(g_raw) (TukeyLeftFlow)
+
+    def __init__(self, init_g, init_h, add_init_f0=False, input_dependent=False):
+        super().__init__()
+        self.input_dependent = bool(input_dependent)      # (compile_flow refuses True: shared parameters only)
+        if add_init_f0:
+            raise ValueError("{}: add_init_f0=True is not supported (the reference stores the argument and never adds f0 "
+                             "to a Tukey flow)".format(type(self).__name__))
+        self.g = nn.Parameter(torch.tensor(init_g, dtype=cg.dtype))
+        self.h = nn.Parameter(torch.tensor(init_h, dtype=cg.dtype))
+        self.add_init_f0 = False
+
+    def get_g_h(self):
+        g = self.g if self.gamma_sign == 0 else self.gamma_sign * Fn.softplus(self.g)
+        return g, Fn.softplus(self.h)
+
+    def torch_map(self, f0):
+        g, h = self.get_g_h()
+        if self.gamma_sign == 0 and float(g.detach()) == 0.0:
+            g = g + 1e-11
+        return torch.expm1(g * f0) / g * torch.exp(h * f0 ** 2 / 2)
+
+
+class TukeyRightFlow(TukeyFlow):
+    """g = softplus(g_raw) > 0: right-skewed (flow.py:476-483)."""
+    gamma_sign = 1
+
+
+class TukeyLeftFlow(TukeyFlow):
+    """g = -softplus(g_raw) < 0: left-skewed (flow.py:485-492)."""
+    gamma_sign = -1
+
+
+class ExpFlow(Flow):
+    """fk = exp(f0) (flow.py:283-294): a positive-range head, no parameters."""
+
+    def torch_map(self, f0):
+        return torch.exp(f0)
+
+
+class SoftplusFlow(Flow):
+    """fk = log(1 + exp(f0)), fk = f0 for f0 > 20 (torch.nn.Softplus, flow.py:262-276): a positive-range head, no parameters."""
+
+    def __init__(self, set_restrictions=False):
+        super().__init__()
+        self.set_restrictions = False
+
+    def torch_map(self, f0):
+        return Fn.softplus(f0)
 
 
 class BoxCoxFlow(Flow):
@@ -375,6 +494,21 @@ def compile_flow(flow):
             flags = (L.FLAG_RESTRICT if fl.set_restrictions else 0) | (L.FLAG_ADD_F0 if fl.add_init_f0 else 0)
             blocks.append((L.FLOW_ARCSINH, 0, len(theta), flags))
             theta += [fl.a, fl.b, fl.c, fl.d]
+        elif isinstance(fl, (_FourParamFlow, TukeyFlow)):
+            if fl.input_dependent:
+                raise NotImplementedError("{}: input-dependent parameters are not supported (the HIP flow kernels take shared "
+                                          "parameters for this kind; only sinh_arcsinh has a per-row variant, as in the "
+                                          "reference)".format(type(fl).__name__))
+            if isinstance(fl, TukeyFlow):
+                flags = {0: 0, 1: L.FLAG_RESTRICT, -1: L.FLAG_RESTRICT | L.FLAG_NEGATE}[fl.gamma_sign]
+                blocks.append((L.FLOW_TUKEY, 0, len(theta), flags))
+                theta += [fl.g, fl.h]
+            else:
+                flags = (L.FLAG_RESTRICT if fl.set_restrictions else 0) | (L.FLAG_ADD_F0 if fl.add_init_f0 else 0)
+                blocks.append((L.FLOW_SINH if isinstance(fl, SinhFlow) else L.FLOW_NORMCDF, 0, len(theta), flags))
+                theta += [fl.a, fl.b, fl.c, fl.d]
+        elif isinstance(fl, (ExpFlow, SoftplusFlow)):
+            blocks.append((L.FLOW_EXP if isinstance(fl, ExpFlow) else L.FLOW_SOFTPLUS, 0, len(theta), 0))
         elif isinstance(fl, BoxCoxFlow):
             kind = L.FLOW_INV_BOXCOX if isinstance(fl, InverseBoxCoxFlow) else L.FLOW_BOXCOX
             blocks.append((kind, 0, len(theta), L.FLAG_ADD_F0 if fl.add_init_f0 else 0))

@@ -3,7 +3,9 @@
 Affine :223-235, StepTanhL :239-277).  Same defaults, same init values and the same numpy.random draw order, so a seeded
 call returns the reference's specs.  The step generators other than StepTanhL (StepSAL, StepArcSL, StepBoxCoxL, ...) are
 not provided: their step flows of mixed kinds have no HIP program.  A Box-Cox `constraint` passes through into the spec;
-flow.BoxCoxFlow refuses anything but None."""
+flow.BoxCoxFlow refuses anything but None.
+SinhL, NormalCDFL, TukeyL, SALSoftplus and SALExp are this package's own: the reference has the flows (models/flow.py) but no
+generator for them, so their defaults and their numpy.random draw order are defined in their docstrings."""
 import numpy
 import torch
 
@@ -115,6 +117,81 @@ def ArcSL(num_blocks, **kwargs):
                                    "add_init_f0": addf0, "set_restrictions": set_res}))
         blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
     return blocks
+
+
+def _raw(value, restricted):
+    """The raw parameter whose used value is `value`: inv_softplus(value) where the block puts softplus on it."""
+    return inv_softplus(torch.tensor(float(value), dtype=torch.float64)).item() if restricted else float(value)
+
+
+def _four_param_layers(name, num_blocks, defaults, kwargs, extra=None):
+    """[name, affine] x num_blocks for a block a + b*h((f-c)/d).  This package's own generator (the reference has none for
+    these flows).  numpy.random draw order, fixed here: per block, with init_random only, randn(2) for the affine block's
+    (a, b), then randn(4) for the block's (a, b, c, d); without init_random nothing is drawn and (a, b, c, d) are the USED
+    values of `defaults` (b and d as raw values through inv_softplus when the block is restricted)."""
+    set_res, addf0, init_random, _ = _common(kwargs)
+    restricted = bool(set_res or addf0)
+    blocks = []
+    for _ in range(num_blocks):
+        if init_random:
+            a_aff, b_aff = numpy.random.randn(2)
+            a, b, c, d = numpy.random.randn(4)
+        else:
+            a_aff, b_aff = 1.0, 0.0
+            a, b, c, d = defaults
+            b, d = _raw(b, restricted), _raw(d, restricted)
+        init = {"init_a": a, "init_b": b, "init_c": c, "init_d": d, "add_init_f0": addf0, "set_restrictions": set_res}
+        init.update(extra or {})
+        blocks.append((name, init))
+        blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
+    return blocks
+
+
+def SinhL(num_blocks, **kwargs):
+    """[sinh, affine] x num_blocks.  Default a = c = 0, b = d = 3: 3 sinh(f/3) = f + f^3/54 + ..., near the identity on the
+    range of standardised targets.  Draw order: _four_param_layers."""
+    return _four_param_layers("sinh", num_blocks, (0.0, 3.0, 0.0, 3.0), kwargs)
+
+
+def NormalCDFL(num_blocks, **kwargs):
+    """[normalCDF, affine] x num_blocks.  Default c = 0, d = 3, b = 3 sqrt(2 pi), a = -b/2: the value 0 and the slope
+    b phi(0)/d = 1 at the origin.  Draw order: _four_param_layers."""
+    b = 3.0 * numpy.sqrt(2.0 * numpy.pi)
+    return _four_param_layers("normalCDF", num_blocks, (-0.5 * b, b, 0.0, 3.0), kwargs, {"is_learnable": True})
+
+
+def TukeyL(num_blocks, side=None, **kwargs):
+    """[tukey | tukey_left | tukey_right, affine] x num_blocks (side None | "left" | "right").  This package's own generator.
+    Default gamma = 0.1 (side None, "right") or -0.1 ("left") and h = softplus(h_raw) = 0.01 -- the raw values are chosen
+    accordingly.  Draw order, with init_random only: per block randn(2) for the affine block's (a, b), then randn(2) for the raw
+    (g, h)."""
+    if side not in (None, "left", "right"):
+        raise ValueError("TukeyL: side must be None, 'left' or 'right' (got {!r})".format(side))
+    set_res, addf0, init_random, _ = _common(kwargs)
+    if addf0:
+        raise ValueError("TukeyL: add_f0 is not supported (the reference never adds f0 to a Tukey flow)")
+    name = "tukey" if side is None else "tukey_" + side
+    blocks = []
+    for _ in range(num_blocks):
+        if init_random:
+            a_aff, b_aff = numpy.random.randn(2)
+            g, h = numpy.random.randn(2)
+        else:
+            a_aff, b_aff = 1.0, 0.0
+            g, h = _raw(0.1, side is not None), _raw(0.01, True)
+        blocks.append((name, {"init_g": g, "init_h": h, "add_init_f0": False}))
+        blocks.append(("affine", {"init_a": a_aff, "init_b": b_aff, "set_restrictions": set_res}))
+    return blocks
+
+
+def SALSoftplus(num_blocks, **kwargs):
+    """SAL(num_blocks) followed by one softplus head: a positive-range flow (this package's own generator; SAL's draw order)."""
+    return SAL(num_blocks, **kwargs) + [("softplus", {})]
+
+
+def SALExp(num_blocks, **kwargs):
+    """SAL(num_blocks) followed by one exp head: a positive-range flow (this package's own generator; SAL's draw order)."""
+    return SAL(num_blocks, **kwargs) + [("exp", {})]
 
 
 def Affine(num_blocks, **kwargs):

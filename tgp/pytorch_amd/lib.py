@@ -13,7 +13,9 @@ LIB_PATH = os.path.join(_HERE, "libtgp_hip.so")
 
 FLOW_AFFINE, FLOW_SAL, FLOW_STEPTANH = 0, 1, 2
 FLOW_ARCSINH, FLOW_BOXCOX, FLOW_INV_BOXCOX = 3, 4, 5
+FLOW_SINH, FLOW_NORMCDF, FLOW_TUKEY, FLOW_EXP, FLOW_SOFTPLUS = 7, 8, 9, 10, 11    # (6 is unassigned and refused)
 FLAG_RESTRICT, FLAG_ADD_F0, FLAG_PER_ROW = 1, 2, 4
+FLAG_NEGATE = 8             # TUKEY only, with FLAG_RESTRICT: gamma = -softplus(raw) (tukey_left)
 LIK_GAUSS, LIK_FLOW = 0, 1
 LIK_BERNOULLI = 3           # probit link through the flow (TGP_LIK_BERNOULLI)
 LIK_WARPED = 4              # the flow warps the targets (TGP_LIK_WARPED)

@@ -172,6 +172,11 @@ class WarpedGaussianLinearMean(GaussianLinearMean):
         super().__init__(out_dim, noise_init, noise_is_shared)
         from .flow import instance_flow
         self.flow = nn.ModuleList([instance_flow(flow) if isinstance(flow, list) else flow])
+        from .flow import ExpFlow, NormalCDFFlow, SoftplusFlow
+        for fl in getattr(self.flow[0], "flow_arr", [self.flow[0]]):
+            if isinstance(fl, (NormalCDFFlow, ExpFlow, SoftplusFlow)):
+                raise ValueError("WarpedGaussianLinearMean: a {} block cannot warp the targets: the warp must map onto the real "
+                                 "line, so that every Gaussian latent value is the image of a target".format(type(fl).__name__))
         self.quad_points = quad_points
 
     def _flow_inputs(self, flow=None, X=None, dev=None, with_grad=False):

@@ -78,7 +78,8 @@ import torch
 from . import config as cg
 from .data import return_dataset
 from .flow import instance_flow
-from .flows import CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, StepTanhL, build_chain
+from .flows import (CHAINS, SAL, Affine, ArcSL, BoxCoxL, InverseBoxCoxL, NormalCDFL, SALExp, SALSoftplus, SinhL, StepTanhL, TukeyL,
+                    build_chain)
 from .initializers import find_forward_params, find_forward_params_input_dependent_flow
 from .kernels import instance_kernel
 from .lib import BETA_MAX_PRECISION, BETA_MIN_PRECISION, GAMMA_MAX_SHAPE, GAMMA_MIN_SHAPE, RQ_MAX_ALPHA, RQ_MIN_ALPHA, STUDENT_MAX_DF
@@ -115,8 +116,11 @@ COUNT_DATASETS = ("synthetic_counts", "synthetic_overdispersed")
 ORDINAL_DATASETS = ("synthetic_ratings",)
 POSITIVE_DATASETS = ("synthetic_claims",)
 PROPORTION_DATASETS = ("synthetic_proportions",)
-FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine") + CHAINS
-_PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine}
+FLOW_ARCHS = ("SAL", "StepTanhL", "ArcSL", "BoxCoxL", "InverseBoxCoxL", "Affine", "SinhL", "NormalCDFL", "TukeyL", "TukeyLeftL",
+              "TukeyRightL", "SALSoftplus", "SALExp") + CHAINS
+_PLAIN_GENERATORS = {"ArcSL": ArcSL, "BoxCoxL": BoxCoxL, "InverseBoxCoxL": InverseBoxCoxL, "Affine": Affine, "SinhL": SinhL,
+                     "NormalCDFL": NormalCDFL, "TukeyL": TukeyL, "TukeyLeftL": lambda nb: TukeyL(nb, side="left"),
+                     "TukeyRightL": lambda nb: TukeyL(nb, side="right"), "SALSoftplus": SALSoftplus, "SALExp": SALExp}
 
 
 def main(argv=None):
