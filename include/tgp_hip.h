@@ -422,6 +422,28 @@ size_t tgp_qf_cov_workspace_bytes(int32_t N, int32_t D, int32_t M);
 int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* Sigma, int32_t* status,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Input gradients of the q(f) marginals: d mu_n / d x_nd and d v_n / d x_nd of tgp_qf_moments_f64's mu (N), v (N) at the rows
+ * X (N,D), whitened q(u).  A stationary kernel is k(d2), d2 = |(x - z) / l|^2, with the weight k_g = -2 dk/d(d2) (the table of
+ * kernels above); with K_ZZ + jitter I = L L^T, W = tril(Lam) tril(Lam)^T - I, a = L^-T m and U = L^-T W L^-1 K(Z, X) (M x N):
+ *   J[n,m,d] = dk(x_n, z_m) / dx_nd = -k_g(d2_nm) (x_nd - z_md) / l_d^2
+ *   mu_n = sum_m k_nm a_m                 dmu[n,d] = sum_m J[n,m,d] a_m
+ *   v_n  = s2 + sum_m k_nm U_mn           dv[n,d]  = 2 sum_m J[n,m,d] U_mn
+ * Each row's mu and v depend on that row's x only, so the Jacobians are the adjoint too: g_X = g_mu dmu + g_v dv, row by row.
+ * The difference (x_nd - z_md) is formed directly from the scaled rows, never from expanded statistics: a row of X equal to a row
+ * of Z bit for bit contributes an exact zero (every k_g is finite at d2 = 0, MATERN32's too).
+ * Uses model->{N,D,M,kernel,jitter,Z,raw_ls,raw_os,m,Lam}; lik / flow fields ignored.  dmu, dv: (N,D) row-major.
+ * status[0] is tgp_cholesky_f64's (pivot of K_ZZ; the host runs the jitter ladder as for tgp_qf_moments_f64).
+ * Rows are processed in passes of TGP_XGRAD_PASS_ROWS rows (fixed: never a function of N), and the workspace is sized for
+ * min(N, TGP_XGRAD_PASS_ROWS) rows; a row's result does not depend on the pass it falls in.
+ * Limits: N >= 1, 1 <= M <= TGP_BIG_MAX_M, 1 <= D <= 16, else TGP_E_UNSUPPORTED; a workspace below
+ * tgp_qf_input_grad_workspace_bytes gives TGP_E_WORKSPACE (tgp_last_error() names the entry in both cases).  The kernel id is
+ * checked before any pointer is read (-1); a null model or model array, X, dmu, dv, status, workspace: -1, -2, -3, -4, -5, -6.
+ * No float atomics, fixed summation orders: two calls on the same input return the same bits. */
+#define TGP_XGRAD_PASS_ROWS 16384
+size_t tgp_qf_input_grad_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_qf_input_grad_f64(const tgp_model* model, const double* X, double* dmu /* (N,D) */, double* dv /* (N,D) */,
+                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Joint draws from N(mu, Sigma): L_Sigma = chol(Sigma + jitter I) (tgp_cholesky_f64's status convention: status[0] = pivot),
  * F0 (S,N) = mu + eps L_Sigma^T for the caller's standard normals eps (S,N) -- sample-major, the layout X.repeat(1, S, 1)
  * gives on the diagonal path.  Lsig (N,N): optional output (NULL to skip).  1 <= N <= TGP_BIG_MAX_M, 1 <= S <= 4096. */
@@ -899,6 +921,21 @@ int tgp_predict_cdf_f64(const tgp_model* model, const double* mu, const double* 
  * model, mu, v, Y, crps: -1, -2, -3, -5, -6.  Every refusal happens before any launch. */
 int tgp_predict_crps_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, const double* Y,
                          double* crps /* (N) */, double* parts /* (2,N): T1 row 0, T2 row 1; optional */, void* stream);
+
+/* Partial derivatives of tgp_predict_f64's predictive moments in the q(f) marginals (TGP_LIK_GAUSS and TGP_LIK_FLOW; model
+ * fields as for tgp_predict_cdf_f64, standardised units).  With f_s = mu_n + sqrt(2 v_n) xs_s, g_s = G(f_s), g'_s = G'(f_s),
+ * m1 = sum_s wn_s g_s and m2 = sum_s wn_s g_s^2 - m1^2 + exp(log_var_noise[0]):
+ *   dm1[0][n] = d m1 / d mu = sum_s wn_s g'_s             dm1[1][n] = d m1 / d v = sum_s wn_s g'_s xs_s / sqrt(2 v_n)
+ *   dm2[0][n] = 2 sum_s wn_s g_s g'_s - 2 m1 dm1[0][n]    dm2[1][n] = 2 sum_s wn_s g_s g'_s xs_s / sqrt(2 v_n) - 2 m1 dm1[1][n]
+ * dm1, dm2: (2,N), row 0 the partial in mu, row 1 the partial in v.  TGP_LIK_GAUSS or an empty program: the closed form
+ * (1, 0) and (0, 1), no sweep.  A row with v <= 0 counts as v = 0: its v-partials are exact zeros (the clamp's derivative) and
+ * its mu-partials come from the one node value.  rowp (N,RP): the partials are taken at fixed per-row parameters.  The sums
+ * are evaluated as written with the caller's wn; 16 lanes share a row and add their partial sums in a fixed lane order: no float
+ * atomics, same input, same bits.  Limits: 1 <= S <= TGP_QUANTILE_MAX_S; every lik but TGP_LIK_GAUSS and TGP_LIK_FLOW is
+ * refused -- TGP_E_UNSUPPORTED, tgp_last_error() starts with the entry and names lik = k or S = k.  A null model, mu, v, dm1,
+ * dm2: -1, -2, -3, -5, -6; rowp missing with RP > 0: -4.  Every refusal happens before any launch. */
+int tgp_predict_moment_grads_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp,
+                                 double* dm1 /* (2,N) */, double* dm2 /* (2,N) */, void* stream);
 
 /* Inducing-point initialisation: the numerical kernels behind utils.KMEANS, which replaces
  * sklearn.cluster.KMeans(init='k-means++', n_init, random_state) of dsp/utils.py:143-159.  Random draws, the stopping

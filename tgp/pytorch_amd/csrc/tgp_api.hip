@@ -427,6 +427,34 @@ int tgp_qf_cov_f64(const tgp_model* model, const double* X, double* mu, double* 
   return launch_qf_cov(*model, X, mu, Sigma, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_qf_input_grad_workspace_bytes(int32_t N, int32_t D, int32_t M) { return qf_input_grad_workspace_bytes(N, D, M); }
+
+int tgp_qf_input_grad_f64(const tgp_model* model, const double* X, double* dmu, double* dv, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (!known_kernel(model->kernel)) {
+    set_error_text("tgp_qf_input_grad_f64: kernel = %d is not a " TGP_KNOWN_KERNELS_TEXT, model->kernel);
+    return -1;
+  }
+  const size_t need = qf_input_grad_workspace_bytes(model->N, model->D, model->M);
+  if (need == 0) {
+    set_error_text("tgp_qf_input_grad_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", model->N, model->D,
+                   model->M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os || !model->m || !model->Lam) return -1;
+  if (!X) return -2;
+  if (!dmu) return -3;
+  if (!dv) return -4;
+  if (!status) return -5;
+  if (!workspace) return -6;
+  if (workspace_bytes < need) {   // (to the byte: open_workspace alone counts whole doubles behind the aligned start)
+    set_error_text("tgp_qf_input_grad_f64: workspace of %zu bytes, tgp_qf_input_grad_workspace_bytes gives %zu", workspace_bytes, need);
+    return TGP_E_WORKSPACE;
+  }
+  return launch_qf_input_grad(*model, X, dmu, dv, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return optimal_qu_workspace_bytes(N, D, M); }
 
 int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
@@ -1187,6 +1215,23 @@ int tgp_predict_crps_f64(const tgp_model* model, const double* mu, const double*
   tgp_model md;
   if (int rc = flow_args(model, flowed, fp, md)) return rc;
   return launch_predict_crps(md, fp, mu, v, rowp, Y, crps, parts, static_cast<hipStream_t>(stream));
+}
+
+int tgp_predict_moment_grads_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, double* dm1,
+                                 double* dm2, void* stream) {
+  if (model && model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW) {
+    set_error_text("tgp_predict_moment_grads_f64: no moment partials for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only: the "
+                   "moments of the other likelihoods are not those of a Gaussian around the flow)", model->lik);
+    return TGP_E_UNSUPPORTED;
+  }
+  bool flowed = false;
+  if (int rc = check_quantile_model(model, mu, v, rowp, "tgp_predict_moment_grads_f64", &flowed)) return rc;
+  if (!dm1) return -5;
+  if (!dm2) return -6;
+  FlowProg fp;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
+  return launch_predict_moment_grads(md, fp, mu, v, rowp, dm1, dm2, static_cast<hipStream_t>(stream));
 }
 
 int tgp_kmeans_assign_f64(const double* X, int32_t N, int32_t D, const double* C, int32_t K, int32_t* labels, double* mind2,

@@ -297,6 +297,20 @@ size_t qf_joint_sample_workspace_bytes(int N, int S) {
   return draw_plan(p, N, S) ? p.bytes() : 0;
 }
 
+int launch_cov_prep(const double* Lam, const double* Linv, int M, int MP, double* Lq, double* W, double* LinvP, hipStream_t st) {
+  hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, Lam, Linv, M, MP, Lq, W, LinvP);
+  LAUNCH_CHECK();
+  return launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, Lq, MP, Lq, MP, 1.0, W, MP, st);
+}
+
+int launch_cov_a(const tgp_model& md, const double* X, int rows, const double* LinvP, int MP, double* A, int NP, double* mu,
+                 hipStream_t st) {
+  hipLaunchKernelGGL(k_cov_a, dim3((unsigned)(NP / TL_T)), dim3(256), 0, st, md.kernel, X, rows, md.Z, md.M, md.D, md.raw_ls,
+                     md.raw_os, LinvP, MP, md.m, A, NP, mu);
+  LAUNCH_CHECK();
+  return 0;
+}
+
 int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigma, int32_t* status, void* workspace,
                   size_t workspace_bytes, hipStream_t st) {
   CovPlan p;
@@ -305,13 +319,8 @@ int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigm
   if (int rc = open_workspace("tgp_qf_cov_f64", "tgp_qf_cov_workspace_bytes", workspace, workspace_bytes, p.total, &ws)) return rc;
   const int N = md.N, D = md.D, M = md.M, MP = p.MP, NP = p.NP;
   if (int rc = p.kzz.factor(md, ws, status, st)) return rc;
-  hipLaunchKernelGGL(k_cov_prep, dim3((unsigned)((size_t)MP * MP / 256)), dim3(256), 0, st, md.Lam, ws + p.kzz.Linv, M, MP, ws + p.Lq,
-                     ws + p.W, ws + p.LinvP);
-  LAUNCH_CHECK();
-  if (int rc = launch_gemm_plain(false, true, 0, MP, MP, MP, 1.0, ws + p.Lq, MP, ws + p.Lq, MP, 1.0, ws + p.W, MP, st)) return rc;
-  hipLaunchKernelGGL(k_cov_a, dim3((unsigned)(NP / TL_T)), dim3(256), 0, st, md.kernel, X, N, md.Z, M, D, md.raw_ls, md.raw_os,
-                     ws + p.LinvP, MP, md.m, ws + p.A, NP, mu);
-  LAUNCH_CHECK();
+  if (int rc = launch_cov_prep(md.Lam, ws + p.kzz.Linv, M, MP, ws + p.Lq, ws + p.W, ws + p.LinvP, st)) return rc;
+  if (int rc = launch_cov_a(md, X, N, ws + p.LinvP, MP, ws + p.A, NP, mu, st)) return rc;
   if (int rc = launch_gemm_plain(false, false, 0, MP, NP, MP, 1.0, ws + p.W, MP, ws + p.A, NP, 0.0, ws + p.C, NP, st)) return rc;
   const int nt = (N + TL_T - 1) / TL_T;
   hipLaunchKernelGGL(k_cov_sigma, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, md.kernel, X, N, D, md.raw_ls, md.raw_os,

@@ -229,6 +229,9 @@ int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu
 // ... the CRPS of the same predictive at Y: crps (N), parts (2,N) = T1, T2 (optional)
 int launch_predict_crps(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                         const double* Y, double* crps, double* parts, hipStream_t st);
+// ... the partials of the predictive moments in mu and v on the same sweep: dm1, dm2 (2,N)
+int launch_predict_moment_grads(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                                double* dm1, double* dm2, hipStream_t st);
 // ... and the heteroscedastic predictive on the same node table: mu, v (2,N), moments and the S x S log density
 int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                           const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st);
@@ -257,6 +260,17 @@ int launch_qf_cov(const tgp_model& md, const double* X, double* mu, double* Sigm
 size_t qf_joint_sample_workspace_bytes(int N, int S);
 int launch_qf_joint_sample(const double* mu, const double* Sigma, int N, double jitter, const double* eps, int S, double* F0,
                            double* Lsig, int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st);
+
+// ... its operand passes, for the units that build on A = L^-1 K(Z, X*) (tgp_xgrad.hip): k_cov_prep + W += L_q L_q^T on the
+// padded (MP x MP) images, and k_cov_a on `rows` rows of X* (A (MP x NP), mu (rows))
+int launch_cov_prep(const double* Lam, const double* Linv, int M, int MP, double* Lq, double* W, double* LinvP, hipStream_t st);
+int launch_cov_a(const tgp_model& md, const double* X, int rows, const double* LinvP, int MP, double* A, int NP, double* mu,
+                 hipStream_t st);
+
+// tgp_xgrad.hip (input gradients of the q(f) marginals: dmu, dv (N,D) in passes of TGP_XGRAD_PASS_ROWS rows)
+size_t qf_input_grad_workspace_bytes(int N, int D, int M);
+int launch_qf_input_grad(const tgp_model& md, const double* X, double* dmu, double* dv, int32_t* status, void* workspace,
+                         size_t workspace_bytes, hipStream_t st);
 
 // tgp_unwhiten.hip (unwhitened q(u): m_w = L^-1 m, Lam_w = L^-1 tril(L_q), and the adjoint down to Z and the kernel parameters)
 size_t unwhiten_workspace_bytes(int M, int D);

@@ -404,6 +404,75 @@ __global__ __launch_bounds__(64) void k_pred_cdf(tgp_model md, FlowProg fp, cons
   }
 }
 
+// The partials of the predictive moments m1 = sum_s wn_s g_s, m2 = sum_s wn_s g_s^2 - m1^2 + sig^2 in mu and v
+// (tgp_predict_moment_grads_f64): with g'_s = G'(f_s) at f_s = mu + sqrt(2 v) xs_s, d f_s / d mu = 1 and d f_s / d v = xs_s / sqrt(2 v),
+//   dm1 = (sum wn g',  sum wn g' xs / sqrt(2 v)),   dm2 = 2 (sum wn g g', sum wn g g' xs / sqrt(2 v)) - 2 m1 dm1.
+// The row's 16 lanes sweep its S nodes with the derivative (flow_forward_n<4, true, X>), lane l the nodes l, l + 16, ... in that
+// order, and keep five partial sums in registers -- no node table; row16_sum adds the 16 lanes in the fixed lane order.  A row
+// with v <= 0 counts as v = 0: every node is mu, the v-partials are exact zeros.
+// dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), then wn and xs (S rounded up to even each)
+template <bool X>
+__global__ __launch_bounds__(64) void k_pred_mgrad(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                   const double* __restrict__ v, const double* __restrict__ rowp,
+                                                   double* __restrict__ dm1, double* __restrict__ dm2) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int lane = threadIdx.x, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S;
+  double* xl = wl + (S + 1) / 2 * 2;
+  for (int s = lane; s < S; s += 64) { wl[s] = md.wn[s]; xl[s] = md.xs[s]; }
+  flow_params_lds<X>(md.theta, fp, tp, tg);   // (ends with a barrier: wl and xl are staged too)
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double m_ = mu[nc], vr = v[nc], vn = vr > 0.0 ? vr : 0.0, sq2 = sqrt(2.0 * vn);
+  constexpr int NB = 4;
+  double sg = 0.0, sd = 0.0, sdx = 0.0, sgd = 0.0, sgdx = 0.0;
+  for (int e0 = 0; e0 < S; e0 += NB * QLPR) {
+    double f[NB], der[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16, ec = e < S ? e : S - 1;
+      f[u] = m_ + sq2 * xl[ec];
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, true, X>(F, f, rpn, der);
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16, ec = e < S ? e : S - 1;
+      const double w = e < S ? wl[ec] : 0.0, wd = w * der[u], wgd = wd * f[u];
+      sg += w * f[u];
+      sd += wd;
+      sdx += wd * xl[ec];
+      sgd += wgd;
+      sgdx += wgd * xl[ec];
+    }
+  }
+  const double m1 = row16_sum(sg), a = row16_sum(sd), gd = row16_sum(sgd);
+  const double tdx = row16_sum(sdx), tgdx = row16_sum(sgdx);   // (the cross-lane adds run with every lane on)
+  const double inv = vr > 0.0 ? 1.0 / sq2 : 0.0;
+  const double b = vr > 0.0 ? tdx * inv : 0.0, gdx = vr > 0.0 ? tgdx * inv : 0.0;
+  if (valid && l16 == 0) {
+    dm1[n] = a;
+    dm1[(size_t)md.N + n] = b;
+    dm2[n] = 2.0 * gd - 2.0 * m1 * a;
+    dm2[(size_t)md.N + n] = vr > 0.0 ? 2.0 * gdx - 2.0 * m1 * b : 0.0;
+  }
+}
+
+// TGP_LIK_GAUSS / the empty program: m1 = mu, m2 = max(v, 0) + sig^2: (1, 0) and (0, 1 where v > 0)
+__global__ __launch_bounds__(256) void k_mgrad_gauss(int N, const double* __restrict__ v, double* __restrict__ dm1,
+                                                     double* __restrict__ dm2) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  dm1[n] = 1.0;
+  dm1[(size_t)N + n] = 0.0;
+  dm2[n] = 0.0;
+  dm2[(size_t)N + n] = v[n] > 0.0 ? 1.0 : 0.0;
+}
+
 // TGP_LIK_GAUSS / the empty program: y ~ N(mu, max(v, 0) + sig^2).  Y == nullptr: quantiles t (Q,N); else cdf / sf (N).
 __global__ __launch_bounds__(256) void k_quantile_gauss(int N, const double* __restrict__ mu, const double* __restrict__ v,
                                                         const double* __restrict__ lvn, const double* __restrict__ zq, int Q,
@@ -676,6 +745,23 @@ int launch_predict_cdf(const tgp_model& md, const FlowProg& fp, const double* mu
                                  : (ext ? k_pred_cdf<QGauss, true> : k_pred_cdf<QGauss, false>);
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * comp + ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, Y, stride, cdf, sf);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_predict_moment_grads(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                                double* dm1, double* dm2, hipStream_t st) {
+  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+    hipLaunchKernelGGL(k_mgrad_gauss, dim3((md.N + 255) / 256), dim3(256), 0, st, md.N, v, dm1, dm2);
+    LAUNCH_CHECK();
+    return 0;
+  }
+  const size_t lds = (2 * (size_t)((md.P + 2) / 2 * 2) + 2 * (size_t)((md.S + 1) / 2 * 2)) * sizeof(double);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[2] = {48 * 1024, 48 * 1024};
+  auto* const kern = ext ? k_pred_mgrad<true> : k_pred_mgrad<false>;
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, dm1, dm2);
   LAUNCH_CHECK();
   return 0;
 }

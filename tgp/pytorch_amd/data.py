@@ -192,7 +192,7 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
     base = dataset_name.replace("synthetic_", "")
     if synth and (base in BINARY_SHAPES or base in ("blobs", "counts", "overdispersed", "ratings", "claims", "proportions")):
         return _binary_dataset(base, batch_size, use_validation, seed, options)
-    if (synth and base not in SHAPES and base not in ("outliers", "hetero")) or (not synth and base not in UCI):
+    if (synth and base not in SHAPES and base not in ("outliers", "hetero", "relevance")) or (not synth and base not in UCI):
         raise ValueError("Unkown dataset provided {}".format(dataset_name))
     if not options.get("split_from_disk", True):
         raise ValueError("only the splits stored on disk are supported (split_from_disk=True, as code/main.py sets it)")
@@ -202,6 +202,14 @@ def return_dataset(dataset_name, batch_size, use_validation=None, seed=None, opt
         from .synthetic import HETERO_SHAPE, hetero_dataset
         n, d, n_tr = HETERO_SHAPE
         X, Y, noise_std = hetero_dataset(0 if seed is None else int(seed))
+        perm = numpy.random.default_rng(seed).permutation(n)
+        tr_idx, te_idx = perm[:n_tr], perm[n_tr:]
+        X_tr, Y_tr, X_te, Y_te = X[tr_idx], Y[tr_idx], X[te_idx], Y[te_idx]
+    elif synth and base == "relevance":
+        # synthetic_relevance (synthetic.relevance_dataset): six inputs, the targets depend on the first two only
+        from .synthetic import RELEVANCE_SHAPE, relevance_dataset
+        n, d, n_tr = RELEVANCE_SHAPE
+        X, Y = relevance_dataset()
         perm = numpy.random.default_rng(seed).permutation(n)
         tr_idx, te_idx = perm[:n_tr], perm[n_tr:]
         X_tr, Y_tr, X_te, Y_te = X[tr_idx], Y[tr_idx], X[te_idx], Y[te_idx]

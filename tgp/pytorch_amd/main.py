@@ -69,6 +69,13 @@ Betas:
 
     python -m tgp.pytorch_amd.main --model TGP --likelihood beta --dataset synthetic_proportions \\
         --train_test_seed_split 1 --num_inducing 20 --epochs 2000 --coverage exact
+
+`--relevance` (SVGP or TGP, --likelihood gaussian) also prints, per input, the relevance on the test split -- the
+root-mean-square slope of the predictive mean in that input (utils.input_relevance, from the HIP input gradients) -- beside the
+inverse ARD length-scale.  synthetic_relevance has six inputs of which only the first two enter the targets:
+
+    python -m tgp.pytorch_amd.main --model SVGP --dataset synthetic_relevance --relevance \\
+        --train_test_seed_split 1 --num_inducing 20 --epochs 300
 """
 import argparse
 
@@ -106,6 +113,7 @@ HYPER = {
     ("TGP", "overdispersed"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "outliers"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "hetero"): dict(arch="SAL", blocks=1, steps=None),
+    ("TGP", "relevance"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "ratings"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "claims"): dict(arch="SAL", blocks=1, steps=None),
     ("TGP", "proportions"): dict(arch="SAL", blocks=1, steps=None),
@@ -127,7 +135,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="TGP on MI355X")
     ap.add_argument("--model", required=True, help="ID_TGP, TGP, SVGP or WGP (warped GP: the flow acts on the targets)")
     ap.add_argument("--dataset", required=True,
-                    choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero"]
+                    choices=["boston", "power", "synthetic_boston", "synthetic_power", "synthetic_outliers", "synthetic_hetero",
+                             "synthetic_relevance"]
                     + list(CLASSIFICATION_DATASETS)
                     + list(MULTICLASS_DATASETS) + list(COUNT_DATASETS) + list(ORDINAL_DATASETS) + list(POSITIVE_DATASETS)
                     + list(PROPORTION_DATASETS))
@@ -187,6 +196,10 @@ def main(argv=None):
     ap.add_argument("--scores", action="store_true",
                     help="also print the test CRPS and 95 %% interval score (regression; raw units): exact where the predictive "
                          "CDF is, else the CRPS of 100 predictive draws per row and no interval score")
+    ap.add_argument("--relevance", action="store_true",
+                    help="also print, per input, the relevance on the test split (root-mean-square slope of the predictive mean in "
+                         "that input, utils.input_relevance) beside the inverse ARD length-scale 1 / l_d (SVGP or TGP, --likelihood "
+                         "gaussian)")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -252,6 +265,10 @@ def main(argv=None):
     if args.scores and (bern or multi):
         ap.error("--scores: regression only (the CRPS and the interval score are scores of a predictive distribution on the reals)")
     wgp = args.model == "WGP"
+    if args.relevance and (args.likelihood != "gaussian" or args.model not in ("SVGP", "TGP")):
+        ap.error("--relevance: SVGP or TGP with --likelihood gaussian only (the input gradients of the predictive moments are built "
+                 "for the Gaussian and flow regression likelihoods; an ID_TGP's per-row flow parameters depend on x through the "
+                 "networks, a WGP warps the targets)")
     if wgp and (bern or multi):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
@@ -490,6 +507,11 @@ def main(argv=None):
         print("Dataset {}, num inducing points {}, model {}, Test CRPS {:.4f}, Test interval score (95%) {}".format(
             args.dataset, args.num_inducing, args.model, sc["crps"],
             "n/a" if sc["interval_score"] is None else "{:.4f}".format(sc["interval_score"])))
+    if args.relevance:
+        rel, ils = trainer.compute_relevance()
+        for d in range(rel.numel()):
+            print("Dataset {}, num inducing points {}, model {}, input {} relevance {:.4f}, 1/lengthscale {:.4f}".format(
+                args.dataset, args.num_inducing, args.model, d, rel[d].item(), ils[d].item()))
     if args.model == "ID_TGP":
         model.be_fully_bayesian(True)
         res = trainer.compute_metrics()

@@ -208,11 +208,14 @@ class sparse_MF_SP(nn.Module):
     def _qf_one(self, X2, c=None):
         """(mu, v) of q(f) at the rows of X2 for latent GP c (None: the only one): tgp_qf_moments_f64, differentiable like the
         reference's autograd through sparse_MF_SP.py:274-396 (tgp_qf_moments_bwd_f64, its own ladder from jitter 0: with an
-        unwhitened q(u) it ends where the transform's did, same matrix, same ladder) when a parameter needs it."""
+        unwhitened q(u) it ends where the transform's did, same matrix, same ladder) when a parameter needs it -- and in the
+        rows of X2 themselves when X2 requires grad (tgp_qf_input_grad_f64); X2 is handed over undetached in that case only."""
         info = {}
         Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam)):
-            return ops.QfMomentsFunction.apply(X2.detach(), Z, rl, ro, m, Lam, self.covariance_function.hip_kernel)
+        x_grad = torch.is_grad_enabled() and X2.requires_grad
+        if x_grad or (torch.is_grad_enabled() and any(t.requires_grad for t in (Z, rl, ro, m, Lam))):
+            return ops.QfMomentsFunction.apply(X2 if x_grad else X2.detach(), Z, rl, ro, m, Lam,
+                                               self.covariance_function.hip_kernel)
         return ops.qf_moments(X2, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
                               kernel=self.covariance_function.hip_kernel)
 
@@ -325,7 +328,8 @@ class sparse_MF_SP(nn.Module):
     def marginal_variational_qf_parameters(self, X, diagonal: bool, is_duvenaud: bool, init_Z=None):
         """q(f) marginals (sparse_MF_SP.py:274-396): returns mu of shape (Dy, MB, 1) and cov of shape (Dy, MB, 1), or
         (Dy, MB, MB) with diagonal=False -- the full covariance K_xx - K_xz K_zz^-1 K_zx + rhs^T S rhs (:384), from
-        tgp_qf_cov_f64.  The full covariance is evaluated WITHOUT autograd and both tensors come back detached; when
+        tgp_qf_cov_f64.  diagonal=True is differentiable in the parameters and, when X requires grad, in X (each row's moments
+        in that row: tgp_qf_input_grad_f64 plus the mean function's slope).  The full covariance is evaluated WITHOUT autograd and both tensors come back detached; when
         gradients are enabled and a parameter requires them the call raises (diagonal=True is the differentiable path).
         MB <= 4096, single-output models only."""
         assert not is_duvenaud, "is_duvenaud=False on this path"
@@ -353,7 +357,9 @@ class sparse_MF_SP(nn.Module):
             return mu.unsqueeze(2), v.unsqueeze(2)
         mu, v = self._qf_one(X2)
         if self._has_mean:           # mu + m(X) (sparse_MF_SP.py:355,360): every method downstream of (mu, v) gets it from here
-            if torch.is_grad_enabled() and (mu.requires_grad or any(q.requires_grad for q in self.mean_function.parameters())):
+            if torch.is_grad_enabled() and X2.requires_grad:       # (the mean's slope reaches X through MeanFunction's g_X)
+                mu = mu + self.mean_function.vector(X2)
+            elif torch.is_grad_enabled() and (mu.requires_grad or any(q.requires_grad for q in self.mean_function.parameters())):
                 mu = mu + self.mean_function.vector(X2.detach())
             else:
                 mu = self.mean_function.vector(X2.detach(), inp=mu)
@@ -739,6 +745,58 @@ class sparse_MF_SP(nn.Module):
                 f = ops.flow_eval(f.contiguous(), spec, theta, rowp, want=("G",))["G"]
         self.train()
         return f.unsqueeze(0)
+
+    def posterior_input_gradients(self, X):
+        """(dmu, dv), each (Dy, N, D): the derivatives of the q(f) marginals mu_c(x_n), v_c(x_n) that
+        marginal_variational_qf_parameters reports in the row x_n, one tgp_qf_input_grad_f64 call per latent GP (a multi-class
+        model: Dy = C; a heteroscedastic one: f and h) -- the unwhitened q(u) through its transform, the mean function's own
+        slope (linear: a, identity: W) added to dmu.  Eval mode, no autograd, then train(), as every prediction."""
+        X2 = X[0] if X.dim() == 3 else X
+        self._require_gpu(X2)
+        self._eval_mode()
+        kern = self.covariance_function.hip_kernel
+        with torch.no_grad():
+            Xd = X2.detach().contiguous()
+            parts = []
+            for c in (range(self.out_dim) if self._is_composed else (None,)):
+                info = {}
+                Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
+                parts.append(ops.qf_input_grad(Xd, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"], kernel=kern))
+            dmu, dv = torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])
+            if self._has_mean:
+                dmu = dmu + self.mean_function._ab()[0].detach().reshape(1, 1, -1)
+        self.train()
+        return dmu, dv
+
+    def predictive_input_gradients(self, X, Y_std=None):
+        """{"m1": (N, D), "m2": (N, D)}: the gradients in x_n of the predictive mean and variance predictive_distribution reports
+        at the rows of X -- the chain rule of ops.predict_moment_grads (the partials of the moments in mu and v, through the
+        flow) with posterior_input_gradients -- in the model's standardised units, or scaled by Y_std and Y_std^2 when Y_std is
+        given.  The Gaussian and flow regression likelihoods only."""
+        lik = self.likelihood
+        if lik.lik_id is not None or lik.composed:
+            raise NotImplementedError("predictive_input_gradients: the Gaussian and flow regression likelihoods only; the "
+                                      "predictive moments of the %s likelihood are not a Gaussian's around the flow, and "
+                                      "tgp_predict_moment_grads_f64 has no partials for them"
+                                      % (lik.display or type(lik).__name__))
+        if self._input_dependent:
+            raise NotImplementedError("predictive_input_gradients: the model has input-dependent flows -- their per-row "
+                                      "parameters depend on x through the networks, and that path has no input gradient")
+        if self.fully_bayesian:
+            raise NotImplementedError("predictive_input_gradients: the fully Bayesian model is an MC-dropout mixture over "
+                                      "parameter draws, which has no input gradient here")
+        X2 = X[0] if X.dim() == 3 else X
+        dmu, dv = self.posterior_input_gradients(X2)
+        mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X2.detach(), "predictive_input_gradients")
+        with torch.no_grad():
+            dm1, dm2 = ops.predict_moment_grads(mu, v, lvn, spec, theta, self.quad_points, rowp)
+            out = {"m1": dm1[0].unsqueeze(1) * dmu[0] + dm1[1].unsqueeze(1) * dv[0],
+                   "m2": dm2[0].unsqueeze(1) * dmu[0] + dm2[1].unsqueeze(1) * dv[0]}
+            if Y_std is not None:
+                s = float(Y_std)
+                out = {"m1": out["m1"] * s, "m2": out["m2"] * (s * s)}
+        self.train()
+        return out
 
     def predictive_cdf(self, X, Y):
         """The predictive CDF at the targets Y (N,1), standardised units: the PIT values of a calibration plot, shape (Dy, N).

@@ -507,6 +507,29 @@ def qf_cov(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_r
     return mu, Sigma
 
 
+def qf_input_grad(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_rbf", info=None, workspace_bytes=None):
+    """Input gradients of the q(f) marginals (tgp_qf_input_grad_f64): returns (dmu, dv), each (N, D), the derivatives of
+    qf_moments' mu_n and v_n in the row x_n they are evaluated at.  A row's moments depend on that row alone, so the adjoint of
+    (g_mu, g_v) in X is g_mu[:, None] * dmu + g_v[:, None] * dv.  No autograd.  `check`: the jitter ladder of psd_safe_cholesky
+    on K_MM, as in qf_moments; `info["jitter"]` receives the value the factorisation ended with.  `workspace_bytes` overrides
+    the size of the workspace handed to the library (tests of its refusal)."""
+    lib = L.load()
+    md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 1.0, kernel)
+    dev = X.device
+    N, D = X.shape
+    ws, nbytes = _scratch(lib.tgp_qf_input_grad_workspace_bytes(N, D, md.M), dev, workspace_bytes)
+    dmu = torch.empty(N, D, dtype=torch.float64, device=dev)
+    dv = torch.empty_like(dmu)
+    status = _status(dev)
+
+    def call(jit):
+        md.jitter = jit
+        L.check(lib.tgp_qf_input_grad_f64(md, L.ptr(X), L.ptr(dmu), L.ptr(dv), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()),
+                "tgp_qf_input_grad_f64")
+    _laddered(call, status, jitter, info=info, check=check)
+    return dmu, dv
+
+
 def qf_joint_sample(mu, Sigma, eps, jitter=0.0, want_L=False, workspace_bytes=None):
     """Joint draws F0 (S, N) = mu + eps chol(Sigma + jitter I)^T (tgp_qf_joint_sample_f64); eps (S, N) standard normals.
     Returns (F0, L_Sigma or None, status): status[0] is the Cholesky's pivot (no ladder here: see qf_joint_sample_safe)."""
@@ -563,9 +586,10 @@ def qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, mu_bar, v_bar, jitter=0.0, kern
 
 class QfMomentsFunction(torch.autograd.Function):
     """(mu, v) = q(f) marginals with autograd in Z, raw_ls, raw_os, m, Lam (what differentiating the reference's
-    marginal_variational_qf_parameters, models/sparse_MF_SP.py:274-396, gives outside ELBO()); X gets no gradient.
+    marginal_variational_qf_parameters, models/sparse_MF_SP.py:274-396, gives outside ELBO()), and in X when X requires grad.
     Forward tgp_qf_moments_f64 (with psd_safe_cholesky's jitter ladder), backward tgp_qf_moments_bwd_f64 at the jitter
-    the forward ended with."""
+    the forward ended with; the gradient in X is g_mu[:, None] * dmu + g_v[:, None] * dv from tgp_qf_input_grad_f64 at that
+    jitter (each row's moments depend on that row only), and nothing is launched for it when X does not require grad."""
 
     @staticmethod
     def forward(ctx, X, Z, raw_ls, raw_os, m, Lam, kernel):
@@ -584,7 +608,11 @@ class QfMomentsFunction(torch.autograd.Function):
         if g_v is None:
             g_v = torch.zeros(X.shape[0], dtype=torch.float64, device=X.device)
         g = qf_moments_bwd(X, Z, raw_ls, raw_os, m, Lam, g_mu, g_v, jitter=ctx.jitter, kernel=ctx.kernel)
-        return (None, g["Z"].reshape(Z.shape), g["raw_ls"].reshape(raw_ls.shape), g["raw_os"].reshape(raw_os.shape),
+        g_X = None
+        if ctx.needs_input_grad[0]:
+            dmu, dv = qf_input_grad(X, Z, raw_ls, raw_os, m, Lam, jitter=ctx.jitter, kernel=ctx.kernel)
+            g_X = (g_mu.reshape(-1, 1) * dmu + g_v.reshape(-1, 1) * dv).reshape(X.shape)
+        return (g_X, g["Z"].reshape(Z.shape), g["raw_ls"].reshape(raw_ls.shape), g["raw_os"].reshape(raw_os.shape),
                 g["m"].reshape(m.shape), g["Lam"].reshape(Lam.shape), None)
 
 
@@ -1767,6 +1795,22 @@ def predict_crps(mu, v, lvn, Y, flow=None, theta=None, S=None, rowp=None, want_p
     L.check(lib.tgp_predict_crps_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(Yc), L.ptr(crps), L.ptr(parts), L.stream_ptr()),
             "tgp_predict_crps_f64")
     return (crps, parts) if want_parts else crps
+
+
+def predict_moment_grads(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, lik=None):
+    """(dm1, dm2), each (2, N): the partial derivatives of the predictive mean m1 and variance m2 that ops.predict reports
+    (standardised units) in the q(f) marginals -- row 0 in mu, row 1 in v -- at fixed per-row parameters
+    (tgp_predict_moment_grads_f64).  flow=None or an empty program: (1, 0) and (0, 1).  A row with v <= 0 has exact zeros in
+    row 1.  Every `lik` but None, lib.LIK_GAUSS and lib.LIK_FLOW is the library's to refuse."""
+    lib = L.load()
+    mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    md, keep = _quantile_model(mu, lvn, flow, theta, S, lik)
+    dm1 = torch.empty(2, mu.numel(), dtype=torch.float64, device=mu.device)
+    dm2 = torch.empty_like(dm1)
+    L.check(lib.tgp_predict_moment_grads_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ptr(dm1), L.ptr(dm2), L.stream_ptr()),
+            "tgp_predict_moment_grads_f64")
+    return dm1, dm2
 
 
 def crps_from_samples(draws, y):

@@ -189,6 +189,20 @@ def gross_errors(Y, seed=0, share=OUTLIERS_SHARE):
     return out, idx
 
 
+# input-relevance stand-in: (rows, inputs, training rows); inputs 2 .. 5 carry nothing
+RELEVANCE_SHAPE = (1000, 6, 900)
+
+
+def relevance_dataset(seed=0):
+    """Seeded `synthetic_relevance`: X ~ N(0, 1)^6, y = sin(2 x0) + 0.5 x1 + 0.1 eps -- the targets depend on the first two inputs
+    only, the other four carry nothing (what utils.input_relevance should report).  Returns numpy float64 X (n, d), Y (n, 1)."""
+    n, d, _ = RELEVANCE_SHAPE
+    rng = np.random.default_rng(32452843 + 31 * seed)
+    X = rng.standard_normal((n, d))
+    Y = np.sin(2.0 * X[:, 0]) + 0.5 * X[:, 1] + 0.1 * rng.standard_normal(n)
+    return X, Y.reshape(-1, 1)
+
+
 # input-dependent-noise stand-in: (rows, inputs, training rows) and the range of the noise standard deviation
 HETERO_SHAPE = (1000, 2, 900)
 HETERO_NOISE = (0.05, 1.0)

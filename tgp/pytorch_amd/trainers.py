@@ -487,6 +487,22 @@ class Trainer_SP_regression:
                 "test": self._loader_scores(self.test_loader, samples) if self.is_test else None}
 
 
+    def compute_relevance(self):
+        """(relevance (D,), inverse length-scales (D,) or None): utils.input_relevance of the model over the rows of the test
+        split -- the root-mean-square slope of the predictive mean in each input, standardised units -- beside 1 / l_d of the ARD
+        kernel (None for a model of several latent GPs, which has a set per GP).  NotImplementedError where
+        predictive_input_gradients has none."""
+        from .utils import input_relevance
+        assert self.is_test, "compute_relevance reads the test split"
+        self.refresh_qu()
+        self.model.set_is_training(False)
+        X = torch.cat([x for x, _ in self.test_loader]).to(cg.device)
+        rel = input_relevance(self.model, X).cpu()
+        raw = self.model.covariance_function.base_kernel.raw_lengthscale.detach().reshape(-1, X.shape[1])
+        ils = (1.0 / torch.nn.functional.softplus(raw[0])).cpu() if raw.shape[0] == 1 else None
+        return rel, ils
+
+
 class Trainer_SP_classification(Trainer_SP_regression):
     """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
     the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood (engine.engine_refusal).  Multi-class models

@@ -248,3 +248,18 @@ def compute_95_and_median_confidence_intervals(model, X, S, distribution, is_dee
     assert distribution in ["posterior", "predictive"], \
         "Invalid arguments for distribution. Got {}, expected one of [posterior, predictive]".format(distribution)
     return confidence_intervals(model, X, [0.025, 0.5, 0.975], S, distribution, is_deep, exact=exact)
+
+
+def input_relevance(model, X, batch_rows=65536):
+    """(D,) relevance of each input: the root-mean-square over the rows of X of d m1 / d x_d, the slope of the predictive mean
+    (model.predictive_input_gradients, standardised units), evaluated in pieces of `batch_rows` rows.  Where ARD length-scales
+    are a proxy -- an input can have a short length-scale and no effect -- this is the sensitivity itself.  Raises what
+    predictive_input_gradients raises for the models it does not serve."""
+    X2 = X[0] if X.dim() == 3 else X
+    if X2.shape[0] < 1 or int(batch_rows) < 1:
+        raise ValueError("input_relevance: at least one row of X and batch_rows >= 1")
+    sq = torch.zeros(X2.shape[1], dtype=X2.dtype, device=X2.device)
+    for r0 in range(0, X2.shape[0], int(batch_rows)):
+        g = model.predictive_input_gradients(X2[r0:r0 + int(batch_rows)])["m1"]
+        sq += (g * g).sum(0)
+    return torch.sqrt(sq / X2.shape[0])
