@@ -444,6 +444,23 @@ size_t tgp_qf_input_grad_workspace_bytes(int32_t N, int32_t D, int32_t M);
 int tgp_qf_input_grad_f64(const tgp_model* model, const double* X, double* dmu /* (N,D) */, double* dv /* (N,D) */,
                           int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The variance of the derivative process under q(f), the error bar of dmu above.  The posterior covariance is
+ * Sigma(x, x') = k(x, x') + k(x, Z) B k(Z, x') with the symmetric B = L^-T W L^-1; its mixed derivative in x_d and x'_d at
+ * x' = x is
+ *   dvar[n,d] = k_g(0) / l_d^2 + sum_{m,m'} J[n,m,d] B[m,m'] J[n,m',d]
+ * with k_g(0) = s2 (RBF), 3 s2 (MATERN32), 5/3 s2 (MATERN52), s2 (RQ).  Per pass of TGP_XGRAD_PASS_ROWS rows and per dimension
+ * d: A_d = L^-1 J_d^T (the tiles of J_d generated on chip, never stored), C_d = W A_d on the fp64 matrix cores, and
+ * dvar[n,d] = k_g(0) / l_d^2 + sum_m A_d[m,n] C_d[m,n] with m ascending.  The value is stored as computed and never clamped
+ * (rounding can leave a tiny negative where the posterior pins the slope; clamp where a square root is taken).  (x - z) is
+ * formed directly from the scaled rows.  Model fields, status[0], passes and the workspace rule as for tgp_qf_input_grad_f64;
+ * dvar: (N,D) row-major.  A row's result depends on that row only, not on N or its pass; no float atomics, same input, same bits.
+ * Limits: N >= 1, 1 <= M <= TGP_BIG_MAX_M, 1 <= D <= 16, a known kernel id, else TGP_E_UNSUPPORTED; a workspace below
+ * tgp_qf_input_grad_var_workspace_bytes gives TGP_E_WORKSPACE (tgp_last_error() names the entry in all three cases).  A null
+ * model or model array, X, dvar, status, workspace: -1, -2, -3, -4, -5.  Every refusal happens before any launch. */
+size_t tgp_qf_input_grad_var_workspace_bytes(int32_t N, int32_t D, int32_t M);
+int tgp_qf_input_grad_var_f64(const tgp_model* model, const double* X, double* dvar /* (N,D) */, int32_t* status,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Joint draws from N(mu, Sigma): L_Sigma = chol(Sigma + jitter I) (tgp_cholesky_f64's status convention: status[0] = pivot),
  * F0 (S,N) = mu + eps L_Sigma^T for the caller's standard normals eps (S,N) -- sample-major, the layout X.repeat(1, S, 1)
  * gives on the diagonal path.  Lsig (N,N): optional output (NULL to skip).  1 <= N <= TGP_BIG_MAX_M, 1 <= S <= 4096. */
@@ -591,6 +608,20 @@ int tgp_pathwise_coeff_f64(const tgp_model* model, const double* omega, int32_t 
 int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
                           const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S, double* F0,
                           void* stream);
+
+/* Input gradients of the draws: dF0 (D,S,N), plane d in F0's layout, dF0[d][s][n] = d f0_s(x_n) / d x_nd.  With
+ * w_jd = omega[j,d] / l_d and k_g = -2 dk/d(d2) (the table of kernels above; finite at d2 = 0):
+ *   d f0_s(x) / d x_d = sum_{j < R2} w_jd [ -amp sin a_j(x) W[s,j] + amp cos a_j(x) W[s,R2+j] ]
+ *                       - sum_{i < M} k_g(d2(x, z_i)) (x_d - z_id) / l_d^2 nu_s[i]
+ * coef is tgp_pathwise_coeff_f64's; the features' derivatives are generated on chip and never stored, and (x_d - z_id) is formed
+ * directly from the scaled rows (a row of X equal to a row of Z bit for bit: an exact zero in that term).  The contraction walks
+ * the rows of coef in tgp_pathwise_eval_f64's order, one set of accumulators per dimension: an element depends on its row of X,
+ * its d and coef only, so X in one call, in pieces, below or above the row count at which the row tiling changes gives the same
+ * bits.  No float atomics.  D * S * N may exceed 2^31.  Limits, refusals and their order: tgp_pathwise_eval_f64's, with dF0 in
+ * the place of F0 (-13); tgp_last_error() names this entry. */
+int tgp_pathwise_grad_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
+                          const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S,
+                          double* dF0 /* (D,S,N) */, void* stream);
 
 /* Mean functions (models/means.py, chosen by model_specs[0], models/utils_models.py:285-294): 'linear' m(x) = x a + b with a (D)
  * and b (1) trainable, 'identity' m(x) = x W with W (D) fixed (b = NULL).  One output GP: a is a vector.  The reference adds

@@ -455,6 +455,34 @@ int tgp_qf_input_grad_f64(const tgp_model* model, const double* X, double* dmu, 
   return launch_qf_input_grad(*model, X, dmu, dv, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+size_t tgp_qf_input_grad_var_workspace_bytes(int32_t N, int32_t D, int32_t M) { return qf_input_grad_var_workspace_bytes(N, D, M); }
+
+int tgp_qf_input_grad_var_f64(const tgp_model* model, const double* X, double* dvar, int32_t* status, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  if (model == nullptr) return -1;
+  if (!known_kernel(model->kernel)) {
+    set_error_text("tgp_qf_input_grad_var_f64: kernel = %d is not a " TGP_KNOWN_KERNELS_TEXT, model->kernel);
+    return TGP_E_UNSUPPORTED;
+  }
+  const size_t need = qf_input_grad_var_workspace_bytes(model->N, model->D, model->M);
+  if (need == 0) {
+    set_error_text("tgp_qf_input_grad_var_f64: N = %d, D = %d, M = %d outside N >= 1, 1 <= M <= %d, 1 <= D <= 16", model->N,
+                   model->D, model->M, TGP_BIG_MAX_M);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!model->Z || !model->raw_ls || !model->raw_os || !model->m || !model->Lam) return -1;
+  if (!X) return -2;
+  if (!dvar) return -3;
+  if (!status) return -4;
+  if (!workspace) return -5;
+  if (workspace_bytes < need) {   // (to the byte: open_workspace alone counts whole doubles behind the aligned start)
+    set_error_text("tgp_qf_input_grad_var_f64: workspace of %zu bytes, tgp_qf_input_grad_var_workspace_bytes gives %zu",
+                   workspace_bytes, need);
+    return TGP_E_WORKSPACE;
+  }
+  return launch_qf_input_grad_var(*model, X, dvar, status, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
 size_t tgp_optimal_qu_workspace_bytes(int32_t N, int32_t D, int32_t M) { return optimal_qu_workspace_bytes(N, D, M); }
 
 int tgp_optimal_qu_f64(const tgp_model* model, const double* X, const double* Y, double* m_out, double* Lam_out, int32_t* status,
@@ -601,6 +629,25 @@ int tgp_pathwise_eval_f64(int32_t kernel, const double* X, int32_t N, int32_t D,
   if (!coef) return -11;
   if (!F0) return -13;
   return launch_pathwise_eval(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, static_cast<hipStream_t>(stream));
+}
+
+int tgp_pathwise_grad_f64(int32_t kernel, const double* X, int32_t N, int32_t D, const double* Z, int32_t M, const double* raw_ls,
+                          const double* raw_os, const double* omega, int32_t R2, const double* coef, int32_t S, double* dF0,
+                          void* stream) {
+  if (!known_kernel(kernel) || pathwise_workspace_bytes(N, D, M, R2, S) == 0) {
+    set_error_text("tgp_pathwise_grad_f64: N = %d, D = %d, M = %d, R2 = %d, S = %d, kernel = %d outside N >= 1, 1 <= D <= 16, "
+                   "1 <= M <= %d, 1 <= R2 <= %d, 1 <= S <= %d, " TGP_KNOWN_KERNELS_TEXT, N, D, M, R2, S,
+                   kernel, TGP_BIG_MAX_M, TGP_PATHWISE_MAX_R2, TGP_PATHWISE_MAX_S);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!X) return -2;
+  if (!Z) return -5;
+  if (!raw_ls) return -7;
+  if (!raw_os) return -8;
+  if (!omega) return -9;
+  if (!coef) return -11;
+  if (!dF0) return -13;
+  return launch_pathwise_grad(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, static_cast<hipStream_t>(stream));
 }
 
 size_t tgp_qf_joint_sample_workspace_bytes(int32_t N, int32_t S) { return qf_joint_sample_workspace_bytes(N, S); }

@@ -272,6 +272,11 @@ size_t qf_input_grad_workspace_bytes(int N, int D, int M);
 int launch_qf_input_grad(const tgp_model& md, const double* X, double* dmu, double* dv, int32_t* status, void* workspace,
                          size_t workspace_bytes, hipStream_t st);
 
+// ... and the variance of the derivative process: dvar (N,D), one A_d = L^-1 J_d^T, C_d = W A_d and column sum per dimension
+size_t qf_input_grad_var_workspace_bytes(int N, int D, int M);
+int launch_qf_input_grad_var(const tgp_model& md, const double* X, double* dvar, int32_t* status, void* workspace,
+                             size_t workspace_bytes, hipStream_t st);
+
 // tgp_unwhiten.hip (unwhitened q(u): m_w = L^-1 m, Lam_w = L^-1 tril(L_q), and the adjoint down to Z and the kernel parameters)
 size_t unwhiten_workspace_bytes(int M, int D);
 int launch_unwhiten(int kernel, const double* Z, const double* raw_ls, const double* raw_os, int M, int D, double jitter,
@@ -318,5 +323,8 @@ int launch_pathwise_coeff(const tgp_model& md, const double* omega, int R2, cons
                           int32_t* status, void* workspace, size_t workspace_bytes, hipStream_t st);
 int launch_pathwise_eval(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls,
                          const double* raw_os, const double* omega, int R2, const double* coef, int S, double* F0, hipStream_t st);
+// ... and their input gradients: dF0 (D,S,N)
+int launch_pathwise_grad(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls,
+                         const double* raw_os, const double* omega, int R2, const double* coef, int S, double* dF0, hipStream_t st);
 
 }  // namespace tgp

@@ -1,4 +1,4 @@
-// tgp_pathwise.hip -- pathwise posterior function draws (tgp_pathwise_coeff_f64, tgp_pathwise_eval_f64): Wilson et al. 2020,
+// tgp_pathwise.hip -- pathwise posterior function draws (tgp_pathwise_coeff_f64, tgp_pathwise_eval_f64, tgp_pathwise_grad_f64): Wilson et al. 2020,
 // "Efficiently sampling functions from Gaussian process posteriors", for the whitened sparse GP.
 //
 // With l = softplus(raw_ls), s2 = softplus(raw_os), K = K_ZZ + jitter I = L L^T, Lam = tril(Lam), frequencies omega (R2, D) of the
@@ -17,6 +17,8 @@
 // buffer and its coefficient tile is loaded before the generation, so no global latency sits in front of the sincos chain.
 // A value of F0 depends on its data row and on coef only: the contraction order is fixed and no lane's result depends on
 // another data row, so X evaluated at once or in pieces gives the same bits.
+// k_pw_grad (tgp_pathwise_grad_f64) is the same walk for d f0_s(x) / d x_d: the derivative of each feature in its place, one set
+// of accumulators per input dimension, the dimensions split over grid.y (see the kernel).
 //
 // Launch sequence of tgp_pathwise_coeff_f64 (one stream, no host sync; operands padded to multiples of 128 in the workspace):
 //   K, its factor and L^-1   launch_kzz_factor; status[0]
@@ -196,6 +198,194 @@ __global__ __launch_bounds__(256) void k_pw_eval(int kernel, const double* __res
   }
 }
 
+// Dimensions of a workgroup of k_pw_grad: one set of NTW accumulator tiles per dimension, 16 tiles (128 registers) at the most
+template <int NT, int DP, int RW>
+struct PwDg {
+  static constexpr int ntw = RW == 64 ? NT : (NT >= 4 ? NT / 4 : 1);
+  static constexpr int v = 16 / ntw < DP ? 16 / ntw : DP;
+};
+
+// dF0[(d S + s) ldf + n] = d f0_s(x_n) / d x_nd = sum_k dfeat_k(x_n) / dx_nd coef[k S + s]: k_pw_eval's walk over the rows of
+// coef with the derivative of each feature in its place.  With w_jd = omega[j,d] / l_d and q_d = (x_d - z_id) / l_d:
+//   d cos a_j / dx_d = -sin a_j w_jd     d sin a_j / dx_d = cos a_j w_jd     d k(x, z_i) / dx_d = -k_g(d2) q_d / l_d
+// A workgroup owns RW data rows, all S samples and the DG dimensions d0 .. d0 + DG - 1 of blockIdx.y (D x NT accumulator tiles
+// do not fit in registers: the dimensions are split over the grid).  Per step the base quantities -- sincos of the step's 8
+// frequencies, k_g of its 16 inducing points -- are generated once into registers; for each dimension of the group they are
+// scaled into one of two operand tiles (the other one is still being multiplied) and multiplied against the step's coefficient
+// tile, which is staged once.  One barrier per dimension and one at the end of the step.  (x - z) is formed directly from the
+// scaled rows.  Tilings, prefetch and roles are k_pw_eval's; every element goes through the same products in the same order
+// under both tilings and whatever the group: an element depends on its row of X, its d and coef only.
+template <int NT, int DP, int RW>
+__global__ __launch_bounds__(256) void k_pw_grad(int kernel, const double* __restrict__ X, int N, int D, const double* __restrict__ Z,
+                                                  int M, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                                  const double* __restrict__ omega, int R2, const double* __restrict__ coef, int S,
+                                                  double* __restrict__ dF0, size_t ldf) {
+  static_assert(RW == 64 || RW == 16, "row tile");
+  constexpr int LDC = PwLdc<NT>::v;
+  constexpr int LDN = RW == 64 ? TL_LDN : 16;
+  constexpr int NTW = PwDg<NT, DP, RW>::ntw;
+  constexpr int DG = PwDg<NT, DP, RW>::v;
+  __shared__ double Ft[2][TL_KC * LDN];  // [dimension parity]: the operand tile of one dimension
+  __shared__ double Ct[TL_KC * LDC];
+  __shared__ double xsT[DP * RW];
+  __shared__ double omS[2][8 * 16];
+  __shared__ double zS[2][16 * 16];
+  __shared__ double ils[TL_ILS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const size_t n0 = (size_t)blockIdx.x * RW;
+  const int d0 = blockIdx.y * DG, dn = D - d0 < DG ? D - d0 : DG;  // the group's dimensions d0 .. d0 + dn - 1
+  const int pk = tid >> 4, pd = tid & 15;
+  const int rt = RW == 64 ? 16 * w : 0, t0 = RW == 64 ? 0 : w, tstep = RW == 64 ? 1 : 4;
+  const bool mma = RW == 64 || NT >= 4 || w == 0;
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
+  __syncthreads();
+  for (int i = tid; i < DP * RW; i += 256) {
+    const int d = i / RW, c = i % RW;
+    const size_t n = n0 + c < (size_t)N ? n0 + c : (size_t)N - 1;  // clamped: rows past N are computed and never stored
+    xsT[i] = d < D ? X[n * D + d] * ils[d] : 0.0;
+  }
+  if (tid < 128) omS[0][tid] = pd < D ? omega[(size_t)(pk < R2 ? pk : R2 - 1) * D + pd] : 0.0;
+  zS[0][tid] = pd < D ? Z[(size_t)(pk < M ? pk : M - 1) * D + pd] * ils[pd] : 0.0;
+  __syncthreads();
+  const Cov cov = tile_cov(kernel, ils);
+  d4 acc[DG][NTW];
+#pragma unroll
+  for (int dd = 0; dd < DG; ++dd)
+#pragma unroll
+    for (int u = 0; u < NTW; ++u) acc[dd][u] = d4{0.0, 0.0, 0.0, 0.0};
+  constexpr int CW = 16 * NT, CPT = TL_KC * CW / 256;
+  double cv[CPT];
+
+  // ---- Fourier rows: tile rows 0..7 meet the cos coefficients (-sin a w_jd), rows 8..15 the sin coefficients (cos a w_jd)
+  {
+    constexpr int FU = RW == 64 ? 2 : 1;
+    const int gk = RW == 64 ? tid >> 5 : tid >> 4, gc = RW == 64 ? tid & 31 : tid & 15;
+    const bool gen = RW == 64 || tid < 128;
+    for (int j0 = 0, par = 0; j0 < R2; j0 += 8, par ^= 1) {
+      double pre = 0.0;
+      if (tid < 128 && pd < D) pre = omega[(size_t)(j0 + 8 + pk < R2 ? j0 + 8 + pk : R2 - 1) * D + pd];
+#pragma unroll
+      for (int u = 0; u < CPT; ++u) {
+        const int idx = tid + 256 * u, r = idx / CW, c = idx - r * CW;
+        const int j = j0 + (r & 7);
+        const size_t row = (size_t)(r < 8 ? 0 : R2) + j;
+        cv[u] = (j < R2 && c < S) ? coef[row * S + c] : 0.0;
+      }
+      double sn[FU] = {}, cs[FU] = {};
+      if (gen) {
+        double om[DP];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) om[d] = omS[par][gk * 16 + d];
+#pragma unroll
+        for (int u = 0; u < FU; ++u) {
+          const int c = gc + 32 * u;
+          double a = 0.0;
+#pragma unroll
+          for (int d = 0; d < DP; ++d) a += om[d] * xsT[d * RW + c];  // (dimensions past D add exact zeros)
+          sincos(a, &sn[u], &cs[u]);
+        }
+      }
+#pragma unroll
+      for (int dd = 0; dd < DG; ++dd) {
+        if (dd < dn) {  // (uniform over the workgroup)
+          double* F = Ft[dd & 1];
+          if (gen) {
+            const double wd = omS[par][gk * 16 + d0 + dd] * ils[d0 + dd];
+#pragma unroll
+            for (int u = 0; u < FU; ++u) {
+              const int c = gc + 32 * u;
+              F[gk * LDN + c] = -(sn[u] * wd);
+              F[(gk + 8) * LDN + c] = cs[u] * wd;
+            }
+          }
+          if (dd == 0) {
+            if (tid < 128) omS[par ^ 1][tid] = pre;  // (read by the next step, behind this step's barriers)
+#pragma unroll
+            for (int u = 0; u < CPT; ++u) {
+              const int idx = tid + 256 * u, r = idx / CW, c = idx - r * CW;
+              Ct[r * LDC + c] = cv[u];
+            }
+          }
+          __syncthreads();
+          if (mma) pw_mma<NTW, LDN, LDC>(F, Ct, rt, t0, tstep, lr, lq, acc[dd]);
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // ---- kernel columns: tile row gk = -k_g(d2) q_d / l_d of the step's inducing point gk
+  {
+    const int gk = tid >> 4, gc = tid & 15;
+    for (int i0 = 0, par = 0; i0 < M; i0 += TL_KC, par ^= 1) {
+      double pre = 0.0;
+      if (pd < D) pre = Z[(size_t)(i0 + TL_KC + pk < M ? i0 + TL_KC + pk : M - 1) * D + pd] * ils[pd];
+#pragma unroll
+      for (int u = 0; u < CPT; ++u) {
+        const int idx = tid + 256 * u, r = idx / CW, c = idx - r * CW;
+        cv[u] = (i0 + r < M && c < S) ? coef[((size_t)2 * R2 + i0 + r) * S + c] : 0.0;
+      }
+      double kg[RW / 16];
+      {
+        double z[DP];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) z[d] = zS[par][gk * 16 + d];
+#pragma unroll
+        for (int u = 0; u < RW / 16; ++u) {
+          const int c = gc + 16 * u;
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < DP; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
+            const double q = xsT[d * RW + c] - z[d];
+            d2 += q * q;
+          }
+          kg[u] = cov_gweight(cov, d2);
+        }
+      }
+#pragma unroll
+      for (int dd = 0; dd < DG; ++dd) {
+        if (dd < dn) {  // (uniform over the workgroup)
+          double* F = Ft[dd & 1];
+          const double zd = zS[par][gk * 16 + d0 + dd], il = ils[d0 + dd];
+#pragma unroll
+          for (int u = 0; u < RW / 16; ++u) {
+            const int c = gc + 16 * u;
+            const double q = xsT[(d0 + dd) * RW + c] - zd;
+            F[gk * LDN + c] = -((kg[u] * q) * il);
+          }
+          if (dd == 0) {
+            zS[par ^ 1][tid] = pre;  // (read by the next step, behind this step's barriers)
+#pragma unroll
+            for (int u = 0; u < CPT; ++u) {
+              const int idx = tid + 256 * u, r = idx / CW, c = idx - r * CW;
+              Ct[r * LDC + c] = cv[u];
+            }
+          }
+          __syncthreads();
+          if (mma) pw_mma<NTW, LDN, LDC>(F, Ct, rt, t0, tstep, lr, lq, acc[dd]);
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  const size_t n = n0 + rt + lr;
+  if (mma && n < (size_t)N) {
+#pragma unroll
+    for (int dd = 0; dd < DG; ++dd)
+      if (dd < dn) {
+        double* const P = dF0 + (size_t)(d0 + dd) * S * ldf;
+#pragma unroll
+        for (int u = 0; u < NTW; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int s = 16 * (t0 + tstep * u) + lq + 4 * r;
+            if (s < S) P[(size_t)s * ldf + n] = acc[dd][u][r];
+          }
+      }
+  }
+}
+
 // The padded operands of the M x M chain and the feature rows of coef.  Thread e serves element e of every image it is inside.
 __global__ __launch_bounds__(256) void k_pw_prep(const double* __restrict__ Lam, const double* __restrict__ Linv,
                                                   const double* __restrict__ eps, const double* __restrict__ W,
@@ -292,6 +482,27 @@ int run_eval(int kernel, const double* X, int N, int D, const double* Z, int M, 
   if (S <= 128) return run_eval_nt<8>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, ldf, st);
   return run_eval_nt<16>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, ldf, st);
 }
+
+// k_pw_grad under the same choices: the fewest sample tiles that hold S, the 16-row workgroups up to PW_SMALL_N rows; the
+// dimensions in groups of PwDg over grid.y
+template <int NT, int RW>
+int run_grad_rw(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls, const double* raw_os,
+                const double* omega, int R2, const double* coef, int S, double* dF0, size_t ldf, hipStream_t st) {
+  dispatch_dp(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value, DG = PwDg<NT, DP, RW>::v;
+    const dim3 grid((unsigned)(((size_t)N + RW - 1) / RW), (unsigned)((D + DG - 1) / DG)), block(256);
+    hipLaunchKernelGGL((k_pw_grad<NT, DP, RW>), grid, block, 0, st, kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0,
+                       ldf);
+  });
+  LAUNCH_CHECK();
+  return 0;
+}
+template <int NT>
+int run_grad_nt(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls, const double* raw_os,
+                const double* omega, int R2, const double* coef, int S, double* dF0, size_t ldf, hipStream_t st) {
+  if (N <= PW_SMALL_N) return run_grad_rw<NT, 16>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
+  return run_grad_rw<NT, 64>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
+}
 }  // namespace
 
 size_t pathwise_workspace_bytes(int N, int D, int M, int R2, int S) {
@@ -303,6 +514,16 @@ int launch_pathwise_eval(int kernel, const double* X, int N, int D, const double
                          const double* raw_os, const double* omega, int R2, const double* coef, int S, double* F0, hipStream_t st) {
   if (!pw_limits(N, D, M, R2, S)) return TGP_E_UNSUPPORTED;  // (tgp_pathwise_eval_f64 has named the limits)
   return run_eval(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, F0, (size_t)N, st);
+}
+
+int launch_pathwise_grad(int kernel, const double* X, int N, int D, const double* Z, int M, const double* raw_ls,
+                         const double* raw_os, const double* omega, int R2, const double* coef, int S, double* dF0, hipStream_t st) {
+  if (!pw_limits(N, D, M, R2, S)) return TGP_E_UNSUPPORTED;  // (tgp_pathwise_grad_f64 has named the limits)
+  const size_t ldf = (size_t)N;
+  if (S <= 16) return run_grad_nt<1>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
+  if (S <= 64) return run_grad_nt<4>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
+  if (S <= 128) return run_grad_nt<8>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
+  return run_grad_nt<16>(kernel, X, N, D, Z, M, raw_ls, raw_os, omega, R2, coef, S, dF0, ldf, st);
 }
 
 int launch_pathwise_coeff(const tgp_model& md, const double* omega, int R2, const double* W, const double* eps, int S, double* coef,

@@ -1,4 +1,5 @@
-// tgp_xgrad.hip -- input gradients of the q(f) marginals (tgp_qf_input_grad_f64): d mu_n / d x_nd and d v_n / d x_nd.
+// tgp_xgrad.hip -- input gradients of the q(f) marginals (tgp_qf_input_grad_f64): d mu_n / d x_nd and d v_n / d x_nd, and the
+// variance of the derivative process under q(f) (tgp_qf_input_grad_var_f64).
 //
 // With K_ZZ + jitter I = L L^T, A = L^-1 K(Z, X), W = tril(Lam) tril(Lam)^T - I, C = W A (the operands of tgp_cov.hip),
 // a = L^-T m and U = L^-T C (M x N):
@@ -17,6 +18,15 @@
 //     k_xgrad<DP>    the two Jacobians of the pass's rows
 // Every reduction has a fixed order and nothing is accumulated with atomics: two runs on the same input are bit-identical, and
 // a row's result does not depend on N or on the pass it falls in (the GEMMs contract over m in an order fixed by M alone).
+//
+// The variance of the derivative process (tgp_qf_input_grad_var_f64), the error bar of dmu: with the symmetric B = L^-T W L^-1 the
+// posterior covariance is Sigma(x, x') = k(x, x') + k(x, Z) B k(Z, x'), and its mixed derivative in x_d, x'_d at x' = x is
+//   dvar[n,d] = k_g(0) / l_d^2 + sum_{m,m'} J[n,m,d] B[m,m'] J[n,m',d]
+// Launch sequence: the same prologue and k_cov_prep, then per pass and per input dimension d
+//   k_xgrad_va       A_d = L^-1 J_d^T (M x rows), the tiles of J_d generated on chip
+//   C_d = W A_d      launch_gemm_plain
+//   k_xgrad_vcol     dvar[n,d] = k_g(0) / l_d^2 + sum_m A_d[m,n] C_d[m,n], m ascending
+// with the same guarantees: fixed orders, no atomics, a row's result independent of N and of its pass.
 #include "tgp_dev.hpp"
 #include "tgp_launch.hpp"
 #include "tgp_tile.hpp"
@@ -119,6 +129,94 @@ __global__ __launch_bounds__(256) void k_xgrad(int kernel, const double* __restr
   }
 }
 
+// A_d = L^-1 J_d^T for one input dimension d (M x rows), J_d[n,m] = dk(x_n, z_m) / dx_nd = -k_g(d2_nm) (x_nd - z_md) / l_d^2:
+// k_cov_a's walk (tgp_cov.hip: 64 columns per workgroup, groups of 64 rows of A, steps of 16 contraction indices, the tile of
+// L^-1 staged with 16-byte loads, the contraction cut at the group's last row) with the 16 x 64 tile of J_d^T generated in LDS
+// in the place of K(Z, X*); J never reaches HBM.  (x - z) is formed directly from the scaled rows: a row of X that is a row of Z
+// bit for bit gives an exact zero there.  Rows m >= M of A_d come out as exact zeros, columns n >= rows are written as zeros.
+__global__ __launch_bounds__(256) void k_xgrad_va(int kernel, const double* __restrict__ X, int N, const double* __restrict__ Z,
+                                                   int M, int D, int dsel, const double* __restrict__ raw_ls,
+                                                   const double* __restrict__ raw_os, const double* __restrict__ LinvP, int MP,
+                                                   double* __restrict__ A, int NP) {
+  __shared__ __attribute__((aligned(16))) double Ls[TL_T * TL_LDK];
+  __shared__ double Jt[TL_KC * TL_LDN];
+  __shared__ double xsT[16 * TL_T];  // [d][column]: scaled rows of X
+  __shared__ double ils[TL_ILS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int n0 = blockIdx.x * TL_T;
+  tile_scales(kernel, D, raw_ls, raw_os, ils);
+  __syncthreads();
+  for (int i = tid; i < 16 * TL_T; i += 256) {
+    const int d = i >> 6, c = i & 63;
+    const int n = n0 + c < N ? n0 + c : N - 1;  // clamped: columns past N are computed and never stored
+    xsT[i] = d < D ? X[(size_t)n * D + d] * ils[d] : 0.0;
+  }
+  __syncthreads();
+  const Cov cov = tile_cov(kernel, ils);
+  const double il = ils[dsel];
+  const int gk = tid >> 4, gc = tid & 15;  // generation role: contraction index gk of the step, columns gc + 16 u
+  const int M16 = (M + 15) / 16 * 16;
+  for (int mg = 0; mg < MP; mg += TL_T) {
+    d4 acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
+    const int kend = mg < M ? (mg + TL_T < M16 ? mg + TL_T : M16) : 0;
+    for (int k0 = 0; k0 < kend; k0 += TL_KC) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {  // 64 rows x 16 k of L^-1: 512 pairs
+        const int idx = tid + 256 * u, r = idx >> 3, c2 = (idx & 7) * 2;
+        *reinterpret_cast<double2*>(Ls + r * TL_LDK + c2) =
+            *reinterpret_cast<const double2*>(LinvP + (size_t)(mg + r) * MP + k0 + c2);
+      }
+      {
+        const int kz = k0 + gk < M ? k0 + gk : M - 1;  // clamped: its row of L^-1 is zero
+        double z[16];
+#pragma unroll
+        for (int d = 0; d < 16; ++d) z[d] = d < D ? Z[(size_t)kz * D + d] * ils[d] : 0.0;
+        const double zd = Z[(size_t)kz * D + dsel] * il;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int c = gc + 16 * u;
+          double d2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 16; ++d) {  // (dimensions past D hold zeros on both sides: they add exact zeros)
+            const double t = xsT[d * TL_T + c] - z[d];
+            d2 += t * t;
+          }
+          Jt[gk * TL_LDN + c] = -((cov_gweight(cov, d2) * (xsT[dsel * TL_T + c] - zd)) * il);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const double b = Jt[(kk * 4 + lq) * TL_LDN + 16 * w + lr];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] = TGP_MFMA(Ls[(16 * t + lr) * TL_LDK + kk * 4 + lq], b, acc[t]);
+      }
+      __syncthreads();
+    }
+    const int n = n0 + 16 * w + lr;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) A[(size_t)(mg + 16 * t + lq + 4 * r) * NP + n] = n < N ? acc[t][r] : 0.0;
+  }
+}
+
+// dvar[n,d] = k_g(0) / l_d^2 + sum_m A_d[m,n] C_d[m,n], C_d = W A_d: one thread per row n, m ascending (consecutive threads read
+// consecutive n: coalesced).  The value is stored as computed, never clamped.
+__global__ __launch_bounds__(64) void k_xgrad_vcol(int kernel, const double* __restrict__ raw_ls, const double* __restrict__ raw_os,
+                                                    const double* __restrict__ A, const double* __restrict__ C, int M, int NP,
+                                                    int rows, int D, int dsel, double* __restrict__ dvar) {
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= rows) return;
+  const double il = 1.0 / softplus_d(raw_ls[dsel]);
+  const Cov cov = make_cov(kernel, softplus_d(raw_os[0]), cov_alpha(kernel, raw_os));
+  double s = 0.0;
+  for (int m = 0; m < M; ++m) s += A[(size_t)m * NP + n] * C[(size_t)m * NP + n];
+  dvar[(size_t)n * D + dsel] = cov_gweight(cov, 0.0) * il * il + s;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------
 namespace {
 struct XgradPlan : Layout {
@@ -141,7 +239,59 @@ bool xgrad_plan(XgradPlan& p, int N, int D, int M) {
   p.C = p.take(pn);
   return true;
 }
+// the slope variance: the same sections without a, mu
+struct XgradVarPlan : Layout {
+  int MP, NP;  // NP: the padded rows of one pass
+  KzzSections kzz;
+  size_t LinvP, Lq, W, A, C;
+};
+bool xgrad_var_plan(XgradVarPlan& p, int N, int D, int M) {
+  if (N < 1 || !inducing_limits(M, D)) return false;
+  p.MP = (int)rup((size_t)M, 128);
+  p.NP = (int)rup((size_t)(N < TGP_XGRAD_PASS_ROWS ? N : TGP_XGRAD_PASS_ROWS), 128);
+  const size_t pp = (size_t)p.MP * p.MP, pn = (size_t)p.MP * p.NP;
+  p.kzz.take(p, M);
+  p.LinvP = p.take(pp);
+  p.Lq = p.take(pp);
+  p.W = p.take(pp);
+  p.A = p.take(pn);
+  p.C = p.take(pn);
+  return true;
+}
 }  // namespace
+
+size_t qf_input_grad_var_workspace_bytes(int N, int D, int M) {
+  XgradVarPlan p;
+  return xgrad_var_plan(p, N, D, M) ? p.bytes() : 0;
+}
+
+int launch_qf_input_grad_var(const tgp_model& md, const double* X, double* dvar, int32_t* status, void* workspace,
+                             size_t workspace_bytes, hipStream_t st) {
+  XgradVarPlan p;
+  if (!xgrad_var_plan(p, md.N, md.D, md.M)) return TGP_E_UNSUPPORTED;  // (tgp_qf_input_grad_var_f64 has named the limits)
+  double* ws;
+  if (int rc = open_workspace("tgp_qf_input_grad_var_f64", "tgp_qf_input_grad_var_workspace_bytes", workspace, workspace_bytes,
+                              p.total, &ws))
+    return rc;
+  const int N = md.N, D = md.D, M = md.M, MP = p.MP;
+  if (int rc = p.kzz.factor(md, ws, status, st)) return rc;
+  if (int rc = launch_cov_prep(md.Lam, ws + p.kzz.Linv, M, MP, ws + p.Lq, ws + p.W, ws + p.LinvP, st)) return rc;
+  for (int r0 = 0; r0 < N; r0 += TGP_XGRAD_PASS_ROWS) {
+    const int rows = N - r0 < TGP_XGRAD_PASS_ROWS ? N - r0 : TGP_XGRAD_PASS_ROWS;
+    const int NP = (int)rup((size_t)rows, 128);
+    const double* Xp = X + (size_t)r0 * D;
+    for (int d = 0; d < D; ++d) {
+      hipLaunchKernelGGL(k_xgrad_va, dim3((unsigned)(NP / TL_T)), dim3(256), 0, st, md.kernel, Xp, rows, md.Z, M, D, d, md.raw_ls,
+                         md.raw_os, ws + p.LinvP, MP, ws + p.A, NP);
+      LAUNCH_CHECK();
+      if (int rc = launch_gemm_plain(false, false, 0, MP, NP, MP, 1.0, ws + p.W, MP, ws + p.A, NP, 0.0, ws + p.C, NP, st)) return rc;
+      hipLaunchKernelGGL(k_xgrad_vcol, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, md.kernel, md.raw_ls, md.raw_os, ws + p.A,
+                         ws + p.C, M, NP, rows, D, d, dvar + (size_t)r0 * D);
+      LAUNCH_CHECK();
+    }
+  }
+  return 0;
+}
 
 size_t qf_input_grad_workspace_bytes(int N, int D, int M) {
   XgradPlan p;

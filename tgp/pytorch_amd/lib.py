@@ -134,6 +134,8 @@ _SIGS = {
     "tgp_qf_cov_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_qf_input_grad_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "tgp_qf_input_grad_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
+    "tgp_qf_input_grad_var_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "tgp_qf_input_grad_var_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_predict_moment_grads_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp]),
     "tgp_qf_joint_sample_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_qf_joint_sample_f64": (C.c_int, [_dp, _dp, C.c_int32, C.c_double, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
@@ -178,6 +180,8 @@ _SIGS = {
     "tgp_pathwise_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "tgp_pathwise_coeff_f64": (C.c_int, [C.POINTER(TgpModel), _dp, C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_pathwise_eval_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
+                                        C.c_int32, _dp, _dp]),
+    "tgp_pathwise_grad_f64": (C.c_int, [C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
                                         C.c_int32, _dp, _dp]),
     "tgp_mean_forward_f64": (C.c_int, [_dp, C.c_int32, C.c_int32, _dp, _dp, C.c_double, _dp, _dp, C.c_int32, C.c_int32, C.c_int32,
                                        _dp]),

@@ -76,6 +76,10 @@ inverse ARD length-scale.  synthetic_relevance has six inputs of which only the 
 
     python -m tgp.pytorch_amd.main --model SVGP --dataset synthetic_relevance --relevance \\
         --train_test_seed_split 1 --num_inducing 20 --epochs 300
+
+`--slope_significance` (same models) prints after everything else, per input, the share of test rows at which the posterior slope
+of the latent function is significant at 95 % -- |E d_d f| > 1.96 sd(d_d f) under q(f), model.posterior_derivative -- which tells
+a small relevance that is slope from one that is posterior noise.
 """
 import argparse
 
@@ -200,6 +204,10 @@ def main(argv=None):
                     help="also print, per input, the relevance on the test split (root-mean-square slope of the predictive mean in "
                          "that input, utils.input_relevance) beside the inverse ARD length-scale 1 / l_d (SVGP or TGP, --likelihood "
                          "gaussian)")
+    ap.add_argument("--slope_significance", action="store_true",
+                    help="also print, per input, the share of test rows at which the posterior slope of the latent function in that "
+                         "input is further than 1.96 posterior standard deviations from zero (utils.slope_significance, from the HIP "
+                         "derivative moments; SVGP or TGP, --likelihood gaussian): the error bar --relevance lacks")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -269,6 +277,10 @@ def main(argv=None):
         ap.error("--relevance: SVGP or TGP with --likelihood gaussian only (the input gradients of the predictive moments are built "
                  "for the Gaussian and flow regression likelihoods; an ID_TGP's per-row flow parameters depend on x through the "
                  "networks, a WGP warps the targets)")
+    if args.slope_significance and (args.likelihood != "gaussian" or args.model not in ("SVGP", "TGP")):
+        ap.error("--slope_significance: SVGP or TGP with --likelihood gaussian only (one latent GP whose slope has the sign of the "
+                 "prediction's: an ID_TGP's flow parameters depend on x through the networks, a WGP warps the targets, the other "
+                 "likelihoods' models carry several latent GPs or a link of their own)")
     if wgp and (bern or multi):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
@@ -517,6 +529,11 @@ def main(argv=None):
         res = trainer.compute_metrics()
         print("Dataset {}, num inducing points {}, BAYESIAN FLOW , Test Negative LOGL {:.3f}, Test RMSE {:.3f}".format(
             args.dataset, args.num_inducing, -res[6], res[7]))
+    if args.slope_significance:
+        sig = trainer.compute_slope_significance()
+        for d in range(sig.numel()):
+            print("Dataset {}, num inducing points {}, model {}, input {} slope significant (95%) on {:.4f} of the test rows".format(
+                args.dataset, args.num_inducing, args.model, d, sig[d].item()))
     return res
 
 

@@ -768,6 +768,28 @@ class sparse_MF_SP(nn.Module):
         self.train()
         return dmu, dv
 
+    def posterior_derivative(self, X):
+        """(mean, var), each (Dy, N, D): the moments under q(f) of the derivative process d f_c(x_n) / d x_nd.  `mean` is
+        posterior_input_gradients' dmu (the mean function's slope included); `var` is Var_q[d_d f_c(x_n)] = k_g(0) / l_d^2 +
+        J_d^T L^-T W L^-1 J_d, one tgp_qf_input_grad_var_f64 call per latent GP through the same parameters -- the unwhitened
+        q(u) through its transform, a multi-class model's C latents, a heteroscedastic one's (f, h).  var is stored as computed
+        (rounding can leave a tiny negative): clamp at 0 where a square root is taken.  Eval mode, no autograd, then train()."""
+        X2 = X[0] if X.dim() == 3 else X
+        mean = self.posterior_input_gradients(X2)[0]
+        self._eval_mode()
+        kern = self.covariance_function.hip_kernel
+        with torch.no_grad():
+            Xd = X2.detach().contiguous()
+            parts = []
+            for c in (range(self.out_dim) if self._is_composed else (None,)):
+                info = {}
+                Z, rl, ro, m, Lam, _ = self._gp_params(c, info=info)
+                parts.append(ops.qf_input_grad_var(Xd, *(t.detach() for t in (Z, rl, ro, m, Lam)), jitter=info["jitter"],
+                                                   kernel=kern))
+            var = torch.stack(parts)
+        self.train()
+        return mean, var
+
     def predictive_input_gradients(self, X, Y_std=None):
         """{"m1": (N, D), "m2": (N, D)}: the gradients in x_n of the predictive mean and variance predictive_distribution reports
         at the rows of X -- the chain rule of ops.predict_moment_grads (the partials of the moments in mu and v, through the

@@ -530,6 +530,27 @@ def qf_input_grad(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="
     return dmu, dv
 
 
+def qf_input_grad_var(X, Z, raw_ls, raw_os, m, Lam, jitter=0.0, check=True, kernel="scale_rbf", info=None, workspace_bytes=None):
+    """dvar (N, D): the variance of the derivative process under q(f), Var_q[d f(x_n) / d x_nd] = k_g(0) / l_d^2 +
+    J_d^T L^-T W L^-1 J_d at the rows of X (tgp_qf_input_grad_var_f64) -- the error bar of qf_input_grad's dmu.  Stored as
+    computed, never clamped: clamp at 0 where a square root is taken.  No autograd.  `check`, `info` and `workspace_bytes` as in
+    qf_input_grad."""
+    lib = L.load()
+    md, X, par, lvn = _qf_model(X, Z, raw_ls, raw_os, m, Lam, jitter, 1.0, kernel)
+    dev = X.device
+    N, D = X.shape
+    ws, nbytes = _scratch(lib.tgp_qf_input_grad_var_workspace_bytes(N, D, md.M), dev, workspace_bytes)
+    dvar = torch.empty(N, D, dtype=torch.float64, device=dev)
+    status = _status(dev)
+
+    def call(jit):
+        md.jitter = jit
+        L.check(lib.tgp_qf_input_grad_var_f64(md, L.ptr(X), L.ptr(dvar), L.ptr(status), L.ptr(ws), nbytes, L.stream_ptr()),
+                "tgp_qf_input_grad_var_f64")
+    _laddered(call, status, jitter, info=info, check=check)
+    return dvar
+
+
 def qf_joint_sample(mu, Sigma, eps, jitter=0.0, want_L=False, workspace_bytes=None):
     """Joint draws F0 (S, N) = mu + eps chol(Sigma + jitter I)^T (tgp_qf_joint_sample_f64); eps (S, N) standard normals.
     Returns (F0, L_Sigma or None, status): status[0] is the Cholesky's pivot (no ladder here: see qf_joint_sample_safe)."""
@@ -976,6 +997,38 @@ def pathwise_eval(X, Z, raw_ls, raw_os, omega, coef, kernel="scale_rbf", batch_r
         b = min(N, a + int(batch_rows))
         F0[:, a:b] = piece(X[a:b])
     return F0
+
+
+def pathwise_grad(X, Z, raw_ls, raw_os, omega, coef, kernel="scale_rbf", batch_rows=None):
+    """(S, N, D): the gradients d f0_s(x_n) / d x_nd of the draws of `coef` in the rows of X they are evaluated at
+    (tgp_pathwise_grad_f64) -- a permuted view of the library's (D, S, N).  An element depends on its row of X, its d and coef
+    only: `batch_rows` evaluates X in pieces of that many rows and returns the same bits.  No autograd."""
+    lib = L.load()
+    X, Z, raw_ls, raw_os = _c(X, "X"), _c(Z, "Z"), _c(raw_ls.reshape(-1), "raw_ls"), _os(raw_os.reshape(-1), kernel)
+    omega, coef = _c(omega, "omega"), _c(coef, "coef")
+    if X.dim() != 2 or Z.dim() != 2 or omega.dim() != 2 or coef.dim() != 2:
+        raise ValueError("pathwise_grad: X (N, D), Z (M, D), omega (R2, D), coef (2 R2 + M, S)")
+    (N, D), M, R2, S = X.shape, Z.shape[0], omega.shape[0], coef.shape[1]
+    if Z.shape[1] != D or omega.shape[1] != D or coef.shape[0] != 2 * R2 + M or raw_ls.numel() != D:
+        raise ValueError("pathwise_grad: X (N, D), Z (M, D), raw_ls (D), raw_os (1), omega (R2, D), coef (2 R2 + M, S)")
+    if batch_rows is not None and int(batch_rows) < 1:
+        raise ValueError("pathwise_grad: batch_rows >= 1")
+    kid = kernel_id(kernel)
+    dev = X.device
+
+    def piece(Xp):
+        n = Xp.shape[0]
+        G = torch.empty(max(D, 1), max(S, 1), max(n, 1), dtype=torch.float64, device=dev)
+        L.check(lib.tgp_pathwise_grad_f64(kid, L.ptr(Xp), n, D, L.ptr(Z), M, L.ptr(raw_ls), L.ptr(raw_os), L.ptr(omega), R2,
+                                          L.ptr(coef), S, L.ptr(G), L.stream_ptr()), "tgp_pathwise_grad_f64")
+        return G
+    if batch_rows is None or int(batch_rows) >= N:
+        return piece(X).permute(1, 2, 0)
+    G = torch.empty(D, S, N, dtype=torch.float64, device=dev)
+    for a in range(0, N, int(batch_rows)):
+        b = min(N, a + int(batch_rows))
+        G[:, :, a:b] = piece(X[a:b])
+    return G.permute(1, 2, 0)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -46,6 +46,7 @@ class PosteriorPaths:
 
     paths.f0(X)  (S, N): the latent draws, plus the mean function where the model has one
     paths(X)     (S, N): the same values through the flow, with the per-row parameters of an input-dependent flow
+    paths.grad_f0(X), paths.grad(X)  (S, N, D): their gradients in the rows of X (a flow with per-row networks: refused)
     `batch_rows` evaluates a large X in pieces of that many rows; the values are the same bits."""
 
     def __init__(self, Z, raw_ls, raw_os, omega, coef, kernel, mean_function=None, flow=None):
@@ -81,6 +82,51 @@ class PosteriorPaths:
         theta = torch.stack([p.detach().reshape(()) for p in theta_list]).to(f0.device) if theta_list else None
         rowp = nets_rowp(nets, X2) if nets else None
         return ops.flow_eval(f0, spec, theta, rowp, want=("G",))["G"]
+
+    def _grad_f0(self, X2):
+        g = ops.pathwise_grad(X2, self.Z, self.raw_ls, self.raw_os, self.omega, self.coef, kernel=self.kernel)
+        if self.mean_function is not None:      # the slope of m(x) = x a + b (identity: a = W)
+            g = g + self.mean_function._ab()[0].detach().reshape(1, 1, -1).to(g.device)
+        return g
+
+    def _grad_flowed(self, X2):
+        g = self._grad_f0(X2)
+        if self.flow is None:
+            return g
+        spec, theta_list, nets = compile_flow(self.flow)
+        if spec.nblk == 0:
+            return g
+        f0 = self._f0(X2)
+        theta = torch.stack([p.detach().reshape(()) for p in theta_list]).to(f0.device) if theta_list else None
+        dG = ops.flow_eval(f0, spec, theta, None, want=("dG",))["dG"]
+        return dG.unsqueeze(2) * g
+
+    def _grad_pieces(self, fn, X, batch_rows):
+        X2 = self._rows(X)
+        N = X2.shape[0]
+        with torch.no_grad():
+            if batch_rows is None or int(batch_rows) >= N:
+                return fn(X2)
+            step = int(batch_rows)
+            if step < 1:
+                raise ValueError("PosteriorPaths: batch_rows >= 1")
+            out = torch.empty(self.S, N, X2.shape[1], dtype=torch.float64, device=X2.device)
+            for a in range(0, N, step):
+                b = min(N, a + step)
+                out[:, a:b] = fn(X2[a:b])
+            return out
+
+    def grad_f0(self, X, batch_rows=None):
+        """(S, N, D): d f0_s(x_n) / d x_nd of the latent draws (ops.pathwise_grad), plus the mean function's slope."""
+        return self._grad_pieces(self._grad_f0, X, batch_rows)
+
+    def grad(self, X, batch_rows=None):
+        """(S, N, D): the gradient of paths(X) in the rows, G'(f0_s(x_n)) grad_f0.  NotImplementedError for a flow with
+        input-dependent parameters."""
+        if self.flow is not None and compile_flow(self.flow)[2]:
+            raise NotImplementedError("PosteriorPaths.grad: the flow has input-dependent parameters -- its per-row parameters "
+                                      "depend on x through the networks, and that path has no input gradient")
+        return self._grad_pieces(self._grad_flowed, X, batch_rows)
 
     def _pieces(self, fn, X, batch_rows):
         X2 = self._rows(X)

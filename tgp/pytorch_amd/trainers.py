@@ -503,6 +503,17 @@ class Trainer_SP_regression:
         return rel, ils
 
 
+    def compute_slope_significance(self, z=1.96):
+        """(D,): utils.slope_significance of the model over the rows of the test split -- the share of rows at which the
+        posterior slope in each input is further than z posterior standard deviations from zero."""
+        from .utils import slope_significance
+        assert self.is_test, "compute_slope_significance reads the test split"
+        self.refresh_qu()
+        self.model.set_is_training(False)
+        X = torch.cat([x for x, _ in self.test_loader]).to(cg.device)
+        return slope_significance(self.model, X, z=z).cpu()
+
+
 class Trainer_SP_classification(Trainer_SP_regression):
     """trainers_classification.py: the same training loop, metrics (logL, accuracy) per split.  Bernoulli models train on
     the eager path (ops.ElboFunction): the resident step engine has no Bernoulli likelihood (engine.engine_refusal).  Multi-class models

@@ -263,3 +263,24 @@ def input_relevance(model, X, batch_rows=65536):
         g = model.predictive_input_gradients(X2[r0:r0 + int(batch_rows)])["m1"]
         sq += (g * g).sum(0)
     return torch.sqrt(sq / X2.shape[0])
+
+
+def slope_significance(model, X, z=1.96, batch_rows=65536):
+    """(D,) share of the rows of X at which the slope of the latent function in input d is significant: |mean_d| > z
+    sqrt(max(var_d, 0)) with (mean, var) = model.posterior_derivative, evaluated in pieces of `batch_rows` rows.  G is
+    increasing, so the sign of the latent slope is the sign of the slope of G(f): a share near 1 says the input moves the
+    prediction almost everywhere, a share near 1 - the coverage of z says the slope input_relevance reports is posterior noise.
+    A model of several latent GPs is refused (a share per GP: call posterior_derivative)."""
+    X2 = X[0] if X.dim() == 3 else X
+    if X2.shape[0] < 1 or int(batch_rows) < 1:
+        raise ValueError("slope_significance: at least one row of X and batch_rows >= 1")
+    if not float(z) >= 0.0:
+        raise ValueError("slope_significance: z >= 0")
+    hits = torch.zeros(X2.shape[1], dtype=X2.dtype, device=X2.device)
+    for r0 in range(0, X2.shape[0], int(batch_rows)):
+        mean, var = model.posterior_derivative(X2[r0:r0 + int(batch_rows)])
+        if mean.shape[0] != 1:
+            raise NotImplementedError("slope_significance: one latent GP only (this model has %d: take the share per GP from "
+                                      "posterior_derivative)" % mean.shape[0])
+        hits += (mean[0].abs() > float(z) * torch.sqrt(var[0].clamp_min(0.0))).to(hits.dtype).sum(0)
+    return hits / X2.shape[0]
