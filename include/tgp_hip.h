@@ -968,6 +968,37 @@ int tgp_predict_crps_f64(const tgp_model* model, const double* mu, const double*
 int tgp_predict_moment_grads_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp,
                                  double* dm1 /* (2,N) */, double* dm2 /* (2,N) */, void* stream);
 
+/* Acquisition functions of Bayesian optimisation on tgp_predict_f64's predictive (TGP_LIK_GAUSS and TGP_LIK_FLOW; model fields
+ * as for tgp_predict_cdf_f64, standardised units) against the incumbent `best`: c = +1 (minimize == 0) or -1, sig =
+ * exp(log_var_noise[0] / 2), g_s = G(mu_n + sqrt(2 v_n) xs_s), z_s = c (g_s - best) / sig, h(z) = z Phi(z) + phi(z):
+ *   TGP_ACQ_EI      value[n] = sig sum_s wn_s h(z_s)                  = E[(c (y - best))_+], the expected improvement
+ *   TGP_ACQ_LOG_EI  value[n] = log sig + logsumexp_s(log wn_s + log h(z_s)), finite where EI underflows (weights of 0 do not enter)
+ *                   -- as long as one term is finite: where z_s^2 overflows at every node of positive weight (|z_s| > 1.3e154; mu and
+ *                   v are not checked) or every weight is 0, the value is -inf and the partials are NaN
+ *   TGP_ACQ_PI      value[n] = sum_s wn_s Phi(z_s)                    = P(c (y - best) > 0), the probability of improvement
+ * partials (optional, (2,N)): row 0 the partial of value in mu, row 1 in v, at fixed flow parameters (rowp: fixed per-row
+ * parameters), g'_s = G'(f_s): d EI / d mu = c sum wn_s Phi(z_s) g'_s, d PI / d mu = (c / sig) sum wn_s phi(z_s) g'_s, d logEI =
+ * d EI / EI formed under the running maximum of the log terms with Phi / h from the stable form of h; in v the same sums with
+ * g'_s xs_s / sqrt(2 v_n).  log h(z): as written for z > -1; -z^2 / 2 - log sqrt(2 pi) + log1p(z q), q = Phi / phi =
+ * sqrt(pi / 2) erfcx(-z / sqrt 2), for -30 < z <= -1; the six-term asymptotic series of 1 + z q in 1 / z^2 for z <= -30.
+ * grad_x (optional, (N,D)): grad_x[n,d] = partials[0][n] dmu_dx[n,d] + partials[1][n] dv_dx[n,d], the chain rule with
+ * tgp_qf_input_grad_f64's Jacobians dmu_dx, dv_dx (N,D), two products and a sum per element; partials may be NULL with it.
+ * TGP_LIK_GAUSS or an empty program: one Gaussian, sd = sqrt(max(v, 0) + sig^2), z = c (mu - best) / sd: EI = sd h(z) with
+ * partials (c Phi(z), phi(z) / (2 sd)), PI and log EI likewise.  A row with v <= 0 counts as v = 0: its v-partial is an exact zero.
+ * 16 lanes share a row, add their partial sums in a fixed lane order and join their maxima by exchange: no float atomics, same
+ * input, same bits, a row's outputs depend on that row's inputs only.  Limits: 1 <= S <= TGP_QUANTILE_MAX_S; every lik but
+ * TGP_LIK_GAUSS and TGP_LIK_FLOW, a kind that is none of the three and a `best` that is not finite are refused --
+ * TGP_E_UNSUPPORTED, tgp_last_error() starts with the entry and names lik = k, S = k, kind = k or best.  A null model, mu, v,
+ * value: -1, -2, -3, -8; rowp missing with RP > 0: -4; with grad_x, a null dmu_dx, dv_dx: -10, -11, and D < 1: -12.  Every
+ * refusal happens before any launch. */
+#define TGP_ACQ_EI 0
+#define TGP_ACQ_LOG_EI 1
+#define TGP_ACQ_PI 2
+int tgp_predict_acquisition_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, int32_t kind,
+                                double best, int32_t minimize, double* value /* (N) */, double* partials /* (2,N); optional */,
+                                const double* dmu_dx /* (N,D) */, const double* dv_dx /* (N,D) */, int32_t D,
+                                double* grad_x /* (N,D); optional */, void* stream);
+
 /* Inducing-point initialisation: the numerical kernels behind utils.KMEANS, which replaces
  * sklearn.cluster.KMeans(init='k-means++', n_init, random_state) of dsp/utils.py:143-159.  Random draws, the stopping
  * rule and the restarts stay on the host (tgp/pytorch_amd/utils.py); D <= 16.

@@ -2,6 +2,7 @@
 // Argument checking, plan/workspace bookkeeping and the launch sequence of one ELBO step:
 //   M <= 128 : k_prep_a -> row kernel (k_rows / k_rows4) -> k_reduce -> k_bwd   (4 launches, no host sync)
 //   M  > 128 : the chunked GEMM pipeline of tgp_big.hip (same entry points, chosen by M / kernel)
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1279,6 +1280,37 @@ int tgp_predict_moment_grads_f64(const tgp_model* model, const double* mu, const
   tgp_model md;
   if (int rc = flow_args(model, flowed, fp, md)) return rc;
   return launch_predict_moment_grads(md, fp, mu, v, rowp, dm1, dm2, static_cast<hipStream_t>(stream));
+}
+
+int tgp_predict_acquisition_f64(const tgp_model* model, const double* mu, const double* v, const double* rowp, int32_t kind,
+                                double best, int32_t minimize, double* value, double* partials, const double* dmu_dx,
+                                const double* dv_dx, int32_t D, double* grad_x, void* stream) {
+  if (model && model->lik != TGP_LIK_GAUSS && model->lik != TGP_LIK_FLOW) {
+    set_error_text("tgp_predict_acquisition_f64: no acquisition function for lik = %d (TGP_LIK_GAUSS and TGP_LIK_FLOW only: the "
+                   "improvement terms are those of a Gaussian around the flow)", model->lik);
+    return TGP_E_UNSUPPORTED;
+  }
+  bool flowed = false;
+  if (int rc = check_quantile_model(model, mu, v, rowp, "tgp_predict_acquisition_f64", &flowed)) return rc;
+  if (kind != TGP_ACQ_EI && kind != TGP_ACQ_LOG_EI && kind != TGP_ACQ_PI) {
+    set_error_text("tgp_predict_acquisition_f64: kind = %d is none of TGP_ACQ_EI, TGP_ACQ_LOG_EI, TGP_ACQ_PI", kind);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!std::isfinite(best)) {
+    set_error_text("tgp_predict_acquisition_f64: best = %g is not finite", best);
+    return TGP_E_UNSUPPORTED;
+  }
+  if (!value) return -8;
+  if (grad_x) {
+    if (!dmu_dx) return -10;
+    if (!dv_dx) return -11;
+    if (D < 1) return -12;
+  }
+  FlowProg fp;
+  tgp_model md;
+  if (int rc = flow_args(model, flowed, fp, md)) return rc;
+  return launch_predict_acquisition(md, fp, mu, v, rowp, kind, best, minimize ? -1.0 : 1.0, value, partials, dmu_dx, dv_dx, D,
+                                    grad_x, static_cast<hipStream_t>(stream));
 }
 
 int tgp_kmeans_assign_f64(const double* X, int32_t N, int32_t D, const double* C, int32_t K, int32_t* labels, double* mind2,

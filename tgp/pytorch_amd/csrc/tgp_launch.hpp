@@ -232,6 +232,11 @@ int launch_predict_crps(const tgp_model& md, const FlowProg& fp, const double* m
 // ... the partials of the predictive moments in mu and v on the same sweep: dm1, dm2 (2,N)
 int launch_predict_moment_grads(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                                 double* dm1, double* dm2, hipStream_t st);
+// ... EI / log EI / PI (kind: TGP_ACQ_*) against the incumbent `best`, c = +1 to maximise, -1 to minimise: value (N), partials
+// (2,N) in mu and v (optional), grad_x (N,D) = the chain rule with dmu_dx, dv_dx (optional)
+int launch_predict_acquisition(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                               int kind, double best, double c, double* value, double* partials, const double* dmu_dx,
+                               const double* dv_dx, int D, double* grad_x, hipStream_t st);
 // ... and the heteroscedastic predictive on the same node table: mu, v (2,N), moments and the S x S log density
 int launch_predict_hetero(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
                           const double* Y, double Y_std, double* m1, double* m2, double* logp, hipStream_t st);

@@ -7,6 +7,8 @@
 //   k_predict_hetero<X> the heteroscedastic predictive (tgp_predict_hetero_f64): moments and log density on the same node table
 //   k_pred_crps<X, W>   the CRPS int (F_n(t) - 1{t >= Y_n})^2 dt in closed form: one pass over the nodes, one over their pairs
 //   k_crps_gauss        ... of one Gaussian (TGP_LIK_GAUSS / the empty program)
+//   k_pred_acq<KIND, X> expected improvement, its logarithm and the probability of improvement against an incumbent, with their
+//                       partials in mu and v and (optionally) the chain rule with the Jacobians of q(f); k_acq_gauss: one Gaussian
 // QLPR = 16 lanes share a data row (4 rows per wave, one wave per workgroup): the lanes sweep the row's S nodes -- and the Q
 // starting points G(mu + zq sqrt v) -- through the flow once (flow_forward_n, 4 elements in flight per lane) into LDS, and
 // every evaluation of F afterwards reads those S numbers only: lane l adds the nodes l, l + 16, ... in that order, the 16
@@ -473,6 +475,203 @@ __global__ __launch_bounds__(256) void k_mgrad_gauss(int N, const double* __rest
   dm2[(size_t)N + n] = v[n] > 0.0 ? 1.0 : 0.0;
 }
 
+// Acquisition functions of the same predictive against an incumbent b (tgp_predict_acquisition_f64), c = +1 to maximise and
+// -1 to minimise, z_s = c (g_s - b) / sig, h(z) = z Phi(z) + phi(z) (h' = Phi):
+//   EI = sig sum_s wn_s h(z_s) = E[(c (y - b))_+],   PI = sum_s wn_s Phi(z_s),   logEI = log sig + logsumexp_s(log wn_s + log h(z_s)).
+// acq_h: h, log h and the ratios Phi / h, phi / h without the cancellation of z Phi + phi at negative z.  With
+// q(z) = Phi / phi = sqrt(pi / 2) erfcx(-z / sqrt 2), h = phi t, t = 1 + z q:
+//   z > -1          h = z Phi + phi as written (Phi through erfc)
+//   -30 < z <= -1   t = 1 + z q, log t = log1p(z q)
+//   z <= -30        t = u (1 - 3 u (1 - 5 u (1 - 7 u (1 - 9 u (1 - 11 u))))), u = 1 / z^2: the asymptotic series of 1 + z q, whose
+//                   direct form has lost eps z^2 of its value to the cancellation by then; the first term left out is 135135 u^7
+// log h = -z^2 / 2 - log sqrt(2 pi) + log t,  Phi / h = q / t,  phi / h = 1 / t on the lower two branches.
+#define Q_SQRT_PI_2 1.25331413731550025121
+#define Q_LOG_SQRT_2PI 0.91893853320467274178
+struct AcqH { double h, logh, Phi_h, phi_h; };
+__device__ __forceinline__ AcqH acq_h(double z) {
+  AcqH r;
+  if (z > -1.0) {
+    const double Phi = 0.5 * erfc(-z * Q_SQRT1_2), phi = Q_INV_SQRT_2PI * exp(-0.5 * z * z);
+    r.h = z * Phi + phi;
+    r.logh = log(r.h);
+    r.Phi_h = Phi / r.h;
+    r.phi_h = phi / r.h;
+    return r;
+  }
+  const double q = Q_SQRT_PI_2 * erfcx(-z * Q_SQRT1_2);
+  double t, logt;
+  if (z > -30.0) {
+    t = 1.0 + z * q;
+    logt = log1p(z * q);
+  } else {
+    const double u = 1.0 / (z * z);
+    t = u * (1.0 - 3.0 * u * (1.0 - 5.0 * u * (1.0 - 7.0 * u * (1.0 - 9.0 * u * (1.0 - 11.0 * u)))));
+    logt = log(t);
+  }
+  r.logh = -0.5 * z * z - Q_LOG_SQRT_2PI + logt;
+  r.h = Q_INV_SQRT_2PI * exp(-0.5 * z * z) * t;
+  r.Phi_h = q / t;
+  r.phi_h = 1.0 / t;
+  return r;
+}
+// Phi(z), as q_eval forms it (PI at b is k_pred_cdf's upper or lower tail at Y = b, term for term)
+__device__ __forceinline__ double acq_Phi(double z) {
+  const double small = 0.5 * erfc(fabs(z) * Q_SQRT1_2);
+  return z < 0.0 ? small : 1.0 - small;
+}
+
+// grad_x[n, :] = a_mu dmu_dx[n, :] + a_v dv_dx[n, :], the row's 16 lanes over d = l16, l16 + 16, ...: the chain rule of the two
+// partials with the Jacobians of q(f) (tgp_qf_input_grad_f64), two products and one sum per element as written
+__device__ __forceinline__ void acq_chain(double a_mu, double a_v, const double* __restrict__ dmu_dx,
+                                          const double* __restrict__ dv_dx, int D, size_t n, int l16, double* __restrict__ grad_x) {
+  for (int d = l16; d < D; d += QLPR) grad_x[n * D + d] = a_mu * dmu_dx[n * D + d] + a_v * dv_dx[n * D + d];
+}
+
+// The partials in mu and v at fixed flow parameters, with g'_s = G'(f_s) as in k_pred_mgrad:
+//   d EI / d mu = c sum wn_s Phi(z_s) g'_s,            d PI / d mu = (c / sig) sum wn_s phi(z_s) g'_s,
+//   d logEI / d mu = (c / sig) sum_s p_s (Phi / h)(z_s) g'_s,   p_s = wn_s h(z_s) / sum_t wn_t h(z_t)  (the softmax weights),
+// and in v the same sums with g'_s xs_s / sqrt(2 v).  The row's 16 lanes sweep its S nodes once with the derivative, lane l the
+// nodes l, l + 16, ... in that order, three partial sums in registers -- no node table.  logEI: each lane keeps its sums relative
+// to its running maximum of log wn_s + log h(z_s) (weights of 0 do not enter), the 16 lanes' sums are joined under the row's
+// maximum: value and partials stay finite where EI itself underflows to 0 (a row whose every term is -inf -- z^2 overflows at
+// every node, or every weight is 0 -- gives -inf and NaN partials).  row16_sum adds the 16 lanes in the fixed lane
+// order; no float atomics: same input, same bits, and a row's outputs depend on that row's inputs only.  A row with v <= 0
+// counts as v = 0: every node is mu, the v-partial is an exact zero.  grad_x (optional): acq_chain with the row's two partials.
+// dynamic LDS: tp, tg ((P + 2) / 2 * 2 each), then wn and xs (S rounded up to even each), then log wn (the same) for logEI
+template <int KIND, bool X>
+__global__ __launch_bounds__(64) void k_pred_acq(tgp_model md, FlowProg fp, const double* __restrict__ mu,
+                                                 const double* __restrict__ v, const double* __restrict__ rowp, double best,
+                                                 double c, double* __restrict__ value, double* __restrict__ partials,
+                                                 const double* __restrict__ dmu_dx, const double* __restrict__ dv_dx, int D,
+                                                 double* __restrict__ grad_x) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  double* tp = reinterpret_cast<double*>(smem_raw);
+  double* tg = tp + (md.P + 2) / 2 * 2;
+  double* wl = tg + (md.P + 2) / 2 * 2;
+  const int lane = threadIdx.x, l16 = lane & (QLPR - 1), r = lane / QLPR, S = md.S, S2 = (S + 1) / 2 * 2;
+  double* xl = wl + S2;
+  double* lw = xl + S2;
+  for (int s = lane; s < S; s += 64) {
+    const double w = md.wn[s];
+    wl[s] = w;
+    xl[s] = md.xs[s];
+    if (KIND == TGP_ACQ_LOG_EI) lw[s] = w > 0.0 ? log(w) : -INFINITY;
+  }
+  flow_params_lds<X>(md.theta, fp, tp, tg);   // (ends with a barrier: the tables are staged too)
+  FlowDev F{fp.blk, fp.nblk, tp, tg};
+  const int n = blockIdx.x * QROWS + r;
+  const bool valid = n < md.N;
+  const int nc = valid ? n : md.N - 1;
+  const double* rp = rowp ? rowp + (size_t)nc * md.RP : nullptr;
+  const double m_ = mu[nc], vr = v[nc], vn = vr > 0.0 ? vr : 0.0, sq2 = sqrt(2.0 * vn);
+  const double sig = exp(0.5 * md.log_var_noise[0]), cs = c / sig;
+  constexpr int NB = 4;
+  double sv = 0.0, sm = 0.0, sx = 0.0, mx = -INFINITY;   // value, mu- and v-sums (logEI: relative to the running maximum mx)
+  for (int e0 = 0; e0 < S; e0 += NB * QLPR) {
+    double f[NB], der[NB];
+    const double* rpn[NB];
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16, ec = e < S ? e : S - 1;
+      f[u] = m_ + sq2 * xl[ec];
+      rpn[u] = rp;
+    }
+    flow_forward_n<NB, true, X>(F, f, rpn, der);
+    TGP_EACH(u, NB) {
+      const int e = e0 + u * QLPR + l16, ec = e < S ? e : S - 1;
+      const double w = e < S ? wl[ec] : 0.0, z = c * ((f[u] - best) / sig);   // (-(b - g) / sig: k_pred_cdf's argument, negated exactly)
+      if (KIND == TGP_ACQ_LOG_EI) {
+        if (w > 0.0) {
+          const AcqH a = acq_h(z);
+          const double term = lw[ec] + a.logh, gd = a.Phi_h * der[u];
+          if (term > mx) {
+            const double k = exp(mx - term);   // (the first term: exp(-inf) = 0)
+            sv = sv * k + 1.0;
+            sm = sm * k + gd;
+            sx = sx * k + gd * xl[ec];
+            mx = term;
+          } else if (term > -INFINITY) {
+            const double k = exp(term - mx);
+            sv += k;
+            sm += k * gd;
+            sx += k * gd * xl[ec];
+          }
+        }
+      } else {
+        const double wd = w * (KIND == TGP_ACQ_EI ? acq_Phi(z) : Q_INV_SQRT_2PI * exp(-0.5 * z * z)) * der[u];
+        sv += w * (KIND == TGP_ACQ_EI ? acq_h(z).h : acq_Phi(z));
+        sm += wd;
+        sx += wd * xl[ec];
+      }
+    }
+  }
+  double val, a_mu, a_v;
+  const double inv = vr > 0.0 ? 1.0 / sq2 : 0.0;
+  if (KIND == TGP_ACQ_LOG_EI) {
+    double gmx = mx;
+#pragma unroll
+    for (int o = 1; o < QLPR; o <<= 1) gmx = fmax(gmx, __shfl_xor(gmx, o));
+    const double k = mx > -INFINITY ? exp(mx - gmx) : 0.0;
+    const double tot = row16_sum(sv * k), tm = row16_sum(sm * k), tx = row16_sum(sx * k);   // (every lane on)
+    val = log(sig) + gmx + log(tot);
+    a_mu = cs * (tm / tot);
+    a_v = vr > 0.0 ? cs * (tx / tot) * inv : 0.0;
+  } else {
+    const double tot = row16_sum(sv), tm = row16_sum(sm), tx = row16_sum(sx);
+    val = KIND == TGP_ACQ_EI ? sig * tot : tot;
+    a_mu = (KIND == TGP_ACQ_EI ? c : cs) * tm;
+    a_v = vr > 0.0 ? (KIND == TGP_ACQ_EI ? c : cs) * tx * inv : 0.0;
+  }
+  if (valid && l16 == 0) {
+    value[n] = val;
+    if (partials) {
+      partials[n] = a_mu;
+      partials[(size_t)md.N + n] = a_v;
+    }
+  }
+  if (valid && grad_x) acq_chain(a_mu, a_v, dmu_dx, dv_dx, D, (size_t)n, l16, grad_x);
+}
+
+// TGP_LIK_GAUSS / the empty program: one Gaussian, sd = sqrt(max(v, 0) + sig^2), z = c (mu - b) / sd:
+//   EI = sd h(z), (c Phi(z), phi(z) / (2 sd));   PI = Phi(z), (c phi(z) / sd, -z phi(z) / (2 sd^2));
+//   logEI = log sd + log h(z), (c (Phi / h)(z) / sd, (phi / h)(z) / (2 sd^2));   a row with v <= 0: the v-partial is an exact zero.
+// 16 lanes per row (each evaluates the closed form), so that acq_chain's stores are those of k_pred_acq.
+__global__ __launch_bounds__(256) void k_acq_gauss(int N, const double* __restrict__ mu, const double* __restrict__ v,
+                                                   const double* __restrict__ lvn, int kind, double best, double c,
+                                                   double* __restrict__ value, double* __restrict__ partials,
+                                                   const double* __restrict__ dmu_dx, const double* __restrict__ dv_dx, int D,
+                                                   double* __restrict__ grad_x) {
+  const int n = blockIdx.x * (256 / QLPR) + threadIdx.x / QLPR, l16 = threadIdx.x & (QLPR - 1);
+  if (n >= N) return;
+  const double vr = v[n], sd = sqrt(fmax(vr, 0.0) + exp(lvn[0])), z = c * (mu[n] - best) / sd;
+  const double phi = Q_INV_SQRT_2PI * exp(-0.5 * z * z);
+  double val, a_mu, a_v;
+  if (kind == TGP_ACQ_PI) {
+    val = acq_Phi(z);
+    a_mu = c * phi / sd;
+    a_v = -z * phi / (2.0 * sd * sd);
+  } else {
+    const AcqH a = acq_h(z);
+    if (kind == TGP_ACQ_EI) {
+      val = sd * a.h;
+      a_mu = c * acq_Phi(z);
+      a_v = phi / (2.0 * sd);
+    } else {
+      val = log(sd) + a.logh;
+      a_mu = c * a.Phi_h / sd;
+      a_v = a.phi_h / (2.0 * sd * sd);
+    }
+  }
+  if (!(vr > 0.0)) a_v = 0.0;
+  if (l16 == 0) {
+    value[n] = val;
+    if (partials) {
+      partials[n] = a_mu;
+      partials[(size_t)N + n] = a_v;
+    }
+  }
+  if (grad_x) acq_chain(a_mu, a_v, dmu_dx, dv_dx, D, (size_t)n, l16, grad_x);
+}
+
 // TGP_LIK_GAUSS / the empty program: y ~ N(mu, max(v, 0) + sig^2).  Y == nullptr: quantiles t (Q,N); else cdf / sf (N).
 __global__ __launch_bounds__(256) void k_quantile_gauss(int N, const double* __restrict__ mu, const double* __restrict__ v,
                                                         const double* __restrict__ lvn, const double* __restrict__ zq, int Q,
@@ -762,6 +961,29 @@ int launch_predict_moment_grads(const tgp_model& md, const FlowProg& fp, const d
   auto* const kern = ext ? k_pred_mgrad<true> : k_pred_mgrad<false>;
   if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[ext])) return rc;
   hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, dm1, dm2);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_predict_acquisition(const tgp_model& md, const FlowProg& fp, const double* mu, const double* v, const double* rowp,
+                               int kind, double best, double c, double* value, double* partials, const double* dmu_dx,
+                               const double* dv_dx, int D, double* grad_x, hipStream_t st) {
+  if (md.lik == TGP_LIK_GAUSS || fp.nblk == 0) {
+    constexpr int rows = 256 / QLPR;
+    hipLaunchKernelGGL(k_acq_gauss, dim3((md.N + rows - 1) / rows), dim3(256), 0, st, md.N, mu, v, md.log_var_noise, kind, best, c,
+                       value, partials, dmu_dx, dv_dx, D, grad_x);
+    LAUNCH_CHECK();
+    return 0;
+  }
+  const size_t lds = (2 * (size_t)((md.P + 2) / 2 * 2) + (kind == TGP_ACQ_LOG_EI ? 3 : 2) * (size_t)((md.S + 1) / 2 * 2)) * sizeof(double);
+  const bool ext = flow_prog_extended(fp.blk, fp.nblk);
+  static size_t cur[6] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
+  auto* const kern = kind == TGP_ACQ_EI       ? (ext ? k_pred_acq<TGP_ACQ_EI, true> : k_pred_acq<TGP_ACQ_EI, false>)
+                     : kind == TGP_ACQ_LOG_EI ? (ext ? k_pred_acq<TGP_ACQ_LOG_EI, true> : k_pred_acq<TGP_ACQ_LOG_EI, false>)
+                                              : (ext ? k_pred_acq<TGP_ACQ_PI, true> : k_pred_acq<TGP_ACQ_PI, false>);
+  if (int rc = ensure_lds(reinterpret_cast<const void*>(kern), lds, &cur[2 * kind + ext])) return rc;
+  hipLaunchKernelGGL(kern, dim3((md.N + QROWS - 1) / QROWS), dim3(64), lds, st, md, fp, mu, v, rowp, best, c, value, partials,
+                     dmu_dx, dv_dx, D, grad_x);
   LAUNCH_CHECK();
   return 0;
 }

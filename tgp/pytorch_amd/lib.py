@@ -39,6 +39,8 @@ GAMMA_PQ_MAXIT = 2048      # most terms of the incomplete gamma function's serie
 ORDINAL_MAX_K = 64         # the supported number of classes is 2 <= K <= ORDINAL_MAX_K (include/tgp_hip.h)
 SOFTMAX_MAX_C, SOFTMAX_MAX_S = 32, 256
 QUANTILE_MAX_S, QUANTILE_MAX_Q = 256, 32   # tgp_predict_quantile_f64 / tgp_predict_cdf_f64
+ACQ_EI, ACQ_LOG_EI, ACQ_PI = 0, 1, 2      # tgp_predict_acquisition_f64's kind (TGP_ACQ_*)
+ACQ_KINDS = {"ei": ACQ_EI, "log_ei": ACQ_LOG_EI, "pi": ACQ_PI}
 PATHWISE_MAX_R2, PATHWISE_MAX_S = 8192, 256  # tgp_pathwise_coeff_f64 / tgp_pathwise_eval_f64
 XGRAD_PASS_ROWS = 16384    # rows per pass of tgp_qf_input_grad_f64 (TGP_XGRAD_PASS_ROWS)
 BIG_MAX_M = 4096           # the most inducing points any entry serves (TGP_BIG_MAX_M)
@@ -137,6 +139,8 @@ _SIGS = {
     "tgp_qf_input_grad_var_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "tgp_qf_input_grad_var_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_predict_moment_grads_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "tgp_predict_acquisition_f64": (C.c_int, [C.POINTER(TgpModel), _dp, _dp, _dp, C.c_int32, C.c_double, C.c_int32, _dp, _dp, _dp,
+                                              _dp, C.c_int32, _dp, _dp]),
     "tgp_qf_joint_sample_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "tgp_qf_joint_sample_f64": (C.c_int, [_dp, _dp, C.c_int32, C.c_double, _dp, C.c_int32, _dp, _dp, _dp, _dp, C.c_size_t, _dp]),
     "tgp_mlp_backward_adam_f64": (C.c_int, [C.POINTER(TgpMlp), _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, C.POINTER(TgpAdamArgs),

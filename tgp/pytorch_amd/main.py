@@ -80,6 +80,11 @@ inverse ARD length-scale.  synthetic_relevance has six inputs of which only the 
 `--slope_significance` (same models) prints after everything else, per input, the share of test rows at which the posterior slope
 of the latent function is significant at 95 % -- |E d_d f| > 1.96 sd(d_d f) under q(f), model.posterior_derivative -- which tells
 a small relevance that is slope from one that is posterior noise.
+
+`--suggest K` (same models) prints after everything else the K best distinct candidates for the next evaluation when the target is
+to be maximised: points inside the bounding box of the (standardised) training inputs found by utils.suggest_candidates --
+projected Adam ascent of model.acquisition from 64 starts, all in one batch on the GPU -- against the best training target, with
+their log expected improvement (`--suggest_kind ei | pi | ucb` for another acquisition function).
 """
 import argparse
 
@@ -208,6 +213,13 @@ def main(argv=None):
                     help="also print, per input, the share of test rows at which the posterior slope of the latent function in that "
                          "input is further than 1.96 posterior standard deviations from zero (utils.slope_significance, from the HIP "
                          "derivative moments; SVGP or TGP, --likelihood gaussian): the error bar --relevance lacks")
+    ap.add_argument("--suggest", type=int, default=0, metavar="K",
+                    help="after everything else, print the K best distinct candidates for the next evaluation inside the bounding "
+                         "box of the training inputs (standardised): utils.suggest_candidates, projected Adam ascent of the "
+                         "acquisition from 64 starts against the best training target, maximising (SVGP or TGP, --likelihood gaussian)")
+    ap.add_argument("--suggest_kind", choices=["log_ei", "ei", "pi", "ucb"], default="log_ei",
+                    help="the acquisition function of --suggest: log expected improvement (default), expected improvement, "
+                         "probability of improvement, or the upper confidence bound m1 + 2 sqrt(m2)")
     args = ap.parse_args(argv)
     base = args.dataset.replace("synthetic_", "")
     bern = args.likelihood == "bernoulli"
@@ -281,6 +293,12 @@ def main(argv=None):
         ap.error("--slope_significance: SVGP or TGP with --likelihood gaussian only (one latent GP whose slope has the sign of the "
                  "prediction's: an ID_TGP's flow parameters depend on x through the networks, a WGP warps the targets, the other "
                  "likelihoods' models carry several latent GPs or a link of their own)")
+    if args.suggest < 0:
+        ap.error("--suggest: K >= 0")
+    if args.suggest and (args.likelihood != "gaussian" or args.model not in ("SVGP", "TGP")):
+        ap.error("--suggest: SVGP or TGP with --likelihood gaussian only (the acquisition functions are built for the Gaussian and "
+                 "flow regression likelihoods; an ID_TGP's per-row flow parameters depend on x through the networks, a WGP warps "
+                 "the targets)")
     if wgp and (bern or multi):
         ap.error("--model WGP is a regression model: --likelihood gaussian only")
     if wgp and args.flow_arch is None and ("TGP", base) not in HYPER:
@@ -534,6 +552,10 @@ def main(argv=None):
         for d in range(sig.numel()):
             print("Dataset {}, num inducing points {}, model {}, input {} slope significant (95%) on {:.4f} of the test rows".format(
                 args.dataset, args.num_inducing, args.model, d, sig[d].item()))
+    if args.suggest:
+        for i, (x, val) in enumerate(trainer.compute_suggestions(args.suggest, args.suggest_kind)):
+            print("Dataset {}, num inducing points {}, model {}, candidate {} {} {:.6g} at x = [{}]".format(
+                args.dataset, args.num_inducing, args.model, i, args.suggest_kind, val, ", ".join("%.6f" % t for t in x.tolist())))
     return res
 
 

@@ -820,6 +820,63 @@ class sparse_MF_SP(nn.Module):
         self.train()
         return out
 
+    ACQUISITION_KINDS = ("ei", "log_ei", "pi", "ucb")
+
+    def acquisition(self, X, kind="log_ei", best=None, maximize=True, beta=2.0, return_grad=False):
+        """An acquisition function of Bayesian optimisation at the rows of X (N, D), in the model's standardised units: (N,), or
+        ((N,), (N, D)) with return_grad, the second its gradient in x_n.  With c = +1 when `maximize`, else -1, and the incumbent
+        `best` (the best target seen so far, standardised; the model does not keep its training targets, so it must be given):
+          "ei"      the expected improvement E[(c (y - best))_+] under the predictive predictive_distribution reports
+          "log_ei"  its logarithm, finite (and with a useful gradient) where EI underflows
+          "pi"      the probability of improvement P(c (y - best) > 0)
+          "ucb"     m1 + c beta sqrt(m2), the confidence bound of the predictive moments (needs no `best`)
+        The first three are one tgp_predict_acquisition_f64 launch, the gradient formed in it from posterior_input_gradients'
+        Jacobians; "ucb" is composed from ops.predict and ops.predict_moment_grads.  The Gaussian and flow regression
+        likelihoods, one output; with return_grad neither input-dependent flows nor the fully Bayesian mode.  Eval mode, no
+        autograd, then train(), as every prediction."""
+        lik = self.likelihood
+        if kind not in self.ACQUISITION_KINDS:
+            raise ValueError("acquisition: kind must be one of %s, got %r" % (", ".join(map(repr, self.ACQUISITION_KINDS)), kind))
+        if best is None and kind != "ucb":
+            raise ValueError("acquisition: kind=%r needs best=, the incumbent target in standardised units (the model does "
+                             "not keep its training targets)" % kind)
+        if lik.lik_id is not None or lik.composed:
+            raise NotImplementedError("acquisition: the Gaussian and flow regression likelihoods only; the predictive of the %s "
+                                      "likelihood is not a Gaussian's around the flow, and tgp_predict_acquisition_f64 has no "
+                                      "improvement terms for it" % (lik.display or type(lik).__name__))
+        if self.out_dim != 1:
+            raise NotImplementedError("acquisition: one output only (the model has %d): an improvement is that of one target"
+                                      % self.out_dim)
+        if return_grad and self._input_dependent:
+            raise NotImplementedError("acquisition: the model has input-dependent flows -- their per-row parameters depend "
+                                      "on x through the networks, and that path has no input gradient (values: "
+                                      "return_grad=False)")
+        if return_grad and self.fully_bayesian:
+            raise NotImplementedError("acquisition: the fully Bayesian model is an MC-dropout mixture over parameter draws, "
+                                      "which has no input gradient here")
+        X2 = X[0] if X.dim() == 3 else X
+        c = 1.0 if maximize else -1.0
+        dmu = dv = None
+        if return_grad:
+            dmu, dv = self.posterior_input_gradients(X2)
+            dmu, dv = dmu[0].contiguous(), dv[0].contiguous()
+        mu, v, lvn, spec, theta, rowp = self._quantile_inputs(X2.detach(), "acquisition")
+        S = self.quad_points
+        with torch.no_grad():
+            if kind == "ucb":
+                m1, m2, _ = ops.predict(mu, v, lvn, spec, theta, S, rowp)
+                sd = torch.sqrt(m2)
+                out = m1 + (c * float(beta)) * sd
+                if return_grad:
+                    dm1, dm2 = ops.predict_moment_grads(mu, v, lvn, spec, theta, S, rowp)
+                    a = dm1 + (0.5 * c * float(beta)) * dm2 / sd.unsqueeze(0)
+                    out = (out, a[0].unsqueeze(1) * dmu + a[1].unsqueeze(1) * dv)
+            else:
+                out = ops.predict_acquisition(mu, v, lvn, kind, float(best), spec, theta, S, rowp, maximize=maximize,
+                                              jac=(dmu, dv) if return_grad else None)
+        self.train()
+        return out
+
     def predictive_cdf(self, X, Y):
         """The predictive CDF at the targets Y (N,1), standardised units: the PIT values of a calibration plot, shape (Dy, N).
         A warped model's is Phi((T(y) - mu) / sqrt(v + noise))."""

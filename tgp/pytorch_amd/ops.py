@@ -1866,6 +1866,40 @@ def predict_moment_grads(mu, v, lvn, flow=None, theta=None, S=None, rowp=None, l
     return dm1, dm2
 
 
+def predict_acquisition(mu, v, lvn, kind, best, flow=None, theta=None, S=None, rowp=None, maximize=True, want_partials=False,
+                        jac=None):
+    """An acquisition function of the predictive ops.predict integrates against the incumbent `best` (a float, standardised
+    units), per row (tgp_predict_acquisition_f64): kind "ei" the expected improvement E[(c (y - best))_+], "log_ei" its
+    logarithm (finite where EI underflows), "pi" the probability of improvement; c = +1 with `maximize`, else -1.  Returns
+    value (N,); with want_partials (value, partials), partials (2, N) = the partials of value in mu (row 0) and v (row 1) at
+    fixed flow parameters; with jac = (dmu_dx, dv_dx), each (N, D) -- ops.qf_input_grad's -- (value, grad_x), grad_x (N, D) =
+    partials[0][:, None] dmu_dx + partials[1][:, None] dv_dx formed in the same launch (with both: all three).  flow=None: the
+    Gaussian likelihood's closed form.  A row with v <= 0 has an exact zero in partials[1].  No autograd."""
+    lib = L.load()
+    if kind not in L.ACQ_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(repr(k) for k in L.ACQ_KINDS), kind))
+    mu, v, lvn = _c(mu.reshape(-1), "mu"), _c(v.reshape(-1), "v"), _c(lvn, "lvn")
+    theta, rowp = _c(theta, "theta"), _c(rowp, "rowp")
+    N = mu.numel()
+    md, keep = _quantile_model(mu, lvn, flow, theta, S)
+    value = torch.empty_like(mu)
+    partials = torch.empty(2, N, dtype=torch.float64, device=mu.device) if want_partials else None
+    dmu_dx = dv_dx = grad_x = None
+    D = 0
+    if jac is not None:
+        dmu_dx, dv_dx = (_c(t, "jac") for t in jac)
+        if dmu_dx.dim() != 2 or dmu_dx.shape[0] != N or dv_dx.shape != dmu_dx.shape:
+            raise ValueError("jac must be (dmu_dx, dv_dx), each of shape (%d, D), got %s and %s"
+                             % (N, tuple(dmu_dx.shape), tuple(dv_dx.shape)))
+        D = dmu_dx.shape[1]
+        grad_x = torch.empty_like(dmu_dx)
+    L.check(lib.tgp_predict_acquisition_f64(md, L.ptr(mu), L.ptr(v), L.ptr(rowp), L.ACQ_KINDS[kind], float(best),
+                                            0 if maximize else 1, L.ptr(value), L.ptr(partials), L.ptr(dmu_dx), L.ptr(dv_dx), D,
+                                            L.ptr(grad_x), L.stream_ptr()), "tgp_predict_acquisition_f64")
+    out = (value,) + ((partials,) if want_partials else ()) + ((grad_x,) if jac is not None else ())
+    return out[0] if len(out) == 1 else out
+
+
 def crps_from_samples(draws, y):
     """The CRPS of the empirical distribution of `draws` (S,N) at y (N,), per row: the sorted-sample form
     1/S sum_i |x_i - y| - 1/S^2 sum_i (2 i - S - 1) x_(i), i = 1..S over the sorted draws, which is exactly the double sum

@@ -8,6 +8,7 @@ specifications entries [lr, name_substring] or [lr, weight_decay, name_substring
 to keep the split resident in HBM (removes the reference's per-step H2D copy and per-row collation).
 `inference_in_cpu` is accepted for signature compatibility and ignored: metrics are computed on the GPU.
 """
+import math
 import time
 from collections import OrderedDict
 
@@ -512,6 +513,33 @@ class Trainer_SP_regression:
         self.model.set_is_training(False)
         X = torch.cat([x for x, _ in self.test_loader]).to(cg.device)
         return slope_significance(self.model, X, z=z).cpu()
+
+    def compute_suggestions(self, K, kind="log_ei", num_starts=64, steps=50, seed=0):
+        """[(x (D,), value)] of at most K entries, best first: the K best distinct candidates for the next evaluation, maximising,
+        inside the bounding box of the training inputs -- utils.suggest_candidates from `num_starts` seeded starts against the
+        best training target (standardised units, as the loaders hold them), the per-start finals ranked by their acquisition
+        value; two finals closer than 1e-6 of the box in every input count as one."""
+        from .utils import suggest_candidates
+        self.refresh_qu()
+        self.model.set_is_training(False)
+        X = torch.cat([x for x, _ in self.train_loader]).to(cg.device)
+        best = float(torch.cat([y for _, y in self.train_loader]).max())
+        bounds = torch.stack((X.min(0).values, X.max(0).values))
+        _, _, finals = suggest_candidates(self.model, bounds, kind=kind, best=best, maximize=True, num_starts=num_starts, steps=steps,
+                                          generator=torch.Generator().manual_seed(int(seed)))
+        Xf = finals["X"]
+        vals = self.model.acquisition(Xf, kind=kind, best=best, maximize=True).cpu()     # (kind="ei": finals hold its logarithm)
+        Xf = Xf.cpu()
+        tol = 1e-6 * (bounds[1] - bounds[0]).cpu()
+        out = []
+        for i in torch.argsort(vals, descending=True).tolist():
+            if not math.isfinite(float(vals[i])):
+                continue
+            if all(bool(((Xf[i] - x).abs() > tol).any()) for x, _ in out):
+                out.append((Xf[i], float(vals[i])))
+            if len(out) == int(K):
+                break
+        return out
 
 
 class Trainer_SP_classification(Trainer_SP_regression):

@@ -284,3 +284,59 @@ def slope_significance(model, X, z=1.96, batch_rows=65536):
                                       "posterior_derivative)" % mean.shape[0])
         hits += (mean[0].abs() > float(z) * torch.sqrt(var[0].clamp_min(0.0))).to(hits.dtype).sum(0)
     return hits / X2.shape[0]
+
+
+def suggest_candidates(model, bounds, kind="log_ei", best=None, maximize=True, num_starts=64, steps=50, lr=0.05, starts=None,
+                       generator=None, beta=2.0):
+    """Where to evaluate next: projected Adam ascent of model.acquisition(X, kind, best, maximize, beta, return_grad=True) inside
+    the box `bounds` (2, D) = (lower, upper), from `num_starts` uniform draws (`generator`: a CPU torch.Generator; the same seed
+    gives the same result) or from the rows of `starts` (S, D).  All starts move together, one (num_starts, D) batch and one
+    acquisition call per step -- on the GPU one tgp_qf_input_grad_f64 and one tgp_predict_acquisition_f64 launch -- and every
+    iterate is clamped to the box.  The step is lr (1 - t / steps) times the box width per coordinate (Adam's unit step, decaying
+    linearly to 0 so that the last iterates settle).
+    Returns (x, value, finals): the BEST ITERATE SEEN over all steps and all starts, the starting points included -- so the
+    result is never below the best start -- its acquisition value, and finals = {"X": (num_starts, D), "value": (num_starts,)},
+    the best iterate of each start and its value of the ascent variable.
+    kind="ei" ascends "log_ei" -- EI's own gradient vanishes (underflows with EI) far from the incumbent, exactly where a
+    start needs a direction, and the logarithm has the same maximisers -- and `value` is the EI at the winner.  kind="ucb" with
+    maximize=False descends m1 - beta sqrt(m2) (its negative is the ascent variable; `value` is the bound itself)."""
+    bounds = torch.as_tensor(bounds)
+    if bounds.dim() != 2 or bounds.shape[0] != 2 or not bool((bounds[1] >= bounds[0]).all()):
+        raise ValueError("suggest_candidates: bounds must be (2, D) with lower <= upper")
+    if int(steps) < 0 or int(num_starts) < 1:
+        raise ValueError("suggest_candidates: steps >= 0 and num_starts >= 1")
+    lo, hi = bounds[0], bounds[1]
+    width = hi - lo
+    if starts is None:
+        u = torch.rand(int(num_starts), bounds.shape[1], generator=generator, dtype=bounds.dtype)
+        x = lo + u.to(bounds.device) * width
+    else:
+        x = torch.as_tensor(starts, dtype=bounds.dtype, device=bounds.device).reshape(-1, bounds.shape[1])
+    x = torch.maximum(torch.minimum(x, hi), lo).contiguous()
+    ascent = "log_ei" if kind == "ei" else kind
+    sign = -1.0 if (kind == "ucb" and not maximize) else 1.0
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    m, s = torch.zeros_like(x), torch.zeros_like(x)
+    top_x = x.clone()
+    top = torch.full((x.shape[0],), float("-inf"), dtype=x.dtype, device=x.device)
+    steps = int(steps)
+    for t in range(steps + 1):
+        val, g = model.acquisition(x, kind=ascent, best=best, maximize=maximize, beta=beta, return_grad=True)
+        val, g = sign * val.reshape(-1), sign * g
+        better = val > top                                   # (a NaN is never better)
+        top = torch.where(better, val, top)
+        top_x = torch.where(better.unsqueeze(1), x, top_x)
+        if t == steps:
+            break
+        g = torch.nan_to_num(g, nan=0.0, posinf=0.0, neginf=0.0)
+        m = b1 * m + (1.0 - b1) * g
+        s = b2 * s + (1.0 - b2) * g * g
+        step = (m / (1.0 - b1 ** (t + 1))) / (torch.sqrt(s / (1.0 - b2 ** (t + 1))) + eps)
+        x = torch.maximum(torch.minimum(x + (lr * (1.0 - t / steps)) * width * step, hi), lo).contiguous()
+    i = int(torch.argmax(top))
+    x_best = top_x[i].clone()
+    if kind == "ei":
+        value = model.acquisition(x_best.unsqueeze(0), kind="ei", best=best, maximize=maximize, beta=beta).reshape(-1)[0]
+    else:
+        value = sign * top[i]
+    return x_best, value, {"X": top_x, "value": top}
